@@ -12,6 +12,11 @@ The timed window: `--preroll` untimed steps first (default 50, reported as confi
 the caller passes land in the collapsing phase SURVEY.md 8d prescribes (50 warm-up + 200 timed), not in the first steps from rest
 where the density loop runs its minimum of 2 iterations; the pre-roll itself is timed and reported as `early_phase`.
 
+A plain run sets up, pre-rolls, warms up, times the --steps steps and prints the line.  `--dump-outputs DIR` then writes what the last
+timed step computed (fluid pos / vel / rho, the step's scalars) as DIR/<name>.npy, so that two builds can be compared output for output.
+The extra objects below take runs of their own and are measured only with `--full` (each can still be left out with its --no-* option),
+all but config.slab_protocol_probe, which chooses how a sharded run's timed steps exchange halos and is part of every N > 1 run:
+
 Extra objects on the line:
   roofline      dominant kernel: algorithmic bytes per launch / its mean launch
                 duration, measured live with HIP events on the library's stream (a separate,
@@ -66,12 +71,16 @@ def parse():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default=None, help="scene name from cfd_taichi_amd.scenes (default dfsph_1m)")
-    ap.add_argument("--profile-steps", type=int, default=1, help="0 = skip the HIP-event profiled replay (roofline leg)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline / kernel_breakdown_us, relaxed, strong_scaling_base, cpu_baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy (at most 64 MB; a seeded sample above that)")
+    ap.add_argument("--profile-steps", type=int, default=1, help="with --full: 0 = skip the HIP-event profiled replay (roofline leg)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg")
     ap.add_argument("--preroll", type=int, default=int(os.environ.get("SPH_BENCH_PREROLL", "50")),
                     help="untimed steps before the warm-up (reported as config.preroll_steps and timed as early_phase)")
-    ap.add_argument("--no-scaling-base", action="store_true", help="N=1: skip the dfsph_10m one-GPU point")
-    ap.add_argument("--no-relaxed", action="store_true", help="N=1 dfsph: skip the tolerance-grade arithmetic leg (the `relaxed` object)")
+    ap.add_argument("--no-scaling-base", action="store_true", help="with --full, N=1: skip the dfsph_10m one-GPU point")
+    ap.add_argument("--no-relaxed", action="store_true", help="with --full, N=1 dfsph: skip the tolerance-grade arithmetic leg (the `relaxed` object)")
     ap.add_argument("--allow-overrides", action="store_true", default=os.environ.get("SPH_BENCH_ALLOW_OVERRIDES") == "1",
                     help="print a line although development overrides (SPH_DEV=1 + SPH_* knobs) are in force; they are named in config.overrides")
     ap.add_argument("--no-overlap-probe", action="store_true", help="N > 1, dfsph: keep the overlapped slab protocol without timing it against the in-order one")
@@ -302,6 +311,32 @@ def load_ceiling():
 # (146 TFLOP/s: the guide's 157.3 TFLOP/s FP32 vector peak), an instruction with an SGPR operand ~4, a transcendental 8.  roofline.valu
 # prices the dominant kernel's own instruction mix at those costs.
 FP32_VECTOR_PEAK_TFLOPS = 157.3
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000      # files included: NPY_HEADER_BYTES of header each
+NPY_HEADER_BYTES = 128
+DUMP_SAMPLE_SEED = 20240807
+
+
+def dump_outputs(directory, per_particle, small):
+    """--dump-outputs: `per_particle` {name: array with one row per fluid particle, original particle order} and `small` {name: scalar or
+    short array, always written whole} as DIR/<name>.npy, float32 as the library returns them (`small` as float64).  Above DUMP_LIMIT_BYTES in all, the same seeded sample of
+    particles is taken from every per-particle array and its particle ids are written as sample_index.npy (float64)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    n = len(next(iter(per_particle.values())))
+    row_bytes = sum(a.nbytes // max(n, 1) for a in per_particle.values())
+    fixed = sum(np.atleast_1d(np.asarray(v, dtype=np.float64)).nbytes for v in small.values()) + NPY_HEADER_BYTES * (len(per_particle) + len(small) + 1)
+    if n * row_bytes + fixed > DUMP_LIMIT_BYTES:
+        keep = (DUMP_LIMIT_BYTES - fixed) // (row_bytes + 8)          # (+ 8: the float64 sample index itself)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=keep, replace=False))
+        per_particle = {k: a[idx] for k, a in per_particle.items()}
+        np.save(os.path.join(directory, "sample_index.npy"), idx.astype(np.float64))
+    for k, a in per_particle.items():
+        assert a.dtype == np.float32, (k, a.dtype)
+        np.save(os.path.join(directory, k + ".npy"), np.ascontiguousarray(a))
+    for k, v in small.items():
+        np.save(os.path.join(directory, k + ".npy"), np.atleast_1d(np.asarray(v, dtype=np.float64)))
 
 
 def make_sim(nat, scenes, scene_name, world, rank, local_rank, transport_group, rebalance=0, discipline=None):
@@ -780,10 +815,37 @@ def main():
 
     overlap_probe = {}
     run = make_run(sim, solver_kind, rigid_active)
-    want_relaxed = rank == 0 and world == 1 and solver_kind in ("dfsph", "wcsph") and not has_rigid and not args.no_relaxed and headline_arith == "exact"
-    want_state = rank == 0 and world == 1 and not has_rigid and solver_kind in ("dfsph", "wcsph", "pbf") and (not args.no_cpu_baseline or want_relaxed)
+    want_cpu_baseline = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_relaxed = (args.full and rank == 0 and world == 1 and solver_kind in ("dfsph", "wcsph") and not has_rigid and not args.no_relaxed
+                    and headline_arith == "exact")
+    want_state = rank == 0 and world == 1 and not has_rigid and solver_kind in ("dfsph", "wcsph", "pbf") and (want_cpu_baseline or want_relaxed)
     elapsed, early, stats, state = timed_window(sim, run, want_state)
     final_exact = (sim.download(nat.F_POS), sim.download(nat.F_VEL)) if want_relaxed else None
+    if args.dump_outputs:
+        # what the last timed step left for a caller: the fluid state in original particle order, dt, the step's iteration counts, the body
+        fields = {"pos": nat.F_POS, "vel": nat.F_VEL, "rho": nat.F_RHO}
+        if world == 1:
+            per_particle = {k: sim.download(f) for k, f in fields.items()}
+        else:                  # every rank's owned particles, assembled on rank 0 over the gloo side group
+            import numpy as np
+            per_particle = {}
+            for k, f in fields.items():
+                ids, vals = sim.download_owned(f)
+                parts = [None] * world if rank == 0 else None
+                dist.gather_object((ids, vals), parts, dst=0, group=side)
+                if rank == 0:
+                    whole = np.empty((n_total,) + vals.shape[1:], dtype=np.float32)
+                    assert sum(len(pid) for pid, _ in parts) == n_total
+                    for pid, pv in parts:
+                        whole[pid] = pv
+                    per_particle[k] = whole
+        if rank == 0:
+            small = {"delta_time": sim.scalar(nat.S_DELTA_TIME)}
+            if stats:
+                small["iterations"] = stats[-1]           # (n_div, n_dens, n_div_evals) of dfsph; (0, pressure iterations, 0) of pcisph / iisph
+            if has_rigid:
+                small["rigid_pos"] = sim.download(nat.F_RIGID_POS, nat.SPECIES_RIGID)
+            dump_outputs(args.dump_outputs, per_particle, small)
 
     value = n_total * args.steps / elapsed / 1e6
     slab_info = sim.slab_info() if world > 1 else None
@@ -829,7 +891,7 @@ def main():
 
     # ---- roofline leg: HIP-event timing of every kernel on a fresh handle that replays the same steps; the events cover the
     # warm-up + timed steps (the pre-roll runs unprofiled), a rocprofv3 trace of this command additionally sees both pre-rolls ----
-    if args.profile_steps > 0:
+    if args.full and args.profile_steps > 0:
         sim.close()
         sim, slab = make_sim(nat, scenes, scene_name, world, rank, local_rank, group_for, args.rebalance, discipline)
         run = make_run(sim, solver_kind, rigid_active)
@@ -891,7 +953,7 @@ def main():
         out["config"]["rigid_active"] = rigid_active
     sim.close()
     # ---- N = 1, default workload: the one-GPU point of the strong-scaling series (the N > 1 workload on this GPU, same flags) ----
-    if world == 1 and args.workload is None and not args.no_scaling_base:
+    if args.full and world == 1 and args.workload is None and not args.no_scaling_base:
         base_name = "dfsph_10m"
         bsim, _ = make_sim(nat, scenes, base_name, 1, 0, local_rank, None)
         b_elapsed, b_early, b_stats, _ = timed_window(bsim, make_run(bsim, "dfsph", False))
@@ -902,7 +964,7 @@ def main():
         bsim.close()
     if want_relaxed:
         out["relaxed"] = relaxed_leg(nat, scenes, scene_name, local_rank, args, state, final_exact, stats, fence, solver_kind)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if want_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(scene_name, solver_kind, state, args.preroll + args.warmup + 1)
         out["vs_cpu_baseline"] = value / out["cpu_baseline"]["value"]
     if dist is not None:

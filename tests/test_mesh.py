@@ -101,16 +101,20 @@ def test_rigid_from_config_relative_asset_path(tmp_path):
     assert len(mesh.rigid_from_config(cfg)["points"]) == 11 * 7 * 13 - 9 * 5 * 11
 
 
-REF_OBJ = "/root/reference/obj"
+# the reference's own mesh assets (obj/ of the MIT-licensed reference), stored byte for byte, gzip-compressed, as test fixtures
+REF_OBJ = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "obj")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_OBJ), reason="the reference's mesh assets are only mounted in the build container")
 @pytest.mark.parametrize("name,nv,nf,scale", [("ball.STL", 2850, 5696, 1.0), ("spot.obj", 2930, 5856, 1.0), ("cube2.STL", 8, 12, 0.5)])
-def test_reference_assets_load_and_voxelise(name, nv, nf, scale):
+def test_reference_assets_load_and_voxelise(name, nv, nf, scale, tmp_path):
     """The bodies the reference ships next to cube1 (binary STL, Wavefront OBJ with quads/normals): loader and voxeliser on the real
-    files, read in place.  Filled voxel volume against the mesh volume (divergence theorem): the voxel layer reaches up to pitch/2
+    files, unpacked under their own names.  Filled voxel volume against the mesh volume (divergence theorem): the voxel layer reaches up to pitch/2
     outside the surface, so the ratio is above 1 and below (1 + pitch / size)^3-ish; the surface voxels are a subset of the filled set."""
-    v, f = mesh.load_mesh(os.path.join(REF_OBJ, name))
+    import gzip
+    path = tmp_path / name
+    with gzip.open(os.path.join(REF_OBJ, name + ".gz"), "rb") as src:
+        path.write_bytes(src.read())
+    v, f = mesh.load_mesh(str(path))
     assert v.shape == (nv, 3) and f.shape == (nf, 3) and f.min() == 0 and f.max() == nv - 1
     v = v * scale
     tri = v[f]

@@ -313,11 +313,11 @@ def test_bench_multi_rank_path_end_to_end(tmp_path, launcher):
     self-check (SPH_BENCH_VERIFY: the synchronous discipline's bytes against the faster ones; native RCCL cannot open two ranks on one
     GPU and must fall through without hanging).  One valid JSON line: strong scaling, the slab description, all particles owned once."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"]
+           "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2", SPH_BENCH_REHEARSAL="1", SPH_BENCH_VERIFY="1", SPH_BENCH_PREROLL="2")
     if not launcher:
         # the launcher-less form (VERDICT r2 next #2): `python bench.py --gpus 2 ...` starts torch.distributed.run itself, as a child process
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"]
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"]
         for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "SPH_BENCH_VERIFY"):
             env.pop(k, None)
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)

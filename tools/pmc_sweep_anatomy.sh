@@ -1,15 +1,16 @@
 #!/bin/bash
 export SPH_DEV=1 SPH_BENCH_ALLOW_OVERRIDES=1     # the SPH_* knobs below are development overrides (include/sph_mi355x.h: sph_overrides)
 # SQ / LDS counters of the sweeps, separate --pmc passes over a short run; prints per-kernel means (tools/pmc_sweep_report.py) into
-# gpurun_out/anat_report[_TAG].txt and removes the (large) rocpd databases.  (A pass with the TA_* counters hung rocprofv3 on this pool: left out.)
+# results/anat_report[_TAG].txt and removes the (large) rocpd databases.  (A pass with the TA_* counters hung rocprofv3: left out.)
 # Usage: [SPH_LIB=alt.so] [TAG=name] tools/pmc_sweep_anatomy.sh [bench args]       values are means per (launch, XCD x SE instance): x 32 = per launch
 cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
 ARGS=${@:---preroll 30 --steps 3 --warmup 1}
-OUT=$R/gpurun_out/anat_report${TAG:+_$TAG}.txt
+mkdir -p $R/results
+OUT=$R/results/anat_report${TAG:+_$TAG}.txt
 : > $OUT
 pass() { name=$1; shift
-  timeout -k 10 300 rocprofv3 --kernel-trace --pmc "$@" -d /tmp/anat_$name -o a -- python3 $R/bench.py $ARGS --profile-steps 0 --no-cpu-baseline --no-scaling-base > /dev/null 2> /tmp/anat_$name.err
+  timeout -k 10 300 rocprofv3 --kernel-trace --pmc "$@" -d /tmp/anat_$name -o a -- python3 $R/bench.py --full $ARGS --profile-steps 0 --no-cpu-baseline --no-scaling-base > /dev/null 2> /tmp/anat_$name.err
   rc=$?
   if [ $rc -ne 0 ]; then echo "pass $name failed rc=$rc" >> $OUT; tail -5 /tmp/anat_$name.err >> $OUT; return 0; fi
   python3 $R/tools/pmc_sweep_report.py $(find /tmp/anat_$name -name "*.db") >> $OUT 2>&1; rm -rf /tmp/anat_$name; }
