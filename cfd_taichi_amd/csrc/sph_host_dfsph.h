@@ -61,7 +61,7 @@ int stage_sort_and_lists(SphHandle *h)
         ProfScope ps(h, K_ORDER_GATHER);
         hipLaunchKernelGGL(k_order_gather, g, b, 0, s, c, h->cell_of, h->cell_start, h->slot_src, h->P[h->pcur], h->V[h->vcur],
                            carry ? h->warm[h->wcur] : (const float *)nullptr, h->id[h->icur], h->P[1 - h->pcur], h->V[1 - h->vcur],
-                           h->warm[1 - h->wcur], h->id[1 - h->icur], rigid_coupled(h) ? h->pos_orig : (float4 *)nullptr, gate, h->x0,
+                           h->warm[1 - h->wcur], h->id[1 - h->icur], rigid_binned(h) ? h->pos_orig : (float4 *)nullptr, gate, h->x0,
                            h->slab ? h->dead : (int *)nullptr);
         h->pcur ^= 1; h->vcur ^= 1; h->icur ^= 1;
         if (carry) h->wcur ^= 1;
@@ -108,7 +108,7 @@ int stage_sort_and_lists(SphHandle *h)
         if ((rc = slab_allreduce_stream(h, 4 * h->Nr, 0))) return rc;
         hipLaunchKernelGGL(k_spread_by_id, grid_for(h->Nr), b, 0, s, h->Nr, h->red_dev, h->pos_orig, (float *)nullptr);
     }
-    if (rigid_coupled(h) && (rc = stage_sort_rigid(h))) return rc;
+    if (rigid_binned(h) && (rc = stage_sort_rigid(h))) return rc;
     {
         ProfScope ps(h, K_BUILD_NL);
         // (the per-build maxima were zeroed by k_hash_count; `overflow` stays sticky until check_overflow reports it)
@@ -128,6 +128,10 @@ int stage_sort_and_lists(SphHandle *h)
         else SPH_BNL(false, false);
 #undef SPH_BNL
 #undef SPH_BNL_SPLIT
+    }
+    if (rigid_binned(h) && !rigid_coupled(h)) {      // one-way body: the quirk count beside the fluid-only lists (see k_quirk_count)
+        ProfScope ps(h, K_RIGID);
+        hipLaunchKernelGGL(k_quirk_count, g, b, 0, s, c, h->P[h->pcur], h->cnt, h->id[h->icur], rigid_view(h), h->ncount);
     }
     if (rx_split(h)) {       // tiles with a rigid sample in reach (32-bit lists) first: the exact RIGID sweeps take them, the relaxed sweeps the rest
         ProfScope ps(h, K_BUILD_NL);
@@ -339,9 +343,11 @@ void launch_div_residual(SphHandle *h, int gate, int phase = 0, SpecUndo un = Sp
                            h->wall_grad, h->nl, h->cnt, h->rho, h->aux, h->ds, h->drho, h->psum, h->pcnt, gate, h->stage_src, h->stage_cnt, h->krho, (const int *)nullptr, (const unsigned char *)nullptr, 1, tpr, un);
         if (!split) return;
     }
-    SPH_LAUNCH_RMX(k_residual, false, rigid_coupled(h), sweep_mode(h), relaxed_unstaged(h), c.n, sweep_lds(h, sizeof(float4) + sizeof(float2)), st, c,
+    // (the `< 20` gate reads get_neighbour_count, :258-261: a one-way body -- binned, not coupled -- takes the RIGID instantiation for its
+    // count, ncount from k_quirk_count; its lists hold no rigid entry, so the sums are the fluid-only ones)
+    SPH_LAUNCH_RMX(k_residual, false, rigid_binned(h), sweep_mode(h), relaxed_unstaged(h), c.n, sweep_lds(h, sizeof(float4) + sizeof(float2)), st, c,
                   h->P[h->pcur], h->V[h->vcur], h->WP, h->nl, h->nlb, h->cnt, h->rho, h->aux, h->ds, h->drho, h->P[1 - h->pcur], h->psum, h->pcnt,
-                  rigid_view_or_none(h), h->ncount, gate, h->stage_src, h->stage_cnt, h->krho, (const int *)nullptr, (const unsigned char *)nullptr, 1,
+                  rigid_binned(h) ? rigid_view(h) : RigidView(), h->ncount, gate, h->stage_src, h->stage_cnt, h->krho, (const int *)nullptr, (const unsigned char *)nullptr, 1,
                   (const float4 *)wall_cache(h), tp, un);
 }
 

@@ -332,7 +332,7 @@ int pcisph_precompute(SphHandle *h)
     if ((rc = stage_sort_and_lists(h))) return rc;
     if ((rc = read_scalars(h))) return rc;
     if ((rc = check_overflow(h))) return rc;
-    if (rigid_coupled(h))   // get_neighbour_count with its rigid-entry quirk (ParticleSystem.py:436-444)
+    if (rigid_binned(h))    // get_neighbour_count with its rigid-entry quirk (ParticleSystem.py:436-444), coupled or not
         hipLaunchKernelGGL(k_unsort_scalar_int, grid_for(N), dim3(kBlock), 0, h->stream, N, h->ncount, h->id[h->icur], h->staging);
     else
         hipLaunchKernelGGL(k_unsort_count, grid_for(N), dim3(kBlock), 0, h->stream, N, h->cnt, h->id[h->icur], h->staging);
@@ -365,7 +365,7 @@ int pcisph_precompute(SphHandle *h)
             bucket[(dx + 1) * 9 + (dy + 1) * 3 + (dz + 1)].push_back(j);
         }
         std::vector<int> rbucket[27];
-        if (rigid_coupled(h))
+        if (rigid_binned(h))        // (the body is in the grid whether or not the fluid couples to it: pre_compute has no fs_couple test)
             for (int j = 0; j < h->Nr; ++j) {
                 int cj[3];
                 cell(h->rigid_pos_host.data() + 3 * (size_t)j, cj);

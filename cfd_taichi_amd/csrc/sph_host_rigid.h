@@ -50,7 +50,12 @@ RigidView rigid_view(const SphHandle *h)
     return rv;
 }
 
-inline bool rigid_coupled(const SphHandle *h) { return h->rigid && h->rigid_active && h->cfg.fs_couple; }
+// binned: the samples are sorted into the grid every step (update_grid_rigid_particles runs for any active body, ParticleSystem.py:399-407)
+// and take part in get_neighbour_count's rigid-entry quirk (ncount: dfsph's `< 20` gate, pcisph's fullest neighbourhood).  coupled: the
+// body's terms also enter the sweeps and the fluid's force on it is accumulated (fs_couple, solver_base.py:32).  A body that is binned and
+// not coupled (one-way) keeps the fluid-only lists and sweeps and takes its count from k_quirk_count.
+inline bool rigid_binned(const SphHandle *h) { return h->rigid && h->rigid_active; }
+inline bool rigid_coupled(const SphHandle *h) { return rigid_binned(h) && h->cfg.fs_couple; }
 inline RigidView rigid_view_or_none(const SphHandle *h) { return rigid_coupled(h) ? rigid_view(h) : RigidView(); }
 
 // the tolerance-grade sweeps (sph_relaxed_kernels.h) run on this handle

@@ -376,12 +376,20 @@ int sph_create_rigid(const SphConfig *cfg, const SphRigid *rigid, SphHandle **ou
         return fail(nullptr, SPH_E_INVALID, "a rigid body on slab handles needs dfsph with two ghost columns (the body's fluid neighbours must be resident on the rank that owns its column)");
     if (rigid->n_particles <= 0 || !rigid->points) return fail(nullptr, SPH_E_INVALID, "rigid body has no sample points");
     if (cfg->solver == SPH_SOLVER_PBF) return fail(nullptr, SPH_E_INVALID, "pbf has no rigid coupling (pbf_solver.py has no material branches)");
+    // a one-way body (active, fs_couple 0: binned, not coupled -- sph_host_rigid.h) is followed on single-GPU handles with the exact arithmetic.
+    // The slab transport gathers the quirk's fluid positions for coupled bodies only, and the relaxed kernels count without the quirk: refused
+    const bool one_way = rigid->active && !cfg->fs_couple;
+    if (one_way && cfg->slab_count > 1)
+        return fail(nullptr, SPH_E_INVALID, "a one-way rigid body (active, fs_couple 0) is not supported on slab handles: use slab_count 1 or fs_couple 1");
     g_creating_with_rigid = true;
     int rc = sph_create(cfg, out);
     g_creating_with_rigid = false;
     if (rc) return rc;
     SphHandle *h = *out;
-    rc = build_rigid(h, rigid);
+    if (one_way && h->relaxed)
+        rc = fail(h, SPH_E_INVALID, "a one-way rigid body (active, fs_couple 0) needs the exact arithmetic (SPH_ARITH_EXACT): the relaxed kernels do not "
+                                    "take get_neighbour_count's rigid-entry quirk");
+    if (!rc) rc = build_rigid(h, rigid);
     if (!rc && h->cfg.solver == SPH_SOLVER_PCISPH) rc = pcisph_precompute(h);   // the solver is constructed after the ParticleSystem: the grid holds the body
     if (rc) {
         g_create_error = h->err;
@@ -560,7 +568,7 @@ int sph_download(SphHandle *h, int species, int field, float *host, size_t n_flo
         case SPH_F_RHO_ADV: hipLaunchKernelGGL(k_unsort_scalar, g, b, 0, s, h->N, h->rho_adv, id, h->staging); break;
         case SPH_F_RHO_DER: hipLaunchKernelGGL(k_unsort_scalar, g, b, 0, s, h->N, h->drho, id, h->staging); break;
         case SPH_F_NBR_COUNT:
-            if (rigid_coupled(h)) hipLaunchKernelGGL(k_unsort_scalar_int, g, b, 0, s, h->N, h->ncount, id, h->staging);
+            if (rigid_binned(h)) hipLaunchKernelGGL(k_unsort_scalar_int, g, b, 0, s, h->N, h->ncount, id, h->staging);
             else hipLaunchKernelGGL(k_unsort_count, g, b, 0, s, h->N, h->cnt, id, h->staging);
             break;
         default: return fail(h, SPH_E_INVALID, "field %d cannot be downloaded", field);

@@ -67,6 +67,42 @@ __global__ __launch_bounds__(kBlock) void k_build_rnl(Consts c, int nr, const fl
     if (w.k > c.kmax) atomicOr(&ds->overflow, 1);
 }
 
+// get_neighbour_count with its rigid-entry quirk (ParticleSystem.py:424-445) for a body that is binned but not coupled (active, fs_couple
+// false).  k_build_nl<true> counts the quirk while it writes rigid entries into the lists; a one-way handle must not have those entries
+// (the fluid ignores the body, and most of its sweeps are RIGID = false instantiations, which would read a tagged entry as a fluid index),
+// so its lists are built by k_build_nl<false> and the count is taken here: the particle's fluid entries (the fluid half of the quirk is the
+// plain count) plus, for every rigid sample binned in its 27 cells, the quirk's test against fluid_particles.pos[the sample's LOCAL index].
+// Same tests as k_build_nl<true>.
+__global__ __launch_bounds__(kBlock) void k_quirk_count(Consts c, const float4 *__restrict__ P, const int *__restrict__ cnt,
+                                                        const int *__restrict__ id, RigidView rv, int *__restrict__ ncount)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= c.n) return;
+    const float4 pi = P[i];
+    const int my_id = id[i];
+    int cx, cy, cz;
+    cell_id_of(c, pi.x, pi.y, pi.z, cx, cy, cz);
+    int nq = cnt[i] & 0xffff;
+    for (int dx = -1; dx <= 1; ++dx)
+        for (int dy = -1; dy <= 1; ++dy)
+            for (int dz = -1; dz <= 1; ++dz) {
+                const int x = cx + dx, y = cy + dy, z = cz + dz;
+                if (x >= c.gx || y >= c.gy || z >= c.gz) continue;
+                if (x < 0 || y < 0 || z < 0) continue;
+                const int slot = cell_slot_xyz(c, x, y, z, x + y * c.sy + z * c.sz);
+                if (slot < 0) continue;
+                for (int j = rv.rcell_start[slot]; j < rv.rcell_start[slot + 1]; ++j) {
+                    const int jl = rv.rid[j];
+                    if (jl == my_id || jl >= rv.n_fluid) continue;                 // :440 (the local index), and fluid_particles' bounds
+                    const float4 pq = rv.pos_orig[jl];
+                    float ex = pi.x - pq.x, ey = pi.y - pq.y, ez = pi.z - pq.z;
+                    float e2 = (ex * ex + ey * ey) + ez * ez;
+                    if (!(e2 > c.r2_cut)) ++nq;                                    // :442
+                }
+            }
+    ncount[i] = nq;
+}
+
 // rigid_particles[j].force += ret * particle_m (dfsph_solver.py:204-212), gathered per rigid particle over its fluid
 // neighbours in list (= cell-walk) order: no atomics, and the same serialisation as the oracle.
 __global__ __launch_bounds__(kBlock) void k_rigid_force(Consts c, int nr, const float4 *__restrict__ RP, const int *__restrict__ rid,
@@ -257,7 +293,9 @@ __global__ __launch_bounds__(kBlock) void k_rigid_translate(int n, float4 *__res
 }
 
 // max_rigid_vel = max_i ( |vel| + |omega x (x_i - c)| )         dfsph_solver.py:104-110: partial maxima per workgroup in part[], the
-// second launch (one workgroup, nparts > 0) takes their maximum into ds->rigid_vmax
+// second launch (one workgroup, nparts > 0) takes their maximum into ds->rigid_vmax.  An inactive body has a NaN centroid (zero volumes,
+// 0 / 0): every term is NaN and fmaxf drops it, as the oracle's `>` does, so the maximum stays 0 (test_rigid_modes_gpu.py).  What Taichi's
+// atomic_max does with a NaN in the reference itself is a question of Taichi's semantics, not pinned here.
 __global__ __launch_bounds__(kBlock) void k_rigid_vmax(int nr, const float4 *__restrict__ RPos, RigidBodyState st, float vel_norm,
                                                        DevScalars *__restrict__ ds, float *__restrict__ part, int nparts)
 {

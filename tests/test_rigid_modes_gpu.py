@@ -1,0 +1,98 @@
+"""GPU suite: the two rigid-body branches every other rigid suite leaves out -- one-way coupling (fs_couple false, active body) and an
+inactive body (active false, or no `active` key) -- with dfsph, wcsph, pcisph and iisph, against the oracle bit for bit (scenes:
+tests/rigid_modes.py; test_rigid_modes_cpu.py proves on the oracle alone that each placement exercises what is asserted here).
+
+A one-way body is binned into the grid although the fluid ignores it: dfsph's neighbour count (the `< 20` gate of the divergence
+residual) and pcisph's delta see its samples through get_neighbour_count's rigid-entry quirk, and the body falls and bounces under
+rigid_solver.step.  An inactive body is never binned and never stepped: its sample volumes are zero, so its centroid is 0 / 0 and its
+inverse inertia is not finite -- the same NaN on both sides."""
+import numpy as np
+import pytest
+
+from cfd_taichi_amd import _native as nat
+from oracle import oracle as orc
+from rigid_modes import MODES, SOLVERS, STEPS, oracle_step, rigid, scene
+from test_rigid_gpu import same
+
+pytestmark = pytest.mark.gpu
+
+
+def same_nan(a, b, what):
+    """same() for values that may hold NaN: the NaN masks agree and everything else is equal bit for bit"""
+    a, b = np.asarray(a, dtype=np.float32), np.asarray(b, dtype=np.float32)
+    assert np.array_equal(np.isnan(a), np.isnan(b)), "%s: NaN at different places: %r vs %r" % (what, a, b)
+    assert np.array_equal(a, b, equal_nan=True), "%s differs: %r vs %r" % (what, a, b)
+
+
+def check_rigid(sim, o, when, nan_aware):
+    a, b = sim.rigid_scalars(), o.rigid_scalars()
+    for k in ("centroid", "omega", "vel", "inertia_inv", "mass"):
+        if nan_aware:
+            same_nan(a[k], b[k], "%s %s" % (k, when))
+        else:
+            same(np.float32(a[k]), np.float32(b[k]), "%s %s" % (k, when))
+    same(sim.download(nat.F_RIGID_POS, nat.SPECIES_RIGID), o.get(orc.F_RIGID_POS), "rigid positions " + when)
+    same(sim.download(nat.F_RIGID_VERT, nat.SPECIES_RIGID), o.get(orc.F_RIGID_VERT), "mesh vertices " + when)
+    return a
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("solver", SOLVERS)
+def test_rigid_mode_steps(solver, mode):
+    cfg = scene(solver, mode)
+    rg = rigid(cfg)
+    sim = nat.Simulation(nat.config_from_dict(cfg), rigid=rg)
+    o = orc.Oracle(cfg, solver=solver, num_threads=8, rigid=rg)
+    active = mode == "oneway"                                   # ps.active_rigid[None] == 1 (ParticleSystem.py:63-64)
+    assert (sim.n_fluid, sim.n_wall, sim.n_rigid) == (o.N, o.Nb, o.Nr) and sim.n_rigid > 0
+    if solver == "pcisph":
+        assert np.float32(sim.scalar(nat.S_PCISPH_DELTA)) == np.float32(o.pcisph_delta), (sim.scalar(nat.S_PCISPH_DELTA), o.pcisph_delta)
+        assert (int(sim.scalar(nat.S_PCISPH_MAX_INDEX)), int(sim.scalar(nat.S_PCISPH_MAX_COUNT))) == o.pcisph_max_index
+    check_rigid(sim, o, "at creation", nan_aware=not active)
+    g_step = {"dfsph": sim.step_dfsph, "wcsph": sim.step_wcsph, "pcisph": sim.step_pcisph, "iisph": sim.step_iisph}[solver]
+    vy = []
+    for s in range(STEPS):
+        st = g_step(1)
+        so = oracle_step(o, solver)
+        assert np.float32(sim.scalar(nat.S_DELTA_TIME)) == np.float32(o.dt), (s, sim.scalar(nat.S_DELTA_TIME), o.dt)
+        if solver == "dfsph":
+            assert (st.n_div, st.n_dens, st.div_first_err, st.div_err, st.dens_err, st.dt) == (
+                so.n_div, so.n_dens, so.div_first_err, so.div_err, so.dens_err, so.dt), s
+            same(sim.download(nat.F_NBR_COUNT), o.get(orc.F_NBR_COUNT), "neighbour count (the rigid-entry quirk) of step %d" % s)
+        elif solver != "wcsph":
+            assert (st.n_dens, st.dens_err) == (so.n_dens, so.dens_err), (s, st.n_dens, so.n_dens, st.dens_err, so.dens_err)
+        if active:
+            if s % 10 == 0:
+                fg, fo = sim.download(nat.F_RIGID_FORCE, nat.SPECIES_RIGID), o.get(orc.F_RIGID_FORCE)
+                assert not fg.any() and not fo.any(), "step %d: a force on a body the fluid does not couple to" % s
+            sim.rigid_step()                                    # main.py:169-171: only an active body is stepped
+            o.rigid_step()
+            vy.append(check_rigid(sim, o, "after rigid step %d" % s, nan_aware=False)["vel"][1])
+    same(sim.download(nat.F_POS), o.get(orc.F_POS), "fluid positions")
+    same(sim.download(nat.F_VEL), o.get(orc.F_VEL), "fluid velocities")
+    same(sim.download(nat.F_RHO), o.get(orc.F_RHO), "rho")
+    if active:
+        assert vy[0] < 0, "the body did not fall"
+        if solver != "wcsph":       # (40 steps of 2.5e-4 end before the floor)
+            assert any(vy[s] > vy[s - 1] for s in range(1, STEPS)), "the body never reached the floor impulse (rigid_solver.py:56-64)"
+    else:
+        check_rigid(sim, o, "after %d steps of an inactive body" % STEPS, nan_aware=True)
+    sim.close(); o.close()
+
+
+def test_missing_active_key_is_inactive():
+    """The mirror API: a `solid` block without `active` builds the body and leaves it inactive (ParticleSystem.py:63-64)."""
+    from cfd_taichi_amd import ParticleSystem
+    ps = ParticleSystem(scene("dfsph", "no_active_key"))
+    assert ps.exist_rigid[None] == 1 and ps.active_rigid[None] == 0 and ps.rigid_particles_num > 0
+
+
+@pytest.mark.parametrize("solver", ["dfsph", "pcisph"])
+def test_one_way_body_with_relaxed_arithmetic_is_refused(solver):
+    """The relaxed kernels count neighbours without the rigid-entry quirk: a one-way body under SPH_ARITH_RELAXED is refused, not run
+    differently from the oracle (an inactive body, which is not binned, is still built)."""
+    cfg = scene(solver, "oneway")
+    with pytest.raises(nat.SphError, match="exact arithmetic"):
+        nat.Simulation(nat.config_from_dict(cfg, arith=nat.ARITH_RELAXED), rigid=rigid(cfg))
+    cfg = scene(solver, "inactive")
+    nat.Simulation(nat.config_from_dict(cfg, arith=nat.ARITH_RELAXED), rigid=rigid(cfg)).close()
