@@ -135,8 +135,10 @@ int step_pcisph_once(SphHandle *h, SphStepStats *st)
     if ((rc = ghosts_xyz(PP))) return rc;
     // tiles without pressure skip update_press_force (k_pci_press): single-GPU staged handles without rigid entries
     int *zero_press = (h->pci_zero_press && h->staged && !h->slab && !rg) ? h->pci_zero_press : nullptr;
-    if (zero_press)       // after k_pci_ext: press_force = 0 and pos_predict = the zero-pressure prediction everywhere
-        HIP_TRY(h, hipMemsetAsync(zero_press, 1, sizeof(int) * (size_t)h->nblocks, s));
+    if (zero_press)       // after k_pci_ext: press_force = +0 and pos_predict = the zero-pressure prediction everywhere.  With walls that is
+        // what k_pci_press would write (-0 + 0 * rho_0 * m = +0); with clamp walls `press_force = - press_force` (:119) of an empty sum is
+        // -0, so there every tile runs once per step, writes it, and only then starts to skip
+        HIP_TRY(h, hipMemsetAsync(zero_press, c.boundary_handle ? 1 : 0, sizeof(int) * (size_t)h->nblocks, s));
     auto predict_rho = [&](int k, int gate) {               // the k-th predict_rho + residual: reads press from PB[k&1]
         ProfScope ps(h, K_P_PREDICT_RHO);
         SPH_LAUNCH_RMX0(k_pci_predict_rho, rg, sweep_mode(h), relaxed_pressure(h), c.n, sweep_lds(h, sizeof(float4)), s, c, h->pci_delta, PP, h->WP, h->nl, h->nlb, h->cnt, h->ds, PB[k & 1],

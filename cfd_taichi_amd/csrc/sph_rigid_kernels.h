@@ -46,9 +46,19 @@ __global__ __launch_bounds__(kBlock) void k_build_rnl(Consts c, int nr, const fl
         for (int dy = -1; dy <= 1; ++dy)
             for (int dz = -1; dz <= 1; ++dz) {
                 const int x = cx + dx, y = cy + dy, z = cz + dz;
-                if (x >= c.gx || y >= c.gy || z >= c.gz) continue;
-                if (x < 0 || y < 0 || z < 0) continue;
-                const int slot = cell_slot_xyz(c, x, y, z, x + y * c.sy + z * c.sz);
+                int slot;
+                if (x >= c.gx || y >= c.gy || z >= c.gz || x < 0 || y < 0 || z < 0) {
+                    // The force is deposited from the FLUID particle's walk (centre = its own 3-D cell, ParticleSystem.py:450-457).  A fluid
+                    // particle that slipped through a wall still meets the samples next to it, but is listed under its wrapped 1-D index
+                    // (:391-396): look for it there.  (A slab handle bins such a particle nowhere, see cell_id_of.)
+                    if (c.strict_cells) continue;
+                    const int id = x + y * c.sy + z * c.sz;
+                    if (id < 0 || id >= c.C) continue;
+                    slot = cell_slot(c, id);
+                    if (slot >= c.S) continue;
+                } else {
+                    slot = cell_slot_xyz(c, x, y, z, x + y * c.sy + z * c.sz);
+                }
                 if (slot < 0) continue;
                 const int a = cell_start[slot], b = cell_start[slot + 1];
                 for (int j0 = a; j0 < b; j0 += 4) {
@@ -58,6 +68,8 @@ __global__ __launch_bounds__(kBlock) void k_build_rnl(Consts c, int nr, const fl
                     while (m) {
                         const int u = __ffs(m) - 1;
                         m &= m - 1;
+                        const float4 q = pb[u];                               // only a particle whose OWN cell this is walks past the sample
+                        if ((int)floorf(q.x / c.hcell) != x || (int)floorf(q.y / c.hcell) != y || (int)floorf(q.z / c.hcell) != z) continue;
                         w.push((uint32_t)(j0 + u));
                     }
                 }

@@ -808,11 +808,14 @@ static void rigid_accumulate_force_mode(Orc *o, int mode)
             for (int dy = -1; dy <= 1; ++dy)
                 for (int dz = -1; dz <= 1; ++dz) {
                     int cx = cc[0] + dx, cy = cc[1] + dy, cz = cc[2] + dz;
-                    if (!cell_valid(o, cx, cy, cz)) continue;
                     int c1 = cx * o->stride[0] + cy * o->stride[1] + cz * o->stride[2];
+                    /* the deposit is made from the FLUID particle's walk, whose centre is its own 3-D cell (ParticleSystem.py:450-457): a
+                     * particle that slipped through a wall meets the samples next to it, but is listed under its wrapped 1-D index (:391-396) */
+                    if (!cell_valid(o, cx, cy, cz) && (c1 < 0 || c1 >= o->C)) continue;
                     for (int e = o->cstart[c1]; e < o->cstart[c1 + 1]; ++e) {
                         int i = o->citems[e];
                         if (i >= o->N) continue;                       /* fluid particles exert the force */
+                        if (o->cell3[3 * i] != cx || o->cell3[3 * i + 1] != cy || o->cell3[3 * i + 2] != cz) continue;   /* its own cell */
                         real xij = o->pos[3 * i] - pr[0], yij = o->pos[3 * i + 1] - pr[1], zij = o->pos[3 * i + 2] - pr[2];
                         if (r_sqrt((xij * xij + yij * yij) + zij * zij) > o->h) continue;
                         real gw[3];

@@ -10,6 +10,8 @@ much less likely.  It does NOT pin the oracle to the reference: both restatement
 import numpy as np
 import pytest
 
+import coupled_scenes as cs
+import restatement_compare as rc
 from cfd_taichi_amd import scenes
 from oracle import oracle as orc
 from second_restatement import Scene, Solver
@@ -120,3 +122,92 @@ def test_jittered_state_five_steps(scene, steps):
             same(s.vel, o.get(orc.F_VEL), "vel, step %d" % (k + 1))
             same(s.pos, o.get(orc.F_POS), "pos, step %d" % (k + 1))
     o.close()
+
+
+# ---- PCISPH, IISPH and the rigid body: the oracle against the second restatement (tests/coupled_scenes.py has the scenes and the loop) ----
+
+
+def _past_minimum(solver, iters):
+    if solver == "dfsph":
+        return any(nd > 1 or ns > 2 for nd, ns in iters)
+    return any(n > 1 for n in iters)
+
+
+KINDS = ["wall", "clamp_rest", "clamp", "jitter"]
+
+
+def uncoupled_case(solver, kind):
+    """(config, steps, state): dfsph_tiny_wall_<solver> for 10 steps; its clamp twin from rest for 10 steps (free fall: the block starts
+    0.075 above the clamp plane); the clamp twin thrown at the floor and the x = 0 plane (cs.clamp_thrown) for cs.CLAMP_THROWN_STEPS; the
+    seeded ragged state of the wall scene for 5 steps"""
+    if kind in ("clamp", "clamp_rest"):
+        cfg = cs.clamp_twin(solver)
+        return (cfg, cs.CLAMP_THROWN_STEPS, cs.clamp_thrown(cfg)) if kind == "clamp" else (cfg, 10, None)
+    cfg = scenes.get("dfsph_tiny_wall_" + solver)
+    return (cfg, 5, cs.jitter(cfg)) if kind == "jitter" else (cfg, 10, None)
+
+
+def check_uncoupled(solver, kind, ev):
+    """each case exercised what it claims"""
+    print("%s %s: pressure iterations per step %s; particle coordinates on a clamp plane %d; press_force of -0: %d" % (
+        solver, kind, ev["iters"], ev["on_plane"], ev["minus_zero"]))
+    if kind == "clamp_rest":    # what it claims is free fall without walls: nothing touches a plane, no pressure builds up
+        assert ev["on_plane"] == 0 and all(n == 1 for n in ev["iters"])
+    else:
+        assert _past_minimum(solver, ev["iters"]), "the pressure loop never ran past its minimum"
+    if kind == "clamp":
+        assert ev["on_plane"] > 0, "no particle ever sat on a clamp plane: the clamp branch did nothing"
+    if solver == "pcisph" and kind in ("clamp", "clamp_rest"):
+        assert ev["minus_zero"] > 0, "`- press_force` of an empty sum (pcisph_solver.py:119) never occurred"
+
+
+@pytest.mark.parametrize("solver", ["pcisph", "iisph"])
+@pytest.mark.parametrize("kind", KINDS)
+def test_pcisph_iisph_steps(solver, kind):
+    """pcisph_solver.py:28-240 / iisph_solver.py:35-349 on the cases of uncoupled_case: pos, vel, rho, pressure, predicted position,
+    pressure force, d_ii, a_ii, sum d_ij, the PCISPH delta and fullest neighbourhood, iteration counts and residuals, every step"""
+    cfg, steps, state = uncoupled_case(solver, kind)
+    check_uncoupled(solver, kind, rc.compare_run(cfg, steps, [rc.OracleSide], state=state))
+
+
+@pytest.mark.parametrize("solver", ["dfsph", "pcisph", "iisph", "wcsph"])
+@pytest.mark.parametrize("tilted", [False, True], ids=["upright", "tilted"])
+def test_coupled_scene(solver, tilted):
+    """Two-way coupling: the rigid samples as a third species in every sum of the solver, the force each one deposits, and
+    rigid_solver.step after every fluid step (cs.STEPS steps; the upright body's first wall impulse lies inside the window)."""
+    cfg = cs.coupled(solver, tilted=tilted)
+    rg = cs.rigid(cfg)
+    ev = rc.compare_run(cfg, cs.TILTED_STEPS[solver] if tilted else cs.STEPS[solver], [rc.OracleSide], rg=rg)
+    b = ev["solver"].body
+    print("%s %s: iterations %s; impulse steps %s; largest per-sample force %.4g; vy %s" % (solver, "tilted" if tilted else "upright", ev["iters"],
+                                                                                           ev["hit_steps"], max(ev["force"]), ev["vy"][-3:]))
+    assert b.Nr == 168 and b.pos[:, 1].min() >= np.float32(0.05), "a sample starts below box_min + diameter"
+    assert max(ev["force"]) > 0, "the fluid never pushed the body"
+    if tilted and solver == "wcsph":    # a particle that slipped through a wall pushes the body from outside the grid (listed under a wrapped index)
+        assert ev["outside_deposits"] > 0, "no fluid particle outside the grid deposited a force"
+    if solver != "wcsph":
+        assert _past_minimum(solver, ev["iters"]), "the pressure loop never ran past its minimum"
+    if not tilted:
+        assert ev["hit_steps"], "no step took the wall-impulse branch (collision_point_cnt > 0)"
+
+
+@pytest.mark.parametrize("solver", ["dfsph", "pcisph"])
+def test_one_way_body(solver):
+    """fs_couple false, active body: binned (get_neighbour_count's rigid branch, quirk included), ignored by the sums, falling and bouncing"""
+    cfg = cs.coupled(solver, fs_couple=False)
+    ev = rc.compare_run(cfg, cs.ONEWAY_STEPS, [rc.OracleSide], rg=cs.rigid(cfg))
+    print("%s one-way: iterations %s; impulse steps %s; quirk count differs for %d particle-steps" % (solver, ev["iters"], ev["hit_steps"], ev["quirk"]))
+    assert max(ev["force"]) == 0, "a force on a body the fluid does not couple to"
+    assert ev["hit_steps"], "the body never reached the floor impulse"
+    assert ev["quirk"] > 0, "the quirk count never differed from the plain fluid count"   # (ncount itself is compared every step, both solvers)
+
+
+def test_inactive_body_equals_no_body():
+    """active false: never binned, never stepped -- the fluid of the run with the body equals the run without a solid block, on both readings"""
+    with_body, without = cs.coupled("pcisph", active=False), cs.coupled("pcisph", solid=False)
+    a = rc.compare_run(with_body, 5, [rc.OracleSide], rg=cs.rigid(with_body))["solver"]
+    b = rc.compare_run(without, 5, [rc.OracleSide])["solver"]
+    same(a.pos, b.pos, "positions with an inactive body and with none")
+    same(a.vel, b.vel, "velocities with an inactive body and with none")
+    assert (a.delta, a.max_index) == (b.delta, b.max_index)
+    assert not a.body.vol.any() and not a.body.force.any()
