@@ -64,7 +64,10 @@ class ParticleSystem:
         has_rigid = self._rigid_input is not None
         self.rigid_particles_num = self._sim.n_rigid if has_rigid else 0
         self.exist_rigid = ScalarField(lambda: 1 if has_rigid else 0)                               # :39-40
-        self.active_rigid = ScalarField(lambda: 1 if has_rigid and self._rigid_input["active"] else 0)   # :63-64
+        # :63-64, a runtime value (main.py:102, :170): read from the handle, written through sph_rigid_set_active; _rigid_input["active"] is
+        # only what the body was created with
+        self.active_rigid = ScalarField(lambda: int(self._sim.scalar(nat.S_RIGID_ACTIVE)) if has_rigid else 0,
+                                        lambda v: self._sim.rigid_set_active(int(v) != 0))
         if has_rigid:
             self.rigid_vertex_count = self._sim.n_vertices
             self.rigid_particles = ParticleFields(
@@ -113,6 +116,11 @@ class ParticleSystem:
 
     def update_grid(self):
         self._sim.build_neighbors()
+
+    def init_rigid_particles_data(self):                 # :249-295
+        """Sample volumes, masses, the centroid and the inertia tensor from the body's current sample positions, with the body binned or not as
+        `active_rigid[None]` says now -- the last call of the release sequence of main.py:101-106."""
+        self._sim.rigid_init_data()
 
     def get_neighbour_count(self):
         """All particles at once: (N,) counts of fluid-grid entries within h (ParticleSystem.py:424-445)."""

@@ -28,6 +28,7 @@ S_DELTA_TIME, S_SIMULATE_CNT, S_PARTICLE_M, S_SUPPORT_RADIUS, S_PS_DELTA_TIME, S
 S_PCISPH_DELTA, S_PCISPH_BETA, S_PCISPH_MAX_INDEX, S_PCISPH_MAX_COUNT = range(6, 10)
 S_ARITH_RELAXED = 30
 S_VERLET_BUILDS = 31
+S_RIGID_ACTIVE = 32
 # `solver.<attribute> = value` (include/sph_mi355x.h SPH_P_*): name of the reference's attribute -> id
 SOLVER_PARAMS = {"density_threshold": 64, "min_iteration_density": 65, "min_iteration_density_divergence": 66, "max_iteration_density_divergence": 67,
                  "density_divergence_threshold": 68, "warm_start": 69, "adaptive_dt": 70, "max_dt": 71, "min_dt": 72,
@@ -41,7 +42,7 @@ EXPORTS = [
     "sph_get_scalar", "sph_set_scalar", "sph_synchronize", "sph_overrides", "sph_profile_enable", "sph_profile_reset", "sph_profile_kernel_count",
     "sph_profile_kernel_name", "sph_profile_get", "sph_selftest_math", "sph_selftest_wave", "sph_tune_time",
     "sph_set_comm", "sph_rccl_unique_id", "sph_rccl_attach", "sph_rccl_selftest", "sph_get_stream", "sph_plan_slabs", "sph_replan_slabs", "sph_slab_set_overlap", "sph_slab_info", "sph_comm_stats", "sph_download_local", "sph_download_ids",
-    "sph_create_rigid", "sph_rigid_step",
+    "sph_create_rigid", "sph_rigid_step", "sph_rigid_set_active", "sph_rigid_init_data",
 ]
 
 
@@ -169,6 +170,9 @@ CORE_EXPORTS = [
     "sph_step_wcsph", "sph_step_dfsph", "sph_step_pcisph", "sph_step_iisph", "sph_step_pbf", "sph_rigid_step",
     "sph_build_neighbors", "sph_compute_density", "sph_compute_alpha", "sph_get_scalar", "sph_set_scalar", "sph_synchronize",
 ]
+# entry points added without a change of SPH_ABI_VERSION (no struct grew, no signature changed): bound where the library has them, and a call on a
+# library without them raises SphError(SPH_E_STATE)
+OPTIONAL_EXPORTS = ["sph_rigid_set_active", "sph_rigid_init_data"]
 
 
 def _bind_core(lib):
@@ -202,6 +206,10 @@ def _bind_core(lib):
         getattr(lib, name).argtypes = [vp]
     lib.sph_get_scalar.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_double)]
     lib.sph_set_scalar.argtypes = [vp, ci, ctypes.c_double]
+    if hasattr(lib, "sph_rigid_set_active"):
+        lib.sph_rigid_set_active.argtypes = [vp, ci]
+    if hasattr(lib, "sph_rigid_init_data"):
+        lib.sph_rigid_init_data.argtypes = [vp]
     return lib
 
 
@@ -439,6 +447,20 @@ class Simulation:
 
     def rigid_step(self):
         self._check(self._lib.sph_rigid_step(self._h))
+
+    def _optional(self, name):
+        fn = getattr(self._lib, name, None)
+        if fn is None:
+            raise SphError(SPH_E_STATE, "%s does not export %s" % (getattr(self._lib, "_name", "this library"), name))
+        return fn
+
+    def rigid_set_active(self, active):
+        """ps.active_rigid[None] = active: the flag alone; an active body is binned (and, with fs_couple, coupled) from the next grid build."""
+        self._check(self._optional("sph_rigid_set_active")(self._h, 1 if active else 0))
+
+    def rigid_init_data(self):
+        """ps.init_rigid_particles_data(): sample volumes, masses, centroid and inertia from the body's current sample positions."""
+        self._check(self._optional("sph_rigid_init_data")(self._h))
 
     def rigid_scalars(self):
         g = self.scalar

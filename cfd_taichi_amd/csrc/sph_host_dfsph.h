@@ -149,6 +149,7 @@ int stage_sort_and_lists(SphHandle *h)
     HIP_TRY(h, hipGetLastError());
     h->nl_valid = true;
     h->density_valid = false;
+    h->lists_predate_flag = false;
     return SPH_OK;
 }
 
@@ -515,9 +516,13 @@ int dfsph_ext_and_dt(SphHandle *h)
         SPH_LAUNCH_RMXQ0(k_dfsph_ext, rigid_coupled(h), sweep_mode(h), relaxed_unstaged(h), c.n, sweep_lds(h, sizeof(float4) + sizeof(uint32_t)), s, c, h->P[h->pcur], h->V[h->vcur], h->nl,
                        h->cnt, h->ds, h->VA[0], h->pmax, rigid_view_or_none(h), h->stage_src, h->stage_cnt, split ? TilePhase{h->tile_order, h->nblocks, 1} : TilePhase{nullptr, 0, 0});
         if (h->rigid) {   // max_rigid_vel, :104-110 (loops over the rigid particles whether or not the body is active)
+            // A body that is not binned stands still: it enters the CFL rule with velocity and omega zero.  For a body that was never active that
+            // is what it holds anyway; a FROZEN body keeps its velocity and omega for a later release (sph_rigid_set_active), and the reference would
+            // go on adding that stored speed to max_vel -- here the fluid next to a frozen body steps as without a body
+            const bool moving = rigid_binned(h);
             RigidBodyState st = rigid_state(h, nullptr, nullptr);
-            for (int a = 0; a < 3; ++a) st.omega[a] = h->r_omega[a];
-            const float vn = sqrtf((h->r_vel[0] * h->r_vel[0] + h->r_vel[1] * h->r_vel[1]) + h->r_vel[2] * h->r_vel[2]);
+            for (int a = 0; a < 3; ++a) st.omega[a] = moving ? h->r_omega[a] : 0.0f;
+            const float vn = moving ? sqrtf((h->r_vel[0] * h->r_vel[0] + h->r_vel[1] * h->r_vel[1]) + h->r_vel[2] * h->r_vel[2]) : 0.0f;
             hipLaunchKernelGGL(k_rigid_vmax, rigid_parts_grid(h), b, 0, s, h->Nr, h->RPos, st, vn, h->ds, h->rvmax_part, 0);
             hipLaunchKernelGGL(k_rigid_vmax, dim3(1), b, 0, s, h->Nr, h->RPos, st, vn, h->ds, h->rvmax_part, (int)rigid_parts_grid(h).x);
         }

@@ -56,6 +56,13 @@ RigidView rigid_view(const SphHandle *h)
 // not coupled (one-way) keeps the fluid-only lists and sweeps and takes its count from k_quirk_count.
 inline bool rigid_binned(const SphHandle *h) { return h->rigid && h->rigid_active; }
 inline bool rigid_coupled(const SphHandle *h) { return rigid_binned(h) && h->cfg.fs_couple; }
+// a body released (sph_rigid_set_active) whose volumes, masses, centroid and inertia still are those of an unbinned body: zeros, 0 / 0 and a
+// non-finite inverse inertia.  The reference would step on with NaN; here every sph_step_* and sph_rigid_step refuses
+inline int rigid_released_unprepared(SphHandle *h)
+{
+    if (rigid_binned(h) && !h->rigid_data_binned) return fail(h, SPH_E_STATE, "call sph_rigid_init_data after releasing the body");
+    return SPH_OK;
+}
 inline RigidView rigid_view_or_none(const SphHandle *h) { return rigid_coupled(h) ? rigid_view(h) : RigidView(); }
 
 // the tolerance-grade sweeps (sph_relaxed_kernels.h) run on this handle
@@ -74,32 +81,15 @@ inline bool relaxed_pressure(const SphHandle *h)
            (h->staged || !(!h->slab && h->opt_quad && h->c.n <= h->quad_below));
 }
 
-// init_rigid_particles_pos + init_rigid_particles_data (ParticleSystem.py:198-223, 249-295), once, on the host
-int build_rigid(SphHandle *h, const SphRigid *rg)
+// init_rigid_particles_data (ParticleSystem.py:249-291) on the host, from the sample positions `rpos` (3 floats each): sample volumes (summed over
+// the rigid cell list when the body is binned; an unbinned body has no neighbours, so its volumes are zero, its centroid 0 / 0 and its inverse inertia
+// not finite, as in the reference), masses, centroid, inertia tensor and its inverse.  build_rigid runs it on the placed samples, sph_rigid_init_data
+// on the current ones.  Nothing of the handle is written before every sample has been found inside the grid.
+int rigid_init_data(SphHandle *h, const std::vector<float> &rpos, bool binned)
 {
     const Consts &c = h->c;
-    h->Nr = rg->n_particles; h->Nv = rg->n_vertices;
-    h->rigid_active = rg->active ? 1 : 0;
-    h->rigid_rho = (float)rg->rho_0;
-    const int Nr = h->Nr, Nv = h->Nv;
-    const double pi = 3.141592653589793;
-    float att[3], m[9], off[3];
-    for (int a = 0; a < 3; ++a) { att[a] = (float)(rg->attitude_offset[a] / 180.0 * pi); off[a] = (float)rg->pos_offset[a]; }   // :52
-    rotation3dh(att[0], att[2], att[1], m);                                                                                     // :200
-    std::vector<float> rpos(3 * (size_t)Nr), rvert(3 * (size_t)(Nv > 0 ? Nv : 1));
-    for (int pass = 0; pass < 2; ++pass) {
-        const int n = pass == 0 ? Nr : Nv;
-        const float *src = pass == 0 ? rg->points : rg->vertices;
-        float *dst = pass == 0 ? rpos.data() : rvert.data();
-        for (int i = 0; i < n; ++i) {
-            const float p[3] = {src[3 * i], src[3 * i + 1], src[3 * i + 2]};
-            for (int r = 0; r < 3; ++r) {
-                float v = ((m[3 * r] * p[0] + m[3 * r + 1] * p[1]) + m[3 * r + 2] * p[2]) + 0.0f * 1.0f;   // mat4 @ (p, 1), :205-207
-                dst[3 * i + r] = v + off[r];                                                                // :218, :223
-            }
-        }
-    }
-    // rigid cell list (canonical: ascending index inside a cell) for the one-time volume sums
+    const int Nr = h->Nr;
+    // rigid cell list (canonical: ascending index inside a cell) for the volume sums
     std::vector<int> rc3(3 * (size_t)Nr), rcell(Nr), rstart((size_t)c.C + 1, 0);
     for (int i = 0; i < Nr; ++i) {
         int cx = (int)floorf(rpos[3 * (size_t)i] / c.h), cy = (int)floorf(rpos[3 * (size_t)i + 1] / c.h), cz = (int)floorf(rpos[3 * (size_t)i + 2] / c.h);
@@ -116,7 +106,7 @@ int build_rigid(SphHandle *h, const SphRigid *rg)
     h->rmass_host.assign(Nr, 0.f);
     for (int i = 0; i < Nr; ++i) {                                                     // :252-259
         float volume = 0.f;
-        if (h->rigid_active) {
+        if (binned) {
             const float *pi_ = &rpos[3 * (size_t)i];
             for (int dx = -1; dx <= 1; ++dx)
                 for (int dy = -1; dy <= 1; ++dy)
@@ -157,10 +147,39 @@ int build_rigid(SphHandle *h, const SphRigid *rg)
     }
     const float I[9] = {Ixx, Ixy, Ixz, Ixy, Iyy, Iyz, Ixz, Iyz, Izz};
     inverse3h(I, h->inertia_inv);                                                       // :291
+    h->rigid_data_binned = binned;
+    return SPH_OK;
+}
+
+// init_rigid_particles_pos + init_rigid_particles_data (ParticleSystem.py:198-223, 249-295), once, on the host
+int build_rigid(SphHandle *h, const SphRigid *rg)
+{
+    h->Nr = rg->n_particles; h->Nv = rg->n_vertices;
+    h->rigid_active = rg->active ? 1 : 0;
+    h->rigid_rho = (float)rg->rho_0;
+    const int Nr = h->Nr, Nv = h->Nv;
+    const double pi = 3.141592653589793;
+    float att[3], m[9], off[3];
+    for (int a = 0; a < 3; ++a) { att[a] = (float)(rg->attitude_offset[a] / 180.0 * pi); off[a] = (float)rg->pos_offset[a]; }   // :52
+    rotation3dh(att[0], att[2], att[1], m);                                                                                     // :200
+    std::vector<float> rpos(3 * (size_t)Nr), rvert(3 * (size_t)(Nv > 0 ? Nv : 1));
+    for (int pass = 0; pass < 2; ++pass) {
+        const int n = pass == 0 ? Nr : Nv;
+        const float *src = pass == 0 ? rg->points : rg->vertices;
+        float *dst = pass == 0 ? rpos.data() : rvert.data();
+        for (int i = 0; i < n; ++i) {
+            const float p[3] = {src[3 * i], src[3 * i + 1], src[3 * i + 2]};
+            for (int r = 0; r < 3; ++r) {
+                float v = ((m[3 * r] * p[0] + m[3 * r + 1] * p[1]) + m[3 * r + 2] * p[2]) + 0.0f * 1.0f;   // mat4 @ (p, 1), :205-207
+                dst[3 * i + r] = v + off[r];                                                                // :218, :223
+            }
+        }
+    }
+    int rc;
+    if ((rc = rigid_init_data(h, rpos, h->rigid_active != 0))) return rc;
     h->rs_dt = (float)h->cfg.delta_time;                                                // rigid_solver.py:13
     h->rigid_pos_host = rpos;
     // device buffers
-    int rc;
     const size_t nr = (size_t)Nr;
     if ((rc = dalloc(h, &h->RPos, nr))) return rc;
     if ((rc = dalloc(h, &h->RPs, nr))) return rc;
@@ -179,7 +198,7 @@ int build_rigid(SphHandle *h, const SphRigid *rg)
     if ((rc = dalloc(h, &h->ncount, (size_t)h->c.stride))) return rc;
     if ((rc = dalloc(h, &h->rred, kRigidParts))) return rc;
     if ((rc = dalloc(h, &h->rvmax_part, kRigidParts))) return rc;
-    if ((rc = dalloc(h, &h->rnl, (nr + 64) * (size_t)c.kpitch))) return rc;
+    if ((rc = dalloc(h, &h->rnl, (nr + 64) * (size_t)h->c.kpitch))) return rc;
     if ((rc = dalloc(h, &h->rcnt, nr))) return rc;
     if (h->relaxed && h->staged && !h->tile_order) {       // relaxed arithmetic next to a body: the tile order of the exact / relaxed split (rx_split)
         if ((rc = dalloc(h, &h->tile_flag, (size_t)(h->c.stride + kBlock - 1) / kBlock + 1))) return rc;

@@ -216,7 +216,9 @@ struct SphHandle {
 
     // rigid body (config 5)
     bool rigid = false;
-    int rigid_active = 0;
+    int rigid_active = 0;         // ps.active_rigid[None]: read at step time (rigid_binned / rigid_coupled), written by sph_rigid_set_active
+    bool rigid_data_binned = false;   // the volumes / masses / centroid / inertia were last derived with the body binned (rigid_init_data)
+    bool lists_predate_flag = false;  // sph_rigid_set_active ran after the last list build: cnt / ncount still count for the old flag
     int Nv = 0;
     float rigid_rho = 0.f;
     float4 *RPos = nullptr;       // [Nr] rigid particles in their own index order: (x, y, z, V_r)
@@ -399,10 +401,62 @@ int sph_create_rigid(const SphConfig *cfg, const SphRigid *rigid, SphHandle **ou
     return rc;
 }
 
+// `ps.active_rigid[None] = active` (ParticleSystem.py:63-64; main.py:102): the flag, and nothing that was derived from the body
+int sph_rigid_set_active(SphHandle *h, int active)
+{
+    if (!h) return SPH_E_INVALID;
+    if (!h->rigid) return fail(h, SPH_E_STATE, "handle has no rigid body");
+    if (h->slab) return fail(h, SPH_E_STATE, "sph_rigid_set_active is not available on slab handles (the body is replicated on every rank)");
+    if (active && !h->cfg.fs_couple && h->relaxed)
+        return fail(h, SPH_E_STATE, "a one-way rigid body (active, fs_couple 0) needs the exact arithmetic (SPH_ARITH_EXACT): the relaxed kernels do not "
+                                    "take get_neighbour_count's rigid-entry quirk");
+    if (rigid_coupled(h) && !active) {
+        // The sweeps fetch one group of list entries past a row's end -- "stale but valid indices" (walk_list, sph_kernels.h).  Rows written while
+        // the body was coupled hold entries tagged with bit 31; beyond the shorter rows of the next build a sweep without the RIGID branches would
+        // take them for fluid indices.  Index 0 is valid in every list format
+        HIP_TRY(h, hipSetDevice(h->device));
+        HIP_TRY(h, hipMemsetAsync(h->nl, 0, sizeof(uint32_t) * ((size_t)h->c.stride + 64) * (size_t)h->c.kpitch, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
+    h->rigid_active = active ? 1 : 0;
+    // what the last list build derived with the old flag: the fluid lists (tagged rigid entries or none), cnt / ncount, the rigid sort, the body's
+    // lists (rnl / rcnt), the exact / relaxed tile split (tile_order) -- stage_sort_and_lists rebuilds all of it from the flag it finds.  The
+    // density loop's working-tiles-first order (dens_order) is a launch order only; it starts afresh as on a new handle
+    h->nl_valid = false;
+    h->density_valid = false;
+    h->lists_predate_flag = true;
+    h->dens_sparse = false;
+    return SPH_OK;
+}
+
+// ps.init_rigid_particles_data() (ParticleSystem.py:249-291) from the body's CURRENT sample positions, binned or not by the flag of this moment
+int sph_rigid_init_data(SphHandle *h)
+{
+    if (!h) return SPH_E_INVALID;
+    if (!h->rigid) return fail(h, SPH_E_STATE, "handle has no rigid body");
+    if (h->slab) return fail(h, SPH_E_STATE, "sph_rigid_init_data is not available on slab handles (the body is replicated on every rank)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t nr = (size_t)h->Nr;
+    std::vector<float4> rp4(nr);
+    HIP_TRY(h, hipMemcpyAsync(rp4.data(), h->RPos, sizeof(float4) * nr, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    std::vector<float> rpos(3 * nr);
+    for (size_t i = 0; i < nr; ++i) { rpos[3 * i] = rp4[i].x; rpos[3 * i + 1] = rp4[i].y; rpos[3 * i + 2] = rp4[i].z; }
+    int rc = rigid_init_data(h, rpos, rigid_binned(h));
+    if (rc) return rc;
+    // the new volumes into RPos[i].w (a strided copy: the positions stay the device's); RPs takes them at the next sort of the samples
+    HIP_TRY(h, hipMemcpy2DAsync(&h->RPos[0].w, sizeof(float4), h->rvol_host.data(), sizeof(float), sizeof(float), nr, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->nl_valid = false;
+    h->density_valid = false;
+    return SPH_OK;
+}
+
 int sph_rigid_step(SphHandle *h)
 {
     if (!h) return SPH_E_INVALID;
     if (!h->rigid) return fail(h, SPH_E_STATE, "handle has no rigid body");
+    if (int rc = rigid_released_unprepared(h)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     if (h->slab) {       // every sample's force was summed whole by the rank that owns its column (k_rigid_force): add the ranks' arrays up, x + 0 = x
         const int n3 = 3 * h->Nr;
@@ -515,6 +569,8 @@ int sph_download(SphHandle *h, int species, int field, float *host, size_t n_flo
         return SPH_OK;
     }
     if (h->slab) return fail(h, SPH_E_STATE, "slab handle: use sph_download_local + sph_download_ids (device order, owned and ghost particles)");
+    // get_neighbour_count after sph_rigid_set_active: the count of the flag as it stands, not of the lists built before it changed
+    if (field == SPH_F_NBR_COUNT && h->lists_predate_flag && (rc = sph_build_neighbors(h))) return rc;
     const bool dfsph = h->cfg.solver == SPH_SOLVER_DFSPH;
     const bool pcisph = h->cfg.solver == SPH_SOLVER_PCISPH, iisph = h->cfg.solver == SPH_SOLVER_IISPH;
     hipStream_t s = h->stream;
@@ -862,6 +918,7 @@ int sph_step_wcsph(SphHandle *h, int nsteps)
 {
     if (!h) return SPH_E_INVALID;
     if (h->cfg.solver != SPH_SOLVER_WCSPH) return fail(h, SPH_E_STATE, "handle was not created for wcsph");
+    if (int rc = rigid_released_unprepared(h)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     int k = 0;
     // The WCSPH step is a fixed launch sequence with no host decision in it, so two steps (after which the ping-pong
@@ -905,6 +962,7 @@ int sph_step_dfsph(SphHandle *h, int nsteps, SphStepStats *last)
 {
     if (!h) return SPH_E_INVALID;
     if (h->cfg.solver != SPH_SOLVER_DFSPH) return fail(h, SPH_E_STATE, "handle was not created for dfsph");
+    if (int rc = rigid_released_unprepared(h)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     SphStepStats st;
     memset(&st, 0, sizeof(st));
@@ -920,6 +978,7 @@ int sph_step_pcisph(SphHandle *h, int nsteps, SphStepStats *last)
 {
     if (!h) return SPH_E_INVALID;
     if (h->cfg.solver != SPH_SOLVER_PCISPH) return fail(h, SPH_E_STATE, "handle was not created for pcisph");
+    if (int rc = rigid_released_unprepared(h)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     SphStepStats st;
     memset(&st, 0, sizeof(st));
@@ -935,6 +994,7 @@ int sph_step_iisph(SphHandle *h, int nsteps, SphStepStats *last)
 {
     if (!h) return SPH_E_INVALID;
     if (h->cfg.solver != SPH_SOLVER_IISPH) return fail(h, SPH_E_STATE, "handle was not created for iisph");
+    if (int rc = rigid_released_unprepared(h)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     SphStepStats st;
     memset(&st, 0, sizeof(st));
@@ -981,6 +1041,7 @@ int sph_get_scalar(SphHandle *h, int which, double *out)
     case SPH_S_PCISPH_MAX_COUNT: *out = (double)h->pci_max_count; return SPH_OK;
     case SPH_S_PS_DELTA_TIME: { int rc = read_scalars(h); if (rc) return rc; *out = (double)h->ds_host->ps_dt; return SPH_OK; }
     case SPH_S_ARITH_RELAXED: *out = (use_relaxed(h) || h->verlet || relaxed_pressure(h) || relaxed_unstaged(h)) ? 1.0 : 0.0; return SPH_OK;
+    case SPH_S_RIGID_ACTIVE: *out = rigid_binned(h) ? 1.0 : 0.0; return SPH_OK;
     case SPH_S_VERLET_BUILDS: { int rc = read_scalars(h); if (rc) return rc; *out = (double)h->ds_host->verlet_builds; return SPH_OK; }      // kr_split is settled by the first list build
     case SPH_P_DENSITY_THRESHOLD: *out = h->p.density_threshold; return SPH_OK;
     case SPH_P_MIN_ITERATION_DENSITY: *out = h->p.min_iteration_density; return SPH_OK;

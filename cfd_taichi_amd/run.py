@@ -6,7 +6,9 @@
 Per frame: `iter_cnt` fluid steps, then `iter_cnt` rigid steps if a rigid body is active (main.py:165-171),
 t += iter_cnt * solver.delta_time[None] (:173); stops at t > 4.0 (:205) or after --steps frames.  With --ply-dir (or
 scene.is_output_ply) it writes ASCII PLY frames `output_%06d.ply` at scene.output_fps like main.py:189-195 (vertex
-xyz + the constant RGBA of ParticleSystem.py:152) and, when a rigid body exists, `obj_%06d.obj` of its mesh (:196-200)."""
+xyz + the constant RGBA of ParticleSystem.py:152) and, when a rigid body exists, `obj_%06d.obj` of its mesh (:196-200).
+--release-rigid-at FRAME runs the release sequence the reference keeps commented out at main.py:100-106 when frame_cnt reaches FRAME: a body
+created with `solid.active: false` drops into the fluid as it is then."""
 import argparse
 import importlib
 import os
@@ -87,6 +89,8 @@ def main(argv=None):
     ap.add_argument("--transport", default=None, choices=["native", "torch"], help="sharded runs: the library's own RCCL communicator (default with one GPU per rank) or torch.distributed callbacks")
     ap.add_argument("--arith", default=None, choices=["exact", "relaxed"],
                     help="exact (default): the reference's f32 operations in its order; relaxed: the tolerance-grade sweeps (SphConfig.arith)")
+    ap.add_argument("--release-rigid-at", type=int, default=None, metavar="FRAME",
+                    help="activate the rigid body when frame_cnt reaches FRAME (main.py:100-106: let the fluid settle first)")
     args = ap.parse_args(argv)
 
     config = utils.read_config(args.config)
@@ -114,6 +118,11 @@ def main(argv=None):
     while True:
         if frame_cnt > 100000:                                                   # :98
             break
+        if rs and args.release_rigid_at is not None and frame_cnt == args.release_rigid_at:   # :100-106
+            ps.active_rigid[None] = 1
+            ps.reset_grid()
+            ps.update_grid()
+            ps.init_rigid_particles_data()
         for _ in range(iter_cnt):
             solver.step()
         for _ in range(iter_cnt):

@@ -179,6 +179,7 @@ typedef struct SphRigid {
 #define SPH_S_RIGID_VEL 16        /* +0,1,2: rigid_particles.vel (uniform over the body) */
 #define SPH_S_RIGID_MASS 19       /* rigid_solver.mass[None] */
 #define SPH_S_RIGID_INERTIA_INV 20 /* +0..8: ps.rigid_inertia_tensor_inv[None], row major */
+#define SPH_S_RIGID_ACTIVE 32      /* ps.active_rigid[None] as it stands (sph_rigid_set_active writes it); 0 on a handle without a body */
 #define SPH_S_VERLET_BUILDS 31    /* diagnostics: list builds so far on a Verlet handle (wcsph under the relaxed arithmetic: the lists carry a skin and are rebuilt on demand) */
 #define SPH_S_ARITH_RELAXED 30    /* diagnostics: 1 if this handle's dfsph sweeps run the tolerance-grade kernels (SphConfig.arith asked AND the handle qualifies) */
 
@@ -213,6 +214,18 @@ int sph_create(const SphConfig *cfg, SphHandle **out);
 int sph_create_rigid(const SphConfig *cfg, const SphRigid *rigid, SphHandle **out);
 /* replaces rigid_solver.step()   rigid_solver.py:216-232 */
 int sph_rigid_step(SphHandle *h);
+/* replaces `ps.active_rigid[None] = active`   ParticleSystem.py:63-64, main.py:102.  The flag and nothing else: from the next grid build an
+ * active body is binned (and, with fs_couple, coupled), an inactive one is not -- its samples leave every neighbour walk and
+ * get_neighbour_count's rigid-entry quirk -- and keeps its pose, velocity and omega.  Nothing is re-derived: pcisph's delta, dfsph's
+ * warm_start_k and delta_time, rigid_particles.force stay as they are.  SPH_E_STATE (handle unchanged): no body; a slab handle; a one-way
+ * body (active, fs_couple 0) under SPH_ARITH_RELAXED, as sph_create_rigid refuses it. */
+int sph_rigid_set_active(SphHandle *h, int active);
+/* replaces ps.init_rigid_particles_data()   ParticleSystem.py:249-291, main.py:106: sample volumes, masses, the centroid, the inertia tensor
+ * and its inverse from the body's CURRENT sample positions, binned or not by the flag of this moment.  Velocity, omega, rigid_solver.mass
+ * and its run_once_flag are left alone.  Host work, once per release.  A body created inactive has zero volumes (the reference's too); once it is
+ * released, sph_step_* and sph_rigid_step return SPH_E_STATE until this call has run -- the reference would step on with NaN.
+ * SPH_E_STATE: no body; a slab handle. */
+int sph_rigid_init_data(SphHandle *h);
 void sph_destroy(SphHandle *h);
 int sph_get_sizes(SphHandle *h, SphSizes *out);
 const char *sph_last_error(SphHandle *h);
