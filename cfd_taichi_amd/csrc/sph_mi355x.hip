@@ -894,12 +894,19 @@ int sph_compute_density(SphHandle *h)
     HIP_TRY(h, hipSetDevice(h->device));
     int rc;
     if (!h->nl_valid) {
-        // pbf_lambda is a per-particle field of the solver that compute_all_rho does not touch; it lives in device order (aux), which the
-        // re-sort below changes: carry it through in API order
+        // pbf_lambda and delta_pos are per-particle fields of the solver that compute_all_rho does not touch; they live in device order (aux,
+        // X[0]), which the re-sort below changes: carry them through in API order -- lambda in the staging buffer, delta_pos as 3 N floats in
+        // X[1] (phase 1's new positions: scratch between steps, 4 N floats)
         const bool keep = h->cfg.solver == SPH_SOLVER_PBF && h->simulate_cnt > 0;
-        if (keep) hipLaunchKernelGGL(k_unsort_scalar, grid_for(h->N), dim3(kBlock), 0, h->stream, h->N, h->aux, h->id[h->icur], h->staging);
+        if (keep) {
+            hipLaunchKernelGGL(k_unsort_scalar, grid_for(h->N), dim3(kBlock), 0, h->stream, h->N, h->aux, h->id[h->icur], h->staging);
+            hipLaunchKernelGGL(k_unsort_vec, grid_for(h->N), dim3(kBlock), 0, h->stream, h->N, h->X[0], h->id[h->icur], (float *)h->X[1]);
+        }
         if ((rc = sph_build_neighbors(h))) return rc;
-        if (keep) hipLaunchKernelGGL(k_sort_in_scalar, grid_for(h->N), dim3(kBlock), 0, h->stream, h->N, h->staging, h->id[h->icur], h->aux);
+        if (keep) {
+            hipLaunchKernelGGL(k_sort_in_scalar, grid_for(h->N), dim3(kBlock), 0, h->stream, h->N, h->staging, h->id[h->icur], h->aux);
+            hipLaunchKernelGGL(k_sort_in_vec, grid_for(h->N), dim3(kBlock), 0, h->stream, h->N, (const float *)h->X[1], h->id[h->icur], h->X[0]);
+        }
     }
     if (h->density_valid) return SPH_OK;
     if ((rc = stage_density(h))) return rc;

@@ -4,7 +4,10 @@
 // as particle structs, ParticleSystem.py:468-469); it is read the way the other solvers' callbacks were updated (callback argument
 // -> the struct's pos / vel / index).  update_all_pos (:66-95) races on pos and vel; the kernels follow the barrier-synchronised
 // schedule (every particle's own writes, then every particle's neighbour reads, then the viscosity update), which is one legal
-// execution of the reference loop and the one the tests' CPU restatement follows.  No rigid coupling (the callbacks have none).
+// execution of the reference loop and the one both CPU restatements of the tests follow: the C restatement under oracle/ (its step_pbf) and the
+// independently written tests/second_restatement_pbf.py, whose docstring numbers the reading as conventions 1-6; the quad and plain
+// instantiations below are held to the second one on linear and on Morton cells (tests/test_second_restatement_gpu.py).  No rigid
+// coupling (the callbacks have none).
 //
 // Three sweeps per step:
 //   k_pbf_lambda   rho (poly6), constrain, constrain_derivative, lambda           :32-52, 108-140   (the reference: five walks)

@@ -4,9 +4,11 @@ of what the run exercised.  TEST INFRASTRUCTURE ONLY."""
 import numpy as np
 
 from second_restatement import Solver
+from second_restatement_pbf import PbfSolver
 
 F_ID = {"pos": 0, "vel": 1, "acc": 2, "rho": 3, "pressure": 4, "alpha": 5, "warm": 6, "rho_adv": 7, "rho_derivative": 8, "vel_adv": 9,
         "ncount": 14, "press_iter": 16, "press_force": 17, "pos_predict": 18, "d_ii": 19, "a_ii": 20, "d_ij": 21,
+        "pbf_lambda": 22, "pbf_delta_pos": 23,
         "rigid_pos": 48, "rigid_vol": 49, "rigid_force": 50, "rigid_vert": 52}       # include/sph_mi355x.h = oracle/sph_oracle.h
 # restatement attribute -> field, per solver
 FIELDS = {
@@ -15,6 +17,7 @@ FIELDS = {
               "ncount": "ncount", "vel": "vel", "pos": "pos"},
     "pcisph": {"rho": "rho", "press_iter": "press_iter", "pos_predict": "pos_predict", "press_force": "press_force", "vel": "vel", "pos": "pos"},
     "iisph": {"rho": "rho", "p_iter": "press_iter", "f_press": "press_force", "d_ii": "d_ii", "a_ii": "a_ii", "d_ij": "d_ij", "vel": "vel", "pos": "pos"},
+    "pbf": {"rho": "rho", "pbf_lambda": "pbf_lambda", "delta_pos": "pbf_delta_pos", "vel": "vel", "pos": "pos"},
 }
 
 
@@ -60,6 +63,10 @@ class OracleSide:
 
     def ncount_after_step(self):
         return None
+
+    def density_only(self):
+        self.o.build_grid()
+        self.o.compute_rho()
 
     def step(self):
         if self.solver == "dfsph":
@@ -107,6 +114,9 @@ class NativeSide:
         """the count of the step's own list build"""
         return self.get("ncount")
 
+    def density_only(self):
+        self.sim.compute_density()
+
     def step(self):
         return getattr(self.sim, "step_" + self.solver)(1)
 
@@ -120,17 +130,19 @@ class NativeSide:
         self.sim.close()
 
 
-def compare_run(cfg, steps, sides, state=None, rg=None):
+def compare_run(cfg, steps, sides, state=None, rg=None, density_after=False):
     """Step the second restatement `steps` times and every side with it; after EVERY step compare the solver's fields, its iteration counts
-    and residuals, and (with a body) the per-sample forces, then rigid_step everywhere (main.py:165-173) and compare the body.  `sides`:
-    callables (cfg, rg, solver) -> OracleSide / NativeSide.  Returns what the run exercised."""
+    and residuals (pbf has none), and (with a body) the per-sample forces, then rigid_step everywhere (main.py:165-173) and compare the body.
+    `sides`: callables (cfg, rg, solver) -> OracleSide / NativeSide.  density_after (pbf): after the last step compute_all_rho alone on every
+    side -- rho as the restatement's, every other field of FIELDS left bit for bit as it was.  Returns what the run exercised."""
     solver = cfg["solver"]["name"]
-    s = Solver(cfg, rg)
+    s = PbfSolver(cfg) if solver == "pbf" else Solver(cfg, rg)
     if solver == "dfsph" and rg is not None:
         s.max_dens = 100
     sides = [make(cfg, rg, solver) for make in sides]
     b = s.body
-    ev = {"iters": [], "hit_steps": [], "force": [], "quirk": 0, "vy": [], "on_plane": 0, "minus_zero": 0}
+    ev = {"iters": [], "hit_steps": [], "force": [], "quirk": 0, "vy": [], "on_plane": 0, "minus_zero": 0,
+          "lambda_active": [], "xsph_max": [], "cell_changes": []}                   # pbf, per step
     count_too = solver == "pcisph" and b is not None and b.active     # dfsph has ncount among its FIELDS; pcisph uses it at construction only
     r = np.float32(s.sc.radius if solver != "wcsph" else s.sc.diameter)
     lo, hi = np.array(s.sc.box_min, dtype=np.float32) + r, np.array(s.sc.box_max, dtype=np.float32) - r
@@ -161,13 +173,17 @@ def compare_run(cfg, steps, sides, state=None, rg=None):
                     if solver == "dfsph":
                         mine = (s.n_div, s.n_dens, np.float32(s.div_first), np.float32(s.div_err), np.float32(s.dens_err), np.float32(s.dt))
                         assert mine == (st.n_div, st.n_dens, np.float32(st.div_first_err), np.float32(st.div_err), np.float32(st.dens_err), np.float32(st.dt)), (when, mine)
-                    elif solver != "wcsph":
+                    elif solver not in ("wcsph", "pbf"):
                         assert (s.n_dens, np.float32(s.dens_err)) == (st.n_dens, np.float32(st.dens_err)), (when, s.n_dens, st.n_dens, s.dens_err, st.dens_err)
                     for attr, name in FIELDS[solver].items():
                         same(getattr(s, attr), side.get(name), "%s: %s" % (when, attr))
                     if b is not None:
                         same(b.force, side.get("rigid_force"), "%s: per-sample force" % when)
                 ev["iters"].append((s.n_div, s.n_dens) if solver == "dfsph" else s.n_dens)
+                if solver == "pbf":
+                    ev["lambda_active"].append(int((s.pbf_lambda != 0).sum()))
+                    ev["xsph_max"].append(s.xsph_max)
+                    ev["cell_changes"].append(s.cell_changes)
                 if not s.walls:
                     ev["on_plane"] += int(((s.pos == lo) | (s.pos == hi)).sum())          # the clamp branch put them there
                     if solver == "pcisph":
@@ -183,6 +199,16 @@ def compare_run(cfg, steps, sides, state=None, rg=None):
                         for side in sides:
                             side.rigid_step()
                             _same_body(b, side, "after rigid step %d" % k, True)
+            if density_after:
+                s.density_only()
+                for side in sides:
+                    kept = {name: side.get(name).copy() for name in FIELDS[solver].values() if name != "rho"}
+                    side.density_only()
+                    same(s.rho, side.get("rho"), "%s: rho of compute_all_rho alone" % side.label)
+                    for name, was in kept.items():
+                        same(was, side.get(name), "%s: %s across compute_all_rho alone" % (side.label, name))
+                for attr, name in FIELDS[solver].items():       # ... and the restatement's own
+                    same(getattr(s, attr), sides[0].get(name), "%s after compute_all_rho alone" % attr)
     finally:
         for side in sides:
             side.close()

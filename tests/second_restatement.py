@@ -1,4 +1,4 @@
-"""A SECOND, independent restatement of the reference's WCSPH / DFSPH / PCISPH / IISPH step -- numpy f32, brute-force O(N^2) neighbour search.
+"""A SECOND, independent restatement of the reference's WCSPH / DFSPH / PCISPH / IISPH step (PBF: second_restatement_pbf.py) -- numpy f32, brute-force O(N^2) neighbour search.
 
 TEST INFRASTRUCTURE ONLY (tests/test_second_restatement.py).  Purpose: a transcription check on oracle/sph_oracle.c.  The oracle and the
 HIP kernels were written by the same hand from the same reading of the reference, and the GPU suite proves that they agree with EACH OTHER;
@@ -21,7 +21,8 @@ and rounded once.
 Reach: WCSPH, DFSPH, PCISPH (pcisph_solver.py) and IISPH (iisph_solver.py) with Akinci walls and with the clamp branch, and the
 material_solid branches of all four with the rigid samples as a third species; the body itself (placement, volumes, inertia,
 rigid_solver.step, its conventions about Taichi numbered there) is tests/second_restatement_rigid.py.  tests/test_second_restatement.py
-holds the oracle against this file, tests/test_second_restatement_gpu.py the library.  PBF and the voxeliser stay on one reading.
+holds the oracle against this file, tests/test_second_restatement_gpu.py the library.  PBF (pbf_solver.py) is tests/second_restatement_pbf.py,
+a subclass of Solver with its own numbered conventions; only the voxeliser stays on one reading.
 """
 import math
 
@@ -132,11 +133,14 @@ class Scene:
 
 class Neighbours:
     """for_all_neighbor / for_all_boundary_neighbor as a SET and an ORDER (ParticleSystem.py:447-469, 337-366), by testing every pair.
-    `centres` walk, `others` are met; same = the two are the same species (the walker skips itself, :461 / :362)."""
+    `centres` walk, `others` are met; same = the two are the same species (the walker skips itself, :461 / :362).
+    cell_centres / cell_others: the positions update_grid saw (belong_grid :397 and the lists :396), where a kernel has moved the particles
+    since -- the cells come from those, the distances of :466 from centres / others (pbf's update_all_pos, second_restatement_pbf.py)."""
 
-    def __init__(self, sc, centres, others, same):
+    def __init__(self, sc, centres, others, same, cell_centres=None, cell_others=None):
         g = np.array(sc.grid, dtype=np.int64)
-        cc, co = sc.cell(centres).astype(np.int64), sc.cell(others).astype(np.int64)
+        cc = sc.cell(centres if cell_centres is None else cell_centres).astype(np.int64)
+        co = sc.cell(others if cell_others is None else cell_others).astype(np.int64)
         # what update_grid put into the lists: a particle whose 1-D index is out of range is not appended (:393-395)
         flat = co[:, 0] + co[:, 1] * (g[0] * g[2]) + co[:, 2] * g[0]                # get_particle_grid_index_1d :486-488
         listed = (flat >= 0) & (flat <= sc.C)

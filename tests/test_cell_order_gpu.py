@@ -16,7 +16,7 @@ import pytest
 from cfd_taichi_amd import _native as nat
 from cfd_taichi_amd import mesh, scenes
 from oracle import oracle as orc
-from test_fuzz_gpu import random_scene
+from test_fuzz_gpu import PBF_FIELDS, random_scene, squeeze_both
 from test_slab_gpu import run_slabs
 
 pytestmark = pytest.mark.gpu
@@ -71,18 +71,29 @@ def test_morton_device_order_small_scene(monkeypatch):
     sim.close()
 
 
-@pytest.mark.parametrize("solver", ["wcsph", "dfsph", "pcisph", "iisph"])
+@pytest.mark.parametrize("solver", ["wcsph", "dfsph", "pcisph", "iisph", "pbf"])
 @pytest.mark.parametrize("seed", range(3))
 def test_random_scene_on_the_morton_curve_matches_oracle(solver, seed, monkeypatch):
+    """(pbf: squeezed on both sides, pbf_lambda and delta_pos compared too -- k_pbf_xsph is the one sweep that walks cell_start through the
+    Morton slots itself)"""
     rng = np.random.default_rng(3000 + seed)
     cfg = random_scene(rng, solver)
     sim = make(cfg, "morton", monkeypatch)
     o = orc.Oracle(cfg, solver=solver, num_threads=4)
+    if solver == "pbf":
+        squeeze_both(sim, o)
+    lambda_active = 0
     for s in range(25):
         sim.step(1)
-        {"wcsph": o.step_wcsph, "pcisph": o.step_pcisph, "iisph": o.step_iisph}.get(solver, lambda n: o.step_dfsph(n, 100))(1)
-    for f, of in ((nat.F_POS, orc.F_POS), (nat.F_VEL, orc.F_VEL), (nat.F_RHO, orc.F_RHO)):
+        {"wcsph": o.step_wcsph, "pcisph": o.step_pcisph, "iisph": o.step_iisph, "pbf": o.step_pbf}.get(solver, lambda n: o.step_dfsph(n, 100))(1)
+        if solver == "pbf":
+            lambda_active = max(lambda_active, int((o.get(orc.F_PBF_LAMBDA) != 0).sum()))
+            for f, of in PBF_FIELDS:
+                assert np.array_equal(sim.download(f), o.get(of)), (seed, s, f, cfg)
+    for f, of in ((nat.F_POS, orc.F_POS), (nat.F_VEL, orc.F_VEL), (nat.F_RHO, orc.F_RHO)) + (PBF_FIELDS if solver == "pbf" else ()):
         assert np.array_equal(sim.download(f), o.get(of), equal_nan=True), (solver, seed, f, cfg)
+    if solver == "pbf":
+        assert lambda_active > 0, ("the density constraint never became active: lambda / delta_pos not exercised", cfg)
     sim.close(); o.close()
 
 

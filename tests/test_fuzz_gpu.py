@@ -1,6 +1,8 @@
-"""GPU suite: seeded random scenes (particle radius, box, water block, start position, dt, wall model) x the four solvers, against the
+"""GPU suite: seeded random scenes (particle radius, box, water block, start position, dt, wall model) x the five solvers, against the
 oracle bit for bit.  Every BASELINE config uses r = 0.025; the constants derived from r (h, m, the exact division by h, the cell grid) and the
-lattice arithmetic must hold for other radii and for boxes that are not multiples of the cell size."""
+lattice arithmetic must hold for other radii and for boxes that are not multiples of the cell size.  For PBF these scenes are the only
+ones that take pbf_consts()'s host-folded constants (kpoly, pih4, w_corr, the clamp planes) away from one value of h; its block is squeezed
+on both sides (test_pbf_gpu.squeeze) so that lambda and delta_pos act, and pbf_lambda / delta_pos are compared as well."""
 import numpy as np
 import pytest
 
@@ -21,12 +23,24 @@ def random_scene(rng, solver):
     cfg = scenes.get("dfsph_tiny_wall")
     cfg["scene"].update(box_max=box, particle_radius=r)
     cfg["solver"].update(name=solver, boundary_handle=walls,
-                         delta_time=float(rng.choice([2.5e-4, 5e-4])) if solver == "wcsph" else float(rng.choice([5e-4, 1e-3])))
+                         delta_time=2.5e-4 if solver == "pbf" else
+                         float(rng.choice([2.5e-4, 5e-4])) if solver == "wcsph" else float(rng.choice([5e-4, 1e-3])))
     cfg["fluid"].update(start_pos=start, water_size=water)
     return cfg
 
 
-@pytest.mark.parametrize("solver", ["wcsph", "dfsph", "pcisph", "iisph"])
+def squeeze_both(sim, o, factor=0.9):
+    """test_pbf_gpu.squeeze: the rest lattice scaled about its minimum corner on both sides, so that the PBF constraint acts from step 1"""
+    pos = o.get(orc.F_POS)
+    about = pos.min(0)
+    sq = (about + (pos - about) * np.float32(factor)).astype(np.float32)
+    o.set(orc.F_POS, sq); sim.upload(nat.F_POS, sq)
+
+
+PBF_FIELDS = ((nat.F_PBF_LAMBDA, orc.F_PBF_LAMBDA), (nat.F_PBF_DELTA_POS, orc.F_PBF_DELTA_POS))
+
+
+@pytest.mark.parametrize("solver", ["wcsph", "dfsph", "pcisph", "iisph", "pbf"])
 @pytest.mark.parametrize("seed", range(6))
 def test_random_scene_matches_oracle(solver, seed):
     rng = np.random.default_rng(1000 + seed)
@@ -39,8 +53,16 @@ def test_random_scene_matches_oracle(solver, seed):
     if o.Nb:
         assert np.array_equal(sim.download(nat.F_WALL_VOL, nat.SPECIES_WALL), o.get(orc.F_WALL_VOL)), "wall volumes"
     steps = 30
+    if solver == "pbf":
+        squeeze_both(sim, o)
+    lambda_active = 0
     for s in range(steps):
-        if solver == "wcsph":
+        if solver == "pbf":
+            sim.step_pbf(1); o.step_pbf(1)
+            lambda_active = max(lambda_active, int((o.get(orc.F_PBF_LAMBDA) != 0).sum()))
+            for f, of in PBF_FIELDS:      # every step: the constraint relaxes within the run, the last step's lambda may be all zero
+                assert np.array_equal(sim.download(f), o.get(of)), (seed, s, f, cfg)
+        elif solver == "wcsph":
             sim.step_wcsph(1); o.step_wcsph(1)
         elif solver == "dfsph":
             st = sim.step_dfsph(1); o.step_dfsph(1, 100)
@@ -50,7 +72,9 @@ def test_random_scene_matches_oracle(solver, seed):
             st = sim.step(1)
             (o.step_pcisph if solver == "pcisph" else o.step_iisph)(1)
             assert (st.n_dens, st.dens_err) == (o.last_stats.n_dens, o.last_stats.dens_err), (s, cfg)
-    for f, of in ((nat.F_POS, orc.F_POS), (nat.F_VEL, orc.F_VEL), (nat.F_RHO, orc.F_RHO)):
+    for f, of in ((nat.F_POS, orc.F_POS), (nat.F_VEL, orc.F_VEL), (nat.F_RHO, orc.F_RHO)) + (PBF_FIELDS if solver == "pbf" else ()):
         a, b = sim.download(f), o.get(of)
         assert np.array_equal(a, b, equal_nan=True), (solver, seed, f, int((a != b).sum()), cfg)
+    if solver == "pbf":
+        assert lambda_active > 0, ("the density constraint never became active: lambda / delta_pos not exercised", cfg)
     sim.close(); o.close()

@@ -3,7 +3,11 @@
 The reference file is stale at the surveyed commit (fluid callbacks written for particle indices, for_all_neighbor passes structs) and
 its update_all_pos races on pos / vel; library and oracle read it the same documented way (csrc/sph_pbf_kernels.h): callbacks on the
 structs' fields, update_all_pos under the barrier-synchronised schedule.  Parity is therefore "equal to the restatement under that
-reading", unpinned like the rest."""
+reading", unpinned like the rest.  The reading itself is checked by a second, independently written restatement
+(tests/second_restatement_pbf.py; tests/test_second_restatement.py for the oracle, tests/test_second_restatement_gpu.py for the library).
+
+The cases of the lower half run what the upper half never reaches: the plain (one lane per particle) instantiations and the Morton cell
+order that a default handle takes above 65 536 and from 131 072 particles, and a particle count that fills no workgroup."""
 import numpy as np
 import pytest
 
@@ -100,11 +104,13 @@ def test_pbf_compute_density_is_poly6_and_leaves_lambda_alone(scene):
         sim.step_pbf(1); o.step_pbf(1)
     lam = o.get(orc.F_PBF_LAMBDA).copy()
     assert (lam != 0).any()
-    pos, vel = sim.download(nat.F_POS), sim.download(nat.F_VEL)
+    pos, vel, dpos = sim.download(nat.F_POS), sim.download(nat.F_VEL), sim.download(nat.F_PBF_DELTA_POS)
+    same(dpos, o.get(orc.F_PBF_DELTA_POS), "delta_pos before compute_density")
     sim.compute_density()
     o.build_grid(); o.compute_rho()
     same(sim.download(nat.F_RHO), o.get(orc.F_RHO), "rho after compute_density")
     same(sim.download(nat.F_PBF_LAMBDA), lam, "pbf_lambda after compute_density")
+    same(sim.download(nat.F_PBF_DELTA_POS), dpos, "delta_pos after compute_density (carried through the re-sort like pbf_lambda)")
     same(sim.download(nat.F_POS), pos, "pos after compute_density")
     same(sim.download(nat.F_VEL), vel, "vel after compute_density")
     # rho is the poly6 sum, not the cubic spline one: the two differ on a squeezed lattice
@@ -112,3 +118,71 @@ def test_pbf_compute_density_is_poly6_and_leaves_lambda_alone(scene):
     same(sim.download(nat.F_POS), o.get(orc.F_POS), "pos, the step after")
     same(sim.download(nat.F_PBF_LAMBDA), o.get(orc.F_PBF_LAMBDA), "pbf_lambda, the step after")
     sim.close(); o.close()
+
+
+# ---- the kernels and cell order a large handle really runs (the cases above all stay below 65 536 particles: k_pbf_*<true>, linear cells) ----
+
+FIELDS = (("rho", nat.F_RHO, orc.F_RHO), ("pbf_lambda", nat.F_PBF_LAMBDA, orc.F_PBF_LAMBDA), ("delta_pos", nat.F_PBF_DELTA_POS, orc.F_PBF_DELTA_POS),
+          ("pos", nat.F_POS, orc.F_POS), ("vel", nat.F_VEL, orc.F_VEL))
+
+
+def water_block(nx, ny, nz, margin=0.5):
+    """pbf_tiny_wall's scene (r = 0.025, Akinci walls) with a block of nx x ny x nz particles at (0.1, 0.1, 0.1) in a box `margin` larger than it"""
+    cfg = scenes.get("pbf_tiny_wall")
+    d = 2 * cfg["scene"]["particle_radius"]
+    ws = [round(n * d, 6) for n in (nx, ny, nz)]
+    cfg["scene"]["box_max"] = [round(w + margin, 6) for w in ws]
+    cfg["fluid"].update(start_pos=[0.1, 0.1, 0.1], water_size=ws)
+    return cfg
+
+
+def lockstep(sim, o, steps):
+    active = 0
+    for s in range(steps):
+        sim.step_pbf(1); o.step_pbf(1)
+        for name, f, of in FIELDS:
+            same(sim.download(f), o.get(of), "%s, step %d" % (name, s + 1))
+        active = max(active, int((o.get(orc.F_PBF_LAMBDA) != 0).sum()))
+    return active
+
+
+@pytest.mark.parametrize("block,lo,hi", [((42, 40, 40), 65536, 131072), ((52, 52, 50), 131072, 1 << 18)],
+                         ids=["linear_cells_plain_sweeps", "morton_cells_plain_sweeps"])
+def test_pbf_beyond_the_thresholds_without_overrides(block, lo, hi):
+    """The two thresholds of a default handle, with no development override in force: above quad_below = 65 536 particles step_pbf_once
+    launches k_pbf_{lambda,delta,xsph}<false>, from 1 << 17 particles on the cells are stored along the Morton curve and k_pbf_xsph reaches them
+    through cell_slot_xyz.  67 200 and 135 200 particles clear the thresholds by 2.5 % and 3.1 %; three squeezed steps, every field, every step."""
+    cfg = water_block(*block)
+    sim = nat.Simulation(nat.config_from_dict(cfg))
+    o = orc.Oracle(cfg, num_threads=16)
+    try:
+        assert sim.overrides() == [], sim.overrides()
+        assert lo < sim.n_fluid < min(hi, int(lo * 1.05)) and sim.n_fluid == block[0] * block[1] * block[2], sim.n_fluid
+        assert (sim.n_fluid, sim.n_wall, tuple(sim.grid)) == (o.N, o.Nb, tuple(o.grid))
+        squeeze(sim, o)
+        active = lockstep(sim, o, 3)
+        print("%d particles: up to %d with lambda != 0" % (sim.n_fluid, active))
+        assert active > 0, "the density constraint never became active"
+    finally:
+        sim.close(); o.close()
+
+
+@pytest.mark.parametrize("quad", ["1", "0"], ids=["quad", "plain"])
+def test_pbf_ragged_last_workgroup(quad, monkeypatch):
+    """A 9 x 10 x 7 block -- 629 particles by the reference's truncating count (ParticleSystem.py:85-86: 0.35 / 0.05 < 7), an incomplete top
+    layer, neither a multiple of 64 (a quad workgroup's particles) nor of 256 (a plain one's): the last workgroup of both grids is partly empty -- `if (i >= c.n) return` with "a quad leaves together" in k_pbf_xsph, the prologue's guard in the list sweeps."""
+    cfg = water_block(9, 10, 7)
+    if quad == "0":
+        monkeypatch.setenv("SPH_QUAD", "0")
+    else:
+        monkeypatch.delenv("SPH_QUAD", raising=False)
+    sim = nat.Simulation(nat.config_from_dict(cfg))
+    o = orc.Oracle(cfg, num_threads=4)
+    try:
+        assert sim.overrides() == (["SPH_QUAD=0"] if quad == "0" else []), sim.overrides()
+        assert sim.n_fluid == o.N == 629 and sim.n_fluid % 64 and sim.n_fluid % 256
+        squeeze(sim, o)
+        active = lockstep(sim, o, 12)
+        assert active > 0, "the density constraint never became active"
+    finally:
+        sim.close(); o.close()

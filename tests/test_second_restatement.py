@@ -6,7 +6,13 @@ proves that they agree with each other.  A transcription error common to both wo
 differ in algorithm (27-cell walk over per-cell lists there, all-pairs test + sort by (cell offset, index) here) and in language, and still
 agree bit for bit over ten steps of a wall-bounded scene -- state, densities, alpha, iteration counts, residuals, dt -- make such an error
 much less likely.  It does NOT pin the oracle to the reference: both restatements rest on the same assumptions about Taichi's arithmetic
-(SURVEY.md Appendix A), and `parity` stays "unpinned"."""
+(SURVEY.md Appendix A), and `parity` stays "unpinned".
+
+PBF (tests/second_restatement_pbf.py, the last section below) is held the same way: rho, pbf_lambda, delta_pos, pos and vel after every step of
+four cases, compute_all_rho alone, and two f64 checks of the restatement's own poly6 / spiky kernel functions that rest on no reading at all.
+Disagreements found between the PBF restatement and the oracle: none, on any case, field or step."""
+import math
+
 import numpy as np
 import pytest
 
@@ -211,3 +217,152 @@ def test_inactive_body_equals_no_body():
     same(a.vel, b.vel, "velocities with an inactive body and with none")
     assert (a.delta, a.max_index) == (b.delta, b.max_index)
     assert not a.body.vol.any() and not a.body.force.any()
+
+
+# ---- PBF: the oracle against tests/second_restatement_pbf.py (its numbered conventions say how pbf_solver.py is read) ----------------------
+
+PBF_KINDS = ["wall_squeezed", "clamp_squeezed", "clamp_thrown", "wall_jitter"]
+PBF_THROWN_SHIFT = (-0.05, -0.05, 0.0)
+
+
+def pbf_squeezed(cfg, factor=0.9):
+    """test_pbf_gpu.squeeze as a state: the rest lattice scaled about its minimum corner, at rest -- lambda and delta_pos act from step 1"""
+    pos = Scene(cfg).pos
+    about = pos.min(0)
+    return (about + (pos - about) * np.float32(factor)).astype(np.float32), np.zeros_like(pos)
+
+
+def pbf_case(kind):
+    """(config, steps, state) on pbf_tiny_wall / pbf_tiny_clamp (640 fluid, 2 402 wall particles, dt 2.5e-4).
+    clamp_thrown: cs.clamp_thrown (the ragged state plus (-4, -4, 0) m/s) covers 1e-3 per step, and the block starts 0.06 above the planes
+    box_min + radius: 60 steps away.  The choice made here is to MOVE THE START, by PBF_THROWN_SHIFT = 0.05 towards the x = 0 and y = 0
+    planes (the lowest coordinate is then 0.035, 0.01 above the planes), and keep the 4 m/s: the planes are reached from step 10 of 30."""
+    if kind == "clamp_thrown":
+        cfg = scenes.get("pbf_tiny_clamp")
+        pos, vel = cs.clamp_thrown(cfg)
+        return cfg, 30, ((pos + np.array(PBF_THROWN_SHIFT, dtype=np.float32)).astype(np.float32), vel)
+    cfg = scenes.get("pbf_tiny_clamp" if kind == "clamp_squeezed" else "pbf_tiny_wall")
+    return (cfg, 5, cs.jitter(cfg)) if kind == "wall_jitter" else (cfg, 10, pbf_squeezed(cfg))
+
+
+def check_pbf(kind, ev):
+    """each case exercised what it claims"""
+    print("pbf %s: particles with lambda != 0 per step %s; particle coordinates on a clamp plane %d; max |v| of phase 2 per step %s; particles "
+          "whose cell changed inside a step %s" % (kind, ev["lambda_active"], ev["on_plane"], ["%.3g" % v for v in ev["xsph_max"]], ev["cell_changes"]))
+    if kind.endswith("squeezed"):
+        assert ev["lambda_active"][0] > 0, "the density constraint is not active at step 1: lambda / delta_pos not exercised"
+    if kind == "clamp_thrown":
+        assert ev["on_plane"] > 0, "no particle ever sat on a clamp plane: the clamp branch did nothing"
+    if kind == "wall_jitter":
+        assert max(ev["xsph_max"]) > 0, "the viscosity sum of update_all_pos was zero throughout"
+    # "old cells, new distances" (convention 3) is observable only where a particle leaves its cell inside a step: every case has some
+    assert sum(ev["cell_changes"]) > 0, "no particle changed its cell inside a step"
+
+
+@pytest.mark.parametrize("kind", PBF_KINDS)
+def test_pbf_steps(kind):
+    """pbf_solver.step (pbf_solver.py:26-187): rho, pbf_lambda, delta_pos, pos, vel on raw bits after every step"""
+    cfg, steps, state = pbf_case(kind)
+    check_pbf(kind, rc.compare_run(cfg, steps, [rc.OracleSide], state=state))
+
+
+def test_pbf_compute_all_rho_alone():
+    """solver_base.compute_all_rho with PBF's poly6 callbacks (solver_base.py:41-51, pbf_solver.py:166-174) after 3 squeezed steps: rho equal,
+    pbf_lambda, delta_pos, pos and vel untouched on both sides"""
+    cfg = scenes.get("pbf_tiny_wall")
+    ev = rc.compare_run(cfg, 3, [rc.OracleSide], state=pbf_squeezed(cfg), density_after=True)
+    assert ev["lambda_active"][-1] > 0, "pbf_lambda is all zero: 'untouched' would prove nothing"
+
+
+# ---- two checks of the PBF restatement's kernel functions that depend on no reading of pbf_solver.py (f64) ---------------------------------
+
+
+def test_poly_kernel_integrates_to_one():
+    """the poly6 kernel is normalised: 4 pi int_0^h W(r) r^2 dr = 1 (composite Simpson, 2000 intervals: the integrand is a polynomial of degree
+    8, the quadrature error ~1e-13; the f32 constants 315 and 64 pi inside poly_kernel are good to 6e-8)"""
+    from second_restatement_pbf import poly_kernel
+    h = np.float64(0.1)
+    n = 2000
+    r = np.linspace(0.0, float(h), n + 1)
+    w = poly_kernel(r, h)
+    assert w.dtype == np.float64
+    f = 4 * math.pi * w * r * r
+    simpson = np.ones(n + 1)
+    simpson[1:-1:2], simpson[2:-1:2] = 4, 2
+    total = float((f * simpson).sum() * (float(h) / n) / 3)
+    print("integral of poly_kernel over the ball: 1 + %.3e" % (total - 1))
+    assert abs(total - 1) <= 1e-6
+    assert poly_kernel(np.float64(0.1000001), h) == 0 and poly_kernel(np.float32(0.2), np.float32(0.1)) == 0
+
+
+def test_spiky_kernel_derivative_is_the_gradient_of_the_spiky_kernel():
+    """d/dr of 15 (1 - q)^3 / (pi h^3) (solver_base.py:105-111) by central differences, at ten radii inside (0, h), along three directions;
+    exactly zero at r = 0 and for q > 1"""
+    from second_restatement_pbf import spiky_kernel_derivative
+    h = np.float64(0.1)
+
+    def spiky(r):
+        return 15 * (1 - r / h) ** 3 / (math.pi * h ** 3)
+
+    eps = 1e-6 * float(h)        # truncation eps^2 / 6 times the third derivative: relative 1e-9 or less at these radii; rounding ~1e-16 / 1e-6
+    worst = 0.0
+    for direction in ([1.0, 0.0, 0.0], [0.0, -1.0, 0.0], [0.6, 0.0, 0.8]):
+        n = np.array(direction)
+        for r in np.linspace(0.05, 0.95, 10) * float(h):
+            g = spiky_kernel_derivative((n * r)[None, :], h)[0]
+            assert g.dtype == np.float64
+            fd = (spiky(r + eps) - spiky(r - eps)) / (2 * eps)
+            rel = float(np.abs(g - fd * n).max() / abs(fd))
+            worst = max(worst, rel)
+            assert rel <= 1e-6, (direction, r, g, fd)
+    print("spiky_kernel_derivative against the central difference: worst relative error %.3e" % worst)
+    zero = spiky_kernel_derivative(np.array([[0.0, 0.0, 0.0], [0.1000001, 0.0, 0.0], [0.08, 0.08, 0.0]]), h)
+    assert np.array_equal(zero, np.zeros((3, 3)))
+    zero32 = spiky_kernel_derivative(np.array([[0.0, 0.0, 0.0], [0.0, 0.11, 0.0]], dtype=np.float32), np.float32(0.1))
+    assert zero32.dtype == np.float32 and np.array_equal(zero32, np.zeros((2, 3), dtype=np.float32))
+
+
+def pbf_rho_f64(cfg, pos, wall_pos, wall_vol):
+    """rho of compute_all_rho with the poly6 callbacks as a plain f64 all-pairs sum (no cells, no order): (rho, K, sum |t_j|) per particle,
+    K = the number of nonzero terms of the particle's two sums, t_j = the f64 terms m W(r_ij) and rho_0 V_b W(r_ib)"""
+    r = cfg["scene"]["particle_radius"]
+    h, m = 4 * r, 1000 * r ** 3 * 8
+    k = 315 / (64 * math.pi * h ** 3)
+    p, w = np.asarray(pos, dtype=np.float64), np.asarray(wall_pos, dtype=np.float64)
+
+    def kernel(a, b):
+        q = np.sqrt(((a[:, None, :] - b[None, :, :]) ** 2).sum(-1)) / h
+        return np.where(q <= 1, k * (1 - q * q) ** 3, 0.0)
+
+    tf = m * kernel(p, p)
+    np.fill_diagonal(tf, 0.0)
+    tw = 1000.0 * np.asarray(wall_vol, dtype=np.float64)[None, :] * kernel(p, w)
+    return 0.001 + tf.sum(1) + tw.sum(1), (tf != 0).sum(1) + (tw != 0).sum(1), np.abs(tf).sum(1) + np.abs(tw).sum(1)
+
+
+PBF_RHO_ROUNDINGS = 10
+
+
+def check_pbf_rho_bound(cfg, pos, wall_pos, wall_vol, rho32, who):
+    """|rho32 - rho64| <= (K + 10) 2^-24 sum |t_j| per particle: an f32 sum of K terms in any order is within (K - 1) u sum |t_j| of the exact
+    sum of its terms (u = 2^-24), and each f32 term carries about ten roundings (the norm's subtractions, squares, additions and square
+    root; r / h; q * q; 1 - q2; the two products of the cube; the products with the constant, with m or V_b and rho_0) -- a derived bound, not
+    a measured one.  The second restatement's own rho uses 0.2 of it at worst on the jittered wall state, so the constant 10 stands."""
+    rho64, K, tot = pbf_rho_f64(cfg, pos, wall_pos, wall_vol)
+    err = np.abs(np.asarray(rho32, dtype=np.float64) - rho64)
+    bound = (K + PBF_RHO_ROUNDINGS) * 2.0 ** -24 * tot
+    print("%s: rho against the f64 all-pairs poly6 sum: terms per particle %d..%d, worst error / bound %.3f" % (who, K.min(), K.max(), float((err / bound).max())))
+    assert K.min() > 0
+    bad = np.flatnonzero(err > bound)
+    assert len(bad) == 0, (who, len(bad), int(bad[0]), float(err[bad[0]]), float(bound[bad[0]]))
+
+
+def test_pbf_rho_of_the_restatement_within_the_f64_bound():
+    """before the library is held to check_pbf_rho_bound (test_second_restatement_gpu.py): the second restatement's f32 rho, bit-equal to what
+    the GPU must produce, satisfies it for every particle of the jittered wall state"""
+    from second_restatement_pbf import PbfSolver
+    cfg = scenes.get("pbf_tiny_wall")
+    s = PbfSolver(cfg)
+    s.pos, s.vel = cs.jitter(cfg)
+    s.density_only()
+    check_pbf_rho_bound(cfg, s.pos, s.sc.wall_pos, s.sc.wall_vol, s.rho, "second restatement")
