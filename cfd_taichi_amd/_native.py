@@ -40,7 +40,7 @@ EXPORTS = [
     "sph_abi_version", "sph_set_comm_sized", "sph_create", "sph_destroy", "sph_get_sizes", "sph_last_error", "sph_upload", "sph_download",
     "sph_step_wcsph", "sph_step_dfsph", "sph_step_pcisph", "sph_step_iisph", "sph_step_pbf", "sph_build_neighbors", "sph_compute_density", "sph_compute_alpha",
     "sph_get_scalar", "sph_set_scalar", "sph_synchronize", "sph_overrides", "sph_profile_enable", "sph_profile_reset", "sph_profile_kernel_count",
-    "sph_profile_kernel_name", "sph_profile_get", "sph_selftest_math", "sph_selftest_wave", "sph_tune_time",
+    "sph_profile_kernel_name", "sph_profile_get", "sph_selftest_math", "sph_selftest_wave", "sph_selftest_stage", "sph_tune_time",
     "sph_set_comm", "sph_rccl_unique_id", "sph_rccl_attach", "sph_rccl_selftest", "sph_get_stream", "sph_plan_slabs", "sph_replan_slabs", "sph_slab_set_overlap", "sph_slab_info", "sph_comm_stats", "sph_download_local", "sph_download_ids",
     "sph_create_rigid", "sph_rigid_step", "sph_rigid_set_active", "sph_rigid_init_data",
 ]
@@ -172,7 +172,7 @@ CORE_EXPORTS = [
 ]
 # entry points added without a change of SPH_ABI_VERSION (no struct grew, no signature changed): bound where the library has them, and a call on a
 # library without them raises SphError(SPH_E_STATE)
-OPTIONAL_EXPORTS = ["sph_rigid_set_active", "sph_rigid_init_data"]
+OPTIONAL_EXPORTS = ["sph_rigid_set_active", "sph_rigid_init_data", "sph_selftest_stage"]
 
 
 def _bind_core(lib):
@@ -251,6 +251,8 @@ def load(build_if_missing=True):
     lib.sph_profile_get.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]
     lib.sph_selftest_math.argtypes = [ci, ci, vp, vp, vp, ctypes.c_size_t]
     lib.sph_selftest_wave.argtypes = [ci, ci, vp, vp, ctypes.c_size_t]
+    if hasattr(lib, "sph_selftest_stage"):
+        lib.sph_selftest_stage.argtypes = [vp, ci, ci, ci, ci, ci, vp, ci, vp, vp, vp, vp, ctypes.c_size_t, vp, ctypes.POINTER(ci)]
     lib.sph_tune_time.argtypes = [vp, ci, ctypes.c_uint, ci, ctypes.POINTER(ctypes.c_double)]
     lib.sph_set_comm.argtypes = [vp, ctypes.POINTER(SphComm)]
     lib.sph_set_comm_sized.argtypes = [vp, ctypes.POINTER(SphComm), ctypes.c_size_t]
@@ -607,3 +609,30 @@ def selftest_wave(op, values, device=0):
     if rc != SPH_OK:
         raise SphError(rc, (lib.sph_last_error(None) or b"").decode())
     return out
+
+
+STAGE_CAP_MAX = 2560          # csrc/sph_kernels.h kStageCapMax
+STAGE_LAYOUTS = {"f4": 0, "f4_scaled": 1, "ps": 2, "ps_scaled": 3, "pv": 4, "pv_scaled": 5, "f4s": 6, "f4src": 7}
+STAGE_CHECKS = {"none": 0, "with": 1, "first": 2}
+
+
+def selftest_stage(layout, check, runs, A, B, S, changed, use_pre=False, not_staged=False, empty_idle=False, handle=None):
+    """(image, verdict) of the LDS staging routine on one workgroup's plan (see sph_selftest_stage): image[e] = the six floats of staged
+    element e, for all STAGE_CAP_MAX slots.  empty_idle: the verdict the call site names for a staged set of no particles is "idle"; handle: the raw
+    handle whose device runs it (None: device 0)."""
+    lib = load()
+    if not hasattr(lib, "sph_selftest_stage"):
+        raise SphError(SPH_E_STATE, "this library has no sph_selftest_stage")
+    runs = np.ascontiguousarray(runs, dtype=np.uint32).reshape(-1, 2)
+    A = np.ascontiguousarray(A, dtype=np.float32).reshape(-1, 4)
+    B = np.ascontiguousarray(B, dtype=np.float32).reshape(-1, 4)
+    S = np.ascontiguousarray(S, dtype=np.float32)
+    changed = np.ascontiguousarray(changed, dtype=np.uint8)
+    assert len(A) == len(B) == len(S) == len(changed)
+    out = np.zeros((STAGE_CAP_MAX, 6), dtype=np.float32)
+    verdict = ctypes.c_int(-1)
+    rc = lib.sph_selftest_stage(handle, STAGE_LAYOUTS[layout], STAGE_CHECKS[check], int(empty_idle), int(use_pre), int(not_staged), runs.ctypes.data, len(runs),
+                                A.ctypes.data, B.ctypes.data, S.ctypes.data, changed.ctypes.data, len(A), out.ctypes.data, ctypes.byref(verdict))
+    if rc != SPH_OK:
+        raise SphError(rc, (lib.sph_last_error(handle) or b"").decode())
+    return out, verdict.value

@@ -1573,8 +1573,8 @@ __global__ __launch_bounds__(kBlock) void k_finalize_max(const float *__restrict
 //   WCSPH: writes Pout = (pos, rho), Vout = (vel, p/rho^2), rho[], pressure[]
 //   DFSPH: writes Pout = (pos, (warm_k/dt)/rho) for the warm start, Vout = (vel, rho), rho[], alpha[]
 // ======================================================================================
-// the workgroup's operand array through stage_src into LDS (see the staging plan in k_build_nl); returns false when this
-// workgroup keeps global indices.  Uniform per workgroup; every thread of the workgroup must call it.
+// the workgroup's operand arrays through stage_src into LDS (see the staging plan in k_build_nl; stage_operands below): kNotStaged when this
+// workgroup keeps global indices.
 // SCALED: the positions are staged multiplied by 2^32 (exact; see norm3_scaled in sph_device.h), .w unchanged
 // The staged set of a workgroup is described by cell runs (k_build_nl): stage_cnt[blk] = particles | runs << 16 (-1: not staged),
 // stage_runs[blk][r] = (first sorted index, local base | count << 16).  stage_expand turns them into the flat list s_idx[e] = sorted
@@ -1585,7 +1585,8 @@ __global__ __launch_bounds__(kBlock) void k_finalize_max(const float *__restrict
 // thread's operands are requested in one batch, then the LDS stores (kStageBatch elements per thread and trip, two trips cover the
 // largest capacity; a clamped index keeps the loads branch-free so that the compiler leaves them in one batch).
 constexpr int kStageBatch = 7;          // 7 x 256 = 1792 >= the default capacity of 1664: one trip
-constexpr int kStageTrips = 2;          // 2 x 1792 >= the largest capacity (2560)
+constexpr int kStageTrips = 2;          // 2 x 1792 >= the largest capacity
+constexpr int kStageCapMax = 2560;      // x 24 B (StagePV) = 60 KB: below the 64 KB of LDS a kernel gets without opting in
 __device__ __forceinline__ int stage_expand(const uint2 *__restrict__ stage_runs, const int *__restrict__ stage_cnt, int blk, uint32_t *__restrict__ s_idx,
                                             const StagePre &pre = kNoPre)
 {
@@ -1631,7 +1632,7 @@ __device__ __forceinline__ bool stage_sources_flagged(const uint2 *__restrict__ 
 }
 
 struct StageIdx { uint32_t j[kStageTrips][kStageBatch]; };
-// this thread's indices of all trips, then the barrier after which s_idx may be overwritten
+// this thread's indices of all trips (stage_operands then synchronises before operands may overwrite an aliased s_idx)
 __device__ __forceinline__ StageIdx stage_take(const uint32_t *__restrict__ s_idx, int nst)
 {
     StageIdx x;
@@ -1645,142 +1646,151 @@ __device__ __forceinline__ StageIdx stage_take(const uint32_t *__restrict__ s_id
 #pragma unroll
         for (int u = 0; u < kStageBatch; ++u) x.j[t][u] = s_idx[min((int)threadIdx.x + (t * kStageBatch + u) * kBlock, nst - 1)];
     }
-    __syncthreads();
     return x;
 }
+// ---- the staging routine: ONE driver for every staged sweep, the differences in a layout type ---------------------------------------
+// A layout says where its operands come from and how a staged element lies in LDS.  Its loads are split in two:
+//   load_key(j)   the part that holds the KEY a check examines; hot(key) says whether it is set.  kKeyStored: the copy needs the key too,
+//                 so it is loaded without a check as well
+//   load_rest(j)  everything else
+// and store(e, key, rest) writes staged element e.  has_key() is true, except for a StagePV without `changed` bytes: only StagePV may lack
+// its key, and only under kCheckWith, where the routine then neither reads a key nor votes and answers kStaged (kCheckFirst needs the bytes).
+// kBytes is the LDS per staged particle -- the launch sites size the dynamic LDS with it (sweep_lds) -- and second() carves the layout's
+// second array behind the first.
+//   StageF4<SCALED>   A -> s_A = A (xyz * 2^32 if SCALED)                              key: A.w
+//   StagePS<SCALED>   A, S -> s_A = (A.xyz [* 2^32], S)                                key: S     (kr_split handles: k / rho from its own array)
+//   StagePV<SCALED>   A, B -> s_A = (A.xyz [* 2^32], B.x), s_B = (B.y, B.z)            key: changed[j], a byte array of its own, not stored
+//   StageF4S          A, S -> s_A = A, s_S = S                                         key: A.w
+//   StageF4Src        A -> s_A = A; the index list is KEPT in s_src (a second operand is gathered from memory through it): nothing aliases
+struct StageNone {};
+template <bool SCALED>
+__device__ __forceinline__ float4 stage_pos(const float4 a, float w)
+{
+    return SCALED ? make_float4(a.x * 0x1p32f, a.y * 0x1p32f, a.z * 0x1p32f, w) : make_float4(a.x, a.y, a.z, w);
+}
 template <bool SCALED = false>
-__device__ __forceinline__ bool stage_operand(const Consts &c, float4 *__restrict__ s_A, const float4 *__restrict__ A,
-                                              const uint2 *__restrict__ stage_runs, const int *__restrict__ stage_cnt, int blk, const StagePre &pre = kNoPre)
-{
-    const int nst = stage_expand(stage_runs, stage_cnt, blk, reinterpret_cast<uint32_t *>(s_A), pre);
-    if (nst < 0) return false;
-    if (nst == 0) return true;                              // a workgroup of ghosts only (slab handles): nothing to stage, uniform
-    const StageIdx x = stage_take(reinterpret_cast<const uint32_t *>(s_A), nst);
-#pragma unroll
-    for (int t = 0; t < kStageTrips; ++t) {
-        const int base = threadIdx.x + t * kStageBatch * kBlock;
-        if (t * kStageBatch * kBlock >= nst) break;
-        float4 a[kStageBatch];
-#pragma unroll
-        for (int u = 0; u < kStageBatch; ++u) a[u] = A[x.j[t][u]];
-#pragma unroll
-        for (int u = 0; u < kStageBatch; ++u)
-            if (base + u * kBlock < nst)
-                s_A[base + u * kBlock] = SCALED ? make_float4(a[u].x * 0x1p32f, a[u].y * 0x1p32f, a[u].z * 0x1p32f, a[u].w) : a[u];
+struct StageF4 {
+    float4 *s_A; const float4 *A;
+    static constexpr size_t kBytes = sizeof(float4);
+    static constexpr bool kIdxAliased = true, kKeyStored = true;
+    using Key = float4; using Rest = StageNone;
+    __device__ __forceinline__ uint32_t *idx() const { return reinterpret_cast<uint32_t *>(s_A); }
+    __device__ __forceinline__ Key load_key(uint32_t j) const { return A[j]; }
+    __device__ __forceinline__ Rest load_rest(uint32_t) const { return StageNone{}; }
+    __device__ __forceinline__ bool has_key() const { return true; }
+    __device__ __forceinline__ bool hot(const Key &a) const { return a.w != 0.f; }
+    __device__ __forceinline__ void store(int e, const Key &a, Rest) const { s_A[e] = stage_pos<SCALED>(a, a.w); }
+};
+struct StageF4Src : StageF4<false> {
+    uint32_t *s_src;
+    static constexpr size_t kBytes = sizeof(float4) + sizeof(uint32_t);
+    static constexpr bool kIdxAliased = false;
+    static __device__ __forceinline__ uint32_t *second(float4 *s_operand, int cap) { return reinterpret_cast<uint32_t *>(s_operand + cap); }
+    __device__ __forceinline__ uint32_t *idx() const { return s_src; }
+};
+template <bool SCALED = false>
+struct StagePS {
+    float4 *s_A; const float4 *A; const float *S;
+    static constexpr size_t kBytes = sizeof(float4);
+    static constexpr bool kIdxAliased = true, kKeyStored = true;
+    using Key = float; using Rest = float4;
+    __device__ __forceinline__ uint32_t *idx() const { return reinterpret_cast<uint32_t *>(s_A); }
+    __device__ __forceinline__ Key load_key(uint32_t j) const { return S[j]; }
+    __device__ __forceinline__ Rest load_rest(uint32_t j) const { return A[j]; }
+    __device__ __forceinline__ bool has_key() const { return true; }
+    __device__ __forceinline__ bool hot(Key s) const { return s != 0.f; }
+    __device__ __forceinline__ void store(int e, Key s, const Rest &a) const { s_A[e] = stage_pos<SCALED>(a, s); }
+};
+struct StagePair { float4 a, b; };
+template <bool SCALED = false>
+struct StagePV {
+    float4 *s_A; float2 *s_B; const float4 *A, *B;
+    const unsigned char *changed;         // read under a check only (kKeyStored = false).  kCheckWith takes nullptr: no bytes, no vote, kStaged
+    static constexpr size_t kBytes = sizeof(float4) + sizeof(float2);
+    static constexpr bool kIdxAliased = true, kKeyStored = false;
+    using Key = unsigned char; using Rest = StagePair;
+    static __device__ __forceinline__ float2 *second(float4 *s_operand, int cap) { return reinterpret_cast<float2 *>(s_operand + cap); }
+    __device__ __forceinline__ uint32_t *idx() const { return reinterpret_cast<uint32_t *>(s_A); }
+    __device__ __forceinline__ Key load_key(uint32_t j) const { return changed[j]; }
+    __device__ __forceinline__ Rest load_rest(uint32_t j) const { return StagePair{A[j], B[j]}; }
+    __device__ __forceinline__ bool has_key() const { return changed != nullptr; }
+    __device__ __forceinline__ bool hot(Key f) const { return f != 0; }
+    __device__ __forceinline__ void store(int e, Key, const Rest &r) const
+    {
+        s_A[e] = stage_pos<SCALED>(r.a, r.b.x);
+        s_B[e] = make_float2(r.b.y, r.b.z);
     }
-    __syncthreads();
-    return true;
-}
+};
+struct StageF4S {
+    float4 *s_A; float *s_S; const float4 *A; const float *S;
+    static constexpr size_t kBytes = sizeof(float4) + sizeof(float);
+    static constexpr bool kIdxAliased = true, kKeyStored = true;
+    using Key = float4; using Rest = float;
+    static __device__ __forceinline__ float *second(float4 *s_operand, int cap) { return reinterpret_cast<float *>(s_operand + cap); }
+    __device__ __forceinline__ uint32_t *idx() const { return reinterpret_cast<uint32_t *>(s_A); }
+    __device__ __forceinline__ Key load_key(uint32_t j) const { return A[j]; }
+    __device__ __forceinline__ Rest load_rest(uint32_t j) const { return S[j]; }
+    __device__ __forceinline__ bool has_key() const { return true; }
+    __device__ __forceinline__ bool hot(const Key &a) const { return a.w != 0.f; }
+    __device__ __forceinline__ void store(int e, const Key &a, Rest s) const { s_A[e] = a; s_S[e] = s; }
+};
 
-// stage_operand<SCALED> that also reports whether any staged element has .w != 0: 1 = staged, 2 = staged and every .w is 0 (the caller's
-// pair loop would add only +-0: see stage_sources_flagged), 0 = not staged.  For handles whose k / rho travels inside the (pos, k / rho)
-// float4 (slab handles, SPH_KR_SPLIT=0): the verdict comes with the copy, so a zero tile saves its pair loop, not its gathers.
-template <bool SCALED>
-__device__ __forceinline__ int stage_operand_w_checked(const Consts &c, float4 *__restrict__ s_A, const float4 *__restrict__ A,
-                                                       const uint2 *__restrict__ stage_runs, const int *__restrict__ stage_cnt, int blk, const StagePre &pre = kNoPre)
+// which workgroup's plan, and what the caller already fetched of it (StagePre)
+struct StagePlan { const uint2 *runs; const int *cnt; int blk; StagePre pre = kNoPre; };
+// kCheckNone   copy, barrier: no vote
+// kCheckWith   the keys come with the copy: everything is staged, and the closing barrier says whether any key is set (a zero tile saves
+//              its pair loop, not its gathers)
+// kCheckFirst  two dependent phases: the keys are requested and voted on FIRST and stay in registers; only a workgroup with a key set
+//              requests the rest (one more round trip for it) -- for the others nothing is copied
+enum StageCheck { kCheckNone, kCheckWith, kCheckFirst };
+// kStagedIdle: staged (kCheckFirst: NOT copied), and no staged element's key is set.  Callers that want a bool test != kNotStaged.
+enum StageVerdict { kNotStaged = 0, kStaged = 1, kStagedIdle = 2 };
+// Uniform per workgroup; every thread of the workgroup must call it.  EMPTY: the verdict for a staged set of no particles (a workgroup of
+// ghosts only, slab handles) -- nothing is staged and no key is set, yet what follows from kStagedIdle differs per sweep: each checked
+// call site names its own.
+template <StageCheck CHECK = kCheckNone, StageVerdict EMPTY = kStaged, class L>
+__device__ __forceinline__ StageVerdict stage_operands(const L lay, const StagePlan &plan)
 {
-    const int nst = stage_expand(stage_runs, stage_cnt, blk, reinterpret_cast<uint32_t *>(s_A), pre);
-    if (nst < 0) return 0;
-    if (nst == 0) return 2;                                 // a workgroup of ghosts only: nothing staged, nothing to add
-    const StageIdx x = stage_take(reinterpret_cast<const uint32_t *>(s_A), nst);
+    const int nst = stage_expand(plan.runs, plan.cnt, plan.blk, lay.idx(), plan.pre);
+    if (nst < 0) return kNotStaged;
+    if (nst == 0) return EMPTY;                             // uniform
+    const StageIdx x = stage_take(lay.idx(), nst);
+    if (L::kIdxAliased) __syncthreads();                    // from here on the operands may overwrite the list
+    typename L::Key k[kStageTrips][kStageBatch] = {};
     int any = 0;
+    if (CHECK == kCheckFirst) {
+#pragma unroll
+        for (int t = 0; t < kStageTrips; ++t) {
+            if (t * kStageBatch * kBlock >= nst) break;
+#pragma unroll
+            for (int u = 0; u < kStageBatch; ++u) k[t][u] = lay.load_key(x.j[t][u]);             // (clamped indices: duplicates of valid slots)
+#pragma unroll
+            for (int u = 0; u < kStageBatch; ++u) any |= lay.hot(k[t][u]);
+        }
+        if (!__syncthreads_or(any)) return kStagedIdle;
+    }
 #pragma unroll
     for (int t = 0; t < kStageTrips; ++t) {
         const int base = threadIdx.x + t * kStageBatch * kBlock;
         if (t * kStageBatch * kBlock >= nst) break;
-        float4 a[kStageBatch];
+        typename L::Rest r[kStageBatch];
 #pragma unroll
-        for (int u = 0; u < kStageBatch; ++u) a[u] = A[x.j[t][u]];
+        for (int u = 0; u < kStageBatch; ++u) {
+            r[u] = lay.load_rest(x.j[t][u]);
+            if (CHECK == kCheckWith) k[t][u] = lay.has_key() ? lay.load_key(x.j[t][u]) : typename L::Key{};
+            else if (CHECK == kCheckNone && L::kKeyStored) k[t][u] = lay.load_key(x.j[t][u]);
+        }
+        if (CHECK == kCheckWith) {
 #pragma unroll
-        for (int u = 0; u < kStageBatch; ++u)
-            if (base + u * kBlock < nst) {
-                any |= a[u].w != 0.f;
-                s_A[base + u * kBlock] = SCALED ? make_float4(a[u].x * 0x1p32f, a[u].y * 0x1p32f, a[u].z * 0x1p32f, a[u].w) : a[u];
-            }
-    }
-    return __syncthreads_or(any) ? 1 : 2;
-}
-
-// kr_split handles: positions from the step's position array and the per-sweep scalar k / rho from its own 4-byte array (the sweeps
-// then write 4 B per particle for their neighbours instead of a fresh (pos, k / rho) float4: 12 MB less written per launch at 1 M)
-__device__ __forceinline__ bool stage_operand_ps_scaled(const Consts &c, float4 *__restrict__ s_A, const float4 *__restrict__ A, const float *__restrict__ S,
-                                                        const uint2 *__restrict__ stage_runs, const int *__restrict__ stage_cnt, int blk, const StagePre &pre = kNoPre)
-{
-    const int nst = stage_expand(stage_runs, stage_cnt, blk, reinterpret_cast<uint32_t *>(s_A), pre);
-    if (nst < 0) return false;
-    if (nst == 0) return true;
-    const StageIdx x = stage_take(reinterpret_cast<const uint32_t *>(s_A), nst);
-#pragma unroll
-    for (int t = 0; t < kStageTrips; ++t) {
-        const int base = threadIdx.x + t * kStageBatch * kBlock;
-        if (t * kStageBatch * kBlock >= nst) break;
-        float4 a[kStageBatch]; float sc[kStageBatch];
-#pragma unroll
-        for (int u = 0; u < kStageBatch; ++u) { a[u] = A[x.j[t][u]]; sc[u] = S[x.j[t][u]]; }
+            for (int u = 0; u < kStageBatch; ++u) any |= lay.hot(k[t][u]);                       // (clamped indices: duplicates of valid slots)
+        }
 #pragma unroll
         for (int u = 0; u < kStageBatch; ++u)
-            if (base + u * kBlock < nst) s_A[base + u * kBlock] = make_float4(a[u].x * 0x1p32f, a[u].y * 0x1p32f, a[u].z * 0x1p32f, sc[u]);
+            if (base + u * kBlock < nst) lay.store(base + u * kBlock, k[t][u], r[u]);
     }
+    if (CHECK == kCheckWith && lay.has_key()) return __syncthreads_or(any) ? kStaged : kStagedIdle;
     __syncthreads();
-    return true;
-}
-
-// The same with the scalars requested first and examined: returns 0 = not staged, 1 = staged, 2 = staged set holds no scalar != 0 (nothing
-// was copied; the correction sweep of the density loop has nothing to do, see stage_sources_flagged).  One more round trip than the
-// plain form for the workgroups that do have work (the positions are requested after the verdict).  (Asking the per-wave flags of the
-// residual sweep instead of the staged scalars themselves -- no expansion, no gather -- was measured: fewer tiles return, 30.5 -> 35.4 us.)
-template <bool SCALED>
-__device__ __forceinline__ int stage_operand_ps_checked(const Consts &c, float4 *__restrict__ s_A, const float4 *__restrict__ A, const float *__restrict__ S,
-                                                        const uint2 *__restrict__ stage_runs, const int *__restrict__ stage_cnt, int blk, const StagePre &pre = kNoPre)
-{
-    const int nst = stage_expand(stage_runs, stage_cnt, blk, reinterpret_cast<uint32_t *>(s_A), pre);
-    if (nst < 0) return 0;
-    if (nst == 0) return 1;
-    const StageIdx x = stage_take(reinterpret_cast<const uint32_t *>(s_A), nst);
-    float sc[kStageTrips][kStageBatch];
-    int any = 0;
-#pragma unroll
-    for (int t = 0; t < kStageTrips; ++t) {
-        if (t * kStageBatch * kBlock >= nst) break;
-#pragma unroll
-        for (int u = 0; u < kStageBatch; ++u) sc[t][u] = S[x.j[t][u]];                      // (clamped indices: duplicates of valid slots)
-#pragma unroll
-        for (int u = 0; u < kStageBatch; ++u) any |= sc[t][u] != 0.f;
-    }
-    if (!__syncthreads_or(any)) return 2;
-#pragma unroll
-    for (int t = 0; t < kStageTrips; ++t) {
-        const int base = threadIdx.x + t * kStageBatch * kBlock;
-        if (t * kStageBatch * kBlock >= nst) break;
-        float4 a[kStageBatch];
-#pragma unroll
-        for (int u = 0; u < kStageBatch; ++u) a[u] = A[x.j[t][u]];
-#pragma unroll
-        for (int u = 0; u < kStageBatch; ++u)
-            if (base + u * kBlock < nst)
-                s_A[base + u * kBlock] = SCALED ? make_float4(a[u].x * 0x1p32f, a[u].y * 0x1p32f, a[u].z * 0x1p32f, sc[t][u]) : make_float4(a[u].x, a[u].y, a[u].z, sc[t][u]);
-    }
-    __syncthreads();
-    return 1;
-}
-
-// two-operand variant: A staged in LDS, the global index of every staged element next to it (B is gathered from HBM/L2 through it)
-__device__ __forceinline__ bool stage_operand_src(const Consts &c, float4 *__restrict__ s_A, uint32_t *__restrict__ s_src,
-                                                  const float4 *__restrict__ A, const uint2 *__restrict__ stage_runs,
-                                                  const int *__restrict__ stage_cnt, int blk)
-{
-    const int nst = stage_expand(stage_runs, stage_cnt, blk, s_src);      // the list stays: B is gathered through it
-    if (nst < 0) return false;
-    for (int base = threadIdx.x; base < nst; base += kStageBatch * kBlock) {
-        float4 a[kStageBatch];
-#pragma unroll
-        for (int u = 0; u < kStageBatch; ++u) a[u] = A[s_src[min(base + u * kBlock, nst - 1)]];
-#pragma unroll
-        for (int u = 0; u < kStageBatch; ++u)
-            if (base + u * kBlock < nst) s_A[base + u * kBlock] = a[u];
-    }
-    __syncthreads();
-    return true;
+    return kStaged;
 }
 // staged walkers: fluid entries are LOCAL indices into the staged arrays, tagged rigid entries stay global (rv.RP)
 template <bool RIGID, bool SCALED = false, class Body>
@@ -1841,82 +1851,6 @@ __device__ __forceinline__ void for_staged_nbrs_pv(const uint32_t *__restrict__ 
     }
 }
 
-// both operands of the residual sweeps staged: (x, y, z, vx) and (vy, vz) -- 24 B per staged particle
-template <bool SCALED = false>
-__device__ __forceinline__ bool stage_operand_pv(const Consts &c, float4 *__restrict__ s_A, float2 *__restrict__ s_B,
-                                                 const float4 *__restrict__ A, const float4 *__restrict__ B,
-                                                 const uint2 *__restrict__ stage_runs, const int *__restrict__ stage_cnt, int blk, const StagePre &pre = kNoPre,
-                                                 const unsigned char *__restrict__ changed = nullptr, int *any_changed = nullptr)
-{
-    // changed (optional): the per-particle bytes of the density loop's check, fetched with the operands; *any_changed = is one of the staged set's set?
-    const int nst = stage_expand(stage_runs, stage_cnt, blk, reinterpret_cast<uint32_t *>(s_A), pre);
-    if (nst < 0) return false;
-    if (nst == 0) return true;                              // a workgroup of ghosts only (slab handles): nothing to stage, uniform
-    const StageIdx x = stage_take(reinterpret_cast<const uint32_t *>(s_A), nst);
-    int any = 0;
-#pragma unroll
-    for (int t = 0; t < kStageTrips; ++t) {
-        const int base = threadIdx.x + t * kStageBatch * kBlock;
-        if (t * kStageBatch * kBlock >= nst) break;
-        float4 a[kStageBatch], b[kStageBatch];
-        unsigned char f[kStageBatch];
-#pragma unroll
-        for (int u = 0; u < kStageBatch; ++u) { a[u] = A[x.j[t][u]]; b[u] = B[x.j[t][u]]; f[u] = changed ? changed[x.j[t][u]] : (unsigned char)0; }
-#pragma unroll
-        for (int u = 0; u < kStageBatch; ++u) any |= f[u];                                   // (clamped indices: duplicates of valid slots)
-#pragma unroll
-        for (int u = 0; u < kStageBatch; ++u)
-            if (base + u * kBlock < nst) {
-                const int e = base + u * kBlock;
-                s_A[e] = SCALED ? make_float4(a[u].x * 0x1p32f, a[u].y * 0x1p32f, a[u].z * 0x1p32f, b[u].x) : make_float4(a[u].x, a[u].y, a[u].z, b[u].x);
-                s_B[e] = make_float2(b[u].y, b[u].z);
-            }
-    }
-    if (changed) *any_changed = __syncthreads_or(any);
-    else __syncthreads();
-    return true;
-}
-// The same with a look at a per-particle byte first: returns 0 = not staged, 1 = staged, 2 = no staged particle has its byte set (nothing was
-// copied).  The residual sweep of the density loop asks it with the bytes the last correction sweep wrote ("this particle's v* changed"):
-// the second, exact level of the change propagation (stage_sources_flagged is the first: per-wave flags, no expansion).
-template <bool SCALED>
-__device__ __forceinline__ int stage_operand_pv_checked(const Consts &c, float4 *__restrict__ s_A, float2 *__restrict__ s_B,
-                                                        const float4 *__restrict__ A, const float4 *__restrict__ B, const unsigned char *__restrict__ changed,
-                                                        const uint2 *__restrict__ stage_runs, const int *__restrict__ stage_cnt, int blk, const StagePre &pre = kNoPre)
-{
-    const int nst = stage_expand(stage_runs, stage_cnt, blk, reinterpret_cast<uint32_t *>(s_A), pre);
-    if (nst < 0) return 0;
-    if (nst == 0) return 1;
-    const StageIdx x = stage_take(reinterpret_cast<const uint32_t *>(s_A), nst);
-    int any = 0;
-#pragma unroll
-    for (int t = 0; t < kStageTrips; ++t) {
-        if (t * kStageBatch * kBlock >= nst) break;
-        unsigned char f[kStageBatch];
-#pragma unroll
-        for (int u = 0; u < kStageBatch; ++u) f[u] = changed[x.j[t][u]];                     // (clamped indices: duplicates of valid slots)
-#pragma unroll
-        for (int u = 0; u < kStageBatch; ++u) any |= f[u];
-    }
-    if (!__syncthreads_or(any)) return 2;
-#pragma unroll
-    for (int t = 0; t < kStageTrips; ++t) {
-        const int base = threadIdx.x + t * kStageBatch * kBlock;
-        if (t * kStageBatch * kBlock >= nst) break;
-        float4 a[kStageBatch], b[kStageBatch];
-#pragma unroll
-        for (int u = 0; u < kStageBatch; ++u) { a[u] = A[x.j[t][u]]; b[u] = B[x.j[t][u]]; }
-#pragma unroll
-        for (int u = 0; u < kStageBatch; ++u)
-            if (base + u * kBlock < nst) {
-                const int e = base + u * kBlock;
-                s_A[e] = SCALED ? make_float4(a[u].x * 0x1p32f, a[u].y * 0x1p32f, a[u].z * 0x1p32f, b[u].x) : make_float4(a[u].x, a[u].y, a[u].z, b[u].x);
-                s_B[e] = make_float2(b[u].y, b[u].z);
-            }
-    }
-    __syncthreads();
-    return 1;
-}
 template <bool RIGID, bool SCALED = false, class Body>
 __device__ __forceinline__ void for_staged_nbrs_pv2(const uint32_t *__restrict__ base, int cnt, const float4 *__restrict__ s_A,
                                                     const float2 *__restrict__ s_B, const RigidView &rv, Body body)
@@ -2035,7 +1969,7 @@ __global__ __launch_bounds__(kBlock) void k_density(Consts c, const float4 *__re
     const int tile = tp.phase == 0 ? xcd_block(blockIdx.x, gridDim.x) : sweep_tile(tp, false);
     if (tile < 0) return;
     SPH_SWEEP_PROLOGUE_G(QUAD, tile, true)
-    const bool staged = STAGED && stage_operand(c, s_operand, P, stage_src, stage_cnt, blk);
+    const bool staged = STAGED && stage_operands(StageF4<>{s_operand, P}, StagePlan{stage_src, stage_cnt, blk}) != kNotStaged;
     float fa[5] = {0.001f, 0.f, 0.f, 0.f, 0.f};              // rho starts at 0.001, solver_base.py:44
     float &rho = fa[0], &sx = fa[1], &sy = fa[2], &sz = fa[3], &sq = fa[4];
     auto pair = [&](const float4 pj, const float4, const uint32_t j) {
@@ -2259,6 +2193,7 @@ __global__ __launch_bounds__(kBlock) void k_correct(Consts c, const float4 *__re
     SPH_SWEEP_PROLOGUE_G(QUAD, tile, true)
     // kr_split: P is the step's position array and k / rho of the neighbours comes from krho[]; else P = (pos, k / rho)
     const bool split = STAGED && c.kr_split;
+    static_assert(StagePS<>::kBytes == StageF4<>::kBytes, "one launch stages either layout: the host sizes the LDS by StagePS");
     // change propagation in the density loop (stage_sources_flagged); with a body in the lists too: its term is V_r rho0 k_i / rho_i grad W, zero with k_i
     const bool track = MODE == CORR_DENS && STAGED && wave_dirty != nullptr;
     // Two-column slab handles store the ghost columns in tiles of their own (slab_cell_order): a tile in which nobody has a list -- ghosts of the
@@ -2272,9 +2207,11 @@ __global__ __launch_bounds__(kBlock) void k_correct(Consts c, const float4 *__re
     }
     bool staged;
     if (track && !direct) {
-        const int verdict = split ? stage_operand_ps_checked<true>(c, s_operand, P, krho, stage_src, stage_cnt, blk, pre)
-                                  : stage_operand_w_checked<true>(c, s_operand, P, stage_src, stage_cnt, blk, pre);
-        if (verdict == 2) {                                                        // every k / rho this tile can see is 0: v* stays
+        // (a staged set of no particles: the split form goes on and computes, the packed form leaves as a zero tile -- as each always did)
+        const StagePlan plan{stage_src, stage_cnt, blk, pre};
+        const int verdict = split ? stage_operands<kCheckFirst, kStaged>(StagePS<true>{s_operand, P, krho}, plan)
+                                  : stage_operands<kCheckWith, kStagedIdle>(StageF4<true>{s_operand, P}, plan);
+        if (verdict == kStagedIdle) {                                                        // every k / rho this tile can see is 0: v* stays
             // (one-column slab handles: a ghost's v* is refreshed from its owner after this sweep and may change behind this rank's back,
             // whatever this rank can see; on two-column handles the inner ghosts are corrected HERE, from the same inputs as on their owner)
             const bool foreign = live && ghost && !c.ghost_walk;
@@ -2283,10 +2220,11 @@ __global__ __launch_bounds__(kBlock) void k_correct(Consts c, const float4 *__re
             if (live) changed8[i] = foreign ? 1 : 0;
             return;
         }
-        staged = verdict == 1;
+        staged = verdict == kStaged;
     } else {
-        staged = STAGED && (split ? stage_operand_ps_scaled(c, s_operand, P, krho, stage_src, stage_cnt, blk, pre)
-                                  : stage_operand<true>(c, s_operand, P, stage_src, stage_cnt, blk, pre));     // positions * 2^32
+        const StagePlan plan{stage_src, stage_cnt, blk, pre};
+        staged = STAGED && (split ? stage_operands(StagePS<true>{s_operand, P, krho}, plan)
+                                  : stage_operands(StageF4<true>{s_operand, P}, plan)) != kNotStaged;     // positions * 2^32
     }
     const float dt = ds->dt;
     const float rho_i = rho[ii];
@@ -2443,21 +2381,24 @@ __global__ __launch_bounds__(kBlock) void k_residual(Consts c, const float4 *__r
         if (flow && threadIdx.x == 0) df.nz[blk] = 0;               // (the ghosts' k / rho is pushed for by the kernel that unpacks it)
         return;
     }
-    float2 *s_v2 = reinterpret_cast<float2 *>(s_operand + c.stage_cap);
+    float2 *s_v2 = StagePV<true>::second(s_operand, c.stage_cap);
+    const StagePlan plan{stage_src, stage_cnt, blk, pre};
     bool staged;
     if (spread && !direct) {       // second level of the change propagation: did the v* of any staged PARTICLE change?  (the flagged waves said "maybe")
-        const int verdict = stage_operand_pv_checked<true>(c, s_operand, s_v2, P, V, changed8, stage_src, stage_cnt, blk, pre);
-        if (verdict == 2) {                                          // (its k / rho stands like an idle tile's)
+        // (a staged set of no particles counts as changed: kStaged, the tile computes)
+        const int verdict = stage_operands<kCheckFirst, kStaged>(StagePV<true>{s_operand, s_v2, P, V, changed8}, plan);
+        if (verdict == kStagedIdle) {                                // (its k / rho stands like an idle tile's)
             if (flow && df.nz[blk] != 0 && threadIdx.x < 64) flow_push(df, my_nbr);
             if (tp.hot && threadIdx.x == 0) tp.hot[blk] = 1;
             return;
         }
-        staged = verdict == 1;
+        staged = verdict == kStaged;
     } else {
         // (a `direct` tile: the bytes of the check ride in the staging batch and say whether it would have passed -- if not, it computes what
-        // stands this once and takes the check again next time)
-        int would = 1;
-        staged = STAGED && stage_operand_pv<true>(c, s_operand, s_v2, P, V, stage_src, stage_cnt, blk, pre, (spread && direct) ? changed8 : nullptr, &would);   // positions * 2^32
+        // stands this once and takes the check again next time.  Without the bytes, unstaged, or with a staged set of no particles: it would)
+        const int verdict = STAGED ? stage_operands<kCheckWith, kStaged>(StagePV<true>{s_operand, s_v2, P, V, (spread && direct) ? changed8 : nullptr}, plan) : kNotStaged;   // positions * 2^32
+        staged = verdict != kNotStaged;
+        const int would = verdict != kStagedIdle;
         if (spread && flow && threadIdx.x == 0) df.worked[blk] = would ? 1 : 0;
         if (spread && tp.hot && threadIdx.x == 0) tp.hot[blk] = would ? 2 : 1;
     }
@@ -2564,8 +2505,8 @@ __global__ __launch_bounds__(kBlock) void k_dfsph_ext(Consts c, const float4 *__
     if (tile < 0) return;
     SPH_SWEEP_PROLOGUE_B(QUAD, tile)
     (void)kb; (void)nlbp;
-    uint32_t *s_src = reinterpret_cast<uint32_t *>(s_operand + c.stage_cap);      // (vel, rho) needs 16 B: gathered from memory
-    const bool staged = STAGED && stage_operand_src(c, s_operand, s_src, P, stage_src, stage_cnt, blk);
+    uint32_t *s_src = StageF4Src::second(s_operand, c.stage_cap);      // (vel, rho) needs 16 B: gathered from memory
+    const bool staged = STAGED && stage_operands(StageF4Src{{s_operand, P}, s_src}, StagePlan{stage_src, stage_cnt, blk}) != kNotStaged;
     const float4 vi = V[ii];
     const float rho_i = vi.w;
     float fa[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -2736,6 +2677,41 @@ __global__ void k_selftest_wave(int op, const double *__restrict__ in, double *_
     else if (op == 3) r = (double)wave_max((int)x);
     else r = (double)wave_inclusive_scan((int)x);
     out[i] = r;
+}
+
+
+// staging self-test (sph_selftest_stage): stage_operands on a caller's plan in one workgroup; the LDS image (up to six floats per staged
+// element: s_A, then the layout's second array) and the verdict go back.  layout: 0/1 StageF4 plain / scaled, 2/3 StagePS, 4/5 StagePV,
+// 6 StageF4S, 7 StageF4Src (its second array is the kept index list, copied out as bits)
+template <StageCheck CHECK, StageVerdict EMPTY>
+__global__ __launch_bounds__(kBlock) void k_selftest_stage(int layout, int use_pre, const uint2 *__restrict__ runs, const int *__restrict__ cnt,
+                                                           const float4 *__restrict__ A, const float4 *__restrict__ B, const float *__restrict__ S,
+                                                           const unsigned char *__restrict__ changed, float *__restrict__ out, int *__restrict__ verdict)
+{
+    extern __shared__ float4 s_operand[];
+    constexpr int cap = kStageCapMax;
+    StagePlan plan{runs, cnt, 0};
+    if (use_pre) plan.pre = StagePre{1, cnt[0], runs[threadIdx.x]};       // (the run table is kStageMaxCells >= kBlock long)
+    int v, nf = 0;
+    switch (layout) {
+    case 0: v = stage_operands<CHECK, EMPTY>(StageF4<false>{s_operand, A}, plan); break;
+    case 1: v = stage_operands<CHECK, EMPTY>(StageF4<true>{s_operand, A}, plan); break;
+    case 2: v = stage_operands<CHECK, EMPTY>(StagePS<false>{s_operand, A, S}, plan); break;
+    case 3: v = stage_operands<CHECK, EMPTY>(StagePS<true>{s_operand, A, S}, plan); break;
+    case 4: v = stage_operands<CHECK, EMPTY>(StagePV<false>{s_operand, StagePV<>::second(s_operand, cap), A, B, changed}, plan); nf = 2; break;
+    case 5: v = stage_operands<CHECK, EMPTY>(StagePV<true>{s_operand, StagePV<>::second(s_operand, cap), A, B, changed}, plan); nf = 2; break;
+    case 6: v = stage_operands<CHECK, EMPTY>(StageF4S{s_operand, StageF4S::second(s_operand, cap), A, S}, plan); nf = 1; break;
+    default: v = stage_operands<CHECK, EMPTY>(StageF4Src{{s_operand, A}, StageF4Src::second(s_operand, cap)}, plan); nf = 1; break;
+    }
+    if (threadIdx.x == 0) *verdict = v;
+    if (v == kNotStaged) return;
+    const int nst = cnt[0] & 0xffff;
+    const float *s_second = reinterpret_cast<const float *>(s_operand + cap);
+    for (int e = threadIdx.x; e < nst; e += kBlock) {
+        const float4 a = s_operand[e];
+        out[6 * e + 0] = a.x; out[6 * e + 1] = a.y; out[6 * e + 2] = a.z; out[6 * e + 3] = a.w;
+        for (int q = 0; q < nf; ++q) out[6 * e + 4 + q] = s_second[e * nf + q];
+    }
 }
 
 }  // namespace sph

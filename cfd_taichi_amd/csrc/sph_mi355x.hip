@@ -1286,4 +1286,59 @@ int sph_selftest_wave(int device, int op, const double *in, double *out, size_t 
     return rc;
 }
 
+int sph_selftest_stage(SphHandle *h, int layout, int check, int empty_idle, int use_pre, int not_staged, const uint32_t *runs, int nruns,
+                       const float *A, const float *B, const float *S, const unsigned char *changed, size_t n_src, float *out, int *verdict)
+{
+    int ndev = 0;
+    const int device = h ? h->device : 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(h, SPH_E_NO_DEVICE, "no HIP device available");
+    if (layout < 0 || layout > 7 || check < 0 || check > 2 || nruns < 0 || nruns > kStageMaxCells || (nruns && !runs) ||
+        !A || !B || !S || !changed || n_src == 0 || !out || !verdict)
+        return fail(h, SPH_E_INVALID, "bad argument");
+    // the plan as k_build_nl writes it: (first, local base | count << 16) per run, particles | runs << 16 for the workgroup
+    std::vector<uint2> plan(kStageMaxCells, make_uint2(0u, 0u));
+    size_t nst = 0;
+    for (int r = 0; r < nruns; ++r) {
+        const uint32_t first = runs[2 * r], n = runs[2 * r + 1];
+        if (n > 0xffffu || (size_t)first + n > n_src || nst + n > (size_t)kStageCapMax) return fail(h, SPH_E_INVALID, "a run leaves the source arrays or the staged set the capacity");
+        plan[r] = make_uint2(first, (uint32_t)nst | (n << 16));
+        nst += n;
+    }
+    const int cnt = not_staged ? -1 : (int)nst | (nruns << 16);
+    if (hipSetDevice(device) != hipSuccess) return fail(h, SPH_E_HIP, "hipSetDevice failed");
+    const size_t out_bytes = (size_t)6 * kStageCapMax * sizeof(float);
+    uint2 *d_runs = nullptr; int *d_cnt = nullptr; float4 *d_A = nullptr, *d_B = nullptr; float *d_S = nullptr, *d_out = nullptr; unsigned char *d_ch = nullptr;
+    int rc = SPH_OK;
+    if (hipMalloc((void **)&d_runs, plan.size() * sizeof(uint2)) != hipSuccess || hipMalloc((void **)&d_cnt, 2 * sizeof(int)) != hipSuccess ||
+        hipMalloc((void **)&d_A, n_src * 16) != hipSuccess || hipMalloc((void **)&d_B, n_src * 16) != hipSuccess || hipMalloc((void **)&d_S, n_src * 4) != hipSuccess ||
+        hipMalloc((void **)&d_ch, n_src) != hipSuccess || hipMalloc((void **)&d_out, out_bytes) != hipSuccess)
+        rc = fail(h, SPH_E_HIP, "hipMalloc failed");
+    if (!rc) {
+        const int head[2] = {cnt, -1};                         // [1]: the verdict
+        (void)hipMemcpy(d_runs, plan.data(), plan.size() * sizeof(uint2), hipMemcpyHostToDevice);
+        (void)hipMemcpy(d_cnt, head, sizeof(head), hipMemcpyHostToDevice);
+        (void)hipMemcpy(d_A, A, n_src * 16, hipMemcpyHostToDevice);
+        (void)hipMemcpy(d_B, B, n_src * 16, hipMemcpyHostToDevice);
+        (void)hipMemcpy(d_S, S, n_src * 4, hipMemcpyHostToDevice);
+        (void)hipMemcpy(d_ch, changed, n_src, hipMemcpyHostToDevice);
+        (void)hipMemset(d_out, 0, out_bytes);
+        const size_t lds = (size_t)kStageCapMax * StagePV<>::kBytes;      // the largest layout
+        auto launch = [&](auto empty) {
+            constexpr StageVerdict EMPTY = decltype(empty)::value;
+            if (check == 0) hipLaunchKernelGGL((k_selftest_stage<kCheckNone, EMPTY>), dim3(1), dim3(kBlock), lds, 0, layout, use_pre, d_runs, d_cnt, d_A, d_B, d_S, d_ch, d_out, d_cnt + 1);
+            else if (check == 1) hipLaunchKernelGGL((k_selftest_stage<kCheckWith, EMPTY>), dim3(1), dim3(kBlock), lds, 0, layout, use_pre, d_runs, d_cnt, d_A, d_B, d_S, d_ch, d_out, d_cnt + 1);
+            else hipLaunchKernelGGL((k_selftest_stage<kCheckFirst, EMPTY>), dim3(1), dim3(kBlock), lds, 0, layout, use_pre, d_runs, d_cnt, d_A, d_B, d_S, d_ch, d_out, d_cnt + 1);
+        };
+        if (empty_idle) launch(std::integral_constant<StageVerdict, kStagedIdle>{});
+        else launch(std::integral_constant<StageVerdict, kStaged>{});
+        if (hipDeviceSynchronize() != hipSuccess) rc = fail(h, SPH_E_HIP, "selftest kernel failed");
+        else {
+            (void)hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost);
+            (void)hipMemcpy(verdict, d_cnt + 1, sizeof(int), hipMemcpyDeviceToHost);
+        }
+    }
+    (void)hipFree(d_runs); (void)hipFree(d_cnt); (void)hipFree(d_A); (void)hipFree(d_B); (void)hipFree(d_S); (void)hipFree(d_ch); (void)hipFree(d_out);
+    return rc;
+}
+
 }  // extern "C"

@@ -109,50 +109,6 @@ __device__ __forceinline__ void for_staged_nbrs_ps(const uint32_t *__restrict__ 
         if (kk + 3 < cnt) body(a[3], sc[3], j[3]);
     }
 }
-// first operand and a per-particle scalar both staged (20 B per staged particle)
-__device__ __forceinline__ bool stage_operand_scalar(const Consts &c, float4 *__restrict__ s_A, float *__restrict__ s_S, const float4 *__restrict__ A,
-                                                     const float *__restrict__ S, const uint2 *__restrict__ stage_runs,
-                                                     const int *__restrict__ stage_cnt, int blk)
-{
-    const int nst = stage_expand(stage_runs, stage_cnt, blk, reinterpret_cast<uint32_t *>(s_A));
-    if (nst < 0) return false;
-    if (nst == 0) return true;
-    const StageIdx x = stage_take(reinterpret_cast<const uint32_t *>(s_A), nst);
-#pragma unroll
-    for (int t = 0; t < kStageTrips; ++t) {
-        const int base = threadIdx.x + t * kStageBatch * kBlock;
-        if (t * kStageBatch * kBlock >= nst) break;
-#pragma unroll
-        for (int u = 0; u < kStageBatch; ++u)
-            if (base + u * kBlock < nst) { s_A[base + u * kBlock] = A[x.j[t][u]]; s_S[base + u * kBlock] = S[x.j[t][u]]; }
-    }
-    __syncthreads();
-    return true;
-}
-// the same, reporting whether any staged A.w is != 0: 0 = not staged, 1 = staged, 2 = staged and every A.w is 0 (k_ii_dij: see there)
-__device__ __forceinline__ int stage_operand_scalar_checked(const Consts &c, float4 *__restrict__ s_A, float *__restrict__ s_S, const float4 *__restrict__ A,
-                                                            const float *__restrict__ S, const uint2 *__restrict__ stage_runs,
-                                                            const int *__restrict__ stage_cnt, int blk)
-{
-    const int nst = stage_expand(stage_runs, stage_cnt, blk, reinterpret_cast<uint32_t *>(s_A));
-    if (nst < 0) return 0;
-    if (nst == 0) return 2;
-    const StageIdx x = stage_take(reinterpret_cast<const uint32_t *>(s_A), nst);
-    int any = 0;
-#pragma unroll
-    for (int t = 0; t < kStageTrips; ++t) {
-        const int base = threadIdx.x + t * kStageBatch * kBlock;
-        if (t * kStageBatch * kBlock >= nst) break;
-#pragma unroll
-        for (int u = 0; u < kStageBatch; ++u)
-            if (base + u * kBlock < nst) {
-                const float4 a = A[x.j[t][u]];
-                any |= a.w != 0.f;
-                s_A[base + u * kBlock] = a; s_S[base + u * kBlock] = S[x.j[t][u]];
-            }
-    }
-    return __syncthreads_or(any) ? 1 : 2;
-}
 template <bool RIGID, class Body>
 __device__ __forceinline__ void for_staged_nbrs_ps2(const uint32_t *__restrict__ base, int cnt, const float4 *__restrict__ s_A,
                                                     const float *__restrict__ s_S, const RigidView &rv, Body body)
@@ -319,8 +275,8 @@ __global__ __launch_bounds__(kBlock) void k_pci_ext(Consts c, float dt, const fl
     const uint32_t *nlb = nullptr;
     SPH_SWEEP_PROLOGUE_M(QUAD)
     (void)kb; (void)nlbp;
-    uint32_t *s_src = reinterpret_cast<uint32_t *>(s_operand + c.stage_cap);
-    const bool staged = STAGED && stage_operand_src(c, s_operand, s_src, P, stage_src, stage_cnt, blk);
+    uint32_t *s_src = StageF4Src::second(s_operand, c.stage_cap);
+    const bool staged = STAGED && stage_operands(StageF4Src{{s_operand, P}, s_src}, StagePlan{stage_src, stage_cnt, blk}) != kNotStaged;
     const float4 vi = V[ii];
     const float rho_i = pi.w;
     float fa[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -391,7 +347,7 @@ __global__ __launch_bounds__(kBlock) void k_pci_predict_rho(Consts c, float delt
     extern __shared__ float4 s_operand[];
     if (gate_closed(ds, gate)) return;
     SPH_SWEEP_PROLOGUE_M(QUAD)
-    const bool staged = STAGED && stage_operand(c, s_operand, P, stage_src, stage_cnt, blk);
+    const bool staged = STAGED && stage_operands(StageF4<>{s_operand, P}, StagePlan{stage_src, stage_cnt, blk}) != kNotStaged;
     float fa[1] = {0.f};
     float &rp = fa[0];
     auto pair = [&](const float4 pj, const float4, const uint32_t j) {
@@ -446,13 +402,14 @@ __global__ __launch_bounds__(kBlock) void k_pci_press(Consts c, float dt, const 
     bool staged, all_zero = false;
     if (track) {
         const int was_zero = zero_press[blk];                      // PF / PP of this tile hold the zero-pressure values (read before the barriers below)
-        const int verdict = stage_operand_w_checked<false>(c, s_operand, P, stage_src, stage_cnt, blk);
-        all_zero = verdict == 2;                                   // every pressure this tile can see is 0: every term below is +-0
+        // (a staged set of no particles sees no pressure: kStagedIdle)
+        const int verdict = stage_operands<kCheckWith, kStagedIdle>(StageF4<>{s_operand, P}, StagePlan{stage_src, stage_cnt, blk});
+        all_zero = verdict == kStagedIdle;                                  // every pressure this tile can see is 0: every term below is +-0
         if (all_zero && was_zero) return;                          // ... and its outputs already say so
         if (threadIdx.x == 0) zero_press[blk] = all_zero ? 1 : 0;
-        staged = verdict != 0;
+        staged = verdict != kNotStaged;
     } else {
-        staged = STAGED && stage_operand(c, s_operand, P, stage_src, stage_cnt, blk);
+        staged = STAGED && stage_operands(StageF4<>{s_operand, P}, StagePlan{stage_src, stage_cnt, blk}) != kNotStaged;
     }
     const float p_i = pi.w;
     constexpr float kRho0Sq = 1000000.0f;                    // self.rho_0 ** 2 (Python int)
@@ -553,8 +510,8 @@ __global__ __launch_bounds__(kBlock) void k_ii_advect(Consts c, float dt, const 
     using K = KF<RX>;                                        // kernel functions of the handle's arithmetic (sph_device.h)
     extern __shared__ float4 s_operand[];
     SPH_SWEEP_PROLOGUE_M(QUAD)
-    uint32_t *s_src = reinterpret_cast<uint32_t *>(s_operand + c.stage_cap);
-    const bool staged = STAGED && stage_operand_src(c, s_operand, s_src, P, stage_src, stage_cnt, blk);
+    uint32_t *s_src = StageF4Src::second(s_operand, c.stage_cap);
+    const bool staged = STAGED && stage_operands(StageF4Src{{s_operand, P}, s_src}, StagePlan{stage_src, stage_cnt, blk}) != kNotStaged;
     const float4 vi = V[ii];
     const float rho_i = pi.w;
     const float s_f = c.neg_m / (rho_i * rho_i);             // compute_d_ii :280 (same value for every fluid neighbour)
@@ -636,8 +593,8 @@ __global__ __launch_bounds__(kBlock) void k_ii_rho_adv(Consts c, float dt, const
     using K = KF<RX>;                                        // kernel functions of the handle's arithmetic (sph_device.h)
     extern __shared__ float4 s_operand[];
     SPH_SWEEP_PROLOGUE_M(QUAD)
-    float2 *s_v2 = reinterpret_cast<float2 *>(s_operand + c.stage_cap);
-    const bool staged = STAGED && stage_operand_pv(c, s_operand, s_v2, P, V, stage_src, stage_cnt, blk);
+    float2 *s_v2 = StagePV<>::second(s_operand, c.stage_cap);
+    const bool staged = STAGED && stage_operands(StagePV<>{s_operand, s_v2, P, V, nullptr}, StagePlan{stage_src, stage_cnt, blk}) != kNotStaged;
     const float4 vi = V[ii], di = DII[ii];
     const float rho_i = pi.w;
     const float cji = -dt * dt * c.m / (rho_i * rho_i);      // scalar prefix of d_ji, compute_a_ii :302-303
@@ -703,17 +660,18 @@ __global__ __launch_bounds__(kBlock) void k_ii_dij(Consts c, float dt, const flo
     const bool track = STAGED && zero_dij != nullptr;
     SPH_SWEEP_PROLOGUE_B(QUAD, track ? (int)blockIdx.x : xcd_block(blockIdx.x, gridDim.x))
     (void)kb; (void)nlbp;
-    float *s_rho = reinterpret_cast<float *>(s_operand + c.stage_cap);
+    float *s_rho = StageF4S::second(s_operand, c.stage_cap);
     bool staged, all_zero = false;
     if (track) {
         const int was_zero = zero_dij[blk];
-        const int verdict = stage_operand_scalar_checked(c, s_operand, s_rho, P, rho, stage_src, stage_cnt, blk);
-        all_zero = verdict == 2;
+        // (a staged set of no particles sees no pressure: kStagedIdle)
+        const int verdict = stage_operands<kCheckWith, kStagedIdle>(StageF4S{s_operand, s_rho, P, rho}, StagePlan{stage_src, stage_cnt, blk});
+        all_zero = verdict == kStagedIdle;
         if (all_zero && was_zero) return;
         if (threadIdx.x == 0) zero_dij[blk] = all_zero ? 1 : 0;
-        staged = verdict != 0;
+        staged = verdict != kNotStaged;
     } else {
-        staged = STAGED && stage_operand_scalar(c, s_operand, s_rho, P, rho, stage_src, stage_cnt, blk);
+        staged = STAGED && stage_operands(StageF4S{s_operand, s_rho, P, rho}, StagePlan{stage_src, stage_cnt, blk}) != kNotStaged;
     }
     float fa[3] = {0.f, 0.f, 0.f};
     float &sx = fa[0], &sy = fa[1], &sz = fa[2];
@@ -750,7 +708,7 @@ __global__ __launch_bounds__(kBlock) void k_ii_update_p(Consts c, float dt, cons
     extern __shared__ float4 s_operand[];
     if (gate_closed(ds, gate)) return;
     SPH_SWEEP_PROLOGUE_M(QUAD)
-    uint32_t *s_src = reinterpret_cast<uint32_t *>(s_operand + c.stage_cap);
+    uint32_t *s_src = StageF4Src::second(s_operand, c.stage_cap);
     float *s_ex = reinterpret_cast<float *>(s_src + c.stage_cap), *s_ey = s_ex + c.stage_cap, *s_ez = s_ey + c.stage_cap;
     const int nst = STAGED ? stage_expand(stage_src, stage_cnt, blk, s_src) : -1;      // the list stays: DII is gathered through it
     const bool staged = nst >= 0;

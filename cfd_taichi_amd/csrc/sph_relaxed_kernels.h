@@ -37,29 +37,6 @@ __device__ __forceinline__ float rx_g(const Consts &c, float dx, float dy, float
     return q <= 0.5f ? g1 : g2;
 }
 
-// positions and k / rho of the workgroup's staged set, unscaled (the relaxed counterpart of stage_operand_ps_scaled)
-__device__ __forceinline__ bool stage_operand_ps(const Consts &c, float4 *__restrict__ s_A, const float4 *__restrict__ A, const float *__restrict__ S,
-                                                 const uint2 *__restrict__ stage_runs, const int *__restrict__ stage_cnt, int blk, const StagePre &pre = kNoPre)
-{
-    const int nst = stage_expand(stage_runs, stage_cnt, blk, reinterpret_cast<uint32_t *>(s_A), pre);
-    if (nst < 0) return false;
-    if (nst == 0) return true;
-    const StageIdx x = stage_take(reinterpret_cast<const uint32_t *>(s_A), nst);
-#pragma unroll
-    for (int t = 0; t < kStageTrips; ++t) {
-        const int base = threadIdx.x + t * kStageBatch * kBlock;
-        if (t * kStageBatch * kBlock >= nst) break;
-        float4 a[kStageBatch]; float sc[kStageBatch];
-#pragma unroll
-        for (int u = 0; u < kStageBatch; ++u) { a[u] = A[x.j[t][u]]; sc[u] = S[x.j[t][u]]; }
-#pragma unroll
-        for (int u = 0; u < kStageBatch; ++u)
-            if (base + u * kBlock < nst) s_A[base + u * kBlock] = make_float4(a[u].x, a[u].y, a[u].z, sc[u]);
-    }
-    __syncthreads();
-    return true;
-}
-
 // Walk of a 16-bit list eight entries at a time WITHOUT tail masks: k_build_nl pads the last group of a list with the particle's own
 // local index (NlWriter::flush), and the particle itself contributes x_ij = 0, v_ij = 0: a term that is exactly 0 (g stays finite: r^2 is
 // floored in rx_g).  Eight independent pair bodies per trip in one basic block; tools/pair_body_relaxed.hip: 22.1 -> 19.1 us per sweep.
@@ -159,19 +136,21 @@ __global__ __launch_bounds__(kBlock) void k_residual_rx(Consts c, const float4 *
     const uint32_t *nlb = nullptr;
     SPH_SWEEP_PROLOGUE_B(false, tile)
     (void)nlbp;
-    float2 *s_v2 = reinterpret_cast<float2 *>(s_operand + c.stage_cap);
+    float2 *s_v2 = StagePV<>::second(s_operand, c.stage_cap);
+    const StagePlan plan{stage_src, stage_cnt, blk, pre};
     bool staged;
-    if (spread && !direct) {       // second, exact level of the change propagation (sph_kernels.h: stage_operand_pv_checked)
-        const int verdict = stage_operand_pv_checked<false>(c, s_operand, s_v2, P, V, changed8, stage_src, stage_cnt, blk, pre);
-        if (verdict == 2) {
+    if (spread && !direct) {       // second, exact level of the change propagation (k_residual in sph_kernels.h, the empty set included)
+        const int verdict = stage_operands<kCheckFirst, kStaged>(StagePV<>{s_operand, s_v2, P, V, changed8}, plan);
+        if (verdict == kStagedIdle) {
             if (flow && df.nz[blk] != 0 && threadIdx.x < 64) flow_push(df, my_nbr);
             if (tp.hot && threadIdx.x == 0) tp.hot[blk] = 1;
             return;
         }
-        staged = verdict == 1;
-    } else {
-        int would = 1;                                              // (see k_residual: a `direct` tile learns from the staging batch whether it would have passed the check)
-        staged = stage_operand_pv<false>(c, s_operand, s_v2, P, V, stage_src, stage_cnt, blk, pre, (spread && direct) ? changed8 : nullptr, &would);
+        staged = verdict == kStaged;
+    } else {                                                        // (see k_residual: a `direct` tile learns from the staging batch whether it would have passed the check)
+        const int verdict = stage_operands<kCheckWith, kStaged>(StagePV<>{s_operand, s_v2, P, V, (spread && direct) ? changed8 : nullptr}, plan);
+        staged = verdict != kNotStaged;
+        const int would = verdict != kStagedIdle;
         if (spread && flow && threadIdx.x == 0) df.worked[blk] = would ? 1 : 0;
         if (spread && tp.hot && threadIdx.x == 0) tp.hot[blk] = would ? 2 : 1;
     }
@@ -268,17 +247,18 @@ __global__ __launch_bounds__(kBlock) void k_correct_rx(Consts c, const float4 *_
     const bool track = MODE == CORR_DENS && wave_dirty != nullptr;  // change propagation in the density loop (sph_kernels.h: stage_sources_flagged)
     bool staged;
     if (track && !direct) {
-        const int verdict = stage_operand_ps_checked<false>(c, s_operand, P, krho, stage_src, stage_cnt, blk, pre);
-        if (verdict == 2) {
+        // (a staged set of no particles: kStaged, the tile goes on -- see k_correct)
+        const int verdict = stage_operands<kCheckFirst, kStaged>(StagePS<>{s_operand, P, krho}, StagePlan{stage_src, stage_cnt, blk, pre});
+        if (verdict == kStagedIdle) {
             const bool foreign = live && ghost && !c.ghost_walk;           // (see k_correct in sph_kernels.h)
             const unsigned long long anyg = __ballot(foreign);
             if ((threadIdx.x & 63) == 0) wave_dirty[blk * (kBlock / 64) + (threadIdx.x >> 6)] = anyg != 0ull ? 1 : 0;
             if (live) changed8[i] = foreign ? 1 : 0;
             return;
         }
-        staged = verdict == 1;
+        staged = verdict == kStaged;
     } else {
-        staged = stage_operand_ps(c, s_operand, P, krho, stage_src, stage_cnt, blk, pre);
+        staged = stage_operands(StagePS<>{s_operand, P, krho}, StagePlan{stage_src, stage_cnt, blk, pre}) != kNotStaged;
     }
     const float dt = ds->dt;
     const float rho_i = rho[ii];
@@ -352,7 +332,7 @@ __global__ __launch_bounds__(kBlock) void k_density_rx(Consts c, const float4 *_
     if (tile < 0) return;
     SPH_SWEEP_PROLOGUE_G(false, tile, true)
     (void)nlbp;
-    const bool staged = stage_operand<false>(c, s_operand, P, stage_src, stage_cnt, blk);
+    const bool staged = stage_operands(StageF4<>{s_operand, P}, StagePlan{stage_src, stage_cnt, blk}) != kNotStaged;
     float ws = 0.f, sx = 0.f, sy = 0.f, sz = 0.f, sq = 0.f;
     auto pair = [&](const float4 pj, bool valid) {
         const float dx = pi.x - pj.x, dy = pi.y - pj.y, dz = pi.z - pj.z;
@@ -411,8 +391,8 @@ __global__ __launch_bounds__(kBlock) void k_dfsph_ext_rx(Consts c, const float4 
     if (tile < 0) return;
     SPH_SWEEP_PROLOGUE_B(false, tile)
     (void)kb; (void)nlbp;
-    uint32_t *s_src = reinterpret_cast<uint32_t *>(s_operand + c.stage_cap);      // (vel, rho) is gathered from memory through the source list
-    const bool staged = stage_operand_src(c, s_operand, s_src, P, stage_src, stage_cnt, blk);
+    uint32_t *s_src = StageF4Src::second(s_operand, c.stage_cap);      // (vel, rho) is gathered from memory through the source list
+    const bool staged = stage_operands(StageF4Src{{s_operand, P}, s_src}, StagePlan{stage_src, stage_cnt, blk}) != kNotStaged;
     const float4 vi = V[ii];
     const float rho_i = vi.w;
     const float tk = c.tens_c * c.kw;

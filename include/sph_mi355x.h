@@ -368,6 +368,17 @@ int sph_selftest_math(int device, int op, const float *a, const float *b, float 
  * (op 0: f64 sum, 1: i32 sum, 2: f32 max, 3: i32 max -- reductions, documented result in lane 0; 4: i32 inclusive prefix sum).
  * The primitives are DPP / ds_swizzle / v_permlane32_swap butterflies (csrc/sph_device.h); n must be a multiple of 256. */
 int sph_selftest_wave(int device, int op, const double *in, double *out, size_t n);
+/* staging self-test: the routine that copies a workgroup's operands into LDS (stage_operands, csrc/sph_kernels.h) run by ONE workgroup of 256
+ * threads on the caller's plan.  h: the handle whose device runs it and whose sph_last_error receives a failure; NULL: device 0.
+ * runs: nruns pairs (first source index, count), at most 640 runs and 2560 particles in all; not_staged: the
+ * plan says "this workgroup is not staged"; use_pre: the plan's head arrives the way the density loop prefetches it.  A, B: n_src float4 each,
+ * S: n_src floats, changed: n_src bytes.  layout: 0 one float4 (A), 1 the same with xyz * 2^32, 2 (A.xyz, S), 3 the same scaled,
+ * 4 (A.xyz, B.x) + (B.y, B.z), 5 the same scaled, 6 A + S in a second array, 7 A + the kept source index (its bits in float 4).
+ * check: 0 none, 1 with the copy, 2 first (the key examined: A.w for layouts 0, 1, 6, 7; S for 2, 3; changed for 4, 5).
+ * out: 2560 x 6 floats, the staged elements in order (floats the layout does not hold are 0); *verdict: 0 not staged, 1 staged, 2 staged and
+ * no key set (check 2: nothing copied then).  An empty staged set gives 1, or 2 with empty_idle (the sweeps choose per call site). */
+int sph_selftest_stage(SphHandle *h, int layout, int check, int empty_idle, int use_pre, int not_staged, const uint32_t *runs, int nruns,
+                       const float *A, const float *B, const float *S, const unsigned char *changed, size_t n_src, float *out, int *verdict);
 
 #ifdef __cplusplus
 }

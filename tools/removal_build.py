@@ -37,8 +37,8 @@ PATCHES = {
     "xcd_chunk128": [(K, "    return xcd_block(orig, nwg);\n}\n\n// Edge / interior split of a sweep",
                     "    const int C = 128, xcd = orig & 7, s = orig >> 3, per = nwg / (8 * C);\n    if (per < 4) return xcd_block(orig, nwg);\n    if (s >= per * C) return orig;\n    return ((s / C) * 8 + xcd) * C + s % C;\n}\n\n// Edge / interior split of a sweep")],
     # exact k_residual: workgroups whose set did not fit the LDS capacity (1-2 % of them at 1 M) return at once: what do they cost the launch?
-    "nounstaged": [(K, "(spread && direct) ? changed8 : nullptr, &would);   // positions * 2^32\n",
-                    "(spread && direct) ? changed8 : nullptr, &would);   // positions * 2^32\n        if (STAGED && !staged) return;\n")],
+    "nounstaged": [(K, "        staged = verdict != kNotStaged;\n        const int would = verdict != kStagedIdle;\n",
+                    "        staged = verdict != kNotStaged;\n        const int would = verdict != kStagedIdle;\n        if (STAGED && !staged) return;\n")],
     # a CORRECT variant with a side effect: every workgroup of the exact divergence-residual sweep leaves (begin, end, XCC id) of its life in a
     # device array that sph_debug_timeline() copies out (tools/wg_timeline.py): how full is the chip over a launch, where is the tail?
     "wg_timeline": [(K, "    else block_partial_mean(blk, (double)val, flag, psum, pcnt);\n    if (flow) {                                                      // does this tile hold",
@@ -61,12 +61,12 @@ PATCHES = {
                        (R, "    const uint32_t *nlb = nullptr;\n    SPH_SWEEP_PROLOGUE_B(false, tile)\n    (void)nlbp;\n    float2 *s_v2",
                         "    const uint32_t *nlb = nullptr;\n    if (threadIdx.x == 0 && blockIdx.x < 16384) g_sub2[blockIdx.x * 4 + 2] = wall_clock64();\n    SPH_SWEEP_PROLOGUE_B(false, tile)\n    (void)nlbp;\n    float2 *s_v2"),
                        ("sph_mi355x.hip", "int sph_set_scalar(", "int sph_debug_sub2(unsigned long long *out, int n)\n{\n    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(sph::g_sub2), sizeof(unsigned long long) * 4 * (size_t)n);\n}\nint sph_set_scalar("),
-                       (K, "// both operands of the residual sweeps staged: (x, y, z, vx) and (vy, vz) -- 24 B per staged particle",
-                        "__device__ unsigned long long g_sub[16384 * 4];\n// both operands of the residual sweeps staged: (x, y, z, vx) and (vy, vz) -- 24 B per staged particle"),
-                       (K, "    const int nst = stage_expand(stage_runs, stage_cnt, blk, reinterpret_cast<uint32_t *>(s_A), pre);\n    if (nst < 0) return false;\n    if (nst == 0) return true;                              // a workgroup of ghosts only (slab handles): nothing to stage, uniform\n    const StageIdx x = stage_take(reinterpret_cast<const uint32_t *>(s_A), nst);\n    int any = 0;\n",
-                        "    const int nst = stage_expand(stage_runs, stage_cnt, blk, reinterpret_cast<uint32_t *>(s_A), pre);\n    const unsigned long long ts1 = wall_clock64();\n    if (nst < 0) return false;\n    if (nst == 0) return true;\n    const StageIdx x = stage_take(reinterpret_cast<const uint32_t *>(s_A), nst);\n    const unsigned long long ts2 = wall_clock64();\n    if (threadIdx.x == 0 && blockIdx.x < 16384) { g_sub[blockIdx.x * 4 + 0] = ts1; g_sub[blockIdx.x * 4 + 1] = ts2; }\n    int any = 0;\n"),
-                       (K, "    if (changed) *any_changed = __syncthreads_or(any);\n    else __syncthreads();\n    return true;\n}\n// The same with a look at a per-particle byte first",
-                        "    if (threadIdx.x == 0 && blockIdx.x < 16384) g_sub[blockIdx.x * 4 + 2] = wall_clock64();\n    if (changed) *any_changed = __syncthreads_or(any);\n    else __syncthreads();\n    return true;\n}\n// The same with a look at a per-particle byte first"),
+                       (K, "struct StageNone {};\n", "__device__ unsigned long long g_sub[16384 * 4];\nstruct StageNone {};\n"),
+                       # (the stamps of the staging routine: the (pos, vel) layout without the check-first pass only -- the batch the residual sweeps stage with)
+                       (K, "    const int nst = stage_expand(plan.runs, plan.cnt, plan.blk, lay.idx(), plan.pre);\n    if (nst < 0) return kNotStaged;\n    if (nst == 0) return EMPTY;                             // uniform\n    const StageIdx x = stage_take(lay.idx(), nst);\n    if (L::kIdxAliased) __syncthreads();                    // from here on the operands may overwrite the list\n",
+                        "    const int nst = stage_expand(plan.runs, plan.cnt, plan.blk, lay.idx(), plan.pre);\n    const unsigned long long ts1 = wall_clock64();\n    if (nst < 0) return kNotStaged;\n    if (nst == 0) return EMPTY;\n    const StageIdx x = stage_take(lay.idx(), nst);\n    if (L::kIdxAliased) __syncthreads();\n    const unsigned long long ts2 = wall_clock64();\n    const bool sub_pv = (std::is_same<L, StagePV<false>>::value || std::is_same<L, StagePV<true>>::value) && CHECK != kCheckFirst && threadIdx.x == 0 && blockIdx.x < 16384;\n    if (sub_pv) { g_sub[blockIdx.x * 4 + 0] = ts1; g_sub[blockIdx.x * 4 + 1] = ts2; }\n"),
+                       (K, "    if (CHECK == kCheckWith && lay.has_key()) return __syncthreads_or(any) ? kStaged : kStagedIdle;\n",
+                        "    if (sub_pv) g_sub[blockIdx.x * 4 + 2] = wall_clock64();\n    if (CHECK == kCheckWith && lay.has_key()) return __syncthreads_or(any) ? kStaged : kStagedIdle;\n"),
                        ("sph_mi355x.hip", "int sph_tune_time(SphHandle *h, int which, unsigned lds_bytes, int reps, double *avg_us)\n{",
                         "int sph_debug_sub(unsigned long long *out, int n)\n{\n    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(sph::g_sub), sizeof(unsigned long long) * 4 * (size_t)n);\n}\nint sph_tune_time(SphHandle *h, int which, unsigned lds_bytes, int reps, double *avg_us)\n{"),
                        (K, "// D3 / D6: divergence residual and predicted density.", "__device__ unsigned long long g_timeline[16384 * 4];\n// D3 / D6: divergence residual and predicted density."),
@@ -91,16 +91,16 @@ PATCHES = {
                        "    const unsigned long long t_begin = wall_clock64();\n    if (fr.mode >= 0 && blockIdx.x == 0) { fin_ride_block(fr); return; }\n"),
                       (K, "            if (direct && threadIdx.x == 0) df.worked[tile] = 0;\n            return;\n        }\n    }\n    const int my_nbr = (flow && threadIdx.x < 64) ? df.nbr[(size_t)tile * kNbrStride + threadIdx.x] : 0;       // requested now, used by the push at the end",
                        "            if (direct && threadIdx.x == 0) df.worked[tile] = 0;\n            tl_note(g_tl7, g_tl_capture[1], df, t_begin, 0, tile);\n            return;\n        }\n    }\n    const int my_nbr = (flow && threadIdx.x < 64) ? df.nbr[(size_t)tile * kNbrStride + threadIdx.x] : 0;"),
-                      (K, "            if (live) changed8[i] = foreign ? 1 : 0;\n            return;\n        }\n        staged = verdict == 1;",
-                       "            if (live) changed8[i] = foreign ? 1 : 0;\n            if (MODE == CORR_DENS) tl_note(g_tl7, g_tl_capture[1], df, t_begin, 1, tile);\n            return;\n        }\n        staged = verdict == 1;"),
+                      (K, "            if (live) changed8[i] = foreign ? 1 : 0;\n            return;\n        }\n        staged = verdict == kStaged;",
+                       "            if (live) changed8[i] = foreign ? 1 : 0;\n            if (MODE == CORR_DENS) tl_note(g_tl7, g_tl_capture[1], df, t_begin, 1, tile);\n            return;\n        }\n        staged = verdict == kStaged;"),
                       (K, "            if (threadIdx.x == 0) df.worked[tile] = moved ? 1 : 0;\n        }\n    }\n    if (!owner) return;",
                        "            if (threadIdx.x == 0) df.worked[tile] = moved ? 1 : 0;\n        }\n    }\n    if (MODE == CORR_DENS) { __builtin_amdgcn_s_barrier(); const unsigned long long t_w = wall_clock64(); tl_note(g_tl7, g_tl_capture[1], df, t_begin, 2, tile, STAGED ? stage_cnt[tile] : 0, ((t_st - t_begin) & 0xffff) | (((t_pr - t_begin) & 0xffff) << 16) | (((t_w - t_begin) & 0xffff) << 32)); }\n    if (!owner) return;"),
                       (K, "    extern __shared__ float4 s_operand[];\n    // (see k_correct: round-robin tiles when most of them return at once; the body",
                        "    extern __shared__ float4 s_operand[];\n    const unsigned long long t_begin = wall_clock64();\n    // (see k_correct: round-robin tiles when most of them return at once; the body"),
                       (K, "        if (idle) return;                                            // rho*, k / rho and the block partial of the last iteration stand",
                        "        if (idle) { tl_note(g_tl6, g_tl_capture[0], df, t_begin, 0, tile); return; }"),
-                      (K, "            if (tp.hot && threadIdx.x == 0) tp.hot[blk] = 1;\n            return;\n        }\n        staged = verdict == 1;",
-                       "            if (tp.hot && threadIdx.x == 0) tp.hot[blk] = 1;\n            tl_note(g_tl6, g_tl_capture[0], df, t_begin, 1, tile);\n            return;\n        }\n        staged = verdict == 1;"),
+                      (K, "            if (tp.hot && threadIdx.x == 0) tp.hot[blk] = 1;\n            return;\n        }\n        staged = verdict == kStaged;",
+                       "            if (tp.hot && threadIdx.x == 0) tp.hot[blk] = 1;\n            tl_note(g_tl6, g_tl_capture[0], df, t_begin, 1, tile);\n            return;\n        }\n        staged = verdict == kStaged;"),
                       (K, "    if (flow) {                                                      // does this tile hold a k / rho != 0?  (a NaN counts)",
                        "    if (DENS) tl_note(g_tl6, g_tl_capture[0], df, t_begin, 2, tile, STAGED ? stage_cnt[tile] : 0, ((t_st - t_begin) & 0xffff) | (((t_pr - t_begin) & 0xffff) << 16) | (((t_w - t_begin) & 0xffff) << 32));\n    if (flow) {                                                      // does this tile hold a k / rho != 0?  (a NaN counts)"),
                       (K, "    const float dt = ds->dt;\n    const float rho_i = rho[ii];\n    float k_i;\n    if (MODE == CORR_WARM) k_i = warm[ii] / dt;                                   // :333",
@@ -135,10 +135,11 @@ PATCHES = {
     # k_build_nl at eight waves per SIMD (a CORRECT variant; the compiler must fit 96 SGPRs): does residency move the list build?  (round 6 A/B)
     "bnl_waves8": [(K, "template <bool RIGID, bool STAGED>\n__global__ __launch_bounds__(kBlock) void k_build_nl(", "template <bool RIGID, bool STAGED>\n__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_build_nl(")],
     # the staging gathers of the residual sweeps removed (plan expansion and barriers kept)
-    "nogather": [(K, "        float4 a[kStageBatch], b[kStageBatch];\n#pragma unroll\n        for (int u = 0; u < kStageBatch; ++u) { a[u] = A[x.j[t][u]]; b[u] = B[x.j[t][u]]; }\n#pragma unroll\n        for (int u = 0; u < kStageBatch; ++u)\n            if (base + u * kBlock < nst) {\n                const int e = base + u * kBlock;",
-                  "        float4 a[kStageBatch], b[kStageBatch];\n#pragma unroll\n        for (int u = 0; u < kStageBatch; ++u) { a[u] = make_float4((float)x.j[t][u], 0.f, 0.f, 0.f); b[u] = a[u]; }\n#pragma unroll\n        for (int u = 0; u < kStageBatch; ++u)\n            if (base + u * kBlock < nst) {\n                const int e = base + u * kBlock;"),
-                 (K, "        for (int u = 0; u < kStageBatch; ++u) { a[u] = A[x.j[t][u]]; b[u] = B[x.j[t][u]]; f[u] = changed ? changed[x.j[t][u]] : (unsigned char)0; }",
-                  "        for (int u = 0; u < kStageBatch; ++u) { a[u] = make_float4((float)x.j[t][u], 0.f, 0.f, 0.f); b[u] = a[u]; f[u] = 0; }")],
+    "nogather": [(K, "    __device__ __forceinline__ Rest load_rest(uint32_t j) const { return StagePair{A[j], B[j]}; }",
+                  "    __device__ __forceinline__ Rest load_rest(uint32_t j) const { const float4 q = make_float4((float)j, 0.f, 0.f, 0.f); return StagePair{q, q}; }"),
+                 # (the bytes that ride in the batch go with the gathers; the check-first pass keeps its own, as it did)
+                 (K, "            if (CHECK == kCheckWith) k[t][u] = lay.has_key() ? lay.load_key(x.j[t][u]) : typename L::Key{};",
+                  "            if (CHECK == kCheckWith) k[t][u] = lay.has_key() && !(std::is_same<L, StagePV<false>>::value || std::is_same<L, StagePV<true>>::value) ? lay.load_key(x.j[t][u]) : typename L::Key{};")],
     # k_build_nl: every wave works its 27 cell entries out per lane (a CORRECT variant: tools/soak_libs.py holds it against the default)
     "bnl_notable": [(K, "    const bool table = nruns <= kRunCap;                                       // wave-uniform",
                      "    const bool table = false;")],
@@ -149,8 +150,8 @@ PATCHES = {
     # LDS gathers, same arithmetic, half the list bytes from HBM): what a 2x more compact list encoding could buy at most
     "rx_halflist": [(R, "        if (kk + 8 < cnt) jn = nl_load(base + (size_t)((kk >> 3) + 1) * 256);\n        pair8(g);",
                      "        if (kk + 8 < cnt && ((kk >> 3) & 1)) jn = nl_load(base + (size_t)((kk >> 3) + 1) * 256);\n        pair8(g);")],
-    "rx_nostage": [(R, "        staged = stage_operand_pv<false>(c, s_operand, s_v2, P, V, stage_src, stage_cnt, blk, pre, (spread && direct) ? changed8 : nullptr, &would);\n",
-                    "        staged = true;\n"),
+    "rx_nostage": [(R, "        const int verdict = stage_operands<kCheckWith, kStaged>(StagePV<>{s_operand, s_v2, P, V, (spread && direct) ? changed8 : nullptr}, plan);\n        staged = verdict != kNotStaged;\n        const int would = verdict != kStagedIdle;\n",
+                    "        staged = true;\n        const int would = 1;\n"),
                    (R, "        rx_walk8(nlp, kfx, [&](const Nl16Group &g) {\n            float4 a[8]; float2 b[8];",
                     "        rx_walk8(nlp, 0, [&](const Nl16Group &g) {\n            float4 a[8]; float2 b[8];")],
 }
