@@ -42,7 +42,7 @@ EXPORTS = [
     "sph_get_scalar", "sph_set_scalar", "sph_synchronize", "sph_overrides", "sph_profile_enable", "sph_profile_reset", "sph_profile_kernel_count",
     "sph_profile_kernel_name", "sph_profile_get", "sph_selftest_math", "sph_selftest_wave", "sph_selftest_stage", "sph_tune_time",
     "sph_set_comm", "sph_rccl_unique_id", "sph_rccl_attach", "sph_rccl_selftest", "sph_get_stream", "sph_plan_slabs", "sph_replan_slabs", "sph_slab_set_overlap", "sph_slab_info", "sph_comm_stats", "sph_download_local", "sph_download_ids",
-    "sph_create_rigid", "sph_rigid_step", "sph_rigid_set_active", "sph_rigid_init_data",
+    "sph_create_rigid", "sph_rigid_step", "sph_rigid_set_active", "sph_rigid_init_data", "sph_slab_set_state",
 ]
 
 
@@ -172,7 +172,7 @@ CORE_EXPORTS = [
 ]
 # entry points added without a change of SPH_ABI_VERSION (no struct grew, no signature changed): bound where the library has them, and a call on a
 # library without them raises SphError(SPH_E_STATE)
-OPTIONAL_EXPORTS = ["sph_rigid_set_active", "sph_rigid_init_data", "sph_selftest_stage"]
+OPTIONAL_EXPORTS = ["sph_rigid_set_active", "sph_rigid_init_data", "sph_selftest_stage", "sph_slab_set_state"]
 
 
 def _bind_core(lib):
@@ -267,6 +267,8 @@ def load(build_if_missing=True):
     lib.sph_replan_slabs.argtypes = [ctypes.POINTER(ctypes.c_int64), ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]
     lib.sph_download_local.argtypes = [vp, ci, vp, ctypes.c_size_t]
     lib.sph_download_ids.argtypes = [vp, vp, ctypes.c_size_t]
+    if hasattr(lib, "sph_slab_set_state"):
+        lib.sph_slab_set_state.argtypes = [vp, vp, vp, vp, ctypes.c_size_t, ctypes.c_double]
     _lib = lib
     return lib
 
@@ -550,6 +552,24 @@ class Simulation:
         self._check(self._lib.sph_comm_stats(self._h, out, 1 if reset else 0))
         keys = ("p2p_groups", "bytes_sent", "bytes_received", "count_exchanges", "allreduce_stream", "allreduce_host", "steps")
         return {k: int(out[i]) for i, k in enumerate(keys)}
+
+    def slab_set_state(self, pos, vel=None, scalar=None, delta_time=0.0):
+        """Collective over all slabs: this handle's share of one full state in original particle order (sph_slab_set_state); vel / scalar None = zeros,
+        delta_time 0 keeps the handle's.  A refusal raises the same SphError on every rank and changes no handle."""
+        def flat(a, shape):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.shape != shape:
+                raise ValueError("expected shape %s, got %s" % (shape, a.shape))
+            return a
+        pos = np.ascontiguousarray(pos, dtype=np.float32)
+        if pos.ndim != 2 or pos.shape[1] != 3:
+            raise ValueError("pos must be (n, 3), got %s" % (pos.shape,))
+        n = len(pos)
+        vel, scalar = flat(vel, (n, 3)), flat(scalar, (n,))
+        self._check(self._optional("sph_slab_set_state")(self._h, pos.ctypes.data, vel.ctypes.data if vel is not None else None,
+                                                         scalar.ctypes.data if scalar is not None else None, n, float(delta_time or 0.0)))
 
     def download_local(self, field):
         """(ids, values) of every resident particle in device order; ids < 0 are ghosts (~id)."""

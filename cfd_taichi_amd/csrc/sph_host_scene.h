@@ -123,17 +123,9 @@ void replan_slab_cuts(const std::vector<long long> &hist, int gx, int nslab, con
 
 // Equal-count cuts along the cell x index, computed identically on every rank from the full lattice:
 // slab k owns cell columns [cut[k], cut[k+1]).
-bool plan_slab_cuts(const std::vector<float> &pos, int N, float hcell, int gx, int nslab, std::vector<int> &col, std::vector<int> &cut,
-                    std::string &why, int layers = 0)
+// (from the column histogram alone: creation counts it on the host, sph_slab_set_state on the device)
+bool plan_slab_cuts_hist(const std::vector<long long> &hist, long long N, int gx, int nslab, std::vector<int> &cut, std::string &why, int layers = 0)
 {
-    std::vector<long long> hist((size_t)gx, 0);
-    col.resize((size_t)N);
-    for (int i = 0; i < N; ++i) {
-        int cx = (int)floorf(pos[3 * (size_t)i] / hcell);
-        cx = cx < 0 ? 0 : (cx >= gx ? gx - 1 : cx);
-        col[i] = cx;
-        hist[cx]++;
-    }
     if (gx < kMinSlabColumns * nslab) {
         char buf[160];
         snprintf(buf, sizeof(buf), "%d slabs need at least %d cell columns along x, the grid has %d: too many slabs for this scene", nslab, kMinSlabColumns * nslab, gx);
@@ -153,6 +145,19 @@ bool plan_slab_cuts(const std::vector<float> &pos, int N, float hcell, int gx, i
     for (int k = 1; k < nslab; ++k)     // every slab at least kMinSlabColumns wide, even where the fluid is narrow
         cut[k] = std::min(std::max(cut[k], cut[k - 1] + kMinSlabColumns), gx - kMinSlabColumns * (nslab - k));
     return true;
+}
+bool plan_slab_cuts(const std::vector<float> &pos, int N, float hcell, int gx, int nslab, std::vector<int> &col, std::vector<int> &cut,
+                    std::string &why, int layers = 0)
+{
+    std::vector<long long> hist((size_t)gx, 0);
+    col.resize((size_t)N);
+    for (int i = 0; i < N; ++i) {
+        int cx = (int)floorf(pos[3 * (size_t)i] / hcell);
+        cx = cx < 0 ? 0 : (cx >= gx ? gx - 1 : cx);
+        col[i] = cx;
+        hist[cx]++;
+    }
+    return plan_slab_cuts_hist(hist, N, gx, nslab, cut, why, layers);
 }
 
 // this rank's columns, its neighbours' far cuts and the ghost columns whose particles own lists, from h->cuts
@@ -588,10 +593,17 @@ int dcommit(SphHandle *h)
     char *base = nullptr;
     HIP_TRY(h, hipMalloc((void **)&base, cur > 0 ? cur : 1));
     h->arenas.push_back(base);
-    for (size_t k = 0; k < h->plan.size(); ++k) *h->plan[k].first = base + off[k];
+    for (size_t k = 0; k < h->plan.size(); ++k) { *h->plan[k].first = base + off[k]; h->blocks.push_back({base + off[k], h->plan[k].second}); }
     HIP_TRY(h, hipMemsetAsync(base, 0, cur, h->stream));
     h->plan.clear();
     return SPH_OK;
+}
+
+// bytes of a dalloc'd array (0: not one)
+inline size_t dalloc_bytes(const SphHandle *h, const void *p)
+{
+    for (const auto &b : h->blocks) if (b.first == p) return b.second;
+    return 0;
 }
 
 inline uint64_t morton_spread(uint64_t v)          // 21 bits -> every third bit
@@ -836,5 +848,23 @@ int read_scalars(SphHandle *h)
     HIP_TRY(h, hipMemcpyAsync(h->ds_host, h->ds, sizeof(DevScalars), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     fold_list_maxima(h);
+    return SPH_OK;
+}
+
+// `solver.delta_time[None] = value`: sph_set_scalar(SPH_S_DELTA_TIME), and sph_slab_set_state with a delta_time
+int write_delta_time(SphHandle *h, double value)
+{
+    h->dt_wcsph = (float)value;                                      // the launch argument of the fixed-dt solvers
+    h->cfg.delta_time = value;
+    if (h->cfg.solver == SPH_SOLVER_DFSPH) {                         // dfsph keeps delta_time, delta_time_2 on the device (dfsph_solver.py:20, :118)
+        int rc = read_scalars(h);
+        if (rc) return rc;
+        h->ds_host->dt = (float)value;
+        h->ds_host->dt2 = h->ds_host->dt * h->ds_host->dt;
+        HIP_TRY(h, hipMemcpyAsync(h->ds, h->ds_host, offsetof(DevScalars, ps_dt), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
+    for (int k = 0; k < 8; ++k)                                      // captured wcsph step pairs carry the old delta_time as a launch argument
+        if (h->wcsph_graph[k]) { (void)hipGraphExecDestroy(h->wcsph_graph[k]); h->wcsph_graph[k] = nullptr; }
     return SPH_OK;
 }

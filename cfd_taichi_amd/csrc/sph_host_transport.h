@@ -425,3 +425,148 @@ int slab_exchange_resid(SphHandle *h, bool dens, float *val, bool overlap, bool 
     if (overlap) HIP_TRY(h, hipEventRecord(h->ev_halo, s));
     return SPH_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// sph_slab_set_state: the owned set of every slab from one full state (include/sph_mi355x.h).  Collective.
+//   1. every rank alone, nothing of the handle touched: the arguments, then pass A over the state (k_state_histogram: particles per cell column,
+//      positions no slab can own), the cuts creation would plan from that histogram, this rank's owned count against its capacity;
+//   2. ONE max-reduce of the verdicts through the handle's transport: every rank returns the same code, and a refusal leaves all handles as they were;
+//   3. commit: the cuts, everything resident cleared to what a new handle holds, pass B (k_state_count / _scan / _write) into the live arrays.
+// The state streams through a buffer of its own, `chunk` particles at a time (28 bytes each): a slab's arena is sized for its share, not for the scene.
+// ---------------------------------------------------------------------------------------------
+struct StateBuf {
+    char *base = nullptr;
+    float *pos = nullptr, *vel = nullptr, *sca = nullptr;
+    int *blk = nullptr, *words = nullptr;        // words[0]: particles pass B has placed, words[1]: pass A's refusal bits
+    int chunk = 0;
+    ~StateBuf() { if (base) (void)hipFree(base); }
+};
+constexpr int kStateChunk = 1 << 20;
+
+int state_buf_alloc(SphHandle *h, StateBuf &b)
+{
+    // (SPH_STATE_CHUNK: particles per chunk -- tests reach the many-chunk path with scenes of a few thousand particles)
+    const char *e = dev_env(&h->overrides, "SPH_STATE_CHUNK");
+    const long long want = e ? std::min<long long>(std::max(atoll(e), 1LL), kStateChunk) : kStateChunk;
+    b.chunk = (int)((std::min<long long>(want, std::max(h->N, 1)) + kBlock - 1) / kBlock * kBlock);
+    const size_t n = (size_t)b.chunk, nblk = n / kBlock + 1;
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    const size_t o_vel = up(12 * n), o_sca = o_vel + up(12 * n), o_blk = o_sca + up(4 * n), o_words = o_blk + up(4 * nblk), total = o_words + 256;
+    HIP_TRY(h, hipMalloc((void **)&b.base, total));
+    b.pos = (float *)b.base; b.vel = (float *)(b.base + o_vel); b.sca = (float *)(b.base + o_sca);
+    b.blk = (int *)(b.base + o_blk); b.words = (int *)(b.base + o_words);
+    HIP_TRY(h, hipMemsetAsync(b.words, 0, 256, h->stream));
+    return SPH_OK;
+}
+
+// step 1: `cut` and `own` for this rank, or the refusal
+int slab_state_plan(SphHandle *h, const float *pos, StateBuf &b, std::vector<int> &cut, int &own)
+{
+    const Consts &c = h->c;
+    hipStream_t s = h->stream;
+    int rc = state_buf_alloc(h, b);
+    if (rc) return rc;
+    HIP_TRY(h, hipMemsetAsync(h->col_hist, 0, sizeof(int) * (size_t)c.gx, s));
+    for (int first = 0; first < h->N; first += b.chunk) {
+        const int m = std::min(b.chunk, h->N - first);
+        HIP_TRY(h, hipMemcpyAsync(b.pos, pos + 3 * (size_t)first, sizeof(float) * 3 * (size_t)m, hipMemcpyHostToDevice, s));
+        ProfScope ps(h, K_SLAB);
+        hipLaunchKernelGGL(k_state_histogram, grid_for(m), dim3(kBlock), 0, s, c, m, b.pos, h->col_hist, b.words + 1);
+    }
+    HIP_TRY(h, hipGetLastError());
+    int bad = 0;
+    HIP_TRY(h, hipMemcpyAsync(h->col_hist_host, h->col_hist, sizeof(int) * (size_t)c.gx, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(&bad, b.words + 1, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    if (bad & 1) return fail(h, SPH_E_INVALID, "sph_slab_set_state: a position is not finite");
+    if (bad & 2) return fail(h, SPH_E_INVALID, "sph_slab_set_state: a position lies in no cell of the grid (no slab can own it)");
+    std::vector<long long> hist((size_t)c.gx);
+    long long total = 0;
+    for (int x = 0; x < c.gx; ++x) { hist[(size_t)x] = h->col_hist_host[x]; total += hist[(size_t)x]; }
+    if (total != h->N) return fail(h, SPH_E_STATE, "sph_slab_set_state: the column histogram counts %lld of %d particles", total, h->N);
+    std::string why;
+    if (!plan_slab_cuts_hist(hist, h->N, c.gx, h->nslab, cut, why, h->geom.layers)) return fail(h, SPH_E_INVALID, "%s", why.c_str());
+    long long mine = 0;
+    for (int x = cut[(size_t)h->slab_rank]; x < cut[(size_t)h->slab_rank + 1]; ++x) mine += hist[(size_t)x];
+    if (mine > h->ncap) return fail(h, SPH_E_OVERFLOW, "sph_slab_set_state: slab %d would own %lld particles, its capacity is %d (slab_capacity)", h->slab_rank, mine, h->ncap);
+    own = (int)mine;
+    return SPH_OK;
+}
+
+// step 3 (every rank has agreed): nothing below may refuse
+int slab_state_commit(SphHandle *h, const float *pos, const float *vel, const float *scalar, double delta_time, StateBuf &b, const std::vector<int> &cut, int own)
+{
+    Consts &c = h->c;
+    hipStream_t s = h->stream;
+    int rc;
+    h->cuts = cut;
+    set_slab_geometry(h);
+    if ((rc = slab_local_grid(h))) return rc;                 // the slab's cell slots follow its columns
+    // everything resident goes -- owned particles, ghosts, dead slots -- and with it what the steps so far left behind: per-particle fields, the edge
+    // lists, DensFlow's stamps and flags, tile flags and orders, what a correction that ran ahead saved.  A new handle's arena is all zeros (dcommit)
+    const void *gone[] = {h->P[0], h->P[1], h->V[0], h->V[1], h->VA[0], h->VA[1], h->warm[0], h->warm[1], h->id[0], h->id[1], h->X[0], h->X[1], h->X[2], h->X[3], h->X[4],
+                          h->rho, h->aux, h->drho, h->rho_adv, h->krho, h->cnt, h->wall_grad, h->wall_gsq, h->wave_dirty, h->changed8, h->dens_hot, h->dens_order,
+                          h->tile_nbr, h->need6, h->need7, h->tile_nz, h->worked6, h->worked7, h->dens_bcast, h->stage_cnt, h->cell_of, h->rank, h->slot_src,
+                          h->psum, h->pcnt, h->pmax, h->dead, h->edge_off[0], h->edge_off[1], h->edge_off[2], h->edge_off[3], h->edge_off[4], h->edge_off[5],
+                          h->edge_off[6], h->edge_off[7], h->edge_list[0], h->edge_list[1], h->edge_list[2], h->edge_list[3], h->counters, h->class_cnt,
+                          h->tile_flag, h->tile_order, h->spec_v, h->spec_w};
+    for (const void *p : gone)
+        if (const size_t bytes = p ? dalloc_bytes(h, p) : 0) HIP_TRY(h, hipMemsetAsync(const_cast<void *>(p), 0, bytes, s));
+    float *warm = carries_scalar(h) ? h->warm[h->wcur] : nullptr;
+    for (int first = 0; first < h->N; first += b.chunk) {
+        const int m = std::min(b.chunk, h->N - first), nblk = (int)grid_for(m).x;
+        HIP_TRY(h, hipMemcpyAsync(b.pos, pos + 3 * (size_t)first, sizeof(float) * 3 * (size_t)m, hipMemcpyHostToDevice, s));
+        if (vel) HIP_TRY(h, hipMemcpyAsync(b.vel, vel + 3 * (size_t)first, sizeof(float) * 3 * (size_t)m, hipMemcpyHostToDevice, s));
+        if (scalar && warm) HIP_TRY(h, hipMemcpyAsync(b.sca, scalar + (size_t)first, sizeof(float) * (size_t)m, hipMemcpyHostToDevice, s));
+        ProfScope ps(h, K_SLAB);
+        hipLaunchKernelGGL(k_state_count, dim3(nblk), dim3(kBlock), 0, s, c, h->geom.x_lo, h->geom.x_hi, m, b.pos, b.blk);
+        hipLaunchKernelGGL(k_state_scan, dim3(1), dim3(kScanBlock), 0, s, nblk, b.blk, b.words);
+        hipLaunchKernelGGL(k_state_write, dim3(nblk), dim3(kBlock), 0, s, c, h->geom.x_lo, h->geom.x_hi, m, first, b.pos, vel ? b.vel : (const float *)nullptr,
+                           (scalar && warm) ? b.sca : (const float *)nullptr, b.blk, h->ncap, h->P[h->pcur], h->V[h->vcur], warm, h->id[h->icur], h->dead);
+    }
+    HIP_TRY(h, hipGetLastError());
+    int placed = -1;
+    HIP_TRY(h, hipMemcpyAsync(&placed, b.words, sizeof(int), hipMemcpyDeviceToHost, s));
+    // the control block as alloc_device leaves it, but for the time steps it holds
+    if ((rc = read_scalars(h))) return rc;
+    if (placed != own) return fail(h, SPH_E_STATE, "internal: sph_slab_set_state placed %d particles on slab %d, the histogram counted %d", placed, h->slab_rank, own);
+    const float dt = h->ds_host->dt, dt2 = h->ds_host->dt2, ps_dt = h->ds_host->ps_dt;
+    memset(h->ds_host, 0, sizeof(DevScalars));
+    h->ds_host->dt = dt; h->ds_host->dt2 = dt2; h->ds_host->ps_dt = ps_dt;
+    h->ds_host->moved = 1;
+    loop_params(h, h->ds_host);
+    HIP_TRY(h, hipMemcpyAsync(h->ds, h->ds_host, sizeof(DevScalars), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    if (delta_time > 0.0 && (rc = write_delta_time(h, delta_time))) return rc;
+    h->n_owned = own; h->n_ghost = 0; h->n_dead = 0;
+    c.n = own;
+    h->nblocks = (c.n + kBlock - 1) / kBlock;
+    for (int k = 0; k < 4; ++k) h->edge_n[k][0] = h->edge_n[k][1] = 0;
+    h->cuts_moved = true;                     // the next step exchanges in two rounds (migrate, then ghosts), as after any change of the cuts
+    h->nl_valid = false; h->density_valid = false; h->lists_predate_flag = false;
+    h->flow_stamp = h->flow_last = 0; h->flow_d6 = kNoFlow;
+    h->dens_sparse = false; h->dens_first = true; h->pending_div = kNoRide;
+    h->last_iters = 2; h->pb_final = 0;
+    return SPH_OK;
+}
+
+int slab_set_state(SphHandle *h, const float *pos, const float *vel, const float *scalar, size_t n_fluid, double delta_time)
+{
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    StateBuf b;
+    std::vector<int> cut;
+    int own = 0;
+    int mine = SPH_OK;
+    if (h->rigid) mine = fail(h, SPH_E_STATE, "sph_slab_set_state: a handle with a rigid body keeps its state (no rigid state can be uploaded)");
+    else if (!pos || n_fluid != (size_t)h->N) mine = fail(h, SPH_E_INVALID, "sph_slab_set_state: the scene holds %d particles, got %zu", h->N, n_fluid);
+    else if (scalar && !carries_scalar(h)) mine = fail(h, SPH_E_INVALID, "sph_slab_set_state: no per-particle scalar travels with a particle on this solver, pass NULL");
+    else if (!(delta_time >= 0.0) || !std::isfinite(delta_time)) mine = fail(h, SPH_E_INVALID, "sph_slab_set_state: delta_time > 0, or 0 to keep the handle's");
+    else mine = slab_state_plan(h, pos, b, cut, own);
+    // the ranks' verdicts: codes are negative, the gravest is the largest magnitude
+    double v[1] = {(double)-mine};
+    int rc = slab_allreduce_host(h, v, 1, 1);
+    if (rc) return rc;
+    const int all = -(int)v[0];
+    if (all != SPH_OK) return mine ? mine : fail(h, all, "sph_slab_set_state was refused on another slab (code %d): no handle was changed", all);
+    return slab_state_commit(h, pos, vel, scalar, delta_time, b, cut, own);
+}

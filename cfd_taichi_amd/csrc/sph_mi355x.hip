@@ -120,6 +120,7 @@ struct SphHandle {
     int *wcell_start = nullptr;
     std::vector<std::pair<void **, size_t>> plan;   // dalloc() requests not yet committed
     std::vector<char *> arenas;                      // dcommit() allocations
+    std::vector<std::pair<const void *, size_t>> blocks;   // ... and every array in them with its bytes (dalloc_bytes)
     int *tile_rank = nullptr;            // Consts.tile_rank
     // slab handles on the Morton curve keep the cell slots of THEIR columns only (slab_local_grid): the whole grid's tile ranks, and the slot count the
     // cell arrays were allocated for
@@ -519,7 +520,7 @@ int sph_upload(SphHandle *h, int species, int field, const float *host, size_t n
     if (count != n_floats) return fail(h, SPH_E_INVALID, "field %d holds %zu floats, got %zu", field, count, n_floats);
     if (species != SPH_SPECIES_FLUID || !(field == SPH_F_POS || field == SPH_F_VEL || field == SPH_F_WARM_K))
         return fail(h, SPH_E_INVALID, "field %d is read-only", field);
-    if (h->slab) return fail(h, SPH_E_STATE, "sph_upload is not available on a slab handle");
+    if (h->slab) return fail(h, SPH_E_STATE, "sph_upload is not available on a slab handle: sph_slab_set_state replaces its whole state (pos, vel, the travelling scalar, delta_time)");
     if (field == SPH_F_WARM_K && h->cfg.solver != SPH_SOLVER_DFSPH) return fail(h, SPH_E_STATE, "warm_start_k needs a dfsph handle");
     hipStream_t s = h->stream;
     HIP_TRY(h, hipMemcpyAsync(h->staging, host, sizeof(float) * count, hipMemcpyHostToDevice, s));
@@ -833,6 +834,15 @@ int sph_slab_set_overlap(SphHandle *h, int32_t on)
     return SPH_OK;
 }
 
+int sph_slab_set_state(SphHandle *h, const float *pos, const float *vel, const float *scalar, size_t n_fluid, double delta_time)
+{
+    if (!h) return SPH_E_INVALID;
+    if (!h->slab) return fail(h, SPH_E_STATE, "sph_slab_set_state needs a handle created with slab_count > 1 (one GPU: sph_upload + sph_set_scalar)");
+    if (!h->comm_set) return fail(h, SPH_E_STATE, "slab handle needs sph_set_comm or sph_rccl_attach before sph_slab_set_state (the slabs agree on one verdict)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    return slab_set_state(h, pos, vel, scalar, n_fluid, delta_time);
+}
+
 int sph_download_ids(SphHandle *h, int32_t *host, size_t n)
 {
     if (!h || !host) return SPH_E_INVALID;
@@ -1134,21 +1144,8 @@ int sph_set_scalar(SphHandle *h, int which, double value)
     if (!h) return SPH_E_INVALID;
     if (which >= SPH_P_DENSITY_THRESHOLD && which <= SPH_P_TENSION_K) return set_param(h, which, value);      // (on slab handles too: every rank sets the same)
     if (which != SPH_S_DELTA_TIME || !(value > 0.0)) return fail(h, SPH_E_INVALID, "sph_set_scalar: SPH_S_DELTA_TIME > 0 or a solver attribute SPH_P_* can be written");
-    if (h->slab) return fail(h, SPH_E_STATE, "sph_set_scalar is not available on slab handles");
     HIP_TRY(h, hipSetDevice(h->device));
-    h->dt_wcsph = (float)value;                                      // the launch argument of the fixed-dt solvers
-    h->cfg.delta_time = value;
-    if (h->cfg.solver == SPH_SOLVER_DFSPH) {                         // dfsph keeps delta_time, delta_time_2 on the device (dfsph_solver.py:20, :118)
-        int rc = read_scalars(h);
-        if (rc) return rc;
-        h->ds_host->dt = (float)value;
-        h->ds_host->dt2 = h->ds_host->dt * h->ds_host->dt;
-        HIP_TRY(h, hipMemcpyAsync(h->ds, h->ds_host, offsetof(DevScalars, ps_dt), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-    }
-    for (int k = 0; k < 8; ++k)                                      // captured wcsph step pairs carry the old delta_time as a launch argument
-        if (h->wcsph_graph[k]) { (void)hipGraphExecDestroy(h->wcsph_graph[k]); h->wcsph_graph[k] = nullptr; }
-    return SPH_OK;
+    return write_delta_time(h, value);                               // (on slab handles too: every rank writes the same)
 }
 
 const char *sph_overrides(SphHandle *h) { return h ? h->overrides.c_str() : ""; }

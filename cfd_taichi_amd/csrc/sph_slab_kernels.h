@@ -538,4 +538,113 @@ __global__ __launch_bounds__(kBlock) void k_copy_vec_local(int n, const float4 *
     dst[3 * (size_t)s] = v.x; dst[3 * (size_t)s + 1] = v.y; dst[3 * (size_t)s + 2] = v.z;
 }
 
+// ---------------------------------------------------------------------------------------------
+// sph_slab_set_state: a slab handle's owned set from a FULL state in original particle order.  The state streams through a bounded device
+// buffer in chunks of `n` particles (pos = 3 n floats, particle `first_id + i` at i); none of this is on the per-step path.
+//   pass A  k_state_histogram   particles per cell column over the whole state (every rank the same gx ints: the cuts are planned from them) and the
+//                               refusals -- bit 0 of *bad: a coordinate that is not finite, bit 1: a cell outside the grid (no slab owns it)
+//   pass B  k_state_count / k_state_scan / k_state_write   the particles of columns [x_lo, x_hi) compacted into P, V, the travelling scalar and id[]
+//                               in ascending original id: per-workgroup counts, one workgroup's exclusive scan over them (+ what the chunks before
+//                               placed), then every lane's slot = its workgroup's offset + the waves before it + its rank inside the wave.
+// The column is cell_id_of's cx -- the expression k_classify_count and the counting sort bin by -- so a particle on a column boundary gets the owner
+// the step would give it.  Integer atomics only (LDS, then one global add per touched column and workgroup); the order of pass B is the id order.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ int state_column(const Consts &c, const float *__restrict__ pos, int i, int &bad)
+{
+    const float x = pos[3 * (size_t)i], y = pos[3 * (size_t)i + 1], z = pos[3 * (size_t)i + 2];
+    bad = 0;
+    if (!(fabsf(x) <= 3.402823466e+38f && fabsf(y) <= 3.402823466e+38f && fabsf(z) <= 3.402823466e+38f)) { bad = 1; return -1; }   // NaN, +-inf
+    int cx, cy, cz;
+    const int cid = cell_id_of(c, x, y, z, cx, cy, cz);
+    if (cid >= c.C || cx < 0 || cx >= c.gx || cy < 0 || cy >= c.gy || cz < 0 || cz >= c.gz) { bad = 2; return -1; }
+    return cx;
+}
+__global__ __launch_bounds__(kBlock) void k_state_histogram(Consts c, int n, const float *__restrict__ pos, int *__restrict__ hist, int *__restrict__ bad)
+{
+    constexpr int kLocal = 2048;
+    __shared__ int local[kLocal];
+    const bool use_lds = c.gx <= kLocal;
+    if (use_lds) {
+        for (int x = threadIdx.x; x < c.gx; x += kBlock) local[x] = 0;
+        __syncthreads();
+    }
+    const int i = blockIdx.x * kBlock + threadIdx.x, lane = threadIdx.x & 63;
+    int flag = 0, col = -1;
+    if (i < n) col = state_column(c, pos, i, flag);
+    // one add per wave and distinct column: the lanes of the first uncounted lane's column are summed over the wave (wave_sum), that lane adds
+    unsigned long long todo = __ballot(col >= 0);
+    while (todo) {
+        const int leader = __ffsll((long long)todo) - 1;
+        const int x = __shfl(col, leader, 64);
+        const bool mine = col == x;
+        const int cnt = wave_sum(mine ? 1 : 0);
+        if (lane == leader) atomicAdd(use_lds ? &local[x] : &hist[x], cnt);
+        todo &= ~__ballot(mine);
+    }
+    flag = wave_max(flag & 1) | wave_max(flag & 2);
+    if (use_lds) {
+        __syncthreads();
+        for (int x = threadIdx.x; x < c.gx; x += kBlock)
+            if (local[x]) atomicAdd(&hist[x], local[x]);
+    }
+    if (lane == 0 && flag) atomicOr(bad, flag);
+}
+__device__ __forceinline__ bool state_owned(const Consts &c, int x_lo, int x_hi, int n, const float *__restrict__ pos, int i)
+{
+    int bad;
+    const int col = i < n ? state_column(c, pos, i, bad) : -1;
+    return col >= x_lo && col < x_hi;
+}
+__global__ __launch_bounds__(kBlock) void k_state_count(Consts c, int x_lo, int x_hi, int n, const float *__restrict__ pos, int *__restrict__ blk_cnt)
+{
+    __shared__ int s_cnt[kBlock / 64];
+    const bool own = state_owned(c, x_lo, x_hi, n, pos, blockIdx.x * kBlock + threadIdx.x);
+    const int cnt = wave_sum(own ? 1 : 0);
+    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int t = 0;
+        for (int w = 0; w < kBlock / 64; ++w) t += s_cnt[w];
+        blk_cnt[blockIdx.x] = t;
+    }
+}
+// one workgroup: blk_cnt[0..nblk) -> exclusive offsets, starting at *placed (what the chunks before this one placed); *placed += the chunk's total
+__global__ __launch_bounds__(kScanBlock) void k_state_scan(int nblk, int *__restrict__ blk_cnt, int *__restrict__ placed)
+{
+    __shared__ int s_w[kScanBlock / 64];
+    const int per = (nblk + kScanBlock - 1) / kScanBlock;
+    const int lo = min((int)threadIdx.x * per, nblk), hi = min(lo + per, nblk);
+    int t = 0;
+    for (int i = lo; i < hi; ++i) t += blk_cnt[i];
+    const int inc = wave_inclusive_scan(t);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 63) s_w[w] = inc;
+    const int base = *placed;
+    __syncthreads();
+    int before = base + inc - t, total = 0;
+    for (int q = 0; q < kScanBlock / 64; ++q) { if (q < w) before += s_w[q]; total += s_w[q]; }
+    for (int i = lo; i < hi; ++i) { const int v = blk_cnt[i]; blk_cnt[i] = before; before += v; }
+    if (threadIdx.x == 0) *placed = base + total;
+}
+// (cap: the arrays' capacity -- the host has checked the owned count against it from the histogram; no slot beyond it is ever written)
+__global__ __launch_bounds__(kBlock) void k_state_write(Consts c, int x_lo, int x_hi, int n, int first_id, const float *__restrict__ pos, const float *__restrict__ vel,
+                                                        const float *__restrict__ scalar, const int *__restrict__ blk_off, int cap, float4 *__restrict__ P,
+                                                        float4 *__restrict__ V, float *__restrict__ S, int *__restrict__ id, int *__restrict__ dead)
+{
+    __shared__ int s_cnt[kBlock / 64];
+    const int i = blockIdx.x * kBlock + threadIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const bool own = state_owned(c, x_lo, x_hi, n, pos, i);
+    const int inc = wave_inclusive_scan(own ? 1 : 0);
+    if (lane == 63) s_cnt[w] = inc;
+    __syncthreads();
+    int slot = blk_off[blockIdx.x] + inc - 1;
+    for (int q = 0; q < w; ++q) slot += s_cnt[q];
+    if (!own || slot >= cap) return;
+    P[slot] = make_float4(pos[3 * (size_t)i], pos[3 * (size_t)i + 1], pos[3 * (size_t)i + 2], 0.f);
+    V[slot] = vel ? make_float4(vel[3 * (size_t)i], vel[3 * (size_t)i + 1], vel[3 * (size_t)i + 2], 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
+    if (S) S[slot] = scalar ? scalar[i] : 0.f;
+    id[slot] = first_id + i;
+    dead[slot] = 0;
+}
+
 }  // namespace sph

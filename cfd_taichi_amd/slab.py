@@ -279,5 +279,30 @@ class SlabSimulation:
                                (int((seen == 0).sum()), int((seen > 1).sum())))
         return out
 
+    def set_state(self, pos, vel=None, scalar=None, delta_time=None, src=None, group=None):
+        """Collective: replace the sharded run's state by one full state in original particle order -- pos (n, 3), vel (n, 3) or None
+        (zeros), scalar (n,) = the per-particle scalar that travels with a particle (dfsph warm_start_k) or None, delta_time or None (keep).
+        Every rank passes the same arrays; with src=RANK only that rank's arguments count and are broadcast through torch.distributed.
+        The cuts are planned anew from the positions; a refusal raises the same SphError on every rank and leaves every handle as it was."""
+        if src is not None:
+            import torch.distributed as dist
+            box = [(pos, vel, scalar, delta_time) if self.rank == src else None]
+            dist.broadcast_object_list(box, src=src, group=group)
+            pos, vel, scalar, delta_time = box[0]
+        try:
+            self.sim.slab_set_state(pos, vel, scalar, delta_time or 0.0)
+        except nat.SphError:
+            if self.comm is not None and self.comm.error is not None:
+                raise self.comm.error
+            raise
+
+    def state(self, dst=0):
+        """(pos, vel, scalar, delta_time) of the whole run in original particle order on rank `dst` (else None): what set_state takes.
+        scalar is None where the solver carries none."""
+        pos, vel = self.gather(nat.F_POS, dst), self.gather(nat.F_VEL, dst)
+        scalar = self.gather(nat.F_WARM_K, dst) if self.solver == "dfsph" else None
+        dt = self.sim.scalar(nat.S_DELTA_TIME)
+        return (pos, vel, scalar, dt) if self.rank == dst else None
+
     def close(self):
         self.sim.close()

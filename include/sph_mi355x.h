@@ -355,6 +355,18 @@ int sph_comm_stats(SphHandle *h, int64_t *out8, int reset);
 /* local (device-order) access for slab handles: all resident particles, owned and ghost; ids < 0 mark ghosts (~id) */
 int sph_download_local(SphHandle *h, int field, float *host, size_t n_floats);
 int sph_download_ids(SphHandle *h, int32_t *host, size_t n);
+/* Start (or continue) a sharded run from any state: replaces everything resident on a slab handle -- owned particles, ghosts, dead slots -- by
+ * its share of one FULL state.  Collective: every rank of the slab group calls it with the same arrays in ORIGINAL particle order: pos = 3 n_fluid
+ * floats, vel = 3 n_fluid floats or NULL (zeros), scalar = the per-particle scalar that travels with a particle on this solver (dfsph warm_start_k;
+ * n_fluid floats) or NULL (zeros; it must be NULL where the solver carries none); delta_time > 0 is written as sph_set_scalar(SPH_S_DELTA_TIME) writes
+ * it, 0 keeps the handle's.  The cuts are planned anew from the positions by the rule of sph_create (from a per-column histogram counted on the
+ * device, the same on every rank); afterwards the handle is a newly created slab handle that holds this state -- the step counter and the
+ * re-balancing counter keep their values, and the next step exchanges particles in two rounds, as after any change of the cuts.
+ * Refusals leave every rank's handle as it was, and every rank returns the same code (one max-reduce of the ranks' verdicts through the
+ * handle's transport, which therefore must be attached): SPH_E_STATE not a slab handle, or one with a rigid body; SPH_E_INVALID n_fluid is not the
+ * scene's particle count, a position that is not finite or lies in no cell of the grid, a scalar where none travels; SPH_E_OVERFLOW a rank would
+ * own more than its capacity (slab_capacity).  (sph_upload of a single field stays refused on slab handles.) */
+int sph_slab_set_state(SphHandle *h, const float *pos, const float *vel, const float *scalar, size_t n_fluid, double delta_time);
 
 /* device arithmetic self-test: out[i] = op(a[i], b[i]) evaluated on the GPU with the same
  * compiler flags as the sweeps (op 0: a/b, 1: sqrt(a), 2: cubic_kernel(a, h=b), 3..5:
