@@ -331,78 +331,82 @@ inline DensFlow dens_flow(SphHandle *h, bool d6)
     h->flow_last = df.stamp_out;
     return df;
 }
-void launch_div_residual(SphHandle *h, int gate, int phase = 0, SpecUndo un = SpecUndo{nullptr, nullptr, nullptr, nullptr, 0}, hipStream_t st = nullptr)          // derivative_iter_all_rho sweep, dfsph_solver.py:252-277
+// Loop control of a residual sweep (ResidCtl in sph_kernels.h), D3 or D6 (`dens`).  D6 takes the next DensFlow stamp -- once per sweep: the interior
+// launch of a split sweep (phase 2) is the same sweep as its edge launch and reuses its stamps -- and the first one of a step computes every tile.
+inline ResidCtl residual_ctl(SphHandle *h, bool dens, int gate, int phase, SpecUndo un)
 {
-    const Consts &c = h->c;
-    if (!st) st = h->stream;
-    ProfScope ps(h, K_D_DIV_RESIDUAL, st);
-    const bool split = rx_split(h);
-    const TilePhase tp = split ? TilePhase{h->tile_order, h->nblocks, 1} : tile_phase(h, phase);
-    if (use_relaxed(h)) {
-        const TilePhase tpr = split ? TilePhase{h->tile_order, h->nblocks, 2} : tp;
-        hipLaunchKernelGGL(k_residual_rx<false>, grid_for(c.n), dim3(kBlock), sweep_lds(h, StagePV<>::kBytes), st, c, h->P[h->pcur], h->V[h->vcur],
-                           h->wall_grad, h->nl, h->cnt, h->rho, h->aux, h->ds, h->drho, h->psum, h->pcnt, gate, h->stage_src, h->stage_cnt, h->krho, (const int *)nullptr, (const unsigned char *)nullptr, 1, tpr, un);
-        if (!split) return;
-    }
-    // (the `< 20` gate reads get_neighbour_count, :258-261: a one-way body -- binned, not coupled -- takes the RIGID instantiation for its
-    // count, ncount from k_quirk_count; its lists hold no rigid entry, so the sums are the fluid-only ones)
-    SPH_LAUNCH_RMX(k_residual, false, rigid_binned(h), sweep_mode(h), relaxed_unstaged(h), c.n, sweep_lds(h, StagePV<>::kBytes), st, c,
-                  h->P[h->pcur], h->V[h->vcur], h->WP, h->nl, h->nlb, h->cnt, h->rho, h->aux, h->ds, h->drho, h->P[1 - h->pcur], h->psum, h->pcnt,
-                  rigid_binned(h) ? rigid_view(h) : RigidView(), h->ncount, gate, h->stage_src, h->stage_cnt, h->krho, (const int *)nullptr, (const unsigned char *)nullptr, 1,
-                  (const float4 *)wall_cache(h), tp, un);
+    ResidCtl lc{gate, rx_split(h) ? TilePhase{h->tile_order, h->nblocks, 1} : tile_phase(h, phase), kNoFlow, nullptr, nullptr, 1, un, h->psum, h->pcnt};
+    if (!dens) return lc;
+    lc.wave_dirty = tile_skip(h) ? h->wave_dirty : nullptr;
+    lc.changed8 = h->changed8;
+    lc.force_all = (h->dens_first || h->tune_all) ? 1 : 0;              // the first compute_all_rho_adv of a step computes every tile
+    if (phase != 1) h->dens_first = false;                              // (an edge launch is followed by the interior launch of the same sweep)
+    if (lc.wave_dirty) lc.df = phase == 2 ? h->flow_d6 : dens_flow(h, true);
+    h->flow_d6 = lc.df;
+    return lc;
 }
-
 // ride_mode >= 0 (one GPU, fin_rides): workgroup 0 of the launch takes the loop decision of evaluation `ride_eval` -- the residual sweep enqueued
 // before this one -- and the grid is one workgroup larger (fin_ride_block in sph_kernels.h)
 inline bool fin_rides(const SphHandle *h) { return !h->slab && h->spec_v != nullptr && !rx_split(h); }
+// Loop control of a correction sweep (CorrCtl), D2 / D4 / D7 (`mode`: CORR_*).  D7 under change propagation takes the next DensFlow stamp.
+inline CorrCtl correct_ctl(SphHandle *h, int mode, int gate, SpecSave sv, int ride_mode, int ride_eval)
+{
+    const bool split = rx_split(h), ride = ride_mode >= 0 && !split;
+    CorrCtl lc{h->ds, gate, split ? TilePhase{h->tile_order, h->nblocks, 1} : tile_phase(h, 0), kNoFlow, nullptr, h->changed8, sv, kNoRide};
+    lc.tp.shift = ride ? 1 : 0;
+    if (ride) lc.fr = FinRide{h->psum, h->pcnt, h->ds, h->nblocks, ride_mode, partial_group(h), partial_count(h), ride_eval};
+    if (mode == CORR_DENS && tile_skip(h) && !h->tune_all) { lc.wave_dirty = h->wave_dirty; lc.df = dens_flow(h, false); }      // change propagation in the density loop
+    return lc;
+}
+// the relaxed launch of a sweep: on rx_split handles it serves the second half of the tile order and the exact launch the first (TilePhase.phase)
+template <class Ctl> inline Ctl rx_half(Ctl lc, bool split) { if (split) lc.tp.phase = 2; return lc; }
+inline StageArgs stage_args(const SphHandle *h) { return StageArgs{h->stage_src, h->stage_cnt}; }
+
+// D3 / D6.  V = the velocities the residual is taken of, out = drho / rho_adv; `rg`: the RIGID instantiation
+template <bool DENS>
+void launch_residual(SphHandle *h, const ResidCtl &lc, const float4 *V, float *out, bool rg, hipStream_t st)
+{
+    const Consts &c = h->c;
+    const bool split = rx_split(h);
+    if (use_relaxed(h)) {
+        hipLaunchKernelGGL(k_residual_rx<DENS>, grid_for(c.n), dim3(kBlock), sweep_lds(h, StagePV<>::kBytes), st, c, h->P[h->pcur], V, h->wall_grad, h->nl, h->cnt,
+                           h->rho, h->aux, h->ds, out, h->krho, stage_args(h), rx_half(lc, split));
+        if (!split) return;
+    }
+    SPH_LAUNCH_RMX(k_residual, DENS, rg, sweep_mode(h), relaxed_unstaged(h), c.n, sweep_lds(h, StagePV<>::kBytes), st, c, h->P[h->pcur], V, h->WP, h->nl, h->nlb, h->cnt,
+                  h->rho, h->aux, h->ds, out, h->krho, stage_args(h), lc, h->P[1 - h->pcur], rg ? rigid_view(h) : RigidView(), h->ncount, (const float4 *)wall_cache(h));
+}
+void launch_div_residual(SphHandle *h, int gate, int phase = 0, SpecUndo un = SpecUndo{nullptr, nullptr, nullptr, nullptr, 0}, hipStream_t st = nullptr)          // derivative_iter_all_rho sweep, dfsph_solver.py:252-277
+{
+    if (!st) st = h->stream;
+    ProfScope ps(h, K_D_DIV_RESIDUAL, st);
+    // (the `< 20` gate reads get_neighbour_count, :258-261: a one-way body -- binned, not coupled -- takes the RIGID instantiation for its
+    // count, ncount from k_quirk_count; its lists hold no rigid entry, so the sums are the fluid-only ones)
+    launch_residual<false>(h, residual_ctl(h, false, gate, phase, un), h->V[h->vcur], h->drho, rigid_binned(h), st);
+}
+void launch_dens_residual(SphHandle *h, int gate, int phase = 0, hipStream_t st = nullptr)          // compute_all_rho_adv sweep, dfsph_solver.py:124-141
+{
+    if (!st) st = h->stream;
+    ProfScope ps(h, K_D_DENS_RESIDUAL, st);
+    launch_residual<true>(h, residual_ctl(h, true, gate, phase, SpecUndo{nullptr, nullptr, nullptr, nullptr, 0}), h->VA[0], h->rho_adv, rigid_coupled(h), st);
+}
+
 template <int MODE>
 void launch_correct(SphHandle *h, int kid, const float *src, float4 *V, int gate, SpecSave sv = SpecSave{nullptr, nullptr}, int ride_mode = -1, int ride_eval = -1)
 {
     const Consts &c = h->c;
     ProfScope ps(h, kid);
-    int *wdirty = (MODE == CORR_DENS && tile_skip(h) && !h->tune_all) ? h->wave_dirty : nullptr;      // change propagation in the density loop
     const bool split = rx_split(h);
-    const bool ride = ride_mode >= 0;
-    const FinRide fr = ride ? FinRide{h->psum, h->pcnt, h->ds, h->nblocks, ride_mode, partial_group(h), partial_count(h), ride_eval} : kNoRide;
-    TilePhase tp0 = tile_phase(h, 0);
-    tp0.shift = ride ? 1 : 0;
-    const DensFlow df = (MODE == CORR_DENS && wdirty) ? dens_flow(h, false) : kNoFlow;
-    const int n_grid = c.n + (ride ? (sweep_mode(h) == SWEEP_QUAD ? 64 : kBlock) : 0);           // one more workgroup
+    const CorrCtl lc = correct_ctl(h, MODE, gate, sv, ride_mode, ride_eval);
+    const int n_grid = c.n + (lc.fr.mode >= 0 ? (sweep_mode(h) == SWEEP_QUAD ? 64 : kBlock) : 0);           // a riding decision: one more workgroup
     if (use_relaxed(h)) {
-        hipLaunchKernelGGL(k_correct_rx<MODE>, grid_for(split ? c.n : n_grid), dim3(kBlock), sweep_lds(h, StagePS<>::kBytes), h->stream, c, h->P[h->pcur], h->wall_grad, h->nl, h->cnt,
-                           h->rho, h->aux, src, h->warm[h->wcur], h->ds, V, V, gate, h->stage_src, h->stage_cnt, h->krho, wdirty, h->changed8,
-                           split ? TilePhase{h->tile_order, h->nblocks, 2} : tp0, sv, split ? kNoRide : fr, df);
+        hipLaunchKernelGGL(k_correct_rx<MODE>, grid_for(n_grid), dim3(kBlock), sweep_lds(h, StagePS<>::kBytes), h->stream, c, h->P[h->pcur], h->wall_grad, h->nl, h->cnt,
+                           h->rho, h->aux, src, h->warm[h->wcur], V, V, h->krho, stage_args(h), rx_half(lc, split));
         if (!split) return;
     }
-    SPH_LAUNCH_RMX(k_correct, MODE, rigid_coupled(h), sweep_mode(h), relaxed_unstaged(h), split ? c.n : n_grid, sweep_lds(h, StagePS<>::kBytes), h->stream, c,
-                  c.kr_split ? h->P[h->pcur] : h->P[1 - h->pcur], h->WP,
-                  h->nl, h->nlb, h->cnt, h->rho, h->aux, src, h->warm[h->wcur], h->ds, V, V, rigid_view_or_none(h), gate, h->stage_src, h->stage_cnt, h->krho, wdirty, h->changed8,
-                  (const float4 *)wall_cache(h), split ? TilePhase{h->tile_order, h->nblocks, 1} : tp0, sv, split ? kNoRide : fr, df);
-}
-
-void launch_dens_residual(SphHandle *h, int gate, int phase = 0, hipStream_t st = nullptr)          // compute_all_rho_adv sweep, dfsph_solver.py:124-141
-{
-    const Consts &c = h->c;
-    if (!st) st = h->stream;
-    ProfScope ps(h, K_D_DENS_RESIDUAL, st);
-    const bool split = rx_split(h);
-    const TilePhase tp = split ? TilePhase{h->tile_order, h->nblocks, 1} : tile_phase(h, phase);
-    const int *wdirty = tile_skip(h) ? h->wave_dirty : nullptr;
-    const int force_all = (h->dens_first || h->tune_all) ? 1 : 0;      // the first compute_all_rho_adv of a step computes every tile
-    if (phase != 1) h->dens_first = false;                              // (an edge launch is followed by the interior launch of the same sweep)
-    // (the interior launch of a split sweep is the same sweep as its edge launch: the same stamps)
-    const DensFlow df = wdirty ? (phase == 2 ? h->flow_d6 : dens_flow(h, true)) : kNoFlow;
-    h->flow_d6 = df;
-    const SpecUndo no_undo{nullptr, nullptr, nullptr, nullptr, 0};
-    if (use_relaxed(h)) {
-        const TilePhase tpr = split ? TilePhase{h->tile_order, h->nblocks, 2} : tp;
-        hipLaunchKernelGGL(k_residual_rx<true>, grid_for(c.n), dim3(kBlock), sweep_lds(h, StagePV<>::kBytes), st, c, h->P[h->pcur], h->VA[0],
-                           h->wall_grad, h->nl, h->cnt, h->rho, h->aux, h->ds, h->rho_adv, h->psum, h->pcnt, gate, h->stage_src, h->stage_cnt, h->krho, wdirty, h->changed8, force_all, tpr, no_undo, df);
-        if (!split) return;
-    }
-    SPH_LAUNCH_RMX(k_residual, true, rigid_coupled(h), sweep_mode(h), relaxed_unstaged(h), c.n, sweep_lds(h, StagePV<>::kBytes), st, c,
-                  h->P[h->pcur], h->VA[0], h->WP, h->nl, h->nlb, h->cnt, h->rho, h->aux, h->ds, h->rho_adv, h->P[1 - h->pcur], h->psum, h->pcnt,
-                  rigid_view_or_none(h), h->ncount, gate, h->stage_src, h->stage_cnt, h->krho, wdirty, h->changed8, force_all, (const float4 *)wall_cache(h), tp, no_undo, df);
+    SPH_LAUNCH_RMX(k_correct, MODE, rigid_coupled(h), sweep_mode(h), relaxed_unstaged(h), n_grid, sweep_lds(h, StagePS<>::kBytes), h->stream, c,
+                  c.kr_split ? h->P[h->pcur] : h->P[1 - h->pcur], h->WP, h->nl, h->nlb, h->cnt, h->rho, h->aux, src, h->warm[h->wcur], V, V, h->krho,
+                  stage_args(h), lc, rigid_view_or_none(h), (const float4 *)wall_cache(h));
 }
 
 // The same in two halves, for the handles that hide the all-reduce (step_dfsph_device_loops): this slab's (sum, count) on the handle's stream ...

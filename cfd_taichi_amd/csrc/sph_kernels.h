@@ -69,7 +69,8 @@ constexpr int kStageMaxCells = 640;        // cell runs a workgroup's staging pl
 constexpr int kNbrStride = 64;            // ints per tile in DensFlow.nbr: header + up to 63 tiles
 constexpr int kNbrOdd = 1 << 30;
 struct DensFlow {
-    const int *nbr;                       // nullptr: off (slab handles, SPH_DENS_PUSH=0): the consumers read their staging plans as before
+    const int *nbr;                       // nullptr: off (no tile_nbr table: one-column slab handles, SPH_DENS_PUSH=0): the consumers read their staging plans
+                                          // as before.  Two-column slab handles have it: ghost tiles take the same heads, k_unpack_resid pushes for the ghosts
     const int *need_in; int *need_out;    // stamps per tile: what this launch consumes / produces
     int *nz;                              // per tile: its own k / rho holds a nonzero
     int *bcast;                           // [0]: "every tile must run D6", [1]: "... D7" (stamps)
@@ -85,6 +86,10 @@ constexpr DensFlow kNoFlow{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0,
 //   * the workgroups at the head of the working-tiles-first order request stage_cnt and their first cell run together with the need word.
 struct StagePre { int have; int sw; uint2 rn0; };
 constexpr StagePre kNoPre{0, 0, {0u, 0u}};
+// the staging plan of a launch (k_build_nl writes it): cell runs per tile and the per-tile header word
+struct StageArgs { const uint2 *src; const int *cnt; };
+// what stage_operands says of a tile.  kStagedIdle: staged (kCheckFirst: NOT copied), and no staged element's key is set.  Callers that want a bool test != kNotStaged.
+enum StageVerdict { kNotStaged = 0, kStaged = 1, kStagedIdle = 2 };
 // The head of a density-loop workgroup under DensFlow: everything its verdict needs, in ONE batch of independent loads -- a load behind a
 // branch (a short-circuit `||` is one) is a round trip of its own, ~0.8 us in a launch that is as long as its slowest workgroup lives.
 //   need    must this tile run?
@@ -116,6 +121,110 @@ __device__ __forceinline__ void flow_push(const DensFlow &df, int mine)
     const int hdr = __shfl(mine, 0, 64);
     if (hdr < 0 || (hdr & kNbrOdd) != 0) { if (lane == 0) df.bcast[df.bc_out] = df.stamp_out; }
     if (hdr >= 0 && lane >= 1 && lane <= (hdr & (kNbrStride - 1))) df.need_out[mine] = df.stamp_out;
+}
+
+// ---- the admission protocol of the density loop, stated once ----------------------------------------------------------------------------------
+// Whether a workgroup of D6 (k_residual<DENS>, k_residual_rx<true>) or D7 (k_correct<DENS>, k_correct_rx<DENS>) runs its tile, what it marks when it
+// leaves early and whom it tells when it worked: head -> [staging] -> notes / idle mark -> [pairs] -> tail / changed mark, the same three routines
+// for the exact and the relaxed kernel of a family.  Uniform per workgroup; every thread must call them.
+//   spread  D6: this launch skips unchanged tiles (change propagation on, and not the step's first residual, which computes every tile)
+//   flow    DensFlow is on: the sweep before said who must run; off, the tile reads the wave flags of its staging plan (stage_sources_flagged)
+// Marks: wave_dirty[wave] / changed8[particle] = "D7 changed this v*" (read by D6's checks), DensFlow.nz[tile] = "D6 left a k / rho != 0 here",
+// DensFlow.worked[tile] = the `direct` hint of the next iteration, TilePhase.hot[tile] = 0 left at the head, 1 left after the check, 2 worked.
+__device__ __forceinline__ bool stage_sources_flagged(const uint2 *__restrict__ stage_runs, int sw, int blk, const int *__restrict__ wave_flags);
+struct TileHead { bool leave, direct; StagePre pre; };
+
+// D6 head.  An idle tile's rho*, k / rho and block partial of the last iteration stand.  Where that k / rho is not zero (nz[tile], kept across the
+// launches in which the tile idles) the correction sweep behind this launch must still be told: the idle tile pushes.
+__device__ __forceinline__ TileHead resid_head(const TilePhase &tp, const DensFlow &df, bool spread, bool flow, int tile, int n2, const StageArgs &st,
+                                               const int *wave_dirty)
+{
+    TileHead h{false, false, kNoPre};
+    if (!spread) return h;
+    if (flow) {                                                      // ONE word: did the correction sweep before this launch change a velocity this tile stages?
+        const FlowHead fh = flow_head(tp, df, tile, n2, st.src, st.cnt);
+        h.pre = fh.pre; h.direct = fh.direct; h.leave = !fh.need;
+        if (h.leave && df.nz[tile] != 0 && threadIdx.x < 64) flow_push(df, df.nbr[(size_t)tile * kNbrStride + threadIdx.x]);
+        if (h.leave && h.direct && threadIdx.x == 0) df.worked[tile] = 0;
+    } else {
+        const int sw = st.cnt[tile];
+        h.leave = sw >= 0 && !stage_sources_flagged(st.src, sw, tile, wave_dirty);
+    }
+    if (tp.hot && threadIdx.x == 0 && h.leave) tp.hot[tile] = 0;
+    return h;
+}
+// D6 after staging; true: the tile leaves.  A tile that took the per-particle check first (spread, not direct) leaves on kStagedIdle -- no staged
+// particle's v* changed; its k / rho stands like an idle tile's, so it pushes like one -- and has worked otherwise.  A `direct` tile staged in one
+// batch with the bytes of the check riding along: they say whether it would have passed -- if not, it computes what stands this once and takes the
+// check again next time.  Without the bytes, unstaged, or with a staged set of no particles: it would.
+__device__ __forceinline__ bool resid_note_work(const TilePhase &tp, const DensFlow &df, bool spread, bool flow, bool direct, int tile, int verdict, int my_nbr)
+{
+    if (!spread) return false;
+    if (!direct) {
+        if (verdict == kStagedIdle) {
+            if (flow && df.nz[tile] != 0 && threadIdx.x < 64) flow_push(df, my_nbr);
+            if (tp.hot && threadIdx.x == 0) tp.hot[tile] = 1;
+            return true;
+        }
+        if (tp.hot && threadIdx.x == 0) tp.hot[tile] = 2;
+        if (flow && threadIdx.x == 0) df.worked[tile] = 1;
+        return false;
+    }
+    const int would = verdict != kStagedIdle;
+    if (flow && threadIdx.x == 0) df.worked[tile] = would ? 1 : 0;
+    if (tp.hot && threadIdx.x == 0) tp.hot[tile] = would ? 2 : 1;
+    return false;
+}
+// D6 tail: does this tile hold a k / rho != 0 (`nz`, per thread; a NaN counts)?  Then every tile that stages its particles must run the correction sweep.
+__device__ __forceinline__ void resid_tail(const DensFlow &df, bool flow, int tile, bool nz, int my_nbr)
+{
+    if (!flow) return;
+    const int nzf = __syncthreads_or(nz ? 1 : 0);
+    if (threadIdx.x == 0) df.nz[tile] = nzf ? 1 : 0;
+    if (nzf && threadIdx.x < 64) flow_push(df, my_nbr);
+}
+
+// D7 head: the residual sweep before this launch said which tiles can see a k / rho != 0; every other tile leaves after ONE word.  Its v* stays, as
+// the idle mark below would find out from the staged scalars themselves -- and it clears changed8 for EVERY particle of the tile, foreign ghosts
+// included, which the idle mark does not.  That is valid only because DensFlow is off wherever a foreign ghost's v* can change behind this rank's
+// back: one-column slab handles never get a tile_nbr table (flow == false there), and on two-column handles no ghost is foreign (Consts.ghost_walk).
+__device__ __forceinline__ TileHead corr_head(const Consts &c, const TilePhase &tp, const DensFlow &df, bool flow, int tile, int n2, const StageArgs &st,
+                                              int *wave_dirty, unsigned char *changed8)
+{
+    TileHead h{false, false, kNoPre};
+    if (!flow) return h;
+    const FlowHead fh = flow_head(tp, df, tile, n2, st.src, st.cnt);
+    h.pre = fh.pre; h.direct = fh.direct; h.leave = !fh.need;
+    if (h.leave) {
+        const int i0 = tile * kBlock + (int)threadIdx.x;
+        if ((threadIdx.x & 63) == 0) wave_dirty[tile * (kBlock / 64) + (threadIdx.x >> 6)] = 0;
+        if (i0 < c.n) changed8[i0] = 0;
+        if (h.direct && threadIdx.x == 0) df.worked[tile] = 0;
+    }
+    return h;
+}
+// D7, verdict kStagedIdle of the per-particle check: every k / rho this tile can see is 0, v* stays.  One-column slab handles: a ghost's v* is
+// refreshed from its owner after this sweep and may change behind this rank's back, whatever this rank can see -- a foreign ghost stays marked; on
+// two-column handles the inner ghosts are corrected HERE, from the same inputs as on their owner, and the outer ghosts' v* is never read.
+__device__ __forceinline__ void corr_mark_idle(const Consts &c, int *wave_dirty, unsigned char *changed8, int tile, int i, bool live, bool ghost)
+{
+    const bool foreign = live && ghost && !c.ghost_walk;
+    const unsigned long long anyg = __ballot(foreign);
+    if ((threadIdx.x & 63) == 0) wave_dirty[tile * (kBlock / 64) + (threadIdx.x >> 6)] = anyg != 0ull ? 1 : 0;
+    if (live) changed8[i] = foreign ? 1 : 0;
+}
+// D7 tail: did any lane of this wave apply a correction (`changed`, per thread: a foreign ghost always counts, see the idle mark; all sums +-0 do
+// not: v - (+-0) * dt leaves v)?  Under DensFlow every tile that stages a particle of a tile that moved must run the next residual sweep.
+__device__ __forceinline__ void corr_mark_changed(const DensFlow &df, bool flow, int *wave_dirty, unsigned char *changed8, int tile, int i, bool live,
+                                                  bool changed, int my_nbr)
+{
+    const unsigned long long any = __ballot(changed);
+    if ((threadIdx.x & 63) == 0) wave_dirty[tile * (kBlock / 64) + (threadIdx.x >> 6)] = any != 0ull ? 1 : 0;
+    if (live) changed8[i] = changed ? 1 : 0;
+    if (!flow) return;
+    const int moved = __syncthreads_or(changed ? 1 : 0);
+    if (moved && threadIdx.x < 64) flow_push(df, my_nbr);
+    if (threadIdx.x == 0) df.worked[tile] = moved ? 1 : 0;
 }
 __device__ __forceinline__ int sweep_tile(const TilePhase &tp, bool spread);
 __device__ __forceinline__ void spec_undo(const Consts &c, const SpecUndo &un, const DevScalars *__restrict__ ds, const TilePhase &tp)
@@ -1743,8 +1852,6 @@ struct StagePlan { const uint2 *runs; const int *cnt; int blk; StagePre pre = kN
 // kCheckFirst  two dependent phases: the keys are requested and voted on FIRST and stay in registers; only a workgroup with a key set
 //              requests the rest (one more round trip for it) -- for the others nothing is copied
 enum StageCheck { kCheckNone, kCheckWith, kCheckFirst };
-// kStagedIdle: staged (kCheckFirst: NOT copied), and no staged element's key is set.  Callers that want a bool test != kNotStaged.
-enum StageVerdict { kNotStaged = 0, kStaged = 1, kStagedIdle = 2 };
 // Uniform per workgroup; every thread of the workgroup must call it.  EMPTY: the verdict for a staged set of no particles (a workgroup of
 // ghosts only, slab handles) -- nothing is staged and no key is set, yet what follows from kStagedIdle differs per sweep: each checked
 // call site names its own.
@@ -2151,44 +2258,50 @@ __global__ __launch_bounds__(kBlock) void k_wcsph_force(Consts c, float dt, cons
 // ======================================================================================
 enum { CORR_WARM = 0, CORR_DIV = 1, CORR_DENS = 2 };
 
+// Loop control of a solver-loop sweep: what a workgroup reads ONCE to learn whether and where it runs -- one kernel argument, built by the host in
+// one place (residual_ctl / correct_ctl in sph_host_dfsph.h), the same type for the exact and the relaxed kernel of a family.  The operands of the
+// pair loop are not in here: they stay direct kernel parameters, whose __restrict__ a struct member would not carry.
+//   ds / gate: the device-side loop decision this launch obeys (gate_closed; the residual sweeps keep ds a direct __restrict__ parameter: as a member
+//   it cost four instantiations of k_residual one or two VGPRs each); tp: which tile this workgroup serves (sweep_tile); df: who must run (the
+//   admission routines at the head of this file); wave_dirty / changed8: the marks of the density loop's change propagation, nullptr = off
+struct ResidCtl {
+    int gate; TilePhase tp; DensFlow df; const int *wave_dirty; const unsigned char *changed8;
+    int force_all;                        // compute every tile (the first compute_all_rho_adv of a step, the divergence loop)
+    SpecUndo un;                          // what a launch whose gate is closed puts back (spec_undo)
+    double *psum; int *pcnt;              // block partials of the mean
+};
+struct CorrCtl {
+    const DevScalars *ds;                 // (workgroup 0 writes the same object through fr.ds -- the tile workgroups may read gate_hist[], dt, dt2 and the
+                                          // p_* parameters only, which fin_ride_block never writes)
+    int gate; TilePhase tp; DensFlow df; int *wave_dirty; unsigned char *changed8;
+    SpecSave sv;                          // where a correction that runs ahead of the loop decision leaves what it overwrites
+    FinRide fr;                           // mode >= 0: workgroup 0 takes the loop decision of the residual sweep before (fin_ride_block)
+};
+
 template <int MODE, bool RIGID, int SWEEP, bool RX = false>
 __global__ __launch_bounds__(kBlock) void k_correct(Consts c, const float4 *__restrict__ P, const float4 *__restrict__ WP,
                                                     const uint32_t *__restrict__ nl, const uint32_t *__restrict__ nlb,
                                                     const int *__restrict__ cnt, const float *__restrict__ rho,
                                                     const float *__restrict__ alpha, const float *__restrict__ src,   // drho (DIV) / rho_adv (DENS)
-                                                    float *__restrict__ warm, const DevScalars *ds,       // (no __restrict__: workgroup 0 writes the same object through fr.ds --
-                                                    // the tile workgroups may read gate_hist[], dt, dt2 and the p_* parameters only, which fin_ride_block never writes)
-                                                    const float4 *Vin, float4 *Vout, RigidView rv, int gate,
-                                                    const uint2 *__restrict__ stage_src, const int *__restrict__ stage_cnt, const float *__restrict__ krho,
-                                                    int *__restrict__ wave_dirty, unsigned char *__restrict__ changed8, const float4 *__restrict__ wall_gc,
-                                                    TilePhase tp, SpecSave sv = SpecSave{nullptr, nullptr}, FinRide fr = kNoRide, DensFlow df = kNoFlow)
+                                                    float *__restrict__ warm, const float4 *Vin, float4 *Vout, const float *__restrict__ krho,
+                                                    StageArgs st, CorrCtl lc, RigidView rv, const float4 *__restrict__ wall_gc)
 {
+    const DevScalars *const ds = lc.ds;
+    const TilePhase &tp = lc.tp; const DensFlow &df = lc.df; int *const wave_dirty = lc.wave_dirty; unsigned char *const changed8 = lc.changed8;
     constexpr bool STAGED = SWEEP == SWEEP_STAGED, QUAD = SWEEP == SWEEP_QUAD;
     using K = KF<RX>;                                        // kernel functions of the sweep's arithmetic (sph_device.h); RX: unstaged handles under SPH_ARITH_RELAXED
     extern __shared__ float4 s_operand[];
-    if (fr.mode >= 0 && blockIdx.x == 0) { fin_ride_block(fr); return; }          // the loop decision of the residual sweep before (whatever the gate says)
+    if (lc.fr.mode >= 0 && blockIdx.x == 0) { fin_ride_block(lc.fr); return; }    // the loop decision of the residual sweep before (whatever the gate says)
     // With change propagation most tiles of a launch return at once and the ones that work are neighbours in space (the floor layer):
     // under the XCD-contiguous mapping they would all land on one or two XCDs.  Those launches deal the tiles round-robin instead.
     // (the tile is looked up BEFORE the gate is tested: two independent scalar loads, one round trip)
     const int tile = sweep_tile(tp, MODE == CORR_DENS && wave_dirty != nullptr);
     const bool flow = MODE == CORR_DENS && STAGED && wave_dirty != nullptr && df.nbr != nullptr;
     const int n2 = (flow && tp.sparse) ? tp.sparse[tp.ntiles + 1] : 0;           // (see flow_head)
-    if (gate_closed(ds, gate)) return;     // Vin may alias Vout: each thread reads and writes only its own element
+    if (gate_closed(ds, lc.gate)) return;  // Vin may alias Vout: each thread reads and writes only its own element
     if (tile < 0) return;
-    // the residual sweep before this launch said which tiles can see a k / rho != 0 (DensFlow): every other tile leaves after ONE word
-    StagePre pre = kNoPre;
-    bool direct = false;                                     // this tile worked in the last iteration: no per-particle check, the operands in one batch
-    if (flow) {
-        const FlowHead fh = flow_head(tp, df, tile, n2, stage_src, stage_cnt);
-        pre = fh.pre; direct = fh.direct;
-        if (!fh.need) {                                      // v* stays, as verdict 2 below would find out from the staged scalars themselves
-            const int i0 = tile * kBlock + (int)threadIdx.x;
-            if ((threadIdx.x & 63) == 0) wave_dirty[tile * (kBlock / 64) + (threadIdx.x >> 6)] = 0;
-            if (i0 < c.n) changed8[i0] = 0;
-            if (direct && threadIdx.x == 0) df.worked[tile] = 0;
-            return;
-        }
-    }
+    const TileHead hd = corr_head(c, tp, df, flow, tile, n2, st, wave_dirty, changed8);
+    if (hd.leave) return;                                    // (DensFlow: nothing this tile stages holds a k / rho != 0)
     const int my_nbr = (flow && threadIdx.x < 64) ? df.nbr[(size_t)tile * kNbrStride + threadIdx.x] : 0;       // requested now, used by the push at the end
     SPH_SWEEP_PROLOGUE_G(QUAD, tile, true)
     // kr_split: P is the step's position array and k / rho of the neighbours comes from krho[]; else P = (pos, k / rho)
@@ -2206,23 +2319,15 @@ __global__ __launch_bounds__(kBlock) void k_correct(Consts c, const float4 *__re
         return;
     }
     bool staged;
-    if (track && !direct) {
+    if (track && !hd.direct) {
         // (a staged set of no particles: the split form goes on and computes, the packed form leaves as a zero tile -- as each always did)
-        const StagePlan plan{stage_src, stage_cnt, blk, pre};
+        const StagePlan plan{st.src, st.cnt, blk, hd.pre};
         const int verdict = split ? stage_operands<kCheckFirst, kStaged>(StagePS<true>{s_operand, P, krho}, plan)
                                   : stage_operands<kCheckWith, kStagedIdle>(StageF4<true>{s_operand, P}, plan);
-        if (verdict == kStagedIdle) {                                                        // every k / rho this tile can see is 0: v* stays
-            // (one-column slab handles: a ghost's v* is refreshed from its owner after this sweep and may change behind this rank's back,
-            // whatever this rank can see; on two-column handles the inner ghosts are corrected HERE, from the same inputs as on their owner)
-            const bool foreign = live && ghost && !c.ghost_walk;
-            const unsigned long long anyg = __ballot(foreign);
-            if ((threadIdx.x & 63) == 0) wave_dirty[blk * (kBlock / 64) + (threadIdx.x >> 6)] = anyg != 0ull ? 1 : 0;
-            if (live) changed8[i] = foreign ? 1 : 0;
-            return;
-        }
+        if (verdict == kStagedIdle) { corr_mark_idle(c, wave_dirty, changed8, blk, i, live, ghost); return; }
         staged = verdict == kStaged;
     } else {
-        const StagePlan plan{stage_src, stage_cnt, blk, pre};
+        const StagePlan plan{st.src, st.cnt, blk, hd.pre};
         staged = STAGED && (split ? stage_operands(StagePS<true>{s_operand, P, krho}, plan)
                                   : stage_operands(StageF4<true>{s_operand, P}, plan)) != kNotStaged;     // positions * 2^32
     }
@@ -2235,10 +2340,13 @@ __global__ __launch_bounds__(kBlock) void k_correct(Consts c, const float4 *__re
     const float kr_i = k_i / rho_i;
     float fa[3] = {0.f, 0.f, 0.f};
     float &ax = fa[0], &ay = fa[1], &az = fa[2];
-    auto pair = [&](const float4 pj, const float4, const uint32_t j) {
-        float dx = pi.x - pj.x, dy = pi.y - pj.y, dz = pi.z - pj.z;
-        float r = K::norm3(dx, dy, dz);
-        F3 g = K::grad_in(c, dx, dy, dz, r);
+    // one pair term; SCALED: every position carries 2^32 (staged operands) -- two multiplications less per pair, same bits
+    const float sx_i = pi.x * 0x1p32f, sy_i = pi.y * 0x1p32f, sz_i = pi.z * 0x1p32f;
+    auto pair_term = [&](auto scaled, const float4 pj, const uint32_t j) {
+        constexpr bool SCALED = decltype(scaled)::value;
+        float dx = (SCALED ? sx_i : pi.x) - pj.x, dy = (SCALED ? sy_i : pi.y) - pj.y, dz = (SCALED ? sz_i : pi.z) - pj.z;
+        float r = SCALED ? norm3_scaled(dx, dy, dz) : K::norm3(dx, dy, dz);
+        F3 g = SCALED ? grad_w_scaled(c, dx, dy, dz, r) : K::grad_in(c, dx, dy, dz, r);
         if (RIGID && (j & kRigidTag)) {
             float s = pj.w * c.rho0 * k_i / rho_i;                                // :345 / :377 / :211  (no 1e-5 gate)
             ax += s * g.x; ay += s * g.y; az += s * g.z;
@@ -2250,26 +2358,11 @@ __global__ __launch_bounds__(kBlock) void k_correct(Consts c, const float4 *__re
             }
         }
     };
-    // the same pair with every position carrying 2^32 (staged operands): two multiplications less per pair, same bits
-    const float sx_i = pi.x * 0x1p32f, sy_i = pi.y * 0x1p32f, sz_i = pi.z * 0x1p32f;
-    auto pair_scaled = [&](const float4 pj, const float4, const uint32_t j) {
-        float dx = sx_i - pj.x, dy = sy_i - pj.y, dz = sz_i - pj.z;
-        float r = norm3_scaled(dx, dy, dz);
-        F3 g = grad_w_scaled(c, dx, dy, dz, r);
-        if (RIGID && (j & kRigidTag)) {
-            float s = pj.w * c.rho0 * k_i / rho_i;
-            ax += s * g.x; ay += s * g.y; az += s * g.z;
-        } else {
-            float ks = kr_i + pj.w;
-            if (MODE != CORR_DIV || ks > 1e-5f) {
-                float s = c.m * ks;
-                ax += s * g.x; ay += s * g.y; az += s * g.z;
-            }
-        }
-    };
+    auto pair = [&](const float4 pj, const float4, const uint32_t j) { pair_term(std::false_type{}, pj, j); };
+    auto pair_scaled = [&](const float4 pj, const float4, const uint32_t j) { pair_term(std::true_type{}, pj, j); };
     struct OperandPS { float4 a; float s; };
     if (QUAD) for_fluid_nbrs_quad<RIGID, false>(nlp, kf, q, fa, P, nullptr, rv, pair);
-    else if (staged && (RIGID ? stage_lists16(stage_cnt, blk) : c.nl16 != 0)) for_staged16_nbrs(nlp, kf, s_operand, pair_scaled);
+    else if (staged && (RIGID ? stage_lists16(st.cnt, blk) : c.nl16 != 0)) for_staged16_nbrs(nlp, kf, s_operand, pair_scaled);
     else if (staged) for_staged_nbrs<RIGID, true>(nlp, kf, s_operand, rv, pair_scaled);
     else if (split)          // a workgroup of a kr_split handle whose set did not fit: two global gathers per neighbour (a tagged entry: the rigid sample)
         walk_list<OperandPS>(nlp, kf, [&](uint32_t j, OperandPS &o) {
@@ -2295,22 +2388,13 @@ __global__ __launch_bounds__(kBlock) void k_correct(Consts c, const float4 *__re
             bx += s * gv.x; by += s * gv.y; bz += s * gv.z;
         });
     else for_nbrs_p(nlbp, kb, WP, wall);
-    if (track) {       // did any lane of this wave apply a correction?  (all sums +-0: v - (+-0) * dt leaves v)
-        // (one-column slab handles: a ghost's v* is refreshed from its owner after this sweep, it may change behind this rank's back; two-column
-        // handles: the inner ghosts' corrections are computed here like everybody's, the outer ghosts' v* is never read)
+    if (track) {
         const bool changed = live && ((ghost && !c.ghost_walk) || ax != 0.f || ay != 0.f || az != 0.f || bx != 0.f || by != 0.f || bz != 0.f);
-        const unsigned long long any = __ballot(changed);
-        if ((threadIdx.x & 63) == 0) wave_dirty[blk * (kBlock / 64) + (threadIdx.x >> 6)] = any != 0ull ? 1 : 0;
-        if (live) changed8[i] = changed ? 1 : 0;
-        if (flow) {                                                               // every tile that stages a particle of this one must run the next residual sweep
-            const int moved = __syncthreads_or(changed ? 1 : 0);
-            if (moved && threadIdx.x < 64) flow_push(df, my_nbr);
-            if (threadIdx.x == 0) df.worked[tile] = moved ? 1 : 0;
-        }
+        corr_mark_changed(df, flow, wave_dirty, changed8, blk, i, live, changed, my_nbr);
     }
     if (!owner) return;
     float4 v = Vin[i];
-    if (MODE == CORR_DIV && sv.v) { sv.v[i] = v; sv.w[i] = warm[i]; }             // this sweep runs AHEAD of the loop decision: what the undo restores
+    if (MODE == CORR_DIV && lc.sv.v) { lc.sv.v[i] = v; lc.sv.w[i] = warm[i]; }    // this sweep runs AHEAD of the loop decision: what the undo restores
     if (c.boundary_handle) {
         // :322 / :310 ; for D7 :187 then :191 -- same association: (a + b*rho0) * dt
         v.x -= (ax + bx * c.rho0) * dt;
@@ -2336,108 +2420,64 @@ __global__ __launch_bounds__(kBlock) void k_residual(Consts c, const float4 *__r
                                                      const float4 *__restrict__ WP, const uint32_t *__restrict__ nl,
                                                      const uint32_t *__restrict__ nlb, const int *__restrict__ cnt,
                                                      const float *__restrict__ rho, const float *__restrict__ alpha,
-                                                     DevScalars *__restrict__ ds, float *__restrict__ out,
-                                                     float4 *__restrict__ Pout, double *__restrict__ psum, int *__restrict__ pcnt,
-                                                     RigidView rv, const int *__restrict__ ncount, int gate,
-                                                     const uint2 *__restrict__ stage_src, const int *__restrict__ stage_cnt, float *__restrict__ krho,
-                                                     const int *__restrict__ wave_dirty, const unsigned char *__restrict__ changed8, int force_all,
-                                                     const float4 *__restrict__ wall_gc, TilePhase tp, SpecUndo un = SpecUndo{nullptr, nullptr, nullptr, nullptr, 0},
-                                                     DensFlow df = kNoFlow)
+                                                     DevScalars *__restrict__ ds, float *__restrict__ out, float *__restrict__ krho, StageArgs st, ResidCtl lc,
+                                                     float4 *__restrict__ Pout, RigidView rv, const int *__restrict__ ncount,
+                                                     const float4 *__restrict__ wall_gc)
 {
+    const TilePhase &tp = lc.tp; const DensFlow &df = lc.df; const int *const wave_dirty = lc.wave_dirty; const unsigned char *const changed8 = lc.changed8;
     constexpr bool STAGED = SWEEP == SWEEP_STAGED, QUAD = SWEEP == SWEEP_QUAD;
     using K = KF<RX>;                                        // kernel functions of the sweep's arithmetic (sph_device.h); RX: unstaged handles under SPH_ARITH_RELAXED
     extern __shared__ float4 s_operand[];
     // (see k_correct: round-robin tiles when most of them return at once; the body does not move inside a solver loop, so its terms stand with v*)
-    const bool spread = DENS && STAGED && wave_dirty && !force_all;
+    const bool spread = DENS && STAGED && wave_dirty && !lc.force_all;
     const int tile = sweep_tile(tp, spread);
     const bool flow = DENS && STAGED && df.nbr != nullptr;           // the producer says who must run (DensFlow)
     const int n2 = (flow && spread && tp.sparse) ? tp.sparse[tp.ntiles + 1] : 0;      // (see flow_head)
-    if (gate_closed(ds, gate)) { spec_undo(c, un, ds, tp); return; }
+    if (gate_closed(ds, lc.gate)) { spec_undo(c, lc.un, ds, tp); return; }
     if (tile < 0) return;
-    StagePre pre = kNoPre;
-    bool direct = false;                                             // this tile worked in the last iteration: no per-particle check (see StagePre)
-    if (spread) {                                                    // change propagation, see stage_sources_flagged
-        bool idle;
-        if (flow) {
-            const FlowHead fh = flow_head(tp, df, tile, n2, stage_src, stage_cnt);
-            pre = fh.pre; direct = fh.direct;
-            idle = !fh.need;                                         // ONE word: did the correction sweep before this launch change a velocity this tile stages?
-            // its k / rho stands; where that is not zero, the correction sweep behind this launch must still be told
-            if (idle && df.nz[tile] != 0 && threadIdx.x < 64) flow_push(df, df.nbr[(size_t)tile * kNbrStride + threadIdx.x]);
-            if (idle && direct && threadIdx.x == 0) df.worked[tile] = 0;
-        } else {
-            const int sw = stage_cnt[tile];
-            idle = sw >= 0 && !stage_sources_flagged(stage_src, sw, tile, wave_dirty);
-        }
-        if (tp.hot && threadIdx.x == 0 && idle) tp.hot[tile] = 0;    // (hot: 0 = left here, 1 = left after the per-particle check, 2 = worked)
-        if (idle) return;                                            // rho*, k / rho and the block partial of the last iteration stand
-    }
+    const TileHead hd = resid_head(tp, df, spread, flow, tile, n2, st, wave_dirty);
+    if (hd.leave) return;                                            // rho*, k / rho and the block partial of the last iteration stand
     const int my_nbr = (flow && threadIdx.x < 64) ? df.nbr[(size_t)tile * kNbrStride + threadIdx.x] : 0;      // requested now, used by the push at the end
     SPH_SWEEP_PROLOGUE_B(QUAD, tile)
     // ... and a tile without an owned particle -- ghosts only -- computes no residual (the ghosts' values arrive with the halo): no staging, a zero partial
     if (c.ghost_walk && !__syncthreads_or(live && !ghost)) {
-        if (QUAD) block_partial_mean_quad(blk, 0.0, 0, owner, psum, pcnt);
-        else block_partial_mean(blk, 0.0, 0, psum, pcnt);
+        if (QUAD) block_partial_mean_quad(blk, 0.0, 0, owner, lc.psum, lc.pcnt);
+        else block_partial_mean(blk, 0.0, 0, lc.psum, lc.pcnt);
         if (flow && threadIdx.x == 0) df.nz[blk] = 0;               // (the ghosts' k / rho is pushed for by the kernel that unpacks it)
         return;
     }
     float2 *s_v2 = StagePV<true>::second(s_operand, c.stage_cap);
-    const StagePlan plan{stage_src, stage_cnt, blk, pre};
-    bool staged;
-    if (spread && !direct) {       // second level of the change propagation: did the v* of any staged PARTICLE change?  (the flagged waves said "maybe")
-        // (a staged set of no particles counts as changed: kStaged, the tile computes)
-        const int verdict = stage_operands<kCheckFirst, kStaged>(StagePV<true>{s_operand, s_v2, P, V, changed8}, plan);
-        if (verdict == kStagedIdle) {                                // (its k / rho stands like an idle tile's)
-            if (flow && df.nz[blk] != 0 && threadIdx.x < 64) flow_push(df, my_nbr);
-            if (tp.hot && threadIdx.x == 0) tp.hot[blk] = 1;
-            return;
-        }
-        staged = verdict == kStaged;
-    } else {
-        // (a `direct` tile: the bytes of the check ride in the staging batch and say whether it would have passed -- if not, it computes what
-        // stands this once and takes the check again next time.  Without the bytes, unstaged, or with a staged set of no particles: it would)
-        const int verdict = STAGED ? stage_operands<kCheckWith, kStaged>(StagePV<true>{s_operand, s_v2, P, V, (spread && direct) ? changed8 : nullptr}, plan) : kNotStaged;   // positions * 2^32
-        staged = verdict != kNotStaged;
-        const int would = verdict != kStagedIdle;
-        if (spread && flow && threadIdx.x == 0) df.worked[blk] = would ? 1 : 0;
-        if (spread && tp.hot && threadIdx.x == 0) tp.hot[blk] = would ? 2 : 1;
-    }
-    if (spread && !direct) {
-        if (tp.hot && threadIdx.x == 0) tp.hot[blk] = 2;
-        if (flow && threadIdx.x == 0) df.worked[blk] = 1;
-    }
+    const StagePlan plan{st.src, st.cnt, blk, hd.pre};
+    // second level of the change propagation: did the v* of any staged PARTICLE change?  A `direct` tile stages in one batch (resid_note_work)
+    int verdict;
+    if (spread && !hd.direct) verdict = stage_operands<kCheckFirst, kStaged>(StagePV<true>{s_operand, s_v2, P, V, changed8}, plan);
+    else verdict = STAGED ? stage_operands<kCheckWith, kStaged>(StagePV<true>{s_operand, s_v2, P, V, (spread && hd.direct) ? changed8 : nullptr}, plan) : kNotStaged;   // positions * 2^32
+    if (resid_note_work(tp, df, spread, flow, hd.direct, blk, verdict, my_nbr)) return;
+    const bool staged = verdict != kNotStaged;
     const float4 vi = V[ii];
     float fa[1] = {0.f};
     float &acc = fa[0];
     const int nq = RIGID ? (live ? ncount[ii] : 0) : kf;                          // ps.get_neighbour_count(i)
     const bool skip = !DENS && nq < 20;                                           // :258-261
     const float dt_r = RIGID ? ds->dt : 0.f;
-    auto pair = [&](const float4 pj, const float4 vj, const uint32_t j) {
-        float dx = pi.x - pj.x, dy = pi.y - pj.y, dz = pi.z - pj.z;
-        float r = K::norm3(dx, dy, dz);
-        F3 g = K::grad_in(c, dx, dy, dz, r);
+    const float sx_i = pi.x * 0x1p32f, sy_i = pi.y * 0x1p32f, sz_i = pi.z * 0x1p32f;
+    auto pair_term = [&](auto scaled, const float4 pj, const float4 vj, const uint32_t j) {      // SCALED: positions carry 2^32 (see k_correct)
+        constexpr bool SCALED = decltype(scaled)::value;
+        float dx = (SCALED ? sx_i : pi.x) - pj.x, dy = (SCALED ? sy_i : pi.y) - pj.y, dz = (SCALED ? sz_i : pi.z) - pj.z;
+        float r = SCALED ? norm3_scaled(dx, dy, dz) : K::norm3(dx, dy, dz);
+        F3 g = SCALED ? grad_w_scaled(c, dx, dy, dz, r) : K::grad_in(c, dx, dy, dz, r);
         if (RIGID && (j & kRigidTag)) {
-            const F3 w = rigid_velocity(rv, pj, dt_r, DENS);                      // :292-293 / :168-169
+            const float4 pu = SCALED ? make_float4(pj.x * 0x1p-32f, pj.y * 0x1p-32f, pj.z * 0x1p-32f, pj.w) : pj;     // the rigid sample, un-scaled
+            const F3 w = rigid_velocity(rv, pu, dt_r, DENS);                      // :292-293 / :168-169
             acc += pj.w * c.rho0 * dot3(vi.x - w.x, vi.y - w.y, vi.z - w.z, g.x, g.y, g.z);   // :294 / :170
         } else {
             acc += c.m * dot3(vi.x - vj.x, vi.y - vj.y, vi.z - vj.z, g.x, g.y, g.z);          // :287 / :162
         }
     };
-    const float sx_i = pi.x * 0x1p32f, sy_i = pi.y * 0x1p32f, sz_i = pi.z * 0x1p32f;
-    auto pair_scaled = [&](const float4 pj, const float4 vj, const uint32_t j) {      // positions carry 2^32 (see k_correct)
-        float dx = sx_i - pj.x, dy = sy_i - pj.y, dz = sz_i - pj.z;
-        float r = norm3_scaled(dx, dy, dz);
-        F3 g = grad_w_scaled(c, dx, dy, dz, r);
-        if (RIGID && (j & kRigidTag)) {
-            const float4 pu = make_float4(pj.x * 0x1p-32f, pj.y * 0x1p-32f, pj.z * 0x1p-32f, pj.w);
-            const F3 w = rigid_velocity(rv, pu, dt_r, DENS);
-            acc += pj.w * c.rho0 * dot3(vi.x - w.x, vi.y - w.y, vi.z - w.z, g.x, g.y, g.z);
-        } else {
-            acc += c.m * dot3(vi.x - vj.x, vi.y - vj.y, vi.z - vj.z, g.x, g.y, g.z);
-        }
-    };
+    auto pair = [&](const float4 pj, const float4 vj, const uint32_t j) { pair_term(std::false_type{}, pj, vj, j); };
+    auto pair_scaled = [&](const float4 pj, const float4 vj, const uint32_t j) { pair_term(std::true_type{}, pj, vj, j); };
     if (QUAD) for_fluid_nbrs_quad<RIGID, true>(nlp, skip ? 0 : kf, q, fa, P, V, rv, pair);
-    else if (staged && (RIGID ? stage_lists16(stage_cnt, blk) : c.nl16 != 0)) for_staged16_nbrs_pv2(nlp, skip ? 0 : kf, s_operand, s_v2, pair_scaled);
+    else if (staged && (RIGID ? stage_lists16(st.cnt, blk) : c.nl16 != 0)) for_staged16_nbrs_pv2(nlp, skip ? 0 : kf, s_operand, s_v2, pair_scaled);
     else if (staged) for_staged_nbrs_pv2<RIGID, true>(nlp, skip ? 0 : kf, s_operand, s_v2, rv, pair_scaled);
     else for_fluid_nbrs<RIGID, true>(nlp, skip ? 0 : kf, P, V, rv, pair);
     float wa[1] = {0.f};
@@ -2477,13 +2517,9 @@ __global__ __launch_bounds__(kBlock) void k_residual(Consts c, const float4 *__r
             else Pout[i] = make_float4(pi.x, pi.y, pi.z, kr);
         }
     }
-    if (QUAD) block_partial_mean_quad(blk, (double)val, flag, owner, psum, pcnt);
-    else block_partial_mean(blk, (double)val, flag, psum, pcnt);
-    if (flow) {                                                      // does this tile hold a k / rho != 0?  (a NaN counts)
-        const int nzf = __syncthreads_or((live && !ghost && kr != 0.f) ? 1 : 0);
-        if (threadIdx.x == 0) df.nz[blk] = nzf ? 1 : 0;
-        if (nzf && threadIdx.x < 64) flow_push(df, my_nbr);
-    }
+    if (QUAD) block_partial_mean_quad(blk, (double)val, flag, owner, lc.psum, lc.pcnt);
+    else block_partial_mean(blk, (double)val, flag, lc.psum, lc.pcnt);
+    resid_tail(df, flow, blk, live && !ghost && kr != 0.f, my_nbr);
 }
 
 // ======================================================================================

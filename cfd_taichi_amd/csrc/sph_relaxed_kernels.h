@@ -102,62 +102,29 @@ template <bool DENS>
 __global__ __launch_bounds__(kBlock) void k_residual_rx(Consts c, const float4 *__restrict__ P, const float4 *__restrict__ V,
                                                         const float4 *__restrict__ G, const uint32_t *__restrict__ nl, const int *__restrict__ cnt,
                                                         const float *__restrict__ rho, const float *__restrict__ alpha,
-                                                        DevScalars *__restrict__ ds, float *__restrict__ out,
-                                                        double *__restrict__ psum, int *__restrict__ pcnt, int gate,
-                                                        const uint2 *__restrict__ stage_src, const int *__restrict__ stage_cnt, float *__restrict__ krho,
-                                                        const int *__restrict__ wave_dirty, const unsigned char *__restrict__ changed8, int force_all, TilePhase tp,
-                                                        SpecUndo un = SpecUndo{nullptr, nullptr, nullptr, nullptr, 0}, DensFlow df = kNoFlow)
+                                                        DevScalars *__restrict__ ds, float *__restrict__ out, float *__restrict__ krho, StageArgs st, ResidCtl lc)
 {
     extern __shared__ float4 s_operand[];
-    const bool spread = DENS && wave_dirty && !force_all;           // (round-robin tiles when most of them return at once, see k_correct in sph_kernels.h)
+    const TilePhase &tp = lc.tp; const DensFlow &df = lc.df;
+    const bool spread = DENS && lc.wave_dirty && !lc.force_all;     // round-robin tiles when most of them return at once (resid_head in sph_kernels.h)
     const int tile = sweep_tile(tp, spread);
-    const bool flow = DENS && df.nbr != nullptr;                    // the producer says who must run (DensFlow in sph_kernels.h; k_residual is the commented form)
+    const bool flow = DENS && df.nbr != nullptr;                    // the producer says who must run (DensFlow in sph_kernels.h)
     const int n2 = (flow && spread && tp.sparse) ? tp.sparse[tp.ntiles + 1] : 0;
-    if (gate_closed(ds, gate)) { spec_undo(c, un, ds, tp); return; }
+    if (gate_closed(ds, lc.gate)) { spec_undo(c, lc.un, ds, tp); return; }
     if (tile < 0) return;
-    StagePre pre = kNoPre;
-    bool direct = false;
-    if (spread) {                                                   // change propagation between the sweeps of the density loop (sph_kernels.h)
-        bool idle;
-        if (flow) {
-            const FlowHead fh = flow_head(tp, df, tile, n2, stage_src, stage_cnt);
-            pre = fh.pre; direct = fh.direct;
-            idle = !fh.need;
-            if (idle && df.nz[tile] != 0 && threadIdx.x < 64) flow_push(df, df.nbr[(size_t)tile * kNbrStride + threadIdx.x]);
-            if (idle && direct && threadIdx.x == 0) df.worked[tile] = 0;
-        } else {
-            const int sw = stage_cnt[tile];
-            idle = sw >= 0 && !stage_sources_flagged(stage_src, sw, tile, wave_dirty);
-        }
-        if (tp.hot && threadIdx.x == 0 && idle) tp.hot[tile] = 0;
-        if (idle) return;
-    }
+    const TileHead hd = resid_head(tp, df, spread, flow, tile, n2, st, lc.wave_dirty);
+    if (hd.leave) return;
     const int my_nbr = (flow && threadIdx.x < 64) ? df.nbr[(size_t)tile * kNbrStride + threadIdx.x] : 0;
     const uint32_t *nlb = nullptr;
     SPH_SWEEP_PROLOGUE_B(false, tile)
     (void)nlbp;
     float2 *s_v2 = StagePV<>::second(s_operand, c.stage_cap);
-    const StagePlan plan{stage_src, stage_cnt, blk, pre};
-    bool staged;
-    if (spread && !direct) {       // second, exact level of the change propagation (k_residual in sph_kernels.h, the empty set included)
-        const int verdict = stage_operands<kCheckFirst, kStaged>(StagePV<>{s_operand, s_v2, P, V, changed8}, plan);
-        if (verdict == kStagedIdle) {
-            if (flow && df.nz[blk] != 0 && threadIdx.x < 64) flow_push(df, my_nbr);
-            if (tp.hot && threadIdx.x == 0) tp.hot[blk] = 1;
-            return;
-        }
-        staged = verdict == kStaged;
-    } else {                                                        // (see k_residual: a `direct` tile learns from the staging batch whether it would have passed the check)
-        const int verdict = stage_operands<kCheckWith, kStaged>(StagePV<>{s_operand, s_v2, P, V, (spread && direct) ? changed8 : nullptr}, plan);
-        staged = verdict != kNotStaged;
-        const int would = verdict != kStagedIdle;
-        if (spread && flow && threadIdx.x == 0) df.worked[blk] = would ? 1 : 0;
-        if (spread && tp.hot && threadIdx.x == 0) tp.hot[blk] = would ? 2 : 1;
-    }
-    if (spread && !direct) {
-        if (tp.hot && threadIdx.x == 0) tp.hot[blk] = 2;
-        if (flow && threadIdx.x == 0) df.worked[blk] = 1;
-    }
+    const StagePlan plan{st.src, st.cnt, blk, hd.pre};
+    int verdict;                   // the per-particle check first, or (a `direct` tile) with the staging batch: resid_note_work in sph_kernels.h
+    if (spread && !hd.direct) verdict = stage_operands<kCheckFirst, kStaged>(StagePV<>{s_operand, s_v2, P, V, lc.changed8}, plan);
+    else verdict = stage_operands<kCheckWith, kStaged>(StagePV<>{s_operand, s_v2, P, V, (spread && hd.direct) ? lc.changed8 : nullptr}, plan);
+    if (resid_note_work(tp, df, spread, flow, hd.direct, blk, verdict, my_nbr)) return;
+    const bool staged = verdict != kNotStaged;
     const float4 vi = V[ii];
     float acc = 0.f;
     const bool skip = !DENS && kf < 20;                                           // :258-261
@@ -200,12 +167,8 @@ __global__ __launch_bounds__(kBlock) void k_residual_rx(Consts c, const float4 *
             krho[i] = kr;
         }
     }
-    block_partial_mean(blk, (double)val, flag, psum, pcnt);
-    if (flow) {
-        const int nzf = __syncthreads_or((live && !ghost && kr != 0.f) ? 1 : 0);
-        if (threadIdx.x == 0) df.nz[blk] = nzf ? 1 : 0;
-        if (nzf && threadIdx.x < 64) flow_push(df, my_nbr);
-    }
+    block_partial_mean(blk, (double)val, flag, lc.psum, lc.pcnt);
+    resid_tail(df, flow, blk, live && !ghost && kr != 0.f, my_nbr);
 }
 
 // D2 / D4 / D7 (k_correct)                                       dfsph_solver.py:314-355, 302-312 + 357-391, 178-219
@@ -214,51 +177,34 @@ template <int MODE>
 __global__ __launch_bounds__(kBlock) void k_correct_rx(Consts c, const float4 *__restrict__ P, const float4 *__restrict__ G,
                                                        const uint32_t *__restrict__ nl, const int *__restrict__ cnt, const float *__restrict__ rho,
                                                        const float *__restrict__ alpha, const float *__restrict__ src,
-                                                       float *__restrict__ warm, const DevScalars *ds,       // (no __restrict__: see k_correct)
-                                                       const float4 *Vin, float4 *Vout, int gate,
-                                                       const uint2 *__restrict__ stage_src, const int *__restrict__ stage_cnt, const float *__restrict__ krho,
-                                                       int *__restrict__ wave_dirty, unsigned char *__restrict__ changed8, TilePhase tp,
-                                                       SpecSave sv = SpecSave{nullptr, nullptr}, FinRide fr = kNoRide, DensFlow df = kNoFlow)
+                                                       float *__restrict__ warm, const float4 *Vin, float4 *Vout, const float *__restrict__ krho,
+                                                       StageArgs st, CorrCtl lc)
 {
     extern __shared__ float4 s_operand[];
-    if (fr.mode >= 0 && blockIdx.x == 0) { fin_ride_block(fr); return; }          // (see k_correct: the loop decision rides in this launch)
+    if (lc.fr.mode >= 0 && blockIdx.x == 0) { fin_ride_block(lc.fr); return; }    // (see k_correct: the loop decision rides in this launch)
     const uint32_t *nlb = nullptr;
+    const DevScalars *const ds = lc.ds;
+    const TilePhase &tp = lc.tp; const DensFlow &df = lc.df; int *const wave_dirty = lc.wave_dirty; unsigned char *const changed8 = lc.changed8;
     const int tile = sweep_tile(tp, MODE == CORR_DENS && wave_dirty != nullptr);
-    const bool flow = MODE == CORR_DENS && wave_dirty != nullptr && df.nbr != nullptr;      // (DensFlow, see k_correct in sph_kernels.h)
+    const bool flow = MODE == CORR_DENS && wave_dirty != nullptr && df.nbr != nullptr;      // (DensFlow in sph_kernels.h)
     const int n2 = (flow && tp.sparse) ? tp.sparse[tp.ntiles + 1] : 0;
-    if (gate_closed(ds, gate)) return;
+    if (gate_closed(ds, lc.gate)) return;
     if (tile < 0) return;
-    StagePre pre = kNoPre;
-    bool direct = false;
-    if (flow) {
-        const FlowHead fh = flow_head(tp, df, tile, n2, stage_src, stage_cnt);
-        pre = fh.pre; direct = fh.direct;
-        if (!fh.need) {
-            const int i0 = tile * kBlock + (int)threadIdx.x;
-            if ((threadIdx.x & 63) == 0) wave_dirty[tile * (kBlock / 64) + (threadIdx.x >> 6)] = 0;
-            if (i0 < c.n) changed8[i0] = 0;
-            if (direct && threadIdx.x == 0) df.worked[tile] = 0;
-            return;
-        }
-    }
+    const TileHead hd = corr_head(c, tp, df, flow, tile, n2, st, wave_dirty, changed8);
+    if (hd.leave) return;
     const int my_nbr = (flow && threadIdx.x < 64) ? df.nbr[(size_t)tile * kNbrStride + threadIdx.x] : 0;
     SPH_SWEEP_PROLOGUE_G(false, tile, true)
     (void)nlbp;
     const bool track = MODE == CORR_DENS && wave_dirty != nullptr;  // change propagation in the density loop (sph_kernels.h: stage_sources_flagged)
+    const StagePlan plan{st.src, st.cnt, blk, hd.pre};
     bool staged;
-    if (track && !direct) {
+    if (track && !hd.direct) {
         // (a staged set of no particles: kStaged, the tile goes on -- see k_correct)
-        const int verdict = stage_operands<kCheckFirst, kStaged>(StagePS<>{s_operand, P, krho}, StagePlan{stage_src, stage_cnt, blk, pre});
-        if (verdict == kStagedIdle) {
-            const bool foreign = live && ghost && !c.ghost_walk;           // (see k_correct in sph_kernels.h)
-            const unsigned long long anyg = __ballot(foreign);
-            if ((threadIdx.x & 63) == 0) wave_dirty[blk * (kBlock / 64) + (threadIdx.x >> 6)] = anyg != 0ull ? 1 : 0;
-            if (live) changed8[i] = foreign ? 1 : 0;
-            return;
-        }
+        const int verdict = stage_operands<kCheckFirst, kStaged>(StagePS<>{s_operand, P, krho}, plan);
+        if (verdict == kStagedIdle) { corr_mark_idle(c, wave_dirty, changed8, blk, i, live, ghost); return; }
         staged = verdict == kStaged;
     } else {
-        staged = stage_operands(StagePS<>{s_operand, P, krho}, StagePlan{stage_src, stage_cnt, blk, pre}) != kNotStaged;
+        staged = stage_operands(StagePS<>{s_operand, P, krho}, plan) != kNotStaged;
     }
     const float dt = ds->dt;
     const float rho_i = rho[ii];
@@ -297,18 +243,11 @@ __global__ __launch_bounds__(kBlock) void k_correct_rx(Consts c, const float4 *_
     }
     if (track) {
         const bool changed = live && ((ghost && !c.ghost_walk) || ax != 0.f || ay != 0.f || az != 0.f || gx != 0.f || gy != 0.f || gz != 0.f);
-        const unsigned long long any = __ballot(changed);
-        if ((threadIdx.x & 63) == 0) wave_dirty[blk * (kBlock / 64) + (threadIdx.x >> 6)] = any != 0ull ? 1 : 0;
-        if (live) changed8[i] = changed ? 1 : 0;
-        if (flow) {
-            const int moved = __syncthreads_or(changed ? 1 : 0);
-            if (moved && threadIdx.x < 64) flow_push(df, my_nbr);
-            if (threadIdx.x == 0) df.worked[tile] = moved ? 1 : 0;
-        }
+        corr_mark_changed(df, flow, wave_dirty, changed8, blk, i, live, changed, my_nbr);
     }
     if (!live) return;
     float4 v = Vin[i];
-    if (MODE == CORR_DIV && sv.v) { sv.v[i] = v; sv.w[i] = warm[i]; }             // (see k_correct: the undo of a correction that ran ahead of the loop decision)
+    if (MODE == CORR_DIV && lc.sv.v) { lc.sv.v[i] = v; lc.sv.w[i] = warm[i]; }    // (see k_correct: the undo of a correction that ran ahead of the loop decision)
     v.x -= (ax + gx) * dt; v.y -= (ay + gy) * dt; v.z -= (az + gz) * dt;         // :324 / :312 / :189
     v.w = rho_i;
     Vout[i] = v;

@@ -22,10 +22,10 @@ from cfd_taichi_amd import build as hip_build  # noqa: E402
 K, R = "sph_kernels.h", "sph_relaxed_kernels.h"
 PATCHES = {
     # exact k_residual (sph_kernels.h): the fluid pair loop / the wall loop removed
-    "nofluid": [(K, "    else if (staged && (RIGID ? stage_lists16(stage_cnt, blk) : c.nl16 != 0)) for_staged16_nbrs_pv2(nlp, skip ? 0 : kf, s_operand, s_v2, pair_scaled);",
-                 "    else if (staged && (RIGID ? stage_lists16(stage_cnt, blk) : c.nl16 != 0)) for_staged16_nbrs_pv2(nlp, 0, s_operand, s_v2, pair_scaled);")],
+    "nofluid": [(K, "    else if (staged && (RIGID ? stage_lists16(st.cnt, blk) : c.nl16 != 0)) for_staged16_nbrs_pv2(nlp, skip ? 0 : kf, s_operand, s_v2, pair_scaled);",
+                 "    else if (staged && (RIGID ? stage_lists16(st.cnt, blk) : c.nl16 != 0)) for_staged16_nbrs_pv2(nlp, 0, s_operand, s_v2, pair_scaled);")],
     "nowall": [(K, "    else for_nbrs_p(nlbp, skip ? 0 : kb, WP, wall);\n    float val = 0.f, kr = 0.f;", "    else for_nbrs_p(nlbp, 0, WP, wall);\n    float val = 0.f, kr = 0.f;")],
-    "nowall_correct": [(K, "    else for_nbrs_p(nlbp, kb, WP, wall);\n    if (track) {       // did any lane", "    else for_nbrs_p(nlbp, 0, WP, wall);\n    if (track) {       // did any lane")],
+    "nowall_correct": [(K, "    else for_nbrs_p(nlbp, kb, WP, wall);\n    if (track) {\n        const bool changed", "    else for_nbrs_p(nlbp, 0, WP, wall);\n    if (track) {\n        const bool changed")],
     # CORRECT variants (speed only): the solver-loop sweeps take their tiles in chunks of C consecutive tiles dealt round-robin over the XCDs
     # instead of one contiguous eighth per XCD (1.5-2 % faster at 16-64, 19 % more HBM traffic: not in the product)
     "xcd_chunk16": [(K, "    return xcd_block(orig, nwg);\n}\n\n// Edge / interior split of a sweep",
@@ -37,12 +37,13 @@ PATCHES = {
     "xcd_chunk128": [(K, "    return xcd_block(orig, nwg);\n}\n\n// Edge / interior split of a sweep",
                     "    const int C = 128, xcd = orig & 7, s = orig >> 3, per = nwg / (8 * C);\n    if (per < 4) return xcd_block(orig, nwg);\n    if (s >= per * C) return orig;\n    return ((s / C) * 8 + xcd) * C + s % C;\n}\n\n// Edge / interior split of a sweep")],
     # exact k_residual: workgroups whose set did not fit the LDS capacity (1-2 % of them at 1 M) return at once: what do they cost the launch?
-    "nounstaged": [(K, "        staged = verdict != kNotStaged;\n        const int would = verdict != kStagedIdle;\n",
-                    "        staged = verdict != kNotStaged;\n        const int would = verdict != kStagedIdle;\n        if (STAGED && !staged) return;\n")],
+    # (only those that staged without the per-particle check first -- every workgroup of the divergence residual, the `direct` tiles of the density loop)
+    "nounstaged": [(K, "    const bool staged = verdict != kNotStaged;\n    const float4 vi = V[ii];\n    float fa[1] = {0.f};\n",
+                    "    const bool staged = verdict != kNotStaged;\n    if (STAGED && !staged && !(spread && !hd.direct)) return;\n    const float4 vi = V[ii];\n    float fa[1] = {0.f};\n")],
     # a CORRECT variant with a side effect: every workgroup of the exact divergence-residual sweep leaves (begin, end, XCC id) of its life in a
     # device array that sph_debug_timeline() copies out (tools/wg_timeline.py): how full is the chip over a launch, where is the tail?
-    "wg_timeline": [(K, "    else block_partial_mean(blk, (double)val, flag, psum, pcnt);\n    if (flow) {                                                      // does this tile hold",
-                     "    else block_partial_mean(blk, (double)val, flag, psum, pcnt);\n    if (!DENS && threadIdx.x == 0 && blockIdx.x < 16384) {\n        unsigned xcc; asm volatile(\"s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)\" : \"=s\"(xcc));\n        g_timeline[blockIdx.x * 4 + 0] = t_begin; g_timeline[blockIdx.x * 4 + 1] = wall_clock64(); g_timeline[blockIdx.x * 4 + 2] = (xcc & 15) | ((t_staged - t_begin) << 8) | ((t_pairs - t_begin) << 24) | ((t_walls - t_begin) << 40); g_timeline[blockIdx.x * 4 + 3] = (unsigned long long)blk;\n    }\n    if (flow) {                                                      // does this tile hold"),
+    "wg_timeline": [(K, "    else block_partial_mean(blk, (double)val, flag, lc.psum, lc.pcnt);\n    resid_tail(df, flow, blk,",
+                     "    else block_partial_mean(blk, (double)val, flag, lc.psum, lc.pcnt);\n    if (!DENS && threadIdx.x == 0 && blockIdx.x < 16384) {\n        unsigned xcc; asm volatile(\"s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)\" : \"=s\"(xcc));\n        g_timeline[blockIdx.x * 4 + 0] = t_begin; g_timeline[blockIdx.x * 4 + 1] = wall_clock64(); g_timeline[blockIdx.x * 4 + 2] = (xcc & 15) | ((t_staged - t_begin) << 8) | ((t_pairs - t_begin) << 24) | ((t_walls - t_begin) << 40); g_timeline[blockIdx.x * 4 + 3] = (unsigned long long)blk;\n    }\n    resid_tail(df, flow, blk,"),
                     (K, "    extern __shared__ float4 s_operand[];\n    // (see k_correct: round-robin tiles when most of them return at once; the body",
                      "    extern __shared__ float4 s_operand[];\n    const unsigned long long t_begin = wall_clock64();\n    // (see k_correct: round-robin tiles when most of them return at once; the body"),
                     (K, "// D3 / D6: divergence residual and predicted density.", "__device__ unsigned long long g_timeline[16384 * 4];\n// D3 / D6: divergence residual and predicted density."),
@@ -72,12 +73,12 @@ PATCHES = {
                        (K, "// D3 / D6: divergence residual and predicted density.", "__device__ unsigned long long g_timeline[16384 * 4];\n// D3 / D6: divergence residual and predicted density."),
                        ("sph_mi355x.hip", "int sph_tune_time(SphHandle *h, int which, unsigned lds_bytes, int reps, double *avg_us)\n{",
                         "int sph_debug_timeline(unsigned long long *out, int n)\n{\n    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(sph::g_timeline), sizeof(unsigned long long) * 4 * (size_t)n);\n}\nint sph_tune_time(SphHandle *h, int which, unsigned lds_bytes, int reps, double *avg_us)\n{"),
-                       (R, "    extern __shared__ float4 s_operand[];\n    const bool spread = DENS && wave_dirty && !force_all;           // (round-robin",
-                        "    extern __shared__ float4 s_operand[];\n    const unsigned long long t_begin = wall_clock64();\n    const bool spread = DENS && wave_dirty && !force_all;           // (round-robin"),
+                       (R, "    extern __shared__ float4 s_operand[];\n    const TilePhase &tp = lc.tp; const DensFlow &df = lc.df;\n    const bool spread = DENS &&",
+                        "    extern __shared__ float4 s_operand[];\n    const unsigned long long t_begin = wall_clock64();\n    const TilePhase &tp = lc.tp; const DensFlow &df = lc.df;\n    const bool spread = DENS &&"),
                        (R, "    const float4 vi = V[ii];\n    float acc = 0.f;\n    const bool skip = !DENS && kf < 20;", "    const unsigned long long t_staged = wall_clock64();\n    const float4 vi = V[ii];\n    float acc = 0.f;\n    const bool skip = !DENS && kf < 20;"),
                        (R, "    float val = 0.f, kr = 0.f;\n    int flag = 0;\n    if (live) {\n        float sum = acc;", "    __builtin_amdgcn_s_barrier();\n    const unsigned long long t_pairs = wall_clock64();\n    const unsigned long long t_walls = t_pairs;\n    float val = 0.f, kr = 0.f;\n    int flag = 0;\n    if (live) {\n        float sum = acc;"),
-                       (R, "    block_partial_mean(blk, (double)val, flag, psum, pcnt);\n    if (flow) {\n        const int nzf",
-                        "    block_partial_mean(blk, (double)val, flag, psum, pcnt);\n    if (!DENS && threadIdx.x == 0 && blockIdx.x < 16384) {\n        unsigned xcc; asm volatile(\"s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)\" : \"=s\"(xcc));\n        g_timeline[blockIdx.x * 4 + 0] = t_begin; g_timeline[blockIdx.x * 4 + 1] = wall_clock64(); g_timeline[blockIdx.x * 4 + 2] = (xcc & 15) | ((t_staged - t_begin) << 8) | ((t_pairs - t_begin) << 24) | ((t_walls - t_begin) << 40); g_timeline[blockIdx.x * 4 + 3] = (unsigned long long)blk;\n    }\n    if (flow) {\n        const int nzf")],
+                       (R, "    block_partial_mean(blk, (double)val, flag, lc.psum, lc.pcnt);\n    resid_tail(df, flow, blk,",
+                        "    block_partial_mean(blk, (double)val, flag, lc.psum, lc.pcnt);\n    if (!DENS && threadIdx.x == 0 && blockIdx.x < 16384) {\n        unsigned xcc; asm volatile(\"s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)\" : \"=s\"(xcc));\n        g_timeline[blockIdx.x * 4 + 0] = t_begin; g_timeline[blockIdx.x * 4 + 1] = wall_clock64(); g_timeline[blockIdx.x * 4 + 2] = (xcc & 15) | ((t_staged - t_begin) << 8) | ((t_pairs - t_begin) << 24) | ((t_walls - t_begin) << 40); g_timeline[blockIdx.x * 4 + 3] = (unsigned long long)blk;\n    }\n    resid_tail(df, flow, blk,")],
     # a CORRECT variant with a side effect (round 6): every workgroup of ONE density-loop launch pair -- the residual sweep D6 and the correction sweep D7 whose
     # DensFlow stamps the host names (sph_debug_dens_capture) -- leaves (begin, end, outcome | XCC id, tile): outcome 0 = left after the need word, 1 = left
     # after the per-particle check, 2 = worked (tools/dens_timeline.py: where does a sparse launch's time go?)
@@ -87,22 +88,22 @@ PATCHES = {
                        "    if (df.nbr == nullptr || df.stamp_out != want || threadIdx.x != 0 || blockIdx.x >= 16384) return;\n"
                        "    unsigned xcc; asm volatile(\"s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)\" : \"=s\"(xcc));\n"
                        "    buf[blockIdx.x * 4 + 0] = t_begin; buf[blockIdx.x * 4 + 1] = wall_clock64(); buf[blockIdx.x * 4 + 2] = (unsigned long long)outcome | ((unsigned long long)(xcc & 15) << 8) | ((unsigned long long)(unsigned)extra << 32); buf[blockIdx.x * 4 + 3] = (unsigned long long)tile | (ph << 16);\n}\n"),
-                      (K, "    if (fr.mode >= 0 && blockIdx.x == 0) { fin_ride_block(fr); return; }          // the loop decision of the residual sweep before (whatever the gate says)\n",
-                       "    const unsigned long long t_begin = wall_clock64();\n    if (fr.mode >= 0 && blockIdx.x == 0) { fin_ride_block(fr); return; }\n"),
-                      (K, "            if (direct && threadIdx.x == 0) df.worked[tile] = 0;\n            return;\n        }\n    }\n    const int my_nbr = (flow && threadIdx.x < 64) ? df.nbr[(size_t)tile * kNbrStride + threadIdx.x] : 0;       // requested now, used by the push at the end",
-                       "            if (direct && threadIdx.x == 0) df.worked[tile] = 0;\n            tl_note(g_tl7, g_tl_capture[1], df, t_begin, 0, tile);\n            return;\n        }\n    }\n    const int my_nbr = (flow && threadIdx.x < 64) ? df.nbr[(size_t)tile * kNbrStride + threadIdx.x] : 0;"),
-                      (K, "            if (live) changed8[i] = foreign ? 1 : 0;\n            return;\n        }\n        staged = verdict == kStaged;",
-                       "            if (live) changed8[i] = foreign ? 1 : 0;\n            if (MODE == CORR_DENS) tl_note(g_tl7, g_tl_capture[1], df, t_begin, 1, tile);\n            return;\n        }\n        staged = verdict == kStaged;"),
-                      (K, "            if (threadIdx.x == 0) df.worked[tile] = moved ? 1 : 0;\n        }\n    }\n    if (!owner) return;",
-                       "            if (threadIdx.x == 0) df.worked[tile] = moved ? 1 : 0;\n        }\n    }\n    if (MODE == CORR_DENS) { __builtin_amdgcn_s_barrier(); const unsigned long long t_w = wall_clock64(); tl_note(g_tl7, g_tl_capture[1], df, t_begin, 2, tile, STAGED ? stage_cnt[tile] : 0, ((t_st - t_begin) & 0xffff) | (((t_pr - t_begin) & 0xffff) << 16) | (((t_w - t_begin) & 0xffff) << 32)); }\n    if (!owner) return;"),
+                      (K, "    if (lc.fr.mode >= 0 && blockIdx.x == 0) { fin_ride_block(lc.fr); return; }    // the loop decision of the residual sweep before (whatever the gate says)\n",
+                       "    const unsigned long long t_begin = wall_clock64();\n    if (lc.fr.mode >= 0 && blockIdx.x == 0) { fin_ride_block(lc.fr); return; }\n"),
+                      (K, "    if (hd.leave) return;                                    // (DensFlow: nothing this tile stages holds a k / rho != 0)\n",
+                       "    if (hd.leave) { tl_note(g_tl7, g_tl_capture[1], df, t_begin, 0, tile); return; }\n"),
+                      (K, "        if (verdict == kStagedIdle) { corr_mark_idle(c, wave_dirty, changed8, blk, i, live, ghost); return; }\n",
+                       "        if (verdict == kStagedIdle) { corr_mark_idle(c, wave_dirty, changed8, blk, i, live, ghost); if (MODE == CORR_DENS) tl_note(g_tl7, g_tl_capture[1], df, t_begin, 1, tile); return; }\n"),
+                      (K, "        corr_mark_changed(df, flow, wave_dirty, changed8, blk, i, live, changed, my_nbr);\n    }\n    if (!owner) return;",
+                       "        corr_mark_changed(df, flow, wave_dirty, changed8, blk, i, live, changed, my_nbr);\n    }\n    if (MODE == CORR_DENS) { __builtin_amdgcn_s_barrier(); const unsigned long long t_w = wall_clock64(); tl_note(g_tl7, g_tl_capture[1], df, t_begin, 2, tile, STAGED ? st.cnt[tile] : 0, ((t_st - t_begin) & 0xffff) | (((t_pr - t_begin) & 0xffff) << 16) | (((t_w - t_begin) & 0xffff) << 32)); }\n    if (!owner) return;"),
                       (K, "    extern __shared__ float4 s_operand[];\n    // (see k_correct: round-robin tiles when most of them return at once; the body",
                        "    extern __shared__ float4 s_operand[];\n    const unsigned long long t_begin = wall_clock64();\n    // (see k_correct: round-robin tiles when most of them return at once; the body"),
-                      (K, "        if (idle) return;                                            // rho*, k / rho and the block partial of the last iteration stand",
-                       "        if (idle) { tl_note(g_tl6, g_tl_capture[0], df, t_begin, 0, tile); return; }"),
-                      (K, "            if (tp.hot && threadIdx.x == 0) tp.hot[blk] = 1;\n            return;\n        }\n        staged = verdict == kStaged;",
-                       "            if (tp.hot && threadIdx.x == 0) tp.hot[blk] = 1;\n            tl_note(g_tl6, g_tl_capture[0], df, t_begin, 1, tile);\n            return;\n        }\n        staged = verdict == kStaged;"),
-                      (K, "    if (flow) {                                                      // does this tile hold a k / rho != 0?  (a NaN counts)",
-                       "    if (DENS) tl_note(g_tl6, g_tl_capture[0], df, t_begin, 2, tile, STAGED ? stage_cnt[tile] : 0, ((t_st - t_begin) & 0xffff) | (((t_pr - t_begin) & 0xffff) << 16) | (((t_w - t_begin) & 0xffff) << 32));\n    if (flow) {                                                      // does this tile hold a k / rho != 0?  (a NaN counts)"),
+                      (K, "    if (hd.leave) return;                                            // rho*, k / rho and the block partial of the last iteration stand",
+                       "    if (hd.leave) { tl_note(g_tl6, g_tl_capture[0], df, t_begin, 0, tile); return; }"),
+                      (K, "    if (resid_note_work(tp, df, spread, flow, hd.direct, blk, verdict, my_nbr)) return;\n",
+                       "    if (resid_note_work(tp, df, spread, flow, hd.direct, blk, verdict, my_nbr)) { tl_note(g_tl6, g_tl_capture[0], df, t_begin, 1, tile); return; }\n"),
+                      (K, "    resid_tail(df, flow, blk, live && !ghost && kr != 0.f, my_nbr);\n}",
+                       "    if (DENS) tl_note(g_tl6, g_tl_capture[0], df, t_begin, 2, tile, STAGED ? st.cnt[tile] : 0, ((t_st - t_begin) & 0xffff) | (((t_pr - t_begin) & 0xffff) << 16) | (((t_w - t_begin) & 0xffff) << 32));\n    resid_tail(df, flow, blk, live && !ghost && kr != 0.f, my_nbr);\n}"),
                       (K, "    const float dt = ds->dt;\n    const float rho_i = rho[ii];\n    float k_i;\n    if (MODE == CORR_WARM) k_i = warm[ii] / dt;                                   // :333",
                        "    __builtin_amdgcn_s_barrier();\n    const unsigned long long t_st = wall_clock64();\n    const float dt = ds->dt;\n    const float rho_i = rho[ii];\n    float k_i;\n    if (MODE == CORR_WARM) k_i = warm[ii] / dt;                                   // :333"),
                       (K, "    float wa[3] = {0.f, 0.f, 0.f};\n    float &bx = wa[0], &by = wa[1], &bz = wa[2];\n    auto wall = [&](const float4 pj) {\n        float dx = pi.x - pj.x, dy = pi.y - pj.y, dz = pi.z - pj.z;\n        float r = K::norm3(dx, dy, dz);\n        F3 g = K::grad_in(c, dx, dy, dz, r);\n        float s = pj.w * k_i / rho_i;                                             // :354 / :390 / :219",
@@ -150,8 +151,8 @@ PATCHES = {
     # LDS gathers, same arithmetic, half the list bytes from HBM): what a 2x more compact list encoding could buy at most
     "rx_halflist": [(R, "        if (kk + 8 < cnt) jn = nl_load(base + (size_t)((kk >> 3) + 1) * 256);\n        pair8(g);",
                      "        if (kk + 8 < cnt && ((kk >> 3) & 1)) jn = nl_load(base + (size_t)((kk >> 3) + 1) * 256);\n        pair8(g);")],
-    "rx_nostage": [(R, "        const int verdict = stage_operands<kCheckWith, kStaged>(StagePV<>{s_operand, s_v2, P, V, (spread && direct) ? changed8 : nullptr}, plan);\n        staged = verdict != kNotStaged;\n        const int would = verdict != kStagedIdle;\n",
-                    "        staged = true;\n        const int would = 1;\n"),
+    "rx_nostage": [(R, "    else verdict = stage_operands<kCheckWith, kStaged>(StagePV<>{s_operand, s_v2, P, V, (spread && hd.direct) ? lc.changed8 : nullptr}, plan);\n",
+                    "    else verdict = kStaged;\n"),
                    (R, "        rx_walk8(nlp, kfx, [&](const Nl16Group &g) {\n            float4 a[8]; float2 b[8];",
                     "        rx_walk8(nlp, 0, [&](const Nl16Group &g) {\n            float4 a[8]; float2 b[8];")],
 }
