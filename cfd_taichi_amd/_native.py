@@ -40,7 +40,7 @@ EXPORTS = [
     "sph_abi_version", "sph_set_comm_sized", "sph_create", "sph_destroy", "sph_get_sizes", "sph_last_error", "sph_upload", "sph_download",
     "sph_step_wcsph", "sph_step_dfsph", "sph_step_pcisph", "sph_step_iisph", "sph_step_pbf", "sph_build_neighbors", "sph_compute_density", "sph_compute_alpha",
     "sph_get_scalar", "sph_set_scalar", "sph_synchronize", "sph_overrides", "sph_profile_enable", "sph_profile_reset", "sph_profile_kernel_count",
-    "sph_profile_kernel_name", "sph_profile_get", "sph_selftest_math", "sph_selftest_wave", "sph_selftest_stage", "sph_tune_time",
+    "sph_profile_kernel_name", "sph_profile_get", "sph_selftest_math", "sph_selftest_wave", "sph_selftest_stage", "sph_selftest_walk", "sph_tune_time",
     "sph_set_comm", "sph_rccl_unique_id", "sph_rccl_attach", "sph_rccl_selftest", "sph_get_stream", "sph_plan_slabs", "sph_replan_slabs", "sph_slab_set_overlap", "sph_slab_info", "sph_comm_stats", "sph_download_local", "sph_download_ids",
     "sph_create_rigid", "sph_rigid_step", "sph_rigid_set_active", "sph_rigid_init_data", "sph_slab_set_state",
 ]
@@ -172,7 +172,7 @@ CORE_EXPORTS = [
 ]
 # entry points added without a change of SPH_ABI_VERSION (no struct grew, no signature changed): bound where the library has them, and a call on a
 # library without them raises SphError(SPH_E_STATE)
-OPTIONAL_EXPORTS = ["sph_rigid_set_active", "sph_rigid_init_data", "sph_selftest_stage", "sph_slab_set_state"]
+OPTIONAL_EXPORTS = ["sph_rigid_set_active", "sph_rigid_init_data", "sph_selftest_stage", "sph_selftest_walk", "sph_slab_set_state"]
 
 
 def _bind_core(lib):
@@ -251,6 +251,8 @@ def load(build_if_missing=True):
     lib.sph_profile_get.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]
     lib.sph_selftest_math.argtypes = [ci, ci, vp, vp, vp, ctypes.c_size_t]
     lib.sph_selftest_wave.argtypes = [ci, ci, vp, vp, ctypes.c_size_t]
+    if hasattr(lib, "sph_selftest_walk"):
+        lib.sph_selftest_walk.argtypes = [vp, ci, ci, ci, vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp]
     if hasattr(lib, "sph_selftest_stage"):
         lib.sph_selftest_stage.argtypes = [vp, ci, ci, ci, ci, ci, vp, ci, vp, vp, vp, vp, ctypes.c_size_t, vp, ctypes.POINTER(ci)]
     lib.sph_tune_time.argtypes = [vp, ci, ctypes.c_uint, ci, ctypes.POINTER(ctypes.c_double)]
@@ -656,3 +658,29 @@ def selftest_stage(layout, check, runs, A, B, S, changed, use_pre=False, not_sta
     if rc != SPH_OK:
         raise SphError(rc, (lib.sph_last_error(handle) or b"").decode())
     return out, verdict.value
+
+
+WALKS = {"list": 0, "quad": 1, "staged": 2, "list16": 3}
+WALK_SOURCES_MEM = {"p": 0, "a": 1, "ab": 2, "as": 3, "abc": 4}
+WALK_SOURCES_LDS = {"f4": 0, "f4_scaled": 1, "ps": 2, "ps_scaled": 3, "pv": 4, "pv_scaled": 5, "f4s": 6, "f4src_b": 7, "update_p": 8}
+WALK_ROWS, WALK_PITCH, WALK_PARTICLES = 24, 28, 256
+
+
+def selftest_walk(walk, src, rigid, lists, counts, run, A, B, C, S, RP, handle=None):
+    """What the pair bodies of one list walk saw (see sph_selftest_walk): a (threads, 4) uint32 array of body calls, hash and, for the quad walk, the
+    bits of the two sums; threads = 256, or 1024 for the quad walk (four per particle)."""
+    lib = load()
+    if not hasattr(lib, "sph_selftest_walk"):
+        raise SphError(SPH_E_STATE, "this library has no sph_selftest_walk")
+    lists = np.ascontiguousarray(lists, dtype=np.uint32).reshape(WALK_PARTICLES, WALK_PITCH)
+    counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(WALK_PARTICLES)
+    A, B, C, RP = (np.ascontiguousarray(x, dtype=np.float32).reshape(-1, 4) for x in (A, B, C, RP))
+    S = np.ascontiguousarray(S, dtype=np.float32)
+    assert len(A) == len(B) == len(C) == len(S)
+    out = np.zeros((WALK_PARTICLES * (4 if walk == "quad" else 1), 4), dtype=np.uint32)
+    table = WALK_SOURCES_LDS if WALKS[walk] >= 2 else WALK_SOURCES_MEM
+    rc = lib.sph_selftest_walk(handle, WALKS[walk], table[src], int(rigid), lists.ctypes.data, counts.ctypes.data, int(run[0]), int(run[1]),
+                               A.ctypes.data, B.ctypes.data, C.ctypes.data, S.ctypes.data, len(A), RP.ctypes.data, len(RP), out.ctypes.data)
+    if rc != SPH_OK:
+        raise SphError(rc, (lib.sph_last_error(handle) or b"").decode())
+    return out

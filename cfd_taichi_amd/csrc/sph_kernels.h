@@ -252,7 +252,7 @@ __device__ __forceinline__ int sweep_tile(const TilePhase &tp, bool spread)
 //   entry (i, k) lives at ((i/64)*kmax + (k & ~3))*64 + (i%64)*4 + (k & 3)
 // so a lane fetches neighbours k..k+3 with ONE 16-byte load, a wave's load is 1 KiB contiguous, and
 // the whole tile (kmax * 256 B) is one contiguous chunk that the wave streams front to back.
-__device__ __forceinline__ size_t nl_index(int i, int k, int kmax)
+__host__ __device__ __forceinline__ size_t nl_index(int i, int k, int kmax)      // (__host__: sph_selftest_walk packs its lists with it)
 {
     return ((size_t)(i >> 6) * kmax + (k & ~3)) * 64 + (size_t)(i & 63) * 4 + (k & 3);
 }
@@ -540,13 +540,19 @@ struct NlAhead {
     }
 };
 
-// fluid-list walkers that understand tagged rigid entries; body(pj, vj, j): j & kRigidTag marks a rigid neighbour,
-// then pj = (x, y, z, V_r) and vj is undefined
-// The walk of a list, software-pipelined: the operands of group g+1 are requested before the bodies of group g run, the index
-// row of group g+2 before that.  Small scenes are bound by the latency of one wave's dependent gathers (one wave per SIMD or
-// less): +12 % on DFSPH at 30 k particles; large scenes are unaffected.  `fetch(j, slot)` loads one neighbour's operands,
-// `use(slot, j)` is the pair body; bodies run in list order.  The speculative fetch past the last group reads stale but valid
-// indices (see for_nbrs_p).
+// ---- the walks of a neighbour list -------------------------------------------------------------------------------------------------
+// Four walks, each written once: walk_list (32-bit entries, operands from memory), walk_list_quad (four lanes per particle), walk_staged
+// (32-bit entries, operands from LDS) and walk_list16 over nl16_stream (16-bit entries, operands from LDS).  What one list entry brings to
+// the pair body is said by an OPERAND SOURCE (below), so an operand layout is described once and not once per walk.  Every walk runs its
+// bodies in list order, exactly `cnt` of them: every accumulator sees its terms in the canonical order.
+//
+// walk_list, software-pipelined: the operands of group g+1 are requested before the bodies of group g run, the index row of group g+2
+// before that (one 16-byte index load per group of four, four independent gathers in flight).  Small scenes are bound by the latency of
+// one wave's dependent gathers (one wave per SIMD or less): +12 % on DFSPH at 30 k particles; large scenes are unaffected.
+// `fetch(j, slot)` loads one neighbour's operands, `use(slot, j)` is the pair body.
+// The 32-bit walks (this one, walk_list_quad, walk_staged) read one group past a list's end.  Rows past a particle's count hold stale but
+// valid indices -- the buffer is zero-initialised, only ever holds indices < n, and one spare tile pads the end -- so the speculative
+// loads are always in bounds.  NlWriter::flush (zero_next) keeps that true on nl16 handles, where a stale group could hold packed 16-bit pairs.
 template <class T, class Fetch, class Use>
 __device__ __forceinline__ void walk_list(const uint32_t *__restrict__ base, int cnt, Fetch fetch, Use use)
 {
@@ -568,27 +574,6 @@ __device__ __forceinline__ void walk_list(const uint32_t *__restrict__ base, int
         for (int u = 0; u < 4; ++u) cur[u] = nxt[u];
         jj = jn;
     }
-}
-struct Operand1 { float4 a; };
-struct Operand2 { float4 a, b; };
-
-template <bool RIGID, bool WITHV, class Body>
-__device__ __forceinline__ void for_fluid_nbrs(const uint32_t *__restrict__ base, int cnt, const float4 *__restrict__ A,
-                                               const float4 *__restrict__ B, const RigidView &rv, Body body)
-{
-    if (WITHV)
-        walk_list<Operand2>(base, cnt, [&](uint32_t j, Operand2 &o) {
-            const bool rg = RIGID && (j & kRigidTag);
-            const uint32_t idx = RIGID ? (j & ~kRigidTag) : j;
-            o.a = rg ? rv.RP[idx] : A[idx];
-            o.b = B[rg ? 0u : idx];
-        }, [&](const Operand2 &o, uint32_t j) { body(o.a, o.b, j); });
-    else
-        walk_list<Operand1>(base, cnt, [&](uint32_t j, Operand1 &o) {
-            const bool rg = RIGID && (j & kRigidTag);
-            const uint32_t idx = RIGID ? (j & ~kRigidTag) : j;
-            o.a = rg ? rv.RP[idx] : A[idx];
-        }, [&](const Operand1 &o, uint32_t j) { body(o.a, make_float4(0.f, 0.f, 0.f, 0.f), j); });
 }
 
 // ---- four lanes per particle (small scenes) ---------------------------------------------------------------------------------
@@ -630,23 +615,167 @@ __device__ __forceinline__ void walk_list_quad(const uint32_t *__restrict__ base
         cur = nxt; jq = jn;
     }
 }
-template <bool RIGID, bool WITHV, int N, class Body>
-__device__ __forceinline__ void for_fluid_nbrs_quad(const uint32_t *__restrict__ base, int cnt, int q, float (&acc)[N], const float4 *__restrict__ A,
-                                                    const float4 *__restrict__ B, const RigidView &rv, Body body)
+
+// ---- operand sources ------------------------------------------------------------------------------------------------------------
+// A source says what one list entry brings to the pair body: an operand set Op (`a` is always the position operand), pos(idx) and
+// rest(idx, o) that load it for a fluid entry, and kScaled: its positions carry 2^32.  One source serves every walk it is valid for.
+// The sources over arrays in memory are here; an LDS source is the reader of the type that wrote the LDS (the stage layouts below).
+//   SrcP    (A)        lists that never hold a tagged entry -- wall lists, PBF: body(pj)
+//   SrcA    (A)        body(pj, 0, j)
+//   SrcAB   (A, B)     body(pj, vj, j)
+//   SrcAS   (A, S)     body(pj, s, j)
+//   SrcABC  (A, B, C)  body(pj, bj, cj, j)
+// j is the raw entry: j & kRigidTag marks a rigid neighbour (the 16-bit walk, which has none, passes 0).
+struct OpP { float4 a; };
+struct OpA { float4 a; };
+struct OpAB { float4 a, b; };
+struct OpAS { float4 a; float s; };
+struct OpABC { float4 a, b, c; };
+template <class Body> __device__ __forceinline__ void nl_call(Body &body, const OpP &o, uint32_t) { body(o.a); }
+template <class Body> __device__ __forceinline__ void nl_call(Body &body, const OpA &o, uint32_t j) { body(o.a, make_float4(0.f, 0.f, 0.f, 0.f), j); }
+template <class Body> __device__ __forceinline__ void nl_call(Body &body, const OpAB &o, uint32_t j) { body(o.a, o.b, j); }
+template <class Body> __device__ __forceinline__ void nl_call(Body &body, const OpAS &o, uint32_t j) { body(o.a, o.s, j); }
+template <class Body> __device__ __forceinline__ void nl_call(Body &body, const OpABC &o, uint32_t j) { body(o.a, o.b, o.c, j); }
+struct SrcP {
+    const float4 *A;
+    using Op = OpP; static constexpr bool kScaled = false;
+    __device__ __forceinline__ float4 pos(uint32_t i) const { return A[i]; }
+    __device__ __forceinline__ void rest(uint32_t, Op &) const {}
+};
+struct SrcA {
+    const float4 *A;
+    using Op = OpA; static constexpr bool kScaled = false;
+    __device__ __forceinline__ float4 pos(uint32_t i) const { return A[i]; }
+    __device__ __forceinline__ void rest(uint32_t, Op &) const {}
+};
+struct SrcAB {
+    const float4 *A, *B;
+    using Op = OpAB; static constexpr bool kScaled = false;
+    __device__ __forceinline__ float4 pos(uint32_t i) const { return A[i]; }
+    __device__ __forceinline__ void rest(uint32_t i, Op &o) const { o.b = B[i]; }
+};
+struct SrcAS {
+    const float4 *A; const float *S;
+    using Op = OpAS; static constexpr bool kScaled = false;
+    __device__ __forceinline__ float4 pos(uint32_t i) const { return A[i]; }
+    __device__ __forceinline__ void rest(uint32_t i, Op &o) const { o.s = S[i]; }
+};
+struct SrcABC {
+    const float4 *A, *B, *C;
+    using Op = OpABC; static constexpr bool kScaled = false;
+    __device__ __forceinline__ float4 pos(uint32_t i) const { return A[i]; }
+    __device__ __forceinline__ void rest(uint32_t i, Op &o) const { o.b = B[i]; o.c = C[i]; }
+};
+template <bool SCALED>
+__device__ __forceinline__ float4 stage_pos(const float4 a, float w)
 {
-    if (WITHV)
-        walk_list_quad<N, Operand2>(base, cnt, q, acc, [&](uint32_t j, Operand2 &o) {
-            const bool rg = RIGID && (j & kRigidTag);
-            const uint32_t idx = RIGID ? (j & ~kRigidTag) : j;
-            o.a = rg ? rv.RP[idx] : A[idx];
-            o.b = B[rg ? 0u : idx];
-        }, [&](const Operand2 &o, uint32_t j) { body(o.a, o.b, j); });
-    else
-        walk_list_quad<N, Operand1>(base, cnt, q, acc, [&](uint32_t j, Operand1 &o) {
-            const bool rg = RIGID && (j & kRigidTag);
-            const uint32_t idx = RIGID ? (j & ~kRigidTag) : j;
-            o.a = rg ? rv.RP[idx] : A[idx];
-        }, [&](const Operand1 &o, uint32_t j) { body(o.a, make_float4(0.f, 0.f, 0.f, 0.f), j); });
+    return SCALED ? make_float4(a.x * 0x1p32f, a.y * 0x1p32f, a.z * 0x1p32f, w) : make_float4(a.x, a.y, a.z, w);
+}
+// rv.RP[idx] for the staged walk, loaded through a pointer that SAYS global memory: next to the LDS read of a staged source the compiler otherwise merges the two
+// loads of .w into one load through a selected pointer -- a flat load in the rigid path of the staged walk (k_correct<DENS, RIGID, staged> on the
+// coupled 2 M scene: 32.1 -> 35.1 us per launch, profiles/r08/ab_steps_walks.txt)
+__device__ __forceinline__ float4 rigid_sample(const RigidView &rv, uint32_t idx)
+{
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    const f32x4 q = *(const __attribute__((address_space(1))) f32x4 *)(rv.RP + idx);
+    return make_float4(q.x, q.y, q.z, q.w);
+}
+// One entry's operands, THE decode of a tagged rigid entry: the index without the tag, the position (x, y, z, V_r) from rv.RP -- times
+// 2^32 exactly where the source is a scaled one.  Every other operand of a tagged entry is unspecified; no pair body reads it.  (Here it
+// is the source's element 0 -- B[s_src[0]] for a gathered operand -- which exists: a particle that has a list is staged itself, so the
+// set of a workgroup that meets a tagged entry is not empty.)  In a list of a staged workgroup a fluid entry is a LOCAL index into the
+// staged set, a tagged one stays global.  RIGID == false: no tag test.
+template <bool RIGID, bool STAGED = false, class Src>
+__device__ __forceinline__ typename Src::Op nl_operand(const Src &s, uint32_t j, const RigidView &rv)
+{
+    const bool rg = RIGID && (j & kRigidTag);
+    const uint32_t idx = RIGID ? (j & ~kRigidTag) : j;
+    typename Src::Op o;
+    if (rg) { const float4 q = STAGED ? rigid_sample(rv, idx) : rv.RP[idx]; o.a = stage_pos<Src::kScaled>(q, q.w); }
+    else o.a = s.pos(idx);
+    s.rest(rg ? 0u : idx, o);
+    return o;
+}
+template <class Src> __device__ __forceinline__ typename Src::Op nl_fluid(const Src &s, uint32_t idx) { return nl_operand<false>(s, idx, RigidView()); }
+
+// the two walks over memory, through a source
+template <bool RIGID, class Src, class Body>
+__device__ __forceinline__ void sweep_list(const Src &s, const uint32_t *__restrict__ base, int cnt, Body body, const RigidView &rv = RigidView())
+{
+    using Op = typename Src::Op;
+    walk_list<Op>(base, cnt, [&](uint32_t j, Op &o) { o = nl_operand<RIGID>(s, j, rv); }, [&](const Op &o, uint32_t j) { nl_call(body, o, j); });
+}
+template <bool RIGID, int N, class Src, class Body>
+__device__ __forceinline__ void sweep_quad(const Src &s, const uint32_t *__restrict__ base, int cnt, int q, float (&acc)[N], Body body,
+                                           const RigidView &rv = RigidView())
+{
+    using Op = typename Src::Op;
+    walk_list_quad<N, Op>(base, cnt, q, acc, [&](uint32_t j, Op &o) { o = nl_operand<RIGID>(s, j, rv); },
+                          [&](const Op &o, uint32_t j) { nl_call(body, o, j); });
+}
+
+// ---- the staged walk of a 32-bit list: the operands of a group come from LDS with no latency to hide, so only the index stream runs
+// ahead (NlAhead: SPH_NL_AHEAD is the one depth knob) -- four LDS reads, four masked bodies.
+// A group without a rigid entry anywhere in the wave (nearly all of them: the body touches a thin layer of the fluid) takes the plain
+// path; the branch is wave-uniform.
+template <bool RIGID, class Src, class Body>
+__device__ __forceinline__ void walk_staged(const Src &s, const uint32_t *__restrict__ base, int cnt, Body body, const RigidView &rv = RigidView())
+{
+    NlAhead ahead(base);
+    for (int kk = 0; kk < cnt; kk += 4) {
+        const uint4 jj = ahead.front();
+        const uint32_t j[4] = {jj.x, jj.y, jj.z, jj.w};
+        typename Src::Op o[4];
+        if (RIGID && __any(((j[0] | j[1] | j[2] | j[3]) & kRigidTag) != 0)) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) o[u] = nl_operand<true, true>(s, j[u], rv);
+        } else {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) o[u] = nl_fluid(s, j[u]);
+        }
+        ahead.advance(kk);
+        nl_call(body, o[0], j[0]);
+        if (kk + 1 < cnt) nl_call(body, o[1], j[1]);
+        if (kk + 2 < cnt) nl_call(body, o[2], j[2]);
+        if (kk + 3 < cnt) nl_call(body, o[3], j[3]);
+    }
+}
+
+// ---- 16-bit lists (staged workgroup of an nl16 handle; no rigid entries): one 16-byte load = eight neighbours.  nl16_stream hands out
+// the groups of a list, group(g, kk) with kk = the list position of the group's first entry.  The next group is requested before the
+// bodies run, and only by lanes whose list goes on: the 16-bit stream never reads past the list (the 32-bit walks read one stale group
+// past the end: 16 B per particle and sweep).
+struct Nl16Group {
+    uint32_t w[4];
+    __device__ __forceinline__ uint32_t lo(int q) const { return w[q] & 0xffffu; }
+    __device__ __forceinline__ uint32_t hi(int q) const { return w[q] >> 16; }
+};
+template <class Group>
+__device__ __forceinline__ void nl16_stream(const uint32_t *__restrict__ base, int cnt, Group group)
+{
+    if (cnt <= 0) return;
+    uint4 jn = nl_load(base);
+    for (int kk = 0; kk < cnt; kk += 8) {
+        const Nl16Group g = {{jn.x, jn.y, jn.z, jn.w}};
+        if (kk + 8 < cnt) jn = nl_load(base + (size_t)((kk >> 3) + 1) * 256);
+        group(g, kk);
+    }
+}
+// the exact sweeps take a group four entries at a time, tails masked, so that the registers in flight stay those of the 32-bit walk
+template <class Src, class Body>
+__device__ __forceinline__ void walk_list16(const Src &s, const uint32_t *__restrict__ base, int cnt, Body body)
+{
+    auto four = [&](uint32_t j0, uint32_t j1, uint32_t j2, uint32_t j3, int k0) {
+        const typename Src::Op o[4] = {nl_fluid(s, j0), nl_fluid(s, j1), nl_fluid(s, j2), nl_fluid(s, j3)};
+        nl_call(body, o[0], 0u);
+        if (k0 + 1 < cnt) nl_call(body, o[1], 0u);
+        if (k0 + 2 < cnt) nl_call(body, o[2], 0u);
+        if (k0 + 3 < cnt) nl_call(body, o[3], 0u);
+    };
+    nl16_stream(base, cnt, [&](const Nl16Group &g, int kk) {
+        four(g.lo(0), g.hi(0), g.lo(1), g.hi(1), kk);
+        if (kk + 4 < cnt) four(g.lo(2), g.hi(2), g.lo(3), g.hi(3), kk + 4);
+    });
 }
 
 // ======================================================================================
@@ -1337,22 +1466,6 @@ __global__ __launch_bounds__(kBlock) void k_tile_flags_exact(const int *__restri
     const uint32_t *nlp = nl + nl_index(ii, 0, c.kpitch);     \
     const uint32_t *nlbp = nlb ? nlb + nl_index(ii, 0, c.kbpitch) : nullptr;
 
-// Walk of a neighbour list in groups of four: one 16-byte index load, four independent float4
-// gathers in flight, the next group's indices requested before the four bodies run.  Bodies run in
-// list order, so every accumulator sees its terms in the canonical order.  Rows past a particle's
-// count hold stale but valid indices (the buffer is zero-initialised, only ever holds indices < n,
-// and one spare tile pads the end), so the speculative loads are always in bounds.
-template <class Body>
-__device__ __forceinline__ void for_nbrs_p(const uint32_t *__restrict__ base, int cnt, const float4 *__restrict__ A, Body body)
-{
-    walk_list<Operand1>(base, cnt, [&](uint32_t j, Operand1 &o) { o.a = A[j]; }, [&](const Operand1 &o, uint32_t) { body(o.a); });
-}
-template <int N, class Body>
-__device__ __forceinline__ void for_nbrs_p_quad(const uint32_t *__restrict__ base, int cnt, int q, float (&acc)[N], const float4 *__restrict__ A, Body body)
-{
-    walk_list_quad<N, Operand1>(base, cnt, q, acc, [&](uint32_t j, Operand1 &o) { o.a = A[j]; }, [&](const Operand1 &o, uint32_t) { body(o.a); });
-}
-
 // ---- the wall terms of the DFSPH solver loops from a per-step cache ------------------------------------------------------------
 // Walls are static and the positions are frozen between the list build and the integrator, so grad W_ib of a (particle, wall
 // particle) pair is the same f32 triple in every sweep of a step: D1 (k_density<DFSPH>) evaluates it anyway and leaves
@@ -1772,11 +1885,6 @@ __device__ __forceinline__ StageIdx stage_take(const uint32_t *__restrict__ s_id
 //   StageF4S          A, S -> s_A = A, s_S = S                                         key: A.w
 //   StageF4Src        A -> s_A = A; the index list is KEPT in s_src (a second operand is gathered from memory through it): nothing aliases
 struct StageNone {};
-template <bool SCALED>
-__device__ __forceinline__ float4 stage_pos(const float4 a, float w)
-{
-    return SCALED ? make_float4(a.x * 0x1p32f, a.y * 0x1p32f, a.z * 0x1p32f, w) : make_float4(a.x, a.y, a.z, w);
-}
 template <bool SCALED = false>
 struct StageF4 {
     float4 *s_A; const float4 *A;
@@ -1789,6 +1897,10 @@ struct StageF4 {
     __device__ __forceinline__ bool has_key() const { return true; }
     __device__ __forceinline__ bool hot(const Key &a) const { return a.w != 0.f; }
     __device__ __forceinline__ void store(int e, const Key &a, Rest) const { s_A[e] = stage_pos<SCALED>(a, a.w); }
+    // the reader (an operand source of the staged walks, see nl_operand)
+    using Op = OpA; static constexpr bool kScaled = SCALED;
+    __device__ __forceinline__ float4 pos(uint32_t e) const { return s_A[e]; }
+    __device__ __forceinline__ void rest(uint32_t, Op &) const {}
 };
 struct StageF4Src : StageF4<false> {
     uint32_t *s_src;
@@ -1796,6 +1908,14 @@ struct StageF4Src : StageF4<false> {
     static constexpr bool kIdxAliased = false;
     static __device__ __forceinline__ uint32_t *second(float4 *s_operand, int cap) { return reinterpret_cast<uint32_t *>(s_operand + cap); }
     __device__ __forceinline__ uint32_t *idx() const { return s_src; }
+    // the reader with a second operand gathered from memory through the kept index list
+    struct Gather {
+        const float4 *s_A; const uint32_t *s_src; const float4 *B;
+        using Op = OpAB; static constexpr bool kScaled = false;
+        __device__ __forceinline__ float4 pos(uint32_t e) const { return s_A[e]; }
+        __device__ __forceinline__ void rest(uint32_t e, Op &o) const { o.b = B[s_src[e]]; }
+    };
+    __device__ __forceinline__ Gather gather(const float4 *B) const { return Gather{s_A, s_src, B}; }
 };
 template <bool SCALED = false>
 struct StagePS {
@@ -1809,6 +1929,10 @@ struct StagePS {
     __device__ __forceinline__ bool has_key() const { return true; }
     __device__ __forceinline__ bool hot(Key s) const { return s != 0.f; }
     __device__ __forceinline__ void store(int e, Key s, const Rest &a) const { s_A[e] = stage_pos<SCALED>(a, s); }
+    // the reader (an operand source of the staged walks, see nl_operand)
+    using Op = OpA; static constexpr bool kScaled = SCALED;
+    __device__ __forceinline__ float4 pos(uint32_t e) const { return s_A[e]; }
+    __device__ __forceinline__ void rest(uint32_t, Op &) const {}
 };
 struct StagePair { float4 a, b; };
 template <bool SCALED = false>
@@ -1829,6 +1953,10 @@ struct StagePV {
         s_A[e] = stage_pos<SCALED>(r.a, r.b.x);
         s_B[e] = make_float2(r.b.y, r.b.z);
     }
+    // the reader (an operand source of the staged walks, see nl_operand)
+    using Op = OpAB; static constexpr bool kScaled = SCALED;
+    __device__ __forceinline__ float4 pos(uint32_t e) const { const float4 pa = s_A[e]; return make_float4(pa.x, pa.y, pa.z, 0.f); }
+    __device__ __forceinline__ void rest(uint32_t e, Op &o) const { const float4 pa = s_A[e]; const float2 pb = s_B[e]; o.b = make_float4(pa.w, pb.x, pb.y, 0.f); }
 };
 struct StageF4S {
     float4 *s_A; float *s_S; const float4 *A; const float *S;
@@ -1842,6 +1970,10 @@ struct StageF4S {
     __device__ __forceinline__ bool has_key() const { return true; }
     __device__ __forceinline__ bool hot(const Key &a) const { return a.w != 0.f; }
     __device__ __forceinline__ void store(int e, const Key &a, Rest s) const { s_A[e] = a; s_S[e] = s; }
+    // the reader (an operand source of the staged walks, see nl_operand)
+    using Op = OpAS; static constexpr bool kScaled = false;
+    __device__ __forceinline__ float4 pos(uint32_t e) const { return s_A[e]; }
+    __device__ __forceinline__ void rest(uint32_t e, Op &o) const { o.s = s_S[e]; }
 };
 
 // which workgroup's plan, and what the caller already fetched of it (StagePre)
@@ -1899,166 +2031,6 @@ __device__ __forceinline__ StageVerdict stage_operands(const L lay, const StageP
     __syncthreads();
     return kStaged;
 }
-// staged walkers: fluid entries are LOCAL indices into the staged arrays, tagged rigid entries stay global (rv.RP)
-template <bool RIGID, bool SCALED = false, class Body>
-__device__ __forceinline__ void for_staged_nbrs(const uint32_t *__restrict__ base, int cnt, const float4 *__restrict__ s_A, const RigidView &rv,
-                                                Body body)
-{
-    NlAhead ahead(base);
-    for (int kk = 0; kk < cnt; kk += 4) {
-        const uint4 jj = ahead.front();
-        const uint32_t j[4] = {jj.x, jj.y, jj.z, jj.w};
-        float4 a[4];
-        // a group without a rigid entry anywhere in the wave (nearly all of them: the body touches a thin layer of the fluid) takes the
-        // plain path; the branch is wave-uniform
-        if (RIGID && __any(((j[0] | j[1] | j[2] | j[3]) & kRigidTag) != 0)) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const bool rg = (j[u] & kRigidTag) != 0;
-                if (rg) {
-                    const float4 q = rv.RP[j[u] & ~kRigidTag];
-                    a[u] = SCALED ? make_float4(q.x * 0x1p32f, q.y * 0x1p32f, q.z * 0x1p32f, q.w) : q;
-                } else {
-                    a[u] = s_A[j[u] & ~kRigidTag];
-                }
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) a[u] = s_A[j[u]];
-        }
-        ahead.advance(kk);
-        const float4 none = make_float4(0.f, 0.f, 0.f, 0.f);
-        body(a[0], none, j[0]);
-        if (kk + 1 < cnt) body(a[1], none, j[1]);
-        if (kk + 2 < cnt) body(a[2], none, j[2]);
-        if (kk + 3 < cnt) body(a[3], none, j[3]);
-    }
-}
-template <bool RIGID, class Body>
-__device__ __forceinline__ void for_staged_nbrs_pv(const uint32_t *__restrict__ base, int cnt, const float4 *__restrict__ s_A,
-                                                   const uint32_t *__restrict__ s_src, const float4 *__restrict__ B, const RigidView &rv, Body body)
-{
-    NlAhead ahead(base);
-    for (int kk = 0; kk < cnt; kk += 4) {
-        const uint4 jj = ahead.front();
-        const uint32_t j[4] = {jj.x, jj.y, jj.z, jj.w};
-        float4 a[4], b[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const bool rg = RIGID && (j[u] & kRigidTag);
-            const uint32_t idx = RIGID ? (j[u] & ~kRigidTag) : j[u];
-            b[u] = B[rg ? 0u : s_src[idx]];
-            a[u] = rg ? rv.RP[idx] : s_A[idx];
-        }
-        ahead.advance(kk);
-        body(a[0], b[0], j[0]);
-        if (kk + 1 < cnt) body(a[1], b[1], j[1]);
-        if (kk + 2 < cnt) body(a[2], b[2], j[2]);
-        if (kk + 3 < cnt) body(a[3], b[3], j[3]);
-    }
-}
-
-template <bool RIGID, bool SCALED = false, class Body>
-__device__ __forceinline__ void for_staged_nbrs_pv2(const uint32_t *__restrict__ base, int cnt, const float4 *__restrict__ s_A,
-                                                    const float2 *__restrict__ s_B, const RigidView &rv, Body body)
-{
-    NlAhead ahead(base);
-    for (int kk = 0; kk < cnt; kk += 4) {
-        const uint4 jj = ahead.front();
-        const uint32_t j[4] = {jj.x, jj.y, jj.z, jj.w};
-        float4 a[4], b[4];
-        if (RIGID && __any(((j[0] | j[1] | j[2] | j[3]) & kRigidTag) != 0)) {      // wave-uniform, rare (see for_staged_nbrs)
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const bool rg = (j[u] & kRigidTag) != 0;
-                const uint32_t idx = j[u] & ~kRigidTag;
-                if (rg) {
-                    const float4 q = rv.RP[idx];                     // (x, y, z, V_r); the velocity operand is undefined for rigid entries
-                    a[u] = SCALED ? make_float4(q.x * 0x1p32f, q.y * 0x1p32f, q.z * 0x1p32f, q.w) : q;
-                    b[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-                } else {
-                    const float4 pa = s_A[idx]; const float2 pb = s_B[idx];
-                    a[u] = make_float4(pa.x, pa.y, pa.z, 0.f);
-                    b[u] = make_float4(pa.w, pb.x, pb.y, 0.f);
-                }
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const float4 pa = s_A[j[u]]; const float2 pb = s_B[j[u]];
-                a[u] = make_float4(pa.x, pa.y, pa.z, 0.f);
-                b[u] = make_float4(pa.w, pb.x, pb.y, 0.f);
-            }
-        }
-        ahead.advance(kk);
-        body(a[0], b[0], j[0]);
-        if (kk + 1 < cnt) body(a[1], b[1], j[1]);
-        if (kk + 2 < cnt) body(a[2], b[2], j[2]);
-        if (kk + 3 < cnt) body(a[3], b[3], j[3]);
-    }
-}
-
-// ---- walks of a 16-bit list (staged workgroup of an nl16 handle; no rigid entries): one 16-byte load = eight neighbours, taken
-// four at a time so that the registers in flight stay those of the 32-bit walk.  The next group is requested before the bodies
-// run, and only by lanes whose list goes on (the 32-bit walks read one stale group past the end: 16 B per particle and sweep).
-struct Nl16Group {
-    uint32_t w[4];
-    __device__ __forceinline__ uint32_t lo(int q) const { return w[q] & 0xffffu; }
-    __device__ __forceinline__ uint32_t hi(int q) const { return w[q] >> 16; }
-};
-template <class Fetch4>
-__device__ __forceinline__ void walk_list16(const uint32_t *__restrict__ base, int cnt, Fetch4 fetch4)
-{
-    if (cnt <= 0) return;
-    uint4 jn = nl_load(base);
-    for (int kk = 0; kk < cnt; kk += 8) {
-        const Nl16Group g = {{jn.x, jn.y, jn.z, jn.w}};
-        if (kk + 8 < cnt) jn = nl_load(base + (size_t)((kk >> 3) + 1) * 256);
-        fetch4(g.lo(0), g.hi(0), g.lo(1), g.hi(1), kk);
-        if (kk + 4 < cnt) fetch4(g.lo(2), g.hi(2), g.lo(3), g.hi(3), kk + 4);
-    }
-}
-template <class Body>
-__device__ __forceinline__ void for_staged16_nbrs(const uint32_t *__restrict__ base, int cnt, const float4 *__restrict__ s_A, Body body)
-{
-    const float4 none = make_float4(0.f, 0.f, 0.f, 0.f);
-    walk_list16(base, cnt, [&](uint32_t j0, uint32_t j1, uint32_t j2, uint32_t j3, int k0) {
-        const float4 a0 = s_A[j0], a1 = s_A[j1], a2 = s_A[j2], a3 = s_A[j3];
-        body(a0, none, 0u);
-        if (k0 + 1 < cnt) body(a1, none, 0u);
-        if (k0 + 2 < cnt) body(a2, none, 0u);
-        if (k0 + 3 < cnt) body(a3, none, 0u);
-    });
-}
-// A staged in LDS, B gathered from memory through the staged source index (k_dfsph_ext and the pressure solvers' three-operand sweeps)
-template <class Body>
-__device__ __forceinline__ void for_staged16_nbrs_pv(const uint32_t *__restrict__ base, int cnt, const float4 *__restrict__ s_A,
-                                                     const uint32_t *__restrict__ s_src, const float4 *__restrict__ B, Body body)
-{
-    walk_list16(base, cnt, [&](uint32_t j0, uint32_t j1, uint32_t j2, uint32_t j3, int k0) {
-        const float4 b0 = B[s_src[j0]], b1 = B[s_src[j1]], b2 = B[s_src[j2]], b3 = B[s_src[j3]];
-        const float4 a0 = s_A[j0], a1 = s_A[j1], a2 = s_A[j2], a3 = s_A[j3];
-        body(a0, b0, 0u);
-        if (k0 + 1 < cnt) body(a1, b1, 0u);
-        if (k0 + 2 < cnt) body(a2, b2, 0u);
-        if (k0 + 3 < cnt) body(a3, b3, 0u);
-    });
-}
-// both operands staged: (x, y, z, vx) and (vy, vz)
-template <class Body>
-__device__ __forceinline__ void for_staged16_nbrs_pv2(const uint32_t *__restrict__ base, int cnt, const float4 *__restrict__ s_A,
-                                                      const float2 *__restrict__ s_B, Body body)
-{
-    walk_list16(base, cnt, [&](uint32_t j0, uint32_t j1, uint32_t j2, uint32_t j3, int k0) {
-        const float4 a0 = s_A[j0], a1 = s_A[j1], a2 = s_A[j2], a3 = s_A[j3];
-        const float2 b0 = s_B[j0], b1 = s_B[j1], b2 = s_B[j2], b3 = s_B[j3];
-        body(make_float4(a0.x, a0.y, a0.z, 0.f), make_float4(a0.w, b0.x, b0.y, 0.f), 0u);
-        if (k0 + 1 < cnt) body(make_float4(a1.x, a1.y, a1.z, 0.f), make_float4(a1.w, b1.x, b1.y, 0.f), 0u);
-        if (k0 + 2 < cnt) body(make_float4(a2.x, a2.y, a2.z, 0.f), make_float4(a2.w, b2.x, b2.y, 0.f), 0u);
-        if (k0 + 3 < cnt) body(make_float4(a3.x, a3.y, a3.z, 0.f), make_float4(a3.w, b3.x, b3.y, 0.f), 0u);
-    });
-}
-
 template <bool DFSPH, bool RIGID, int MODE, bool RX = false>
 __global__ __launch_bounds__(kBlock) void k_density(Consts c, const float4 *__restrict__ P, const float4 *V,
                                                     const float4 *__restrict__ WP, const uint32_t *__restrict__ nl,
@@ -2076,7 +2048,9 @@ __global__ __launch_bounds__(kBlock) void k_density(Consts c, const float4 *__re
     const int tile = tp.phase == 0 ? xcd_block(blockIdx.x, gridDim.x) : sweep_tile(tp, false);
     if (tile < 0) return;
     SPH_SWEEP_PROLOGUE_G(QUAD, tile, true)
-    const bool staged = STAGED && stage_operands(StageF4<>{s_operand, P}, StagePlan{stage_src, stage_cnt, blk}) != kNotStaged;
+    const SrcA mem{P};
+    const StageF4<> lds{s_operand, P};
+    const bool staged = STAGED && stage_operands(lds, StagePlan{stage_src, stage_cnt, blk}) != kNotStaged;
     float fa[5] = {0.001f, 0.f, 0.f, 0.f, 0.f};              // rho starts at 0.001, solver_base.py:44
     float &rho = fa[0], &sx = fa[1], &sy = fa[2], &sz = fa[3], &sq = fa[4];
     auto pair = [&](const float4 pj, const float4, const uint32_t j) {
@@ -2093,10 +2067,10 @@ __global__ __launch_bounds__(kBlock) void k_density(Consts c, const float4 *__re
             sq += (rx * rx + ry * ry) + rz * rz;             // :71
         }
     };
-    if (QUAD) for_fluid_nbrs_quad<RIGID, false>(nlp, kf, q, fa, P, nullptr, rv, pair);
-    else if (staged && (RIGID ? stage_lists16(stage_cnt, blk) : c.nl16 != 0)) for_staged16_nbrs(nlp, kf, s_operand, pair);     // (a rigid build: no rigid cell near this tile)
-    else if (staged) for_staged_nbrs<RIGID>(nlp, kf, s_operand, rv, pair);
-    else for_fluid_nbrs<RIGID, false>(nlp, kf, P, nullptr, rv, pair);
+    if (QUAD) sweep_quad<RIGID>(mem, nlp, kf, q, fa, pair, rv);
+    else if (staged && (RIGID ? stage_lists16(stage_cnt, blk) : c.nl16 != 0)) walk_list16(lds, nlp, kf, pair);     // (a rigid build: no rigid cell near this tile)
+    else if (staged) walk_staged<RIGID>(lds, nlp, kf, pair, rv);
+    else sweep_list<RIGID>(mem, nlp, kf, pair, rv);
     float wa[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
     float &rho_b = wa[0], &bx = wa[1], &by = wa[2], &bz = wa[3], &bsq = wa[4];
     float4 *gcw = (DFSPH && !QUAD && wall_gc) ? wall_gc + gc_index(ii, 0, c.kbpitch) : nullptr;   // bodies run in list order: entry k goes to row k
@@ -2113,8 +2087,8 @@ __global__ __launch_bounds__(kBlock) void k_density(Consts c, const float4 *__re
             if (!QUAD && gcw) { *gcw = make_float4(g.x, g.y, g.z, pj.w); gcw += 64; }     // the solver loops' wall terms (for_wall_cache)
         }
     };
-    if (QUAD) for_nbrs_p_quad(nlbp, kb, q, wa, WP, wall);
-    else for_nbrs_p(nlbp, kb, WP, wall);
+    if (QUAD) sweep_quad<false>(SrcP{WP}, nlbp, kb, q, wa, wall);
+    else sweep_list<false>(SrcP{WP}, nlbp, kb, wall);
     float rho_i = c.boundary_handle ? rho + rho_b * c.rho0 : rho;   // solver_base.py:49,51
     if (!owner) return;
     rho_out[i] = rho_i;
@@ -2204,8 +2178,9 @@ __global__ __launch_bounds__(kBlock) void k_wcsph_force(Consts c, float dt, cons
         float st = c.tens_c * cubic_w_in(c, r);                 // :216
         tx += st * dx; ty += st * dy; tz += st * dz;
     };
-    if (QUAD) for_fluid_nbrs_quad<RIGID, true>(nlp, kf, q, fa, P, V, rv, pair);
-    else for_fluid_nbrs<RIGID, true>(nlp, kf, P, V, rv, pair);
+    const SrcAB mem{P, V};
+    if (QUAD) sweep_quad<RIGID>(mem, nlp, kf, q, fa, pair, rv);
+    else sweep_list<RIGID>(mem, nlp, kf, pair, rv);
     float wa[3] = {0.f, 0.f, 0.f};
     float &bx = wa[0], &by = wa[1], &bz = wa[2];
     if (c.boundary_handle) {
@@ -2218,8 +2193,8 @@ __global__ __launch_bounds__(kBlock) void k_wcsph_force(Consts c, float dt, cons
             float s = pj.w * p_i / rho_i_2;                  // wcsph_solver.py:99
             bx -= s * g.x; by -= s * g.y; bz -= s * g.z;
         };
-        if (QUAD) for_nbrs_p_quad(nlbp, kb, q, wa, WP, wall);
-        else for_nbrs_p(nlbp, kb, WP, wall);
+        if (QUAD) sweep_quad<false>(SrcP{WP}, nlbp, kb, q, wa, wall);
+        else sweep_list<false>(SrcP{WP}, nlbp, kb, wall);
     }
     if (!owner) return;
     float pg[3] = {gx, gy, gz};
@@ -2360,18 +2335,16 @@ __global__ __launch_bounds__(kBlock) void k_correct(Consts c, const float4 *__re
     };
     auto pair = [&](const float4 pj, const float4, const uint32_t j) { pair_term(std::false_type{}, pj, j); };
     auto pair_scaled = [&](const float4 pj, const float4, const uint32_t j) { pair_term(std::true_type{}, pj, j); };
-    struct OperandPS { float4 a; float s; };
-    if (QUAD) for_fluid_nbrs_quad<RIGID, false>(nlp, kf, q, fa, P, nullptr, rv, pair);
-    else if (staged && (RIGID ? stage_lists16(st.cnt, blk) : c.nl16 != 0)) for_staged16_nbrs(nlp, kf, s_operand, pair_scaled);
-    else if (staged) for_staged_nbrs<RIGID, true>(nlp, kf, s_operand, rv, pair_scaled);
-    else if (split)          // a workgroup of a kr_split handle whose set did not fit: two global gathers per neighbour (a tagged entry: the rigid sample)
-        walk_list<OperandPS>(nlp, kf, [&](uint32_t j, OperandPS &o) {
-                                 const bool rg = RIGID && (j & kRigidTag);
-                                 const uint32_t idx = RIGID ? (j & ~kRigidTag) : j;
-                                 o.a = rg ? rv.RP[idx] : P[idx]; o.s = rg ? o.a.w : krho[idx];
-                             },
-                             [&](const OperandPS &o, uint32_t j) { pair(make_float4(o.a.x, o.a.y, o.a.z, o.s), make_float4(0.f, 0.f, 0.f, 0.f), j); });
-    else for_fluid_nbrs<RIGID, false>(nlp, kf, P, nullptr, rv, pair);
+    const SrcA mem{P};
+    const StageF4<true> lds{s_operand, P};                   // (either layout staged above leaves (pos * 2^32, k / rho): one reader)
+    if (QUAD) sweep_quad<RIGID>(mem, nlp, kf, q, fa, pair, rv);
+    else if (staged && (RIGID ? stage_lists16(st.cnt, blk) : c.nl16 != 0)) walk_list16(lds, nlp, kf, pair_scaled);
+    else if (staged) walk_staged<RIGID>(lds, nlp, kf, pair_scaled, rv);
+    else if (split)          // a workgroup of a kr_split handle whose set did not fit: two global gathers per neighbour (a tagged entry: the rigid sample, V_r in .w)
+        sweep_list<RIGID>(SrcAS{P, krho}, nlp, kf, [&](const float4 a, const float s, const uint32_t j) {
+            pair(make_float4(a.x, a.y, a.z, (RIGID && (j & kRigidTag)) ? a.w : s), make_float4(0.f, 0.f, 0.f, 0.f), j);
+        }, rv);
+    else sweep_list<RIGID>(mem, nlp, kf, pair, rv);
     float wa[3] = {0.f, 0.f, 0.f};
     float &bx = wa[0], &by = wa[1], &bz = wa[2];
     auto wall = [&](const float4 pj) {
@@ -2381,13 +2354,13 @@ __global__ __launch_bounds__(kBlock) void k_correct(Consts c, const float4 *__re
         float s = pj.w * k_i / rho_i;                                             // :354 / :390 / :219
         bx += s * g.x; by += s * g.y; bz += s * g.z;
     };
-    if (QUAD) for_nbrs_p_quad(nlbp, kb, q, wa, WP, wall);
+    if (QUAD) sweep_quad<false>(SrcP{WP}, nlbp, kb, q, wa, wall);
     else if (wall_gc)
         for_wall_cache(wall_gc + gc_index(ii, 0, c.kbpitch), kb, [&](const float4 gv) {       // (grad W_ib, V_b) as D1 left them
             float s = gv.w * k_i / rho_i;
             bx += s * gv.x; by += s * gv.y; bz += s * gv.z;
         });
-    else for_nbrs_p(nlbp, kb, WP, wall);
+    else sweep_list<false>(SrcP{WP}, nlbp, kb, wall);
     if (track) {
         const bool changed = live && ((ghost && !c.ghost_walk) || ax != 0.f || ay != 0.f || az != 0.f || bx != 0.f || by != 0.f || bz != 0.f);
         corr_mark_changed(df, flow, wave_dirty, changed8, blk, i, live, changed, my_nbr);
@@ -2447,6 +2420,8 @@ __global__ __launch_bounds__(kBlock) void k_residual(Consts c, const float4 *__r
         return;
     }
     float2 *s_v2 = StagePV<true>::second(s_operand, c.stage_cap);
+    const SrcAB mem{P, V};
+    const StagePV<true> lds{s_operand, s_v2, P, V, nullptr};         // the reader; the launches below say which bytes they check
     const StagePlan plan{st.src, st.cnt, blk, hd.pre};
     // second level of the change propagation: did the v* of any staged PARTICLE change?  A `direct` tile stages in one batch (resid_note_work)
     int verdict;
@@ -2476,10 +2451,10 @@ __global__ __launch_bounds__(kBlock) void k_residual(Consts c, const float4 *__r
     };
     auto pair = [&](const float4 pj, const float4 vj, const uint32_t j) { pair_term(std::false_type{}, pj, vj, j); };
     auto pair_scaled = [&](const float4 pj, const float4 vj, const uint32_t j) { pair_term(std::true_type{}, pj, vj, j); };
-    if (QUAD) for_fluid_nbrs_quad<RIGID, true>(nlp, skip ? 0 : kf, q, fa, P, V, rv, pair);
-    else if (staged && (RIGID ? stage_lists16(st.cnt, blk) : c.nl16 != 0)) for_staged16_nbrs_pv2(nlp, skip ? 0 : kf, s_operand, s_v2, pair_scaled);
-    else if (staged) for_staged_nbrs_pv2<RIGID, true>(nlp, skip ? 0 : kf, s_operand, s_v2, rv, pair_scaled);
-    else for_fluid_nbrs<RIGID, true>(nlp, skip ? 0 : kf, P, V, rv, pair);
+    if (QUAD) sweep_quad<RIGID>(mem, nlp, skip ? 0 : kf, q, fa, pair, rv);
+    else if (staged && (RIGID ? stage_lists16(st.cnt, blk) : c.nl16 != 0)) walk_list16(lds, nlp, skip ? 0 : kf, pair_scaled);
+    else if (staged) walk_staged<RIGID>(lds, nlp, skip ? 0 : kf, pair_scaled, rv);
+    else sweep_list<RIGID>(mem, nlp, skip ? 0 : kf, pair, rv);
     float wa[1] = {0.f};
     float &accb = wa[0];
     auto wall = [&](const float4 pj) {
@@ -2488,12 +2463,12 @@ __global__ __launch_bounds__(kBlock) void k_residual(Consts c, const float4 *__r
         F3 g = K::grad_in(c, dx, dy, dz, r);
         accb += pj.w * dot3(vi.x, vi.y, vi.z, g.x, g.y, g.z);                     // :300 / :176
     };
-    if (QUAD) for_nbrs_p_quad(nlbp, skip ? 0 : kb, q, wa, WP, wall);
+    if (QUAD) sweep_quad<false>(SrcP{WP}, nlbp, skip ? 0 : kb, q, wa, wall);
     else if (wall_gc)
         for_wall_cache(wall_gc + gc_index(ii, 0, c.kbpitch), skip ? 0 : kb, [&](const float4 gv) {
             accb += gv.w * dot3(vi.x, vi.y, vi.z, gv.x, gv.y, gv.z);
         });
-    else for_nbrs_p(nlbp, skip ? 0 : kb, WP, wall);
+    else sweep_list<false>(SrcP{WP}, nlbp, skip ? 0 : kb, wall);
     float val = 0.f, kr = 0.f;
     int flag = 0;
     if (live) {
@@ -2542,7 +2517,10 @@ __global__ __launch_bounds__(kBlock) void k_dfsph_ext(Consts c, const float4 *__
     SPH_SWEEP_PROLOGUE_B(QUAD, tile)
     (void)kb; (void)nlbp;
     uint32_t *s_src = StageF4Src::second(s_operand, c.stage_cap);      // (vel, rho) needs 16 B: gathered from memory
-    const bool staged = STAGED && stage_operands(StageF4Src{{s_operand, P}, s_src}, StagePlan{stage_src, stage_cnt, blk}) != kNotStaged;
+    const SrcAB mem{P, V};
+    const StageF4Src lay{{s_operand, P}, s_src};
+    const StageF4Src::Gather lds = lay.gather(V);
+    const bool staged = STAGED && stage_operands(lay, StagePlan{stage_src, stage_cnt, blk}) != kNotStaged;
     const float4 vi = V[ii];
     const float rho_i = vi.w;
     float fa[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -2580,10 +2558,10 @@ __global__ __launch_bounds__(kBlock) void k_dfsph_ext(Consts c, const float4 *__
             wx += sv * g.x; wy += sv * g.y; wz += sv * g.z;
         }
     };
-    if (QUAD) for_fluid_nbrs_quad<RIGID, true>(nlp, kf, q, fa, P, V, rv, pair);
-    else if (staged && (RIGID ? stage_lists16(stage_cnt, blk) : c.nl16 != 0)) for_staged16_nbrs_pv(nlp, kf, s_operand, s_src, V, pair);
-    else if (staged) for_staged_nbrs_pv<RIGID>(nlp, kf, s_operand, s_src, V, rv, pair);
-    else for_fluid_nbrs<RIGID, true>(nlp, kf, P, V, rv, pair);
+    if (QUAD) sweep_quad<RIGID>(mem, nlp, kf, q, fa, pair, rv);
+    else if (staged && (RIGID ? stage_lists16(stage_cnt, blk) : c.nl16 != 0)) walk_list16(lds, nlp, kf, pair);
+    else if (staged) walk_staged<RIGID>(lds, nlp, kf, pair, rv);
+    else sweep_list<RIGID>(mem, nlp, kf, pair, rv);
     float vn = -INFINITY;
     if (live) {
         const float dt = ds->dt;

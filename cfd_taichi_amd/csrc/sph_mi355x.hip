@@ -25,6 +25,7 @@
 #include "sph_rigid_kernels.h"
 #include "sph_pbf_kernels.h"
 #include "sph_relaxed_kernels.h"
+#include "sph_selftest_walk.h"
 
 using namespace sph;
 
@@ -1335,6 +1336,75 @@ int sph_selftest_stage(SphHandle *h, int layout, int check, int empty_idle, int 
         }
     }
     (void)hipFree(d_runs); (void)hipFree(d_cnt); (void)hipFree(d_A); (void)hipFree(d_B); (void)hipFree(d_S); (void)hipFree(d_ch); (void)hipFree(d_out);
+    return rc;
+}
+
+int sph_selftest_walk(SphHandle *h, int walk, int src, int rigid, const uint32_t *lists, const int *counts, uint32_t run_first, uint32_t run_n,
+                      const float *A, const float *B, const float *C, const float *S, size_t n_src, const float *RP, size_t n_rig, uint32_t *out)
+{
+    int ndev = 0;
+    const int device = h ? h->device : 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(h, SPH_E_NO_DEVICE, "no HIP device available");
+    constexpr int NP = kWalkTestParticles, ROWS = kWalkTestRows, PITCH = kWalkTestPitch;
+    const bool lds = walk >= 2, half = walk == 3;
+    if (walk < 0 || walk > 3 || src < 0 || src > (lds ? 8 : 4) || (rigid && (half || (!lds && src == 0))) || !lists || !counts || !A || !B || !C || !S ||
+        !RP || n_src == 0 || n_rig == 0 || !out || run_n == 0 || run_n > (uint32_t)kWalkTestCap || (size_t)run_first + run_n > n_src)
+        return fail(h, SPH_E_INVALID, "bad argument");
+    // the lists as k_build_nl lays them out (nl_index; 16-bit: entry 2q in the low, 2q + 1 in the high half of word q of a group, NlWriter), one
+    // zeroed spare tile behind them.  Every entry a walk can fetch must be a valid index, the slots past a count and the spare group included
+    std::vector<uint32_t> nl((size_t)(NP / 64 + 1) * PITCH * 64, 0u);
+    for (int i = 0; i < NP; ++i) {
+        if (counts[i] < 0 || counts[i] > ROWS) return fail(h, SPH_E_INVALID, "a count leaves 0 .. 24");
+        for (int k = 0; k < (half ? ROWS : PITCH); ++k) {
+            const uint32_t j = lists[(size_t)i * PITCH + k];
+            const bool rg = (j & kRigidTag) != 0;
+            if (rg ? (!rigid || (j & ~kRigidTag) >= n_rig) : j >= (lds ? (size_t)run_n : n_src)) return fail(h, SPH_E_INVALID, "a list entry leaves its array");
+            if (half) nl[nl_index(i, 4 * (k >> 3) + ((k & 7) >> 1), PITCH)] |= j << (16 * (k & 1));
+            else nl[nl_index(i, k, PITCH)] = j;
+        }
+    }
+    std::vector<uint2> plan(kStageMaxCells, make_uint2(0u, 0u));
+    plan[0] = make_uint2(run_first, run_n << 16);
+    const int head = (int)run_n | (1 << 16);
+    const int nthreads = walk == 1 ? 4 * NP : NP;
+    if (hipSetDevice(device) != hipSuccess) return fail(h, SPH_E_HIP, "hipSetDevice failed");
+    uint2 *d_runs = nullptr; int *d_head = nullptr, *d_cnt = nullptr; float4 *d_A = nullptr, *d_B = nullptr, *d_C = nullptr, *d_RP = nullptr; float *d_S = nullptr;
+    uint32_t *d_nl = nullptr, *d_out = nullptr;
+    int rc = SPH_OK;
+    if (hipMalloc((void **)&d_runs, plan.size() * sizeof(uint2)) != hipSuccess || hipMalloc((void **)&d_head, sizeof(int)) != hipSuccess ||
+        hipMalloc((void **)&d_cnt, NP * sizeof(int)) != hipSuccess || hipMalloc((void **)&d_A, n_src * 16) != hipSuccess || hipMalloc((void **)&d_B, n_src * 16) != hipSuccess ||
+        hipMalloc((void **)&d_C, n_src * 16) != hipSuccess || hipMalloc((void **)&d_S, n_src * 4) != hipSuccess || hipMalloc((void **)&d_RP, n_rig * 16) != hipSuccess ||
+        hipMalloc((void **)&d_nl, nl.size() * 4) != hipSuccess || hipMalloc((void **)&d_out, (size_t)nthreads * 16) != hipSuccess)
+        rc = fail(h, SPH_E_HIP, "hipMalloc failed");
+    if (!rc) {
+        (void)hipMemcpy(d_runs, plan.data(), plan.size() * sizeof(uint2), hipMemcpyHostToDevice);
+        (void)hipMemcpy(d_head, &head, sizeof(int), hipMemcpyHostToDevice);
+        (void)hipMemcpy(d_cnt, counts, NP * sizeof(int), hipMemcpyHostToDevice);
+        (void)hipMemcpy(d_A, A, n_src * 16, hipMemcpyHostToDevice);
+        (void)hipMemcpy(d_B, B, n_src * 16, hipMemcpyHostToDevice);
+        (void)hipMemcpy(d_C, C, n_src * 16, hipMemcpyHostToDevice);
+        (void)hipMemcpy(d_S, S, n_src * 4, hipMemcpyHostToDevice);
+        (void)hipMemcpy(d_RP, RP, n_rig * 16, hipMemcpyHostToDevice);
+        (void)hipMemcpy(d_nl, nl.data(), nl.size() * 4, hipMemcpyHostToDevice);
+        (void)hipMemset(d_out, 0, (size_t)nthreads * 16);
+        RigidView rv{};
+        rv.RP = d_RP;
+        const size_t smem = (size_t)kWalkTestCap * 32;            // the largest set: StageUpdateP
+        const dim3 grid((unsigned)(nthreads / kBlock)), block(kBlock);
+        auto launch = [&](auto rg) {
+            constexpr bool RG = decltype(rg)::value;
+            if (walk == 0) hipLaunchKernelGGL((k_selftest_walk<0, RG>), grid, block, smem, 0, src, d_runs, d_head, d_A, d_B, d_C, d_S, rv, d_nl, d_cnt, d_out);
+            else if (walk == 1) hipLaunchKernelGGL((k_selftest_walk<1, RG>), grid, block, smem, 0, src, d_runs, d_head, d_A, d_B, d_C, d_S, rv, d_nl, d_cnt, d_out);
+            else if (walk == 2) hipLaunchKernelGGL((k_selftest_walk<2, RG>), grid, block, smem, 0, src, d_runs, d_head, d_A, d_B, d_C, d_S, rv, d_nl, d_cnt, d_out);
+        };
+        if (walk == 3) hipLaunchKernelGGL((k_selftest_walk<3, false>), grid, block, smem, 0, src, d_runs, d_head, d_A, d_B, d_C, d_S, rv, d_nl, d_cnt, d_out);
+        else if (rigid) launch(std::true_type{});
+        else launch(std::false_type{});
+        if (hipDeviceSynchronize() != hipSuccess) rc = fail(h, SPH_E_HIP, "selftest kernel failed");
+        else (void)hipMemcpy(out, d_out, (size_t)nthreads * 16, hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(d_runs); (void)hipFree(d_head); (void)hipFree(d_cnt); (void)hipFree(d_A); (void)hipFree(d_B); (void)hipFree(d_C); (void)hipFree(d_S);
+    (void)hipFree(d_RP); (void)hipFree(d_nl); (void)hipFree(d_out);
     return rc;
 }
 

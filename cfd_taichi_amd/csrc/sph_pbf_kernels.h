@@ -68,8 +68,8 @@ __global__ __launch_bounds__(kBlock) void k_pbf_lambda(Consts c, PbfConsts k, co
         cx += gx; cy += gy; cz += gz;                              // :116-117
         sum += (gx * gx + gy * gy) + gz * gz;                      // :133-134
     };
-    if (QUAD) for_nbrs_p_quad(nlp, kf, q, fa, P, pair);
-    else for_nbrs_p(nlp, kf, P, pair);
+    if (QUAD) sweep_quad<false>(SrcP{P}, nlp, kf, q, fa, pair);
+    else sweep_list<false>(SrcP{P}, nlp, kf, pair);
     float wa[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
     float &rb = wa[0], &bx = wa[1], &by = wa[2], &bz = wa[3], &sb = wa[4];
     auto wall = [&](const float4 pj) {
@@ -81,8 +81,8 @@ __global__ __launch_bounds__(kBlock) void k_pbf_lambda(Consts c, PbfConsts k, co
         bx += gx; by += gy; bz += gz;                              // :120-122
         sb += (gx * gx + gy * gy) + gz * gz;                       // :139-140
     };
-    if (QUAD) for_nbrs_p_quad(nlbp, kb, q, wa, WP, wall);
-    else for_nbrs_p(nlbp, kb, WP, wall);
+    if (QUAD) sweep_quad<false>(SrcP{WP}, nlbp, kb, q, wa, wall);
+    else sweep_list<false>(SrcP{WP}, nlbp, kb, wall);
     if (!owner) return;
     const float rho_i = c.boundary_handle ? rho + rb * c.rho0 : rho;
     if (rho_only) { rho_out[i] = rho_i; return; }                  // compute_all_rho alone (solver_base.py:36-50 with :166-174): pbf_lambda keeps its values
@@ -118,8 +118,8 @@ __global__ __launch_bounds__(kBlock) void k_pbf_delta(Consts c, PbfConsts k, flo
         const float f = (li + pj.w) + sc;                          // :153
         ax += f * g.x; ay += f * g.y; az += f * g.z;
     };
-    if (QUAD) for_nbrs_p_quad(nlp, kf, q, fa, PL, pair);
-    else for_nbrs_p(nlp, kf, PL, pair);
+    if (QUAD) sweep_quad<false>(SrcP{PL}, nlp, kf, q, fa, pair);
+    else sweep_list<false>(SrcP{PL}, nlp, kf, pair);
     float wa[3] = {0.f, 0.f, 0.f};
     float &bx = wa[0], &by = wa[1], &bz = wa[2];
     auto wall = [&](const float4 pj) {
@@ -131,8 +131,8 @@ __global__ __launch_bounds__(kBlock) void k_pbf_delta(Consts c, PbfConsts k, flo
         const float f = li + sc;                                   // :164
         bx += f * g.x; by += f * g.y; bz += f * g.z;
     };
-    if (QUAD) for_nbrs_p_quad(nlbp, kb, q, wa, WP, wall);
-    else for_nbrs_p(nlbp, kb, WP, wall);
+    if (QUAD) sweep_quad<false>(SrcP{WP}, nlbp, kb, q, wa, wall);
+    else sweep_list<false>(SrcP{WP}, nlbp, kb, wall);
     if (!owner) return;
     float dp[3];
     if (c.boundary_handle) { dp[0] = (ax + bx) / c.rho0; dp[1] = (ay + by) / c.rho0; dp[2] = (az + bz) / c.rho0; }   // :62

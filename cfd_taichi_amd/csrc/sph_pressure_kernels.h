@@ -29,165 +29,6 @@ __device__ __forceinline__ float div_const(float a, float d, float rd)
     return __builtin_fmaf(e, rd, q0);
 }
 
-// fluid-list walkers; with RIGID the list may hold tagged rigid entries (bit 31): their position comes from rv.RP and the
-// other operands are undefined.  body(..., j): j & kRigidTag marks a rigid neighbour.
-template <bool RIGID, class Body>
-__device__ __forceinline__ void for_nbrs_ps(const uint32_t *__restrict__ base, int cnt, const float4 *__restrict__ A,
-                                            const float *__restrict__ S, const RigidView &rv, Body body)
-{
-    struct Op { float4 a; float s; };
-    walk_list<Op>(base, cnt, [&](uint32_t j, Op &o) {
-        const bool rg = RIGID && (j & kRigidTag);
-        const uint32_t idx = RIGID ? (j & ~kRigidTag) : j;
-        o.a = rg ? rv.RP[idx] : A[idx];
-        o.s = S[rg ? 0u : idx];
-    }, [&](const Op &o, uint32_t j) { body(o.a, o.s, j); });
-}
-template <bool RIGID, class Body>
-__device__ __forceinline__ void for_nbrs_3(const uint32_t *__restrict__ base, int cnt, const float4 *__restrict__ A,
-                                           const float4 *__restrict__ B, const float4 *__restrict__ C, const RigidView &rv, Body body)
-{
-    struct Op { float4 a, b, c; };
-    walk_list<Op>(base, cnt, [&](uint32_t j, Op &o) {
-        const bool rg = RIGID && (j & kRigidTag);
-        const uint32_t idx = RIGID ? (j & ~kRigidTag) : j;
-        o.a = rg ? rv.RP[idx] : A[idx];
-        o.b = B[rg ? 0u : idx];
-        o.c = C[rg ? 0u : idx];
-    }, [&](const Op &o, uint32_t j) { body(o.a, o.b, o.c, j); });
-}
-
-// quad forms (small scenes, four lanes per particle: walk_list_quad in sph_kernels.h)
-template <bool RIGID, int N, class Body>
-__device__ __forceinline__ void for_nbrs_ps_quad(const uint32_t *__restrict__ base, int cnt, int q, float (&acc)[N], const float4 *__restrict__ A,
-                                                 const float *__restrict__ S, const RigidView &rv, Body body)
-{
-    struct Op { float4 a; float s; };
-    walk_list_quad<N, Op>(base, cnt, q, acc, [&](uint32_t j, Op &o) {
-        const bool rg = RIGID && (j & kRigidTag);
-        const uint32_t idx = RIGID ? (j & ~kRigidTag) : j;
-        o.a = rg ? rv.RP[idx] : A[idx];
-        o.s = S[rg ? 0u : idx];
-    }, [&](const Op &o, uint32_t j) { body(o.a, o.s, j); });
-}
-template <bool RIGID, int N, class Body>
-__device__ __forceinline__ void for_nbrs_3_quad(const uint32_t *__restrict__ base, int cnt, int q, float (&acc)[N], const float4 *__restrict__ A,
-                                                const float4 *__restrict__ B, const float4 *__restrict__ C, const RigidView &rv, Body body)
-{
-    struct Op { float4 a, b, c; };
-    walk_list_quad<N, Op>(base, cnt, q, acc, [&](uint32_t j, Op &o) {
-        const bool rg = RIGID && (j & kRigidTag);
-        const uint32_t idx = RIGID ? (j & ~kRigidTag) : j;
-        o.a = rg ? rv.RP[idx] : A[idx];
-        o.b = B[rg ? 0u : idx];
-        o.c = C[rg ? 0u : idx];
-    }, [&](const Op &o, uint32_t j) { body(o.a, o.b, o.c, j); });
-}
-
-// staged forms (LDS staging plan of k_build_nl, IISPH on the Morton curve): the first operand comes from LDS, the others are
-// gathered from memory through the staged source index
-template <bool RIGID, class Body>
-__device__ __forceinline__ void for_staged_nbrs_ps(const uint32_t *__restrict__ base, int cnt, const float4 *__restrict__ s_A,
-                                                   const uint32_t *__restrict__ s_src, const float *__restrict__ S, const RigidView &rv, Body body)
-{
-    NlAhead ahead(base);
-    for (int kk = 0; kk < cnt; kk += 4) {
-        const uint4 jj = ahead.front();
-        const uint32_t j[4] = {jj.x, jj.y, jj.z, jj.w};
-        float4 a[4]; float sc[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const bool rg = RIGID && (j[u] & kRigidTag);
-            const uint32_t idx = RIGID ? (j[u] & ~kRigidTag) : j[u];
-            sc[u] = S[rg ? 0u : s_src[idx]];
-            a[u] = rg ? rv.RP[idx] : s_A[idx];
-        }
-        ahead.advance(kk);
-        body(a[0], sc[0], j[0]);
-        if (kk + 1 < cnt) body(a[1], sc[1], j[1]);
-        if (kk + 2 < cnt) body(a[2], sc[2], j[2]);
-        if (kk + 3 < cnt) body(a[3], sc[3], j[3]);
-    }
-}
-template <bool RIGID, class Body>
-__device__ __forceinline__ void for_staged_nbrs_ps2(const uint32_t *__restrict__ base, int cnt, const float4 *__restrict__ s_A,
-                                                    const float *__restrict__ s_S, const RigidView &rv, Body body)
-{
-    NlAhead ahead(base);
-    for (int kk = 0; kk < cnt; kk += 4) {
-        const uint4 jj = ahead.front();
-        const uint32_t j[4] = {jj.x, jj.y, jj.z, jj.w};
-        float4 a[4]; float sc[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const bool rg = RIGID && (j[u] & kRigidTag);
-            const uint32_t idx = RIGID ? (j[u] & ~kRigidTag) : j[u];
-            sc[u] = s_S[rg ? 0u : idx];
-            a[u] = rg ? rv.RP[idx] : s_A[idx];
-        }
-        ahead.advance(kk);
-        body(a[0], sc[0], j[0]);
-        if (kk + 1 < cnt) body(a[1], sc[1], j[1]);
-        if (kk + 2 < cnt) body(a[2], sc[2], j[2]);
-        if (kk + 3 < cnt) body(a[3], sc[3], j[3]);
-    }
-}
-// update_p: positions + p, the source index and the three components of the third operand staged (32 B per staged particle);
-// the second operand is gathered from memory through the source index
-template <bool RIGID, class Body>
-__device__ __forceinline__ void for_staged_nbrs_3e(const uint32_t *__restrict__ base, int cnt, const float4 *__restrict__ s_A,
-                                                   const uint32_t *__restrict__ s_src, const float *__restrict__ s_cx,
-                                                   const float *__restrict__ s_cy, const float *__restrict__ s_cz,
-                                                   const float4 *__restrict__ B, const RigidView &rv, Body body)
-{
-    NlAhead ahead(base);
-    for (int kk = 0; kk < cnt; kk += 4) {
-        const uint4 jj = ahead.front();
-        const uint32_t j[4] = {jj.x, jj.y, jj.z, jj.w};
-        float4 a[4], b[4], cc[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const bool rg = RIGID && (j[u] & kRigidTag);
-            const uint32_t idx = RIGID ? (j[u] & ~kRigidTag) : j[u];
-            const uint32_t li = rg ? 0u : idx;
-            b[u] = B[s_src[li]];
-            cc[u] = make_float4(s_cx[li], s_cy[li], s_cz[li], 0.f);
-            a[u] = rg ? rv.RP[idx] : s_A[idx];
-        }
-        ahead.advance(kk);
-        body(a[0], b[0], cc[0], j[0]);
-        if (kk + 1 < cnt) body(a[1], b[1], cc[1], j[1]);
-        if (kk + 2 < cnt) body(a[2], b[2], cc[2], j[2]);
-        if (kk + 3 < cnt) body(a[3], b[3], cc[3], j[3]);
-    }
-}
-template <bool RIGID, class Body>
-__device__ __forceinline__ void for_staged_nbrs_3(const uint32_t *__restrict__ base, int cnt, const float4 *__restrict__ s_A,
-                                                  const uint32_t *__restrict__ s_src, const float4 *__restrict__ B, const float4 *__restrict__ C,
-                                                  const RigidView &rv, Body body)
-{
-    NlAhead ahead(base);
-    for (int kk = 0; kk < cnt; kk += 4) {
-        const uint4 jj = ahead.front();
-        const uint32_t j[4] = {jj.x, jj.y, jj.z, jj.w};
-        float4 a[4], b[4], cc[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const bool rg = RIGID && (j[u] & kRigidTag);
-            const uint32_t idx = RIGID ? (j[u] & ~kRigidTag) : j[u];
-            const uint32_t src = rg ? 0u : s_src[idx];
-            b[u] = B[src];
-            cc[u] = C[src];
-            a[u] = rg ? rv.RP[idx] : s_A[idx];
-        }
-        ahead.advance(kk);
-        body(a[0], b[0], cc[0], j[0]);
-        if (kk + 1 < cnt) body(a[1], b[1], cc[1], j[1]);
-        if (kk + 2 < cnt) body(a[2], b[2], cc[2], j[2]);
-        if (kk + 3 < cnt) body(a[3], b[3], cc[3], j[3]);
-    }
-}
-
 // predicted / integrated positions against the clamp walls      pcisph_solver.py:79-89, 234-244; iisph_solver.py:198-207
 __device__ __forceinline__ void clamp_walls(const Consts &c, float pos[3], float vel[3])
 {
@@ -276,7 +117,10 @@ __global__ __launch_bounds__(kBlock) void k_pci_ext(Consts c, float dt, const fl
     SPH_SWEEP_PROLOGUE_M(QUAD)
     (void)kb; (void)nlbp;
     uint32_t *s_src = StageF4Src::second(s_operand, c.stage_cap);
-    const bool staged = STAGED && stage_operands(StageF4Src{{s_operand, P}, s_src}, StagePlan{stage_src, stage_cnt, blk}) != kNotStaged;
+    const SrcAB mem{P, V};
+    const StageF4Src lay{{s_operand, P}, s_src};
+    const StageF4Src::Gather lds = lay.gather(V);
+    const bool staged = STAGED && stage_operands(lay, StagePlan{stage_src, stage_cnt, blk}) != kNotStaged;
     const float4 vi = V[ii];
     const float rho_i = pi.w;
     float fa[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -299,9 +143,9 @@ __global__ __launch_bounds__(kBlock) void k_pci_ext(Consts c, float dt, const fl
             wx += sv * g.x; wy += sv * g.y; wz += sv * g.z;
         }
     };
-    if (QUAD) for_fluid_nbrs_quad<RIGID, true>(nlp, kf, q, fa, P, V, rv, pair);
-    else if (staged) for_staged_nbrs_pv<RIGID>(nlp, kf, s_operand, s_src, V, rv, pair);
-    else for_fluid_nbrs<RIGID, true>(nlp, kf, P, V, rv, pair);
+    if (QUAD) sweep_quad<RIGID>(mem, nlp, kf, q, fa, pair, rv);
+    else if (staged) walk_staged<RIGID>(lds, nlp, kf, pair, rv);
+    else sweep_list<RIGID>(mem, nlp, kf, pair, rv);
     if (!owner) return;
     float ten[3] = {tx * c.m, ty * c.m, tz * c.m};           // :209
     float vis[3] = {wx * c.m, wy * c.m, wz * c.m};           // :175
@@ -347,7 +191,9 @@ __global__ __launch_bounds__(kBlock) void k_pci_predict_rho(Consts c, float delt
     extern __shared__ float4 s_operand[];
     if (gate_closed(ds, gate)) return;
     SPH_SWEEP_PROLOGUE_M(QUAD)
-    const bool staged = STAGED && stage_operands(StageF4<>{s_operand, P}, StagePlan{stage_src, stage_cnt, blk}) != kNotStaged;
+    const SrcA mem{P};
+    const StageF4<> lds{s_operand, P};
+    const bool staged = STAGED && stage_operands(lds, StagePlan{stage_src, stage_cnt, blk}) != kNotStaged;
     float fa[1] = {0.f};
     float &rp = fa[0];
     auto pair = [&](const float4 pj, const float4, const uint32_t j) {
@@ -355,17 +201,17 @@ __global__ __launch_bounds__(kBlock) void k_pci_predict_rho(Consts c, float delt
         if (RIGID && (j & kRigidTag)) rp += K::w(c, K::norm3(dx, dy, dz)) * pj.w * c.rho0;
         else rp += K::w(c, K::norm3(dx, dy, dz)) * c.m;      // :155-156
     };
-    if (QUAD) for_fluid_nbrs_quad<RIGID, false>(nlp, kf, q, fa, P, nullptr, rv, pair);
-    else if (staged) for_staged_nbrs<RIGID>(nlp, kf, s_operand, rv, pair);
-    else for_fluid_nbrs<RIGID, false>(nlp, kf, P, nullptr, rv, pair);
+    if (QUAD) sweep_quad<RIGID>(mem, nlp, kf, q, fa, pair, rv);
+    else if (staged) walk_staged<RIGID>(lds, nlp, kf, pair, rv);
+    else sweep_list<RIGID>(mem, nlp, kf, pair, rv);
     float wa[1] = {0.f};
     float &rb = wa[0];
     auto wall = [&](const float4 pj) {
         float dx = pi.x - pj.x, dy = pi.y - pj.y, dz = pi.z - pj.z;
         rb += K::w(c, K::norm3(dx, dy, dz)) * pj.w;          // :167-168
     };
-    if (QUAD) for_nbrs_p_quad(nlbp, kb, q, wa, WP, wall);
-    else for_nbrs_p(nlbp, kb, WP, wall);
+    if (QUAD) sweep_quad<false>(SrcP{WP}, nlbp, kb, q, wa, wall);
+    else sweep_list<false>(SrcP{WP}, nlbp, kb, wall);
     float val = 0.f;
     int flag = 0;
     if (live) {
@@ -399,17 +245,19 @@ __global__ __launch_bounds__(kBlock) void k_pci_press(Consts c, float dt, const 
     if (gate_closed(ds, gate)) return;
     const bool track = STAGED && !RIGID && zero_press != nullptr;          // tiles without pressure, see the note above k_pci_predict_rho
     SPH_SWEEP_PROLOGUE_B(QUAD, track ? (int)blockIdx.x : xcd_block(blockIdx.x, gridDim.x))
+    const SrcA mem{P};
+    const StageF4<> lds{s_operand, P};
     bool staged, all_zero = false;
     if (track) {
         const int was_zero = zero_press[blk];                      // PF / PP of this tile hold the zero-pressure values (read before the barriers below)
         // (a staged set of no particles sees no pressure: kStagedIdle)
-        const int verdict = stage_operands<kCheckWith, kStagedIdle>(StageF4<>{s_operand, P}, StagePlan{stage_src, stage_cnt, blk});
+        const int verdict = stage_operands<kCheckWith, kStagedIdle>(lds, StagePlan{stage_src, stage_cnt, blk});
         all_zero = verdict == kStagedIdle;                                  // every pressure this tile can see is 0: every term below is +-0
         if (all_zero && was_zero) return;                          // ... and its outputs already say so
         if (threadIdx.x == 0) zero_press[blk] = all_zero ? 1 : 0;
         staged = verdict != kNotStaged;
     } else {
-        staged = STAGED && stage_operands(StageF4<>{s_operand, P}, StagePlan{stage_src, stage_cnt, blk}) != kNotStaged;
+        staged = STAGED && stage_operands(lds, StagePlan{stage_src, stage_cnt, blk}) != kNotStaged;
     }
     const float p_i = pi.w;
     constexpr float kRho0Sq = 1000000.0f;                    // self.rho_0 ** 2 (Python int)
@@ -434,9 +282,9 @@ __global__ __launch_bounds__(kBlock) void k_pci_press(Consts c, float dt, const 
     };
     // (all_zero: the sums would be +0 + (+-0 terms) = +0, the accumulators as they stand)
     if (all_zero) {}
-    else if (QUAD) for_fluid_nbrs_quad<RIGID, false>(nlp, kf, q, fa, P, nullptr, rv, pair);
-    else if (staged) for_staged_nbrs<RIGID>(nlp, kf, s_operand, rv, pair);
-    else for_fluid_nbrs<RIGID, false>(nlp, kf, P, nullptr, rv, pair);
+    else if (QUAD) sweep_quad<RIGID>(mem, nlp, kf, q, fa, pair, rv);
+    else if (staged) walk_staged<RIGID>(lds, nlp, kf, pair, rv);
+    else sweep_list<RIGID>(mem, nlp, kf, pair, rv);
     float wa[3] = {0.f, 0.f, 0.f};
     float &bx = wa[0], &by = wa[1], &bz = wa[2];
     if (c.boundary_handle && !all_zero) {
@@ -448,8 +296,8 @@ __global__ __launch_bounds__(kBlock) void k_pci_press(Consts c, float dt, const 
             float s = pj.w * p_i / rho_i_2;                  // :223
             bx -= s * g.x; by -= s * g.y; bz -= s * g.z;
         };
-        if (QUAD) for_nbrs_p_quad(nlbp, kb, q, wa, WP, wall);
-        else for_nbrs_p(nlbp, kb, WP, wall);
+        if (QUAD) sweep_quad<false>(SrcP{WP}, nlbp, kb, q, wa, wall);
+        else sweep_list<false>(SrcP{WP}, nlbp, kb, wall);
     }
     if (!owner) return;
     float pf[3];
@@ -511,7 +359,10 @@ __global__ __launch_bounds__(kBlock) void k_ii_advect(Consts c, float dt, const 
     extern __shared__ float4 s_operand[];
     SPH_SWEEP_PROLOGUE_M(QUAD)
     uint32_t *s_src = StageF4Src::second(s_operand, c.stage_cap);
-    const bool staged = STAGED && stage_operands(StageF4Src{{s_operand, P}, s_src}, StagePlan{stage_src, stage_cnt, blk}) != kNotStaged;
+    const SrcAB mem{P, V};
+    const StageF4Src lay{{s_operand, P}, s_src};
+    const StageF4Src::Gather lds = lay.gather(V);
+    const bool staged = STAGED && stage_operands(lay, StagePlan{stage_src, stage_cnt, blk}) != kNotStaged;
     const float4 vi = V[ii];
     const float rho_i = pi.w;
     const float s_f = c.neg_m / (rho_i * rho_i);             // compute_d_ii :280 (same value for every fluid neighbour)
@@ -542,9 +393,9 @@ __global__ __launch_bounds__(kBlock) void k_ii_advect(Consts c, float dt, const 
             wx += sv * g.x; wy += sv * g.y; wz += sv * g.z;
         }
     };
-    if (QUAD) for_fluid_nbrs_quad<RIGID, true>(nlp, kf, q, fa, P, V, rv, pair);
-    else if (staged) for_staged_nbrs_pv<RIGID>(nlp, kf, s_operand, s_src, V, rv, pair);
-    else for_fluid_nbrs<RIGID, true>(nlp, kf, P, V, rv, pair);
+    if (QUAD) sweep_quad<RIGID>(mem, nlp, kf, q, fa, pair, rv);
+    else if (staged) walk_staged<RIGID>(lds, nlp, kf, pair, rv);
+    else sweep_list<RIGID>(mem, nlp, kf, pair, rv);
     float wa[3] = {0.f, 0.f, 0.f};
     float &bx = wa[0], &by = wa[1], &bz = wa[2];
     if (c.boundary_handle) {
@@ -556,8 +407,8 @@ __global__ __launch_bounds__(kBlock) void k_ii_advect(Consts c, float dt, const 
             float s = -pj.w / den;                           // compute_boundary_d_ii :292
             bx += s * g.x; by += s * g.y; bz += s * g.z;
         };
-        if (QUAD) for_nbrs_p_quad(nlbp, kb, q, wa, WP, wall);
-        else for_nbrs_p(nlbp, kb, WP, wall);
+        if (QUAD) sweep_quad<false>(SrcP{WP}, nlbp, kb, q, wa, wall);
+        else sweep_list<false>(SrcP{WP}, nlbp, kb, wall);
     }
     if (!owner) return;
     float ten[3] = {tx * c.m, ty * c.m, tz * c.m};
@@ -594,7 +445,9 @@ __global__ __launch_bounds__(kBlock) void k_ii_rho_adv(Consts c, float dt, const
     extern __shared__ float4 s_operand[];
     SPH_SWEEP_PROLOGUE_M(QUAD)
     float2 *s_v2 = StagePV<>::second(s_operand, c.stage_cap);
-    const bool staged = STAGED && stage_operands(StagePV<>{s_operand, s_v2, P, V, nullptr}, StagePlan{stage_src, stage_cnt, blk}) != kNotStaged;
+    const SrcAB mem{P, V};
+    const StagePV<> lds{s_operand, s_v2, P, V, nullptr};
+    const bool staged = STAGED && stage_operands(lds, StagePlan{stage_src, stage_cnt, blk}) != kNotStaged;
     const float4 vi = V[ii], di = DII[ii];
     const float rho_i = pi.w;
     const float cji = -dt * dt * c.m / (rho_i * rho_i);      // scalar prefix of d_ji, compute_a_ii :302-303
@@ -614,9 +467,9 @@ __global__ __launch_bounds__(kBlock) void k_ii_rho_adv(Consts c, float dt, const
         ra += c.m * dot3(vi.x - vj.x, vi.y - vj.y, vi.z - vj.z, g.x, g.y, g.z);        // compute_rho_adv :332
         aii += c.m * dot3(ex, ey, ez, g.x, g.y, g.z);                                  // compute_a_ii :304
     };
-    if (QUAD) for_fluid_nbrs_quad<RIGID, true>(nlp, kf, q, fa, P, V, rv, pair);
-    else if (staged) for_staged_nbrs_pv2<RIGID>(nlp, kf, s_operand, s_v2, rv, pair);
-    else for_fluid_nbrs<RIGID, true>(nlp, kf, P, V, rv, pair);
+    if (QUAD) sweep_quad<RIGID>(mem, nlp, kf, q, fa, pair, rv);
+    else if (staged) walk_staged<RIGID>(lds, nlp, kf, pair, rv);
+    else sweep_list<RIGID>(mem, nlp, kf, pair, rv);
     float wa[2] = {0.f, 0.f};
     float &rb = wa[0], &ab = wa[1];
     if (c.boundary_handle) {
@@ -628,8 +481,8 @@ __global__ __launch_bounds__(kBlock) void k_ii_rho_adv(Consts c, float dt, const
             float ex = di.x - cji * -g.x, ey = di.y - cji * -g.y, ez = di.z - cji * -g.z;
             ab += pj.w * dot3(ex, ey, ez, g.x, g.y, g.z);                              // compute_a_ii_boundary :322
         };
-        if (QUAD) for_nbrs_p_quad(nlbp, kb, q, wa, WP, wall);
-        else for_nbrs_p(nlbp, kb, WP, wall);
+        if (QUAD) sweep_quad<false>(SrcP{WP}, nlbp, kb, q, wa, wall);
+        else sweep_list<false>(SrcP{WP}, nlbp, kb, wall);
     }
     if (!owner) return;
     if (c.boundary_handle) {
@@ -661,17 +514,19 @@ __global__ __launch_bounds__(kBlock) void k_ii_dij(Consts c, float dt, const flo
     SPH_SWEEP_PROLOGUE_B(QUAD, track ? (int)blockIdx.x : xcd_block(blockIdx.x, gridDim.x))
     (void)kb; (void)nlbp;
     float *s_rho = StageF4S::second(s_operand, c.stage_cap);
+    const SrcAS mem{P, rho};
+    const StageF4S lds{s_operand, s_rho, P, rho};
     bool staged, all_zero = false;
     if (track) {
         const int was_zero = zero_dij[blk];
         // (a staged set of no particles sees no pressure: kStagedIdle)
-        const int verdict = stage_operands<kCheckWith, kStagedIdle>(StageF4S{s_operand, s_rho, P, rho}, StagePlan{stage_src, stage_cnt, blk});
+        const int verdict = stage_operands<kCheckWith, kStagedIdle>(lds, StagePlan{stage_src, stage_cnt, blk});
         all_zero = verdict == kStagedIdle;
         if (all_zero && was_zero) return;
         if (threadIdx.x == 0) zero_dij[blk] = all_zero ? 1 : 0;
         staged = verdict != kNotStaged;
     } else {
-        staged = STAGED && stage_operands(StageF4S{s_operand, s_rho, P, rho}, StagePlan{stage_src, stage_cnt, blk}) != kNotStaged;
+        staged = STAGED && stage_operands(lds, StagePlan{stage_src, stage_cnt, blk}) != kNotStaged;
     }
     float fa[3] = {0.f, 0.f, 0.f};
     float &sx = fa[0], &sy = fa[1], &sz = fa[2];
@@ -685,13 +540,21 @@ __global__ __launch_bounds__(kBlock) void k_ii_dij(Consts c, float dt, const flo
         sx += div_shared(a * g.x, den); sy += div_shared(a * g.y, den); sz += div_shared(a * g.z, den);   // :327
     };
     if (all_zero) {}                                         // (the sums would be +0 + (+-0 terms) = +0)
-    else if (QUAD) for_nbrs_ps_quad<RIGID>(nlp, kf, q, fa, P, rho, rv, pair);
-    else if (staged) for_staged_nbrs_ps2<RIGID>(nlp, kf, s_operand, s_rho, rv, pair);
-    else for_nbrs_ps<RIGID>(nlp, kf, P, rho, rv, pair);
+    else if (QUAD) sweep_quad<RIGID>(mem, nlp, kf, q, fa, pair, rv);
+    else if (staged) walk_staged<RIGID>(lds, nlp, kf, pair, rv);
+    else sweep_list<RIGID>(mem, nlp, kf, pair, rv);
     if (!owner) return;
     DIJ[i] = make_float4(sx * dt * dt, sy * dt * dt, sz * dt * dt, 0.f);   // :135
 }
 
+// the reader of the set k_ii_update_p stages by hand (its fill loop): positions + p, the source index and the three components of the third operand
+// (32 B per staged particle); the second operand is gathered from memory through the source index
+struct StageUpdateP {
+    const float4 *s_A; const uint32_t *s_src; const float *s_cx, *s_cy, *s_cz; const float4 *B;
+    using Op = OpABC; static constexpr bool kScaled = false;
+    __device__ __forceinline__ float4 pos(uint32_t e) const { return s_A[e]; }
+    __device__ __forceinline__ void rest(uint32_t e, Op &o) const { o.b = B[s_src[e]]; o.c = make_float4(s_cx[e], s_cy[e], s_cz[e], 0.f); }
+};
 // update_p (:137-157) + compute_residual partials (:110-121).   P = PBin = (pos, p_iter); writes PBout = (pos, new p_iter)
 template <bool RIGID, int SWEEP, bool RX = false>
 __global__ __launch_bounds__(kBlock) void k_ii_update_p(Consts c, float dt, const float4 *__restrict__ P, const float4 *__restrict__ DII,
@@ -711,6 +574,8 @@ __global__ __launch_bounds__(kBlock) void k_ii_update_p(Consts c, float dt, cons
     uint32_t *s_src = StageF4Src::second(s_operand, c.stage_cap);
     float *s_ex = reinterpret_cast<float *>(s_src + c.stage_cap), *s_ey = s_ex + c.stage_cap, *s_ez = s_ey + c.stage_cap;
     const int nst = STAGED ? stage_expand(stage_src, stage_cnt, blk, s_src) : -1;      // the list stays: DII is gathered through it
+    const SrcABC mem{P, DII, DIJ};
+    const StageUpdateP lds{s_operand, s_src, s_ex, s_ey, s_ez, DII};
     const bool staged = nst >= 0;
     if (staged) {
         for (int e = threadIdx.x; e < nst; e += kBlock) {
@@ -741,9 +606,9 @@ __global__ __launch_bounds__(kBlock) void k_ii_update_p(Consts c, float dt, cons
         float tz = a.z - dj.z * pj.w - (ej.z - jz);
         sum += c.m * dot3(tx, ty, tz, g.x, g.y, g.z);        // sum_factor :254
     };
-    if (QUAD) for_nbrs_3_quad<RIGID>(nlp, kf, q, fa, P, DII, DIJ, rv, pair);
-    else if (staged) for_staged_nbrs_3e<RIGID>(nlp, kf, s_operand, s_src, s_ex, s_ey, s_ez, DII, rv, pair);
-    else for_nbrs_3<RIGID>(nlp, kf, P, DII, DIJ, rv, pair);
+    if (QUAD) sweep_quad<RIGID>(mem, nlp, kf, q, fa, pair, rv);
+    else if (staged) walk_staged<RIGID>(lds, nlp, kf, pair, rv);
+    else sweep_list<RIGID>(mem, nlp, kf, pair, rv);
     float wa[1] = {0.f};
     float &bsum = wa[0];
     if (c.boundary_handle) {
@@ -753,8 +618,8 @@ __global__ __launch_bounds__(kBlock) void k_ii_update_p(Consts c, float dt, cons
             F3 g = K::grad_in(c, dx, dy, dz, r);
             bsum += dot3(a.x, a.y, a.z, g.x, g.y, g.z) * pj.w * c.rho0;   // sum_factor_boundary :240
         };
-        if (QUAD) for_nbrs_p_quad(nlbp, kb, q, wa, WP, wall);
-        else for_nbrs_p(nlbp, kb, WP, wall);
+        if (QUAD) sweep_quad<false>(SrcP{WP}, nlbp, kb, q, wa, wall);
+        else sweep_list<false>(SrcP{WP}, nlbp, kb, wall);
     }
     float val = 0.f;
     int flag = 0;

@@ -37,19 +37,15 @@ __device__ __forceinline__ float rx_g(const Consts &c, float dx, float dy, float
     return q <= 0.5f ? g1 : g2;
 }
 
-// Walk of a 16-bit list eight entries at a time WITHOUT tail masks: k_build_nl pads the last group of a list with the particle's own
-// local index (NlWriter::flush), and the particle itself contributes x_ij = 0, v_ij = 0: a term that is exactly 0 (g stays finite: r^2 is
-// floored in rx_g).  Eight independent pair bodies per trip in one basic block; tools/pair_body_relaxed.hip: 22.1 -> 19.1 us per sweep.
-template <class Pair8>
-__device__ __forceinline__ void rx_walk8(const uint32_t *__restrict__ base, int cnt, Pair8 pair8)
+// The staged relaxed sweeps take a 16-bit list eight entries at a time WITHOUT tail masks (nl16_stream in sph_kernels.h, called directly):
+// k_build_nl pads the last group of a list with the particle's own local index (NlWriter::flush), and the particle itself contributes
+// x_ij = 0, v_ij = 0: a term that is exactly 0 (g stays finite: r^2 is floored in rx_g).  Eight independent pair bodies per trip in one
+// basic block; tools/pair_body_relaxed.hip: 22.1 -> 19.1 us per sweep.
+template <class Src>
+__device__ __forceinline__ void rx_group8(const Src &s, const Nl16Group &g, typename Src::Op (&o)[8])
 {
-    if (cnt <= 0) return;
-    uint4 jn = nl_load(base);
-    for (int kk = 0; kk < cnt; kk += 8) {
-        const Nl16Group g = {{jn.x, jn.y, jn.z, jn.w}};
-        if (kk + 8 < cnt) jn = nl_load(base + (size_t)((kk >> 3) + 1) * 256);
-        pair8(g);
-    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) { o[2 * u] = nl_fluid(s, g.lo(u)); o[2 * u + 1] = nl_fluid(s, g.hi(u)); }
 }
 
 // W / kw and m s / (h r) of one pair from its difference vector: the two scalars D1 and D5 need (rx_g is the second alone)
@@ -92,7 +88,7 @@ __global__ __launch_bounds__(kBlock) void k_rx_wall_grad(Consts c, const float4 
         sq = __builtin_fmaf(tz, tz, __builtin_fmaf(ty, ty, __builtin_fmaf(tx, tx, sq)));
         ws = __builtin_fmaf(pj.w, k.w, ws);
     };
-    for_nbrs_p(nlbp, kb, WP, wall);
+    sweep_list<false>(SrcP{WP}, nlbp, kb, wall);
     if (live) { G[i] = make_float4(gx, gy, gz, ws * c.kw); Gsq[i] = sq; }
 }
 
@@ -119,6 +115,7 @@ __global__ __launch_bounds__(kBlock) void k_residual_rx(Consts c, const float4 *
     SPH_SWEEP_PROLOGUE_B(false, tile)
     (void)nlbp;
     float2 *s_v2 = StagePV<>::second(s_operand, c.stage_cap);
+    const StagePV<> lds{s_operand, s_v2, P, V, nullptr};            // the reader; the launches below say which bytes they check
     const StagePlan plan{st.src, st.cnt, blk, hd.pre};
     int verdict;                   // the per-particle check first, or (a `direct` tile) with the staging batch: resid_note_work in sph_kernels.h
     if (spread && !hd.direct) verdict = stage_operands<kCheckFirst, kStaged>(StagePV<>{s_operand, s_v2, P, V, lc.changed8}, plan);
@@ -136,14 +133,13 @@ __global__ __launch_bounds__(kBlock) void k_residual_rx(Consts c, const float4 *
         acc = __builtin_fmaf(g, dot, acc);                                        // :287 / :162
     };
     if (staged)
-        rx_walk8(nlp, kfx, [&](const Nl16Group &g) {
-            float4 a[8]; float2 b[8];
+        nl16_stream(nlp, kfx, [&](const Nl16Group &g, int) {
+            OpAB o[8];
+            rx_group8(lds, g, o);
 #pragma unroll
-            for (int u = 0; u < 4; ++u) { a[2 * u] = s_operand[g.lo(u)]; a[2 * u + 1] = s_operand[g.hi(u)]; b[2 * u] = s_v2[g.lo(u)]; b[2 * u + 1] = s_v2[g.hi(u)]; }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) pair(a[u], make_float4(a[u].w, b[u].x, b[u].y, 0.f), 0u);
+            for (int u = 0; u < 8; ++u) pair(o[u].a, o[u].b, 0u);
         });
-    else for_fluid_nbrs<false, true>(nlp, kfx, P, V, RigidView(), pair);        // a workgroup whose set did not fit: 32-bit global indices, masked tails
+    else sweep_list<false>(SrcAB{P, V}, nlp, kfx, pair);        // a workgroup whose set did not fit: 32-bit global indices, masked tails
     float val = 0.f, kr = 0.f;
     int flag = 0;
     if (live) {
@@ -197,14 +193,15 @@ __global__ __launch_bounds__(kBlock) void k_correct_rx(Consts c, const float4 *_
     (void)nlbp;
     const bool track = MODE == CORR_DENS && wave_dirty != nullptr;  // change propagation in the density loop (sph_kernels.h: stage_sources_flagged)
     const StagePlan plan{st.src, st.cnt, blk, hd.pre};
+    const StagePS<> lds{s_operand, P, krho};
     bool staged;
     if (track && !hd.direct) {
         // (a staged set of no particles: kStaged, the tile goes on -- see k_correct)
-        const int verdict = stage_operands<kCheckFirst, kStaged>(StagePS<>{s_operand, P, krho}, plan);
+        const int verdict = stage_operands<kCheckFirst, kStaged>(lds, plan);
         if (verdict == kStagedIdle) { corr_mark_idle(c, wave_dirty, changed8, blk, i, live, ghost); return; }
         staged = verdict == kStaged;
     } else {
-        staged = stage_operands(StagePS<>{s_operand, P, krho}, plan) != kNotStaged;
+        staged = stage_operands(lds, plan) != kNotStaged;
     }
     const float dt = ds->dt;
     const float rho_i = rho[ii];
@@ -222,19 +219,16 @@ __global__ __launch_bounds__(kBlock) void k_correct_rx(Consts c, const float4 *_
         const float s = ks * g;                                                   // :337 / :369 / :203 (m inside g)
         ax = __builtin_fmaf(s, dx, ax); ay = __builtin_fmaf(s, dy, ay); az = __builtin_fmaf(s, dz, az);
     };
-    struct OperandPS { float4 a; float s; };
     const float4 none = make_float4(0.f, 0.f, 0.f, 0.f);
     if (staged)
-        rx_walk8(nlp, kf, [&](const Nl16Group &g) {
-            float4 a[8];
+        nl16_stream(nlp, kf, [&](const Nl16Group &g, int) {
+            OpA o[8];
+            rx_group8(lds, g, o);
 #pragma unroll
-            for (int u = 0; u < 4; ++u) { a[2 * u] = s_operand[g.lo(u)]; a[2 * u + 1] = s_operand[g.hi(u)]; }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) pair(a[u], none, 0u);
+            for (int u = 0; u < 8; ++u) pair(o[u].a, none, 0u);
         });
     else        // a workgroup whose set did not fit: two global gathers per neighbour, masked tails
-        walk_list<OperandPS>(nlp, kf, [&](uint32_t j, OperandPS &o) { o.a = P[j]; o.s = krho[j]; },
-                             [&](const OperandPS &o, uint32_t j) { pair(make_float4(o.a.x, o.a.y, o.a.z, o.s), none, j); });
+        sweep_list<false>(SrcAS{P, krho}, nlp, kf, [&](const float4 a, const float s, const uint32_t j) { pair(make_float4(a.x, a.y, a.z, s), none, j); });
     float gx = 0.f, gy = 0.f, gz = 0.f;
     if (c.boundary_handle && kb > 0 && live) {                                    // :322 / :310 / :187,191
         const float4 gw = G[i];
@@ -271,7 +265,8 @@ __global__ __launch_bounds__(kBlock) void k_density_rx(Consts c, const float4 *_
     if (tile < 0) return;
     SPH_SWEEP_PROLOGUE_G(false, tile, true)
     (void)nlbp;
-    const bool staged = stage_operands(StageF4<>{s_operand, P}, StagePlan{stage_src, stage_cnt, blk}) != kNotStaged;
+    const StageF4<> lds{s_operand, P};
+    const bool staged = stage_operands(lds, StagePlan{stage_src, stage_cnt, blk}) != kNotStaged;
     float ws = 0.f, sx = 0.f, sy = 0.f, sz = 0.f, sq = 0.f;
     auto pair = [&](const float4 pj, bool valid) {
         const float dx = pi.x - pj.x, dy = pi.y - pj.y, dz = pi.z - pj.z;
@@ -281,22 +276,14 @@ __global__ __launch_bounds__(kBlock) void k_density_rx(Consts c, const float4 *_
         sx += rx; sy += ry; sz += rz;
         sq = __builtin_fmaf(rz, rz, __builtin_fmaf(ry, ry, __builtin_fmaf(rx, rx, sq)));     // :71
     };
-    if (staged) {
-        if (kf > 0) {
-            uint4 jn = nl_load(nlp);
-            for (int kk = 0; kk < kf; kk += 8) {
-                const Nl16Group g = {{jn.x, jn.y, jn.z, jn.w}};
-                if (kk + 8 < kf) jn = nl_load(nlp + (size_t)((kk >> 3) + 1) * 256);
-                float4 a[8];
+    if (staged)
+        nl16_stream(nlp, kf, [&](const Nl16Group &g, int kk) {
+            OpA o[8];
+            rx_group8(lds, g, o);
 #pragma unroll
-                for (int u = 0; u < 4; ++u) { a[2 * u] = s_operand[g.lo(u)]; a[2 * u + 1] = s_operand[g.hi(u)]; }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) pair(a[u], kk + u < kf);
-            }
-        }
-    } else {
-        for_fluid_nbrs<false, false>(nlp, kf, P, nullptr, RigidView(), [&](const float4 pj, const float4, const uint32_t) { pair(pj, true); });
-    }
+            for (int u = 0; u < 8; ++u) pair(o[u].a, kk + u < kf);
+        });
+    else sweep_list<false>(SrcA{P}, nlp, kf, [&](const float4 pj, const float4, const uint32_t) { pair(pj, true); });
     if (!live) return;
     float rho_i = __builtin_fmaf(c.kw * c.m, ws, 0.001f);                         // rho starts at 0.001, solver_base.py:44
     float den = (__builtin_fmaf(sz, sz, __builtin_fmaf(sy, sy, sx * sx))) + sq;   // dfsph_solver.py:47
@@ -331,7 +318,9 @@ __global__ __launch_bounds__(kBlock) void k_dfsph_ext_rx(Consts c, const float4 
     SPH_SWEEP_PROLOGUE_B(false, tile)
     (void)kb; (void)nlbp;
     uint32_t *s_src = StageF4Src::second(s_operand, c.stage_cap);      // (vel, rho) is gathered from memory through the source list
-    const bool staged = stage_operands(StageF4Src{{s_operand, P}, s_src}, StagePlan{stage_src, stage_cnt, blk}) != kNotStaged;
+    const StageF4Src lay{{s_operand, P}, s_src};
+    const StageF4Src::Gather lds = lay.gather(V);
+    const bool staged = stage_operands(lay, StagePlan{stage_src, stage_cnt, blk}) != kNotStaged;
     const float4 vi = V[ii];
     const float rho_i = vi.w;
     const float tk = c.tens_c * c.kw;
@@ -347,25 +336,14 @@ __global__ __launch_bounds__(kBlock) void k_dfsph_ext_rx(Consts c, const float4 
         const float sv = shear < 0.f ? mp * k.g : 0.f;                            // :184, :189 (m inside g)
         wx = __builtin_fmaf(sv, dx, wx); wy = __builtin_fmaf(sv, dy, wy); wz = __builtin_fmaf(sv, dz, wz);
     };
-    if (staged) {
-        if (kf > 0) {
-            uint4 jn = nl_load(nlp);
-            for (int kk = 0; kk < kf; kk += 8) {
-                const Nl16Group g = {{jn.x, jn.y, jn.z, jn.w}};
-                if (kk + 8 < kf) jn = nl_load(nlp + (size_t)((kk >> 3) + 1) * 256);
-                float4 a[8], b[8];
+    if (staged)
+        nl16_stream(nlp, kf, [&](const Nl16Group &g, int) {
+            OpAB o[8];
+            rx_group8(lds, g, o);
 #pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    a[2 * u] = s_operand[g.lo(u)]; a[2 * u + 1] = s_operand[g.hi(u)];
-                    b[2 * u] = V[s_src[g.lo(u)]]; b[2 * u + 1] = V[s_src[g.hi(u)]];
-                }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) pair(a[u], b[u]);
-            }
-        }
-    } else {
-        for_fluid_nbrs<false, true>(nlp, kf, P, V, RigidView(), [&](const float4 pj, const float4 vj, const uint32_t) { pair(pj, vj); });
-    }
+            for (int u = 0; u < 8; ++u) pair(o[u].a, o[u].b);
+        });
+    else sweep_list<false>(SrcAB{P, V}, nlp, kf, [&](const float4 pj, const float4 vj, const uint32_t) { pair(pj, vj); });
     float vn = -INFINITY;
     if (live) {
         const float dt = ds->dt;
@@ -429,13 +407,13 @@ __global__ __launch_bounds__(kBlock) void k_wcsph_density_rx(Consts c, const flo
     if (blockIdx.x == 0 && threadIdx.x == 0 && ds->moved != 0) { ds->moved = 0; if (count_build) ds->verlet_builds += 1; }
     SPH_SWEEP_PROLOGUE_M(false)
     float ws = 0.f;
-    for_fluid_nbrs<false, false>(nlp, kf, P, nullptr, RigidView(), [&](const float4 pj, const float4, const uint32_t) {
+    sweep_list<false>(SrcA{P}, nlp, kf, [&](const float4 pj, const float4, const uint32_t) {
         const RxWG k = rx_wg_clamped(c, pi.x - pj.x, pi.y - pj.y, pi.z - pj.z);
         ws += k.w;                                                             // solver_base.py:62 (m kw outside the sum)
     });
     float wb = 0.f, gx = 0.f, gy = 0.f, gz = 0.f;
     if (c.boundary_handle)
-        for_nbrs_p(nlbp, kb, WP, [&](const float4 pj) {
+        sweep_list<false>(SrcP{WP}, nlbp, kb, [&](const float4 pj) {
             const float dx = pi.x - pj.x, dy = pi.y - pj.y, dz = pi.z - pj.z;
             const RxWG k = rx_wg_clamped(c, dx, dy, dz);
             wb = __builtin_fmaf(pj.w, k.w, wb);                                // :70-71
@@ -470,7 +448,7 @@ __global__ __launch_bounds__(kBlock) void k_wcsph_force_rx(Consts c, float dt, c
     const float rho_i = pi.w, a_i = vi.w;
     const float tk = c.tens_c * c.kw;
     float px = 0.f, py = 0.f, pz = 0.f, wx = 0.f, wy = 0.f, wz = 0.f, tx = 0.f, ty = 0.f, tz = 0.f;
-    for_fluid_nbrs<false, true>(nlp, kf, P, V, RigidView(), [&](const float4 pj, const float4 vj, const uint32_t) {
+    sweep_list<false>(SrcAB{P, V}, nlp, kf, [&](const float4 pj, const float4 vj, const uint32_t) {
         const float dx = pi.x - pj.x, dy = pi.y - pj.y, dz = pi.z - pj.z;
         const RxWG k = rx_wg_clamped(c, dx, dy, dz);
         const float s = (a_i + vj.w) * k.g;                                    // wcsph_solver.py:116 (m inside g)

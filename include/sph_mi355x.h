@@ -392,6 +392,18 @@ int sph_selftest_wave(int device, int op, const double *in, double *out, size_t 
 int sph_selftest_stage(SphHandle *h, int layout, int check, int empty_idle, int use_pre, int not_staged, const uint32_t *runs, int nruns,
                        const float *A, const float *B, const float *S, const unsigned char *changed, size_t n_src, float *out, int *verdict);
 
+/* Self-test of the list walks of the sweeps (optional export): 256 particles walk the lists the caller supplies through one walk and one operand
+ * source.  walk: 0 the pipelined 32-bit walk over memory, 1 its four-lanes-per-particle form, 2 the staged 32-bit walk, 3 the staged 16-bit walk.
+ * src, walks 0 / 1: 0 (A) without entry word, 1 (A), 2 (A, B), 3 (A, S), 4 (A, B, C); walks 2 / 3, staged from the run (run_first, run_n <= 512) of
+ * the source arrays: the layouts 0-6 of sph_selftest_stage, 7 A staged + B gathered through the kept index, 8 A and C.xyz staged + B gathered.
+ * lists: 256 x 28 entries (24 + the spare group, all of them valid: indices into the source arrays for walks 0 / 1, into the staged run for
+ * 2 / 3; with rigid != 0 an entry may carry bit 31 and then indexes RP); counts: 256 values in 0 .. 24.  rigid needs walk != 3 and not src 0 of
+ * the memory walks.  A, B, C: n_src float4, S: n_src floats, RP: n_rig float4.  out: 4 words per thread (walk 1: 1024 threads, four per
+ * particle; else 256): body calls, the hash h = h * 0x9E3779B1 + word over every call's operand bits and rigid flag, and (walk 1) the bits of two
+ * sums that start at 0.001 and 0 and take a.x and a.y of every call in list order. */
+int sph_selftest_walk(SphHandle *h, int walk, int src, int rigid, const uint32_t *lists, const int *counts, uint32_t run_first, uint32_t run_n,
+                      const float *A, const float *B, const float *C, const float *S, size_t n_src, const float *RP, size_t n_rig, uint32_t *out);
+
 #ifdef __cplusplus
 }
 #endif

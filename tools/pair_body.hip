@@ -1,7 +1,7 @@
 // pair_body.hip -- how fast can gfx950 run the DFSPH pair body itself?  The residual sweep's per-neighbour arithmetic (difference,
 // correctly rounded norm, grad_w_scaled with its Newton divisions, velocity dot product) in a loop with its LDS operand reads and
 // nothing else: no index stream, no staging, no tails.  Compares, at the sweep's occupancy (4 workgroups of 256 per CU):
-//   seq    four bodies per group, each in its own EXEC-masked region (the shape of for_staged_nbrs_pv2)
+//   seq    four bodies per group, each in its own EXEC-masked region (the shape of walk_staged)
 //   ilp    four bodies per group in one basic block (walk_staged_pv)
 //   x, c   operands gathered from LDS at scattered (x) or wave-uniform, conflict-free (c) addresses
 // prints pairs per second and the equivalent microseconds for `PAIRS` pairs (default 38e6 = one sweep over dfsph_1m late in the collapse).

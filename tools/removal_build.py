@@ -22,10 +22,10 @@ from cfd_taichi_amd import build as hip_build  # noqa: E402
 K, R = "sph_kernels.h", "sph_relaxed_kernels.h"
 PATCHES = {
     # exact k_residual (sph_kernels.h): the fluid pair loop / the wall loop removed
-    "nofluid": [(K, "    else if (staged && (RIGID ? stage_lists16(st.cnt, blk) : c.nl16 != 0)) for_staged16_nbrs_pv2(nlp, skip ? 0 : kf, s_operand, s_v2, pair_scaled);",
-                 "    else if (staged && (RIGID ? stage_lists16(st.cnt, blk) : c.nl16 != 0)) for_staged16_nbrs_pv2(nlp, 0, s_operand, s_v2, pair_scaled);")],
-    "nowall": [(K, "    else for_nbrs_p(nlbp, skip ? 0 : kb, WP, wall);\n    float val = 0.f, kr = 0.f;", "    else for_nbrs_p(nlbp, 0, WP, wall);\n    float val = 0.f, kr = 0.f;")],
-    "nowall_correct": [(K, "    else for_nbrs_p(nlbp, kb, WP, wall);\n    if (track) {\n        const bool changed", "    else for_nbrs_p(nlbp, 0, WP, wall);\n    if (track) {\n        const bool changed")],
+    "nofluid": [(K, "    else if (staged && (RIGID ? stage_lists16(st.cnt, blk) : c.nl16 != 0)) walk_list16(lds, nlp, skip ? 0 : kf, pair_scaled);",
+                 "    else if (staged && (RIGID ? stage_lists16(st.cnt, blk) : c.nl16 != 0)) walk_list16(lds, nlp, 0, pair_scaled);")],
+    "nowall": [(K, "    else sweep_list<false>(SrcP{WP}, nlbp, skip ? 0 : kb, wall);\n    float val = 0.f, kr = 0.f;", "    else sweep_list<false>(SrcP{WP}, nlbp, 0, wall);\n    float val = 0.f, kr = 0.f;")],
+    "nowall_correct": [(K, "    else sweep_list<false>(SrcP{WP}, nlbp, kb, wall);\n    if (track) {\n        const bool changed", "    else sweep_list<false>(SrcP{WP}, nlbp, 0, wall);\n    if (track) {\n        const bool changed")],
     # CORRECT variants (speed only): the solver-loop sweeps take their tiles in chunks of C consecutive tiles dealt round-robin over the XCDs
     # instead of one contiguous eighth per XCD (1.5-2 % faster at 16-64, 19 % more HBM traffic: not in the product)
     "xcd_chunk16": [(K, "    return xcd_block(orig, nwg);\n}\n\n// Edge / interior split of a sweep",
@@ -50,7 +50,7 @@ PATCHES = {
                     (K, "    const float4 vi = V[ii];\n    float fa[1] = {0.f};\n    float &acc = fa[0];\n    const int nq = RIGID", "    const unsigned long long t_staged = wall_clock64();\n    const float4 vi = V[ii];\n    float fa[1] = {0.f};\n    float &acc = fa[0];\n    const int nq = RIGID"),
                     (K, "    float wa[1] = {0.f};\n    float &accb = wa[0];\n    auto wall = [&](const float4 pj) {\n        float dx = pi.x - pj.x, dy = pi.y - pj.y, dz = pi.z - pj.z;\n        float r = K::norm3(dx, dy, dz);\n        F3 g = K::grad_in(c, dx, dy, dz, r);\n        accb += pj.w * dot3(vi.x, vi.y, vi.z, g.x, g.y, g.z);",
                      "    __builtin_amdgcn_s_barrier();\n    const unsigned long long t_pairs = wall_clock64();\n    float wa[1] = {0.f};\n    float &accb = wa[0];\n    auto wall = [&](const float4 pj) {\n        float dx = pi.x - pj.x, dy = pi.y - pj.y, dz = pi.z - pj.z;\n        float r = K::norm3(dx, dy, dz);\n        F3 g = K::grad_in(c, dx, dy, dz, r);\n        accb += pj.w * dot3(vi.x, vi.y, vi.z, g.x, g.y, g.z);"),
-                    (K, "    else for_nbrs_p(nlbp, skip ? 0 : kb, WP, wall);\n    float val = 0.f, kr = 0.f;", "    else for_nbrs_p(nlbp, skip ? 0 : kb, WP, wall);\n    __builtin_amdgcn_s_barrier();\n    const unsigned long long t_walls = wall_clock64();\n    float val = 0.f, kr = 0.f;"),
+                    (K, "    else sweep_list<false>(SrcP{WP}, nlbp, skip ? 0 : kb, wall);\n    float val = 0.f, kr = 0.f;", "    else sweep_list<false>(SrcP{WP}, nlbp, skip ? 0 : kb, wall);\n    __builtin_amdgcn_s_barrier();\n    const unsigned long long t_walls = wall_clock64();\n    float val = 0.f, kr = 0.f;"),
                     ("sph_mi355x.hip", "int sph_tune_time(SphHandle *h, int which, unsigned lds_bytes, int reps, double *avg_us)\n{",
                      "int sph_debug_timeline(unsigned long long *out, int n)\n{\n    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(sph::g_timeline), sizeof(unsigned long long) * 4 * (size_t)n);\n}\nint sph_tune_time(SphHandle *h, int which, unsigned lds_bytes, int reps, double *avg_us)\n{")],
     # the same stamps in the relaxed divergence-residual sweep (tools/wg_timeline.py with SPH_ARITH=relaxed reads the same array)
@@ -111,7 +111,7 @@ PATCHES = {
                       (K, "    const float4 vi = V[ii];\n    float fa[1] = {0.f};\n    float &acc = fa[0];\n    const int nq = RIGID", "    __builtin_amdgcn_s_barrier();\n    const unsigned long long t_st = wall_clock64();\n    const float4 vi = V[ii];\n    float fa[1] = {0.f};\n    float &acc = fa[0];\n    const int nq = RIGID"),
                       (K, "    float wa[1] = {0.f};\n    float &accb = wa[0];\n    auto wall = [&](const float4 pj) {\n        float dx = pi.x - pj.x, dy = pi.y - pj.y, dz = pi.z - pj.z;\n        float r = K::norm3(dx, dy, dz);\n        F3 g = K::grad_in(c, dx, dy, dz, r);\n        accb += pj.w * dot3(vi.x, vi.y, vi.z, g.x, g.y, g.z);",
                        "    __builtin_amdgcn_s_barrier();\n    const unsigned long long t_pr = wall_clock64();\n    float wa[1] = {0.f};\n    float &accb = wa[0];\n    auto wall = [&](const float4 pj) {\n        float dx = pi.x - pj.x, dy = pi.y - pj.y, dz = pi.z - pj.z;\n        float r = K::norm3(dx, dy, dz);\n        F3 g = K::grad_in(c, dx, dy, dz, r);\n        accb += pj.w * dot3(vi.x, vi.y, vi.z, g.x, g.y, g.z);"),
-                      (K, "    else for_nbrs_p(nlbp, skip ? 0 : kb, WP, wall);\n    float val = 0.f, kr = 0.f;", "    else for_nbrs_p(nlbp, skip ? 0 : kb, WP, wall);\n    __builtin_amdgcn_s_barrier();\n    const unsigned long long t_w = wall_clock64();\n    float val = 0.f, kr = 0.f;"),
+                      (K, "    else sweep_list<false>(SrcP{WP}, nlbp, skip ? 0 : kb, wall);\n    float val = 0.f, kr = 0.f;", "    else sweep_list<false>(SrcP{WP}, nlbp, skip ? 0 : kb, wall);\n    __builtin_amdgcn_s_barrier();\n    const unsigned long long t_w = wall_clock64();\n    float val = 0.f, kr = 0.f;"),
                       ("sph_mi355x.hip", "int sph_tune_time(SphHandle *h, int which, unsigned lds_bytes, int reps, double *avg_us)\n{",
                        "int sph_debug_flow_stamp(SphHandle *h) { return h->flow_stamp; }\nint sph_debug_dens_capture(int stamp6, int stamp7)\n{\n    int v[2] = {stamp6, stamp7};\n    return (int)hipMemcpyToSymbol(HIP_SYMBOL(sph::g_tl_capture), v, sizeof(v));\n}\n"
                        "int sph_debug_dens_timeline(int which, unsigned long long *out, int n)\n{\n    return which == 6 ? (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(sph::g_tl6), sizeof(unsigned long long) * 4 * (size_t)n)\n                      : (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(sph::g_tl7), sizeof(unsigned long long) * 4 * (size_t)n);\n}\n"
@@ -145,16 +145,17 @@ PATCHES = {
     "bnl_notable": [(K, "    const bool table = nruns <= kRunCap;                                       // wave-uniform",
                      "    const bool table = false;")],
     # relaxed k_residual_rx: pair loop removed / staging gathers removed / whole staging removed (the decomposition in DESIGN.md section 4b)
-    "rx_nofluid": [(R, "        rx_walk8(nlp, kfx, [&](const Nl16Group &g) {\n            float4 a[8]; float2 b[8];",
-                    "        rx_walk8(nlp, 0, [&](const Nl16Group &g) {\n            float4 a[8]; float2 b[8];")],
+    "rx_nofluid": [(R, "        nl16_stream(nlp, kfx, [&](const Nl16Group &g, int) {\n            OpAB o[8];",
+                    "        nl16_stream(nlp, 0, [&](const Nl16Group &g, int) {\n            OpAB o[8];")],
     # relaxed sweeps with HALF the index stream (every second 16-byte group of a list is not loaded, the walk reuses the group before it: same
-    # LDS gathers, same arithmetic, half the list bytes from HBM): what a 2x more compact list encoding could buy at most
-    "rx_halflist": [(R, "        if (kk + 8 < cnt) jn = nl_load(base + (size_t)((kk >> 3) + 1) * 256);\n        pair8(g);",
-                     "        if (kk + 8 < cnt && ((kk >> 3) & 1)) jn = nl_load(base + (size_t)((kk >> 3) + 1) * 256);\n        pair8(g);")],
+    # LDS gathers, same arithmetic, half the list bytes from HBM): what a 2x more compact list encoding could buy at most.
+    # The stream (nl16_stream) is shared with walk_list16: the exact sweeps of this build skip groups too -- time it under SPH_ARITH=relaxed only
+    "rx_halflist": [(K, "        if (kk + 8 < cnt) jn = nl_load(base + (size_t)((kk >> 3) + 1) * 256);\n        group(g, kk);",
+                     "        if (kk + 8 < cnt && ((kk >> 3) & 1)) jn = nl_load(base + (size_t)((kk >> 3) + 1) * 256);\n        group(g, kk);")],
     "rx_nostage": [(R, "    else verdict = stage_operands<kCheckWith, kStaged>(StagePV<>{s_operand, s_v2, P, V, (spread && hd.direct) ? lc.changed8 : nullptr}, plan);\n",
                     "    else verdict = kStaged;\n"),
-                   (R, "        rx_walk8(nlp, kfx, [&](const Nl16Group &g) {\n            float4 a[8]; float2 b[8];",
-                    "        rx_walk8(nlp, 0, [&](const Nl16Group &g) {\n            float4 a[8]; float2 b[8];")],
+                   (R, "        nl16_stream(nlp, kfx, [&](const Nl16Group &g, int) {\n            OpAB o[8];",
+                    "        nl16_stream(nlp, 0, [&](const Nl16Group &g, int) {\n            OpAB o[8];")],
 }
 
 
