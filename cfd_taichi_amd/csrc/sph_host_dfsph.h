@@ -224,7 +224,7 @@ int stage_density(SphHandle *h)
         h->pcur ^= 1; h->vcur ^= 1;   // P = (pos, rho), V = (vel, p/rho^2)
     }
     HIP_TRY(h, hipGetLastError());
-    if (h->slab && dfsph && rigid_coupled(h)) {      // fluid densities by original id < Nr (the viscosity quirk), summed over the owners
+    if (h->slab && rigid_coupled(h)) {      // fluid densities by original id < Nr (the viscosity quirk of every solver's sweeps), summed over the owners
         ProfScope ps(h, K_RIGID);
         HIP_TRY(h, hipMemsetAsync(h->red_dev, 0, sizeof(double) * (size_t)h->Nr, s));
         hipLaunchKernelGGL(k_collect_by_id, grid_for(c.n), dim3(kBlock), 0, s, c.n, h->id[h->icur], (const float4 *)nullptr, h->rho, h->Nr, h->red_dev);
@@ -246,13 +246,14 @@ int stage_density(SphHandle *h)
     return SPH_OK;
 }
 
-// force of the fluid on the body for wcsph (S = pressure) / pcisph / iisph (PB.w = press_iter / p_iter); see k_rigid_force_p
+// force of the fluid on the body for wcsph (S = pressure) / pcisph / iisph (PB.w = press_iter / p_iter); see k_rigid_force_p.  On a slab handle
+// the rank that owns a sample's cell column sums its force, and PB must have been refreshed on the ghosts (slab_refresh_w_and_pressure_finalize)
 template <int MODE>
 void launch_rigid_force_p(SphHandle *h, const float4 *P, const float4 *PB, int gate)
 {
     ProfScope ps(h, K_RIGID);
     hipLaunchKernelGGL(k_rigid_force_p<MODE>, grid_for(h->Nr), dim3(kBlock), 0, h->stream, h->c, h->Nr, h->RPs, h->rid, P, h->rnl, h->rcnt, h->rho,
-                       h->aux, PB, h->ds, h->rforce, gate);
+                       h->aux, PB, h->ds, h->rforce, gate, h->slab ? 1 : 0, h->geom.x_lo, h->geom.x_hi);
 }
 
 int step_wcsph_once(SphHandle *h)

@@ -330,6 +330,40 @@ int pcisph_precompute(SphHandle *h)
             }
             counts[i] = (float)cnt;
         }
+        if (rigid_binned(h)) {
+            // get_neighbour_count's rigid entries (ParticleSystem.py:436-444) as k_build_nl<true> counts them: for every sample binned in one of the
+            // particle's 27 cells, the test against fluid_particles.pos[the sample's LOCAL index] -- the initial lattice here
+            const float *rp = h->rigid_pos_host.data();
+            std::vector<int> rstart((size_t)c.C + 1, 0), rcid((size_t)h->Nr), rorder((size_t)h->Nr);
+            for (int j = 0; j < h->Nr; ++j) {
+                const int x = (int)floorf(rp[3 * (size_t)j] / c.h), y = (int)floorf(rp[3 * (size_t)j + 1] / c.h), z = (int)floorf(rp[3 * (size_t)j + 2] / c.h);
+                rcid[j] = (x < 0 || y < 0 || z < 0 || x >= c.gx || y >= c.gy || z >= c.gz) ? -1 : x + y * c.sy + z * c.sz;
+                if (rcid[j] >= 0) rstart[(size_t)rcid[j] + 1]++;
+            }
+            for (int k = 0; k < c.C; ++k) rstart[(size_t)k + 1] += rstart[k];
+            std::vector<int> rfill(rstart.begin(), rstart.end() - 1);
+            for (int j = 0; j < h->Nr; ++j) if (rcid[j] >= 0) rorder[rfill[rcid[j]]++] = j;
+            for (int i = 0; i < N; ++i) {
+                if (cid[i] < 0) continue;
+                const int x = cid[i] % c.gx, z = (cid[i] / c.gx) % c.gz, y = cid[i] / (c.gx * c.gz);
+                int cnt = 0;
+                for (int dx = -1; dx <= 1; ++dx)
+                    for (int dy = -1; dy <= 1; ++dy)
+                        for (int dz = -1; dz <= 1; ++dz) {
+                            const int xx = x + dx, yy = y + dy, zz = z + dz;
+                            if (xx < 0 || yy < 0 || zz < 0 || xx >= c.gx || yy >= c.gy || zz >= c.gz) continue;
+                            const int nb = xx + yy * c.sy + zz * c.sz;
+                            for (int e = rstart[nb]; e < rstart[(size_t)nb + 1]; ++e) {
+                                const int jl = rorder[e];
+                                if (jl == i || jl >= N) continue;
+                                const float ax = pos[3 * (size_t)i] - pos[3 * (size_t)jl], ay = pos[3 * (size_t)i + 1] - pos[3 * (size_t)jl + 1],
+                                            az = pos[3 * (size_t)i + 2] - pos[3 * (size_t)jl + 2];
+                                if (!((ax * ax + ay * ay) + az * az > c.r2_cut)) ++cnt;
+                            }
+                        }
+                counts[i] += (float)cnt;
+            }
+        }
     } else {
     if ((rc = stage_sort_and_lists(h))) return rc;
     if ((rc = read_scalars(h))) return rc;

@@ -376,7 +376,9 @@ int sph_create(const SphConfig *cfg, SphHandle **out)
 int sph_create_rigid(const SphConfig *cfg, const SphRigid *rigid, SphHandle **out)
 {
     if (!cfg || !rigid || !out) return fail(nullptr, SPH_E_INVALID, "null argument");
-    if (cfg->slab_count > 1 && (cfg->solver != SPH_SOLVER_DFSPH || cfg->slab_ghost_layers == 1))
+    // slab handles: a coupled body on every solver but pbf.  wcsph / pcisph / iisph run on one ghost column (a sample of an edge column finds its fluid
+    // neighbours there, with the owners' values: k_rigid_force_p); dfsph's body needs the two-column protocol, whose inner ghosts run the sweeps themselves
+    if (cfg->slab_count > 1 && cfg->solver == SPH_SOLVER_DFSPH && cfg->slab_ghost_layers == 1)
         return fail(nullptr, SPH_E_INVALID, "a rigid body on slab handles needs dfsph with two ghost columns (the body's fluid neighbours must be resident on the rank that owns its column)");
     if (rigid->n_particles <= 0 || !rigid->points) return fail(nullptr, SPH_E_INVALID, "rigid body has no sample points");
     if (cfg->solver == SPH_SOLVER_PBF) return fail(nullptr, SPH_E_INVALID, "pbf has no rigid coupling (pbf_solver.py has no material branches)");

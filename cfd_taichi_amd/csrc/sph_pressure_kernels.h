@@ -673,22 +673,30 @@ __global__ __launch_bounds__(kBlock) void k_ii_integrate(Consts c, float dt, con
 //   RF_IISPH  iisph_solver.py:166-167   force += f * m,     f = V_j rho_0 / rho_i^2 * gradW * p_iter_i       (PB.w)
 enum { RF_WCSPH = 0, RF_PCISPH = 2, RF_IISPH = 3 };
 
+// Slab handles (slab != 0): the body is replicated on every rank and a sample's force is summed WHOLE by the rank that owns the sample's cell column
+// [col_lo, col_hi), as in k_rigid_force; a sample of an edge column walks the fluid of the one ghost column, so every operand must be the owner's
+// value on a ghost.  pcisph / iisph: rho[] came with the density refresh (k_unpack_field mode 3) and PB.w with the refresh that follows the sweep
+// that wrote it.  wcsph: a ghost receives (pos, rho) and (vel, p / rho^2) and neither rho[] nor pressure[]; P = (pos, rho) here, and the pressure is
+// taken from that rho with the device function k_density stored it with -- the same f32 on an owned particle, so a slab handle takes this form for all
 template <int MODE>
 __global__ __launch_bounds__(kBlock) void k_rigid_force_p(Consts c, int nr, const float4 *__restrict__ RP, const int *__restrict__ rid,
                                                           const float4 *__restrict__ P, const uint32_t *__restrict__ rnl,
                                                           const int *__restrict__ rcnt, const float *__restrict__ rho,
                                                           const float *__restrict__ S, const float4 *__restrict__ PB,
-                                                          const DevScalars *__restrict__ ds, float *__restrict__ force, int gate)
+                                                          const DevScalars *__restrict__ ds, float *__restrict__ force, int gate,
+                                                          int slab = 0, int col_lo = 0, int col_hi = 0)
 {
     if (gate_closed(ds, gate)) return;
     int r = blockIdx.x * kBlock + threadIdx.x;
     if (r >= nr) return;
     const float4 pr = RP[r];
+    if (slab) { const int cx = (int)floorf(pr.x / c.hcell); if (cx < col_lo || cx >= col_hi) return; }
     float fx = 0.f, fy = 0.f, fz = 0.f;
     struct Op { float4 p; float rho, s; };
     walk_list<Op>(rnl + nl_index(r, 0, c.kpitch), rcnt[r], [&](uint32_t i, Op &o) {      // k_build_rnl (sph_rigid_kernels.h)
-        o.p = P[i]; o.rho = rho[i];
-        o.s = MODE == RF_WCSPH ? S[i] : PB[i].w;
+        o.p = P[i];
+        if (MODE == RF_WCSPH && slab) { o.rho = o.p.w; o.s = tait_pressure(o.rho); }
+        else { o.rho = rho[i]; o.s = MODE == RF_WCSPH ? S[i] : PB[i].w; }
     }, [&](const Op &o, uint32_t) {
         const float4 pi = o.p;
         float ddx = pi.x - pr.x, ddy = pi.y - pr.y, ddz = pi.z - pr.z;

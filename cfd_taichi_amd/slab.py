@@ -224,8 +224,8 @@ class SlabSimulation:
         cfg = nat.config_from_dict(config, solver_name=solver_name, device=device, slab_rank=rank, slab_count=world,
                                    slab_capacity=slab_capacity, slab_rebalance_every=rebalance_every, **native_opts)
         self.solver = {v: k for k, v in nat.SOLVER_IDS.items()}[cfg.solver]
-        # a rigid body (config["solid"]): replicated on every rank (dfsph, two ghost columns); the sums that keep the copies identical go through the
-        # transport's reduce buffer, 4 doubles per rigid sample
+        # a rigid body (config["solid"]): replicated on every rank (dfsph with two ghost columns; wcsph, pcisph and iisph with their one); the sums
+        # that keep the copies identical go through the transport's reduce buffer, 4 doubles per rigid sample
         rigid = None
         if config.get("solid"):
             from . import mesh
@@ -242,8 +242,11 @@ class SlabSimulation:
         self.n_fluid = self.sim.n_fluid
 
     def step(self, nsteps=1):
+        """nsteps solver steps; returns the last one's SphStepStats (None for wcsph).  With an active rigid body every solver step is followed
+        by one body step (main.py:165-171 with iter_cnt 1).  Forces accumulated over several solver steps before one body step (iter_cnt > 1)
+        are not supported on slabs: a sample's force is summed by the rank that owns its cell column, and ownership can change between steps."""
         try:
-            if self.solver == "wcsph":
+            if self.solver == "wcsph" and not self.rigid_active:
                 self.sim.step_wcsph(nsteps)
                 return None
             st = None

@@ -45,6 +45,7 @@ int32_t sph_abi_version(void);
 #define SPH_SOLVER_PCISPH 2   /* pcisph_solver.py */
 #define SPH_SOLVER_IISPH 3    /* iisph_solver.py */
 #define SPH_SOLVER_PBF 4      /* pbf_solver.py (stale in the reference: read as csrc/sph_pbf_kernels.h states; single GPU, no rigid body) */
+/* (wcsph, dfsph, pcisph and iisph run on slab handles, with or without a coupled rigid body: sph_create_rigid) */
 
 /* config/X.json of the reference, flattened (utils.py:3-11 reads it,
  * ParticleSystem.py:31-103 and solver_base.py:7-39 consume it).  Doubles carry the Python
@@ -209,8 +210,11 @@ typedef struct SphHandle SphHandle;
 int sph_create(const SphConfig *cfg, SphHandle **out);
 /* the same with a rigid body: replaces ParticleSystem(config) with a `solid` block + rigid_solver(ps, config)   main.py:69-71.
  * All four solvers couple to the body (wcsph_solver.py:118-127, dfsph_solver.py:204-212, pcisph_solver.py:200-211, iisph_solver.py:159-168).
- * On slab handles: dfsph with two ghost columns only; the body is replicated on every rank, three small all-reduces per step (the fluid positions and
- * densities the reference's index quirks read, the per-sample forces) keep every rank's copy bit-identical to the one-GPU run. */
+ * On slab handles: a two-way coupled body (active, fs_couple 1) on dfsph with two ghost columns and on wcsph / pcisph / iisph with their one; the body
+ * is replicated on every rank, three small all-reduces per step (the fluid positions and densities the reference's index quirks read, the per-sample
+ * forces, each summed whole by the rank that owns the sample's cell column) keep every rank's copy bit-identical to the one-GPU run.  One sph_rigid_step
+ * after every solver step: forces gathered over several solver steps are not supported there (column ownership changes between steps).  SPH_E_INVALID
+ * on slab handles: dfsph with slab_ghost_layers = 1, a one-way body (active, fs_couple 0), pbf. */
 int sph_create_rigid(const SphConfig *cfg, const SphRigid *rigid, SphHandle **out);
 /* replaces rigid_solver.step()   rigid_solver.py:216-232 */
 int sph_rigid_step(SphHandle *h);
