@@ -170,6 +170,14 @@ int check_overflow(SphHandle *h)
 }
 
 PbfConsts pbf_consts(const SphHandle *h);
+// one PBF sweep: quad or plain grid, exact or relaxed pair body
+#define SPH_LAUNCH_PBF(KERNEL, QUAD, RX, G, GQ, STREAM, ...)                                                                 \
+    do {                                                                                                                      \
+        if (QUAD) { if (RX) hipLaunchKernelGGL((KERNEL<true, true>), GQ, dim3(kBlock), 0, STREAM, __VA_ARGS__);               \
+                    else hipLaunchKernelGGL((KERNEL<true, false>), GQ, dim3(kBlock), 0, STREAM, __VA_ARGS__); }               \
+        else { if (RX) hipLaunchKernelGGL((KERNEL<false, true>), G, dim3(kBlock), 0, STREAM, __VA_ARGS__);                    \
+               else hipLaunchKernelGGL((KERNEL<false, false>), G, dim3(kBlock), 0, STREAM, __VA_ARGS__); }                    \
+    } while (0)
 
 
 int stage_density(SphHandle *h)
@@ -182,12 +190,8 @@ int stage_density(SphHandle *h)
         // the lambda sweep alone: pbf_lambda (aux), the (pos, lambda) scratch and the P / V roles stay as they are.
         ProfScope ps(h, K_B_LAMBDA);
         const PbfConsts k = pbf_consts(h);
-        if (sweep_mode(h) == SWEEP_QUAD)
-            hipLaunchKernelGGL(k_pbf_lambda<true>, dim3((unsigned)std::max(1, (c.n + 63) / 64)), dim3(kBlock), 0, s, c, k, h->P[h->pcur], h->WP, h->nl, h->nlb,
-                               h->cnt, h->rho, h->aux, h->P[1 - h->pcur], 1);
-        else
-            hipLaunchKernelGGL(k_pbf_lambda<false>, grid_for(c.n), dim3(kBlock), 0, s, c, k, h->P[h->pcur], h->WP, h->nl, h->nlb, h->cnt, h->rho, h->aux,
-                               h->P[1 - h->pcur], 1);
+        SPH_LAUNCH_PBF(k_pbf_lambda, sweep_mode(h) == SWEEP_QUAD, relaxed_pbf(h), grid_for(c.n), dim3((unsigned)std::max(1, (c.n + 63) / 64)), s, c, k,
+                       h->P[h->pcur], h->WP, h->nl, h->nlb, h->cnt, h->rho, h->aux, h->P[1 - h->pcur], 1);      // the step's own instantiation
         HIP_TRY(h, hipGetLastError());
         h->density_valid = true;
         return SPH_OK;

@@ -20,6 +20,16 @@ PbfConsts pbf_consts(const SphHandle *h)
         k.lo[a] = (float)h->cfg.box_min[a] + (float)r;
         k.hi[a] = (float)h->cfg.box_max[a] - (float)r;
     }
+    {   // the RX pair bodies (sph_pbf_kernels.h): every constant factor of a sum, folded in f64
+        const double hd = 4 * r, md = 1000 * (r * r * r) * 8, kpd = 315.0 / (64 * pi * hd * hd * hd), qc = 0.3, tc = 1.0 - qc * qc;
+        const double kgd = -45.0 / (pi * (hd * hd) * (hd * hd)), wr = 1.0 / (tc * tc * tc);      // wr = kpoly / w_corr
+        k.rx_rh2 = (float)(1.0 / (hd * hd));
+        k.rx_mk = (float)(md * kpd);
+        k.rx_kg = (float)kgd;
+        k.rx_kg_rho0 = (float)(kgd / 1000.0);
+        k.rx_sc = (float)(-1e-7 * (wr * wr) * (wr * wr));
+        k.rx_ck = (float)(9e-6 * kpd);
+    }
     return k;
 }
 
@@ -32,22 +42,20 @@ int step_pbf_once(SphHandle *h)
     const Consts &c = h->c;
     const PbfConsts k = pbf_consts(h);
     const bool quad = sweep_mode(h) == SWEEP_QUAD;          // four lanes per particle in all three sweeps (small scenes)
-    const dim3 g = grid_for(c.n), b(kBlock), gq((unsigned)std::max(1, (c.n + 63) / 64));
+    const bool rx = relaxed_pbf(h);                         // the tolerance-grade pair bodies (SphConfig.arith)
+    const dim3 g = grid_for(c.n), gq((unsigned)std::max(1, (c.n + 63) / 64));
     hipStream_t s = h->stream;
     {
         ProfScope ps(h, K_B_LAMBDA);                          // compute_all_lambda :32-52
-        if (quad) hipLaunchKernelGGL(k_pbf_lambda<true>, gq, b, 0, s, c, k, h->P[h->pcur], h->WP, h->nl, h->nlb, h->cnt, h->rho, h->aux, h->P[1 - h->pcur], 0);
-        else hipLaunchKernelGGL(k_pbf_lambda<false>, g, b, 0, s, c, k, h->P[h->pcur], h->WP, h->nl, h->nlb, h->cnt, h->rho, h->aux, h->P[1 - h->pcur], 0);
+        SPH_LAUNCH_PBF(k_pbf_lambda, quad, rx, g, gq, s, c, k, h->P[h->pcur], h->WP, h->nl, h->nlb, h->cnt, h->rho, h->aux, h->P[1 - h->pcur], 0);
     }
     {
         ProfScope ps(h, K_B_DELTA);                           // compute_all_delta_pos :55-64, the prediction :26-29, update_all_pos phase 1 :66-84
-        if (quad) hipLaunchKernelGGL(k_pbf_delta<true>, gq, b, 0, s, c, k, h->dt_wcsph, h->P[1 - h->pcur], h->V[h->vcur], h->WP, h->nl, h->nlb, h->cnt, h->X[0], h->X[1], h->X[2]);
-        else hipLaunchKernelGGL(k_pbf_delta<false>, g, b, 0, s, c, k, h->dt_wcsph, h->P[1 - h->pcur], h->V[h->vcur], h->WP, h->nl, h->nlb, h->cnt, h->X[0], h->X[1], h->X[2]);
+        SPH_LAUNCH_PBF(k_pbf_delta, quad, rx, g, gq, s, c, k, h->dt_wcsph, h->P[1 - h->pcur], h->V[h->vcur], h->WP, h->nl, h->nlb, h->cnt, h->X[0], h->X[1], h->X[2]);
     }
     {
         ProfScope ps(h, K_B_XSPH);                            // update_all_pos phases 2-3 :86-98
-        if (quad) hipLaunchKernelGGL(k_pbf_xsph<true>, gq, b, 0, s, c, k, h->P[h->pcur], h->X[1], h->X[2], h->cell_start, h->P[1 - h->pcur], h->V[1 - h->vcur]);
-        else hipLaunchKernelGGL(k_pbf_xsph<false>, g, b, 0, s, c, k, h->P[h->pcur], h->X[1], h->X[2], h->cell_start, h->P[1 - h->pcur], h->V[1 - h->vcur]);
+        SPH_LAUNCH_PBF(k_pbf_xsph, quad, rx, g, gq, s, c, k, h->P[h->pcur], h->X[1], h->X[2], h->cell_start, h->P[1 - h->pcur], h->V[1 - h->vcur]);
     }
     h->pcur ^= 1; h->vcur ^= 1;
     HIP_TRY(h, hipGetLastError());

@@ -80,6 +80,9 @@ inline bool relaxed_pressure(const SphHandle *h)
     return h->relaxed && (h->cfg.solver == SPH_SOLVER_PCISPH || h->cfg.solver == SPH_SOLVER_IISPH) && !rigid_coupled(h) &&
            (h->staged || !(!h->slab && h->opt_quad && h->c.n <= h->quad_below));
 }
+// pbf under the relaxed arithmetic: the RX pair bodies of sph_pbf_kernels.h in all three sweeps, quad and plain (slab handles and handles with a body
+// refuse pbf)
+inline bool relaxed_pbf(const SphHandle *h) { return h->relaxed && h->cfg.solver == SPH_SOLVER_PBF; }
 
 // init_rigid_particles_data (ParticleSystem.py:249-291) on the host, from the sample positions `rpos` (3 floats each): sample volumes (summed over
 // the rigid cell list when the body is binned; an unbinned body has no neighbours, so its volumes are zero, its centroid 0 / 0 and its inverse inertia

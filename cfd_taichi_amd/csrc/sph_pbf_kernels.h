@@ -13,6 +13,18 @@
 //   k_pbf_lambda   rho (poly6), constrain, constrain_derivative, lambda           :32-52, 108-140   (the reference: five walks)
 //   k_pbf_delta    delta_pos; externel_force_predict_pos; update_all_pos phase 1   :26-29, 55-64, 66-84
 //   k_pbf_xsph     v_i = sum_j (vel_j - vel_i) W(|x_i - x_j|) on the NEW positions through the cell lists of the step's start; vel += c v   :86-98
+//
+// RX (SphConfig.arith = SPH_ARITH_RELAXED, relaxed_pbf() in sph_host_rigid.h): the tolerance-grade pair bodies.  Same pairs, lists, cell walk and
+// buffers; only the pair arithmetic changes.  r2 = fma(z,z, fma(y,y, fma(x,x, 1e-30))); poly6 is a polynomial in r2 -- tp = max(1 - r2 / h^2, 0),
+// W = kpoly tp^3, no root, no divide; the spiky gradient is one scalar times x_ij -- rinv = v_rsq_f32(r2), r = r2 rinv, ts = max(1 - r / h, 0),
+// grad W = K ts^2 rinv x_ij with K = -45 / (pi h^4), no q > 0 gate (a coincident pair has x_ij = 0 and a finite scalar through the floor on r2).
+// Every constant factor of a sum is taken out of it and applied once per particle (PbfConsts.rx_*, folded in f64 on the host): the sweeps add
+// tp^3, ts^2 rinv x_ij and (ts^2 rinv)^2 r2, and s_corr = -k (W / w_corr)^4 is rx_sc tp^12.  k_pbf_xsph decides membership by r2 <= r2_cut
+// (Consts: the f32 image of r <= h) and never takes a root.  What stays exact: the per-particle epilogues that set the discrete outcomes --
+// the constraint and its max, lambda's `con == 0` branch and divide, the prediction, vel = (pp - pos) / dt, the clamp planes, vel += c v.  The wall
+// walk of k_pbf_delta is kept (the regrouping lambda_i G_i + T_i through k_pbf_lambda was not built).  tests/test_pbf_relaxed_gpu.py holds the RX
+// instantiations to 4 x the f32 oracle's own error against the f64 oracle; RX = false is the exact code as it was before the argument
+// existed (same registers: profiles/r09/pbf_relaxed/kernel_resources.txt; same bits: tests/test_pbf_gpu.py).
 #pragma once
 #include "sph_kernels.h"
 
@@ -26,7 +38,29 @@ struct PbfConsts {
     float c_visc;     // c                                      :92
     float eps;        // epsilon                                :17
     float lo[3], hi[3];   // clamp walls at particle_radius     :74-81
+    // the RX pair bodies (folded in f64, pbf_consts)
+    float rx_rh2;         // 1 / h^2
+    float rx_mk;          // m kpoly: rho = 0.001 + rx_mk sum tp^3
+    float rx_kg;          // -45 / (pi h^4): k_pbf_delta's sums, divided by rho0 once as in the exact epilogue
+    float rx_kg_rho0;     // -45 / (pi h^4 rho0): the sums of k_pbf_lambda
+    float rx_sc;          // -k (kpoly / w_corr)^4: s_corr = rx_sc tp^12
+    float rx_ck;          // c kpoly: vel += rx_ck sum (vel_j - vel_i) tp^3
 };
+
+// the RX pair: squared distance with its floor, the poly6 base tp and the spiky scalar s = ts^2 / r (see the header)
+struct PbfPairRx { float r2, tp, s; };
+__device__ __forceinline__ float pbf_r2_rx(float dx, float dy, float dz) { return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, __builtin_fmaf(dx, dx, 1e-30f))); }
+__device__ __forceinline__ float pbf_tp_rx(const PbfConsts &k, float r2) { return __builtin_fmaxf(__builtin_fmaf(-r2, k.rx_rh2, 1.0f), 0.0f); }
+__device__ __forceinline__ PbfPairRx pbf_pair_rx(const Consts &c, const PbfConsts &k, float dx, float dy, float dz)
+{
+    PbfPairRx o;
+    o.r2 = pbf_r2_rx(dx, dy, dz);
+    const float rinv = __builtin_amdgcn_rsqf(o.r2), r = o.r2 * rinv;
+    o.tp = pbf_tp_rx(k, o.r2);
+    const float ts = __builtin_fmaxf(__builtin_fmaf(-r, c.rh, 1.0f), 0.0f);
+    o.s = (ts * ts) * rinv;
+    return o;
+}
 
 __device__ __forceinline__ float pow3f(float a) { return a * (a * a); }
 __device__ __forceinline__ float poly_w(const Consts &c, const PbfConsts &k, float r)       // solver_base.py:123-129
@@ -50,17 +84,24 @@ __device__ __forceinline__ F3 spiky_grad(const Consts &c, const PbfConsts &k, fl
 
 // rho, constrain, constrain_derivative, lambda.  Pout = (pos, lambda) for the gather of k_pbf_delta.
 // QUAD (both list sweeps): four lanes per particle, small scenes (walk_list_quad, sph_kernels.h)
-template <bool QUAD>
+template <bool QUAD, bool RX = false>
 __global__ __launch_bounds__(kBlock) void k_pbf_lambda(Consts c, PbfConsts k, const float4 *__restrict__ P, const float4 *__restrict__ WP,
                                                        const uint32_t *__restrict__ nl, const uint32_t *__restrict__ nlb,
                                                        const int *__restrict__ cnt, float *__restrict__ rho_out, float *__restrict__ lambda_out,
                                                        float4 *__restrict__ Pout, int rho_only)
 {
     SPH_SWEEP_PROLOGUE_M(QUAD)
-    float fa[5] = {0.001f, 0.f, 0.f, 0.f, 0.f};                    // rho starts at 0.001, solver_base.py:44
+    float fa[5] = {RX ? 0.f : 0.001f, 0.f, 0.f, 0.f, 0.f};        // rho starts at 0.001, solver_base.py:44 (RX: added in the epilogue)
     float &rho = fa[0], &cx = fa[1], &cy = fa[2], &cz = fa[3], &sum = fa[4];
     auto pair = [&](const float4 pj) {
         const float dx = pi.x - pj.x, dy = pi.y - pj.y, dz = pi.z - pj.z;
+        if constexpr (RX) {
+            const PbfPairRx p = pbf_pair_rx(c, k, dx, dy, dz);
+            rho = __builtin_fmaf(p.tp * p.tp, p.tp, rho);
+            cx = __builtin_fmaf(p.s, dx, cx); cy = __builtin_fmaf(p.s, dy, cy); cz = __builtin_fmaf(p.s, dz, cz);
+            sum = __builtin_fmaf(p.s * p.s, p.r2, sum);
+            return;
+        }
         const float r = norm3(dx, dy, dz);
         rho += c.m * poly_w(c, k, r);                              // :169-170
         const F3 g = spiky_grad(c, k, dx, dy, dz, r);
@@ -74,6 +115,13 @@ __global__ __launch_bounds__(kBlock) void k_pbf_lambda(Consts c, PbfConsts k, co
     float &rb = wa[0], &bx = wa[1], &by = wa[2], &bz = wa[3], &sb = wa[4];
     auto wall = [&](const float4 pj) {
         const float dx = pi.x - pj.x, dy = pi.y - pj.y, dz = pi.z - pj.z;
+        if constexpr (RX) {
+            const PbfPairRx p = pbf_pair_rx(c, k, dx, dy, dz);
+            rb = __builtin_fmaf(pj.w * (p.tp * p.tp), p.tp, rb);
+            bx = __builtin_fmaf(p.s, dx, bx); by = __builtin_fmaf(p.s, dy, by); bz = __builtin_fmaf(p.s, dz, bz);
+            sb = __builtin_fmaf(p.s * p.s, p.r2, sb);
+            return;
+        }
         const float r = norm3(dx, dy, dz);
         rb += pj.w * poly_w(c, k, r);                              // :173-176
         const F3 g = spiky_grad(c, k, dx, dy, dz, r);
@@ -84,6 +132,11 @@ __global__ __launch_bounds__(kBlock) void k_pbf_lambda(Consts c, PbfConsts k, co
     if (QUAD) sweep_quad<false>(SrcP{WP}, nlbp, kb, q, wa, wall);
     else sweep_list<false>(SrcP{WP}, nlbp, kb, wall);
     if (!owner) return;
+    if constexpr (RX) {                                            // the constant factors of the sums, once
+        rho = __builtin_fmaf(k.rx_mk, rho, 0.001f); rb *= k.kpoly;
+        cx *= k.rx_kg_rho0; cy *= k.rx_kg_rho0; cz *= k.rx_kg_rho0; bx *= k.rx_kg_rho0; by *= k.rx_kg_rho0; bz *= k.rx_kg_rho0;
+        sum *= k.rx_kg_rho0 * k.rx_kg_rho0; sb *= k.rx_kg_rho0 * k.rx_kg_rho0;
+    }
     const float rho_i = c.boundary_handle ? rho + rb * c.rho0 : rho;
     if (rho_only) { rho_out[i] = rho_i; return; }                  // compute_all_rho alone (solver_base.py:36-50 with :166-174): pbf_lambda keeps its values
     const float con = rmax(rho_i / c.rho0 - 1.0f, 0.0f);          // :127-128
@@ -98,7 +151,7 @@ __global__ __launch_bounds__(kBlock) void k_pbf_lambda(Consts c, PbfConsts k, co
 }
 
 // delta_pos, the prediction and phase 1 of update_all_pos.  PL = (pos, lambda); writes Pn = new position, Vn = phase-1 velocity.
-template <bool QUAD>
+template <bool QUAD, bool RX = false>
 __global__ __launch_bounds__(kBlock) void k_pbf_delta(Consts c, PbfConsts k, float dt, const float4 *__restrict__ PL, const float4 *__restrict__ V,
                                                       const float4 *__restrict__ WP, const uint32_t *__restrict__ nl,
                                                       const uint32_t *__restrict__ nlb, const int *__restrict__ cnt,
@@ -111,6 +164,13 @@ __global__ __launch_bounds__(kBlock) void k_pbf_delta(Consts c, PbfConsts k, flo
     float &ax = fa[0], &ay = fa[1], &az = fa[2];
     auto pair = [&](const float4 pj) {
         const float dx = pi.x - pj.x, dy = pi.y - pj.y, dz = pi.z - pj.z;
+        if constexpr (RX) {
+            const PbfPairRx p = pbf_pair_rx(c, k, dx, dy, dz);
+            float t12 = (p.tp * p.tp) * p.tp; t12 *= t12; t12 *= t12;
+            const float f = __builtin_fmaf(k.rx_sc, t12, li + pj.w) * p.s;
+            ax = __builtin_fmaf(f, dx, ax); ay = __builtin_fmaf(f, dy, ay); az = __builtin_fmaf(f, dz, az);
+            return;
+        }
         const float r = norm3(dx, dy, dz);
         float sc = poly_w(c, k, r) / k.w_corr;                     // :148
         sc *= sc; sc *= sc; sc *= k.neg_k;                         // :149-151
@@ -124,6 +184,13 @@ __global__ __launch_bounds__(kBlock) void k_pbf_delta(Consts c, PbfConsts k, flo
     float &bx = wa[0], &by = wa[1], &bz = wa[2];
     auto wall = [&](const float4 pj) {
         const float dx = pi.x - pj.x, dy = pi.y - pj.y, dz = pi.z - pj.z;
+        if constexpr (RX) {
+            const PbfPairRx p = pbf_pair_rx(c, k, dx, dy, dz);
+            float t12 = (p.tp * p.tp) * p.tp; t12 *= t12; t12 *= t12;
+            const float f = __builtin_fmaf(k.rx_sc, t12, li) * p.s;
+            bx = __builtin_fmaf(f, dx, bx); by = __builtin_fmaf(f, dy, by); bz = __builtin_fmaf(f, dz, bz);
+            return;
+        }
         const float r = norm3(dx, dy, dz);
         float sc = poly_w(c, k, r) / k.w_corr;
         sc *= sc; sc *= sc; sc *= k.neg_k;
@@ -134,6 +201,7 @@ __global__ __launch_bounds__(kBlock) void k_pbf_delta(Consts c, PbfConsts k, flo
     if (QUAD) sweep_quad<false>(SrcP{WP}, nlbp, kb, q, wa, wall);
     else sweep_list<false>(SrcP{WP}, nlbp, kb, wall);
     if (!owner) return;
+    if constexpr (RX) { ax *= k.rx_kg; ay *= k.rx_kg; az *= k.rx_kg; bx *= k.rx_kg; by *= k.rx_kg; bz *= k.rx_kg; }
     float dp[3];
     if (c.boundary_handle) { dp[0] = (ax + bx) / c.rho0; dp[1] = (ay + by) / c.rho0; dp[2] = (az + bz) / c.rho0; }   // :62
     else { dp[0] = ax / c.rho0; dp[1] = ay / c.rho0; dp[2] = az / c.rho0; }                                          // :64
@@ -162,7 +230,7 @@ __global__ __launch_bounds__(kBlock) void k_pbf_delta(Consts c, PbfConsts k, flo
 // QUAD (small scenes): the four lanes of a quad serve one particle; lane q evaluates candidate j0 + q of every batch of four of a cell and
 // all four add the four terms in candidate order (quad_bcast, sph_kernels.h) -- a candidate that is skipped contributes +0, which leaves
 // the running sums (never -0) unchanged: the same additions in the same order as the one-lane walk.
-template <bool QUAD>
+template <bool QUAD, bool RX = false>
 __global__ __launch_bounds__(kBlock) void k_pbf_xsph(Consts c, PbfConsts k, const float4 *__restrict__ Pold, const float4 *__restrict__ Pn,
                                                      const float4 *__restrict__ Vn, const int *__restrict__ cell_start,
                                                      float4 *__restrict__ Pfin, float4 *__restrict__ Vfin)
@@ -178,6 +246,14 @@ __global__ __launch_bounds__(kBlock) void k_pbf_xsph(Consts c, PbfConsts k, cons
     auto term = [&](int j, float &tx, float &ty, float &tz) {      // (vel_j - vel_i) W, or nothing
         const float4 pj = Pn[j];
         const float ex = pi.x - pj.x, ey = pi.y - pj.y, ez = pi.z - pj.z;
+        if constexpr (RX) {                                        // membership and W from r2 alone; rx_ck in the epilogue
+            const float r2 = pbf_r2_rx(ex, ey, ez);
+            if (r2 > c.r2_cut) return;
+            const float4 vj = Vn[j];
+            const float tp = pbf_tp_rx(k, r2), w = (tp * tp) * tp;
+            tx = (vj.x - vi.x) * w; ty = (vj.y - vi.y) * w; tz = (vj.z - vi.z) * w;
+            return;
+        }
         const float r = norm3(ex, ey, ez);
         if (r > c.h) return;                                       // :466
         const float4 vj = Vn[j];
@@ -205,6 +281,11 @@ __global__ __launch_bounds__(kBlock) void k_pbf_xsph(Consts c, PbfConsts k, cons
                     for (int j = a; j < b; ++j) {
                         if (j == i) continue;                      // :461
                         float tx = 0.f, ty = 0.f, tz = 0.f;
+                        if constexpr (RX) {
+                            term(j, tx, ty, tz);
+                            ax += tx; ay += ty; az += tz;
+                            continue;
+                        }
                         const float4 pj = Pn[j];
                         const float ex = pi.x - pj.x, ey = pi.y - pj.y, ez = pi.z - pj.z;
                         const float r = norm3(ex, ey, ez);
@@ -218,7 +299,8 @@ __global__ __launch_bounds__(kBlock) void k_pbf_xsph(Consts c, PbfConsts k, cons
             }
     if (q != 0) return;
     Pfin[i] = make_float4(pi.x, pi.y, pi.z, 0.f);
-    Vfin[i] = make_float4(vi.x + k.c_visc * ax, vi.y + k.c_visc * ay, vi.z + k.c_visc * az, 0.f);   // :92 / :94
+    const float cv = RX ? k.rx_ck : k.c_visc;
+    Vfin[i] = make_float4(vi.x + cv * ax, vi.y + cv * ay, vi.z + cv * az, 0.f);   // :92 / :94
 }
 
 }  // namespace sph

@@ -9,8 +9,8 @@ from .solver_base import solver_base
 class pbf_solver(solver_base):
     _kind = "pbf"
 
-    def __init__(self, particle_system, config):
-        super().__init__(particle_system, config)
+    def __init__(self, particle_system, config, arith=None):
+        super().__init__(particle_system, config, arith)
         self.epsilon = 1.0e-6                           # pbf_solver.py:17-21
         self.k = 1e-7
         self.c = 9e-6

@@ -70,8 +70,9 @@ typedef struct SphConfig {
     int32_t slab_capacity;      /* particles (owned + ghosts) a slab handle can hold; 0 = default (1.75 N / slab_count + 256k) */
     int32_t slab_rebalance_every; /* re-cut the slabs from the current particle distribution every M steps; 0 = static cuts */
     int32_t arith;              /* SPH_ARITH_EXACT (0, default): every f32 operation of the reference in its order, bit-equal to oracle/;
-                                   SPH_ARITH_RELAXED (1): the dfsph pair sweeps of large single-GPU scenes may use approximate
-                                   reciprocal square roots and FMA contraction (north_star's 1e-5 bar; see csrc/sph_relaxed_kernels.h).
+                                   SPH_ARITH_RELAXED (1): the pair sweeps of every fluid solver (wcsph, dfsph, pcisph, iisph, pbf) may use
+                                   approximate reciprocal square roots, FMA contraction and regrouped constant factors (north_star's 1e-5
+                                   bar; see csrc/sph_relaxed_kernels.h, KF<true> in csrc/sph_device.h and RX in csrc/sph_pbf_kernels.h).
                                    A permission: handles the relaxed sweeps do not cover run the exact ones. */
     int32_t slab_ghost_layers;  /* slab handles: ghost cell columns per side.  0 = default: 2 for dfsph (the correction sweeps run on the inner
                                    ghost column too, so a solver iteration needs ONE halo refresh -- the residual's -- instead of two), 1 for
@@ -182,7 +183,7 @@ typedef struct SphRigid {
 #define SPH_S_RIGID_INERTIA_INV 20 /* +0..8: ps.rigid_inertia_tensor_inv[None], row major */
 #define SPH_S_RIGID_ACTIVE 32      /* ps.active_rigid[None] as it stands (sph_rigid_set_active writes it); 0 on a handle without a body */
 #define SPH_S_VERLET_BUILDS 31    /* diagnostics: list builds so far on a Verlet handle (wcsph under the relaxed arithmetic: the lists carry a skin and are rebuilt on demand) */
-#define SPH_S_ARITH_RELAXED 30    /* diagnostics: 1 if this handle's dfsph sweeps run the tolerance-grade kernels (SphConfig.arith asked AND the handle qualifies) */
+#define SPH_S_ARITH_RELAXED 30    /* diagnostics: 1 if any pair sweep of this handle's solver runs the tolerance-grade kernels (SphConfig.arith asked AND the handle qualifies) */
 
 /* Solver attributes a caller of the reference edits on the solver object after constructing it -- sph_set_scalar / sph_get_scalar.
  * The defaults are the reference's.  The dfsph loop attributes (64-68) are read by Python-scope loops at every step (dfsph_solver.py:225, :400)
