@@ -184,15 +184,21 @@ def compare(e_cand, e_f32, margin=MARGIN):
 class Pool:
     """Per-particle errors of the candidate and of the f32 oracle, by (field, population), pooled over the seeds of one case."""
 
-    def __init__(self):
+    def __init__(self, fields=FIELDS):
+        """fields: ((name, field id), ...) of the solver under test (tests/pressure_states.py has its own)"""
         self.e = {}
+        self.fields = fields
 
-    def add(self, scene, seed, cand, r32, r64):
-        pops = populations(scene, seed, r64.nbr)
-        for name, _ in FIELDS:
+    def add(self, scene, seed, cand, r32, r64, pops=None, tag=None):
+        """pops: name -> mask, default populations(scene, seed, r64.nbr); tag: what keeps the pooled entries apart, default the seed"""
+        if pops is None:
+            pops = populations(scene, seed, r64.nbr)
+        if tag is None:
+            tag = "seed%d" % seed
+        for name, _ in self.fields:
             ec, er = errors(cand[name], r64[name]), errors(r32[name], r64[name])
             for pop, m in pops.items():
-                key = (name, pop if pop.startswith("mod8") else "%s/seed%d" % (pop, seed))      # mod-8 classes pooled, the rest per seed
+                key = (name, pop if pop.startswith("mod8") else "%s/%s" % (pop, tag))      # mod-8 classes pooled, the rest per seed
                 a, b = self.e.get(key, (np.empty(0), np.empty(0)))
                 self.e[key] = (np.concatenate([a, ec[m]]), np.concatenate([b, er[m]]))
 
@@ -219,7 +225,7 @@ class Pool:
             for stat in STATS:
                 w = max((r for r in mine if r[1].startswith("all/") and r[3] == stat), key=lambda r: r[6])
                 txt.append("%s %.2e/%.2e=%.2f" % (stat, w[4], w[5], w[6]))
-            for group in ("wall", "rest", "mod8"):
+            for group in dict.fromkeys("mod8" if r[1].startswith("mod8") else r[1].split("/")[0] for r in mine if not r[1].startswith("all/")):
                 sub = [r for r in mine if r[1].startswith(group)]
                 if sub:
                     w = max(sub, key=lambda r: r[6])

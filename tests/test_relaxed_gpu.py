@@ -11,7 +11,10 @@ different sum.  So:
   * after 100 steps: relaxed deviates from the canonical oracle no more than seeded legal executions of the oracle do
     (per-particle quantiles), and
   * on dfsph_1m from the step-55 state: 20 steps next to the exact kernels -- iteration counts, quantiles, health.
-The small scenes are put on the Morton curve (SPH_CELL_ORDER=morton: staged sweeps, 16-bit lists) -- the path relaxed covers."""
+The small scenes are put on the Morton curve (SPH_CELL_ORDER=morton: staged sweeps, 16-bit lists) -- the path relaxed covers.
+These are envelope tests of free-running steps.  The per-step bound -- every field within 4 x the f32 oracle's own error against the f64 oracle --
+is held by tests/test_relaxed_sweeps_gpu.py (dfsph), tests/test_pbf_relaxed_gpu.py (pbf), tests/test_relaxed_wcsph_sweeps_gpu.py (wcsph on Verlet
+lists) and tests/test_relaxed_pressure_sweeps_gpu.py (pcisph, iisph)."""
 import os
 
 import numpy as np
