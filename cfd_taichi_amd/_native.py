@@ -611,7 +611,13 @@ class Simulation:
         return res
 
 
+MATH_RECIP, MATH_DIV_SHARED, MATH_DIV_SHARED_TWO_STEP, MATH_DIV_SHARED_FLOORED = 7, 8, 9, 10    # sph_selftest_math ops (include/sph_mi355x.h)
+
+
 def selftest_math(op, a, b, device=0):
+    """out[i] = op(a[i], b[i]) in f32 on the device (see sph_selftest_math): 0 a/b, 1 sqrt(a), 2 W(a; h=b), 3-5 grad W, 6 sqrt_rn(a),
+    MATH_RECIP recip_prepare(b).y, MATH_DIV_SHARED / MATH_DIV_SHARED_TWO_STEP the sweeps' quotient a/b with one / two residual corrections,
+    MATH_DIV_SHARED_FLOORED the first of them with the divisor raised to kDenFloor."""
     lib = load()
     a = np.ascontiguousarray(a, dtype=np.float32)
     b = np.ascontiguousarray(b, dtype=np.float32)

@@ -135,14 +135,33 @@ struct F3 {
 // The sweeps need RN(a/b) (the oracle's IEEE divide), four times per pair.  hipcc's generic expansion is
 // ~10 instructions + VCC hazard nops each (v_div_scale x2, v_rcp, 5 fma, v_div_fmas, v_div_fixup).
 //
-// (1) Division by the constant h: with y = RN(1/h), q0 = RN(a*y), e = a - h*q0 (exact, fma),
-//     q = RN(q0 + e*y) is the correctly rounded quotient (Markstein's theorem; h's significand is not all
-//     ones).  3 instructions.
-// (2) Three numerators over one denominator: exactly the Newton-Raphson sequence LLVM emits for `/`
-//     (fma0..fma4 + fmas) minus the v_div_scale / v_div_fixup range handling, with the reciprocal refinement
-//     shared.  Operands here are h*r in [1e-7, 1e-2] and s*dx, far inside the range where v_div_scale is
-//     the identity, so the result is bit-identical to `/`.  3 + 3*5 instructions instead of 3*10 + nops.
-// tests/test_parity_gpu.py checks both against the oracle's plain divisions bit for bit.
+// Markstein's theorem: if y = RN(1/d) and q0 is within one ulp of a/d, then with the exact residual
+// e = a - d*q0 (one fma) the single correction q = RN(q0 + e*y) is RN(a/d), provided nothing overflows or
+// underflows on the way.  q0 = RN(a*y) is such a q0.  The exception is in the premise, not in the correction:
+// a Newton step y = y0 + y0*(1 - d*y0) from a y0 within one ulp reaches RN(1/d) for every significand of d
+// but the one that is all ones (there 1/d lies a hair above the midpoint of two floats and the step's last
+// rounding falls to the lower one).
+//
+// (1) Division by the constant h (div_by_h; div_const in sph_pressure_kernels.h): y = RN(1/h) is computed on
+//     the host, h's significand is not all ones.  3 instructions.
+// (2) Three numerators over one denominator (recip_prepare + div_shared): y is v_rcp_f32 refined by one
+//     Newton step, shared by the three quotients; each quotient is then the same 3 instructions.  Operands
+//     are h*r in [1e-7, 1e-2] (times 2^32 in the staged sweeps) or rho^2 ~ 1e6 under numerators s*dx, far
+//     inside the range where v_div_scale / v_div_fixup of the generic expansion are the identity.
+//     3 + 3*3 instructions instead of 3*10 + nops.
+//     That y = RN(1/d) holds for THIS hardware's v_rcp_f32 is not something the theorem can say:
+//     tests/test_division_gpu.py runs recip_prepare over all 2^23 significands in every binade the sweeps
+//     divide in and collects the significands E where y != RN(1/d), then runs every numerator significand
+//     against each d of E and against the all-ones d, and 64+ numerators (random ones and the neighbours of
+//     d*RN(k/d), and numerators whose quotient lies within 2^-21 ulp of a rounding boundary) against every
+//     other d.  Found on gfx950: E is empty in all eight binades -- from this v_rcp_f32 the Newton step reaches
+//     RN(1/d) even for the all-ones significand -- and every quotient of the test, the 2^24 numerators over each
+//     all-ones d included, equals the host's `/` bit for bit.
+//     The bit-equality of div_shared with `/` rests on the theorem plus that test.
+//     div_shared_two_step is the form used before: LLVM's Newton-Raphson sequence for `/` (fma0..fma4 + fmas)
+//     without its range handling, i.e. a second residual correction on top.  With y = RN(1/d) the second
+//     correction adds 0; it is kept for the self-test, which holds the two forms equal on the exceptional d.
+// tests/test_parity_gpu.py checks (1) and (2) against the oracle's plain divisions bit for bit.
 __device__ __forceinline__ float div_by_h(const Consts &c, float a)
 {
 #ifdef SPH_GENERIC_DIV
@@ -169,6 +188,12 @@ __device__ __forceinline__ float div_shared(float a, const Recip &r)
 #ifdef SPH_GENERIC_DIV
     return a / r.d;
 #endif
+    float q0 = a * r.y;
+    float r0 = __builtin_fmaf(-r.d, q0, a);
+    return __builtin_fmaf(r0, r.y, q0);
+}
+__device__ __forceinline__ float div_shared_two_step(float a, const Recip &r)     // self-test only (see above)
+{
     float q0 = a * r.y;
     float r0 = __builtin_fmaf(-r.d, q0, a);
     float q1 = __builtin_fmaf(r0, r.y, q0);

@@ -2670,6 +2670,10 @@ __global__ void k_selftest(Consts c, int op, const float *__restrict__ a, const 
     else if (op == 1) r = sqrtf(x);
     else if (op == 2) { c.h = y; r = cubic_w(c, x); }
     else if (op == 6) r = sqrt_rn(x);
+    else if (op == 7) r = recip_prepare(y).y;
+    else if (op == 8) r = div_shared(x, recip_prepare(y));
+    else if (op == 9) r = div_shared_two_step(x, recip_prepare(y));
+    else if (op == 10) r = div_shared(x, recip_prepare(__builtin_fmaxf(y, kDenFloor)));
     else {
         float dz = 0.25f * x;
         float rn = norm3(x, y, dz);

@@ -375,8 +375,11 @@ int sph_slab_set_state(SphHandle *h, const float *pos, const float *vel, const f
 
 /* device arithmetic self-test: out[i] = op(a[i], b[i]) evaluated on the GPU with the same
  * compiler flags as the sweeps (op 0: a/b, 1: sqrt(a), 2: cubic_kernel(a, h=b), 3..5:
- * component op-3 of cubic_kernel_derivative((a, b, 0.25*a), h=0.1)).  Used by tests to prove
- * the device's f32 divide/sqrt are correctly rounded like the oracle's. */
+ * component op-3 of cubic_kernel_derivative((a, b, 0.25*a), h=0.1), 6: the sweeps' own root sqrt_rn(a)).
+ * Used by tests to prove the device's f32 divide/sqrt are correctly rounded like the oracle's.
+ * The shared-denominator division of the sweeps (csrc/sph_device.h), piece by piece: 7: recip_prepare(b).y, the refined
+ * reciprocal; 8: div_shared(a, recip_prepare(b)), the quotient the sweeps form; 9: div_shared_two_step(a, recip_prepare(b)),
+ * the same with a second residual correction; 10: op 8 with the divisor raised to the sweeps' floor (kDenFloor) first. */
 /* tuning aid: mean microseconds of `reps` launches of one dfsph sweep (0 divergence residual, 1 divergence correction, 2 density
  * residual, 3 sort + list build) with `lds_bytes` of dynamic LDS per block; see tools/tune_sweeps.py */
 int sph_tune_time(SphHandle *h, int which, unsigned lds_bytes, int reps, double *avg_us);

@@ -36,13 +36,25 @@ __device__ __forceinline__ float sqrt_fma(float x)      // LLVM's correctly roun
     const float d = __builtin_fmaf(-s, s, x);
     return __builtin_fmaf(d, h, s);
 }
-template <bool FMASQRT>
+// norm3_scaled with the two compare-selects of its rounding step as integer arithmetic: r = yp, one ulp down if rp <= 0, one more if rm <= 0
+// (bits(t) - 1 is negative as an integer exactly when t <= 0: an exact fma residual is never -0).  x = 0 is NOT covered: rm is a NaN there.
+__device__ __forceinline__ float norm3_scaled_int(float xs, float ys, float zs)
+{
+    const float x = (xs * xs + ys * ys) + zs * zs;
+    const float y = __builtin_amdgcn_sqrtf(x);
+    const float ym = __uint_as_float(__float_as_uint(y) - 1u), yp = __uint_as_float(__float_as_uint(y) + 1u);
+    const float rm = __builtin_fmaf(-ym, y, x), rp = __builtin_fmaf(-yp, y, x);
+    return __int_as_float(__float_as_int(yp) + ((__float_as_int(rm) - 1) >> 31) + ((__float_as_int(rp) - 1) >> 31));
+}
+template <bool FMASQRT, bool INTROUND = false>
 __device__ __forceinline__ float norm3_scaled2(float xs, float ys, float zs)
 {
     const float x = (xs * xs + ys * ys) + zs * zs;
     if (FMASQRT) return sqrt_fma(x);
+    if (INTROUND) return norm3_scaled_int(xs, ys, zs);
     return norm3_scaled(xs, ys, zs);
 }
+template <bool BFI = false>
 __device__ __forceinline__ F3 grad_w_scaled2(const PairK &k, float dxs, float dys, float dzs, float rs)
 {
     float q0 = rs * k.rh_s;
@@ -53,6 +65,10 @@ __device__ __forceinline__ F3 grad_w_scaled2(const PairK &k, float dxs, float dy
     float t = 1.0f - q;
     float s2 = k.neg_kg6 * (t * t);
     float s = q <= 0.5f ? s1 : s2;
+    if (BFI) {                                                     // the same select through the sign of 0.5 - q (q finite): mask ? s2 : s1 as v_bfi_b32
+        const int mask = __float_as_int(0.5f - q) >> 31;
+        s = __int_as_float((mask & __float_as_int(s2)) | (~mask & __float_as_int(s1)));
+    }
     s = 1e-5f < q ? s : 0.0f;                                      // ONE select on the scalar instead of three on the components (a v_cndmask whose
                                                                    // mask does not come straight from the preceding v_cmp costs ~23 cycles)
     const Recip den = recip_prepare(__builtin_fmaxf(k.h * rs, 1e-30f));   // r = 0 (coincident particles): finite divisor, numerators are 0
@@ -81,8 +97,8 @@ __global__ __launch_bounds__(256) void k_body(Consts c, float *out, int groups, 
     auto eval = [&](const float4 pa, const float2 pb) -> float {
         const float dx = sx_i - pa.x, dy = sy_i - pa.y, dz = sz_i - pa.z;
         if (KIND >= 2) {
-            const float r = norm3_scaled2<(KIND == 4)>(dx, dy, dz);
-            const F3 g = grad_w_scaled2(pk, dx, dy, dz, r);
+            const float r = norm3_scaled2<(KIND == 4), (KIND >= 6)>(dx, dy, dz);
+            const F3 g = grad_w_scaled2<(KIND == 7)>(pk, dx, dy, dz, r);
             return pk.m * dot3(vi.x - pa.w, vi.y - pb.x, vi.z - pb.y, g.x, g.y, g.z);
         }
         const float r = norm3_scaled(dx, dy, dz);
@@ -95,7 +111,7 @@ __global__ __launch_bounds__(256) void k_body(Consts c, float *out, int groups, 
         for (int u = 0; u < 4; ++u) { j0 = (j0 * 5u + 7u + (SCATTER ? 0u : 0u)) % kCap; j[u] = SCATTER ? j0 : (uint32_t)((kk + u) % kCap); }
         const float4 a0 = s_A[j[0]], a1 = s_A[j[1]], a2 = s_A[j[2]], a3 = s_A[j[3]];
         const float2 b0 = s_B[j[0]], b1 = s_B[j[1]], b2 = s_B[j[2]], b3 = s_B[j[3]];
-        if (KIND != 1 && KIND != 5) {
+        if (KIND != 1 && KIND != 5) {      // 0, 2-4, 6, 7
             acc += eval(a0, b0);
             if (kk + 1 < cnt) acc += eval(a1, b1);
             if (kk + 2 < cnt) acc += eval(a2, b2);
@@ -163,10 +179,11 @@ int main(int argc, char **argv)
     const int groups = 250;
     const int nout = cus * 16 * 256;
     std::vector<float> ref(nout), got(nout);
-    const char *names[6] = {"seq (current body)", "one basic block", "seq, gate on the scalar + max(den)", "+ constants in VGPRs", "+ fma square root",
-                            "one basic block, masked terms (no selects), gate on the scalar"};
+    const char *names[8] = {"seq (current body)", "one basic block", "seq, gate on the scalar + max(den)", "+ constants in VGPRs", "+ fma square root",
+                            "one basic block, masked terms (no selects), gate on the scalar", "seq, root rounded with integer arithmetic (no selects)",
+                            "seq, integer root + q <= 0.5 select as v_bfi_b32"};
     printf("{\"pairs_per_sweep\": %.3g, \"results\": {\n", target);
-    for (int kind = 0; kind < 6; ++kind) {
+    for (int kind = 0; kind < 8; ++kind) {
         double rx, rc;
         switch (kind) {
         case 0: rx = run<0, true>(c, cus, dout, didx, groups); break;
@@ -174,7 +191,9 @@ int main(int argc, char **argv)
         case 2: rx = run<2, true>(c, cus, dout, didx, groups); break;
         case 3: rx = run<3, true>(c, cus, dout, didx, groups); break;
         case 4: rx = run<4, true>(c, cus, dout, didx, groups); break;
-        default: rx = run<5, true>(c, cus, dout, didx, groups); break;
+        case 5: rx = run<5, true>(c, cus, dout, didx, groups); break;
+        case 6: rx = run<6, true>(c, cus, dout, didx, groups); break;
+        default: rx = run<7, true>(c, cus, dout, didx, groups); break;
         }
         CHECK(hipMemcpy(got.data(), dout, (size_t)nout * 4, hipMemcpyDeviceToHost));
         if (kind == 0) ref = got;
@@ -186,10 +205,12 @@ int main(int argc, char **argv)
         case 2: rc = run<2, false>(c, cus, dout, didx, groups); break;
         case 3: rc = run<3, false>(c, cus, dout, didx, groups); break;
         case 4: rc = run<4, false>(c, cus, dout, didx, groups); break;
-        default: rc = run<5, false>(c, cus, dout, didx, groups); break;
+        case 5: rc = run<5, false>(c, cus, dout, didx, groups); break;
+        case 6: rc = run<6, false>(c, cus, dout, didx, groups); break;
+        default: rc = run<7, false>(c, cus, dout, didx, groups); break;
         }
         printf("  \"%s\": {\"scattered_us\": %.1f, \"conflict_free_us\": %.1f, \"outputs_differing_from_current\": %zu}%s\n", names[kind], target / rx * 1e6,
-               target / rc * 1e6, bad, kind == 5 ? "" : ",");
+               target / rc * 1e6, bad, kind == 7 ? "" : ",");
     }
     printf("}}\n");
     return 0;
