@@ -895,8 +895,20 @@ int sph_build_neighbors(SphHandle *h)
 {
     if (!h) return SPH_E_INVALID;
     HIP_TRY(h, hipSetDevice(h->device));
+    // pbf_lambda and delta_pos are per-particle fields of the solver that neither update_grid nor compute_all_rho touches; they live in device order
+    // (aux, X[0]), which the re-sort changes: carry them through in API order -- lambda in the staging buffer, delta_pos as 3 N floats in X[1]
+    // (phase 1's new positions: scratch between steps, 4 N floats).  Here and not in sph_compute_density: a sph_build_neighbors of its own re-sorts too
+    const bool keep = h->cfg.solver == SPH_SOLVER_PBF && h->simulate_cnt > 0;
+    if (keep) {
+        hipLaunchKernelGGL(k_unsort_scalar, grid_for(h->N), dim3(kBlock), 0, h->stream, h->N, h->aux, h->id[h->icur], h->staging);
+        hipLaunchKernelGGL(k_unsort_vec, grid_for(h->N), dim3(kBlock), 0, h->stream, h->N, h->X[0], h->id[h->icur], (float *)h->X[1]);
+    }
     int rc = stage_sort_and_lists(h);
     if (rc) return rc;
+    if (keep) {
+        hipLaunchKernelGGL(k_sort_in_scalar, grid_for(h->N), dim3(kBlock), 0, h->stream, h->N, h->staging, h->id[h->icur], h->aux);
+        hipLaunchKernelGGL(k_sort_in_vec, grid_for(h->N), dim3(kBlock), 0, h->stream, h->N, (const float *)h->X[1], h->id[h->icur], h->X[0]);
+    }
     if ((rc = read_scalars(h))) return rc;
     return check_overflow_all(h);
 }
@@ -906,21 +918,7 @@ int sph_compute_density(SphHandle *h)
     if (!h) return SPH_E_INVALID;
     HIP_TRY(h, hipSetDevice(h->device));
     int rc;
-    if (!h->nl_valid) {
-        // pbf_lambda and delta_pos are per-particle fields of the solver that compute_all_rho does not touch; they live in device order (aux,
-        // X[0]), which the re-sort below changes: carry them through in API order -- lambda in the staging buffer, delta_pos as 3 N floats in
-        // X[1] (phase 1's new positions: scratch between steps, 4 N floats)
-        const bool keep = h->cfg.solver == SPH_SOLVER_PBF && h->simulate_cnt > 0;
-        if (keep) {
-            hipLaunchKernelGGL(k_unsort_scalar, grid_for(h->N), dim3(kBlock), 0, h->stream, h->N, h->aux, h->id[h->icur], h->staging);
-            hipLaunchKernelGGL(k_unsort_vec, grid_for(h->N), dim3(kBlock), 0, h->stream, h->N, h->X[0], h->id[h->icur], (float *)h->X[1]);
-        }
-        if ((rc = sph_build_neighbors(h))) return rc;
-        if (keep) {
-            hipLaunchKernelGGL(k_sort_in_scalar, grid_for(h->N), dim3(kBlock), 0, h->stream, h->N, h->staging, h->id[h->icur], h->aux);
-            hipLaunchKernelGGL(k_sort_in_vec, grid_for(h->N), dim3(kBlock), 0, h->stream, h->N, (const float *)h->X[1], h->id[h->icur], h->X[0]);
-        }
-    }
+    if (!h->nl_valid && (rc = sph_build_neighbors(h))) return rc;      // (carries pbf_lambda and delta_pos through its re-sort)
     if (h->density_valid) return SPH_OK;
     if ((rc = stage_density(h))) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -1189,8 +1187,9 @@ int sph_profile_get(SphHandle *h, int kid, double *total_ms, int64_t *launches)
 }
 
 // Tuning aid (not part of the reference's surface): mean duration in microseconds of `reps` back-to-back launches of one DFSPH sweep
-// on the handle's current state with `lds_bytes` of dynamic LDS, bracketed by one HIP event pair.  which: 0 = divergence residual
-// (idempotent), 1 = divergence correction (advances the velocities: use a throw-away handle), 2 = density residual, 3 = sort + list build.
+// on the handle's current state with `lds_bytes` of dynamic LDS, bracketed by one HIP event pair.  `which` and what each value leaves behind on
+// the handle: include/sph_mi355x.h (0, 2, 3 and any value outside 0 .. 7, which runs 3's sort + list build, change no trajectory; 1 and 4 .. 7 are
+// for throw-away handles).
 int sph_tune_time(SphHandle *h, int which, unsigned lds_bytes, int reps, double *avg_us)
 {
     if (!h || !avg_us || reps < 1) return SPH_E_INVALID;

@@ -255,7 +255,14 @@ int sph_step_iisph(SphHandle *h, int nsteps, SphStepStats *last);
 /* replaces pbf_solver.step() x nsteps     pbf_solver.py:176-187 (update_all_pos under the barrier-synchronised schedule, csrc/sph_pbf_kernels.h) */
 int sph_step_pbf(SphHandle *h, int nsteps);
 /* stages of the step, for parity tests against the oracle's stages:
- * ps.reset_grid()+update_grid() (+ neighbour-list build), solver.compute_all_rho(), dfsph compute_all_alpha() */
+ * ps.reset_grid()+update_grid() (+ neighbour-list build), solver.compute_all_rho(), dfsph compute_all_alpha().
+ * None of them changes a trajectory: called between two steps, any number of times and in any order, they leave positions, velocities, warm_start_k,
+ * delta_time, pbf_lambda / delta_pos and a body's state as they were, and the steps that follow are bit for bit those of a handle that never
+ * called them (tests/test_midrun_calls_gpu.py).  What they do change: sph_build_neighbors re-sorts the device arrays by cell, so the OTHER
+ * per-particle results of the last step (rho, alpha, pressure, acc, rho_adv, rho_derivative, vel_adv, press_iter, press_force, pos_predict, d_ii,
+ * a_ii, d_ij) are no longer valid for sph_download until they are computed again -- rho (dfsph: and alpha, wcsph: and pressure, which the fused
+ * sweep writes with it) by sph_compute_density / sph_compute_alpha, the rest by the next step; SPH_F_NBR_COUNT becomes that of the current
+ * positions.  sph_compute_density and sph_compute_alpha build the lists first if positions changed since the last build. */
 int sph_build_neighbors(SphHandle *h);
 int sph_compute_density(SphHandle *h);
 int sph_compute_alpha(SphHandle *h);
@@ -381,7 +388,13 @@ int sph_slab_set_state(SphHandle *h, const float *pos, const float *vel, const f
  * reciprocal; 8: div_shared(a, recip_prepare(b)), the quotient the sweeps form; 9: div_shared_two_step(a, recip_prepare(b)),
  * the same with a second residual correction; 10: op 8 with the divisor raised to the sweeps' floor (kDenFloor) first. */
 /* tuning aid: mean microseconds of `reps` launches of one dfsph sweep (0 divergence residual, 1 divergence correction, 2 density
- * residual, 3 sort + list build) with `lds_bytes` of dynamic LDS per block; see tools/tune_sweeps.py */
+ * residual, 3 sort + list build) with `lds_bytes` of dynamic LDS per block; see tools/tune_sweeps.py.
+ * What it changes on the handle: all of them first bring the lists and rho / alpha up to date, as sph_compute_alpha does.  0, 2 and 3 then write
+ * only what the next step recomputes before reading it (rho_derivative, rho_adv, the sorted order and the lists): the steps that follow are, bit for
+ * bit, those of a handle that was never timed (tests/test_midrun_calls_gpu.py draws them between steps).  1 applies the divergence correction `reps`
+ * times: it ADVANCES the velocities and warm_start_k; 4 .. 7 (a residual with its reduction, the reduction alone, residual + correction without and
+ * with the reduction) write the loop-control block and, 6 and 7, the velocities as well.  1 and 4 .. 7 are for throw-away handles.  Any other
+ * value of `which` is not refused: it times sort + list build, as 3 does. */
 int sph_tune_time(SphHandle *h, int which, unsigned lds_bytes, int reps, double *avg_us);
 int sph_selftest_math(int device, int op, const float *a, const float *b, float *out, size_t n);
 /* wave primitive self-test: out[i] = what lane i % 64 holds after one cross-lane primitive over the 64 values in[64*(i/64) ..]

@@ -210,6 +210,10 @@ class Oracle:
         """`solver.<attribute> = value`: which = the SPH_P_* numbers of include/sph_mi355x.h (64..76)."""
         assert self._lib.orc_set_scalar(self._h, int(which), float(value)) == 0
 
+    def param(self, which):
+        """`solver.<attribute>` as it stands: which = SPH_P_* (64..76)"""
+        return self._lib.orc_get_scalar(self._h, int(which))
+
     @property
     def particle_m(self):
         return self._lib.orc_get_scalar(self._h, 2)
