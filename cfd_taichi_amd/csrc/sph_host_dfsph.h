@@ -170,6 +170,9 @@ int check_overflow(SphHandle *h)
 }
 
 PbfConsts pbf_consts(const SphHandle *h);
+// relaxed pbf on a slab handle of a scene whose one-GPU handle walks quad-wide (sweep_mode: N <= quad_below, SPH_QUAD not 0): the one-lane sweeps
+// with the quad walk's additions (k_pbf_lambda / k_pbf_delta <false, true, true>), so that the sharded run gives the one-GPU handle's bits at every size
+inline bool pbf_qsum(const SphHandle *h) { return h->slab && relaxed_pbf(h) && !h->staged && h->opt_quad && h->N <= h->quad_below; }
 // one PBF sweep: quad or plain grid, exact or relaxed pair body
 #define SPH_LAUNCH_PBF(KERNEL, QUAD, RX, G, GQ, STREAM, ...)                                                                 \
     do {                                                                                                                      \
@@ -190,6 +193,9 @@ int stage_density(SphHandle *h)
         // the lambda sweep alone: pbf_lambda (aux), the (pos, lambda) scratch and the P / V roles stay as they are.
         ProfScope ps(h, K_B_LAMBDA);
         const PbfConsts k = pbf_consts(h);
+        if (pbf_qsum(h))
+            hipLaunchKernelGGL((k_pbf_lambda<false, true, true>), grid_for(c.n), dim3(kBlock), 0, s, c, k, h->P[h->pcur], h->WP, h->nl, h->nlb, h->cnt, h->rho, h->aux, h->P[1 - h->pcur], 1);
+        else
         SPH_LAUNCH_PBF(k_pbf_lambda, sweep_mode(h) == SWEEP_QUAD, relaxed_pbf(h), grid_for(c.n), dim3((unsigned)std::max(1, (c.n + 63) / 64)), s, c, k,
                        h->P[h->pcur], h->WP, h->nl, h->nlb, h->cnt, h->rho, h->aux, h->P[1 - h->pcur], 1);      // the step's own instantiation
         HIP_TRY(h, hipGetLastError());

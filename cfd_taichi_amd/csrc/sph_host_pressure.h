@@ -33,6 +33,13 @@ PbfConsts pbf_consts(const SphHandle *h)
     return k;
 }
 
+// Slab handles (one ghost column, in order on the handle's stream; slab_overlap is ignored, the sweeps are the plain ones): the ghosts carry empty
+// lists, so every value a neighbour reads of them comes from the owner, after the sweep that produced it --
+//   stage_sort_and_lists   re-cut (if due), particle exchange: migrants and this step's ghosts        1 group (2 on a re-cut step), 32 B per record
+//   k_pbf_lambda           then lambda of the ghosts = P[1 - pcur].w                                  1 group, 4 B per ghost
+//   k_pbf_delta            then the ghosts' new position and phase-1 velocity, X[1] / X[2], together  1 group, 24 B per ghost
+//   k_pbf_xsph             owned particles walk the cell lists of the step's start over the refreshed arrays; a ghost copies (k_pbf_xsph_slab)
+// No reduction inside the step.  The refresh after k_pbf_delta is complete before k_pbf_xsph starts because both are ordered on one stream.
 int step_pbf_once(SphHandle *h)
 {
     int rc;
@@ -43,24 +50,34 @@ int step_pbf_once(SphHandle *h)
     const PbfConsts k = pbf_consts(h);
     const bool quad = sweep_mode(h) == SWEEP_QUAD;          // four lanes per particle in all three sweeps (small scenes)
     const bool rx = relaxed_pbf(h);                         // the tolerance-grade pair bodies (SphConfig.arith)
-    const dim3 g = grid_for(c.n), gq((unsigned)std::max(1, (c.n + 63) / 64));
+    const bool qsum = pbf_qsum(h);                          // ... on a slab handle, summed as the one-GPU handle of this scene sums them
+    const dim3 g = grid_for(c.n), gq((unsigned)std::max(1, (c.n + 63) / 64));      // (c.n of after the sort: a slab's dead slots are gone)
     hipStream_t s = h->stream;
     {
         ProfScope ps(h, K_B_LAMBDA);                          // compute_all_lambda :32-52
-        SPH_LAUNCH_PBF(k_pbf_lambda, quad, rx, g, gq, s, c, k, h->P[h->pcur], h->WP, h->nl, h->nlb, h->cnt, h->rho, h->aux, h->P[1 - h->pcur], 0);
+        if (qsum) hipLaunchKernelGGL((k_pbf_lambda<false, true, true>), g, dim3(kBlock), 0, s, c, k, h->P[h->pcur], h->WP, h->nl, h->nlb, h->cnt, h->rho, h->aux, h->P[1 - h->pcur], 0);
+        else SPH_LAUNCH_PBF(k_pbf_lambda, quad, rx, g, gq, s, c, k, h->P[h->pcur], h->WP, h->nl, h->nlb, h->cnt, h->rho, h->aux, h->P[1 - h->pcur], 0);
     }
+    if (h->slab && (rc = slab_exchange_field(h, 0, h->P[1 - h->pcur], nullptr, nullptr))) return rc;      // lambda of the ghosts
     {
         ProfScope ps(h, K_B_DELTA);                           // compute_all_delta_pos :55-64, the prediction :26-29, update_all_pos phase 1 :66-84
-        SPH_LAUNCH_PBF(k_pbf_delta, quad, rx, g, gq, s, c, k, h->dt_wcsph, h->P[1 - h->pcur], h->V[h->vcur], h->WP, h->nl, h->nlb, h->cnt, h->X[0], h->X[1], h->X[2]);
+        if (qsum) hipLaunchKernelGGL((k_pbf_delta<false, true, true>), g, dim3(kBlock), 0, s, c, k, h->dt_wcsph, h->P[1 - h->pcur], h->V[h->vcur], h->WP, h->nl, h->nlb, h->cnt, h->X[0], h->X[1], h->X[2]);
+        else SPH_LAUNCH_PBF(k_pbf_delta, quad, rx, g, gq, s, c, k, h->dt_wcsph, h->P[1 - h->pcur], h->V[h->vcur], h->WP, h->nl, h->nlb, h->cnt, h->X[0], h->X[1], h->X[2]);
     }
+    if (h->slab && (rc = slab_exchange_field(h, 4, h->X[1], h->X[2], nullptr))) return rc;               // their new position and phase-1 velocity
     {
         ProfScope ps(h, K_B_XSPH);                            // update_all_pos phases 2-3 :86-98
-        SPH_LAUNCH_PBF(k_pbf_xsph, quad, rx, g, gq, s, c, k, h->P[h->pcur], h->X[1], h->X[2], h->cell_start, h->P[1 - h->pcur], h->V[1 - h->vcur]);
+        if (h->slab) {
+            if (rx) hipLaunchKernelGGL((k_pbf_xsph_slab<true>), g, dim3(kBlock), 0, s, c, k, h->P[h->pcur], h->X[1], h->X[2], h->cell_start, h->cnt, h->P[1 - h->pcur], h->V[1 - h->vcur]);
+            else hipLaunchKernelGGL((k_pbf_xsph_slab<false>), g, dim3(kBlock), 0, s, c, k, h->P[h->pcur], h->X[1], h->X[2], h->cell_start, h->cnt, h->P[1 - h->pcur], h->V[1 - h->vcur]);
+        } else
+            SPH_LAUNCH_PBF(k_pbf_xsph, quad, rx, g, gq, s, c, k, h->P[h->pcur], h->X[1], h->X[2], h->cell_start, h->P[1 - h->pcur], h->V[1 - h->vcur]);
     }
     h->pcur ^= 1; h->vcur ^= 1;
     HIP_TRY(h, hipGetLastError());
     h->nl_valid = false;
     h->density_valid = false;
+    h->pbf_fields = true;                                   // pbf_lambda (aux) and delta_pos (X[0]) in the device order of this step
     return SPH_OK;
 }
 

@@ -372,10 +372,14 @@ int slab_exchange_field(SphHandle *h, int mode, float4 *P, float4 *V, float *rho
 {
     hipStream_t s = h->stream;
     const dim3 b(kBlock);
-    const size_t fl = mode == 0 ? 1 : (mode == 1 ? 3 : 2);      // modes 2 and 3: two floats
+    const size_t fl = mode == 0 ? 1 : mode == 1 ? 3 : mode == 4 ? 6 : 2;      // modes 2 and 3: two floats; 4: the xyz of two arrays
     auto cnt = [&](int k) { return h->edge_n[k][0] + (cols >= 2 && h->geom.layers >= 2 ? h->edge_n[k][1] : 0); };
     const int nsl = cnt(1), nsr = cnt(2), nrl = cnt(0), nrr = cnt(3);
     float *S = h->c.kr_split ? h->krho : nullptr;               // where the per-sweep scalar k / rho lives (else P.w)
+    // before anything is packed: an edge list holds up to two messages' worth of records of the particle exchange (32 bytes each), so only a
+    // refresh of more than 16 bytes per ghost can outgrow the buffers the exchange fitted into
+    if (4 * fl * (size_t)std::max(std::max(nsl, nsr), std::max(nrl, nrr)) > h->comm.capacity)
+        return fail(h, SPH_E_OVERFLOW, "halo refresh of %zu bytes per ghost exceeds the comm buffer capacity %zu", 4 * fl, (size_t)h->comm.capacity);
     {
         ProfScope ps(h, K_SLAB);
         if (nsl + nsr)
@@ -547,6 +551,7 @@ int slab_state_commit(SphHandle *h, const float *pos, const float *vel, const fl
     h->flow_stamp = h->flow_last = 0; h->flow_d6 = kNoFlow;
     h->dens_sparse = false; h->dens_first = true; h->pending_div = kNoRide;
     h->last_iters = 2; h->pb_final = 0;
+    h->pbf_fields = false;                    // pbf_lambda / delta_pos: "before the first step" again
     return SPH_OK;
 }
 

@@ -95,6 +95,7 @@ struct SphHandle {
     int simulate_cnt = 0;
     bool nl_valid = false;      // neighbour list matches the current positions
     bool density_valid = false;
+    bool pbf_fields = false;    // pbf: aux / X[0] hold pbf_lambda / delta_pos of the last step in the current device order (slab handles lose them at a re-sort)
 
     // device state (sorted order); index [cur] is the live one
     float4 *P[2] = {nullptr, nullptr};
@@ -874,6 +875,15 @@ int sph_download_local(SphHandle *h, int field, float *host, size_t n_floats)
     case SPH_F_WARM_K: if (dfsph) sca = h->warm[h->wcur]; break;
     case SPH_F_RHO_ADV: sca = h->rho_adv; break;
     case SPH_F_RHO_DER: sca = h->drho; break;
+    case SPH_F_PBF_LAMBDA: case SPH_F_PBF_DELTA_POS: case SPH_F_POS_PREDICT:
+        if (h->cfg.solver != SPH_SOLVER_PBF) break;
+        if (!h->pbf_fields)
+            return fail(h, SPH_E_STATE, h->simulate_cnt == 0 ? "pbf_lambda / delta_pos / pos_predict exist after the first step"
+                                                             : "pbf_lambda / delta_pos / pos_predict of a slab handle are valid from a step until the next sort "
+                                                               "(sph_build_neighbors, sph_compute_density, sph_slab_set_state): step first");
+        if (field == SPH_F_PBF_LAMBDA) sca = h->aux;
+        else vec = field == SPH_F_PBF_DELTA_POS ? h->X[0] : h->P[h->pcur];      // pos = pos_predict after a step (:84)
+        break;
     default: break;
     }
     if (!vec && !sca) return fail(h, SPH_E_INVALID, "field %d cannot be downloaded from this handle", field);
@@ -898,7 +908,11 @@ int sph_build_neighbors(SphHandle *h)
     // pbf_lambda and delta_pos are per-particle fields of the solver that neither update_grid nor compute_all_rho touches; they live in device order
     // (aux, X[0]), which the re-sort changes: carry them through in API order -- lambda in the staging buffer, delta_pos as 3 N floats in X[1]
     // (phase 1's new positions: scratch between steps, 4 N floats).  Here and not in sph_compute_density: a sph_build_neighbors of its own re-sorts too
-    const bool keep = h->cfg.solver == SPH_SOLVER_PBF && h->simulate_cnt > 0;
+    // Slab handles do NOT carry: there id[] holds global ids (~id for ghosts), fewer or more than N particles are resident, and the re-sort starts with
+    // a particle exchange that changes who is -- k_unsort_* / k_sort_in_* over N elements would index outside the arrays.  pbf_lambda / delta_pos of a
+    // slab handle are valid from a step until the next sort; sph_download_local answers SPH_E_STATE after it
+    const bool keep = h->cfg.solver == SPH_SOLVER_PBF && h->simulate_cnt > 0 && !h->slab;
+    if (h->slab) h->pbf_fields = false;
     if (keep) {
         hipLaunchKernelGGL(k_unsort_scalar, grid_for(h->N), dim3(kBlock), 0, h->stream, h->N, h->aux, h->id[h->icur], h->staging);
         hipLaunchKernelGGL(k_unsort_vec, grid_for(h->N), dim3(kBlock), 0, h->stream, h->N, h->X[0], h->id[h->icur], (float *)h->X[1]);
@@ -918,7 +932,7 @@ int sph_compute_density(SphHandle *h)
     if (!h) return SPH_E_INVALID;
     HIP_TRY(h, hipSetDevice(h->device));
     int rc;
-    if (!h->nl_valid && (rc = sph_build_neighbors(h))) return rc;      // (carries pbf_lambda and delta_pos through its re-sort)
+    if (!h->nl_valid && (rc = sph_build_neighbors(h))) return rc;      // (one GPU: carries pbf_lambda and delta_pos through its re-sort)
     if (h->density_valid) return SPH_OK;
     if ((rc = stage_density(h))) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -1028,16 +1042,17 @@ int sph_step_pbf(SphHandle *h, int nsteps)
 {
     if (!h || nsteps < 0) return SPH_E_INVALID;
     if (h->cfg.solver != SPH_SOLVER_PBF) return fail(h, SPH_E_STATE, "handle was not created with solver = SPH_SOLVER_PBF");
-    if (h->slab) return fail(h, SPH_E_STATE, "pbf is not available on slab handles");
     HIP_TRY(h, hipSetDevice(h->device));
     for (int k = 0; k < nsteps; ++k) {
         int rc = step_pbf_once(h);
         if (rc) return rc;
     }
     if (nsteps > 0) {
+        // overflow is sticky within a call: one read-back per call, and on slab handles one verdict of all ranks (a rank that failed alone would leave
+        // its peers waiting in the next exchange)
         int rc = read_scalars(h);
         if (rc) return rc;
-        if ((rc = check_overflow(h))) return rc;
+        if ((rc = check_overflow_all(h))) return rc;
     }
     return SPH_OK;
 }

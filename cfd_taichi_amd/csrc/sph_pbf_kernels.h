@@ -82,9 +82,31 @@ __device__ __forceinline__ F3 spiky_grad(const Consts &c, const PbfConsts &k, fl
     return o;
 }
 
+// QSUM (x-slab handles under RX, one lane per particle): the additions of the quad walk.  walk_list_quad forms every entry's terms in ZEROED
+// accumulators and then adds them in list order; under RX the pair bodies accumulate with fma, so a QUAD handle rounds fma(a, b, 0) and then the
+// sum where the plain walk rounds fma(a, b, acc) once -- other bits.  A slab handle runs one lane per particle whatever the scene's size, and must
+// give what the one-GPU handle of the same scene gives: where that handle walks quad-wide (pbf_qsum(), sph_host_dfsph.h) the slabs take this
+// walk.  The exact bodies round every product and sum separately: QUAD and plain agree there, and QSUM is never instantiated.
+// (a functor, not a lambda in the sweep: the kernels' own closures keep their places, and the instantiations without QSUM stay the code they were)
+template <int N, class Body>
+struct PbfQuadSum {
+    float (&acc)[N];
+    Body &body;
+    __device__ __forceinline__ void operator()(const float4 pj) const
+    {
+        float save[N];
+#pragma unroll
+        for (int n = 0; n < N; ++n) { save[n] = acc[n]; acc[n] = 0.0f; }
+        body(pj);
+#pragma unroll
+        for (int n = 0; n < N; ++n) acc[n] = save[n] + acc[n];
+    }
+};
+template <int N, class Body> __device__ __forceinline__ PbfQuadSum<N, Body> pbf_quad_sum(float (&acc)[N], Body &body) { return PbfQuadSum<N, Body>{acc, body}; }
+
 // rho, constrain, constrain_derivative, lambda.  Pout = (pos, lambda) for the gather of k_pbf_delta.
 // QUAD (both list sweeps): four lanes per particle, small scenes (walk_list_quad, sph_kernels.h)
-template <bool QUAD, bool RX = false>
+template <bool QUAD, bool RX = false, bool QSUM = false>
 __global__ __launch_bounds__(kBlock) void k_pbf_lambda(Consts c, PbfConsts k, const float4 *__restrict__ P, const float4 *__restrict__ WP,
                                                        const uint32_t *__restrict__ nl, const uint32_t *__restrict__ nlb,
                                                        const int *__restrict__ cnt, float *__restrict__ rho_out, float *__restrict__ lambda_out,
@@ -110,6 +132,7 @@ __global__ __launch_bounds__(kBlock) void k_pbf_lambda(Consts c, PbfConsts k, co
         sum += (gx * gx + gy * gy) + gz * gz;                      // :133-134
     };
     if (QUAD) sweep_quad<false>(SrcP{P}, nlp, kf, q, fa, pair);
+    else if constexpr (QSUM) sweep_list<false>(SrcP{P}, nlp, kf, pbf_quad_sum(fa, pair));
     else sweep_list<false>(SrcP{P}, nlp, kf, pair);
     float wa[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
     float &rb = wa[0], &bx = wa[1], &by = wa[2], &bz = wa[3], &sb = wa[4];
@@ -130,6 +153,7 @@ __global__ __launch_bounds__(kBlock) void k_pbf_lambda(Consts c, PbfConsts k, co
         sb += (gx * gx + gy * gy) + gz * gz;                       // :139-140
     };
     if (QUAD) sweep_quad<false>(SrcP{WP}, nlbp, kb, q, wa, wall);
+    else if constexpr (QSUM) sweep_list<false>(SrcP{WP}, nlbp, kb, pbf_quad_sum(wa, wall));
     else sweep_list<false>(SrcP{WP}, nlbp, kb, wall);
     if (!owner) return;
     if constexpr (RX) {                                            // the constant factors of the sums, once
@@ -151,7 +175,7 @@ __global__ __launch_bounds__(kBlock) void k_pbf_lambda(Consts c, PbfConsts k, co
 }
 
 // delta_pos, the prediction and phase 1 of update_all_pos.  PL = (pos, lambda); writes Pn = new position, Vn = phase-1 velocity.
-template <bool QUAD, bool RX = false>
+template <bool QUAD, bool RX = false, bool QSUM = false>
 __global__ __launch_bounds__(kBlock) void k_pbf_delta(Consts c, PbfConsts k, float dt, const float4 *__restrict__ PL, const float4 *__restrict__ V,
                                                       const float4 *__restrict__ WP, const uint32_t *__restrict__ nl,
                                                       const uint32_t *__restrict__ nlb, const int *__restrict__ cnt,
@@ -179,6 +203,7 @@ __global__ __launch_bounds__(kBlock) void k_pbf_delta(Consts c, PbfConsts k, flo
         ax += f * g.x; ay += f * g.y; az += f * g.z;
     };
     if (QUAD) sweep_quad<false>(SrcP{PL}, nlp, kf, q, fa, pair);
+    else if constexpr (QSUM) sweep_list<false>(SrcP{PL}, nlp, kf, pbf_quad_sum(fa, pair));
     else sweep_list<false>(SrcP{PL}, nlp, kf, pair);
     float wa[3] = {0.f, 0.f, 0.f};
     float &bx = wa[0], &by = wa[1], &bz = wa[2];
@@ -199,6 +224,7 @@ __global__ __launch_bounds__(kBlock) void k_pbf_delta(Consts c, PbfConsts k, flo
         bx += f * g.x; by += f * g.y; bz += f * g.z;
     };
     if (QUAD) sweep_quad<false>(SrcP{WP}, nlbp, kb, q, wa, wall);
+    else if constexpr (QSUM) sweep_list<false>(SrcP{WP}, nlbp, kb, pbf_quad_sum(wa, wall));
     else sweep_list<false>(SrcP{WP}, nlbp, kb, wall);
     if (!owner) return;
     if constexpr (RX) { ax *= k.rx_kg; ay *= k.rx_kg; az *= k.rx_kg; bx *= k.rx_kg; by *= k.rx_kg; bz *= k.rx_kg; }
@@ -230,16 +256,30 @@ __global__ __launch_bounds__(kBlock) void k_pbf_delta(Consts c, PbfConsts k, flo
 // QUAD (small scenes): the four lanes of a quad serve one particle; lane q evaluates candidate j0 + q of every batch of four of a cell and
 // all four add the four terms in candidate order (quad_bcast, sph_kernels.h) -- a candidate that is skipped contributes +0, which leaves
 // the running sums (never -0) unchanged: the same additions in the same order as the one-lane walk.
-template <bool QUAD, bool RX = false>
-__global__ __launch_bounds__(kBlock) void k_pbf_xsph(Consts c, PbfConsts k, const float4 *__restrict__ Pold, const float4 *__restrict__ Pn,
-                                                     const float4 *__restrict__ Vn, const int *__restrict__ cell_start,
-                                                     float4 *__restrict__ Pfin, float4 *__restrict__ Vfin)
+//
+// SLAB (x-slab handles, one lane per particle): a ghost (cnt < 0, k_build_nl's ghost bit) does not walk -- half of its 27 cells are not resident --
+// and copies what its owner sent after k_pbf_delta (slab_exchange_field mode 4: Pn, Vn) into Pfin / Vfin, so that every resident slot of the
+// final arrays holds defined values.  Nothing downstream depends on them: the next particle exchange decides "last step's ghost: dies" from the
+// sign of id[] alone, in k_classify_count and k_classify_write alike (classify_slot returns before it reads P), the dead slot takes no part in
+// the sort, and the owner sends the ghost's successor.  An owned particle of an edge column finds its ghost neighbours' refreshed Pn / Vn through
+// the same cell lists as on one GPU, in the same (cell, id) order.  The one-GPU kernels are the instantiations SLAB = false of the same body.
+template <bool QUAD, bool RX, bool SLAB>
+__device__ __forceinline__ void pbf_xsph_body(const Consts &c, const PbfConsts &k, const float4 *__restrict__ Pold, const float4 *__restrict__ Pn,
+                                              const float4 *__restrict__ Vn, const int *__restrict__ cell_start, const int *__restrict__ cnt,
+                                              float4 *__restrict__ Pfin, float4 *__restrict__ Vfin)
 {
     const int blk = xcd_block(blockIdx.x, gridDim.x);
     const int q = QUAD ? (int)(threadIdx.x & 3) : 0;
     const int i = QUAD ? blk * (kBlock / 4) + (int)(threadIdx.x >> 2) : blk * kBlock + (int)threadIdx.x;
     if (i >= c.n) return;                                          // (a quad leaves together)
     const float4 po = Pold[i], pi = Pn[i], vi = Vn[i];
+    if constexpr (SLAB) {
+        if (cnt[i] < 0) {                                          // a ghost: the owner's values, no walk
+            Pfin[i] = make_float4(pi.x, pi.y, pi.z, 0.f);
+            Vfin[i] = make_float4(vi.x, vi.y, vi.z, 0.f);
+            return;
+        }
+    }
     int cx, cy, cz;
     cell_id_of(c, po.x, po.y, po.z, cx, cy, cz);                   // belong_grid, set by update_grid at the step's start
     float ax = 0.f, ay = 0.f, az = 0.f;
@@ -301,6 +341,20 @@ __global__ __launch_bounds__(kBlock) void k_pbf_xsph(Consts c, PbfConsts k, cons
     Pfin[i] = make_float4(pi.x, pi.y, pi.z, 0.f);
     const float cv = RX ? k.rx_ck : k.c_visc;
     Vfin[i] = make_float4(vi.x + cv * ax, vi.y + cv * ay, vi.z + cv * az, 0.f);   // :92 / :94
+}
+template <bool QUAD, bool RX = false>
+__global__ __launch_bounds__(kBlock) void k_pbf_xsph(Consts c, PbfConsts k, const float4 *__restrict__ Pold, const float4 *__restrict__ Pn,
+                                                     const float4 *__restrict__ Vn, const int *__restrict__ cell_start,
+                                                     float4 *__restrict__ Pfin, float4 *__restrict__ Vfin)
+{
+    pbf_xsph_body<QUAD, RX, false>(c, k, Pold, Pn, Vn, cell_start, nullptr, Pfin, Vfin);
+}
+template <bool RX>
+__global__ __launch_bounds__(kBlock) void k_pbf_xsph_slab(Consts c, PbfConsts k, const float4 *__restrict__ Pold, const float4 *__restrict__ Pn,
+                                                          const float4 *__restrict__ Vn, const int *__restrict__ cell_start, const int *__restrict__ cnt,
+                                                          float4 *__restrict__ Pfin, float4 *__restrict__ Vfin)
+{
+    pbf_xsph_body<false, RX, true>(c, k, Pold, Pn, Vn, cell_start, cnt, Pfin, Vfin);
 }
 
 }  // namespace sph

@@ -339,7 +339,8 @@ __global__ __launch_bounds__(kBlock) void k_layer_list(Consts c, const int *__re
 }
 
 // ghost field refresh: mode 0 = the per-sweep scalar k / rho (1 float), 1 = V.xyz (3 floats), 2 = (scalar, V.w) (2 floats; rho[] := V.w, dfsph),
-// 3 = (P.w, V.w) with rho[] := P.w (pcisph / iisph: P.w carries rho).  The scalar is S[s] on kr_split handles (S = krho), else P[s].w.
+// 3 = (P.w, V.w) with rho[] := P.w (pcisph / iisph: P.w carries rho), 4 = (P.xyz, V.xyz) (6 floats: pbf's new position and phase-1 velocity in
+// one message; the w components stay the receiver's).  The scalar is S[s] on kr_split handles (S = krho), else P[s].w.
 // One launch serves both sides: threads [0, count_a) work on side a (left), threads [count_a, count_a + count_b) on side b (right).
 __global__ __launch_bounds__(kBlock) void k_pack_field(const int *__restrict__ list_a, int count_a, float *__restrict__ out_a,
                                                        const int *__restrict__ list_b, int count_b, float *__restrict__ out_b, int mode,
@@ -353,6 +354,11 @@ __global__ __launch_bounds__(kBlock) void k_pack_field(const int *__restrict__ l
     float *out = b ? out_b : out_a;
     if (mode == 0) out[r] = S ? S[s] : P[s].w;
     else if (mode == 1) { float4 v = V[s]; out[3 * (size_t)r] = v.x; out[3 * (size_t)r + 1] = v.y; out[3 * (size_t)r + 2] = v.z; }
+    else if (mode == 4) {
+        const float4 p = P[s], v = V[s];
+        float *o = out + 6 * (size_t)r;
+        o[0] = p.x; o[1] = p.y; o[2] = p.z; o[3] = v.x; o[4] = v.y; o[5] = v.z;
+    }
     else { out[2 * (size_t)r] = S ? S[s] : P[s].w; out[2 * (size_t)r + 1] = V[s].w; }
 }
 
@@ -368,6 +374,10 @@ __global__ __launch_bounds__(kBlock) void k_unpack_field(const int *__restrict__
     const float *in = b ? in_b : in_a;
     if (mode == 0) { if (S) S[s] = in[r]; else P[s].w = in[r]; }
     else if (mode == 1) { V[s].x = in[3 * (size_t)r]; V[s].y = in[3 * (size_t)r + 1]; V[s].z = in[3 * (size_t)r + 2]; }
+    else if (mode == 4) {
+        const float *q = in + 6 * (size_t)r;
+        P[s].x = q[0]; P[s].y = q[1]; P[s].z = q[2]; V[s].x = q[3]; V[s].y = q[4]; V[s].z = q[5];
+    }
     else {
         const float aa = in[2 * (size_t)r];
         const float bb = in[2 * (size_t)r + 1];

@@ -242,7 +242,9 @@ class SlabSimulation:
         self.n_fluid = self.sim.n_fluid
 
     def step(self, nsteps=1):
-        """nsteps solver steps; returns the last one's SphStepStats (None for wcsph).  With an active rigid body every solver step is followed
+        """nsteps solver steps; returns the last one's SphStepStats (None for wcsph and pbf, which report none).  pbf runs on slabs like the
+        others -- one ghost column, a lambda refresh and a position / velocity refresh per step (csrc/sph_host_pressure.h: step_pbf_once) -- and
+        takes its list-overflow verdict once per sim.step call, on all ranks together.  With an active rigid body every solver step is followed
         by one body step (main.py:165-171 with iter_cnt 1).  Forces accumulated over several solver steps before one body step (iter_cnt > 1)
         are not supported on slabs: a sample's force is summed by the rank that owns its cell column, and ownership can change between steps."""
         try:
@@ -284,7 +286,8 @@ class SlabSimulation:
 
     def set_state(self, pos, vel=None, scalar=None, delta_time=None, src=None, group=None):
         """Collective: replace the sharded run's state by one full state in original particle order -- pos (n, 3), vel (n, 3) or None
-        (zeros), scalar (n,) = the per-particle scalar that travels with a particle (dfsph warm_start_k) or None, delta_time or None (keep).
+        (zeros), scalar (n,) = the per-particle scalar that travels with a particle (dfsph warm_start_k) or None -- it must be None where the solver
+        carries none (wcsph, pcisph, pbf) --, delta_time or None (keep).
         Every rank passes the same arrays; with src=RANK only that rank's arguments count and are broadcast through torch.distributed.
         The cuts are planned anew from the positions; a refusal raises the same SphError on every rank and leaves every handle as it was."""
         if src is not None:
@@ -301,7 +304,8 @@ class SlabSimulation:
 
     def state(self, dst=0):
         """(pos, vel, scalar, delta_time) of the whole run in original particle order on rank `dst` (else None): what set_state takes.
-        scalar is None where the solver carries none."""
+        scalar is None where the solver carries none (pbf: pos, vel and delta_time are the whole state; pbf_lambda / delta_pos are results of a
+        step, "before the first step" again after set_state)."""
         pos, vel = self.gather(nat.F_POS, dst), self.gather(nat.F_VEL, dst)
         scalar = self.gather(nat.F_WARM_K, dst) if self.solver == "dfsph" else None
         dt = self.sim.scalar(nat.S_DELTA_TIME)

@@ -44,8 +44,8 @@ int32_t sph_abi_version(void);
 #define SPH_SOLVER_DFSPH 1
 #define SPH_SOLVER_PCISPH 2   /* pcisph_solver.py */
 #define SPH_SOLVER_IISPH 3    /* iisph_solver.py */
-#define SPH_SOLVER_PBF 4      /* pbf_solver.py (stale in the reference: read as csrc/sph_pbf_kernels.h states; single GPU, no rigid body) */
-/* (wcsph, dfsph, pcisph and iisph run on slab handles, with or without a coupled rigid body: sph_create_rigid) */
+#define SPH_SOLVER_PBF 4      /* pbf_solver.py (stale in the reference: read as csrc/sph_pbf_kernels.h states; no rigid body) */
+/* (all five run on slab handles; wcsph, dfsph, pcisph and iisph with or without a coupled rigid body: sph_create_rigid) */
 
 /* config/X.json of the reference, flattened (utils.py:3-11 reads it,
  * ParticleSystem.py:31-103 and solver_base.py:7-39 consume it).  Doubles carry the Python
@@ -215,7 +215,7 @@ int sph_create(const SphConfig *cfg, SphHandle **out);
  * is replicated on every rank, three small all-reduces per step (the fluid positions and densities the reference's index quirks read, the per-sample
  * forces, each summed whole by the rank that owns the sample's cell column) keep every rank's copy bit-identical to the one-GPU run.  One sph_rigid_step
  * after every solver step: forces gathered over several solver steps are not supported there (column ownership changes between steps).  SPH_E_INVALID
- * on slab handles: dfsph with slab_ghost_layers = 1, a one-way body (active, fs_couple 0), pbf. */
+ * on slab handles: dfsph with slab_ghost_layers = 1, a one-way body (active, fs_couple 0); on every handle: pbf (pbf_solver.py has no coupling). */
 int sph_create_rigid(const SphConfig *cfg, const SphRigid *rigid, SphHandle **out);
 /* replaces rigid_solver.step()   rigid_solver.py:216-232 */
 int sph_rigid_step(SphHandle *h);
@@ -252,7 +252,12 @@ int sph_step_pcisph(SphHandle *h, int nsteps, SphStepStats *last);
 /* replaces iisph_solver.step() x nsteps   iisph_solver.py:340-347.  last->n_dens = l and last->dens_err = residual as printed at :102;
  * last->n_div = 1 when the loop left on "Iteration trend to divergence" (:97-99); last->capped = 1 at max_iter_cnt (180) */
 int sph_step_iisph(SphHandle *h, int nsteps, SphStepStats *last);
-/* replaces pbf_solver.step() x nsteps     pbf_solver.py:176-187 (update_all_pos under the barrier-synchronised schedule, csrc/sph_pbf_kernels.h) */
+/* replaces pbf_solver.step() x nsteps     pbf_solver.py:176-187 (update_all_pos under the barrier-synchronised schedule, csrc/sph_pbf_kernels.h).
+ * On slab handles (one ghost column, any transport; in order on the handle's stream -- slab_overlap is ignored; exact or relaxed): per step the
+ * particle exchange, then lambda of the ghosts after the lambda sweep (4 bytes per ghost), then their new position and phase-1 velocity in one
+ * message after the delta_pos sweep (24 bytes per ghost) -- three point-to-point groups, no all-reduce.  The overflow verdict is taken once per
+ * call by all ranks together (one host all-reduce): every rank returns SPH_E_OVERFLOW if any rank's lists overflowed.  Bit for bit the one-GPU
+ * handle's pos, vel, rho, pbf_lambda and delta_pos. */
 int sph_step_pbf(SphHandle *h, int nsteps);
 /* stages of the step, for parity tests against the oracle's stages:
  * ps.reset_grid()+update_grid() (+ neighbour-list build), solver.compute_all_rho(), dfsph compute_all_alpha().
@@ -262,7 +267,9 @@ int sph_step_pbf(SphHandle *h, int nsteps);
  * per-particle results of the last step (rho, alpha, pressure, acc, rho_adv, rho_derivative, vel_adv, press_iter, press_force, pos_predict, d_ii,
  * a_ii, d_ij) are no longer valid for sph_download until they are computed again -- rho (dfsph: and alpha, wcsph: and pressure, which the fused
  * sweep writes with it) by sph_compute_density / sph_compute_alpha, the rest by the next step; SPH_F_NBR_COUNT becomes that of the current
- * positions.  sph_compute_density and sph_compute_alpha build the lists first if positions changed since the last build. */
+ * positions.  sph_compute_density and sph_compute_alpha build the lists first if positions changed since the last build.
+ * Slab handles: the three are collective (the re-sort starts with a particle exchange, and all ranks agree on one overflow verdict).  A pbf slab
+ * handle does NOT carry pbf_lambda / delta_pos through the re-sort: there they are valid from a step until the next sort (sph_download_local). */
 int sph_build_neighbors(SphHandle *h);
 int sph_compute_density(SphHandle *h);
 int sph_compute_alpha(SphHandle *h);
@@ -364,13 +371,16 @@ int sph_slab_info(SphHandle *h, int32_t *out8);
  * out[6] steps, out[7] 0.  bench.py reports them per step in config.rank0_comm so that a measured N > 1 line can be read against the
  * cost model of DESIGN.md section 6. */
 int sph_comm_stats(SphHandle *h, int64_t *out8, int reset);
-/* local (device-order) access for slab handles: all resident particles, owned and ghost; ids < 0 mark ghosts (~id) */
+/* local (device-order) access for slab handles: all resident particles, owned and ghost; ids < 0 mark ghosts (~id).  pbf handles also give
+ * SPH_F_PBF_LAMBDA, SPH_F_PBF_DELTA_POS and SPH_F_POS_PREDICT (= pos after a step): SPH_E_STATE before the first step, as from sph_download, and on
+ * a slab handle from the next sort (sph_build_neighbors, sph_compute_density) or sph_slab_set_state until the step after it.  The ghosts' entries
+ * of rho and delta_pos are not the owners' values (a ghost has no lists); their lambda, pos and vel are. */
 int sph_download_local(SphHandle *h, int field, float *host, size_t n_floats);
 int sph_download_ids(SphHandle *h, int32_t *host, size_t n);
 /* Start (or continue) a sharded run from any state: replaces everything resident on a slab handle -- owned particles, ghosts, dead slots -- by
  * its share of one FULL state.  Collective: every rank of the slab group calls it with the same arrays in ORIGINAL particle order: pos = 3 n_fluid
  * floats, vel = 3 n_fluid floats or NULL (zeros), scalar = the per-particle scalar that travels with a particle on this solver (dfsph warm_start_k;
- * n_fluid floats) or NULL (zeros; it must be NULL where the solver carries none); delta_time > 0 is written as sph_set_scalar(SPH_S_DELTA_TIME) writes
+ * n_fluid floats) or NULL (zeros; it must be NULL where the solver carries none: wcsph, pcisph, pbf); delta_time > 0 is written as sph_set_scalar(SPH_S_DELTA_TIME) writes
  * it, 0 keeps the handle's.  The cuts are planned anew from the positions by the rule of sph_create (from a per-column histogram counted on the
  * device, the same on every rank); afterwards the handle is a newly created slab handle that holds this state -- the step counter and the
  * re-balancing counter keep their values, and the next step exchanges particles in two rounds, as after any change of the cuts.
