@@ -29,6 +29,9 @@ S_PCISPH_DELTA, S_PCISPH_BETA, S_PCISPH_MAX_INDEX, S_PCISPH_MAX_COUNT = range(6,
 S_ARITH_RELAXED = 30
 S_VERLET_BUILDS = 31
 S_RIGID_ACTIVE = 32
+S_RIGID_ACC, S_RIGID_ALPHA, S_RIGID_MODE = 33, 36, 39
+RIGID_DYNAMIC, RIGID_SCRIPTED, RIGID_FIXED = 0, 1, 2          # sph_rigid_set_mode
+RIGID_MODES = {"dynamic": RIGID_DYNAMIC, "scripted": RIGID_SCRIPTED, "fixed": RIGID_FIXED}
 # `solver.<attribute> = value` (include/sph_mi355x.h SPH_P_*): name of the reference's attribute -> id
 SOLVER_PARAMS = {"density_threshold": 64, "min_iteration_density": 65, "min_iteration_density_divergence": 66, "max_iteration_density_divergence": 67,
                  "density_divergence_threshold": 68, "warm_start": 69, "adaptive_dt": 70, "max_dt": 71, "min_dt": 72,
@@ -43,6 +46,7 @@ EXPORTS = [
     "sph_profile_kernel_name", "sph_profile_get", "sph_selftest_math", "sph_selftest_wave", "sph_selftest_stage", "sph_selftest_walk", "sph_tune_time",
     "sph_set_comm", "sph_rccl_unique_id", "sph_rccl_attach", "sph_rccl_selftest", "sph_get_stream", "sph_plan_slabs", "sph_replan_slabs", "sph_slab_set_overlap", "sph_slab_info", "sph_comm_stats", "sph_download_local", "sph_download_ids",
     "sph_create_rigid", "sph_rigid_step", "sph_rigid_set_active", "sph_rigid_init_data", "sph_slab_set_state",
+    "sph_rigid_set_mode", "sph_rigid_set_motion", "sph_rigid_get_load",
 ]
 
 
@@ -172,7 +176,8 @@ CORE_EXPORTS = [
 ]
 # entry points added without a change of SPH_ABI_VERSION (no struct grew, no signature changed): bound where the library has them, and a call on a
 # library without them raises SphError(SPH_E_STATE)
-OPTIONAL_EXPORTS = ["sph_rigid_set_active", "sph_rigid_init_data", "sph_selftest_stage", "sph_selftest_walk", "sph_slab_set_state"]
+OPTIONAL_EXPORTS = ["sph_rigid_set_active", "sph_rigid_init_data", "sph_selftest_stage", "sph_selftest_walk", "sph_slab_set_state",
+                    "sph_rigid_set_mode", "sph_rigid_set_motion", "sph_rigid_get_load"]
 
 
 def _bind_core(lib):
@@ -210,6 +215,12 @@ def _bind_core(lib):
         lib.sph_rigid_set_active.argtypes = [vp, ci]
     if hasattr(lib, "sph_rigid_init_data"):
         lib.sph_rigid_init_data.argtypes = [vp]
+    if hasattr(lib, "sph_rigid_set_mode"):
+        lib.sph_rigid_set_mode.argtypes = [vp, ci]
+    if hasattr(lib, "sph_rigid_set_motion"):
+        lib.sph_rigid_set_motion.argtypes = [vp, vp, vp, vp, vp]
+    if hasattr(lib, "sph_rigid_get_load"):
+        lib.sph_rigid_get_load.argtypes = [vp, vp, vp]
     return lib
 
 
@@ -468,11 +479,32 @@ class Simulation:
         """ps.init_rigid_particles_data(): sample volumes, masses, centroid and inertia from the body's current sample positions."""
         self._check(self._optional("sph_rigid_init_data")(self._h))
 
-    def rigid_scalars(self):
+    def rigid_set_mode(self, mode):
+        """what rigid_step does with the body: "dynamic" (rigid_solver.step, the default), "scripted" (moved by rigid_set_motion's motion) or
+        "fixed" (never moves); a name of RIGID_MODES or its number."""
+        self._check(self._optional("sph_rigid_set_mode")(self._h, RIGID_MODES.get(mode, mode)))
+
+    def rigid_set_motion(self, vel, omega, acc=None, alpha=None):
+        """the motion a scripted body follows from the next rigid_step on, until it is replaced (acc, alpha: None = zeros)"""
+        arrs = [None if v is None else np.ascontiguousarray(v, dtype=np.float32).reshape(3) for v in (vel, omega, acc, alpha)]
+        self._check(self._optional("sph_rigid_set_motion")(self._h, *[None if a is None else a.ctypes.data for a in arrs]))
+
+    def rigid_load(self):
+        """(force, torque) of the fluid on the body as the last rigid_step summed them, f64; the torque about the centroid before that step's move"""
+        force, torque = np.zeros(3, dtype=np.float64), np.zeros(3, dtype=np.float64)
+        self._check(self._optional("sph_rigid_get_load")(self._h, force.ctypes.data, torque.ctypes.data))
+        return force, torque
+
+    def rigid_scalars(self, motion=False):
+        """the body's scalars; motion=True adds acc, alpha (what the sweeps extrapolate vel and omega with) and mode (RIGID_*), which a library
+        from before the body modes does not have"""
         g = self.scalar
-        return {"centroid": [g(S_RIGID_CENTROID + k) for k in range(3)], "omega": [g(S_RIGID_OMEGA + k) for k in range(3)],
-                "vel": [g(S_RIGID_VEL + k) for k in range(3)], "mass": g(S_RIGID_MASS),
-                "inertia_inv": [g(S_RIGID_INERTIA_INV + k) for k in range(9)]}
+        out = {"centroid": [g(S_RIGID_CENTROID + k) for k in range(3)], "omega": [g(S_RIGID_OMEGA + k) for k in range(3)],
+               "vel": [g(S_RIGID_VEL + k) for k in range(3)], "mass": g(S_RIGID_MASS),
+               "inertia_inv": [g(S_RIGID_INERTIA_INV + k) for k in range(9)]}
+        if motion:
+            out.update(acc=[g(S_RIGID_ACC + k) for k in range(3)], alpha=[g(S_RIGID_ALPHA + k) for k in range(3)], mode=int(g(S_RIGID_MODE)))
+        return out
 
     def build_neighbors(self):
         self._check(self._lib.sph_build_neighbors(self._h))

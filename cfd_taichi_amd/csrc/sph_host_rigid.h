@@ -137,6 +137,11 @@ int rigid_init_data(SphHandle *h, const std::vector<float> &rpos, bool binned)
         sum_mass += h->rmass_host[i];
     }
     for (int a = 0; a < 3; ++a) h->centroid[a] = cs[a] / sum_mass;
+    h->rigid_radius = 0.f;                                                              // (not the reference's: the grid guard of a scripted step)
+    for (int i = 0; i < Nr; ++i) {
+        float x = rpos[3 * (size_t)i] - h->centroid[0], y = rpos[3 * (size_t)i + 1] - h->centroid[1], z = rpos[3 * (size_t)i + 2] - h->centroid[2];
+        h->rigid_radius = fmaxf(h->rigid_radius, sqrtf((x * x + y * y) + z * z));
+    }
     float Ixx = 0, Iyy = 0, Izz = 0, Ixy = 0, Ixz = 0, Iyz = 0;                         // :275-288
     for (int i = 0; i < Nr; ++i) {
         float x = rpos[3 * (size_t)i] - h->centroid[0], y = rpos[3 * (size_t)i + 1] - h->centroid[1], z = rpos[3 * (size_t)i + 2] - h->centroid[2];
@@ -201,6 +206,7 @@ int build_rigid(SphHandle *h, const SphRigid *rg)
     if ((rc = dalloc(h, &h->ncount, (size_t)h->c.stride))) return rc;
     if ((rc = dalloc(h, &h->rred, kRigidParts))) return rc;
     if ((rc = dalloc(h, &h->rvmax_part, kRigidParts))) return rc;
+    if ((rc = dalloc(h, &h->rload, 6))) return rc;
     if ((rc = dalloc(h, &h->rnl, (nr + 64) * (size_t)h->c.kpitch))) return rc;
     if ((rc = dalloc(h, &h->rcnt, nr))) return rc;
     if (h->relaxed && h->staged && !h->tile_order) {       // relaxed arithmetic next to a body: the tile order of the exact / relaxed split (rx_split)
@@ -286,8 +292,74 @@ int read_rigid_reduce(SphHandle *h)
     return SPH_OK;
 }
 
+// The dt of the coming body step: ps.delta_time if dfsph has set it, the value of the step before otherwise   rigid_solver.py:223-224
+int rigid_next_dt(SphHandle *h, float *dt)
+{
+    *dt = h->rs_dt;
+    if (h->cfg.solver == SPH_SOLVER_DFSPH) {
+        if (int rc = read_scalars(h)) return rc;
+        if (h->ds_host->ps_dt > 0.0f) *dt = h->ds_host->ps_dt;
+    }
+    return SPH_OK;
+}
+
+// A scripted body has no wall test, so nothing but this keeps it in the cell grid: the sphere around the centroid after the step's
+// translation, with the largest sample distance rigid_init_data saw (a rotation about the centroid keeps it up to rounding: 0.1 % on top), has
+// to lie in the grid's cells [0, g h) on every axis.  Conservative on purpose (a body may be refused whose corners would have stayed inside);
+// host arithmetic only, before the step launches or changes anything.  An unbinned body (centroid 0 / 0) fails every comparison: refused.
+int rigid_scripted_guard(SphHandle *h, float dt)
+{
+    const int g[3] = {h->c.gx, h->c.gy, h->c.gz};
+    const float r = h->rigid_radius * 1.001f;
+    for (int a = 0; a < 3; ++a) {
+        const float to = h->centroid[a] + h->rm_vel[a] * dt;
+        if (!(to - r > 0.0f && to + r < (float)g[a] * h->c.h))
+            return fail(h, SPH_E_INVALID, "scripted rigid step refused: the body's sphere (centre %g, radius %g on axis %d) would leave the cell grid [0, %g)",
+                        (double)to, (double)r, a, (double)((float)g[a] * h->c.h));
+    }
+    return SPH_OK;
+}
+
+// sph_rigid_step for a body that is not moved by the forces on it (SPH_RIGID_SCRIPTED, SPH_RIGID_FIXED; include/sph_mi355x.h states the
+// contract).  The sums of k_rigid_torque_force stay on the device (k_rigid_load): three launches for a scripted body, two for a fixed one, and
+// the host waits for nothing (dfsph: for ps.delta_time, because the rotation matrix is formed here, with the host's sinf / cosf as ever).
+int rigid_step_prescribed(SphHandle *h, float dt)
+{
+    hipStream_t s = h->stream;
+    const dim3 b(kBlock);
+    const int np = (int)rigid_parts_grid(h).x;
+    const bool fixed = h->rigid_mode == SPH_RIGID_FIXED;
+    ProfScope ps(h, K_RIGID);
+    hipLaunchKernelGGL(k_rigid_torque_force, rigid_parts_grid(h), b, 0, s, h->Nr, h->RPos, h->rforce, rigid_state(h, nullptr, nullptr), h->rred);
+    hipLaunchKernelGGL(k_rigid_load, fixed ? grid_for(3 * h->Nr) : dim3(1), b, 0, s, np, h->rred, h->rload, fixed ? h->rforce : (float *)nullptr, 3 * h->Nr);
+    h->rload_at = 2;
+    if (fixed) {
+        for (int a = 0; a < 3; ++a) h->r_vel[a] = h->r_acc[a] = h->r_omega[a] = h->r_alpha[a] = h->rs_omega[a] = 0.0f;
+    } else {
+        for (int a = 0; a < 3; ++a) {
+            h->rs_omega[a] = h->rm_omega[a];
+            h->rs_attitude[a] = h->rs_omega[a] * dt;
+            h->r_alpha[a] = h->rm_alpha[a];
+        }
+        Mat3 R;
+        float mt[9], tmp[9], out[9], disp[3];
+        rotation3dh(-h->rs_attitude[0], -h->rs_attitude[2], -h->rs_attitude[1], R.m);
+        for (int a = 0; a < 3; ++a) { h->r_acc[a] = h->rm_acc[a]; h->r_vel[a] = h->rm_vel[a]; disp[a] = h->r_vel[a] * dt; }
+        hipLaunchKernelGGL(k_rigid_move, grid_for(h->Nr + h->Nv), b, 0, s, h->Nr, h->Nv, h->RPos, h->rvert, h->rforce, R, rigid_state(h, nullptr, nullptr),
+                           disp[0], disp[1], disp[2]);
+        for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) mt[3 * r + c] = R.m[3 * c + r];
+        matmul3h(R.m, h->inertia_inv, tmp);
+        matmul3h(tmp, mt, out);
+        memcpy(h->inertia_inv, out, sizeof(out));
+        for (int a = 0; a < 3; ++a) { h->centroid[a] += disp[a]; h->r_omega[a] = h->rs_omega[a]; }
+    }
+    HIP_TRY(h, hipGetLastError());
+    h->nl_valid = false;
+    return SPH_OK;
+}
+
 // rigid_solver.step                                                      rigid_solver.py:216-232
-int rigid_step(SphHandle *h)
+int rigid_step(SphHandle *h, float dt_next)
 {
     hipStream_t s = h->stream;
     const dim3 b(kBlock), gr = grid_for(h->Nr), gv = grid_for(h->Nv > 0 ? h->Nv : 1);
@@ -299,15 +371,15 @@ int rigid_step(SphHandle *h)
         h->rs_run_once = true;
     }
     h->rs_cnt += 1;
-    if (h->cfg.solver == SPH_SOLVER_DFSPH) {
-        if ((rc = read_scalars(h))) return rc;
-        if (h->ds_host->ps_dt > 0.0f) h->rs_dt = h->ds_host->ps_dt;     // :223-224
-    }
+    h->rs_dt = dt_next;                                                 // :223-224 (rigid_next_dt)
     const float dt = h->rs_dt;
+    if (h->rigid_mode != SPH_RIGID_DYNAMIC) return rigid_step_prescribed(h, dt);
     ProfScope ps(h, K_RIGID);
     // compute_attitude :118-128 (+ the force sum of kinematic :35-38: the forces do not change in between)
     hipLaunchKernelGGL(k_rigid_torque_force, rigid_parts_grid(h), b, 0, s, h->Nr, h->RPos, h->rforce, rigid_state(h, nullptr, nullptr), h->rred);
     if ((rc = read_rigid_reduce(h))) return rc;
+    for (int a = 0; a < 3; ++a) { h->rload_host[a] = h->rred_host->force[a]; h->rload_host[3 + a] = h->rred_host->torque[a]; }
+    h->rload_at = 1;
     {
         const float torque[3] = {(float)h->rred_host->torque[0], (float)h->rred_host->torque[1], (float)h->rred_host->torque[2]};
         float alpha[3];

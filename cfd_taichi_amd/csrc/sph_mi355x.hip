@@ -242,6 +242,13 @@ struct SphHandle {
     float rs_dt = 0.f, rs_omega[3] = {0, 0, 0}, rs_attitude[3] = {0, 0, 0}, rs_mass = 0.f;
     bool rs_run_once = false;
     int rs_cnt = 0;
+    // what sph_rigid_step does with the body (SPH_RIGID_*), the motion a scripted body follows, and the load of the last body step
+    int rigid_mode = SPH_RIGID_DYNAMIC;
+    float rm_vel[3] = {0, 0, 0}, rm_omega[3] = {0, 0, 0}, rm_acc[3] = {0, 0, 0}, rm_alpha[3] = {0, 0, 0};
+    float rigid_radius = 0.f;     // largest |sample - centroid| when rigid_init_data last ran: the sphere of a scripted step's grid guard
+    double *rload = nullptr;      // [6] force, torque of the last scripted / fixed step (k_rigid_load)
+    double rload_host[6] = {0, 0, 0, 0, 0, 0};
+    int rload_at = 0;             // 0: no body step yet, 1: rload_host (a dynamic step's host sums), 2: rload on the device
 
     // hipGraph replay of WCSPH step pairs (launch-bound at small N): one executable graph per buffer parity
     hipGraphExec_t wcsph_graph[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -463,6 +470,10 @@ int sph_rigid_step(SphHandle *h)
     if (!h->rigid) return fail(h, SPH_E_STATE, "handle has no rigid body");
     if (int rc = rigid_released_unprepared(h)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
+    float dt;
+    if (int rc = rigid_next_dt(h, &dt)) return rc;
+    if (h->rigid_mode == SPH_RIGID_SCRIPTED)
+        if (int rc = rigid_scripted_guard(h, dt)) return rc;
     if (h->slab) {       // every sample's force was summed whole by the rank that owns its column (k_rigid_force): add the ranks' arrays up, x + 0 = x
         const int n3 = 3 * h->Nr;
         hipLaunchKernelGGL(k_floats_to_doubles, grid_for(n3), dim3(kBlock), 0, h->stream, n3, h->rforce, h->red_dev);
@@ -470,7 +481,47 @@ int sph_rigid_step(SphHandle *h)
         if (rc) return rc;
         hipLaunchKernelGGL(k_doubles_to_floats, grid_for(n3), dim3(kBlock), 0, h->stream, n3, h->red_dev, h->rforce);
     }
-    return rigid_step(h);
+    return rigid_step(h, dt);
+}
+
+int sph_rigid_set_mode(SphHandle *h, int mode)
+{
+    if (!h) return SPH_E_INVALID;
+    if (!h->rigid) return fail(h, SPH_E_STATE, "handle has no rigid body");
+    if (mode != SPH_RIGID_DYNAMIC && mode != SPH_RIGID_SCRIPTED && mode != SPH_RIGID_FIXED) return fail(h, SPH_E_INVALID, "unknown rigid body mode %d", mode);
+    h->rigid_mode = mode;
+    return SPH_OK;
+}
+
+int sph_rigid_set_motion(SphHandle *h, const float vel[3], const float omega[3], const float acc[3], const float alpha[3])
+{
+    if (!h) return SPH_E_INVALID;
+    if (!h->rigid) return fail(h, SPH_E_STATE, "handle has no rigid body");
+    if (!vel || !omega) return fail(h, SPH_E_INVALID, "sph_rigid_set_motion: vel and omega must be given");
+    const float *in[4] = {vel, omega, acc, alpha};
+    for (int q = 0; q < 4; ++q)
+        for (int a = 0; a < 3; ++a)
+            if (in[q] && !std::isfinite(in[q][a])) return fail(h, SPH_E_INVALID, "sph_rigid_set_motion: a value that is not finite");
+    for (int a = 0; a < 3; ++a) {
+        h->rm_vel[a] = vel[a]; h->rm_omega[a] = omega[a];
+        h->rm_acc[a] = acc ? acc[a] : 0.0f; h->rm_alpha[a] = alpha ? alpha[a] : 0.0f;
+    }
+    return SPH_OK;
+}
+
+int sph_rigid_get_load(SphHandle *h, double force[3], double torque[3])
+{
+    if (!h || !force || !torque) return SPH_E_INVALID;
+    if (!h->rigid) return fail(h, SPH_E_STATE, "handle has no rigid body");
+    if (h->rload_at == 0) return fail(h, SPH_E_STATE, "sph_rigid_get_load before the first sph_rigid_step");
+    if (h->rload_at == 2) {
+        HIP_TRY(h, hipSetDevice(h->device));
+        HIP_TRY(h, hipMemcpyAsync(h->rload_host, h->rload, sizeof(double) * 6, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        h->rload_at = 1;
+    }
+    for (int a = 0; a < 3; ++a) { force[a] = h->rload_host[a]; torque[a] = h->rload_host[3 + a]; }
+    return SPH_OK;
 }
 
 void sph_destroy(SphHandle *h)
@@ -1075,6 +1126,7 @@ int sph_get_scalar(SphHandle *h, int which, double *out)
     case SPH_S_PS_DELTA_TIME: { int rc = read_scalars(h); if (rc) return rc; *out = (double)h->ds_host->ps_dt; return SPH_OK; }
     case SPH_S_ARITH_RELAXED: *out = (use_relaxed(h) || h->verlet || relaxed_pressure(h) || relaxed_unstaged(h) || relaxed_pbf(h)) ? 1.0 : 0.0; return SPH_OK;
     case SPH_S_RIGID_ACTIVE: *out = rigid_binned(h) ? 1.0 : 0.0; return SPH_OK;
+    case SPH_S_RIGID_MODE: *out = h->rigid ? (double)h->rigid_mode : 0.0; return SPH_OK;
     case SPH_S_VERLET_BUILDS: { int rc = read_scalars(h); if (rc) return rc; *out = (double)h->ds_host->verlet_builds; return SPH_OK; }      // kr_split is settled by the first list build
     case SPH_P_DENSITY_THRESHOLD: *out = h->p.density_threshold; return SPH_OK;
     case SPH_P_MIN_ITERATION_DENSITY: *out = h->p.min_iteration_density; return SPH_OK;
@@ -1096,6 +1148,10 @@ int sph_get_scalar(SphHandle *h, int which, double *out)
             else if (which < SPH_S_RIGID_MASS) *out = (double)h->r_vel[which - SPH_S_RIGID_VEL];
             else if (which == SPH_S_RIGID_MASS) *out = (double)h->rs_mass;
             else *out = (double)h->inertia_inv[which - SPH_S_RIGID_INERTIA_INV];
+            return SPH_OK;
+        }
+        if (h->rigid && which >= SPH_S_RIGID_ACC && which < SPH_S_RIGID_ALPHA + 3) {
+            *out = which < SPH_S_RIGID_ALPHA ? (double)h->r_acc[which - SPH_S_RIGID_ACC] : (double)h->r_alpha[which - SPH_S_RIGID_ALPHA];
             return SPH_OK;
         }
         return fail(h, SPH_E_INVALID, "unknown scalar %d", which);

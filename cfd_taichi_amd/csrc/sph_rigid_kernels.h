@@ -304,7 +304,50 @@ __global__ __launch_bounds__(kBlock) void k_rigid_translate(int n, float4 *__res
     if (force_to_zero) { force_to_zero[3 * i] = 0.f; force_to_zero[3 * i + 1] = 0.f; force_to_zero[3 * i + 2] = 0.f; }
 }
 
-// max_rigid_vel = max_i ( |vel| + |omega x (x_i - c)| )         dfsph_solver.py:104-110: partial maxima per workgroup in part[], the
+// A scripted body's step (SPH_RIGID_SCRIPTED) in one launch over the samples (i < nr) and the vertices behind them: k_rigid_rotate, then
+// k_rigid_translate with its force reset, per element the same operations in the same order -- (R (p - c) + c) + disp, every sum rounded on
+// its own (no contraction in this build) -- so a scripted body fed a dynamic body's motion retraces it bit for bit.
+__global__ __launch_bounds__(kBlock) void k_rigid_move(int nr, int nv, float4 *__restrict__ RPos, float *__restrict__ vert,
+                                                       float *__restrict__ force, Mat3 R, RigidBodyState st, float dx, float dy, float dz)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= nr + nv) return;
+    const bool sample = i < nr;
+    const int v = i - nr;
+    float x, y, z, w = 0.f;
+    if (sample) { float4 p = RPos[i]; x = p.x; y = p.y; z = p.z; w = p.w; }
+    else { x = vert[3 * v]; y = vert[3 * v + 1]; z = vert[3 * v + 2]; }
+    float rx = x - st.c[0], ry = y - st.c[1], rz = z - st.c[2];
+    float ox = ((R.m[0] * rx + R.m[1] * ry) + R.m[2] * rz) + st.c[0];
+    float oy = ((R.m[3] * rx + R.m[4] * ry) + R.m[5] * rz) + st.c[1];
+    float oz = ((R.m[6] * rx + R.m[7] * ry) + R.m[8] * rz) + st.c[2];
+    ox += dx; oy += dy; oz += dz;
+    if (sample) {
+        RPos[i] = make_float4(ox, oy, oz, w);
+        force[3 * i] = 0.f; force[3 * i + 1] = 0.f; force[3 * i + 2] = 0.f;
+    } else { vert[3 * v] = ox; vert[3 * v + 1] = oy; vert[3 * v + 2] = oz; }
+}
+
+// Second stage of k_rigid_torque_force for the bodies whose step needs no sum on the host (scripted, fixed): the nparts partials combined on
+// the device into load[0..2] = force, load[3..5] = torque, which sph_rigid_get_load copies out on demand.  One thread per component adds its
+// partials one after the other in index order, in f64 -- the very sequence read_rigid_reduce runs on the host for a dynamic body, so the load
+// of a handle does not depend on its mode (a tree over the partials would round differently).  At most kRigidParts = 64 additions.
+// force_to_zero (a fixed body, which has no move launch to do it): the samples' forces are reset here, n3 floats over all workgroups.
+__global__ __launch_bounds__(kBlock) void k_rigid_load(int nparts, const RigidReduce *__restrict__ part, double *__restrict__ load,
+                                                       float *__restrict__ force_to_zero, int n3)
+{
+    if (blockIdx.x == 0 && threadIdx.x < 6) {
+        const int a = threadIdx.x % 3;
+        const bool f = threadIdx.x < 3;
+        double s = f ? part[0].force[a] : part[0].torque[a];
+        for (int k = 1; k < nparts; ++k) s += f ? part[k].force[a] : part[k].torque[a];
+        load[threadIdx.x] = s;
+    }
+    if (force_to_zero)
+        for (int i = blockIdx.x * kBlock + threadIdx.x; i < n3; i += gridDim.x * kBlock) force_to_zero[i] = 0.f;
+}
+
+// max_rigid_vel = max_i ( |vel| + |omega x (x_i - c)| )        dfsph_solver.py:104-110: partial maxima per workgroup in part[], the
 // second launch (one workgroup, nparts > 0) takes their maximum into ds->rigid_vmax.  An inactive body has a NaN centroid (zero volumes,
 // 0 / 0): every term is NaN and fmaxf drops it, as the oracle's `>` does, so the maximum stays 0 (test_rigid_modes_gpu.py).  What Taichi's
 // atomic_max does with a NaN in the reference itself is a question of Taichi's semantics, not pinned here.

@@ -22,6 +22,33 @@ class rigid_solver:
         self.simulate_cnt = ScalarField(lambda: self.simulate_cnt_host)
         self.omega = ScalarField(lambda: np.asarray(self.ps._sim.rigid_scalars()["omega"], dtype=np.float32))
         self.mass = ScalarField(lambda: self.ps._sim.rigid_scalars()["mass"])
+        # not the reference's: `"motion": {"mode": "fixed"}` or `{"mode": "scripted", "vel": [...], "omega": [...]}` in the solid block makes the
+        # body an obstacle or a paddle (an absent key: the reference's dynamic body)
+        motion = solid_config.get("motion")
+        if motion:
+            if motion.get("mode", "dynamic") not in nat.RIGID_MODES:
+                raise ValueError("solid.motion.mode must be one of %s, got %r" % (sorted(nat.RIGID_MODES), motion.get("mode")))
+            if "vel" in motion or "omega" in motion:
+                self.set_motion(motion.get("vel", [0.0, 0.0, 0.0]), motion.get("omega", [0.0, 0.0, 0.0]), motion.get("acc"), motion.get("alpha"))
+            self.mode = motion.get("mode", "dynamic")
+
+    @property
+    def mode(self):
+        """"dynamic" (rigid_solver.step as in the reference), "scripted" (the body follows set_motion) or "fixed"; writable between steps"""
+        number = self.ps._sim.rigid_scalars(motion=True)["mode"]
+        return [name for name, value in nat.RIGID_MODES.items() if value == number][0]
+
+    @mode.setter
+    def mode(self, value):
+        self.ps._sim.rigid_set_mode(value)
+
+    def set_motion(self, vel, omega, acc=None, alpha=None):
+        """the velocity and angular velocity a scripted body has from the next step() on (acc, alpha: what the fluid extrapolates them with)"""
+        self.ps._sim.rigid_set_motion(vel, omega, acc, alpha)
+
+    def load(self):
+        """(force, torque about the centroid) of the fluid on the body, as the last step() summed them"""
+        return self.ps._sim.rigid_load()
 
     def step(self):
         self.simulate_cnt_host += 1

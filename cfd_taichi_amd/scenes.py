@@ -67,6 +67,11 @@ def _with_solid(cfg, mesh, scale, pos_offset, attitude_offset, rho_0, active=Tru
     return cfg
 
 
+def _with_motion(cfg, motion):
+    cfg["solid"]["motion"] = dict(motion)
+    return cfg
+
+
 # relative to the package directory (mesh._resolve); the reference's configs say ./obj/cube1.stl relative to its checkout
 _CUBE = "assets/cube1.stl"
 
@@ -96,6 +101,10 @@ SCENES.update({
     # density loop runs into its cap there): a coupled solve that converges, for a throughput datum that means something
     "dfsph_rigid_2m_clear": lambda: _with_solid(_scene("dfsph", 1e-3, [16.0, 12.0, 8.0], [5.0, 6.6, 7.6]),
                                                 _CUBE, 3.3, [8.75, 2.97, 2.31], [0.0, 0.0, 90.0], 5000),
+    # not the reference's: the 30 k dam break against a FIXED cube1 block standing in the flow 0.9 m down the tank (`"motion": {"mode": "fixed"}`,
+    # rigid_solver.py of this package): the obstacle never moves, rigid_solver.load() reads the force and torque of the water on it
+    "dam_obstacle_dfsph": lambda: _with_motion(_with_solid(_scene("dfsph", 2.5e-4, [5.0, 3.0, 1.5], [1.0, 2.8, 1.3]),
+                                                           _CUBE, 0.6, [2.0, 0.05, 0.45], [0.0, 0.0, 0.0], 2000), {"mode": "fixed"}),
 })
 
 

@@ -262,6 +262,17 @@ class SlabSimulation:
                 raise self.comm.error
             raise
 
+    # the body's mode, motion and load: plain local calls -- every rank makes the same ones between the same steps (the body is replicated)
+    def set_rigid_mode(self, mode):
+        self.sim.rigid_set_mode(mode)
+
+    def set_rigid_motion(self, vel, omega, acc=None, alpha=None):
+        self.sim.rigid_set_motion(vel, omega, acc, alpha)
+
+    def rigid_load(self):
+        """(force, torque) over the WHOLE body as the last rigid_step summed them: the same bits on every rank"""
+        return self.sim.rigid_load()
+
     def owned(self, field):
         return self.sim.download_owned(field)
 

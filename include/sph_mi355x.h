@@ -182,6 +182,9 @@ typedef struct SphRigid {
 #define SPH_S_RIGID_MASS 19       /* rigid_solver.mass[None] */
 #define SPH_S_RIGID_INERTIA_INV 20 /* +0..8: ps.rigid_inertia_tensor_inv[None], row major */
 #define SPH_S_RIGID_ACTIVE 32      /* ps.active_rigid[None] as it stands (sph_rigid_set_active writes it); 0 on a handle without a body */
+#define SPH_S_RIGID_ACC 33         /* +0,1,2: rigid_particles.acc (uniform over the body): what the sweeps add to the body's velocity as acc * dt */
+#define SPH_S_RIGID_ALPHA 36       /* +0,1,2: rigid_particles.alpha (uniform over the body) */
+#define SPH_S_RIGID_MODE 39        /* SPH_RIGID_DYNAMIC / _SCRIPTED / _FIXED as sph_rigid_set_mode left it; 0 on a handle without a body */
 #define SPH_S_VERLET_BUILDS 31    /* diagnostics: list builds so far on a Verlet handle (wcsph under the relaxed arithmetic: the lists carry a skin and are rebuilt on demand) */
 #define SPH_S_ARITH_RELAXED 30    /* diagnostics: 1 if any pair sweep of this handle's solver runs the tolerance-grade kernels (SphConfig.arith asked AND the handle qualifies) */
 
@@ -231,6 +234,29 @@ int sph_rigid_set_active(SphHandle *h, int active);
  * released, sph_step_* and sph_rigid_step return SPH_E_STATE until this call has run -- the reference would step on with NaN.
  * SPH_E_STATE: no body; a slab handle. */
 int sph_rigid_init_data(SphHandle *h);
+
+/* What sph_rigid_step does with the body (the reference has the first mode only).  The mode governs sph_rigid_step and nothing else: binning,
+ * coupling, fs_couple, sph_rigid_set_active / sph_rigid_init_data, pcisph's delta and the fluid sweeps are as before -- the sweeps go on reading the
+ * body's motion (vel + acc dt, omega + alpha dt, the centroid) and summing the fluid's force on every sample.  In every mode a step counts
+ * (simulate_cnt), takes dt as before (dfsph: ps.delta_time), forms the f64 sums of the samples' forces and torques and zeroes the forces. */
+#define SPH_RIGID_DYNAMIC 0   /* rigid_solver.step: the body is moved by the forces, the wall test and the wall impulse (the default) */
+#define SPH_RIGID_SCRIPTED 1  /* the body is moved by the motion of sph_rigid_set_motion: omega = the given omega, attitude = omega dt, the samples, the
+                               * vertices and the inverse inertia are rotated about the centroid as rigid_solver.rotation does (always, also by
+                               * zero angles), then acc, vel = the given ones, and samples, vertices and centroid += vel dt.  No wall test, no impulse:
+                               * a step whose sphere (centroid + vel dt, the largest sample distance from the centroid when the body's data were last
+                               * derived, plus 0.1 %) does not lie inside the cell grid returns SPH_E_INVALID before anything is launched or changed
+                               * (a conservative bound).  No read-back (dfsph: the one of ps.delta_time) */
+#define SPH_RIGID_FIXED 2     /* the body never moves: positions, vertices, centroid and inverse inertia stay bit for bit; vel, acc, omega, alpha = 0 */
+/* between steps; the body goes on from its current vel and omega when the mode returns to DYNAMIC.  SPH_E_STATE: no body; SPH_E_INVALID: an
+ * unknown mode.  On slab handles every rank makes the same calls between the same steps (as with sph_set_scalar). */
+int sph_rigid_set_mode(SphHandle *h, int mode);
+/* the motion SPH_RIGID_SCRIPTED follows, kept until it is replaced; allowed in every mode.  acc / alpha may be NULL (zeros): they are what the
+ * fluid sweeps extrapolate the body's velocity with during the NEXT solver step.  SPH_E_INVALID (handle unchanged): a value that is not finite,
+ * vel or omega NULL; SPH_E_STATE: no body. */
+int sph_rigid_set_motion(SphHandle *h, const float vel[3], const float omega[3], const float acc[3], const float alpha[3]);
+/* the fluid's load on the body as the last sph_rigid_step summed it over the samples' forces, in f64: force, and torque about the centroid
+ * before that step's move.  All three modes, identical on every rank of a slab run.  SPH_E_STATE: no body, or no sph_rigid_step yet. */
+int sph_rigid_get_load(SphHandle *h, double force[3], double torque[3]);
 void sph_destroy(SphHandle *h);
 int sph_get_sizes(SphHandle *h, SphSizes *out);
 const char *sph_last_error(SphHandle *h);
