@@ -91,7 +91,7 @@ class ParticleSystem:
     # ---- native handle management -------------------------------------------------------------
     def _make_sim(self, kind):
         cfg = nat.config_from_dict(self.config, solver_name=kind, **self._native_opts)
-        self._sim = nat.Simulation(cfg, rigid=self._rigid_input)
+        self._sim = nat.Simulation(cfg, rigid=self._rigid_input, config=self.config)   # (config: scene.gravity as a vector, scene.forcing)
         self._solver_kind = kind
 
     def _attach_solver(self, kind, arith=None):

@@ -30,6 +30,7 @@ S_ARITH_RELAXED = 30
 S_VERLET_BUILDS = 31
 S_RIGID_ACTIVE = 32
 S_RIGID_ACC, S_RIGID_ALPHA, S_RIGID_MODE = 33, 36, 39
+S_TIME, S_ACCEL, S_GRAVITY_VEC = 40, 41, 44                  # the handle's clock (f64), its acceleration vector (+0, 1, 2) and the base vector g
 RIGID_DYNAMIC, RIGID_SCRIPTED, RIGID_FIXED = 0, 1, 2          # sph_rigid_set_mode
 RIGID_MODES = {"dynamic": RIGID_DYNAMIC, "scripted": RIGID_SCRIPTED, "fixed": RIGID_FIXED}
 # `solver.<attribute> = value` (include/sph_mi355x.h SPH_P_*): name of the reference's attribute -> id
@@ -46,7 +47,7 @@ EXPORTS = [
     "sph_profile_kernel_name", "sph_profile_get", "sph_selftest_math", "sph_selftest_wave", "sph_selftest_stage", "sph_selftest_walk", "sph_tune_time",
     "sph_set_comm", "sph_rccl_unique_id", "sph_rccl_attach", "sph_rccl_selftest", "sph_get_stream", "sph_plan_slabs", "sph_replan_slabs", "sph_slab_set_overlap", "sph_slab_info", "sph_comm_stats", "sph_download_local", "sph_download_ids",
     "sph_create_rigid", "sph_rigid_step", "sph_rigid_set_active", "sph_rigid_init_data", "sph_slab_set_state",
-    "sph_rigid_set_mode", "sph_rigid_set_motion", "sph_rigid_get_load",
+    "sph_rigid_set_mode", "sph_rigid_set_motion", "sph_rigid_get_load", "sph_set_gravity", "sph_set_forcing",
 ]
 
 
@@ -177,7 +178,7 @@ CORE_EXPORTS = [
 # entry points added without a change of SPH_ABI_VERSION (no struct grew, no signature changed): bound where the library has them, and a call on a
 # library without them raises SphError(SPH_E_STATE)
 OPTIONAL_EXPORTS = ["sph_rigid_set_active", "sph_rigid_init_data", "sph_selftest_stage", "sph_selftest_walk", "sph_slab_set_state",
-                    "sph_rigid_set_mode", "sph_rigid_set_motion", "sph_rigid_get_load"]
+                    "sph_rigid_set_mode", "sph_rigid_set_motion", "sph_rigid_get_load", "sph_set_gravity", "sph_set_forcing"]
 
 
 def _bind_core(lib):
@@ -221,6 +222,10 @@ def _bind_core(lib):
         lib.sph_rigid_set_motion.argtypes = [vp, vp, vp, vp, vp]
     if hasattr(lib, "sph_rigid_get_load"):
         lib.sph_rigid_get_load.argtypes = [vp, vp, vp]
+    if hasattr(lib, "sph_set_gravity"):
+        lib.sph_set_gravity.argtypes = [vp, vp]
+    if hasattr(lib, "sph_set_forcing"):
+        lib.sph_set_forcing.argtypes = [vp, vp, vp, vp]
     return lib
 
 
@@ -301,7 +306,7 @@ def config_from_dict(config, solver_name=None, device=0, max_neighbors=0, max_wa
     c.box_min[:] = [float(v) for v in scene["box_min"]]
     c.box_max[:] = [float(v) for v in scene["box_max"]]
     c.particle_radius = float(scene["particle_radius"])
-    c.gravity = float(scene["gravity"])
+    c.gravity = gravity_scalar(scene["gravity"])
     c.delta_time = float(sol["delta_time"])
     c.start_pos[:] = [float(v) for v in fluid["start_pos"]]
     c.water_size[:] = [float(v) for v in fluid["water_size"]]
@@ -320,6 +325,51 @@ def config_from_dict(config, solver_name=None, device=0, max_neighbors=0, max_wa
     c.slab_ghost_layers = int(slab_ghost_layers)
     c.slab_overlap = int(slab_overlap)
     return c
+
+
+def _vec3(value, what):
+    """three finite numbers -> a list of three floats; anything else is refused"""
+    import math
+    if isinstance(value, (str, bytes)) or not hasattr(value, "__len__") or len(value) != 3:
+        raise ValueError("%s must be a list of three numbers, got %r" % (what, value))
+    out = []
+    for v in value:
+        if isinstance(v, (bool, str, bytes)) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(float(v)):
+            raise ValueError("%s must be a list of three finite numbers, got %r" % (what, value))
+        out.append(float(v))
+    return out
+
+
+def gravity_scalar(gravity):
+    """SphConfig.gravity of `scene.gravity`: the number itself, or for a list of three (the vector g) its downward part -g[1], so that
+    [0, -G, 0] creates the handle G creates; the vector is then applied by gravity_calls()."""
+    return float(gravity) if not hasattr(gravity, "__len__") else -_vec3(gravity, "scene.gravity")[1]
+
+
+def gravity_calls(config):
+    """What a config asks of a new handle, as the calls that will be made: [("set_gravity", [gx, gy, gz])] for a `scene.gravity` that is a list of
+    three, [("set_forcing", amplitude, omega, phase)] for a block `scene.forcing` = {"amplitude": [...], "omega": [...], "phase": [...]}
+    (omega / phase optional: None).  A plain number and no block: no call, the handle keeps gravity * (0, -1, 0).  Pure Python; a malformed
+    list raises ValueError."""
+    scene = config["scene"]
+    calls = []
+    g = scene.get("gravity")
+    if hasattr(g, "__len__"):
+        calls.append(("set_gravity", _vec3(g, "scene.gravity")))
+    frc = scene.get("forcing")
+    if frc is not None:
+        if not isinstance(frc, dict) or "amplitude" not in frc or set(frc) - {"amplitude", "omega", "phase"}:
+            raise ValueError("scene.forcing must be {\"amplitude\": [...], \"omega\": [...], \"phase\": [...]}, got %r" % (frc,))
+        calls.append(("set_forcing", _vec3(frc["amplitude"], "scene.forcing.amplitude"),
+                      None if frc.get("omega") is None else _vec3(frc["omega"], "scene.forcing.omega"),
+                      None if frc.get("phase") is None else _vec3(frc["phase"], "scene.forcing.phase")))
+    return calls
+
+
+def apply_gravity_calls(target, config):
+    """make gravity_calls(config) on a Simulation, a SlabSimulation or a solver mirror, right after creation"""
+    for name, *args in gravity_calls(config):
+        getattr(target, name)(*args)
 
 
 def arith_id(arith):
@@ -370,9 +420,11 @@ def replan_slabs(column_histogram, old_cuts, ghost_layers=0):
 class Simulation:
     """Owns one SphHandle: device buffers of one ParticleSystem + one fluid solver."""
 
-    def __init__(self, cfg, rigid=None, lib=None):
+    def __init__(self, cfg, rigid=None, lib=None, config=None):
         """rigid: dict(points, vertices, rho_0, pos_offset, attitude_offset (degrees), active) from mesh.rigid_from_config;
-        lib: another implementation of the ABI's per-step path (bind_core), default libsph_mi355x.so"""
+        lib: another implementation of the ABI's per-step path (bind_core), default libsph_mi355x.so;
+        config: the config dict cfg was flattened from: its `scene.gravity` list and `scene.forcing` block (gravity_calls) are applied right
+        after creation"""
         self._lib = lib or load()
         self.cfg = cfg
         handle = ctypes.c_void_p()
@@ -401,6 +453,8 @@ class Simulation:
         self.n_cells = sizes.n_cells
         self.max_neighbors, self.max_wall_neighbors = sizes.max_neighbors, sizes.max_wall_neighbors
         self.last_stats = SphStepStats()
+        if config is not None:
+            apply_gravity_calls(self, config)
 
     def _check(self, rc):
         if rc != SPH_OK:
@@ -523,6 +577,31 @@ class Simulation:
     def set_dt(self, value):
         """solver.delta_time[None] = value"""
         self._check(self._lib.sph_set_scalar(self._h, S_DELTA_TIME, float(value)))
+
+    def set_gravity(self, vec):
+        """the base vector g of the handle's acceleration (sph_set_gravity), between steps: three finite numbers, rounded to f32"""
+        g = np.ascontiguousarray(vec, dtype=np.float32).reshape(3)
+        self._check(self._optional("sph_set_gravity")(self._h, g.ctypes.data))
+
+    def set_forcing(self, amp, omega=None, phase=None):
+        """harmonic forcing per axis, a_k = f32(g_k + amp_k sin(omega_k t + phase_k)) in f64 (sph_set_forcing), between steps; amp None switches it
+        off, omega / phase None are zeros"""
+        arrs = [None if v is None else np.ascontiguousarray(v, dtype=np.float64).reshape(3) for v in (amp, omega, phase)]
+        self._check(self._optional("sph_set_forcing")(self._h, *[None if a is None else a.ctypes.data for a in arrs]))
+
+    def time(self):
+        """the handle's simulated time: the f64 sum of the delta_time of every solver step so far"""
+        return self.scalar(S_TIME)
+
+    def set_time(self, value):
+        self._check(self._lib.sph_set_scalar(self._h, S_TIME, float(value)))
+
+    def accel(self):
+        """the acceleration vector (three f32) as the last solver step used it, or as the next will if none has run since a set call"""
+        return np.array([self.scalar(S_ACCEL + k) for k in range(3)], dtype=np.float32)
+
+    def gravity_vec(self):
+        return np.array([self.scalar(S_GRAVITY_VEC + k) for k in range(3)], dtype=np.float32)
 
     def set_param(self, name, value):
         """solver.<name> = value for the attributes of SOLVER_PARAMS (dfsph_solver.py:21-29, solver_base.py:23-26, wcsph_solver.py:17-20)."""

@@ -51,6 +51,11 @@ struct Consts {
     int S;                // slots in cell_start[] (>= C: tiles pad each axis to a multiple of the tile edge); slot S = "outside the grid"
     int tbits, tnx, tnxz; // tiles of 2^tbits cells per axis; tile strides: tiles along x, tiles along x times tiles along z
     const int *tile_rank; // position of every tile along the Morton curve of the tile coordinates
+    // the handle's acceleration vector and clock in device memory (DevScalars.frc.accel, DevScalars.sim_time), for the kernels that take no
+    // DevScalars pointer: a step reads accel[0..2] where the reference writes gravity * (0, -1, 0); the fixed-dt solvers' once-per-step
+    // kernels add their dt to *clock (clock_advance)
+    const float *accel;
+    double *clock;
     int stage_cap;        // LDS staging: particles a workgroup may stage (see the plan in k_build_nl); 0 = staging off
     int nl16;             // fluid lists of staged workgroups hold 16-bit local indices, eight per 16-byte group (NlWriter)
     int kr_split;         // dfsph sweeps hand k / rho to the next sweep in a 4-byte array instead of a (pos, k / rho) float4 (k_correct)
@@ -109,6 +114,16 @@ struct DevScalars {
     // shards into max_nbrs / max_wall_nbrs after a read-back.  (Thousands of waves checking ONE word cost 10 us of a 30 k-particle
     // list build: same-address traffic serialises even when it is only loads.)
     int nbr_shard[64], wall_shard[64];
+    // The handle's simulated time and acceleration vector.  sim_time: 0 at creation, += (double)dt once per solver step, by
+    // one thread of a kernel the step launches anyway (clock_advance; dfsph: apply_dt_body, behind the CFL rule).  frc.accel is what every sweep,
+    // the body's host step and every slab rank read for gravity: frc.g itself while no forcing is set (written by the host, no arithmetic), else
+    // (float)((double)g_k + amp_k sin(omega_k t + phase_k)) per axis with amp_k != 0, formed by k_accel_eval at the head of the step
+    double sim_time;
+    struct Forcing {
+        double amp[3], omega[3], phase[3];
+        float g[3], accel[3];
+        int on, pad;
+    } frc;
     // dfsph loop parameters: the attributes dfsph_solver.py:21-25 sets and its Python-scope loops read at every step (:225, :400).  Written by
     // sph_create (the reference's values) and sph_set_scalar(SPH_P_*); k_ctrl_begin leaves them alone
     double p_dens_thr;   // density_threshold * rho_0 * 0.01, folded in f64 like the Python expression                 :225
@@ -116,6 +131,9 @@ struct DevScalars {
     int p_min_dens, p_min_div, p_max_div, p_pad;       // min_iteration_density, min / max_iteration_density_divergence
 };
 constexpr int kNoteShards = 64;
+
+// one thread per step: the step's dt joins the handle's clock (the same f64 additions in the same order as a host sum of the read-back dt's)
+__device__ __forceinline__ void clock_advance(double *clock, float dt) { *clock += (double)dt; }
 
 enum { GATE_NONE = 0, GATE_DIV = 1, GATE_DENS = 2, GATE_DENS_D7 = 3, GATE_HIST0 = 16, GATE_HIST1 = 17 };
 __device__ __forceinline__ bool gate_closed(const DevScalars *ds, int gate)

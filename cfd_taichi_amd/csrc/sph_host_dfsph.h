@@ -271,6 +271,7 @@ int step_wcsph_once(SphHandle *h)
     int rc;
     h->simulate_cnt += 1;                                   // solver_base.py:137
     h->comm_stat[6] += 1;
+    step_head(h);                                           // the step's acceleration vector, if it is forced
     if ((rc = stage_sort_and_lists(h))) return rc;          // :139-141
     if (h->verlet) {                                        // the relaxed arithmetic: two kernels over the Verlet lists (sph_relaxed_kernels.h)
         const Consts &cv = h->c;
@@ -841,6 +842,7 @@ int step_dfsph_once(SphHandle *h, SphStepStats *st)
     memset(st, 0, sizeof(*st));
     h->simulate_cnt += 1;                                   // solver_base.py:137
     h->comm_stat[6] += 1;
+    step_head(h);                                           // the step's acceleration vector, if it is forced
     if ((rc = stage_sort_and_lists(h))) return rc;          // :139-141 (reset() is the no-op override, dfsph_solver.py:418-421)
     if ((rc = stage_density(h))) return rc;                 // initialize(): dfsph_solver.py:423-426
     const bool host_loops = h->slab && !slab_async(h);      // a transport without allreduce_stream

@@ -45,6 +45,7 @@ int step_pbf_once(SphHandle *h)
     int rc;
     h->simulate_cnt += 1;                                   // solver_base.py:137
     h->comm_stat[6] += 1;
+    step_head(h);                                           // the step's acceleration vector, if it is forced
     if ((rc = stage_sort_and_lists(h))) return rc;          // :139-141
     const Consts &c = h->c;
     const PbfConsts k = pbf_consts(h);
@@ -138,6 +139,7 @@ int step_pcisph_once(SphHandle *h, SphStepStats *st)
     memset(st, 0, sizeof(*st));
     h->simulate_cnt += 1;                                   // solver_base.py:137
     h->comm_stat[6] += 1;
+    step_head(h);                                           // the step's acceleration vector, if it is forced
     if ((rc = require_async_slab(h))) return rc;
     if ((rc = stage_sort_and_lists(h))) return rc;          // :139-141
     if ((rc = stage_density(h))) return rc;                 // compute_all_rho :239; P = (pos, rho)
@@ -149,7 +151,7 @@ int step_pcisph_once(SphHandle *h, SphStepStats *st)
     const RigidView rv = rg ? rigid_view(h) : RigidView();
     float4 *EF = h->X[0], *PF = h->X[1], *PP = h->X[2], *PB[2] = {h->X[3], h->X[4]};
     const int cap = 80;                                     // max_iteration :21
-    hipLaunchKernelGGL(k_pressure_ctrl_begin, dim3(1), dim3(1), 0, s, h->ds, cap);
+    hipLaunchKernelGGL(k_pressure_ctrl_begin, dim3(1), dim3(1), 0, s, h->ds, cap, dt);
     {
         ProfScope ps(h, K_P_EXT);                           // compute_ext_force, reset(), first predict_vel_pos
         SPH_LAUNCH_RMX0(k_pci_ext, rg, sweep_mode(h), relaxed_pressure(h), c.n, sweep_lds(h, StageF4Src::kBytes), s, c, dt, h->P[h->pcur], h->V[h->vcur], h->nl, h->cnt, EF, PF,
@@ -218,6 +220,7 @@ int step_iisph_once(SphHandle *h, SphStepStats *st)
     memset(st, 0, sizeof(*st));
     h->simulate_cnt += 1;
     h->comm_stat[6] += 1;
+    step_head(h);                                           // the step's acceleration vector, if it is forced
     if ((rc = require_async_slab(h))) return rc;
     if ((rc = stage_sort_and_lists(h))) return rc;
     if ((rc = stage_density(h))) return rc;                 // predict_advection :38; P = (pos, rho)
@@ -229,7 +232,7 @@ int step_iisph_once(SphHandle *h, SphStepStats *st)
     const RigidView rv = rg ? rigid_view(h) : RigidView();
     float4 *DII = h->X[0], *DIJ = h->X[1], *FP = h->X[2], *PB[2] = {h->X[3], h->X[4]}, *VA = h->VA[0];
     const int cap = 180;                                    // max_iter_cnt :27
-    hipLaunchKernelGGL(k_pressure_ctrl_begin, dim3(1), dim3(1), 0, s, h->ds, cap);
+    hipLaunchKernelGGL(k_pressure_ctrl_begin, dim3(1), dim3(1), 0, s, h->ds, cap, dt);
     {
         ProfScope ps(h, K_I_ADVECT);                        // :43-56
         SPH_LAUNCH_RMX0(k_ii_advect, rg, sweep_mode(h), relaxed_pressure(h), c.n, sweep_lds(h, StageF4Src::kBytes), s, c, dt, h->P[h->pcur], h->V[h->vcur], h->WP, h->nl, h->nlb,

@@ -377,6 +377,8 @@ int rigid_step(SphHandle *h, float dt_next)
     ProfScope ps(h, K_RIGID);
     // compute_attitude :118-128 (+ the force sum of kinematic :35-38: the forces do not change in between)
     hipLaunchKernelGGL(k_rigid_torque_force, rigid_parts_grid(h), b, 0, s, h->Nr, h->RPos, h->rforce, rigid_state(h, nullptr, nullptr), h->rred);
+    // under forcing the vector of the solver step before is the device's (k_accel_eval): it rides in the read-back below, the same bits the sweeps saw
+    if (h->frc.on) HIP_TRY(h, hipMemcpyAsync(h->frc.accel, h->ds->frc.accel, sizeof(h->frc.accel), hipMemcpyDeviceToHost, s));
     if ((rc = read_rigid_reduce(h))) return rc;
     for (int a = 0; a < 3; ++a) { h->rload_host[a] = h->rred_host->force[a]; h->rload_host[3 + a] = h->rred_host->torque[a]; }
     h->rload_at = 1;
@@ -407,7 +409,7 @@ int rigid_step(SphHandle *h, float dt_next)
     float vel[3], disp[3], ori[3];
     {
         const float force[3] = {(float)h->rred_host->force[0], (float)h->rred_host->force[1], (float)h->rred_host->force[2]};
-        const float g[3] = {h->c.gravity * 0.0f, h->c.gravity * -1.0f, h->c.gravity * 0.0f};
+        const float *g = h->frc.accel;                                  // the handle's vector, as the solver step before used it
         for (int a = 0; a < 3; ++a) {
             h->r_acc[a] = force[a] / h->rs_mass + g[a];                 // :40-41
             vel[a] = h->r_acc[a] * dt + h->r_vel[a];                    // :43

@@ -774,6 +774,8 @@ int alloc_device(SphHandle *h, const HostScene &sc)
     if ((rc = dalloc(h, &h->staging, stg))) return rc;
 
     if ((rc = dcommit(h))) return rc;
+    h->c.accel = h->ds->frc.accel;          // (addresses only: device memory)
+    h->c.clock = &h->ds->sim_time;
     if (c.order == CELL_ORDER_TILED) {
         HIP_TRY(h, hipMemcpyAsync(h->tile_rank, tile_rank.data(), sizeof(int) * tile_rank.size(), hipMemcpyHostToDevice, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -802,6 +804,12 @@ int alloc_device(SphHandle *h, const HostScene &sc)
     h->ds_host->ps_dt = 0.f;                                         // ParticleSystem.py:37
     h->ds_host->moved = 1;                                           // Verlet handles: the first step builds the lists
     loop_params(h, h->ds_host);
+    // the acceleration vector: the three floats the reference forms, gravity * (0, -1, 0), in f32 as its kernels do   solver_base.py:131-133
+    h->frc = DevScalars::Forcing{};
+    h->frc.g[0] = h->c.gravity * 0.0f; h->frc.g[1] = h->c.gravity * -1.0f; h->frc.g[2] = h->c.gravity * 0.0f;
+    for (int a = 0; a < 3; ++a) h->frc.accel[a] = h->frc.g[a];
+    h->ds_host->frc = h->frc;
+    h->ds_host->sim_time = 0.0;
     HIP_TRY(h, hipMemcpyAsync(h->ds, h->ds_host, sizeof(DevScalars), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->dt_wcsph = (float)h->cfg.delta_time;
@@ -848,6 +856,33 @@ int read_scalars(SphHandle *h)
     HIP_TRY(h, hipMemcpyAsync(h->ds_host, h->ds, sizeof(DevScalars), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     fold_list_maxima(h);
+    return SPH_OK;
+}
+
+// Head of every solver step.  While no forcing is set there is nothing to do: DevScalars.frc.accel holds g.  Under forcing one thread forms the
+// step's vector from the clock as it stands (k_accel_eval) before the first sweep; it is held through the step and the body step behind it.
+// Enqueued like any launch: no host wait, and a node of the captured wcsph step pair like the others.
+inline void step_head(SphHandle *h)
+{
+    if (!h->frc.on) return;
+    ProfScope ps(h, K_ACCEL);
+    hipLaunchKernelGGL(k_accel_eval, dim3(1), dim3(1), 0, h->stream, h->ds);
+}
+
+// sph_set_gravity / sph_set_forcing / a written SPH_S_TIME, between steps: h->frc (validated by the caller) goes to the device, the vector is
+// formed at once for the current clock -- by the kernel the steps use, so the bits are the step's -- and read back.  The captured wcsph step pairs
+// hold or lack the k_accel_eval node: they are dropped (the vector itself is device memory and would reach a replay anyway).
+int forcing_commit(SphHandle *h)
+{
+    for (int a = 0; a < 3; ++a) h->frc.accel[a] = h->frc.g[a];
+    HIP_TRY(h, hipMemcpyAsync(&h->ds->frc, &h->frc, sizeof(h->frc), hipMemcpyHostToDevice, h->stream));
+    if (h->frc.on) {
+        hipLaunchKernelGGL(k_accel_eval, dim3(1), dim3(1), 0, h->stream, h->ds);
+        HIP_TRY(h, hipMemcpyAsync(h->frc.accel, h->ds->frc.accel, sizeof(h->frc.accel), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (int k = 0; k < 8; ++k)
+        if (h->wcsph_graph[k]) { (void)hipGraphExecDestroy(h->wcsph_graph[k]); h->wcsph_graph[k] = nullptr; }
     return SPH_OK;
 }
 

@@ -535,8 +535,11 @@ int slab_state_commit(SphHandle *h, const float *pos, const float *vel, const fl
     if ((rc = read_scalars(h))) return rc;
     if (placed != own) return fail(h, SPH_E_STATE, "internal: sph_slab_set_state placed %d particles on slab %d, the histogram counted %d", placed, h->slab_rank, own);
     const float dt = h->ds_host->dt, dt2 = h->ds_host->dt2, ps_dt = h->ds_host->ps_dt;
+    const double sim_time = h->ds_host->sim_time;              // the clock and the acceleration vector stay
+    const DevScalars::Forcing frc = h->ds_host->frc;
     memset(h->ds_host, 0, sizeof(DevScalars));
     h->ds_host->dt = dt; h->ds_host->dt2 = dt2; h->ds_host->ps_dt = ps_dt;
+    h->ds_host->sim_time = sim_time; h->ds_host->frc = frc;
     h->ds_host->moved = 1;
     loop_params(h, h->ds_host);
     HIP_TRY(h, hipMemcpyAsync(h->ds, h->ds_host, sizeof(DevScalars), hipMemcpyHostToDevice, s));

@@ -1743,6 +1743,19 @@ __global__ void k_ctrl_begin(DevScalars *__restrict__ ds, int dens_cap)
     ctrl_begin_body(ds, dens_cap);
 }
 
+// The acceleration vector of the coming step under harmonic forcing (launched only while frc.on): one thread, from the clock as it stands, in f64
+// with one rounding to f32; an axis without amplitude keeps g's bits.  The only place the vector is formed: sph_set_gravity / sph_set_forcing /
+// a written SPH_S_TIME launch it too, so what is read back before a step is what that step uses.
+__global__ void k_accel_eval(DevScalars *__restrict__ ds)
+{
+    const double t = ds->sim_time;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double amp = ds->frc.amp[k];
+        ds->frc.accel[k] = amp != 0.0 ? (float)((double)ds->frc.g[k] + amp * sin(ds->frc.omega[k] * t + ds->frc.phase[k])) : ds->frc.g[k];
+    }
+}
+
 // the CFL time step from ds->vmax (global maximum)              dfsph_solver.py:104-119
 __device__ __forceinline__ void apply_dt_body(const Consts &c, DevScalars *__restrict__ ds, const double *__restrict__ red, int gather_n)
 {
@@ -1760,6 +1773,7 @@ __device__ __forceinline__ void apply_dt_body(const Consts &c, DevScalars *__res
         ds->dt2 = dt * dt;                                        // :118
         ds->ps_dt = dt;                                           // :119
     }
+    clock_advance(&ds->sim_time, ds->dt);                         // delta_time as this step leaves it (once per step, one thread: every dfsph path ends here)
     ds->gate_hist[0] = 1; ds->gate_hist[1] = 1;                   // (between the two solver loops: the density loop's decisions start afresh)
 }
 __global__ void k_apply_dt(Consts c, DevScalars *__restrict__ ds, const double *__restrict__ red, int gather_n = 0)
@@ -2145,6 +2159,7 @@ __global__ __launch_bounds__(kBlock) void k_wcsph_force(Consts c, float dt, cons
                                                         const float *__restrict__ pressure, float4 *__restrict__ Pn,
                                                         float4 *__restrict__ Vn, float4 *__restrict__ acc_out, RigidView rv)
 {
+    if (blockIdx.x == 0 && threadIdx.x == 0) clock_advance(c.clock, dt);      // the step's last launch: its dt joins the handle's clock
     SPH_SWEEP_PROLOGUE_M(QUAD)
     const float4 vi = V[ii];
     const float rho_i = pi.w;
@@ -2201,7 +2216,7 @@ __global__ __launch_bounds__(kBlock) void k_wcsph_force(Consts c, float dt, cons
     float vis[3] = {wx * c.m, wy * c.m, wz * c.m};           // solver_base.py:175
     float ten[3] = {tx * c.m, ty * c.m, tz * c.m};           // solver_base.py:209
     float bac[3] = {bx * c.rho0, by * c.rho0, bz * c.rho0};  // wcsph_solver.py:83
-    float acc[3] = {c.gravity * 0.0f, c.gravity * -1.0f, c.gravity * 0.0f};   // solver_base.py:131-133
+    float acc[3] = {c.accel[0], c.accel[1], c.accel[2]};     // solver_base.py:131-133: the handle's vector (DevScalars.frc.accel)
     float pos[3] = {pi.x, pi.y, pi.z};
     float vel[3] = {vi.x, vi.y, vi.z};
 #pragma unroll
@@ -2567,7 +2582,7 @@ __global__ __launch_bounds__(kBlock) void k_dfsph_ext(Consts c, const float4 *__
         const float dt = ds->dt;
         float ten[3] = {tx * c.m, ty * c.m, tz * c.m};       // :209
         float vis[3] = {wx * c.m, wy * c.m, wz * c.m};       // :175
-        float g[3] = {c.gravity * 0.0f, c.gravity * -1.0f, c.gravity * 0.0f};
+        float g[3] = {ds->frc.accel[0], ds->frc.accel[1], ds->frc.accel[2]};      // :96, the handle's vector
         float v[3] = {vi.x, vi.y, vi.z};
         float va[3];
 #pragma unroll

@@ -35,14 +35,14 @@ enum KernelId {
     K_HASH = 0, K_SCAN, K_SCATTER, K_ORDER_GATHER, K_BUILD_NL, K_W_DENSITY, K_W_FORCE, K_D_DENSITY_ALPHA,
     K_D_WARM, K_D_DIV_RESIDUAL, K_D_DIV_CORRECT, K_D_EXT, K_D_DENS_RESIDUAL, K_D_DENS_CORRECT, K_D_INTEGRATE,
     K_FINALIZE, K_TRANSFER, K_SLAB, K_RIGID, K_P_EXT, K_P_PREDICT_RHO, K_P_PRESS, K_P_INTEGRATE, K_I_ADVECT, K_I_RHO_ADV, K_I_DIJ,
-    K_I_UPDATE_P, K_I_INTEGRATE, K_B_LAMBDA, K_B_DELTA, K_B_XSPH, K_COUNT
+    K_I_UPDATE_P, K_I_INTEGRATE, K_B_LAMBDA, K_B_DELTA, K_B_XSPH, K_ACCEL, K_COUNT
 };
 const char *kKernelNames[K_COUNT] = {
     "hash_count", "scan", "scatter", "order_gather", "build_nl", "wcsph_density", "wcsph_force", "dfsph_density_alpha",
     "dfsph_warm_start", "dfsph_div_residual", "dfsph_div_correct", "dfsph_ext_force", "dfsph_dens_residual",
     "dfsph_dens_correct", "dfsph_integrate", "finalize", "transfer", "slab_exchange", "rigid",
     "pcisph_ext_force", "pcisph_predict_rho", "pcisph_press_force", "pcisph_integrate", "iisph_advect", "iisph_rho_adv", "iisph_d_ij",
-    "iisph_update_p", "iisph_integrate", "pbf_lambda", "pbf_delta_pos", "pbf_xsph"};
+    "iisph_update_p", "iisph_integrate", "pbf_lambda", "pbf_delta_pos", "pbf_xsph", "accel_eval"};
 
 thread_local std::string g_create_error;
 thread_local bool g_creating_with_rigid = false;     // sph_create_rigid builds the fluid handle first: no Verlet lists there (the body moves through the grid)
@@ -93,6 +93,9 @@ struct SphHandle {
     int nblocks = 0;
     float dt_wcsph = 0.f;
     int simulate_cnt = 0;
+    // gravity as a vector, constant or harmonic (sph_set_gravity / sph_set_forcing): the host's copy of DevScalars.frc.  frc.accel is exact here
+    // while frc.on == 0 (= frc.g); under forcing the device forms it (k_accel_eval) and a read-back refreshes this copy
+    DevScalars::Forcing frc = {};
     bool nl_valid = false;      // neighbour list matches the current positions
     bool density_valid = false;
     bool pbf_fields = false;    // pbf: aux / X[0] hold pbf_lambda / delta_pos of the last step in the current device order (slab handles lose them at a re-sort)
@@ -1127,6 +1130,14 @@ int sph_get_scalar(SphHandle *h, int which, double *out)
     case SPH_S_ARITH_RELAXED: *out = (use_relaxed(h) || h->verlet || relaxed_pressure(h) || relaxed_unstaged(h) || relaxed_pbf(h)) ? 1.0 : 0.0; return SPH_OK;
     case SPH_S_RIGID_ACTIVE: *out = rigid_binned(h) ? 1.0 : 0.0; return SPH_OK;
     case SPH_S_RIGID_MODE: *out = h->rigid ? (double)h->rigid_mode : 0.0; return SPH_OK;
+    case SPH_S_TIME: { int rc = read_scalars(h); if (rc) return rc; *out = h->ds_host->sim_time; return SPH_OK; }
+    case SPH_S_ACCEL: case SPH_S_ACCEL + 1: case SPH_S_ACCEL + 2:
+        if (h->frc.on) {                                            // formed on the device (k_accel_eval): by the last step, or by a set call since
+            int rc = read_scalars(h); if (rc) return rc;
+            for (int a = 0; a < 3; ++a) h->frc.accel[a] = h->ds_host->frc.accel[a];
+        }
+        *out = (double)h->frc.accel[which - SPH_S_ACCEL]; return SPH_OK;
+    case SPH_S_GRAVITY_VEC: case SPH_S_GRAVITY_VEC + 1: case SPH_S_GRAVITY_VEC + 2: *out = (double)h->frc.g[which - SPH_S_GRAVITY_VEC]; return SPH_OK;
     case SPH_S_VERLET_BUILDS: { int rc = read_scalars(h); if (rc) return rc; *out = (double)h->ds_host->verlet_builds; return SPH_OK; }      // kr_split is settled by the first list build
     case SPH_P_DENSITY_THRESHOLD: *out = h->p.density_threshold; return SPH_OK;
     case SPH_P_MIN_ITERATION_DENSITY: *out = h->p.min_iteration_density; return SPH_OK;
@@ -1215,9 +1226,45 @@ int sph_set_scalar(SphHandle *h, int which, double value)
 {
     if (!h) return SPH_E_INVALID;
     if (which >= SPH_P_DENSITY_THRESHOLD && which <= SPH_P_TENSION_K) return set_param(h, which, value);      // (on slab handles too: every rank sets the same)
-    if (which != SPH_S_DELTA_TIME || !(value > 0.0)) return fail(h, SPH_E_INVALID, "sph_set_scalar: SPH_S_DELTA_TIME > 0 or a solver attribute SPH_P_* can be written");
+    if (which == SPH_S_TIME) {                                        // the handle's clock; the acceleration vector follows at once
+        if (!std::isfinite(value)) return fail(h, SPH_E_INVALID, "sph_set_scalar(SPH_S_TIME): a finite value expected, got %g", value);
+        HIP_TRY(h, hipSetDevice(h->device));
+        HIP_TRY(h, hipMemcpyAsync(&h->ds->sim_time, &value, sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        return forcing_commit(h);
+    }
+    if (which != SPH_S_DELTA_TIME || !(value > 0.0)) return fail(h, SPH_E_INVALID, "sph_set_scalar: SPH_S_DELTA_TIME > 0, SPH_S_TIME or a solver attribute SPH_P_* can be written");
     HIP_TRY(h, hipSetDevice(h->device));
     return write_delta_time(h, value);                               // (on slab handles too: every rank writes the same)
+}
+
+int sph_set_gravity(SphHandle *h, const float g[3])
+{
+    if (!h) return SPH_E_INVALID;
+    if (!g) return fail(h, SPH_E_INVALID, "sph_set_gravity: null argument");
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(g[a])) return fail(h, SPH_E_INVALID, "sph_set_gravity: finite values expected, got %g on axis %d", (double)g[a], a);
+    HIP_TRY(h, hipSetDevice(h->device));
+    for (int a = 0; a < 3; ++a) h->frc.g[a] = g[a];
+    return forcing_commit(h);
+}
+
+int sph_set_forcing(SphHandle *h, const double amp[3], const double omega[3], const double phase[3])
+{
+    if (!h) return SPH_E_INVALID;
+    const double *arg[3] = {amp, omega, phase};
+    for (int k = 0; k < 3; ++k)
+        for (int a = 0; amp && arg[k] && a < 3; ++a)
+            if (!std::isfinite(arg[k][a])) return fail(h, SPH_E_INVALID, "sph_set_forcing: finite values expected, got %g (argument %d, axis %d)", arg[k][a], k, a);
+    HIP_TRY(h, hipSetDevice(h->device));
+    h->frc.on = 0;
+    for (int a = 0; a < 3; ++a) {
+        h->frc.amp[a] = amp ? amp[a] : 0.0;
+        h->frc.omega[a] = (amp && omega) ? omega[a] : 0.0;
+        h->frc.phase[a] = (amp && phase) ? phase[a] : 0.0;
+        if (h->frc.amp[a] != 0.0) h->frc.on = 1;                      // all amplitudes zero: a = g, nothing is evaluated
+    }
+    return forcing_commit(h);
 }
 
 const char *sph_overrides(SphHandle *h) { return h ? h->overrides.c_str() : ""; }

@@ -181,6 +181,7 @@ __global__ __launch_bounds__(kBlock) void k_pbf_delta(Consts c, PbfConsts k, flo
                                                       const uint32_t *__restrict__ nlb, const int *__restrict__ cnt,
                                                       float4 *__restrict__ dpos_out, float4 *__restrict__ Pn, float4 *__restrict__ Vn)
 {
+    if (blockIdx.x == 0 && threadIdx.x == 0) clock_advance(c.clock, dt);      // once per step: its dt joins the handle's clock
     const float4 *P = PL;
     SPH_SWEEP_PROLOGUE_M(QUAD)
     const float li = pi.w;
@@ -232,7 +233,7 @@ __global__ __launch_bounds__(kBlock) void k_pbf_delta(Consts c, PbfConsts k, flo
     if (c.boundary_handle) { dp[0] = (ax + bx) / c.rho0; dp[1] = (ay + by) / c.rho0; dp[2] = (az + bz) / c.rho0; }   // :62
     else { dp[0] = ax / c.rho0; dp[1] = ay / c.rho0; dp[2] = az / c.rho0; }                                          // :64
     const float4 vi = V[i];
-    const float acc[3] = {c.gravity * 0.0f, c.gravity * -1.0f, c.gravity * 0.0f};      // reset(), solver_base.py:131-133
+    const float acc[3] = {c.accel[0], c.accel[1], c.accel[2]};     // reset(), solver_base.py:131-133: the handle's vector (DevScalars.frc.accel)
     const float pos[3] = {pi.x, pi.y, pi.z};
     float vel[3] = {vi.x, vi.y, vi.z}, pp[3];
 #pragma unroll

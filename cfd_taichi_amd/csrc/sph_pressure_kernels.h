@@ -92,8 +92,9 @@ __global__ __launch_bounds__(kFinBlock) void k_finalize_pressure(const double *_
     }
 }
 
-__global__ void k_pressure_ctrl_begin(DevScalars *__restrict__ ds, int cap)
+__global__ void k_pressure_ctrl_begin(DevScalars *__restrict__ ds, int cap, float dt)
 {
+    clock_advance(&ds->sim_time, dt);      // once per step, one thread: delta_time never changes inside a pcisph / iisph step
     ds->overflow_any = 0;
     ds->dens_active = 1; ds->dens_it = 0; ds->dens_cap = cap; ds->dens_capped = 0; ds->dens_avg = 0.f;
     ds->res_prev = 0.f; ds->res_have_prev = 0; ds->res_diverged = 0;
@@ -149,7 +150,7 @@ __global__ __launch_bounds__(kBlock) void k_pci_ext(Consts c, float dt, const fl
     if (!owner) return;
     float ten[3] = {tx * c.m, ty * c.m, tz * c.m};           // :209
     float vis[3] = {wx * c.m, wy * c.m, wz * c.m};           // :175
-    float g[3] = {c.gravity * 0.0f, c.gravity * -1.0f, c.gravity * 0.0f};
+    float g[3] = {c.accel[0], c.accel[1], c.accel[2]};       // the handle's vector (DevScalars.frc.accel)
     float pos[3] = {pi.x, pi.y, pi.z};
     float v[3] = {vi.x, vi.y, vi.z};
     float ext[3], vp[3], pp[3];
@@ -413,7 +414,7 @@ __global__ __launch_bounds__(kBlock) void k_ii_advect(Consts c, float dt, const 
     if (!owner) return;
     float ten[3] = {tx * c.m, ty * c.m, tz * c.m};
     float vis[3] = {wx * c.m, wy * c.m, wz * c.m};
-    float g[3] = {c.gravity * 0.0f, c.gravity * -1.0f, c.gravity * 0.0f};
+    float g[3] = {c.accel[0], c.accel[1], c.accel[2]};       // the handle's vector (DevScalars.frc.accel)
     float v[3] = {vi.x, vi.y, vi.z};
     float va[3];
 #pragma unroll

@@ -349,7 +349,7 @@ __global__ __launch_bounds__(kBlock) void k_dfsph_ext_rx(Consts c, const float4 
         const float dt = ds->dt;
         const float ten[3] = {tx * c.m, ty * c.m, tz * c.m};                      // :209
         const float vis[3] = {wx * c.m, wy * c.m, wz * c.m};                      // :175
-        const float g[3] = {c.gravity * 0.0f, c.gravity * -1.0f, c.gravity * 0.0f};
+        const float g[3] = {ds->frc.accel[0], ds->frc.accel[1], ds->frc.accel[2]};   // :96, the handle's vector
         const float v[3] = {vi.x, vi.y, vi.z};
         float va[3];
 #pragma unroll
@@ -441,6 +441,7 @@ __global__ __launch_bounds__(kBlock) void k_wcsph_force_rx(Consts c, float dt, c
                                                            float4 *__restrict__ Pn, float4 *__restrict__ Vn, float4 *__restrict__ acc_out,
                                                            DevScalars *__restrict__ ds)
 {
+    if (blockIdx.x == 0 && threadIdx.x == 0) clock_advance(c.clock, dt);       // the step's last launch: its dt joins the handle's clock
     const uint32_t *nlb = nullptr;
     SPH_SWEEP_PROLOGUE_M(false)
     (void)kb; (void)nlbp;
@@ -463,7 +464,7 @@ __global__ __launch_bounds__(kBlock) void k_wcsph_force_rx(Consts c, float dt, c
     });
     bool far = false;
     if (live) {
-        float acc[3] = {c.gravity * 0.0f, c.gravity * -1.0f, c.gravity * 0.0f};       // solver_base.py:131-133
+        float acc[3] = {c.accel[0], c.accel[1], c.accel[2]};                   // solver_base.py:131-133: the handle's vector (DevScalars.frc.accel)
         const float pg[3] = {-px, -py, -pz};
         const float vis[3] = {wx * c.m, wy * c.m, wz * c.m};                   // :175
         const float ten[3] = {tx * c.m, ty * c.m, tz * c.m};                   // :209

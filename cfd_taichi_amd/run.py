@@ -19,6 +19,9 @@ import numpy as np
 from . import ParticleSystem, rigid_solver, utils
 
 
+LAST = {}      # the objects of the last single-GPU main() call (ps, solver, rigid), for a caller that embeds the runner and reads the end state
+
+
 def write_ply_ascii(path, pos, rgba):
     """ASCII PLY in the layout of ti.tools.PLYWriter.export_frame_ascii: float x y z red green blue alpha."""
     n = len(pos)
@@ -141,6 +144,7 @@ def main(argv=None):
             break
     print("frames: %d, simulated time: %.6f s, PLY frames: %d" % (frame_cnt, t, ply_cnt))
     print("Simulation time: {}".format(time.time() - start_time))               # :211
+    LAST.update(ps=ps, solver=solver, rigid=rs)
     return frame_cnt, t, ply_cnt
 
 

@@ -135,6 +135,24 @@ SCENES.update({
 })
 
 
+def _with_radius(cfg, radius):
+    cfg["scene"]["particle_radius"] = radius
+    return cfg
+
+
+def _with_forcing(cfg, amplitude, omega, phase=(0.0, 0.0, 0.0)):
+    cfg["scene"]["forcing"] = {"amplitude": list(amplitude), "omega": list(omega), "phase": list(phase)}
+    return cfg
+
+
+SCENES.update({
+    # not the reference's: a tank about half full (2 288 particles, r = 0.02) shaken along x, described in the tank's frame: gravity stays
+    # (0, -9.8, 0) and `scene.forcing` adds 3 sin(6 t) m/s^2 on x (sph_set_forcing)
+    "sloshing_dfsph": lambda: _with_forcing(_with_radius(_scene("dfsph", 1e-3, [1.2, 0.8, 0.6], [1.04, 0.32, 0.44], start_pos=(0.08, 0.08, 0.08)), 0.02),
+                                            [3.0, 0.0, 0.0], [6.0, 0.0, 0.0]),
+})
+
+
 def get(name):
     return SCENES[name]()
 

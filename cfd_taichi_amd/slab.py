@@ -231,7 +231,7 @@ class SlabSimulation:
             from . import mesh
             rigid = mesh.rigid_from_config(config)
         self.rigid_active = bool(rigid and rigid.get("active"))
-        self.sim = nat.Simulation(cfg, rigid=rigid)
+        self.sim = nat.Simulation(cfg, rigid=rigid, config=config)      # (config: scene.gravity as a vector, scene.forcing -- the same calls on every rank)
         if transport == "native":
             self.comm = None
             attach_native(self.sim, rank, capacity_bytes, group)
@@ -268,6 +268,13 @@ class SlabSimulation:
 
     def set_rigid_motion(self, vel, omega, acc=None, alpha=None):
         self.sim.rigid_set_motion(vel, omega, acc, alpha)
+
+    # the acceleration vector: plain local calls as well -- every rank makes the same ones between the same steps, and forms the same bits
+    def set_gravity(self, vec):
+        self.sim.set_gravity(vec)
+
+    def set_forcing(self, amp, omega=None, phase=None):
+        self.sim.set_forcing(amp, omega, phase)
 
     def rigid_load(self):
         """(force, torque) over the WHOLE body as the last rigid_step summed them: the same bits on every rank"""

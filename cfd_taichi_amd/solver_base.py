@@ -36,6 +36,7 @@ class solver_base:
         self._prologue_cnt = 0
         self.simulate_cnt = ScalarField(lambda: int(self._sim.scalar(nat.S_SIMULATE_CNT)) + self._prologue_cnt)   # :21
         self.rho = DeviceField(self, nat.F_RHO)               # :14
+        self.time = ScalarField(lambda: self._sim.time())     # the handle's simulated time (f64): the sum of delta_time over the steps so far
         print("\033[32m[Solver]: {}\033[0m".format(solver_config.get("name")))   # :39
 
     def _forward_attributes(self):
@@ -51,6 +52,15 @@ class solver_base:
                 self._sim.set_param(name, value)
                 sent[name] = value
         sent["_started"] = 1.0
+
+    def set_gravity(self, vec):
+        """The acceleration vector's base g, wherever the reference writes `gravity * (0, -1, 0)` (between steps).  The scalar attribute
+        `gravity` stays what the config says."""
+        self._sim.set_gravity(vec)
+
+    def set_forcing(self, amp, omega=None, phase=None):
+        """Harmonic forcing per axis on top of g: a_k = g_k + amp_k sin(omega_k time + phase_k); amp None switches it off."""
+        self._sim.set_forcing(amp, omega, phase)
 
     def compute_all_rho(self):
         """solver_base.compute_all_rho (:41-51) as a stand-alone stage (rebuilds the lists if needed)."""

@@ -185,6 +185,11 @@ typedef struct SphRigid {
 #define SPH_S_RIGID_ACC 33         /* +0,1,2: rigid_particles.acc (uniform over the body): what the sweeps add to the body's velocity as acc * dt */
 #define SPH_S_RIGID_ALPHA 36       /* +0,1,2: rigid_particles.alpha (uniform over the body) */
 #define SPH_S_RIGID_MODE 39        /* SPH_RIGID_DYNAMIC / _SCRIPTED / _FIXED as sph_rigid_set_mode left it; 0 on a handle without a body */
+#define SPH_S_TIME 40              /* the handle's simulated time, a device-resident f64: 0 at creation, += (double)delta_time at the end of every solver
+                                    * step (dfsph: the CFL value the step leaves).  Writable through sph_set_scalar with a finite value */
+#define SPH_S_ACCEL 41             /* +0,1,2: the acceleration vector as the last solver step used it, or as the next will if none has run since
+                                    * sph_set_gravity / sph_set_forcing / a written SPH_S_TIME */
+#define SPH_S_GRAVITY_VEC 44       /* +0,1,2: the base vector g of sph_set_gravity (default: scene.gravity * (0, -1, 0) in f32) */
 #define SPH_S_VERLET_BUILDS 31    /* diagnostics: list builds so far on a Verlet handle (wcsph under the relaxed arithmetic: the lists carry a skin and are rebuilt on demand) */
 #define SPH_S_ARITH_RELAXED 30    /* diagnostics: 1 if any pair sweep of this handle's solver runs the tolerance-grade kernels (SphConfig.arith asked AND the handle qualifies) */
 
@@ -257,6 +262,19 @@ int sph_rigid_set_motion(SphHandle *h, const float vel[3], const float omega[3],
 /* the fluid's load on the body as the last sph_rigid_step summed it over the samples' forces, in f64: force, and torque about the centroid
  * before that step's move.  All three modes, identical on every rank of a slab run.  SPH_E_STATE: no body, or no sph_rigid_step yet. */
 int sph_rigid_get_load(SphHandle *h, double force[3], double torque[3]);
+/* Gravity as a vector, constant or harmonic: tilted tanks, tanks shaken along an axis (described in the tank's frame), zero g.  The handle's
+ * acceleration vector a stands wherever the reference writes `gravity * (0, -1, 0)`: solver_base.py:131-133, dfsph_solver.py:91-96 (divided by
+ * m later, as there), the ext-force lines of pcisph_solver.py / iisph_solver.py, pbf_solver.py:26-30, and rigid_solver.py:40-41 for a DYNAMIC
+ * body (scripted and fixed bodies do not read it).  a_k = (float)((double)g_k + amp_k sin(omega_k t + phase_k)), evaluated in f64 on the device and
+ * rounded once, t = SPH_S_TIME at the head of the solver step, held through the step and the sph_rigid_step behind it; an axis with amp_k == 0,
+ * and every axis while no forcing is set, takes g_k as it is (no arithmetic).  The default g is the three floats the reference forms, so a handle
+ * that never calls these, or calls sph_set_gravity with them, computes the same bits.  Stage calls and sph_rigid_step do not advance t;
+ * sph_slab_set_state keeps t, g and the forcing.  A multi-step call stays asynchronous under forcing (one one-thread launch per step).
+ * Both calls: between steps only; a value that is not finite gives SPH_E_INVALID and leaves the handle unchanged; the vector is evaluated at once
+ * for the current t (SPH_S_ACCEL reads it back).  On slab handles every rank makes the same calls between the same steps (as with sph_set_scalar). */
+int sph_set_gravity(SphHandle *h, const float g[3]);
+/* amp == NULL switches the forcing off (omega and phase are ignored); omega or phase NULL: zeros */
+int sph_set_forcing(SphHandle *h, const double amp[3], const double omega[3], const double phase[3]);
 void sph_destroy(SphHandle *h);
 int sph_get_sizes(SphHandle *h, SphSizes *out);
 const char *sph_last_error(SphHandle *h);
