@@ -17,9 +17,14 @@
 // RX (SphConfig.arith = SPH_ARITH_RELAXED, relaxed_pbf() in sph_host_rigid.h): the tolerance-grade pair bodies.  Same pairs, lists, cell walk and
 // buffers; only the pair arithmetic changes.  r2 = fma(z,z, fma(y,y, fma(x,x, 1e-30))); poly6 is a polynomial in r2 -- tp = max(1 - r2 / h^2, 0),
 // W = kpoly tp^3, no root, no divide; the spiky gradient is one scalar times x_ij -- rinv = v_rsq_f32(r2), r = r2 rinv, ts = max(1 - r / h, 0),
-// grad W = K ts^2 rinv x_ij with K = -45 / (pi h^4), no q > 0 gate (a coincident pair has x_ij = 0 and a finite scalar through the floor on r2).
-// Every constant factor of a sum is taken out of it and applied once per particle (PbfConsts.rx_*, folded in f64 on the host): the sweeps add
-// tp^3, ts^2 rinv x_ij and (ts^2 rinv)^2 r2, and s_corr = -k (W / w_corr)^4 is rx_sc tp^12.  k_pbf_xsph decides membership by r2 <= r2_cut
+// grad W = K ts^2 rinv x_ij with K = -45 / (pi h^4).  Every constant factor of a sum is taken out of it and applied once per particle (PbfConsts.rx_*,
+// folded in f64 on the host): the sweeps add tp^3, ts^2 rinv x_ij and (ts^2 rinv)^2 r2, and s_corr = -k (W / w_corr)^4 is rx_sc tp^12.
+// A coincident pair (x_ij = 0 exactly; r2 is its floor, the scalar s = ts^2 rinv is 1e15, finite) contributes, as in the reference:
+//   tp^3 = 1 to the poly6 sums (rho, the wall's rb, s_corr, xsph's W = kpoly: poly6 has no gate at q = 0);
+//   s x_ij = 0 to the three vector sums of k_pbf_lambda and k_pbf_delta -- the reference's q > 0 gate gives the same 0, so they carry no gate;
+//   0 to the SCALAR sum of squared gradients of k_pbf_lambda (sum, sb): pbf_sq_rx selects it on x_ij == 0.  Ungated the term is s^2 r2 = 1,
+//   after the epilogue (K / rho0)^2 -- the limit r -> 0+, the largest term a pair can give, where the reference's gate gives 0.
+// Any pair with x_ij != 0 takes the ungated term, bit for bit what it was before the select existed.  k_pbf_xsph decides membership by r2 <= r2_cut
 // (Consts: the f32 image of r <= h) and never takes a root.  What stays exact: the per-particle epilogues that set the discrete outcomes --
 // the constraint and its max, lambda's `con == 0` branch and divide, the prediction, vel = (pp - pos) / dt, the clamp planes, vel += c v.  The wall
 // walk of k_pbf_delta is kept (the regrouping lambda_i G_i + T_i through k_pbf_lambda was not built).  tests/test_pbf_relaxed_gpu.py holds the RX
@@ -60,6 +65,13 @@ __device__ __forceinline__ PbfPairRx pbf_pair_rx(const Consts &c, const PbfConst
     const float ts = __builtin_fmaxf(__builtin_fmaf(-r, c.rh, 1.0f), 0.0f);
     o.s = (ts * ts) * rinv;
     return o;
+}
+
+// the pair's term of k_pbf_lambda's sum of squared gradients: (ts^2 / r)^2 r2, and 0 for a coincident pair (the reference's q > 0 gate)
+__device__ __forceinline__ float pbf_sq_rx(const PbfPairRx &p, float dx, float dy, float dz)
+{
+    const bool apart = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(dx), __builtin_fabsf(dy)), __builtin_fabsf(dz)) > 0.0f;
+    return apart ? p.s * p.s : 0.0f;
 }
 
 __device__ __forceinline__ float pow3f(float a) { return a * (a * a); }
@@ -121,7 +133,7 @@ __global__ __launch_bounds__(kBlock) void k_pbf_lambda(Consts c, PbfConsts k, co
             const PbfPairRx p = pbf_pair_rx(c, k, dx, dy, dz);
             rho = __builtin_fmaf(p.tp * p.tp, p.tp, rho);
             cx = __builtin_fmaf(p.s, dx, cx); cy = __builtin_fmaf(p.s, dy, cy); cz = __builtin_fmaf(p.s, dz, cz);
-            sum = __builtin_fmaf(p.s * p.s, p.r2, sum);
+            sum = __builtin_fmaf(pbf_sq_rx(p, dx, dy, dz), p.r2, sum);
             return;
         }
         const float r = norm3(dx, dy, dz);
@@ -142,7 +154,7 @@ __global__ __launch_bounds__(kBlock) void k_pbf_lambda(Consts c, PbfConsts k, co
             const PbfPairRx p = pbf_pair_rx(c, k, dx, dy, dz);
             rb = __builtin_fmaf(pj.w * (p.tp * p.tp), p.tp, rb);
             bx = __builtin_fmaf(p.s, dx, bx); by = __builtin_fmaf(p.s, dy, by); bz = __builtin_fmaf(p.s, dz, bz);
-            sb = __builtin_fmaf(p.s * p.s, p.r2, sb);
+            sb = __builtin_fmaf(pbf_sq_rx(p, dx, dy, dz), p.r2, sb);
             return;
         }
         const float r = norm3(dx, dy, dz);

@@ -1,0 +1,191 @@
+"""Input states at the edges for PBF (csrc/sph_pbf_kernels.h): what tests/test_edge_cases_gpu.py and test_particles_outside_the_grid give the four
+older solvers, built for the solver that has a 27-cell walk of its own (k_pbf_xsph) and a second set of pair bodies (RX).
+
+  ragged(scene, water)       1, 6, 73 and 82 particles (the water_size triples of test_ragged_particle_counts) at (0.05, 0.05, 0.05), the lattice drawn
+                             together about its lowest corner by SQUEEZE (test_pbf_gpu.squeeze: the rest lattice is under-dense and lambda would stay 0)
+  coincident(scene, seed)    pbf_states.pbf_state(scene, "bulk", seed) with
+                               (a) marks["a"] = (i, j): j put ON i with i's velocity.  i is the first particle from index 300 on whose lambda is != 0 in the
+                                   f64 oracle's first step from the bulk state and whose nearest neighbour j has lambda != 0 too
+                               (b) marks["b"]: a coincident pair that keeps its two velocities (its xsph term at r = 0 is kpoly dv) and separates
+                               (c) marks["c"]: a pair 1e-7 apart on every axis
+                               (d) marks["d"]: one particle at (0.4, 0.5, 0.6), on cell faces (h = 0.1)
+                             the four groups at least 2.5 h from one another
+  on_a_wall_particle(seed)   pbf_tiny_wall's bulk state; the fluid particle closest to the wall is put on the position of its nearest wall particle
+                             (marks["w"] = (fluid index, wall index); the f32 oracle's F_WALL_POS, which tests/test_parity_gpu.py shows bit-equal to
+                             the handle's -- tests/test_pbf_edges_gpu.py asserts it again before it relies on it).  For the exact check only: the f64
+                             oracle builds its wall lattice in f64 and does not agree that this pair is coincident
+  spray_and_clump(scene)     box 2.0^3; one particle per cell on a jittered lattice of pitch h plus 40 particles inside one cell, rng seed 5
+                             (test_edge_cases_gpu.test_spray_and_clump): k_pbf_xsph's batches of four with lengths 1 and 40 + 1, j == i in mid-batch
+  outside(scene, seed)       the bulk state translated so that its minimum corner is 0.02 from the low faces; 48 particles moved 0.3 h (1 + n % 4)
+                             beyond the six faces (test_lds_staging_with_particles_outside_the_box); marks["moved"]
+
+Every input is an `Input`: cfg, read-only f32 pos and vel that every participant gets bit for bit, marks.  tests/test_pbf_edge_states_cpu.py shows on
+the two oracles alone that the inputs are fair; tests/test_pbf_edges_gpu.py holds the library to them.
+
+TEST INFRASTRUCTURE ONLY: nothing here imports the HIP library; a handle is anything with upload / step_pbf / download."""
+import functools
+
+import numpy as np
+
+import pbf_states as pb
+from cfd_taichi_amd import scenes
+from oracle import oracle as orc
+
+SCENES = ("pbf_tiny_wall", "pbf_tiny_clamp")
+# water_size -> N = int(wx / d) int(wy / d) int(wz / d)   (ParticleSystem.py:85-86)
+RAGGED = {(0.05, 0.05, 0.05): 1, (0.35, 0.05, 0.05): 6, (0.36, 0.16, 0.16): 73, (0.26, 0.66, 0.06): 82}
+# chosen on the CPU (tests/test_pbf_edge_states_cpu.py): at 0.9 the clamp scene's 82 particles (one layer) never reach rho_0 and its 73 show lambda != 0
+# on exactly 5; at 0.85 the 82 still never do.  At 0.8 lambda != 0 in the first step on 55 (wall scene) and 36 (clamp scene) of the 73 and on 37 and 6 of
+# the 82; the 1 and the 6 particles of the clamp scene have no wall to lean on and stay below rho_0 at any factor (their step is rho, prediction, clamp, xsph)
+SQUEEZE = 0.8
+SEEDS = (1, 3)
+APART = 0.25          # 2.5 h: the marked groups of coincident() do not see one another
+N_OUTSIDE = 48
+
+
+class Input:
+    def __init__(self, label, cfg, pos, vel, **marks):
+        self.label, self.cfg, self.marks = label, cfg, marks
+        self.pos, self.vel = (np.ascontiguousarray(a, dtype=np.float32) for a in (pos, vel))
+        for a in (self.pos, self.vel):
+            a.setflags(write=False)
+
+
+def _lattice(cfg):
+    o = orc.Oracle(cfg, num_threads=1)
+    pos = o.get(orc.F_POS)
+    o.close()
+    return pos
+
+
+@functools.lru_cache(maxsize=None)
+def ragged(scene, water):
+    cfg = scenes.get(scene)
+    cfg["fluid"].update(start_pos=[0.05, 0.05, 0.05], water_size=list(water))
+    pos = _lattice(cfg)
+    about = pos.min(0)
+    pos = (about + (pos - about) * np.float32(SQUEEZE)).astype(np.float32)
+    return Input("ragged %s N=%d" % (scene, len(pos)), cfg, pos, np.zeros_like(pos))
+
+
+def _far(pos, i, taken):
+    return all(np.linalg.norm(pos[i].astype(np.float64) - pos[t]) >= APART for t in taken)
+
+
+def _nearest(pos, i):
+    d = np.linalg.norm(pos.astype(np.float64) - pos[i], axis=1)
+    d[i] = np.inf
+    return int(d.argmin())
+
+
+@functools.lru_cache(maxsize=None)
+def coincident(scene, seed):
+    cfg = scenes.get(scene)
+    pos, vel = (a.copy() for a in pb.pbf_state(scene, "bulk", seed))
+    n = len(pos)
+    lam = pb.references(scene, "bulk", seed, dict((c[:2], c[2]) for c in pb.CASES)[(scene, "bulk")])[1][0]["pbf_lambda"]
+    order = [(300 + k) % n for k in range(n)]
+    i = next(i for i in order if lam[i] != 0 and lam[_nearest(pos, i)] != 0)
+    a = (i, _nearest(pos, i))
+    taken = list(a)
+    # (d) first: the particle that has the shortest way to the point on the cell faces
+    face = np.float32([0.4, 0.5, 0.6])
+    by_way = np.argsort(np.linalg.norm(pos.astype(np.float64) - face, axis=1), kind="stable")
+    d = next(int(k) for k in by_way if _far(pos, k, taken))
+    assert all(np.linalg.norm(face.astype(np.float64) - pos[t]) >= APART for t in taken)
+    taken.append(d)
+    pos[d] = face
+    pairs = []
+    for start in (100, 500):
+        k = next(k for k in [(start + s) % n for s in range(n)] if _far(pos, k, taken) and _far(pos, _nearest(pos, k), taken)
+                 and _nearest(pos, k) not in taken)
+        pairs.append((k, _nearest(pos, k)))
+        taken += list(pairs[-1])
+    b, c = pairs
+    pos[a[1]], vel[a[1]] = pos[a[0]], vel[a[0]]
+    pos[b[1]] = pos[b[0]]
+    pos[c[1]] = pos[c[0]] + np.float32(1e-7)
+    assert (vel[b[0]] != vel[b[1]]).any() and (pos[c[1]] != pos[c[0]]).any()
+    return Input("coincident %s seed %d" % (scene, seed), cfg, pos, vel, a=a, b=b, c=c, d=d)
+
+
+@functools.lru_cache(maxsize=None)
+def on_a_wall_particle(seed):
+    scene = "pbf_tiny_wall"
+    cfg = scenes.get(scene)
+    pos, vel = (a.copy() for a in pb.pbf_state(scene, "bulk", seed))
+    o = orc.Oracle(cfg, num_threads=1)
+    wall = o.get(orc.F_WALL_POS)
+    o.close()
+    wall.setflags(write=False)
+    lo, hi = np.asarray(cfg["scene"]["box_min"], dtype=np.float64), np.asarray(cfg["scene"]["box_max"], dtype=np.float64)
+    i = int(np.minimum(pos - lo, hi - pos).min(1).argmin())            # the fluid particle closest to a face of the box
+    w = int(np.linalg.norm(wall.astype(np.float64) - pos[i], axis=1).argmin())
+    pos[i] = wall[w]
+    inp = Input("on a wall particle, seed %d" % seed, cfg, pos, vel, w=(i, w))
+    inp.wall = wall
+    return inp
+
+
+@functools.lru_cache(maxsize=None)
+def spray_and_clump(scene):
+    cfg = scenes.get(scene)
+    cfg["scene"]["box_max"] = [2.0, 2.0, 2.0]
+    n = len(_lattice(cfg))
+    rng = np.random.default_rng(5)
+    pos = np.empty((n, 3), dtype=np.float32)
+    side = int(np.ceil((n - 40) ** (1.0 / 3.0)))
+    g = np.stack(np.meshgrid(np.arange(side), np.arange(side), np.arange(side), indexing="ij"), -1).reshape(-1, 3)[: n - 40]
+    pos[: n - 40] = (0.15 + 0.1 * g + rng.uniform(-0.02, 0.02, (n - 40, 3))).astype(np.float32)
+    pos[n - 40:] = (1.5 + rng.uniform(0.02, 0.08, (40, 3))).astype(np.float32)
+    perm = rng.permutation(n)
+    pos = pos[perm]
+    clump = np.flatnonzero(perm >= n - 40)
+    return Input("spray and clump %s" % scene, cfg, pos, np.zeros_like(pos), clump=clump)
+
+
+@functools.lru_cache(maxsize=None)
+def outside(scene, seed):
+    cfg = scenes.get(scene)
+    pos, vel = (a.copy() for a in pb.pbf_state(scene, "bulk", seed))
+    lo = np.asarray(cfg["scene"]["box_min"], dtype=np.float64)
+    pos = (pos.astype(np.float64) + (lo + 0.02 - pos.astype(np.float64).min(0))).astype(np.float32)
+    box = np.asarray(cfg["scene"]["box_max"], dtype=np.float32)
+    h = np.float32(4 * cfg["scene"]["particle_radius"])
+    rng = np.random.default_rng(3)
+    pick = rng.choice(len(pos), size=N_OUTSIDE, replace=False)
+    for n, i in enumerate(pick):
+        axis, side = n % 3, (n // 3) % 2
+        pos[i, axis] = (-np.float32(0.3) * h * (1 + n % 4)) if side == 0 else box[axis] + np.float32(0.3) * h * (1 + n % 4)
+    return Input("outside %s seed %d" % (scene, seed), cfg, pos, vel, moved=np.sort(pick))
+
+
+# ---- the participants ----------------------------------------------------------------------------------------------------------------------------
+
+def run_oracle(inp, steps, precision, num_threads=8):
+    """[fields after step 1, ..., after step `steps`]; each with ["lost"] = the oracle's count of particles outside the grid in that step"""
+    o = orc.Oracle(inp.cfg, num_threads=num_threads, precision=precision)
+    o.set(orc.F_POS, inp.pos); o.set(orc.F_VEL, inp.vel)
+    out = []
+    for _ in range(steps):
+        o.step_pbf(1)
+        res = pb.snapshot(o.get)
+        res["lost"] = o.lost
+        out.append(res)
+    o.close()
+    return out
+
+
+_refs = {}
+
+
+def references(inp, steps):
+    """(f32 oracle, f64 oracle) per step on one Input: computed once per (input, steps), shared by every test that needs them, never written to."""
+    key = (inp.label, steps)
+    if key not in _refs:
+        _refs[key] = (run_oracle(inp, steps, "f32"), run_oracle(inp, steps, "f64"))
+    return _refs[key]
+
+
+def upload(sim, inp):
+    sim.upload(pb.F_POS, inp.pos); sim.upload(pb.F_VEL, inp.vel)

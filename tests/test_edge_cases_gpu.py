@@ -1,7 +1,8 @@
 """GPU suite, edge cases (the reference has no tests; these are the degenerate inputs its code paths imply):
 ragged particle counts far below one wave / one workgroup, a single particle, coincident particles (r = 0 takes the q <= 1e-5
 branch of the kernel derivative, solver_base.py:96), and particles resting exactly on a cell face.  All four solvers, against
-the oracle, bit for bit."""
+the oracle, bit for bit -- on the default handle and, for the ragged counts and the coincident particles, on the plain sweeps (SPH_QUAD=0) and
+on Morton cells in tiles of 4^3 as well.  PBF, the fifth solver, has its own file: tests/test_pbf_edges_gpu.py."""
 import numpy as np
 import pytest
 
@@ -38,22 +39,40 @@ def step_both(sim, o, solver, n):
         assert np.array_equal(a, b, equal_nan=True), (solver, f, a[:4], b[:4])
 
 
-@pytest.mark.parametrize("solver", SOLVERS)
-@pytest.mark.parametrize("water", [(0.05, 0.05, 0.05), (0.35, 0.05, 0.05), (0.36, 0.16, 0.16), (0.26, 0.66, 0.06)])
-def test_ragged_particle_counts(solver, water):
-    """N = int(wx/d * wy/d * wz/d) (ParticleSystem.py:85-86): 1, 6, 73 and 82 particles -- below one wave, just above one wave."""
-    cfg = tiny_scene(solver, water, start=(0.05, 0.05, 0.05))
+WATERS = [(0.05, 0.05, 0.05), (0.35, 0.05, 0.05), (0.36, 0.16, 0.16), (0.26, 0.66, 0.06)]
+# the other families of handle: the sweeps with one lane per particle instead of four, and cells along the Morton curve in tiles of 4^3
+KIND_KNOBS = ("SPH_QUAD", "SPH_CELL_ORDER", "SPH_CELL_TILE")
+KINDS = {"plain": {"SPH_QUAD": "0"}, "morton": {"SPH_CELL_ORDER": "morton", "SPH_CELL_TILE": "4"}}
+
+
+def handle_of_kind(cfg, kind, monkeypatch):
+    """kind None: the default handle, no knob in force.  Every knob that was set must be named by sim.overrides(), and no other of the three."""
+    knobs = KINDS[kind] if kind else {}
+    for name in KIND_KNOBS:
+        monkeypatch.delenv(name, raising=False)
+    for name, value in knobs.items():
+        monkeypatch.setenv(name, value)
     sim = nat.Simulation(nat.config_from_dict(cfg))
+    for name in KIND_KNOBS:
+        monkeypatch.delenv(name, raising=False)
+    named = sim.overrides()
+    for name in KIND_KNOBS:
+        assert [t for t in named if t.startswith(name + "=")] == (["%s=%s" % (name, knobs[name])] if name in knobs else []), (kind, named)
+    return sim
+
+
+def ragged_particle_counts(solver, water, sim_of):
+    cfg = tiny_scene(solver, water, start=(0.05, 0.05, 0.05))
+    sim = sim_of(cfg)
     o = orc.Oracle(cfg, solver=solver, num_threads=2)
     assert sim.n_fluid == o.N and 1 <= o.N < 128
     step_both(sim, o, solver, 25)
     sim.close(); o.close()
 
 
-@pytest.mark.parametrize("solver", SOLVERS)
-def test_coincident_particles_and_cell_faces(solver):
+def coincident_particles_and_cell_faces(solver, sim_of):
     cfg = tiny_scene(solver, (0.3, 0.3, 0.3), start=(0.3, 0.3, 0.3), walls=False)
-    sim = nat.Simulation(nat.config_from_dict(cfg))
+    sim = sim_of(cfg)
     o = orc.Oracle(cfg, solver=solver, num_threads=2)
     pos = o.get(orc.F_POS)
     pos[5] = pos[4]                                     # two particles in the same place: |x_ij| = 0
@@ -63,6 +82,32 @@ def test_coincident_particles_and_cell_faces(solver):
     sim.upload(nat.F_POS, pos)
     step_both(sim, o, solver, 15)
     sim.close(); o.close()
+
+
+@pytest.mark.parametrize("solver", SOLVERS)
+@pytest.mark.parametrize("water", WATERS)
+def test_ragged_particle_counts(solver, water):
+    """N = int(wx/d * wy/d * wz/d) (ParticleSystem.py:85-86): 1, 6, 73 and 82 particles -- below one wave, just above one wave."""
+    ragged_particle_counts(solver, water, lambda cfg: nat.Simulation(nat.config_from_dict(cfg)))
+
+
+@pytest.mark.parametrize("solver", SOLVERS)
+def test_coincident_particles_and_cell_faces(solver):
+    coincident_particles_and_cell_faces(solver, lambda cfg: nat.Simulation(nat.config_from_dict(cfg)))
+
+
+@pytest.mark.parametrize("solver", SOLVERS)
+@pytest.mark.parametrize("water", WATERS)
+@pytest.mark.parametrize("kind", KINDS)
+def test_ragged_particle_counts_on_the_other_handles(kind, solver, water, monkeypatch):
+    """the same 1, 6, 73 and 82 particles on the plain sweeps and on Morton cells (the cases above keep their ids and run the default handle)"""
+    ragged_particle_counts(solver, water, lambda cfg: handle_of_kind(cfg, kind, monkeypatch))
+
+
+@pytest.mark.parametrize("solver", SOLVERS)
+@pytest.mark.parametrize("kind", KINDS)
+def test_coincident_particles_and_cell_faces_on_the_other_handles(kind, solver, monkeypatch):
+    coincident_particles_and_cell_faces(solver, lambda cfg: handle_of_kind(cfg, kind, monkeypatch))
 
 
 @pytest.mark.parametrize("scene,solver,steps", [("dfsph_dam_x", "dfsph", 700), ("wcsph_dam_x", "wcsph", 5000), ("dfsph_tiny_wall_iisph", "iisph", 800),

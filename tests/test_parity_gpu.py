@@ -275,11 +275,12 @@ def mesh_rigid(cfg):
     return mesh.rigid_from_config(cfg)
 
 
-@pytest.mark.parametrize("solver", ["wcsph", "dfsph"])
+@pytest.mark.parametrize("solver", ["wcsph", "dfsph", "pbf"])
 def test_particles_outside_the_grid(solver):
     """Escaped particles (the reference only prints an error, ParticleSystem.py:393-395): both sides keep them out of the
-    cell lists, still integrate them, and report how many there are."""
-    scene = "wcsph_tiny_wall" if solver == "wcsph" else "dfsph_tiny_wall"
+    cell lists, still integrate them, and report how many there are (sph_step_pbf reports nothing: there the oracle's count says that
+    the case is what it claims, and pbf_lambda and delta_pos are compared as well)."""
+    scene = {"wcsph": "wcsph_tiny_wall", "dfsph": "dfsph_tiny_wall", "pbf": "pbf_tiny_wall"}[solver]
     sim, o = make(scene)
     pos = o.get(orc.F_POS)
     pos[0] = [-0.31, 0.2, 0.2]       # linear cell id < 0
@@ -290,6 +291,11 @@ def test_particles_outside_the_grid(solver):
     for _ in range(5):
         if solver == "wcsph":
             sim.step_wcsph(1); o.step_wcsph(1)
+        elif solver == "pbf":
+            sim.step_pbf(1); o.step_pbf(1)
+            assert o.lost >= 1
+            assert_same(sim.download(nat.F_PBF_LAMBDA), o.get(orc.F_PBF_LAMBDA), "pbf_lambda")
+            assert_same(sim.download(nat.F_PBF_DELTA_POS), o.get(orc.F_PBF_DELTA_POS), "delta_pos")
         else:
             st = sim.step_dfsph(1); o.step_dfsph(1, 100)
             assert st.lost == o.lost and st.lost >= 1
