@@ -1,10 +1,8 @@
-"""Worker of the loopback-transport tests: the library's NATIVE transport (ncclSend / ncclRecv / ncclAllReduce issued by the library itself on
-its main, halo and reduction streams -- the discipline a multi-GPU node runs, with no host wait between the sweeps) on ONE GPU.
-
-`world` slab handles live in this one process, one thread each; tests/loopback_rccl.hip stands in for librccl (SPH_RCCL_LIB, a development
-override) and moves the bytes device-to-device under the same ordering rules.  The owned particles of all handles are compared bit for bit
-with the same steps on a one-GPU handle.  With --time the steps are timed as well (all handles share the GPU: what this measures is the GPU
-work a sharded step adds -- packing, ghosts' sweeps, the split launches -- not a scaling figure)."""
+"""Worker of the loopback-transport tests: the library's NATIVE transport on ONE GPU -- the discipline a multi-GPU node runs, with no host wait
+between the sweeps.  `world` slab handles live in this one process, one thread each around the rank's whole run (tests/slab_ranks.py holds the rank
+group and describes the stand-in for librccl).  The owned particles of all handles are compared bit for bit with the same steps on a one-GPU handle.
+With --time the steps are timed as well (all handles share the GPU: what this measures is the GPU work a sharded step adds -- packing, ghosts'
+sweeps, the split launches -- not a scaling figure)."""
 import argparse
 import json
 import os
@@ -16,16 +14,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-
-
-def shim_path(build=True):
-    so = os.path.join(ROOT, "tests", "_build", "libloopback_rccl.so")
-    src = os.path.join(ROOT, "tests", "loopback_rccl.hip")
-    if build and (not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src)):
-        import subprocess
-        os.makedirs(os.path.dirname(so), exist_ok=True)
-        subprocess.run(["hipcc", "--offload-arch=gfx950", "-O2", "-shared", "-fPIC", src, "-o", so], check=True, cwd=ROOT)
-    return so
+sys.path.insert(0, os.path.join(ROOT, "tests"))          # the build and tests/test_abi.py load this file by path, for shim_path
+from slab_ranks import Ranks, loopback_env, shim_path, stat_row  # noqa: E402,F401
 
 
 def main():
@@ -50,9 +40,7 @@ def main():
     ap.add_argument("--param", action="append", default=[], help="name=value: a solver attribute (sph_set_scalar SPH_P_*) set on every slab handle AND on the one-GPU reference")
     ap.add_argument("--out", required=True)
     args = ap.parse_args()
-    os.environ["SPH_DEV"] = "1"
-    os.environ["SPH_RCCL_LIB"] = shim_path()
-    os.environ.setdefault("SPH_SLAB_CHECK", "1")
+    loopback_env()
     from cfd_taichi_amd import _native as nat
     from cfd_taichi_amd import scenes
     cfg = json.load(open(args.scene)) if os.path.exists(args.scene) else scenes.get(args.scene)
@@ -62,16 +50,9 @@ def main():
         from cfd_taichi_amd import mesh
         rigid = mesh.rigid_from_config(cfg)
     active = bool(rigid and rigid.get("active"))
-    sims = [] if args.load_log else [nat.Simulation(nat.config_from_dict(cfg, slab_rank=r, slab_count=world, slab_rebalance_every=args.rebalance,
-                                                                          slab_ghost_layers=args.layers, slab_overlap=args.overlap, arith=args.arith,
-                                                                          max_neighbors=args.max_neighbors if r == args.overflow_rank else 0), rigid=rigid)
-                                     for r in range(world)]
+    slab_opts = dict(slab_rebalance_every=args.rebalance, slab_ghost_layers=args.layers, slab_overlap=args.overlap, arith=args.arith)
     params = [(kv.split("=")[0], float(kv.split("=")[1])) for kv in args.param]
-    for sim_ in sims:
-        for k_, v_ in params:
-            sim_.set_param(k_, v_)
-    wcsph = nat.config_from_dict(cfg).solver == nat.SOLVER_IDS["wcsph"]
-    uid = nat.rccl_unique_id()
+    wcsph = nat.config_from_dict(cfg).solver == nat.SOLVER_WCSPH
     shim = None
     if args.replay_rank >= 0:
         import ctypes
@@ -86,6 +67,12 @@ def main():
             assert rc == 0, "loopback_log_load: %d" % rc
         else:
             assert shim.loopback_record_begin(args.replay_rank, args.log_mb << 20) == 0
+    # a replay against a saved log has no group: the one rank comes further down
+    group = None if args.load_log else Ranks(nat, cfg, world, rigid=rigid, per_rank={args.overflow_rank: {"max_neighbors": args.max_neighbors}}, **slab_opts)
+    sims = group.sims if group else []
+    for sim_ in sims:
+        for k_, v_ in params:
+            sim_.set_param(k_, v_)
 
     def state_digest(sim):
         import hashlib
@@ -96,14 +83,11 @@ def main():
             h.update(ids[order].tobytes()); h.update(vals[order].tobytes())
         return h.hexdigest()
     stats = [[] for _ in range(world)]
-    errors = [None] * world
-    codes = [0] * world
     owned_max = [0] * world
     start = threading.Barrier(world)
     timing = {}
 
-    def one_step(r):
-        sim = sims[r]
+    def one_step(sim):
         if wcsph:
             sim.step_wcsph(1)
             return None
@@ -112,48 +96,41 @@ def main():
             sim.rigid_step()
         return st
 
-    def run(r):
+    def run(r, sim):
         try:
-            sims[r].rccl_attach(uid, 64 << 20)              # collective: returns when every rank has joined
             for k in range(args.steps):
                 if args.toggle_overlap and k % args.toggle_overlap == 0:
-                    sims[r].set_slab_overlap((k // args.toggle_overlap) % 2 == 1)
-                st = one_step(r)
-                owned_max[r] = max(owned_max[r], sims[r].slab_info()["owned"])
+                    sim.set_slab_overlap((k // args.toggle_overlap) % 2 == 1)
+                st = one_step(sim)
+                owned_max[r] = max(owned_max[r], sim.slab_info()["owned"])
                 if st is not None:
-                    stats[r].append([st.n_div, st.n_dens, st.n_div_evals, float(st.div_first_err), float(st.div_err), float(st.dens_err), float(st.dt)])
+                    stats[r].append(stat_row(st))
             if args.time:
-                sims[r].synchronize()
+                sim.synchronize()
                 start.wait()
                 t0 = time.perf_counter()
                 for _ in range(args.time):
-                    one_step(r)
-                sims[r].synchronize()
+                    one_step(sim)
+                sim.synchronize()
                 start.wait()
                 if r == 0:
                     timing["ms_per_step"] = (time.perf_counter() - t0) * 1e3 / args.time
-        except BaseException as e:  # noqa: BLE001 - reported by the main thread; the other ranks run into the stand-in's bounded waits
-            errors[r] = repr(e)
-            codes[r] = getattr(e, "code", None)
-            try:
-                start.abort()
-            except Exception:  # noqa: BLE001
-                pass
+        except BaseException:  # noqa: BLE001 - no rank may wait at the timing barrier for one that failed
+            start.abort()
+            raise
 
-    threads = [] if args.load_log else [threading.Thread(target=run, args=(r,)) for r in range(world)]
-    for t in threads:
-        t.start()
-    for t in threads:
-        t.join()
     if args.overflow_rank >= 0:        # every rank must have failed its step, with the overflow code, and none may hang (the caller's timeout)
+        codes = group.codes(run)
         with open(args.out, "w") as f:
-            json.dump({"codes": codes, "errors": errors, "steps_done": [len(s) for s in stats]}, f)
-        for s in sims:
-            s.close()
+            json.dump({"codes": codes, "errors": [None if e is None else repr(e) for e in group.errors], "steps_done": [len(s) for s in stats]}, f)
+        group.close()
         return
-    if any(errors):
-        print("loopback worker failed:", errors, file=sys.stderr)
-        sys.exit(1)
+    if group:
+        try:
+            group.each(run)
+        except BaseException:  # noqa: BLE001 - every rank's error, not the first alone: the others' are often the broken barrier
+            print("loopback worker failed:", [e and repr(e) for e in group.errors], file=sys.stderr)
+            sys.exit(1)
     infos = []
     for r in range(len(sims)):
         info = sims[r].slab_info()
@@ -161,19 +138,6 @@ def main():
         info["overrides"] = sims[r].overrides()
         infos.append(info)
     n = sims[0].n_fluid if sims else 0
-
-    def gather(field):
-        out = None
-        seen = np.zeros(n, dtype=np.int32)
-        for s in sims:
-            ids, vals = s.download_owned(field)
-            if out is None:
-                out = np.full((n,) + vals.shape[1:], np.nan, dtype=np.float32)
-            out[ids] = vals
-            np.add.at(seen, ids, 1)
-        assert np.all(seen == 1), "slab ownership is not a partition: %d missing, %d duplicated" % (int((seen == 0).sum()), int((seen > 1).sum()))
-        return out
-
     result = {"world": world, "scene": args.scene, "steps": args.steps, "n": int(n), "slabs": infos, "lib_comm": sims[0].comm_stats() if sims else None,
               "stats_same_on_all_ranks": all(s == stats[0] for s in stats), "timing": timing or None,
               "relaxed": [s.scalar(nat.S_ARITH_RELAXED) for s in sims]}
@@ -183,7 +147,7 @@ def main():
         result["recorded"] = {"rank": args.replay_rank, "digest": state_digest(sims[args.replay_rank]), "log": args.save_log}
         shim = None
     if not args.no_compare and not args.time:
-        pos, vel, rho = gather(nat.F_POS), gather(nat.F_VEL), gather(nat.F_RHO)
+        pos, vel, rho = group.gather(nat.F_POS), group.gather(nat.F_VEL), group.gather(nat.F_RHO)
         bodies = [{"scalars": s.rigid_scalars(), "pos": s.download(nat.F_RIGID_POS, nat.SPECIES_RIGID).tolist()} for s in sims] if rigid else None
         ref = nat.Simulation(nat.config_from_dict(cfg, arith=args.arith), rigid=rigid)
         for k_, v_ in params:
@@ -193,8 +157,7 @@ def main():
             if wcsph:
                 ref.step_wcsph(1)
             else:
-                st = ref.step(1)
-                ref_stats.append([st.n_div, st.n_dens, st.n_div_evals, float(st.div_first_err), float(st.div_err), float(st.dens_err), float(st.dt)])
+                ref_stats.append(stat_row(ref.step(1)))
             if active:
                 ref.rigid_step()
         rp, rv, rr = ref.download(nat.F_POS), ref.download(nat.F_VEL), ref.download(nat.F_RHO)
@@ -217,18 +180,16 @@ def main():
         assert entries > 0, "the log overflowed: raise --log-mb"
         rid = ctypes.create_string_buffer(128)
         shim.loopback_replay_id(rid)
-        solo = nat.Simulation(nat.config_from_dict(cfg, slab_rank=k, slab_count=world, slab_rebalance_every=args.rebalance, slab_ghost_layers=args.layers,
-                                                   slab_overlap=args.overlap, arith=args.arith), rigid=rigid)
+        solo = nat.Simulation(nat.config_from_dict(cfg, slab_rank=k, slab_count=world, **slab_opts), rigid=rigid)
         solo.rccl_attach(rid.raw, 64 << 20)
-        sims.append(solo)
-        world = len(sims) - 1
+        sims = sims + [solo]
         for _ in range(args.steps):
-            one_step(world)
+            one_step(solo)
         solo.synchronize()
         shim.loopback_marker(ctypes.c_void_p(solo.stream_ptr()))
         t0 = time.perf_counter()
         for _ in range(args.time):
-            one_step(world)
+            one_step(solo)
         solo.synchronize()
         dt = (time.perf_counter() - t0) * 1e3 / max(args.time, 1)
         shim.loopback_marker(ctypes.c_void_p(solo.stream_ptr()))
@@ -241,16 +202,15 @@ def main():
         if args.one_gpu:          # the yardstick, same process, same clocks: the whole scene on one handle, same steps
             for s_ in sims:
                 s_.close()
-            sims = []
             one = nat.Simulation(nat.config_from_dict(cfg, arith=args.arith), rigid=rigid)
-            sims.append(one)
+            sims = [one]
             for _ in range(args.steps):
-                one_step(0)
+                one_step(one)
             one.synchronize()
             shim.loopback_marker(ctypes.c_void_p(one.stream_ptr()))
             t0 = time.perf_counter()
             for _ in range(args.time):
-                one_step(0)
+                one_step(one)
             one.synchronize()
             result["one_gpu"] = {"ms_per_step": (time.perf_counter() - t0) * 1e3 / max(args.time, 1), "n": int(one.n_fluid)}
             shim.loopback_marker(ctypes.c_void_p(one.stream_ptr()))

@@ -1,6 +1,6 @@
 """Worker of tests/test_slab_forcing_gpu.py: gravity as a vector under harmonic forcing (sph_set_gravity / sph_set_forcing) on x-slab handles
 against the same calls on a one-GPU handle, bit for bit.  `world` slab handles of this one process, one thread each per collective call, on the
-library's native transport with tests/loopback_rccl.hip standing in for librccl (tests/loopback_worker.py describes the stand-in).
+library's native transport with tests/loopback_rccl.hip standing in for librccl (tests/slab_ranks.py holds the rank group and describes the stand-in).
 
 Every rank makes the same set calls before its first step.  After every step: the gathered pos and vel against the one-GPU handle's, and
 SPH_S_TIME and SPH_S_ACCEL of every rank against its (the clock's eight bytes, the vector's twelve).  With --body (a scene with a `solid` block)
@@ -9,7 +9,6 @@ import argparse
 import json
 import os
 import sys
-import threading
 
 import numpy as np
 
@@ -17,44 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import forcing as fo  # noqa: E402
-from loopback_worker import shim_path  # noqa: E402
-
-
-def each(sims, fn):
-    """fn(rank, sim) on every rank at once; raises the first exception after all threads have ended"""
-    out, err = [None] * len(sims), [None] * len(sims)
-
-    def run(r):
-        try:
-            out[r] = fn(r, sims[r])
-        except BaseException as e:  # noqa: BLE001 - reported below; the other ranks run into the stand-in's bounded waits
-            err[r] = e
-    threads = [threading.Thread(target=run, args=(r,)) for r in range(len(sims))]
-    for t in threads:
-        t.start()
-    for t in threads:
-        t.join()
-    for e in err:
-        if e is not None:
-            raise e
-    return out
-
-
-def gather(sims, field):
-    n = sims[0].n_fluid
-    out, seen = None, np.zeros(n, dtype=np.int32)
-    for s in sims:
-        ids, vals = s.download_owned(field)
-        if out is None:
-            out = np.full((n,) + vals.shape[1:], np.nan, dtype=np.float32)
-        out[ids] = vals
-        np.add.at(seen, ids, 1)
-    assert np.all(seen == 1), "slab ownership is not a partition"
-    return out
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+from slab_ranks import Ranks, loopback_env, same_bits  # noqa: E402
 
 
 def clock_and_vector(sim):
@@ -74,9 +36,7 @@ def main():
     ap.add_argument("--body", action="store_true")
     ap.add_argument("--out", required=True)
     args = ap.parse_args()
-    os.environ.setdefault("SPH_SLAB_CHECK", "1")
-    os.environ["SPH_DEV"] = "1"
-    os.environ["SPH_RCCL_LIB"] = shim_path()
+    loopback_env()
     from cfd_taichi_amd import _native as nat
     cfg = json.load(open(args.scene))
     rigid = None
@@ -84,10 +44,9 @@ def main():
         from cfd_taichi_amd import mesh
         rigid = mesh.rigid_from_config(cfg)
     world = args.world
-    sims = [nat.Simulation(nat.config_from_dict(cfg, slab_rank=r, slab_count=world), rigid=rigid) for r in range(world)]
+    group = Ranks(nat, cfg, world, rigid=rigid)
+    sims = group.sims
     ref = nat.Simulation(nat.config_from_dict(cfg), rigid=rigid)
-    uid = nat.rccl_unique_id()
-    each(sims, lambda r, s: s.rccl_attach(uid, 64 << 20))
 
     def prepare(s):
         s.set_gravity(fo.TILT)
@@ -99,18 +58,18 @@ def main():
             s.rigid_step()
         return None if st is None else [st.n_div, st.n_dens, st.lost]
 
-    each(sims, lambda r, s: prepare(s))
+    group.each(lambda r, s: prepare(s))
     prepare(ref)
     res = {"n": int(ref.n_fluid), "world": world, "first_difference": None, "vectors": [], "stats_equal": True,
            "clock_start_equal": all(clock_and_vector(s) == clock_and_vector(ref) for s in sims)}
     for k in range(1, args.steps + 1):
-        stats = each(sims, lambda r, s: full_step(s))
+        stats = group.each(lambda r, s: full_step(s))
         want = full_step(ref)
         res["stats_equal"] = res["stats_equal"] and all(st == want for st in stats)
         res["vectors"].append(ref.accel().tolist())
         if res["first_difference"] is None:
             for name, f in (("pos", nat.F_POS), ("vel", nat.F_VEL)):
-                if not np.array_equal(bits(gather(sims, f)), bits(ref.download(f))):
+                if not same_bits(group.gather(f), ref.download(f)):
                     res["first_difference"] = {"step": k, "what": name}
                     break
         if res["first_difference"] is None:
@@ -130,8 +89,8 @@ def main():
         res["body_vel"] = ref.rigid_scalars()["vel"]
     with open(args.out, "w") as f:
         json.dump(res, f)
-    for s in sims + [ref]:
-        s.close()
+    group.close()
+    ref.close()
 
 
 if __name__ == "__main__":

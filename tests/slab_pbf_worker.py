@@ -3,7 +3,7 @@
 Two ways to run `world` ranks on one GPU:
   --transport gloo       launched by torch.distributed.run, one process per rank, SlabSimulation over the callback transport (mode equal only);
   --transport loopback   `world` slab handles of this one process, one thread each per collective call, on the library's NATIVE transport with
-                         tests/loopback_rccl.hip standing in for librccl (tests/loopback_worker.py describes the stand-in; SPH_DEV=1 is set here).
+                         tests/loopback_rccl.hip standing in for librccl (tests/slab_ranks.py holds the rank group and describes the stand-in; SPH_DEV=1 is set here).
 (tests/slab_worker.py and tests/loopback_worker.py read step statistics, which PBF has none of.)
 
 The yardstick of every comparison: a one-GPU handle given the same state with sph_upload (pos, vel) and stepped the same number of steps; the
@@ -18,7 +18,6 @@ import argparse
 import json
 import os
 import sys
-import threading
 
 import numpy as np
 
@@ -26,11 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import slab_pbf_states as sp  # noqa: E402
-from loopback_worker import shim_path  # noqa: E402
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and bool(np.array_equal(a.view(np.uint32), b.view(np.uint32)))
+from slab_ranks import Ranks, loopback_env, process_group, same_bits  # noqa: E402
 
 
 def first_difference(step, got, ref):
@@ -54,77 +49,8 @@ def fields_of(nat, download):
     return {name: download(f) for name, f in sp.FIELDS}
 
 
-class Ranks:
-    """`world` slab handles of one process on the loopback transport; a collective call runs on one thread per rank."""
-
-    def __init__(self, nat, cfg, world, rebalance=0, arith=0, max_neighbors=None):
-        self.nat, self.world = nat, world
-        self.sims = [nat.Simulation(nat.config_from_dict(cfg, slab_rank=r, slab_count=world, slab_rebalance_every=rebalance, arith=arith,
-                                                         max_neighbors=(max_neighbors or {}).get(r, 0))) for r in range(world)]
-        self.n = self.sims[0].n_fluid
-        uid = nat.rccl_unique_id()
-        self.each(lambda r, s: s.rccl_attach(uid, 64 << 20))
-
-    def each(self, fn):
-        """fn(rank, sim) on every rank at once; returns the results, raises the first exception after ALL threads have ended"""
-        out, err = [None] * self.world, [None] * self.world
-
-        def run(r):
-            try:
-                out[r] = fn(r, self.sims[r])
-            except BaseException as e:  # noqa: BLE001 - reported below; the other ranks run into the stand-in's bounded waits
-                err[r] = e
-        threads = [threading.Thread(target=run, args=(r,)) for r in range(self.world)]
-        for t in threads:
-            t.start()
-        for t in threads:
-            t.join()
-        self.errors = err
-        for e in err:
-            if e is not None:
-                raise e
-        return out
-
-    def codes(self, fn):
-        """the SphError code of fn on every rank (0: no error)"""
-        try:
-            self.each(fn)
-        except self.nat.SphError:
-            pass
-        return [0 if e is None else getattr(e, "code", repr(e)) for e in self.errors]
-
-    def step(self, nsteps=1):
-        self.each(lambda r, s: s.step_pbf(nsteps))
-
-    def set_state(self, pos, vel, scalar=None, dt=0.0):
-        self.each(lambda r, s: s.slab_set_state(pos, vel, scalar, dt))
-
-    def gather(self, field):
-        out, seen = None, np.zeros(self.n, dtype=np.int32)
-        for s in self.sims:
-            ids, vals = s.download_owned(field)
-            if out is None:
-                out = np.full((self.n,) + vals.shape[1:], np.nan, dtype=np.float32)
-            out[ids] = vals
-            np.add.at(seen, ids, 1)
-        assert np.all(seen == 1), "slab ownership is not a partition: %d missing, %d duplicated" % (int((seen == 0).sum()), int((seen > 1).sum()))
-        return out
-
-    def fields(self):
-        return {name: self.gather(f) for name, f in sp.FIELDS}
-
-    def owners(self):
-        own = np.full(self.n, -1, dtype=np.int32)
-        for r, s in enumerate(self.sims):
-            own[s.download_owned(self.nat.F_POS)[0]] = r
-        return own
-
-    def infos(self):
-        return [s.slab_info() for s in self.sims]
-
-    def close(self):
-        for s in self.sims:
-            s.close()
+def set_state(group, pos, vel, scalar=None, dt=0.0):
+    group.each(lambda r, s: s.slab_set_state(pos, vel, scalar, dt))
 
 
 def load_state(path):
@@ -142,14 +68,14 @@ def window(stats0, stats1, recuts0, recuts1):
 
 def mode_equal_loopback(nat, cfg, args):
     state = load_state(args.state)
-    b = Ranks(nat, cfg, args.world, rebalance=args.rebalance, arith=args.arith)
+    b = Ranks(nat, cfg, args.world, slab_rebalance_every=args.rebalance, arith=args.arith)
     a = one_gpu(nat, cfg, state, arith=args.arith)
     if state is not None:
-        b.set_state(state[0], state[1])
+        set_state(b, state[0], state[1])
     own0 = b.owners()
     for s in b.sims:
         s.comm_stats(reset=True)
-    res = {"n": int(b.n), "world": args.world, "cuts_start": [i["x_lo"] for i in b.infos()], "owned_sums": [], "ghosts_max": [0] * args.world,
+    res = {"n": int(b.sims[0].n_fluid), "world": args.world, "cuts_start": [i["x_lo"] for i in b.infos()], "owned_sums": [], "ghosts_max": [0] * args.world,
            "first_difference": None}
     after_first = None
     for k in range(1, args.steps + 1):
@@ -160,7 +86,7 @@ def mode_equal_loopback(nat, cfg, args):
         if k == 1:
             after_first = ([s.comm_stats() for s in b.sims], [i["recuts"] for i in infos])
         if res["first_difference"] is None and (args.every_step or k == args.steps):
-            res["first_difference"] = first_difference(k, b.fields(), fields_of(nat, a.download))
+            res["first_difference"] = first_difference(k, fields_of(nat, b.gather), fields_of(nat, a.download))
     infos = b.infos()
     total = [s.comm_stats() for s in b.sims]
     res["comm_whole_run"] = [dict(t, recuts=i["recuts"]) for t, i in zip(total, infos)]
@@ -172,7 +98,7 @@ def mode_equal_loopback(nat, cfg, args):
     res["relaxed"] = [s.scalar(nat.S_ARITH_RELAXED) for s in b.sims] + [a.scalar(nat.S_ARITH_RELAXED)]
     res["overrides"] = b.sims[0].overrides()
     if args.dump:
-        np.savez(args.dump, **b.fields())
+        np.savez(args.dump, **fields_of(nat, b.gather))
     a.close(); b.close()
     return res
 
@@ -183,8 +109,8 @@ def mode_roundtrip(nat, cfg, args):
     state = load_state(args.state)
     a = one_gpu(nat, cfg, state)
     b = Ranks(nat, cfg, args.world)
-    b.set_state(state[0], state[1])
-    res = {"n": int(b.n)}
+    set_state(b, state[0], state[1])
+    res = {"n": int(b.sims[0].n_fluid)}
     res["lambda_before_first_step"] = b.codes(lambda r, s: s.download_local(nat.F_PBF_LAMBDA))
     for _ in range(args.steps):
         b.step()
@@ -193,17 +119,17 @@ def mode_roundtrip(nat, cfg, args):
     res["state_equal_one_gpu"] = same_bits(pos, a.download(nat.F_POS)) and same_bits(vel, a.download(nat.F_VEL))
     res["scalar_refused"] = b.codes(lambda r, s: s.slab_set_state(pos, vel, np.zeros(len(pos), dtype=np.float32), dt))
     c = Ranks(nat, cfg, 2)
-    c.set_state(pos, vel, None, dt)
+    set_state(c, pos, vel, None, dt)
     res["owned_after_set"] = [i["owned"] for i in c.infos()]
     res["lambda_after_set_state"] = c.codes(lambda r, s: s.download_local(nat.F_PBF_LAMBDA))
     for _ in range(args.steps):
         b.step(); c.step()
     a.step_pbf(args.steps)
     ref = fields_of(nat, a.download)
-    res["first_difference"] = first_difference(2 * args.steps, c.fields(), ref)
-    res["refused_group_runs_on"] = first_difference(2 * args.steps, b.fields(), ref)
+    res["first_difference"] = first_difference(2 * args.steps, fields_of(nat, c.gather), ref)
+    res["refused_group_runs_on"] = first_difference(2 * args.steps, fields_of(nat, b.gather), ref)
     # set_state on handles that have stepped: pbf_lambda / delta_pos are "before the first step" again
-    b.set_state(pos, vel, None, dt)
+    set_state(b, pos, vel, None, dt)
     res["lambda_after_set_state_mid_run"] = b.codes(lambda r, s: s.download_local(nat.F_PBF_LAMBDA))
     a.close(); b.close(); c.close()
     return res
@@ -214,12 +140,12 @@ def mode_midrun(nat, cfg, args):
     state = load_state(args.state)
     a = one_gpu(nat, cfg, state)
     b = Ranks(nat, cfg, args.world)
-    b.set_state(state[0], state[1])
-    res = {"n": int(b.n), "first_difference": None}
+    set_state(b, state[0], state[1])
+    res = {"n": int(b.sims[0].n_fluid), "first_difference": None}
     for k in range(1, args.steps + 1):
         b.step(); a.step_pbf(1)
         if res["first_difference"] is None:
-            res["first_difference"] = first_difference(k, b.fields(), fields_of(nat, a.download))
+            res["first_difference"] = first_difference(k, fields_of(nat, b.gather), fields_of(nat, a.download))
         if k == args.at:
             b.each(lambda r, s: s.compute_density())
             a2 = one_gpu(nat, cfg, state)
@@ -240,19 +166,16 @@ def mode_midrun(nat, cfg, args):
 
 def mode_overflow(nat, cfg, args):
     state = load_state(args.state)
-    b = Ranks(nat, cfg, args.world, max_neighbors={args.overflow_rank: args.max_neighbors})
-    b.set_state(state[0], state[1])
+    b = Ranks(nat, cfg, args.world, per_rank={args.overflow_rank: {"max_neighbors": args.max_neighbors}})
+    set_state(b, state[0], state[1])
     res = {"codes": b.codes(lambda r, s: s.step_pbf(1)), "errors": [None if e is None else str(e) for e in b.errors]}
     b.close()
     return res
 
 
-def mode_equal_gloo(args):
+def mode_equal_gloo(args, rank, world, device):
     import torch
     import torch.distributed as dist
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    device = int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1)
-    dist.init_process_group("gloo")
     from cfd_taichi_amd import _native as nat
     from cfd_taichi_amd.slab import SlabSimulation
     cfg = sp.config(args.scene)
@@ -311,8 +234,6 @@ def mode_equal_gloo(args):
             json.dump(res, f)
         a.close()
     sim.close()
-    dist.barrier()
-    dist.destroy_process_group()
 
 
 def main():
@@ -335,10 +256,10 @@ def main():
     os.environ.setdefault("SPH_SLAB_CHECK", "1")
     if args.transport == "gloo":
         assert args.mode == "equal", "the gloo worker runs mode equal"
-        mode_equal_gloo(args)
+        with process_group() as (rank, world, device):
+            mode_equal_gloo(args, rank, world, device)
         return
-    os.environ["SPH_DEV"] = "1"
-    os.environ["SPH_RCCL_LIB"] = shim_path()
+    loopback_env()
     from cfd_taichi_amd import _native as nat
     cfg = sp.config(args.scene)
     res = {"equal": mode_equal_loopback, "roundtrip": mode_roundtrip, "midrun": mode_midrun, "overflow": mode_overflow}[args.mode](nat, cfg, args)

@@ -8,14 +8,13 @@ import argparse
 import json
 import os
 import sys
-import threading
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-
-from slab_rigid_worker import stat_row  # noqa: E402
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from slab_ranks import body_ranks, owned_samples, stat_row  # noqa: E402
 
 
 def body_of(sim, nat):
@@ -68,11 +67,7 @@ def compare(nat, cfg, rigid, args, reps, fields):
     pos, vel, rho = fields
 
     def owners(tag):
-        out = []
-        for r in reps:
-            col = np.floor(r["sample_x_" + tag] / h).astype(np.int64)
-            out.append(int(((col >= r["cols_" + tag][0]) & (col < r["cols_" + tag][1])).sum()))
-        return out
+        return [owned_samples(r["sample_x_" + tag], h, r["cols_" + tag]) for r in reps]
     return {
         "n": int(len(rp)), "steps": args.steps, "slabs": [r["info"] for r in reps], "mode": rr["body"]["scalars"]["mode"],
         "pos_equal": bool(np.array_equal(pos, rp)), "vel_equal": bool(np.array_equal(vel, rv)), "rho_equal": bool(np.array_equal(rho, rrho)),
@@ -87,84 +82,6 @@ def compare(nat, cfg, rigid, args, reps, fields):
         "cols_first": [r["cols_first"] for r in reps], "cols_last": [r["cols_last"] for r in reps],
         "body_moved": float(np.abs(end - start).max()), "body_centroid": rr["body"]["scalars"]["centroid"],
     }
-
-
-def main_gloo(args, cfg, rigid):
-    import torch
-    import torch.distributed as dist
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    device = int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1)
-    dist.init_process_group("gloo")
-    from cfd_taichi_amd import _native as nat
-    from cfd_taichi_amd.slab import SlabSimulation
-    sim = SlabSimulation(cfg, rank, world, device=device, rebalance_every=args.rebalance)
-    sim.set_rigid_mode(args.mode)
-    if args.mode == "scripted":
-        sim.set_rigid_motion(args.vel, args.omega)
-    rep = run_rank(nat, sim.sim, args.steps, lambda: sim.step(1), sim.rigid_load)
-    reps = [None] * world if rank == 0 else None
-    dist.gather_object(rep, reps, dst=0)
-    fields = [sim.gather(f) for f in (nat.F_POS, nat.F_VEL, nat.F_RHO)]
-    if rank == 0:
-        with open(args.out, "w") as f:
-            json.dump(compare(nat, cfg, rigid, args, reps, fields), f)
-    sim.close()
-    dist.barrier()
-    dist.destroy_process_group()
-
-
-def main_loopback(args, cfg, rigid):
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("loopback_worker", os.path.join(ROOT, "tests", "loopback_worker.py"))
-    lw = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(lw)
-    os.environ["SPH_DEV"] = "1"
-    os.environ["SPH_RCCL_LIB"] = lw.shim_path()
-    from cfd_taichi_amd import _native as nat
-    world = args.world
-    sims = [nat.Simulation(nat.config_from_dict(cfg, slab_rank=r, slab_count=world, slab_rebalance_every=args.rebalance), rigid=rigid) for r in range(world)]
-    uid = nat.rccl_unique_id()
-    reps, errors = [None] * world, [None] * world
-
-    def run(r):
-        try:
-            sims[r].rccl_attach(uid, 64 << 20)              # collective: returns when every rank has joined
-            prepare(sims[r], args)
-
-            def full_step():
-                st = sims[r].step(1)
-                sims[r].rigid_step()
-                return st
-            reps[r] = run_rank(nat, sims[r], args.steps, full_step, sims[r].rigid_load)
-        except BaseException as e:  # noqa: BLE001 - reported by the main thread; the other ranks run into the stand-in's bounded waits
-            errors[r] = repr(e)
-
-    threads = [threading.Thread(target=run, args=(r,)) for r in range(world)]
-    for t in threads:
-        t.start()
-    for t in threads:
-        t.join()
-    if any(errors):
-        print("slab_scripted_worker failed:", errors, file=sys.stderr)
-        sys.exit(1)
-    n = sims[0].n_fluid
-    fields = []
-    for field in (nat.F_POS, nat.F_VEL, nat.F_RHO):
-        out, seen = None, np.zeros(n, dtype=np.int32)
-        for s in sims:
-            ids, vals = s.download_owned(field)
-            if out is None:
-                out = np.full((n,) + vals.shape[1:], np.nan, dtype=np.float32)
-            out[ids] = vals
-            np.add.at(seen, ids, 1)
-        assert np.all(seen == 1), "slab ownership is not a partition"
-        fields.append(out)
-    result = compare(nat, cfg, rigid, args, reps, fields)
-    result["overrides"] = [s.overrides() for s in sims]
-    with open(args.out, "w") as f:
-        json.dump(result, f)
-    for s in sims:
-        s.close()
 
 
 def main():
@@ -183,7 +100,11 @@ def main():
     cfg = json.load(open(args.scene))
     from cfd_taichi_amd import mesh
     rigid = mesh.rigid_from_config(cfg)
-    (main_gloo if args.transport == "gloo" else main_loopback)(args, cfg, rigid)
+
+    def per_rank(nat, native, full_step):
+        prepare(native, args)
+        return run_rank(nat, native, args.steps, full_step, native.rigid_load)
+    body_ranks(args, cfg, rigid, per_rank, lambda nat, reps, fields: compare(nat, cfg, rigid, args, reps, fields))
 
 
 if __name__ == "__main__":

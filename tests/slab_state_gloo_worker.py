@@ -20,51 +20,47 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--out", required=True)
     args = ap.parse_args()
-    import torch
     import torch.distributed as dist
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    device = int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1)
-    dist.init_process_group("gloo")
-    from cfd_taichi_amd import _native as nat
-    from cfd_taichi_amd import scenes
-    from cfd_taichi_amd.slab import SlabSimulation
-    from slab_state_worker import one_gpu_state, same_bits, stat_row
-    cfg = scenes.get(args.scene)
-    sim = SlabSimulation(cfg, rank, world, device=device)
-    state = one_gpu_state(nat, cfg, args.state_steps) if rank == 0 else (None, None, None, None)
-    sim.set_state(*state, src=0)
-    back = sim.state()                                   # rank 0: (pos, vel, scalar, delta_time) in original order
-    a = None
-    res = {}
-    if rank == 0:
-        pos, vel, warm, dt = state
-        res["roundtrip"] = same_bits(back[0], pos) and same_bits(back[1], vel) and same_bits(back[2], warm)
-        res["state_dt"] = np.float32(back[3]) == np.float32(dt)
-        a = nat.Simulation(nat.config_from_dict(cfg, device=device))
-        a.upload(nat.F_POS, pos); a.upload(nat.F_VEL, vel); a.upload(nat.F_WARM_K, warm)
-        a.set_dt(dt)
-    first_bad, stats_bad = None, None
-    for k in range(args.steps):
-        sb = stat_row(sim.step(1))
-        rows = [None] * world if rank == 0 else None
-        dist.gather_object(sb, rows, dst=0)
-        got = [sim.gather(f) for f in (nat.F_POS, nat.F_VEL, nat.F_RHO)]
+    from slab_ranks import process_group, same_bits, stat_row
+    from slab_state_worker import one_gpu_state
+    with process_group() as (rank, world, device):
+        from cfd_taichi_amd import _native as nat
+        from cfd_taichi_amd import scenes
+        from cfd_taichi_amd.slab import SlabSimulation
+        cfg = scenes.get(args.scene)
+        sim = SlabSimulation(cfg, rank, world, device=device)
+        state = one_gpu_state(nat, cfg, args.state_steps) if rank == 0 else (None, None, None, None)
+        sim.set_state(*state, src=0)
+        back = sim.state()                                   # rank 0: (pos, vel, scalar, delta_time) in original order
+        a = None
+        res = {}
         if rank == 0:
-            sa = stat_row(a.step(1))
-            if stats_bad is None and any(row != sa for row in rows):
-                stats_bad = {"step": k + 1, "one_gpu": sa, "ranks": rows}
-            for name, field, g in zip(("pos", "vel", "rho"), (nat.F_POS, nat.F_VEL, nat.F_RHO), got):
-                if first_bad is None and not same_bits(g, a.download(field)):
-                    first_bad = {"step": k + 1, "field": name}
-    if rank == 0:
-        res.update({"first_difference": first_bad, "stats_difference": stats_bad, "world": world, "n": int(sim.n_fluid)})
-        res["roundtrip"], res["state_dt"] = bool(res["roundtrip"]), bool(res["state_dt"])
-        with open(args.out, "w") as f:
-            json.dump(res, f)
-        a.close()
-    sim.close()
-    dist.barrier()
-    dist.destroy_process_group()
+            pos, vel, warm, dt = state
+            res["roundtrip"] = same_bits(back[0], pos) and same_bits(back[1], vel) and same_bits(back[2], warm)
+            res["state_dt"] = np.float32(back[3]) == np.float32(dt)
+            a = nat.Simulation(nat.config_from_dict(cfg, device=device))
+            a.upload(nat.F_POS, pos); a.upload(nat.F_VEL, vel); a.upload(nat.F_WARM_K, warm)
+            a.set_dt(dt)
+        first_bad, stats_bad = None, None
+        for k in range(args.steps):
+            sb = stat_row(sim.step(1))
+            rows = [None] * world if rank == 0 else None
+            dist.gather_object(sb, rows, dst=0)
+            got = [sim.gather(f) for f in (nat.F_POS, nat.F_VEL, nat.F_RHO)]
+            if rank == 0:
+                sa = stat_row(a.step(1))
+                if stats_bad is None and any(row != sa for row in rows):
+                    stats_bad = {"step": k + 1, "one_gpu": sa, "ranks": rows}
+                for name, field, g in zip(("pos", "vel", "rho"), (nat.F_POS, nat.F_VEL, nat.F_RHO), got):
+                    if first_bad is None and not same_bits(g, a.download(field)):
+                        first_bad = {"step": k + 1, "field": name}
+        if rank == 0:
+            res.update({"first_difference": first_bad, "stats_difference": stats_bad, "world": world, "n": int(sim.n_fluid)})
+            res["roundtrip"], res["state_dt"] = bool(res["roundtrip"]), bool(res["state_dt"])
+            with open(args.out, "w") as f:
+                json.dump(res, f)
+            a.close()
+        sim.close()
 
 
 if __name__ == "__main__":

@@ -1,5 +1,5 @@
 """Worker of tests/test_slab_state_gpu.py: sph_slab_set_state on the loopback stand-in for the native transport (the ranks are slab handles of
-this one process, one thread each per collective call -- tests/loopback_worker.py describes the stand-in).
+this one process, one thread each per collective call -- tests/slab_ranks.py holds the rank group and describes the stand-in).
 
 The yardstick of every comparison: A = a fresh one-GPU handle given a state with sph_upload (pos, vel, warm_start_k) + sph_set_scalar(delta_time),
 B = `world` slab handles given the same state with sph_slab_set_state.  After EVERY following step the owned particles of B, gathered by id, must
@@ -8,11 +8,9 @@ equal A bit for bit (positions, velocities, densities), and so must the step sta
 modes: equal (cases 1-7: options for re-cuts, ghost columns, steps from rest before the hand-over, a mirrored state), roundtrip (case 8),
 refuse (case 9: every refusal on every rank alike, the handles untouched), time (the cost of the call, for BASELINE.md)."""
 import argparse
-import hashlib
 import json
 import os
 import sys
-import threading
 import time
 
 import numpy as np
@@ -20,96 +18,13 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-from loopback_worker import shim_path  # noqa: E402
+from slab_ranks import Ranks, gather_by_id, loopback_env, same_bits, stat_row  # noqa: E402
 
 
-def stat_row(st):
-    return None if st is None else [st.n_div, st.n_dens, st.n_div_evals, float(st.div_first_err), float(st.div_err), float(st.dens_err), float(st.dt)]
-
-
-class Ranks:
-    """`world` slab handles of one process on the loopback transport; a collective call runs on one thread per rank."""
-
-    def __init__(self, nat, cfg, world, rigid=None, capacities=None, **opts):
-        self.nat, self.world = nat, world
-        self.active = bool(rigid and rigid.get("active"))
-        self.wcsph = nat.config_from_dict(cfg).solver == nat.SOLVER_WCSPH
-        self.sims = [nat.Simulation(nat.config_from_dict(cfg, slab_rank=r, slab_count=world, slab_capacity=(capacities or {}).get(r, 0), **opts), rigid=rigid)
-                     for r in range(world)]
-        uid = nat.rccl_unique_id()
-        self.each(lambda r, s: s.rccl_attach(uid, 64 << 20))
-
-    def each(self, fn):
-        """fn(rank, sim) on every rank at once; returns the results, raises the first exception after ALL threads have ended."""
-        out, err = [None] * self.world, [None] * self.world
-
-        def run(r):
-            try:
-                out[r] = fn(r, self.sims[r])
-            except BaseException as e:  # noqa: BLE001 - reported below; the other ranks run into the stand-in's bounded waits
-                err[r] = e
-        threads = [threading.Thread(target=run, args=(r,)) for r in range(self.world)]
-        for t in threads:
-            t.start()
-        for t in threads:
-            t.join()
-        self.errors = err
-        for e in err:
-            if e is not None:
-                raise e
-        return out
-
-    def codes(self, fn):
-        """the SphError code of fn on every rank (0: no error)"""
-        try:
-            self.each(fn)
-        except self.nat.SphError:
-            pass
-        return [0 if e is None else getattr(e, "code", repr(e)) for e in self.errors]
-
-    def step(self):
-        def one(r, s):
-            if self.wcsph:
-                s.step_wcsph(1)
-                return None
-            st = stat_row(s.step(1))
-            if self.active:
-                s.rigid_step()
-            return st
-        return self.each(one)
-
-    def gather(self, field):
-        n = self.sims[0].n_fluid
-        out, seen = None, np.zeros(n, dtype=np.int32)
-        for s in self.sims:
-            ids, vals = s.download_owned(field)
-            if out is None:
-                out = np.full((n,) + vals.shape[1:], np.nan, dtype=np.float32)
-            out[ids] = vals
-            np.add.at(seen, ids, 1)
-        return out, bool(np.all(seen == 1))
-
-    def digest(self):
-        """everything resident on every rank, ghosts included, by particle id"""
-        h = hashlib.sha1()
-        for s in self.sims:
-            for field in (self.nat.F_POS, self.nat.F_VEL, self.nat.F_RHO):
-                ids, vals = s.download_local(field)
-                order = np.argsort(ids, kind="stable")
-                h.update(ids[order].tobytes()); h.update(vals[order].tobytes())
-            h.update(json.dumps(s.slab_info(), sort_keys=True).encode())
-        return h.hexdigest()
-
-    def cuts(self):
-        return [s.slab_info()["x_lo"] for s in self.sims] + [self.sims[-1].slab_info()["x_hi"]]
-
-    def close(self):
-        for s in self.sims:
-            s.close()
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and bool(np.array_equal(a.view(np.uint32), b.view(np.uint32)))
+def gather_ok(b, field):
+    """(the owned particles by id, whether the ownership is a partition): the flag goes into the report instead of an assertion"""
+    out, seen = gather_by_id(b.sims, field)
+    return out, bool(np.all(seen == 1))
 
 
 def one_gpu_state(nat, cfg, steps, rigid=None):
@@ -142,7 +57,7 @@ def mode_equal(nat, cfg, args):
     res["owned"] = [s.slab_info()["owned"] for s in b.sims]
     res["ghosts_after_set"] = [s.slab_info()["ghosts"] for s in b.sims]
     res["n"] = int(a.n_fluid)
-    back = [b.gather(f) for f in (nat.F_POS, nat.F_VEL)] + ([b.gather(nat.F_WARM_K)] if warm is not None else [])
+    back = [gather_ok(b, f) for f in (nat.F_POS, nat.F_VEL)] + ([gather_ok(b, nat.F_WARM_K)] if warm is not None else [])
     res["partition"] = all(ok for _, ok in back)
     res["roundtrip"] = all(same_bits(got, want) for (got, _), want in zip(back, (pos, vel, warm)))
     res["dt_set"] = [s.scalar(nat.S_DELTA_TIME) for s in b.sims] == [a.scalar(nat.S_DELTA_TIME)] * args.world
@@ -153,7 +68,7 @@ def mode_equal(nat, cfg, args):
         if stats_bad is None and any(row != sa for row in sb):
             stats_bad = {"step": k + 1, "one_gpu": sa, "ranks": sb}
         for name, field in (("pos", nat.F_POS), ("vel", nat.F_VEL), ("rho", nat.F_RHO)):
-            got, ok = b.gather(field)
+            got, ok = gather_ok(b, field)
             if first_bad is None and not (ok and same_bits(got, a.download(field))):
                 first_bad = {"step": k + 1, "field": name, "partition": ok}
     res.update({"steps_compared": args.m, "first_difference": first_bad, "stats_difference": stats_bad, "stats_last": sa,
@@ -169,12 +84,12 @@ def mode_roundtrip(nat, cfg, args):
     warm = rng.standard_normal(len(pos)).astype(np.float32)
     b = Ranks(nat, cfg, args.world)
     b.each(lambda r, s: s.slab_set_state(pos, vel, warm, 0.0))
-    back = [b.gather(f) for f in (nat.F_POS, nat.F_VEL, nat.F_WARM_K)]
+    back = [gather_ok(b, f) for f in (nat.F_POS, nat.F_VEL, nat.F_WARM_K)]
     res = {"partition": all(ok for _, ok in back), "equal": [same_bits(got, want) for (got, _), want in zip(back, (pos, vel, warm))],
            "owned": [s.slab_info()["owned"] for s in b.sims], "n": len(pos), "overrides": b.sims[0].overrides()}
     # vel / scalar NULL: zeros
     b.each(lambda r, s: s.slab_set_state(pos))
-    back = [b.gather(f) for f in (nat.F_VEL, nat.F_WARM_K)]
+    back = [gather_ok(b, f) for f in (nat.F_VEL, nat.F_WARM_K)]
     res["null_is_zero"] = all(ok and not got.view(np.uint32).any() for got, ok in back)
     b.close()
     return res
@@ -185,7 +100,7 @@ def mode_refuse(nat, scenes, args):
     E_INVALID, E_OVERFLOW, E_STATE = nat.SPH_E_INVALID, nat.SPH_E_OVERFLOW, nat.SPH_E_STATE
     res = {}
 
-    def group(name, scene, world, calls, capacities=None):
+    def group(name, scene, world, calls, per_rank=None):
         cfg = scenes.get(scene)
         rigid = None
         if cfg.get("solid"):
@@ -193,7 +108,7 @@ def mode_refuse(nat, scenes, args):
             rigid = mesh.rigid_from_config(cfg)
         pos, vel, warm, dt = one_gpu_state(nat, cfg, 0)        # the lattice at rest: valid where a call does not spoil it
         n = len(pos)
-        twin = Ranks(nat, cfg, world, rigid=rigid, capacities=capacities)
+        twin = Ranks(nat, cfg, world, rigid=rigid, per_rank=per_rank)
         want = []
         for _ in range(3):
             twin.step()
@@ -202,7 +117,7 @@ def mode_refuse(nat, scenes, args):
                 twin.step()
             want.append(twin.digest())
         twin.close()
-        b = Ranks(nat, cfg, world, rigid=rigid, capacities=capacities)
+        b = Ranks(nat, cfg, world, rigid=rigid, per_rank=per_rank)
         for _ in range(3):
             b.step()
         for (label, make, code), digest in zip(calls, want):
@@ -239,7 +154,7 @@ def mode_refuse(nat, scenes, args):
     group("wcsph", "wcsph_small", 2, [("scalar", scalar_where_none, E_INVALID)])
     group("rigid", "dfsph_rigid_small", 2, [("body", plain, E_STATE)])
     # rank 2 of 3 owns nothing of the lattice at rest (it lies beyond the fluid) and gets room for 600 particles; the mirrored lattice gives it thousands
-    group("capacity", "dfsph_small", 3, [("one_rank", mirrored, E_OVERFLOW)], capacities={2: 600})
+    group("capacity", "dfsph_small", 3, [("one_rank", mirrored, E_OVERFLOW)], per_rank={2: {"slab_capacity": 600}})
     return res
 
 
@@ -272,9 +187,7 @@ def main():
     ap.add_argument("--mirror", action="store_true")
     ap.add_argument("--out", required=True)
     args = ap.parse_args()
-    os.environ["SPH_DEV"] = "1"
-    os.environ["SPH_RCCL_LIB"] = shim_path()
-    os.environ.setdefault("SPH_SLAB_CHECK", "1")
+    loopback_env()
     from cfd_taichi_amd import _native as nat
     from cfd_taichi_amd import scenes
     if args.mode == "refuse":
