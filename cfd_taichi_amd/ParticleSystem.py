@@ -44,7 +44,6 @@ class ParticleSystem:
         self._solver_kind = name if name in nat.SOLVER_IDS else ("dfsph" if self._rigid_input else "wcsph")
         self._sim = None
         self._make_sim(self._solver_kind)
-        self.particle_num = self._sim.n_fluid                            # :85
         self.boundary_particles_num = self._sim.n_wall                   # :95
         self.grid_num = np.asarray(self._sim.grid, dtype=np.int32)       # :101
         self._3d_to_1d_tran = np.asarray([1, self.grid_num[0] * self.grid_num[2], self.grid_num[0]])   # :102
@@ -53,14 +52,14 @@ class ParticleSystem:
             pos=DeviceField(self, nat.F_POS, writable=True),
             vel=DeviceField(self, nat.F_VEL, writable=True),
             acc=DeviceField(self, nat.F_ACC),
-            rgb=ConstField(self.particle_num, [0.0, 0.28, 1.0]),          # :227
+            rgb=ConstField(lambda: self.particle_num, [0.0, 0.28, 1.0]),          # :227
         )
         self.boundary_particles = ParticleFields(
             pos=DeviceField(self, nat.F_WALL_POS, nat.SPECIES_WALL),
             volume=DeviceField(self, nat.F_WALL_VOL, nat.SPECIES_WALL),
         )
-        self.rgba = ConstField(self.particle_num, [0.0, 0.26, 0.68, 1.0])   # :152
-        self.rgb = ConstField(self.particle_num, [0.0, 0.28, 1.0])          # :117
+        self.rgba = ConstField(lambda: self.particle_num, [0.0, 0.26, 0.68, 1.0])   # :152
+        self.rgb = ConstField(lambda: self.particle_num, [0.0, 0.28, 1.0])          # :117
         has_rigid = self._rigid_input is not None
         self.rigid_particles_num = self._sim.n_rigid if has_rigid else 0
         self.exist_rigid = ScalarField(lambda: 1 if has_rigid else 0)                               # :39-40
@@ -87,6 +86,11 @@ class ParticleSystem:
         print("Solid particle count: {}k".format(self.rigid_particles_num / 1000))
         print("Particle mass: {}".format(self.particle_m))
         print("Grid: {}, Grid count: {}".format(self.grid_num, int(np.prod(self.grid_num))))
+
+    @property
+    def particle_num(self):                               # :85
+        """the live fluid count: the lattice's (:85) until an inlet or a sink of this package changes it (sim.add_particles / remove_in_box)"""
+        return self._sim.n_fluid
 
     # ---- native handle management -------------------------------------------------------------
     def _make_sim(self, kind):

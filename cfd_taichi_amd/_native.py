@@ -31,6 +31,7 @@ S_VERLET_BUILDS = 31
 S_RIGID_ACTIVE = 32
 S_RIGID_ACC, S_RIGID_ALPHA, S_RIGID_MODE = 33, 36, 39
 S_TIME, S_ACCEL, S_GRAVITY_VEC = 40, 41, 44                  # the handle's clock (f64), its acceleration vector (+0, 1, 2) and the base vector g
+S_FLUID_CAPACITY = 47                                         # fluid particles the handle can hold (SphConfig.fluid_capacity, or the lattice's count)
 RIGID_DYNAMIC, RIGID_SCRIPTED, RIGID_FIXED = 0, 1, 2          # sph_rigid_set_mode
 RIGID_MODES = {"dynamic": RIGID_DYNAMIC, "scripted": RIGID_SCRIPTED, "fixed": RIGID_FIXED}
 # `solver.<attribute> = value` (include/sph_mi355x.h SPH_P_*): name of the reference's attribute -> id
@@ -48,6 +49,7 @@ EXPORTS = [
     "sph_set_comm", "sph_rccl_unique_id", "sph_rccl_attach", "sph_rccl_selftest", "sph_get_stream", "sph_plan_slabs", "sph_replan_slabs", "sph_slab_set_overlap", "sph_slab_info", "sph_comm_stats", "sph_download_local", "sph_download_ids",
     "sph_create_rigid", "sph_rigid_step", "sph_rigid_set_active", "sph_rigid_init_data", "sph_slab_set_state",
     "sph_rigid_set_mode", "sph_rigid_set_motion", "sph_rigid_get_load", "sph_set_gravity", "sph_set_forcing",
+    "sph_add_particles", "sph_remove_in_box",
 ]
 
 
@@ -74,7 +76,8 @@ class SphConfig(ctypes.Structure):
         ("arith", ctypes.c_int32),
         ("slab_ghost_layers", ctypes.c_int32),
         ("slab_overlap", ctypes.c_int32),
-        ("reserved", ctypes.c_int32 * 2),
+        ("fluid_capacity", ctypes.c_int32),
+        ("reserved", ctypes.c_int32 * 1),
     ]
 
 
@@ -178,7 +181,8 @@ CORE_EXPORTS = [
 # entry points added without a change of SPH_ABI_VERSION (no struct grew, no signature changed): bound where the library has them, and a call on a
 # library without them raises SphError(SPH_E_STATE)
 OPTIONAL_EXPORTS = ["sph_rigid_set_active", "sph_rigid_init_data", "sph_selftest_stage", "sph_selftest_walk", "sph_slab_set_state",
-                    "sph_rigid_set_mode", "sph_rigid_set_motion", "sph_rigid_get_load", "sph_set_gravity", "sph_set_forcing"]
+                    "sph_rigid_set_mode", "sph_rigid_set_motion", "sph_rigid_get_load", "sph_set_gravity", "sph_set_forcing",
+                    "sph_add_particles", "sph_remove_in_box"]
 
 
 def _bind_core(lib):
@@ -226,6 +230,10 @@ def _bind_core(lib):
         lib.sph_set_gravity.argtypes = [vp, vp]
     if hasattr(lib, "sph_set_forcing"):
         lib.sph_set_forcing.argtypes = [vp, vp, vp, vp]
+    if hasattr(lib, "sph_add_particles"):
+        lib.sph_add_particles.argtypes = [vp, vp, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int32)]
+    if hasattr(lib, "sph_remove_in_box"):
+        lib.sph_remove_in_box.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_int32)]
     return lib
 
 
@@ -299,7 +307,8 @@ class SphError(RuntimeError):
 
 def config_from_dict(config, solver_name=None, device=0, max_neighbors=0, max_wall_neighbors=0, max_density_iters=0,
                      slab_rank=0, slab_count=0, slab_capacity=0, slab_rebalance_every=0, arith=0, slab_ghost_layers=0, slab_overlap=0):
-    """Flatten a reference-style config dict (config/*.json schema) into SphConfig."""
+    """Flatten a reference-style config dict (config/*.json schema) into SphConfig.  `fluid.capacity` (optional, an integer): the fluid
+    particles the handle can ever hold (SphConfig.fluid_capacity: add_particles, emitters); absent or 0: the lattice's own count."""
     scene, sol, fluid = config["scene"], config["solver"], config["fluid"]
     name = solver_name or sol["name"]
     c = SphConfig()
@@ -324,6 +333,10 @@ def config_from_dict(config, solver_name=None, device=0, max_neighbors=0, max_wa
     c.arith = int(arith)
     c.slab_ghost_layers = int(slab_ghost_layers)
     c.slab_overlap = int(slab_overlap)
+    capacity = fluid.get("capacity", 0)
+    if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or capacity < 0:
+        raise ValueError("fluid.capacity must be an integer >= 0, got %r" % (capacity,))
+    c.fluid_capacity = int(capacity)
     return c
 
 
@@ -448,7 +461,7 @@ class Simulation:
         self._h = handle
         sizes = SphSizes()
         self._check(self._lib.sph_get_sizes(self._h, ctypes.byref(sizes)))
-        self.n_fluid, self.n_wall, self.n_rigid = sizes.n_fluid, sizes.n_wall, sizes.n_rigid
+        self._n_fluid, self.n_wall, self.n_rigid = sizes.n_fluid, sizes.n_wall, sizes.n_rigid
         self.grid = tuple(sizes.grid)
         self.n_cells = sizes.n_cells
         self.max_neighbors, self.max_wall_neighbors = sizes.max_neighbors, sizes.max_wall_neighbors
@@ -459,6 +472,50 @@ class Simulation:
     def _check(self, rc):
         if rc != SPH_OK:
             raise SphError(rc, (self._lib.sph_last_error(self._h) or b"").decode())
+
+    @property
+    def n_fluid(self):
+        """the live particle count: the lattice's until add_particles / remove_in_box change it"""
+        return self._n_fluid
+
+    @property
+    def capacity(self):
+        """fluid particles the handle can hold (SphConfig.fluid_capacity, or the lattice's count)"""
+        try:
+            return int(self.scalar(S_FLUID_CAPACITY))
+        except SphError:              # an implementation of the ABI without the scalar: a handle of a fixed count
+            return self._n_fluid
+
+    def _refresh_count(self):
+        sizes = SphSizes()
+        self._check(self._lib.sph_get_sizes(self._h, ctypes.byref(sizes)))
+        self._n_fluid = sizes.n_fluid
+
+    def add_particles(self, pos, vel=None):
+        """Append len(pos) fluid particles between steps (sph_add_particles): pos (n, 3), vel (n, 3) or None (at rest).  Returns the original id
+        of the first one; the others follow it.  No overlap test is made against the fluid already there."""
+        pos = np.ascontiguousarray(pos, dtype=np.float32)
+        if pos.ndim != 2 or pos.shape[1] != 3:
+            raise ValueError("pos must be (n, 3), got %s" % (pos.shape,))
+        if vel is not None:
+            vel = np.ascontiguousarray(vel, dtype=np.float32)
+            if vel.shape != pos.shape:
+                raise ValueError("expected vel of shape %s, got %s" % (pos.shape, vel.shape))
+        first = ctypes.c_int32(-1)
+        self._check(self._optional("sph_add_particles")(self._h, pos.ctypes.data if len(pos) else None, vel.ctypes.data if vel is not None and len(pos) else None,
+                                                        len(pos), ctypes.byref(first)))
+        self._refresh_count()
+        return int(first.value)
+
+    def remove_in_box(self, lo, hi):
+        """Remove every fluid particle with lo <= x < hi on all three axes, between steps (sph_remove_in_box); the survivors are renumbered
+        densely in the order of their ids.  Returns the number removed."""
+        lo = np.ascontiguousarray(lo, dtype=np.float32).reshape(3)
+        hi = np.ascontiguousarray(hi, dtype=np.float32).reshape(3)
+        removed = ctypes.c_int32(0)
+        self._check(self._optional("sph_remove_in_box")(self._h, lo.ctypes.data, hi.ctypes.data, ctypes.byref(removed)))
+        self._refresh_count()
+        return int(removed.value)
 
     def close(self):
         if getattr(self, "_h", None):

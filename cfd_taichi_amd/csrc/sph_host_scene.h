@@ -261,6 +261,16 @@ int build_scene(SphHandle *h, HostScene &sc)
     int g[3];
     for (int a = 0; a < 3; ++a) g[a] = (int)std::ceil((cf.box_max[a] - cf.box_min[a]) / cell_edge) + 1;   // :100-101 (cell_edge = support but on Verlet handles)
     if (h->N <= 0) return fail(h, SPH_E_INVALID, "scene has no fluid particles");
+    // SphConfig.fluid_capacity: the particles the handle can ever hold (sph_add_particles).  What is decided once, at creation, is decided by it --
+    // the arrays' size, the cell order, the staging of the sweeps; what a step decides (sweep_mode, the list build's split) follows the live count
+    if (cf.fluid_capacity < 0) return fail(h, SPH_E_INVALID, "fluid_capacity %d: 0 (the lattice's count) or a particle count", cf.fluid_capacity);
+    if (cf.fluid_capacity > 0) {
+        if (cf.slab_count > 1) return fail(h, SPH_E_INVALID, "fluid_capacity is not supported on slab handles (their count is the scene's; slab_capacity sizes a slab)");
+        if (g_creating_with_rigid) return fail(h, SPH_E_INVALID, "fluid_capacity is not supported on a handle with a rigid body (get_neighbour_count's quirk reads fluid ids below the body's sample count)");
+        if (cf.fluid_capacity < h->N) return fail(h, SPH_E_INVALID, "fluid_capacity %d is below the lattice's %d particles", cf.fluid_capacity, h->N);
+        if ((long long)cf.fluid_capacity >= (1LL << 28)) return fail(h, SPH_E_INVALID, "fluid_capacity %d: one handle addresses its particle arrays with 32-bit byte offsets (< 2^28 particles)", cf.fluid_capacity);
+    }
+    const int ncap = cf.fluid_capacity > 0 ? cf.fluid_capacity : h->N;
     long long C = (long long)g[0] * g[1] * g[2];
     if (C <= 0 || C > 0x7ffffff0LL) return fail(h, SPH_E_INVALID, "grid too large");
 
@@ -312,7 +322,7 @@ int build_scene(SphHandle *h, HostScene &sc)
         // iisph 1M 37 -> 48; wcsph 1M 1348 -> 1423, 250k equal or 3% slower); scenes of tens of thousands of particles are launch-bound and
         // run 5-8% faster in the reference's own order.  SPH_CELL_ORDER=linear|morton forces one, SPH_CELL_TILE=4|8|16 the tile edge.
         const char *e = dev_env(&h->overrides, "SPH_CELL_ORDER"), *t = dev_env(&h->overrides, "SPH_CELL_TILE");
-        const bool morton = e && !strcmp(e, "morton") ? true : e && !strcmp(e, "linear") ? false : h->N >= (cf.solver == SPH_SOLVER_WCSPH ? 1 << 19 : 1 << 17);
+        const bool morton = e && !strcmp(e, "morton") ? true : e && !strcmp(e, "linear") ? false : ncap >= (cf.solver == SPH_SOLVER_WCSPH ? 1 << 19 : 1 << 17);
         c.order = morton ? CELL_ORDER_TILED : CELL_ORDER_LINEAR;
         const int edge = t ? atoi(t) : 4;
         c.tbits = edge >= 16 ? 4 : edge >= 8 ? 3 : 2;
@@ -328,7 +338,7 @@ int build_scene(SphHandle *h, HostScene &sc)
     c.strict_cells = cf.slab_count > 1 ? 1 : 0;
     c.n = h->N;                                    // refined below for slab handles
     c.gw_left = c.gw_right = -1; c.ghost_walk = 0;
-    c.stride = (h->N + 63) / 64 * 64;
+    c.stride = (ncap + 63) / 64 * 64;             // (the capacity: c.n is the live count)
     // (Verlet lists hold (1 + skin)^3 as many pairs: default capacity 80 there)
     c.kmax = ((cf.max_neighbors > 0 ? cf.max_neighbors : (h->verlet ? 80 : 64)) + 3) & ~3;        // rows come in groups of four
     c.kbmax = ((cf.max_wall_neighbors > 0 ? cf.max_wall_neighbors : (h->verlet ? 80 : 64)) + 3) & ~3;
@@ -389,7 +399,7 @@ int build_scene(SphHandle *h, HostScene &sc)
     h->init_ids.resize((size_t)N);
     for (int i = 0; i < N; ++i) h->init_ids[i] = i;
     h->n_owned = N;
-    h->ncap = N;
+    h->ncap = ncap;
     if (h->slab) {
         h->slab_rank = cf.slab_rank; h->nslab = cf.slab_count;
         if (h->slab_rank < 0 || h->slab_rank >= h->nslab) return fail(h, SPH_E_INVALID, "slab_rank %d out of range [0,%d)", h->slab_rank, h->nslab);
@@ -550,11 +560,13 @@ int build_scene(SphHandle *h, HostScene &sc)
     } while (0)
 constexpr int kBnlSplit9Below = 65536, kBnlSplitBelow = 100000;   // k_build_nl_split with nine / three waves per 64 particles up to these sizes (unstaged handles)
 // dynamic LDS of a staged sweep: bytes per staged particle x capacity (else the occupancy-experiment knob)
-inline int sweep_mode(const SphHandle *h)
+inline int sweep_mode_at(const SphHandle *h, int n)
 {
     if (h->staged) return SWEEP_STAGED;
-    return (!h->slab && h->opt_quad && h->c.n <= h->quad_below) ? SWEEP_QUAD : SWEEP_PLAIN;
+    return (!h->slab && h->opt_quad && n <= h->quad_below) ? SWEEP_QUAD : SWEEP_PLAIN;
 }
+// (by the live count: a handle with a capacity may cross quad_below between two steps; the modes give the same bits)
+inline int sweep_mode(const SphHandle *h) { return sweep_mode_at(h, h->c.n); }
 // partials of the block reductions: one per 256 particles, or one per 64 from quad sweeps (k_finalize_mean adds them in groups of four)
 inline int partial_group(const SphHandle *h) { return sweep_mode(h) == SWEEP_QUAD ? 4 : 1; }
 inline int partial_count(const SphHandle *h) { return sweep_mode(h) == SWEEP_QUAD ? (h->c.n + 63) / 64 : h->nblocks; }
@@ -563,7 +575,8 @@ inline RigidView rigid_view_or_none(const SphHandle *h);
 
 inline bool is_dfsph(const SphHandle *h) { return h->cfg.solver == SPH_SOLVER_DFSPH; }
 // (grad W_ib, V_b) of every wall-list entry, written by D1 and read by D2-D7 of the same step (for_wall_cache); nullptr: the sweeps walk the wall lists
-inline float4 *wall_cache(const SphHandle *h) { return h->wall_gc; }
+// (a handle whose capacity lies above quad_below owns the cache and uses it once its live count does too: quad sweeps walk the wall lists)
+inline float4 *wall_cache(const SphHandle *h) { return sweep_mode(h) == SWEEP_QUAD ? nullptr : h->wall_gc; }
 inline bool is_pressure_solver(const SphHandle *h) { return h->cfg.solver == SPH_SOLVER_PCISPH || h->cfg.solver == SPH_SOLVER_IISPH; }
 // solvers with a per-particle scalar that must follow the particle through the sort: dfsph warm_start_k, iisph p_past
 inline bool carries_scalar(const SphHandle *h) { return h->cfg.solver == SPH_SOLVER_DFSPH || h->cfg.solver == SPH_SOLVER_IISPH; }
@@ -666,6 +679,7 @@ int alloc_device(SphHandle *h, const HostScene &sc)
     if ((rc = dalloc(h, &h->nlb, (n + 64) * (size_t)c.kbpitch))) return rc;
     // the wall terms of the solver loops from a per-step cache: 16 B per wall-list row (1 GiB per million particles at 64 rows, allocated like the list
     // itself; only the rows of particles next to a wall are ever touched).  Not for quad sweeps (small scenes), not where the relaxed sweeps run.
+    // Asked of the capacity: allocated whenever some live count up to it would want it (sweep_mode_at is monotone in the count).
     const bool want_wall_cache = h->cfg.solver == SPH_SOLVER_DFSPH && c.boundary_handle && h->Nb > 0 && h->opt_wall_cache;
     {
         // LDS staging of the gather operands (plan in k_build_nl): DFSPH, PCISPH and IISPH on the Morton curve; SPH_STAGE=0 turns it off, SPH_STAGE_CAP sets the capacity
@@ -705,7 +719,7 @@ int alloc_device(SphHandle *h, const HostScene &sc)
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = (size_t)1 << 62;
         const size_t gc_bytes = (n + 64) * (size_t)c.kbpitch * sizeof(float4);
-        if (want_wall_cache && sweep_mode(h) != SWEEP_QUAD && !h->wall_grad && gc_bytes <= ((size_t)64 << 30) && gc_bytes <= free_b / 2)
+        if (want_wall_cache && sweep_mode_at(h, h->ncap) != SWEEP_QUAD && !h->wall_grad && gc_bytes <= ((size_t)64 << 30) && gc_bytes <= free_b / 2)
             if ((rc = dalloc(h, &h->wall_gc, (n + 64) * (size_t)c.kbpitch))) return rc;
     }
     if (h->verlet) {      // the wall sums of the step (density -> force kernel) and the positions of the last list build

@@ -553,6 +553,8 @@ struct NlAhead {
 // The 32-bit walks (this one, walk_list_quad, walk_staged) read one group past a list's end.  Rows past a particle's count hold stale but
 // valid indices -- the buffer is zero-initialised, only ever holds indices < n, and one spare tile pads the end -- so the speculative
 // loads are always in bounds.  NlWriter::flush (zero_next) keeps that true on nl16 handles, where a stale group could hold packed 16-bit pairs.
+// A handle whose count shrinks (sph_remove_in_box) keeps entries from when it held more: they index below the capacity, which is what
+// every operand array is sized by, so "in bounds" holds there too; rows of tiles past the live count are never walked.
 template <class T, class Fetch, class Use>
 __device__ __forceinline__ void walk_list(const uint32_t *__restrict__ base, int cnt, Fetch fetch, Use use)
 {
@@ -2672,6 +2674,72 @@ __global__ __launch_bounds__(kBlock) void k_sort_in_scalar(int n, const float *_
     int s = blockIdx.x * kBlock + threadIdx.x;
     if (s >= n) return;
     dst[s] = src[id[s]];
+}
+
+// ======================================================================================
+// particles that arrive and leave between steps (sph_add_particles / sph_remove_in_box)
+// ======================================================================================
+// Append: slots [n_old, n_old + m) of the CURRENT buffers take the new particles with the ids first_id + i -- the highest ids of the handle, so
+// inside its cell each sits behind every older particle, where k_order_gather of a fresh handle that holds the same particles would put it.
+// rows = 3 m floats of positions, then (has_vel) 3 m floats of velocities.  A new particle is a particle at creation: the carried scalar
+// (warm_start_k / iisph's last pressure) and the last step's rho / pbf_lambda / delta_pos read 0 until a step writes them.
+__global__ __launch_bounds__(kBlock) void k_append(int n_old, int m, int first_id, const float *__restrict__ rows, int has_vel, float4 *__restrict__ P,
+                                                   float4 *__restrict__ V, float *__restrict__ warm, int *__restrict__ id, float4 *__restrict__ x0,
+                                                   float *__restrict__ rho, float *__restrict__ lambda, float4 *__restrict__ delta_pos)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= m) return;
+    const int s = n_old + i;
+    const float4 p = make_float4(rows[3 * (size_t)i], rows[3 * (size_t)i + 1], rows[3 * (size_t)i + 2], 0.f);
+    const float *vr = rows + 3 * (size_t)m;
+    P[s] = p;
+    V[s] = has_vel ? make_float4(vr[3 * (size_t)i], vr[3 * (size_t)i + 1], vr[3 * (size_t)i + 2], 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
+    if (warm) warm[s] = 0.f;
+    id[s] = first_id + i;
+    if (x0) x0[s] = p;
+    rho[s] = 0.f;
+    if (lambda) lambda[s] = 0.f;
+    if (delta_pos) delta_pos[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// Remove: the sink's box test, lo[k] <= x[k] < hi[k] on all three axes in f32.  One function for the flags and the compaction, on the same
+// stored positions: both see the same verdict.
+struct RemoveBox { float lo[3], hi[3]; };
+__device__ __forceinline__ int in_remove_box(const RemoveBox &b, float4 p)
+{
+    return (b.lo[0] <= p.x && p.x < b.hi[0] && b.lo[1] <= p.y && p.y < b.hi[1] && b.lo[2] <= p.z && p.z < b.hi[2]) ? 1 : 0;
+}
+// flag per slot, and the same flag scattered to the particle's id (every id below n is held by exactly one slot: all n entries are written).
+// The two exclusive scans over them (k_scan_tiles / k_scan_sums / k_scan_add, which zero the flags as they read them) give the removed
+// particles in front of a slot -- the compaction -- and the removed ids below an id -- the renumbering.
+__global__ __launch_bounds__(kBlock) void k_remove_flag(int n, RemoveBox box, const float4 *__restrict__ P, const int *__restrict__ id,
+                                                        int *__restrict__ flag_slot, int *__restrict__ flag_id)
+{
+    const int s = blockIdx.x * kBlock + threadIdx.x;
+    if (s >= n) return;
+    const int f = in_remove_box(box, P[s]);
+    flag_slot[s] = f;
+    flag_id[id[s]] = f;
+}
+__global__ void k_remove_count(int n, RemoveBox box, const float4 *__restrict__ P, const int *__restrict__ scan_slot, int *__restrict__ total)
+{
+    *total = scan_slot[n - 1] + in_remove_box(box, P[n - 1]);
+}
+// stable compaction into the other buffer of each pair: survivors keep the device order and the order of their ids
+__global__ __launch_bounds__(kBlock) void k_remove_compact(int n, RemoveBox box, const int *__restrict__ scan_slot, const int *__restrict__ scan_id,
+                                                           const float4 *__restrict__ Pin, const float4 *__restrict__ Vin, const float *__restrict__ warm_in,
+                                                           const int *__restrict__ id_in, float4 *__restrict__ Pout, float4 *__restrict__ Vout,
+                                                           float *__restrict__ warm_out, int *__restrict__ id_out)
+{
+    const int s = blockIdx.x * kBlock + threadIdx.x;
+    if (s >= n) return;
+    const float4 p = Pin[s];
+    if (in_remove_box(box, p)) return;
+    const int d = s - scan_slot[s], o = id_in[s];
+    Pout[d] = p;
+    Vout[d] = Vin[s];
+    if (warm_in) warm_out[d] = warm_in[s];
+    id_out[d] = o - scan_id[o];
 }
 
 // device arithmetic self-test (sph_selftest_math)

@@ -527,6 +527,134 @@ int sph_rigid_get_load(SphHandle *h, double force[3], double torque[3])
     return SPH_OK;
 }
 
+// ---- inlets and sinks ---------------------------------------------------------------------------------------
+static int flow_refused(SphHandle *h, const char *call)
+{
+    if (h->slab) return fail(h, SPH_E_STATE, "%s is not available on a slab handle", call);
+    if (h->rigid) return fail(h, SPH_E_STATE, "%s is not available on a handle with a rigid body", call);
+    return SPH_OK;
+}
+
+// The live count is now `n`: what the host caches from it, and what the steps so far left behind that a fresh handle of these particles would
+// not have -- the tail of slab_state_commit, but for what travels with the handle (delta_time, the clock, gravity and forcing, the carried
+// scalars of the particles that stay, pcisph's delta).  The density loop's stamps start at 0 again, so the arrays that hold stamps and per-tile
+// flags of earlier sweeps are cleared with them (staged dfsph handles only; a few ints per tile).
+static int fluid_count_changed(SphHandle *h, int n)
+{
+    hipStream_t s = h->stream;
+    h->N = n; h->n_owned = n;
+    h->c.n = n;
+    h->nblocks = (n + kBlock - 1) / kBlock;
+    h->nl_valid = false; h->density_valid = false; h->lists_predate_flag = false;
+    h->flow_stamp = h->flow_last = 0; h->flow_d6 = kNoFlow;
+    h->dens_sparse = false; h->dens_first = true; h->pending_div = kNoRide;
+    h->pbf_fields = false;
+    const void *stamped[] = {h->wave_dirty, h->changed8, h->dens_hot, h->dens_order, h->tile_nbr, h->need6, h->need7, h->tile_nz, h->worked6, h->worked7,
+                             h->dens_bcast, h->pci_zero_press};
+    for (const void *p : stamped)
+        if (const size_t bytes = p ? dalloc_bytes(h, p) : 0) HIP_TRY(h, hipMemsetAsync(const_cast<void *>(p), 0, bytes, s));
+    if (h->verlet) {              // the lists of the last build know neither the new particles nor the new slots: the next step builds them
+        h->ds_host->moved = 1;
+        HIP_TRY(h, hipMemcpyAsync(&h->ds->moved, &h->ds_host->moved, sizeof(int), hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(h, hipStreamSynchronize(s));
+    for (int k = 0; k < 8; ++k)                                      // captured wcsph step pairs carry the old count and grids as launch arguments
+        if (h->wcsph_graph[k]) { (void)hipGraphExecDestroy(h->wcsph_graph[k]); h->wcsph_graph[k] = nullptr; }
+    return SPH_OK;
+}
+
+int sph_add_particles(SphHandle *h, const float *pos, const float *vel, size_t n, int32_t *first_id)
+{
+    if (!h) return SPH_E_INVALID;
+    if (int rc = flow_refused(h, "sph_add_particles")) return rc;
+    if (n == 0) { if (first_id) *first_id = h->N; return SPH_OK; }
+    if (!pos) return fail(h, SPH_E_INVALID, "sph_add_particles: null positions");
+    if (n > (size_t)(h->ncap - h->N))
+        return fail(h, SPH_E_INVALID, "sph_add_particles: %d particles held, %zu more exceed the capacity of %d (SphConfig.fluid_capacity)", h->N, n, h->ncap);
+    const float lo[3] = {(float)h->cfg.box_min[0], (float)h->cfg.box_min[1], (float)h->cfg.box_min[2]};
+    const float hi[3] = {(float)h->cfg.box_max[0], (float)h->cfg.box_max[1], (float)h->cfg.box_max[2]};
+    for (size_t i = 0; i < n; ++i)
+        for (int a = 0; a < 3; ++a) {
+            const float x = pos[3 * i + a];
+            if (!std::isfinite(x) || (vel && !std::isfinite(vel[3 * i + a]))) return fail(h, SPH_E_INVALID, "sph_add_particles: particle %zu has a coordinate or velocity that is not finite", i);
+            if (!(lo[a] < x && x < hi[a])) return fail(h, SPH_E_INVALID, "sph_add_particles: particle %zu lies at %g on axis %d, not strictly inside the box (%g, %g)", i, (double)x, a, (double)lo[a], (double)hi[a]);
+        }
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    HIP_TRY(h, hipStreamSynchronize(s));
+    // one copy of the new rows (positions, then velocities) and one k_append; the staging buffer holds 3 x capacity floats, so a call that brings
+    // more than half the capacity WITH velocities goes in two
+    const bool pbf = h->cfg.solver == SPH_SOLVER_PBF;
+    const size_t per = vel ? 6 : 3, room = 3 * (size_t)h->c.stride / per;
+    std::vector<float> rows;
+    int at = h->N;
+    for (size_t first = 0; first < n; first += room) {
+        const size_t m = std::min(room, n - first);
+        rows.assign(pos + 3 * first, pos + 3 * (first + m));
+        if (vel) rows.insert(rows.end(), vel + 3 * first, vel + 3 * (first + m));
+        HIP_TRY(h, hipMemcpyAsync(h->staging, rows.data(), sizeof(float) * rows.size(), hipMemcpyHostToDevice, s));
+        ProfScope ps(h, K_TRANSFER);
+        hipLaunchKernelGGL(k_append, grid_for((int)m), dim3(kBlock), 0, s, at, (int)m, at, (const float *)h->staging, vel ? 1 : 0, h->P[h->pcur], h->V[h->vcur],
+                           carries_scalar(h) ? h->warm[h->wcur] : (float *)nullptr, h->id[h->icur], h->x0, h->rho, pbf ? h->aux : (float *)nullptr,
+                           pbf ? h->X[0] : (float4 *)nullptr);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipStreamSynchronize(s));          // (rows is reused)
+        at += (int)m;
+    }
+    if (first_id) *first_id = h->N;
+    return fluid_count_changed(h, at);
+}
+
+int sph_remove_in_box(SphHandle *h, const float lo[3], const float hi[3], int32_t *removed)
+{
+    if (!h) return SPH_E_INVALID;
+    if (int rc = flow_refused(h, "sph_remove_in_box")) return rc;
+    if (!lo || !hi) return fail(h, SPH_E_INVALID, "sph_remove_in_box: null argument");
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    HIP_TRY(h, hipStreamSynchronize(s));
+    const int n = h->c.n, stride = h->c.stride, nt = (n + kScanTile - 1) / kScanTile;
+    RemoveBox box;
+    for (int a = 0; a < 3; ++a) { box.lo[a] = lo[a]; box.hi[a] = hi[a]; }
+    // scratch between steps: the sort's three int arrays (rewritten by the next sort before anything reads them) and the staging buffer as
+    // three int arrays of `stride` entries -- the scan over ids, the two scans' tile sums, the count in the last word
+    int *flag_slot = h->cell_of, *flag_id = h->rank, *scan_slot = h->slot_src;
+    int *scan_id = (int *)h->staging, *sums_slot = scan_id + stride, *sums_id = scan_id + 2 * (size_t)stride, *total = scan_id + 3 * (size_t)stride - 1;
+    const dim3 g = grid_for(n), b(kBlock);
+    const float4 *P = h->P[h->pcur];
+    const int *id = h->id[h->icur];
+    {
+        ProfScope ps(h, K_TRANSFER);
+        hipLaunchKernelGGL(k_remove_flag, g, b, 0, s, n, box, P, id, flag_slot, flag_id);
+        hipLaunchKernelGGL(k_scan_tiles, dim3(nt), b, 0, s, flag_slot, scan_slot, sums_slot, n, (const int *)nullptr);
+        hipLaunchKernelGGL(k_scan_sums, dim3(1), b, 0, s, sums_slot, nt, (const int *)nullptr);
+        hipLaunchKernelGGL(k_scan_add, g, b, 0, s, scan_slot, (const int *)sums_slot, n, (const int *)nullptr, 0);
+        hipLaunchKernelGGL(k_scan_tiles, dim3(nt), b, 0, s, flag_id, scan_id, sums_id, n, (const int *)nullptr);
+        hipLaunchKernelGGL(k_scan_sums, dim3(1), b, 0, s, sums_id, nt, (const int *)nullptr);
+        hipLaunchKernelGGL(k_scan_add, g, b, 0, s, scan_id, (const int *)sums_id, n, (const int *)nullptr, 0);
+        hipLaunchKernelGGL(k_remove_count, dim3(1), dim3(1), 0, s, n, box, P, (const int *)scan_slot, total);
+    }
+    HIP_TRY(h, hipGetLastError());
+    int r = -1;
+    HIP_TRY(h, hipMemcpyAsync(&r, total, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    if (r < 0 || r > n) return fail(h, SPH_E_STATE, "internal: sph_remove_in_box counted %d of %d particles", r, n);
+    if (r == n) return fail(h, SPH_E_INVALID, "sph_remove_in_box: the box holds all %d particles (an empty handle is not supported)", n);
+    if (removed) *removed = r;
+    if (r == 0) return SPH_OK;
+    const bool carry = carries_scalar(h);
+    {
+        ProfScope ps(h, K_TRANSFER);
+        hipLaunchKernelGGL(k_remove_compact, g, b, 0, s, n, box, (const int *)scan_slot, (const int *)scan_id, P, (const float4 *)h->V[h->vcur],
+                           carry ? (const float *)h->warm[h->wcur] : (const float *)nullptr, id, h->P[1 - h->pcur], h->V[1 - h->vcur], h->warm[1 - h->wcur],
+                           h->id[1 - h->icur]);
+    }
+    HIP_TRY(h, hipGetLastError());
+    h->pcur ^= 1; h->vcur ^= 1; h->icur ^= 1;
+    if (carry) h->wcur ^= 1;
+    return fluid_count_changed(h, n - r);
+}
+
 void sph_destroy(SphHandle *h)
 {
     if (!h) return;
@@ -1130,6 +1258,7 @@ int sph_get_scalar(SphHandle *h, int which, double *out)
     case SPH_S_ARITH_RELAXED: *out = (use_relaxed(h) || h->verlet || relaxed_pressure(h) || relaxed_unstaged(h) || relaxed_pbf(h)) ? 1.0 : 0.0; return SPH_OK;
     case SPH_S_RIGID_ACTIVE: *out = rigid_binned(h) ? 1.0 : 0.0; return SPH_OK;
     case SPH_S_RIGID_MODE: *out = h->rigid ? (double)h->rigid_mode : 0.0; return SPH_OK;
+    case SPH_S_FLUID_CAPACITY: *out = (double)(h->slab ? h->N : h->ncap); return SPH_OK;      // (a slab handle's ncap is its slab's: sph_slab_info)
     case SPH_S_TIME: { int rc = read_scalars(h); if (rc) return rc; *out = h->ds_host->sim_time; return SPH_OK; }
     case SPH_S_ACCEL: case SPH_S_ACCEL + 1: case SPH_S_ACCEL + 2:
         if (h->frc.on) {                                            // formed on the device (k_accel_eval): by the last step, or by a set call since

@@ -34,13 +34,15 @@ class DeviceField:
 
 
 class ConstField:
-    """Host-resident constant-per-particle field (colours)."""
+    """Host-resident constant-per-particle field (colours).  n: the particle count, or a callable that gives the count of the moment (the fluid's,
+    which inlets and sinks change)."""
 
     def __init__(self, n, value):
         self._n, self._value = n, np.asarray(value, dtype=np.float32)
 
     def to_numpy(self):
-        return np.broadcast_to(self._value, (self._n,) + self._value.shape).copy()
+        n = self._n() if callable(self._n) else self._n
+        return np.broadcast_to(self._value, (n,) + self._value.shape).copy()
 
     def fill(self, value):
         self._value = np.asarray(value, dtype=np.float32)

@@ -8,7 +8,9 @@ t += iter_cnt * solver.delta_time[None] (:173); stops at t > 4.0 (:205) or after
 scene.is_output_ply) it writes ASCII PLY frames `output_%06d.ply` at scene.output_fps like main.py:189-195 (vertex
 xyz + the constant RGBA of ParticleSystem.py:152) and, when a rigid body exists, `obj_%06d.obj` of its mesh (:196-200).
 --release-rigid-at FRAME runs the release sequence the reference keeps commented out at main.py:100-106 when frame_cnt reaches FRAME: a body
-created with `solid.active: false` drops into the fluid as it is then."""
+created with `solid.active: false` drops into the fluid as it is then.
+`scene.emitters` / `scene.sinks` (cfd_taichi_amd/emitter.py; the handle needs a `fluid.capacity`): after every solver step the sinks are applied,
+then the emitters; the PLY frames hold the particles of the moment.  Single GPU, no rigid body."""
 import argparse
 import importlib
 import os
@@ -16,7 +18,7 @@ import time
 
 import numpy as np
 
-from . import ParticleSystem, rigid_solver, utils
+from . import ParticleSystem, emitter, rigid_solver, utils
 
 
 LAST = {}      # the objects of the last single-GPU main() call (ps, solver, rigid), for a caller that embeds the runner and reads the end state
@@ -43,6 +45,8 @@ def main_sharded(args, config):
     rank, world, local = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"]), int(os.environ.get("LOCAL_RANK", "0"))
     if config.get("solid"):
         raise SystemExit("rigid bodies are not sharded: run this config on one GPU")
+    if config["scene"].get("emitters") or config["scene"].get("sinks") or config["fluid"].get("capacity"):
+        raise SystemExit("emitters, sinks and fluid.capacity are not sharded: run this config on one GPU")
     own_gpu = torch.cuda.device_count() >= int(os.environ.get("LOCAL_WORLD_SIZE", world))
     device = local if own_gpu else 0
     if own_gpu:
@@ -112,6 +116,7 @@ def main(argv=None):
     solver = getattr(module, name + "_solver")(ps, config)
     rs = rigid_solver(ps, config) if config.get("solid", {}) else None           # :69-71
     iter_cnt = solver_config.get("iter_cnt")
+    emitters, sinks = emitter.from_config(config)
     ply_dir = args.ply_dir or ("./output" if scene_config.get("is_output_ply", False) else None)
     if ply_dir:
         os.makedirs(ply_dir, exist_ok=True)
@@ -128,12 +133,16 @@ def main(argv=None):
             ps.init_rigid_particles_data()
         for _ in range(iter_cnt):
             solver.step()
+            if emitters or sinks:
+                emitter.apply(ps._sim, emitters, sinks)
         for _ in range(iter_cnt):
             if rs and ps.active_rigid[None] == 1:
                 rs.step()
         frame_cnt += 1
         t += iter_cnt * solver.delta_time[None]
         if ply_dir and (t / frame_time) > ply_cnt:                               # :189
+            if len(np_rgba) != ps.particle_num:                                   # an emitter or a sink changed the count
+                np_rgba = ps.rgba.to_numpy()
             write_ply_ascii(os.path.join(ply_dir, "output_%06d.ply" % ply_cnt), ps.fluid_particles.pos.to_numpy(), np_rgba)
             if ps.exist_rigid[None] == 1:                                        # :196-200
                 ps.update_mesh_vextics()
@@ -144,7 +153,7 @@ def main(argv=None):
             break
     print("frames: %d, simulated time: %.6f s, PLY frames: %d" % (frame_cnt, t, ply_cnt))
     print("Simulation time: {}".format(time.time() - start_time))               # :211
-    LAST.update(ps=ps, solver=solver, rigid=rs)
+    LAST.update(ps=ps, solver=solver, rigid=rs, emitters=emitters, sinks=sinks)
     return frame_cnt, t, ply_cnt
 
 

@@ -153,6 +153,30 @@ SCENES.update({
 })
 
 
+def _with_flow(cfg, capacity, emitters=(), sinks=()):
+    cfg["fluid"]["capacity"] = int(capacity)
+    if emitters:
+        cfg["scene"]["emitters"] = [dict(e) for e in emitters]
+    if sinks:
+        cfg["scene"]["sinks"] = [dict(s) for s in sinks]
+    return cfg
+
+
+SCENES.update({
+    # not the reference's: inlets and sinks (cfd_taichi_amd/emitter.py).
+    # A tap filling a tank: a puddle two layers deep (512 particles) under a downward jet of 8 x 8 particles at 2 m/s from 0.7 m, clear of the
+    # puddle; the jet runs for 0.6 s (a layer every 25 ms: 24 layers, 1 536 particles) into a capacity of five puddles
+    "filling_tank_dfsph": lambda: _with_flow(_scene("dfsph", 1e-3, [1.0, 1.0, 1.0], [0.8, 0.1, 0.8], start_pos=(0.1, 0.05, 0.1)), 2560,
+                                             emitters=[{"center": [0.5, 0.7, 0.5], "direction": [0.0, -1.0, 0.0], "size": [0.4, 0.4], "speed": 2.0,
+                                                        "start": 0.0, "stop": 0.6}]),
+    # A channel: a jet of 4 x 6 particles at 1.5 m/s enters at the left end above a shallow layer, a sink takes what reaches the right end; once
+    # the front has crossed the box the count stays about steady (what enters leaves)
+    "channel_wcsph": lambda: _with_flow(_scene("wcsph", 2.5e-4, [2.0, 0.8, 0.5], [1.6, 0.1, 0.3], start_pos=(0.1, 0.05, 0.1)), 8192,
+                                        emitters=[{"center": [0.2, 0.35, 0.25], "direction": [1.0, 0.0, 0.0], "size": [0.2, 0.3], "speed": 1.5}],
+                                        sinks=[{"box_min": [1.7, 0.0, 0.0], "box_max": [2.0, 0.8, 0.5]}]),
+})
+
+
 def get(name):
     return SCENES[name]()
 

@@ -85,14 +85,18 @@ typedef struct SphConfig {
                                    between steps; 1 = in order only (no second / third stream); 2 = start overlapped.  What "can do both" costs: two more
                                    HIP streams, four events, a tile order and 20 bytes per particle of slab capacity (what a divergence correction that
                                    runs ahead of its loop decision overwrites) -- allocated with the handle; pass 1 where that memory matters */
-    int32_t reserved[2];
+    int32_t fluid_capacity;     /* fluid particles the handle can ever hold (sph_add_particles); 0 = default: the lattice's own count, a handle whose
+                                   count never changes.  > 0: at least the lattice's count and below 2^28; every per-particle array, the cell order
+                                   (Morton from 2^17 particles, wcsph 2^19) and the staging of the sweeps are sized and chosen by it, the sweeps of a
+                                   step by the live count.  SPH_E_INVALID on slab handles (slab_count > 1) and with a rigid body (sph_create_rigid) */
+    int32_t reserved[1];
 } SphConfig;
 
 #define SPH_ARITH_EXACT 0
 #define SPH_ARITH_RELAXED 1
 
 typedef struct SphSizes {
-    int32_t n_fluid;            /* ps.particle_num                 ParticleSystem.py:85 */
+    int32_t n_fluid;            /* ps.particle_num                 ParticleSystem.py:85 (the live count: sph_add_particles / sph_remove_in_box) */
     int32_t n_wall;             /* ps.boundary_particles_num       ParticleSystem.py:95 */
     int32_t n_rigid;            /* ps.rigid_particles_num */
     int32_t grid[3];            /* ps.grid_num                     ParticleSystem.py:101 */
@@ -190,6 +194,8 @@ typedef struct SphRigid {
 #define SPH_S_ACCEL 41             /* +0,1,2: the acceleration vector as the last solver step used it, or as the next will if none has run since
                                     * sph_set_gravity / sph_set_forcing / a written SPH_S_TIME */
 #define SPH_S_GRAVITY_VEC 44       /* +0,1,2: the base vector g of sph_set_gravity (default: scene.gravity * (0, -1, 0) in f32) */
+#define SPH_S_FLUID_CAPACITY 47     /* read-only: fluid particles the handle can hold (SphConfig.fluid_capacity, or the lattice's count); SphSizes.n_fluid is
+                                    * the live count */
 #define SPH_S_VERLET_BUILDS 31    /* diagnostics: list builds so far on a Verlet handle (wcsph under the relaxed arithmetic: the lists carry a skin and are rebuilt on demand) */
 #define SPH_S_ARITH_RELAXED 30    /* diagnostics: 1 if any pair sweep of this handle's solver runs the tolerance-grade kernels (SphConfig.arith asked AND the handle qualifies) */
 
@@ -275,6 +281,23 @@ int sph_rigid_get_load(SphHandle *h, double force[3], double torque[3]);
 int sph_set_gravity(SphHandle *h, const float g[3]);
 /* amp == NULL switches the forcing off (omega and phase are ignored); omega or phase NULL: zeros */
 int sph_set_forcing(SphHandle *h, const double amp[3], const double omega[3], const double phase[3]);
+/* Inlets and sinks: fluid particles that arrive and leave between steps, on a single-GPU handle without a body.  Both calls
+ * synchronise the handle's stream first.  A call that changes the count leaves the handle as a fresh handle that holds the same particles would be
+ * before its first step -- the lists, rho and every other per-particle result of the last step are no longer valid for sph_download until a stage
+ * or a step computes them again -- but for what travels: delta_time, SPH_S_TIME, gravity and forcing, the step counter, warm_start_k and iisph's last
+ * pressure of the particles that stay, and pcisph's delta, a constant of construction.  Refusals leave the handle unchanged: SPH_E_STATE on a slab
+ * handle or a handle with a body.
+ * sph_add_particles appends n particles with the original ids n_fluid .. n_fluid + n - 1 (*first_id = n_fluid, may be NULL): everything indexed by
+ * original id grows at the end, existing ids never change.  pos = 3 n floats, vel = 3 n floats or NULL (at rest).  A new particle has the state of a
+ * particle at creation: warm_start_k = 0, iisph's last pressure 0, rho / pbf_lambda / delta_pos 0 until a step writes them.  No overlap test is made
+ * against the fluid already there.  n == 0 is a no-op.  SPH_E_INVALID: a coordinate or velocity that is not finite, a position not strictly inside
+ * box_min .. box_max, n_fluid + n > SPH_S_FLUID_CAPACITY (a handle created with fluid_capacity 0 refuses every add).
+ * sph_remove_in_box removes every particle with lo[k] <= x[k] < hi[k] on all three axes (f32 compares); *removed = their number (may be NULL).
+ * Survivors keep the order of their ids and are renumbered densely: new id = old id - the number of removed ids below it, so a download afterwards
+ * is the old download with the removed rows squeezed out.  On the device, deterministic; the count comes back in one blocking read.  Nothing
+ * removed: nothing changes, not even what is valid.  SPH_E_INVALID: a box that would remove every particle (an empty handle is not supported). */
+int sph_add_particles(SphHandle *h, const float *pos, const float *vel, size_t n, int32_t *first_id);
+int sph_remove_in_box(SphHandle *h, const float lo[3], const float hi[3], int32_t *removed);
 void sph_destroy(SphHandle *h);
 int sph_get_sizes(SphHandle *h, SphSizes *out);
 const char *sph_last_error(SphHandle *h);
