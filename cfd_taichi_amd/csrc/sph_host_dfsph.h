@@ -1,5 +1,5 @@
 // sph_host_dfsph.h -- a SECTION of csrc/sph_mi355x.hip's one translation unit (included there once, inside its anonymous namespace, in file order):
-// the step stages (sort + lists, density), the wcsph step and the dfsph step with its device-side loop control.  Not a stand-alone header: it uses SphHandle and the helpers defined above its include.
+// the step stages (sort + lists, density), the frame every step runs in (step_begin / step_end / run_steps), the wcsph step and the dfsph step with its device-side loop control.  Not a stand-alone header: it uses SphHandle and the helpers defined above its include.
 
 // ---------------------------------------------------------------------------------------------
 // step stages
@@ -194,10 +194,10 @@ int stage_density(SphHandle *h)
         ProfScope ps(h, K_B_LAMBDA);
         const PbfConsts k = pbf_consts(h);
         if (pbf_qsum(h))
-            hipLaunchKernelGGL((k_pbf_lambda<false, true, true>), grid_for(c.n), dim3(kBlock), 0, s, c, k, h->P[h->pcur], h->WP, h->nl, h->nlb, h->cnt, h->rho, h->aux, h->P[1 - h->pcur], 1);
+            hipLaunchKernelGGL((k_pbf_lambda<false, true, true>), grid_for(c.n), dim3(kBlock), 0, s, c, k, h->P[h->pcur], h->WP, h->nl, h->nlb, h->cnt, h->rho, pbf_arrays(h).lambda, h->P[1 - h->pcur], 1);
         else
         SPH_LAUNCH_PBF(k_pbf_lambda, sweep_mode(h) == SWEEP_QUAD, relaxed_pbf(h), grid_for(c.n), dim3((unsigned)std::max(1, (c.n + 63) / 64)), s, c, k,
-                       h->P[h->pcur], h->WP, h->nl, h->nlb, h->cnt, h->rho, h->aux, h->P[1 - h->pcur], 1);      // the step's own instantiation
+                       h->P[h->pcur], h->WP, h->nl, h->nlb, h->cnt, h->rho, pbf_arrays(h).lambda, h->P[1 - h->pcur], 1);      // the step's own instantiation
         HIP_TRY(h, hipGetLastError());
         h->density_valid = true;
         return SPH_OK;
@@ -206,7 +206,7 @@ int stage_density(SphHandle *h)
     if (h->verlet) {      // wcsph under the relaxed arithmetic: Verlet lists hold pairs beyond h, only the clamped kernel functions may walk them
         ProfScope ps(h, K_W_DENSITY);
         hipLaunchKernelGGL(k_wcsph_density_rx, grid_for(c.n), dim3(kBlock), 0, s, c, h->P[h->pcur], h->V[h->vcur], h->WP, h->nl, h->nlb, h->cnt,
-                           h->rho, h->aux, h->P[1 - h->pcur], h->V[1 - h->vcur], h->wall_grad, h->ds, 1);
+                           h->rho, wcsph_pressure(h), h->P[1 - h->pcur], h->V[1 - h->vcur], h->wall_grad, h->ds, 1);
         h->pcur ^= 1; h->vcur ^= 1;                         // P = (pos, rho), V = (vel, p / rho^2)
         HIP_TRY(h, hipGetLastError());
         h->density_valid = true;
@@ -220,16 +220,16 @@ int stage_density(SphHandle *h)
         const bool split = rx_split(h);
         if (use_relaxed(h))
             hipLaunchKernelGGL(k_density_rx, grid_for(c.n), dim3(kBlock), sweep_lds(h, StageF4<>::kBytes), s, c, h->P[h->pcur], h->V[h->vcur], h->wall_grad, h->wall_gsq,
-                               h->nl, h->cnt, h->warm[h->wcur], h->ds, h->rho, h->aux, h->V[h->vcur], h->stage_src, h->stage_cnt, h->krho,
+                               h->nl, h->cnt, h->warm[h->wcur], h->ds, h->rho, dfsph_alpha(h), h->V[h->vcur], h->stage_src, h->stage_cnt, h->krho,
                                split ? TilePhase{h->tile_order, h->nblocks, 2} : TilePhase{nullptr, 0, 0}, h->id[h->icur], split ? h->rho_orig : (float *)nullptr);
         if (!use_relaxed(h) || split)
         SPH_LAUNCH_RMX(k_density, true, rigid_coupled(h), sweep_mode(h), relaxed_unstaged(h), c.n, sweep_lds(h, StageF4<>::kBytes), s, c, h->P[h->pcur], h->V[h->vcur], h->WP, h->nl, h->nlb,
-                      h->cnt, h->warm[h->wcur], h->ds, h->rho, h->aux, h->P[1 - h->pcur], h->V[h->vcur], rigid_view_or_none(h), h->id[h->icur],
+                      h->cnt, h->warm[h->wcur], h->ds, h->rho, dfsph_alpha(h), h->P[1 - h->pcur], h->V[h->vcur], rigid_view_or_none(h), h->id[h->icur],
                       h->rho_orig, h->stage_src, h->stage_cnt, h->krho, wall_cache(h), split ? TilePhase{h->tile_order, h->nblocks, 1} : TilePhase{nullptr, 0, 0});
     } else {
         ProfScope ps(h, K_W_DENSITY);
         SPH_LAUNCH_RM(k_density, false, rigid_coupled(h), sweep_mode(h), c.n, sweep_lds(h, StageF4<>::kBytes), s, c, h->P[h->pcur], h->V[h->vcur], h->WP, h->nl, h->nlb,
-                      h->cnt, (const float *)nullptr, h->ds, h->rho, h->aux, h->P[1 - h->pcur], h->V[1 - h->vcur], rigid_view_or_none(h), h->id[h->icur],
+                      h->cnt, (const float *)nullptr, h->ds, h->rho, density_aux(h), h->P[1 - h->pcur], h->V[1 - h->vcur], rigid_view_or_none(h), h->id[h->icur],
                       h->rho_orig, h->stage_src, h->stage_cnt, h->krho, (float4 *)nullptr);
         h->pcur ^= 1; h->vcur ^= 1;   // P = (pos, rho), V = (vel, p/rho^2)
     }
@@ -256,6 +256,35 @@ int stage_density(SphHandle *h)
     return SPH_OK;
 }
 
+// sharded pcisph / iisph need the device-side loop control (an in-place all-reduce on the stream)
+int require_async_slab(SphHandle *h)
+{
+    if (h->slab && !slab_async(h))
+        return fail(h, SPH_E_STATE, "pcisph / iisph on slabs need a transport with allreduce_stream (TorchComm) or the native RCCL transport");
+    return SPH_OK;
+}
+
+// What every solver's step does before its own sweeps: the count (solver_base.py:137), the step's acceleration vector if it is forced, reset_grid +
+// update_grid + the lists (:139-141), and compute_all_rho where the solver's step starts with it (all but pbf; after it P = (pos, rho))
+int step_begin(SphHandle *h)
+{
+    int rc;
+    h->simulate_cnt += 1;
+    h->comm_stat[6] += 1;
+    step_head(h);
+    if (is_pressure_solver(h) && (rc = require_async_slab(h))) return rc;
+    if ((rc = stage_sort_and_lists(h))) return rc;
+    return h->cfg.solver == SPH_SOLVER_PBF ? SPH_OK : stage_density(h);
+}
+// ... and behind its integrator: the positions moved, so neither the lists nor the densities describe them
+int step_end(SphHandle *h)
+{
+    HIP_TRY(h, hipGetLastError());
+    h->nl_valid = false;
+    h->density_valid = false;
+    return SPH_OK;
+}
+
 // force of the fluid on the body for wcsph (S = pressure) / pcisph / iisph (PB.w = press_iter / p_iter); see k_rigid_force_p.  On a slab handle
 // the rank that owns a sample's cell column sums its force, and PB must have been refreshed on the ghosts (slab_refresh_w_and_pressure_finalize)
 template <int MODE>
@@ -263,31 +292,22 @@ void launch_rigid_force_p(SphHandle *h, const float4 *P, const float4 *PB, int g
 {
     ProfScope ps(h, K_RIGID);
     hipLaunchKernelGGL(k_rigid_force_p<MODE>, grid_for(h->Nr), dim3(kBlock), 0, h->stream, h->c, h->Nr, h->RPs, h->rid, P, h->rnl, h->rcnt, h->rho,
-                       h->aux, PB, h->ds, h->rforce, gate, h->slab ? 1 : 0, h->geom.x_lo, h->geom.x_hi);
+                       wcsph_pressure(h), PB, h->ds, h->rforce, gate, h->slab ? 1 : 0, h->geom.x_lo, h->geom.x_hi);
 }
 
 int step_wcsph_once(SphHandle *h)
 {
-    int rc;
-    h->simulate_cnt += 1;                                   // solver_base.py:137
-    h->comm_stat[6] += 1;
-    step_head(h);                                           // the step's acceleration vector, if it is forced
-    if ((rc = stage_sort_and_lists(h))) return rc;          // :139-141
+    if (int rc = step_begin(h)) return rc;                  // ... compute_all_rho + the pressures: wcsph_solver.py:32-38
     if (h->verlet) {                                        // the relaxed arithmetic: two kernels over the Verlet lists (sph_relaxed_kernels.h)
         const Consts &cv = h->c;
-        if ((rc = stage_density(h))) return rc;             // pressure_phase, wcsph_solver.py:32-38
         {
             ProfScope ps(h, K_W_FORCE);                     // + kinematic_phase :40-63
             hipLaunchKernelGGL(k_wcsph_force_rx, grid_for(cv.n), dim3(kBlock), 0, h->stream, cv, h->dt_wcsph, h->P[h->pcur], h->V[h->vcur], h->nl, h->cnt,
                                h->wall_grad, h->x0, h->P[1 - h->pcur], h->V[1 - h->vcur], h->VA[0], h->ds);
             h->pcur ^= 1; h->vcur ^= 1;
         }
-        HIP_TRY(h, hipGetLastError());
-        h->nl_valid = false;
-        h->density_valid = false;
-        return SPH_OK;
+        return step_end(h);
     }
-    if ((rc = stage_density(h))) return rc;                 // wcsph_solver.py:34-35
     const Consts &c = h->c;
     if (rigid_coupled(h)) launch_rigid_force_p<RF_WCSPH>(h, h->P[h->pcur], nullptr, GATE_NONE);   // wcsph_solver.py:127, positions of this step
     {
@@ -295,16 +315,13 @@ int step_wcsph_once(SphHandle *h)
         const bool quad = sweep_mode(h) == SWEEP_QUAD;
         const dim3 gf = quad ? dim3((unsigned)std::max(1, (c.n + 63) / 64)) : grid_for(c.n);
 #define SPH_WFORCE(R, Q, RV) hipLaunchKernelGGL((k_wcsph_force<R, Q>), gf, dim3(kBlock), 0, h->stream, c, h->dt_wcsph, h->P[h->pcur], h->V[h->vcur], h->WP, \
-                                                h->nl, h->nlb, h->cnt, h->aux, h->P[1 - h->pcur], h->V[1 - h->vcur], h->VA[0], RV)
+                                                h->nl, h->nlb, h->cnt, wcsph_pressure(h), h->P[1 - h->pcur], h->V[1 - h->vcur], h->VA[0], RV)
         if (rigid_coupled(h)) { if (quad) SPH_WFORCE(true, true, rigid_view(h)); else SPH_WFORCE(true, false, rigid_view(h)); }
         else { if (quad) SPH_WFORCE(false, true, RigidView()); else SPH_WFORCE(false, false, RigidView()); }
 #undef SPH_WFORCE
         h->pcur ^= 1; h->vcur ^= 1;
     }
-    HIP_TRY(h, hipGetLastError());
-    h->nl_valid = false;
-    h->density_valid = false;
-    return SPH_OK;
+    return step_end(h);
 }
 
 // every slab must see a list overflow at the same point, or the others would wait in a collective forever
@@ -321,6 +338,36 @@ int check_overflow_all(SphHandle *h, bool reduced_on_device = false)
     }
     return check_overflow(h);
 }
+
+// The frame of the five sph_step_* entry points: the handle's solver or SPH_E_STATE, a released body that was not prepared, the device, `nsteps` times
+// `once`, the last step's stats, and the one read-back per call that reports a list overflow where the solver's own step has none (overflow is sticky
+// within a call, which keeps the steps asynchronous; on slab handles it is one verdict of all ranks -- a rank that failed alone would leave its peers
+// waiting in the next exchange).  `lead` may take steps of its own first and says how many (wcsph: the replayed step pairs)
+enum StepTail { TAIL_NONE, TAIL_IF_STEPPED, TAIL_ALWAYS };
+struct StepFrame { int solver; const char *wrong_solver; bool rigid_check, refuse_negative; StepTail tail; };
+template <class Once, class Lead>
+int run_steps(SphHandle *h, const StepFrame &f, int nsteps, SphStepStats *last, Once once, Lead lead)
+{
+    if (!h || (f.refuse_negative && nsteps < 0)) return SPH_E_INVALID;
+    if (h->cfg.solver != f.solver) return fail(h, SPH_E_STATE, "%s", f.wrong_solver);
+    if (f.rigid_check)
+        if (int rc = rigid_released_unprepared(h)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    SphStepStats st;
+    memset(&st, 0, sizeof(st));
+    int k = 0;
+    if (int rc = lead(&k)) return rc;
+    for (; k < nsteps; ++k)
+        if (int rc = once(h, &st)) return rc;
+    if (last) *last = st;
+    if (f.tail == TAIL_ALWAYS || (f.tail == TAIL_IF_STEPPED && nsteps > 0)) {
+        if (int rc = read_scalars(h)) return rc;
+        return check_overflow_all(h);
+    }
+    return SPH_OK;
+}
+template <class Once>
+int run_steps(SphHandle *h, const StepFrame &f, int nsteps, SphStepStats *last, Once once) { return run_steps(h, f, nsteps, last, once, [](int *) { return SPH_OK; }); }
 
 // ---- DFSPH launch helpers (buffer roles: see stage_density) --------------------------------------------------
 // tiles of the density loop whose inputs did not change are not recomputed (staged dfsph handles)
@@ -382,11 +429,11 @@ void launch_residual(SphHandle *h, const ResidCtl &lc, const float4 *V, float *o
     const bool split = rx_split(h);
     if (use_relaxed(h)) {
         hipLaunchKernelGGL(k_residual_rx<DENS>, grid_for(c.n), dim3(kBlock), sweep_lds(h, StagePV<>::kBytes), st, c, h->P[h->pcur], V, h->wall_grad, h->nl, h->cnt,
-                           h->rho, h->aux, h->ds, out, h->krho, stage_args(h), rx_half(lc, split));
+                           h->rho, dfsph_alpha(h), h->ds, out, h->krho, stage_args(h), rx_half(lc, split));
         if (!split) return;
     }
     SPH_LAUNCH_RMX(k_residual, DENS, rg, sweep_mode(h), relaxed_unstaged(h), c.n, sweep_lds(h, StagePV<>::kBytes), st, c, h->P[h->pcur], V, h->WP, h->nl, h->nlb, h->cnt,
-                  h->rho, h->aux, h->ds, out, h->krho, stage_args(h), lc, h->P[1 - h->pcur], rg ? rigid_view(h) : RigidView(), h->ncount, (const float4 *)wall_cache(h));
+                  h->rho, dfsph_alpha(h), h->ds, out, h->krho, stage_args(h), lc, h->P[1 - h->pcur], rg ? rigid_view(h) : RigidView(), h->ncount, (const float4 *)wall_cache(h));
 }
 void launch_div_residual(SphHandle *h, int gate, int phase = 0, SpecUndo un = SpecUndo{nullptr, nullptr, nullptr, nullptr, 0}, hipStream_t st = nullptr)          // derivative_iter_all_rho sweep, dfsph_solver.py:252-277
 {
@@ -413,11 +460,11 @@ void launch_correct(SphHandle *h, int kid, const float *src, float4 *V, int gate
     const int n_grid = c.n + (lc.fr.mode >= 0 ? (sweep_mode(h) == SWEEP_QUAD ? 64 : kBlock) : 0);           // a riding decision: one more workgroup
     if (use_relaxed(h)) {
         hipLaunchKernelGGL(k_correct_rx<MODE>, grid_for(n_grid), dim3(kBlock), sweep_lds(h, StagePS<>::kBytes), h->stream, c, h->P[h->pcur], h->wall_grad, h->nl, h->cnt,
-                           h->rho, h->aux, src, h->warm[h->wcur], V, V, h->krho, stage_args(h), rx_half(lc, split));
+                           h->rho, dfsph_alpha(h), src, h->warm[h->wcur], V, V, h->krho, stage_args(h), rx_half(lc, split));
         if (!split) return;
     }
     SPH_LAUNCH_RMX(k_correct, MODE, rigid_coupled(h), sweep_mode(h), relaxed_unstaged(h), n_grid, sweep_lds(h, StagePS<>::kBytes), h->stream, c,
-                  c.kr_split ? h->P[h->pcur] : h->P[1 - h->pcur], h->WP, h->nl, h->nlb, h->cnt, h->rho, h->aux, src, h->warm[h->wcur], V, V, h->krho,
+                  c.kr_split ? h->P[h->pcur] : h->P[1 - h->pcur], h->WP, h->nl, h->nlb, h->cnt, h->rho, dfsph_alpha(h), src, h->warm[h->wcur], V, V, h->krho,
                   stage_args(h), lc, rigid_view_or_none(h), (const float4 *)wall_cache(h));
 }
 
@@ -466,7 +513,7 @@ void launch_rigid_force(SphHandle *h, int gate)            // dfsph_solver.py:21
     const Consts &c = h->c;
     ProfScope ps(h, K_RIGID);
     hipLaunchKernelGGL(k_rigid_force, grid_for(h->Nr), dim3(kBlock), 0, h->stream, c, h->Nr, h->RPs, h->rid, h->P[h->pcur], h->rnl, h->rcnt, h->rho,
-                       h->rho_adv, h->aux, h->ds, h->rforce, gate, h->slab ? h->geom.x_lo : -0x7fffffff, h->slab ? h->geom.x_hi : 0x7fffffff);
+                       h->rho_adv, dfsph_alpha(h), h->ds, h->rforce, gate, h->slab ? h->geom.x_lo : -0x7fffffff, h->slab ? h->geom.x_hi : 0x7fffffff);
 }
 
 // The in-order protocol of a two-column slab handle: the residual's refresh AND its mean in four enqueues instead of six -- [pack + this slab's
@@ -495,7 +542,7 @@ int slab_exchange_resid_and_finalize(SphHandle *h, bool dens, float *val, int mo
     {
         ProfScope ps(h, K_SLAB);
         const ResidLists L{h->edge_list[0], nrl, h->edge_n[0][0], (float *)h->drecv[0], h->edge_list[3], nrr, h->edge_n[3][0], (float *)h->drecv[1]};
-        hipLaunchKernelGGL(k_unpack_resid_decide, dim3((unsigned)((nrl + nrr + kFinBlock - 1) / kFinBlock + 1)), dim3(kFinBlock), 0, s, h->c, L, dens ? 1 : 0, h->aux, h->rho,
+        hipLaunchKernelGGL(k_unpack_resid_decide, dim3((unsigned)((nrl + nrr + kFinBlock - 1) / kFinBlock + 1)), dim3(kFinBlock), 0, s, h->c, L, dens ? 1 : 0, dfsph_alpha(h), h->rho,
                            val, P, S, h->psum, h->pcnt, h->nblocks, h->ds, mode, gather ? h->gath_dev : h->red_dev, partial_group(h), partial_count(h), gather ? h->nslab : 0,
                            dens ? h->flow_d6 : kNoFlow);
     }
@@ -583,10 +630,7 @@ int dfsph_integrate(SphHandle *h)
     hipLaunchKernelGGL(k_dfsph_integrate, grid_for(c.n), dim3(kBlock), 0, h->stream, c, h->P[h->pcur], h->VA[0], h->ds, h->P[1 - h->pcur],
                        h->V[h->vcur]);
     h->pcur ^= 1;
-    HIP_TRY(h, hipGetLastError());
-    h->nl_valid = false;
-    h->density_valid = false;
-    return SPH_OK;
+    return step_end(h);
 }
 
 // One DFSPH step on a single GPU: the reference's two host loops run on the device (k_finalize_mean applies their
@@ -838,13 +882,8 @@ int step_dfsph_host_loops(SphHandle *h, SphStepStats *st)
 
 int step_dfsph_once(SphHandle *h, SphStepStats *st)
 {
-    int rc;
     memset(st, 0, sizeof(*st));
-    h->simulate_cnt += 1;                                   // solver_base.py:137
-    h->comm_stat[6] += 1;
-    step_head(h);                                           // the step's acceleration vector, if it is forced
-    if ((rc = stage_sort_and_lists(h))) return rc;          // :139-141 (reset() is the no-op override, dfsph_solver.py:418-421)
-    if ((rc = stage_density(h))) return rc;                 // initialize(): dfsph_solver.py:423-426
+    if (int rc = step_begin(h)) return rc;                  // (reset() is the no-op override, dfsph_solver.py:418-421); initialize(): :423-426
     const bool host_loops = h->slab && !slab_async(h);      // a transport without allreduce_stream
     return host_loops ? step_dfsph_host_loops(h, st) : step_dfsph_device_loops(h, st);
 }

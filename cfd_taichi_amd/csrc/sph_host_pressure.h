@@ -1,5 +1,5 @@
 // sph_host_pressure.h -- a SECTION of csrc/sph_mi355x.hip's one translation unit (included there once, inside its anonymous namespace, in file order):
-// the pbf, pcisph and iisph steps and the field table of upload / download.  Not a stand-alone header: it uses SphHandle and the helpers defined above its include.
+// the pbf, pcisph and iisph steps.  Not a stand-alone header: it uses SphHandle and the helpers defined above its include.
 
 // ---------------------------------------------------------------------------------------------
 // PBF (csrc/sph_pbf_kernels.h)                                pbf_solver.py:176-187
@@ -43,12 +43,10 @@ PbfConsts pbf_consts(const SphHandle *h)
 int step_pbf_once(SphHandle *h)
 {
     int rc;
-    h->simulate_cnt += 1;                                   // solver_base.py:137
-    h->comm_stat[6] += 1;
-    step_head(h);                                           // the step's acceleration vector, if it is forced
-    if ((rc = stage_sort_and_lists(h))) return rc;          // :139-141
+    if ((rc = step_begin(h))) return rc;
     const Consts &c = h->c;
     const PbfConsts k = pbf_consts(h);
+    const PbfFields f = pbf_arrays(h);
     const bool quad = sweep_mode(h) == SWEEP_QUAD;          // four lanes per particle in all three sweeps (small scenes)
     const bool rx = relaxed_pbf(h);                         // the tolerance-grade pair bodies (SphConfig.arith)
     const bool qsum = pbf_qsum(h);                          // ... on a slab handle, summed as the one-GPU handle of this scene sums them
@@ -56,29 +54,27 @@ int step_pbf_once(SphHandle *h)
     hipStream_t s = h->stream;
     {
         ProfScope ps(h, K_B_LAMBDA);                          // compute_all_lambda :32-52
-        if (qsum) hipLaunchKernelGGL((k_pbf_lambda<false, true, true>), g, dim3(kBlock), 0, s, c, k, h->P[h->pcur], h->WP, h->nl, h->nlb, h->cnt, h->rho, h->aux, h->P[1 - h->pcur], 0);
-        else SPH_LAUNCH_PBF(k_pbf_lambda, quad, rx, g, gq, s, c, k, h->P[h->pcur], h->WP, h->nl, h->nlb, h->cnt, h->rho, h->aux, h->P[1 - h->pcur], 0);
+        if (qsum) hipLaunchKernelGGL((k_pbf_lambda<false, true, true>), g, dim3(kBlock), 0, s, c, k, h->P[h->pcur], h->WP, h->nl, h->nlb, h->cnt, h->rho, f.lambda, h->P[1 - h->pcur], 0);
+        else SPH_LAUNCH_PBF(k_pbf_lambda, quad, rx, g, gq, s, c, k, h->P[h->pcur], h->WP, h->nl, h->nlb, h->cnt, h->rho, f.lambda, h->P[1 - h->pcur], 0);
     }
     if (h->slab && (rc = slab_exchange_field(h, 0, h->P[1 - h->pcur], nullptr, nullptr))) return rc;      // lambda of the ghosts
     {
         ProfScope ps(h, K_B_DELTA);                           // compute_all_delta_pos :55-64, the prediction :26-29, update_all_pos phase 1 :66-84
-        if (qsum) hipLaunchKernelGGL((k_pbf_delta<false, true, true>), g, dim3(kBlock), 0, s, c, k, h->dt_wcsph, h->P[1 - h->pcur], h->V[h->vcur], h->WP, h->nl, h->nlb, h->cnt, h->X[0], h->X[1], h->X[2]);
-        else SPH_LAUNCH_PBF(k_pbf_delta, quad, rx, g, gq, s, c, k, h->dt_wcsph, h->P[1 - h->pcur], h->V[h->vcur], h->WP, h->nl, h->nlb, h->cnt, h->X[0], h->X[1], h->X[2]);
+        if (qsum) hipLaunchKernelGGL((k_pbf_delta<false, true, true>), g, dim3(kBlock), 0, s, c, k, h->dt_wcsph, h->P[1 - h->pcur], h->V[h->vcur], h->WP, h->nl, h->nlb, h->cnt, f.delta_pos, f.pos_new, f.vel_1);
+        else SPH_LAUNCH_PBF(k_pbf_delta, quad, rx, g, gq, s, c, k, h->dt_wcsph, h->P[1 - h->pcur], h->V[h->vcur], h->WP, h->nl, h->nlb, h->cnt, f.delta_pos, f.pos_new, f.vel_1);
     }
-    if (h->slab && (rc = slab_exchange_field(h, 4, h->X[1], h->X[2], nullptr))) return rc;               // their new position and phase-1 velocity
+    if (h->slab && (rc = slab_exchange_field(h, 4, f.pos_new, f.vel_1, nullptr))) return rc;               // their new position and phase-1 velocity
     {
         ProfScope ps(h, K_B_XSPH);                            // update_all_pos phases 2-3 :86-98
         if (h->slab) {
-            if (rx) hipLaunchKernelGGL((k_pbf_xsph_slab<true>), g, dim3(kBlock), 0, s, c, k, h->P[h->pcur], h->X[1], h->X[2], h->cell_start, h->cnt, h->P[1 - h->pcur], h->V[1 - h->vcur]);
-            else hipLaunchKernelGGL((k_pbf_xsph_slab<false>), g, dim3(kBlock), 0, s, c, k, h->P[h->pcur], h->X[1], h->X[2], h->cell_start, h->cnt, h->P[1 - h->pcur], h->V[1 - h->vcur]);
+            if (rx) hipLaunchKernelGGL((k_pbf_xsph_slab<true>), g, dim3(kBlock), 0, s, c, k, h->P[h->pcur], f.pos_new, f.vel_1, h->cell_start, h->cnt, h->P[1 - h->pcur], h->V[1 - h->vcur]);
+            else hipLaunchKernelGGL((k_pbf_xsph_slab<false>), g, dim3(kBlock), 0, s, c, k, h->P[h->pcur], f.pos_new, f.vel_1, h->cell_start, h->cnt, h->P[1 - h->pcur], h->V[1 - h->vcur]);
         } else
-            SPH_LAUNCH_PBF(k_pbf_xsph, quad, rx, g, gq, s, c, k, h->P[h->pcur], h->X[1], h->X[2], h->cell_start, h->P[1 - h->pcur], h->V[1 - h->vcur]);
+            SPH_LAUNCH_PBF(k_pbf_xsph, quad, rx, g, gq, s, c, k, h->P[h->pcur], f.pos_new, f.vel_1, h->cell_start, h->P[1 - h->pcur], h->V[1 - h->vcur]);
     }
     h->pcur ^= 1; h->vcur ^= 1;
-    HIP_TRY(h, hipGetLastError());
-    h->nl_valid = false;
-    h->density_valid = false;
-    h->pbf_fields = true;                                   // pbf_lambda (aux) and delta_pos (X[0]) in the device order of this step
+    if ((rc = step_end(h))) return rc;
+    h->pbf_fields = true;                                   // pbf_lambda and delta_pos in the device order of this step
     return SPH_OK;
 }
 
@@ -124,11 +120,33 @@ int launch_pressure_finalize(SphHandle *h, int mode)
     return SPH_OK;
 }
 
-// sharded pcisph / iisph need the device-side loop control (an in-place all-reduce on the stream)
-int require_async_slab(SphHandle *h)
+// The pressure loop of pcisph / iisph.  `iteration(k)` enqueues iteration k = 1 .. cap whole -- the ones the loop would not run leave at their first
+// instruction (GATE_DENS) -- and the host looks at the control block once per chunk: first after as many iterations as the last step took (the count
+// changes slowly), then every two.  Fills the step's stats and notes which PB holds the final pressures
+template <class Iteration>
+int pressure_loop(SphHandle *h, int cap, float dt, SphStepStats *st, Iteration iteration)
 {
-    if (h->slab && !slab_async(h))
-        return fail(h, SPH_E_STATE, "pcisph / iisph on slabs need a transport with allreduce_stream (TorchComm) or the native RCCL transport");
+    int rc;
+    bool first = true;
+    for (int k = 1, chunk = std::max(2, h->last_iters); k <= cap; chunk = 2) {
+        for (int q = 0; q < chunk && k <= cap; ++q, ++k)
+            if ((rc = iteration(k))) return rc;
+        if ((rc = read_scalars(h))) return rc;
+        if (first) {
+            if ((rc = check_overflow_all(h, slab_async(h)))) return rc;      // (the slabs' flags came with the loop's first reduction)
+            first = false;
+        }
+        if (!h->ds_host->dens_active) break;
+    }
+    st->max_nbrs = h->ds_host->max_nbrs;
+    st->max_wall_nbrs = h->ds_host->max_wall_nbrs;
+    st->lost = h->ds_host->lost;
+    st->n_dens = h->ds_host->dens_it;
+    st->capped = h->ds_host->dens_capped;
+    st->dens_err = h->ds_host->dens_avg;
+    st->dt = dt;
+    h->pb_final = h->ds_host->dens_it & 1;
+    h->last_iters = h->ds_host->dens_it;
     return SPH_OK;
 }
 
@@ -137,19 +155,15 @@ int step_pcisph_once(SphHandle *h, SphStepStats *st)
 {
     int rc;
     memset(st, 0, sizeof(*st));
-    h->simulate_cnt += 1;                                   // solver_base.py:137
-    h->comm_stat[6] += 1;
-    step_head(h);                                           // the step's acceleration vector, if it is forced
-    if ((rc = require_async_slab(h))) return rc;
-    if ((rc = stage_sort_and_lists(h))) return rc;          // :139-141
-    if ((rc = stage_density(h))) return rc;                 // compute_all_rho :239; P = (pos, rho)
+    if ((rc = step_begin(h))) return rc;                    // ... compute_all_rho :239
     const Consts &c = h->c;
     hipStream_t s = h->stream;
     const dim3 g = grid_for(c.n), b(kBlock);
     const float dt = h->dt_wcsph;                           // delta_time never changes in pcisph
     const bool rg = rigid_coupled(h);
     const RigidView rv = rg ? rigid_view(h) : RigidView();
-    float4 *EF = h->X[0], *PF = h->X[1], *PP = h->X[2], *PB[2] = {h->X[3], h->X[4]};
+    const PciFields f = pci_fields(h);
+    float4 *EF = f.ext_force, *PF = f.press_force, *PP = f.pos_predict, *const *PB = f.press;
     const int cap = 80;                                     // max_iteration :21
     hipLaunchKernelGGL(k_pressure_ctrl_begin, dim3(1), dim3(1), 0, s, h->ds, cap, dt);
     {
@@ -173,44 +187,25 @@ int step_pcisph_once(SphHandle *h, SphStepStats *st)
     };
     predict_rho(0, GATE_NONE);                              // :53-56
     if ((rc = slab_refresh_w_and_pressure_finalize(h, PB[1], PFIN_PCI_FIRST))) return rc;
-    bool first = true;
-    for (int k = 1, chunk = std::max(2, h->last_iters); k <= cap; chunk = 2) {
-        for (int q = 0; q < chunk && k <= cap; ++q, ++k) {
-            {
-                ProfScope ps(h, K_P_PRESS);                 // iter_press (already in PB[k&1]), update_press_force, predict_vel_pos
-                SPH_LAUNCH_RMX0(k_pci_press, rg, sweep_mode(h), relaxed_pressure(h), c.n, sweep_lds(h, StageF4<>::kBytes), s, c, dt, PB[k & 1], h->WP, h->nl, h->nlb, h->cnt, h->rho, h->V[h->vcur],
-                               EF, h->ds, PF, PP, GATE_DENS, rv, h->stage_src, h->stage_cnt, zero_press);
-            }
-            if (rg) launch_rigid_force_p<RF_PCISPH>(h, h->P[h->pcur], PB[k & 1], GATE_DENS);   // :209, every iteration
-            if ((rc = ghosts_xyz(PP))) return rc;
-            predict_rho(k, GATE_DENS);
-            if ((rc = slab_refresh_w_and_pressure_finalize(h, PB[(k + 1) & 1], PFIN_PCI_LOOP))) return rc;
+    rc = pressure_loop(h, cap, dt, st, [&](int k) -> int {
+        int r;
+        {
+            ProfScope ps(h, K_P_PRESS);                     // iter_press (already in PB[k&1]), update_press_force, predict_vel_pos
+            SPH_LAUNCH_RMX0(k_pci_press, rg, sweep_mode(h), relaxed_pressure(h), c.n, sweep_lds(h, StageF4<>::kBytes), s, c, dt, PB[k & 1], h->WP, h->nl, h->nlb, h->cnt, h->rho, h->V[h->vcur],
+                           EF, h->ds, PF, PP, GATE_DENS, rv, h->stage_src, h->stage_cnt, zero_press);
         }
-        if ((rc = read_scalars(h))) return rc;
-        if (first) {
-            if ((rc = check_overflow_all(h, slab_async(h)))) return rc;      // (the slabs' flags came with the loop's first reduction)
-            first = false;
-        }
-        if (!h->ds_host->dens_active) break;
-    }
-    st->max_nbrs = h->ds_host->max_nbrs;
-    st->max_wall_nbrs = h->ds_host->max_wall_nbrs;
-    st->lost = h->ds_host->lost;
-    st->n_dens = h->ds_host->dens_it;
-    st->capped = h->ds_host->dens_capped;
-    st->dens_err = h->ds_host->dens_avg;
-    st->dt = dt;
-    h->pb_final = h->ds_host->dens_it & 1;
-    h->last_iters = h->ds_host->dens_it;
+        if (rg) launch_rigid_force_p<RF_PCISPH>(h, h->P[h->pcur], PB[k & 1], GATE_DENS);   // :209, every iteration
+        if ((r = ghosts_xyz(PP))) return r;
+        predict_rho(k, GATE_DENS);
+        return slab_refresh_w_and_pressure_finalize(h, PB[(k + 1) & 1], PFIN_PCI_LOOP);
+    });
+    if (rc) return rc;
     {
         ProfScope ps(h, K_P_INTEGRATE);
         hipLaunchKernelGGL(k_pci_integrate, g, b, 0, s, c, dt, h->P[h->pcur], h->V[h->vcur], EF, PF, h->P[1 - h->pcur], h->V[1 - h->vcur]);
         h->pcur ^= 1; h->vcur ^= 1;
     }
-    HIP_TRY(h, hipGetLastError());
-    h->nl_valid = false;
-    h->density_valid = false;
-    return SPH_OK;
+    return step_end(h);
 }
 
 // iisph_solver.step :340-347
@@ -218,19 +213,15 @@ int step_iisph_once(SphHandle *h, SphStepStats *st)
 {
     int rc;
     memset(st, 0, sizeof(*st));
-    h->simulate_cnt += 1;
-    h->comm_stat[6] += 1;
-    step_head(h);                                           // the step's acceleration vector, if it is forced
-    if ((rc = require_async_slab(h))) return rc;
-    if ((rc = stage_sort_and_lists(h))) return rc;
-    if ((rc = stage_density(h))) return rc;                 // predict_advection :38; P = (pos, rho)
+    if ((rc = step_begin(h))) return rc;                    // ... compute_all_rho: predict_advection :38
     const Consts &c = h->c;
     hipStream_t s = h->stream;
     const dim3 g = grid_for(c.n), b(kBlock);
     const float dt = h->dt_wcsph;
     const bool rg = rigid_coupled(h);
     const RigidView rv = rg ? rigid_view(h) : RigidView();
-    float4 *DII = h->X[0], *DIJ = h->X[1], *FP = h->X[2], *PB[2] = {h->X[3], h->X[4]}, *VA = h->VA[0];
+    const IiFields f = ii_fields(h);
+    float4 *DII = f.d_ii, *DIJ = f.d_ij, *FP = f.f_press, *const *PB = f.p, *VA = f.v_adv;
     const int cap = 180;                                    // max_iter_cnt :27
     hipLaunchKernelGGL(k_pressure_ctrl_begin, dim3(1), dim3(1), 0, s, h->ds, cap, dt);
     {
@@ -244,43 +235,26 @@ int step_iisph_once(SphHandle *h, SphStepStats *st)
     {
         ProfScope ps(h, K_I_RHO_ADV);                       // :58-82; a_ii lives in aux, p_past in the carried scalar
         SPH_LAUNCH_RMX0(k_ii_rho_adv, rg, sweep_mode(h), relaxed_pressure(h), c.n, sweep_lds(h, StagePV<>::kBytes), s, c, dt, h->P[h->pcur], VA, h->WP, h->nl, h->nlb, h->cnt,
-                       DII, h->warm[h->wcur], h->rho_adv, h->aux, PB[0], rv, h->stage_src, h->stage_cnt);
+                       DII, h->warm[h->wcur], h->rho_adv, f.a_ii, PB[0], rv, h->stage_src, h->stage_cnt);
     }
     int *zero_dij = (h->pci_zero_press && h->staged && !h->slab) ? h->pci_zero_press : nullptr;      // tiles without pressure skip compute_all_d_ij (k_ii_dij)
     if (zero_dij) HIP_TRY(h, hipMemsetAsync(zero_dij, 0, sizeof(int) * (size_t)h->nblocks, s));      // DIJ still holds last step's sums
-    bool first = true;
-    for (int k = 1, chunk = std::max(2, h->last_iters); k <= cap; chunk = 2) {
-        for (int q = 0; q < chunk && k <= cap; ++q, ++k) {
-            {
-                ProfScope ps(h, K_I_DIJ);                   // compute_all_d_ij :91
-                SPH_LAUNCH_RMX0(k_ii_dij, rg, sweep_mode(h), relaxed_pressure(h), c.n, sweep_lds(h, StageF4S::kBytes), s, c, dt, PB[(k - 1) & 1], h->rho, h->nl, h->cnt, h->ds,
-                               DIJ, GATE_DENS, rv, h->stage_src, h->stage_cnt, zero_dij);
-            }
-            if ((rc = ghosts_xyz(DIJ))) return rc;
-            {
-                ProfScope ps(h, K_I_UPDATE_P);              // update_p :93 + compute_residual :97
-                SPH_LAUNCH_RMX0(k_ii_update_p, rg, sweep_mode(h), relaxed_pressure(h), c.n, sweep_lds(h, StageF4Src::kBytes + 3 * sizeof(float)), s, c, dt, PB[(k - 1) & 1], DII, DIJ, h->WP, h->nl,
-                               h->nlb, h->cnt, h->rho, h->rho_adv, h->aux, h->ds, PB[k & 1], h->psum, h->pcnt, GATE_DENS, rv, h->stage_src, h->stage_cnt);
-            }
-            if ((rc = slab_refresh_w_and_pressure_finalize(h, PB[k & 1], PFIN_II_LOOP))) return rc;
+    rc = pressure_loop(h, cap, dt, st, [&](int k) -> int {
+        {
+            ProfScope ps(h, K_I_DIJ);                       // compute_all_d_ij :91
+            SPH_LAUNCH_RMX0(k_ii_dij, rg, sweep_mode(h), relaxed_pressure(h), c.n, sweep_lds(h, StageF4S::kBytes), s, c, dt, PB[(k - 1) & 1], h->rho, h->nl, h->cnt, h->ds,
+                           DIJ, GATE_DENS, rv, h->stage_src, h->stage_cnt, zero_dij);
         }
-        if ((rc = read_scalars(h))) return rc;
-        if (first) {
-            if ((rc = check_overflow_all(h, slab_async(h)))) return rc;      // (the slabs' flags came with the loop's first reduction)
-            first = false;
+        if (int r = ghosts_xyz(DIJ)) return r;
+        {
+            ProfScope ps(h, K_I_UPDATE_P);                  // update_p :93 + compute_residual :97
+            SPH_LAUNCH_RMX0(k_ii_update_p, rg, sweep_mode(h), relaxed_pressure(h), c.n, sweep_lds(h, StageF4Src::kBytes + 3 * sizeof(float)), s, c, dt, PB[(k - 1) & 1], DII, DIJ, h->WP, h->nl,
+                           h->nlb, h->cnt, h->rho, h->rho_adv, f.a_ii, h->ds, PB[k & 1], h->psum, h->pcnt, GATE_DENS, rv, h->stage_src, h->stage_cnt);
         }
-        if (!h->ds_host->dens_active) break;
-    }
-    st->max_nbrs = h->ds_host->max_nbrs;
-    st->max_wall_nbrs = h->ds_host->max_wall_nbrs;
-    st->lost = h->ds_host->lost;
-    st->n_dens = h->ds_host->dens_it;
-    st->capped = h->ds_host->dens_capped;
+        return slab_refresh_w_and_pressure_finalize(h, PB[k & 1], PFIN_II_LOOP);
+    });
+    if (rc) return rc;
     st->n_div = h->ds_host->res_diverged;                   // 1: the loop left on "Iteration trend to divergence" (:97-99)
-    st->dens_err = h->ds_host->dens_avg;
-    st->dt = dt;
-    h->pb_final = h->ds_host->dens_it & 1;
-    h->last_iters = h->ds_host->dens_it;
     if (rg) launch_rigid_force_p<RF_IISPH>(h, h->P[h->pcur], PB[h->pb_final], GATE_NONE);   // compute_all_press_force :172-179
     {
         ProfScope ps(h, K_I_INTEGRATE);
@@ -288,10 +262,7 @@ int step_iisph_once(SphHandle *h, SphStepStats *st)
                            FP, h->warm[h->wcur]);
         h->pcur ^= 1; h->vcur ^= 1;
     }
-    HIP_TRY(h, hipGetLastError());
-    h->nl_valid = false;
-    h->density_valid = false;
-    return SPH_OK;
+    return step_end(h);
 }
 
 // host copy of solver_base.cubic_kernel_derivative (:90-103), same f32 operations as the device's grad_w
@@ -396,10 +367,9 @@ int pcisph_precompute(SphHandle *h)
     if ((rc = stage_sort_and_lists(h))) return rc;
     if ((rc = read_scalars(h))) return rc;
     if ((rc = check_overflow(h))) return rc;
-    if (rigid_binned(h))    // get_neighbour_count with its rigid-entry quirk (ParticleSystem.py:436-444), coupled or not
-        hipLaunchKernelGGL(k_unsort_scalar_int, grid_for(N), dim3(kBlock), 0, h->stream, N, h->ncount, h->id[h->icur], h->staging);
-    else
-        hipLaunchKernelGGL(k_unsort_count, grid_for(N), dim3(kBlock), 0, h->stream, N, h->cnt, h->id[h->icur], h->staging);
+    FieldLoc counted;       // get_neighbour_count, with its rigid-entry quirk (ParticleSystem.py:436-444) where a body is binned, coupled or not
+    if ((rc = locate_field(h, SPH_F_NBR_COUNT, FV_API, &counted))) return rc;
+    launch_unsort(h, counted, h->staging);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemcpyAsync(counts.data(), h->staging, sizeof(float) * (size_t)N, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -454,28 +424,4 @@ int pcisph_precompute(SphHandle *h)
     }
     h->pci_delta = 1.0f / ((((sx * sx + sy * sy) + sz * sz) + sq) * h->pci_beta);   // :47
     return SPH_OK;
-}
-
-int field_floats(SphHandle *h, int species, int field, size_t *count, bool *vec)
-{
-    *vec = false;
-    if (species == SPH_SPECIES_FLUID) {
-        switch (field) {
-        case SPH_F_POS: case SPH_F_VEL: case SPH_F_ACC: case SPH_F_VEL_ADV: case SPH_F_PRESS_FORCE: case SPH_F_POS_PREDICT: case SPH_F_D_II:
-        case SPH_F_D_IJ: case SPH_F_PBF_DELTA_POS:
-            *vec = true; *count = 3 * (size_t)h->N; return SPH_OK;
-        case SPH_F_RHO: case SPH_F_PRESSURE: case SPH_F_ALPHA: case SPH_F_WARM_K: case SPH_F_RHO_ADV: case SPH_F_RHO_DER:
-        case SPH_F_NBR_COUNT: case SPH_F_PRESS_ITER: case SPH_F_A_II: case SPH_F_PBF_LAMBDA:
-            *count = (size_t)h->N; return SPH_OK;
-        default: break;
-        }
-    } else if (species == SPH_SPECIES_WALL) {
-        if (field == SPH_F_WALL_POS) { *vec = true; *count = 3 * (size_t)h->Nb; return SPH_OK; }
-        if (field == SPH_F_WALL_VOL) { *count = (size_t)h->Nb; return SPH_OK; }
-    } else if (species == SPH_SPECIES_RIGID && h->rigid) {
-        if (field == SPH_F_RIGID_POS || field == SPH_F_RIGID_FORCE) { *vec = true; *count = 3 * (size_t)h->Nr; return SPH_OK; }
-        if (field == SPH_F_RIGID_VOL || field == SPH_F_RIGID_MASS) { *count = (size_t)h->Nr; return SPH_OK; }
-        if (field == SPH_F_RIGID_VERT) { *vec = true; *count = 3 * (size_t)h->Nv; return SPH_OK; }
-    }
-    return fail(h, SPH_E_INVALID, "unknown species/field %d/%d", species, field);
 }

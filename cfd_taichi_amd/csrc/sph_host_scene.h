@@ -618,6 +618,13 @@ inline size_t dalloc_bytes(const SphHandle *h, const void *p)
     for (const auto &b : h->blocks) if (b.first == p) return b.second;
     return 0;
 }
+// zero whole dalloc'd arrays on the handle's stream (a null or foreign pointer is skipped)
+int dzero(SphHandle *h, const void *const *arrays, size_t count)
+{
+    for (size_t k = 0; k < count; ++k)
+        if (const size_t bytes = arrays[k] ? dalloc_bytes(h, arrays[k]) : 0) HIP_TRY(h, hipMemsetAsync(const_cast<void *>(arrays[k]), 0, bytes, h->stream));
+    return SPH_OK;
+}
 
 inline uint64_t morton_spread(uint64_t v)          // 21 bits -> every third bit
 {
@@ -883,6 +890,13 @@ inline void step_head(SphHandle *h)
     hipLaunchKernelGGL(k_accel_eval, dim3(1), dim3(1), 0, h->stream, h->ds);
 }
 
+// the captured wcsph step pairs hold the count, the grids, delta_time and the k_accel_eval node (or its absence) as they were at capture
+inline void drop_wcsph_graphs(SphHandle *h)
+{
+    for (int k = 0; k < 8; ++k)
+        if (h->wcsph_graph[k]) { (void)hipGraphExecDestroy(h->wcsph_graph[k]); h->wcsph_graph[k] = nullptr; }
+}
+
 // sph_set_gravity / sph_set_forcing / a written SPH_S_TIME, between steps: h->frc (validated by the caller) goes to the device, the vector is
 // formed at once for the current clock -- by the kernel the steps use, so the bits are the step's -- and read back.  The captured wcsph step pairs
 // hold or lack the k_accel_eval node: they are dropped (the vector itself is device memory and would reach a replay anyway).
@@ -895,8 +909,7 @@ int forcing_commit(SphHandle *h)
         HIP_TRY(h, hipMemcpyAsync(h->frc.accel, h->ds->frc.accel, sizeof(h->frc.accel), hipMemcpyDeviceToHost, h->stream));
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    for (int k = 0; k < 8; ++k)
-        if (h->wcsph_graph[k]) { (void)hipGraphExecDestroy(h->wcsph_graph[k]); h->wcsph_graph[k] = nullptr; }
+    drop_wcsph_graphs(h);
     return SPH_OK;
 }
 
@@ -913,7 +926,21 @@ int write_delta_time(SphHandle *h, double value)
         HIP_TRY(h, hipMemcpyAsync(h->ds, h->ds_host, offsetof(DevScalars, ps_dt), hipMemcpyHostToDevice, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
     }
-    for (int k = 0; k < 8; ++k)                                      // captured wcsph step pairs carry the old delta_time as a launch argument
-        if (h->wcsph_graph[k]) { (void)hipGraphExecDestroy(h->wcsph_graph[k]); h->wcsph_graph[k] = nullptr; }
+    drop_wcsph_graphs(h);                                            // (they carry the old delta_time as a launch argument)
     return SPH_OK;
+}
+
+// Forget what the steps so far left behind that a fresh handle of the same particles would not have: the host's flags about lists, density, the density
+// loop's launch order and stamps, pbf's fields, and the device arrays that hold stamps and per-tile flags of earlier sweeps (the stamps start at 0
+// again, so what was stamped must go with them; staged dfsph handles only, a few ints per tile).  "A handle's history must not show in its bits":
+// sph_slab_set_state (slab_state_commit) and the calls that change the particle count (fluid_count_changed) both end here -- a new flag of this kind,
+// or a new array that carries stamps or per-tile flags across steps, is added HERE and nowhere else.  Enqueues on the handle's stream; no wait
+int forget_step_history(SphHandle *h)
+{
+    h->nl_valid = false; h->density_valid = false; h->lists_predate_flag = false;
+    h->flow_stamp = h->flow_last = 0; h->flow_d6 = kNoFlow;
+    h->dens_sparse = false; h->dens_first = true; h->pending_div = kNoRide;
+    h->pbf_fields = false;                    // pbf_lambda / delta_pos: "before the first step" again
+    const void *stamped[] = {h->wave_dirty, h->changed8, h->dens_hot, h->dens_order, h->tile_nbr, h->need6, h->need7, h->tile_nz, h->worked6, h->worked7, h->dens_bcast};
+    return dzero(h, stamped, sizeof(stamped) / sizeof(stamped[0]));
 }

@@ -423,7 +423,7 @@ int slab_exchange_resid(SphHandle *h, bool dens, float *val, bool overlap, bool 
         ProfScope ps(h, K_SLAB, s);
         if (nrl + nrr)
             hipLaunchKernelGGL(k_unpack_resid, grid_for(nrl + nrr), b, 0, s, h->c, h->edge_list[0], nrl, h->edge_n[0][0], (const float *)h->drecv[0], h->edge_list[3], nrr,
-                               h->edge_n[3][0], (const float *)h->drecv[1], dens ? 1 : 0, h->aux, h->rho, h->ds, val, P, S, dens ? h->flow_d6 : kNoFlow);
+                               h->edge_n[3][0], (const float *)h->drecv[1], dens ? 1 : 0, dfsph_alpha(h), h->rho, h->ds, val, P, S, dens ? h->flow_d6 : kNoFlow);
     }
     HIP_TRY(h, hipGetLastError());
     if (overlap) HIP_TRY(h, hipEventRecord(h->ev_halo, s));
@@ -509,13 +509,12 @@ int slab_state_commit(SphHandle *h, const float *pos, const float *vel, const fl
     // everything resident goes -- owned particles, ghosts, dead slots -- and with it what the steps so far left behind: per-particle fields, the edge
     // lists, DensFlow's stamps and flags, tile flags and orders, what a correction that ran ahead saved.  A new handle's arena is all zeros (dcommit)
     const void *gone[] = {h->P[0], h->P[1], h->V[0], h->V[1], h->VA[0], h->VA[1], h->warm[0], h->warm[1], h->id[0], h->id[1], h->X[0], h->X[1], h->X[2], h->X[3], h->X[4],
-                          h->rho, h->aux, h->drho, h->rho_adv, h->krho, h->cnt, h->wall_grad, h->wall_gsq, h->wave_dirty, h->changed8, h->dens_hot, h->dens_order,
-                          h->tile_nbr, h->need6, h->need7, h->tile_nz, h->worked6, h->worked7, h->dens_bcast, h->stage_cnt, h->cell_of, h->rank, h->slot_src,
+                          h->rho, h->aux, h->drho, h->rho_adv, h->krho, h->cnt, h->wall_grad, h->wall_gsq, h->stage_cnt, h->cell_of, h->rank, h->slot_src,
                           h->psum, h->pcnt, h->pmax, h->dead, h->edge_off[0], h->edge_off[1], h->edge_off[2], h->edge_off[3], h->edge_off[4], h->edge_off[5],
                           h->edge_off[6], h->edge_off[7], h->edge_list[0], h->edge_list[1], h->edge_list[2], h->edge_list[3], h->counters, h->class_cnt,
                           h->tile_flag, h->tile_order, h->spec_v, h->spec_w};
-    for (const void *p : gone)
-        if (const size_t bytes = p ? dalloc_bytes(h, p) : 0) HIP_TRY(h, hipMemsetAsync(const_cast<void *>(p), 0, bytes, s));
+    if ((rc = dzero(h, gone, sizeof(gone) / sizeof(gone[0])))) return rc;
+    if ((rc = forget_step_history(h))) return rc;             // ... the stamped arrays and the host's flags about them, lists and density
     float *warm = carries_scalar(h) ? h->warm[h->wcur] : nullptr;
     for (int first = 0; first < h->N; first += b.chunk) {
         const int m = std::min(b.chunk, h->N - first), nblk = (int)grid_for(m).x;
@@ -550,11 +549,7 @@ int slab_state_commit(SphHandle *h, const float *pos, const float *vel, const fl
     h->nblocks = (c.n + kBlock - 1) / kBlock;
     for (int k = 0; k < 4; ++k) h->edge_n[k][0] = h->edge_n[k][1] = 0;
     h->cuts_moved = true;                     // the next step exchanges in two rounds (migrate, then ghosts), as after any change of the cuts
-    h->nl_valid = false; h->density_valid = false; h->lists_predate_flag = false;
-    h->flow_stamp = h->flow_last = 0; h->flow_d6 = kNoFlow;
-    h->dens_sparse = false; h->dens_first = true; h->pending_div = kNoRide;
     h->last_iters = 2; h->pb_final = 0;
-    h->pbf_fields = false;                    // pbf_lambda / delta_pos: "before the first step" again
     return SPH_OK;
 }
 

@@ -98,18 +98,18 @@ struct SphHandle {
     DevScalars::Forcing frc = {};
     bool nl_valid = false;      // neighbour list matches the current positions
     bool density_valid = false;
-    bool pbf_fields = false;    // pbf: aux / X[0] hold pbf_lambda / delta_pos of the last step in the current device order (slab handles lose them at a re-sort)
+    bool pbf_fields = false;    // pbf: pbf_lambda / delta_pos are those of the last step, in the current device order (slab handles lose them at a re-sort)
 
     // device state (sorted order); index [cur] is the live one
     float4 *P[2] = {nullptr, nullptr};
     float4 *V[2] = {nullptr, nullptr};
-    float4 *VA[2] = {nullptr, nullptr};   // dfsph v* ping-pong; VA[0] doubles as wcsph acc
+    float4 *VA[2] = {nullptr, nullptr};   // dfsph v* ping-pong; VA[0] doubles as wcsph acc and iisph v_adv (sph_host_fields.h)
     float *warm[2] = {nullptr, nullptr};
     int *id[2] = {nullptr, nullptr};
     int pcur = 0, vcur = 0, vacur = 0, wcur = 0, icur = 0;
 
-    float *rho = nullptr, *aux = nullptr /* pressure | alpha | a_ii */, *drho = nullptr, *rho_adv = nullptr, *krho = nullptr /* k / rho (kr_split) */;
-    float4 *X[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // pcisph: EF, PF, PP, PB0, PB1; iisph: DII, DIJ, f_press, PB0, PB1
+    float *rho = nullptr, *aux = nullptr /* pressure | alpha | a_ii | pbf_lambda: sph_host_fields.h */, *drho = nullptr, *rho_adv = nullptr, *krho = nullptr /* k / rho (kr_split) */;
+    float4 *X[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // per-solver working arrays: which is what is said once, by pci_fields / ii_fields / pbf_arrays (sph_host_fields.h)
     int pb_final = 0;            // which PB holds press_iter / p_iter after the last step
     unsigned sweep_lds = 0;      // sph_tune_time: dynamic LDS bytes per block on the unstaged DFSPH sweeps (caps the waves per CU)
     int last_iters = 2;          // iteration count of the last step's density / pressure loop: size of the next step's first chunk
@@ -321,6 +321,7 @@ void drain_profile(SphHandle *h)
 inline dim3 grid_for(int n) { return dim3((unsigned)std::max(1, (n + kBlock - 1) / kBlock)); }   // an empty slab still launches one (idle) block
 
 #include "sph_host_scene.h"
+#include "sph_host_fields.h"
 #include "sph_host_transport.h"
 #include "sph_host_rigid.h"
 #include "sph_host_dfsph.h"
@@ -536,30 +537,23 @@ static int flow_refused(SphHandle *h, const char *call)
 }
 
 // The live count is now `n`: what the host caches from it, and what the steps so far left behind that a fresh handle of these particles would
-// not have -- the tail of slab_state_commit, but for what travels with the handle (delta_time, the clock, gravity and forcing, the carried
-// scalars of the particles that stay, pcisph's delta).  The density loop's stamps start at 0 again, so the arrays that hold stamps and per-tile
-// flags of earlier sweeps are cleared with them (staged dfsph handles only; a few ints per tile).
+// not have (forget_step_history, as sph_slab_set_state) -- but for what travels with the handle: delta_time, the clock, gravity and forcing, the
+// carried scalars of the particles that stay, pcisph's delta, last_iters and pb_final.
 static int fluid_count_changed(SphHandle *h, int n)
 {
     hipStream_t s = h->stream;
     h->N = n; h->n_owned = n;
     h->c.n = n;
     h->nblocks = (n + kBlock - 1) / kBlock;
-    h->nl_valid = false; h->density_valid = false; h->lists_predate_flag = false;
-    h->flow_stamp = h->flow_last = 0; h->flow_d6 = kNoFlow;
-    h->dens_sparse = false; h->dens_first = true; h->pending_div = kNoRide;
-    h->pbf_fields = false;
-    const void *stamped[] = {h->wave_dirty, h->changed8, h->dens_hot, h->dens_order, h->tile_nbr, h->need6, h->need7, h->tile_nz, h->worked6, h->worked7,
-                             h->dens_bcast, h->pci_zero_press};
-    for (const void *p : stamped)
-        if (const size_t bytes = p ? dalloc_bytes(h, p) : 0) HIP_TRY(h, hipMemsetAsync(const_cast<void *>(p), 0, bytes, s));
+    if (int rc = forget_step_history(h)) return rc;
+    const void *tile_flags[] = {h->pci_zero_press};
+    if (int rc = dzero(h, tile_flags, 1)) return rc;
     if (h->verlet) {              // the lists of the last build know neither the new particles nor the new slots: the next step builds them
         h->ds_host->moved = 1;
         HIP_TRY(h, hipMemcpyAsync(&h->ds->moved, &h->ds_host->moved, sizeof(int), hipMemcpyHostToDevice, s));
     }
     HIP_TRY(h, hipStreamSynchronize(s));
-    for (int k = 0; k < 8; ++k)                                      // captured wcsph step pairs carry the old count and grids as launch arguments
-        if (h->wcsph_graph[k]) { (void)hipGraphExecDestroy(h->wcsph_graph[k]); h->wcsph_graph[k] = nullptr; }
+    drop_wcsph_graphs(h);                                            // (they carry the old count and grids as launch arguments)
     return SPH_OK;
 }
 
@@ -584,7 +578,7 @@ int sph_add_particles(SphHandle *h, const float *pos, const float *vel, size_t n
     HIP_TRY(h, hipStreamSynchronize(s));
     // one copy of the new rows (positions, then velocities) and one k_append; the staging buffer holds 3 x capacity floats, so a call that brings
     // more than half the capacity WITH velocities goes in two
-    const bool pbf = h->cfg.solver == SPH_SOLVER_PBF;
+    const PbfFields pbf = h->cfg.solver == SPH_SOLVER_PBF ? pbf_arrays(h) : PbfFields{};      // the new rows' pbf_lambda and delta_pos start at zero
     const size_t per = vel ? 6 : 3, room = 3 * (size_t)h->c.stride / per;
     std::vector<float> rows;
     int at = h->N;
@@ -595,8 +589,7 @@ int sph_add_particles(SphHandle *h, const float *pos, const float *vel, size_t n
         HIP_TRY(h, hipMemcpyAsync(h->staging, rows.data(), sizeof(float) * rows.size(), hipMemcpyHostToDevice, s));
         ProfScope ps(h, K_TRANSFER);
         hipLaunchKernelGGL(k_append, grid_for((int)m), dim3(kBlock), 0, s, at, (int)m, at, (const float *)h->staging, vel ? 1 : 0, h->P[h->pcur], h->V[h->vcur],
-                           carries_scalar(h) ? h->warm[h->wcur] : (float *)nullptr, h->id[h->icur], h->x0, h->rho, pbf ? h->aux : (float *)nullptr,
-                           pbf ? h->X[0] : (float4 *)nullptr);
+                           carries_scalar(h) ? h->warm[h->wcur] : (float *)nullptr, h->id[h->icur], h->x0, h->rho, pbf.lambda, pbf.delta_pos);
         HIP_TRY(h, hipGetLastError());
         HIP_TRY(h, hipStreamSynchronize(s));          // (rows is reused)
         at += (int)m;
@@ -700,21 +693,20 @@ int sph_upload(SphHandle *h, int species, int field, const float *host, size_t n
 {
     if (!h || !host) return SPH_E_INVALID;
     HIP_TRY(h, hipSetDevice(h->device));
-    size_t count; bool vec;
-    int rc = field_floats(h, species, field, &count, &vec);
+    size_t count;
+    int rc = field_floats(h, species, field, &count);
     if (rc) return rc;
     if (count != n_floats) return fail(h, SPH_E_INVALID, "field %d holds %zu floats, got %zu", field, count, n_floats);
-    if (species != SPH_SPECIES_FLUID || !(field == SPH_F_POS || field == SPH_F_VEL || field == SPH_F_WARM_K))
-        return fail(h, SPH_E_INVALID, "field %d is read-only", field);
+    const FieldRow *row = species == SPH_SPECIES_FLUID ? fluid_field(field) : nullptr;
+    if (!row || !row->upload) return fail(h, SPH_E_INVALID, "field %d is read-only", field);
     if (h->slab) return fail(h, SPH_E_STATE, "sph_upload is not available on a slab handle: sph_slab_set_state replaces its whole state (pos, vel, the travelling scalar, delta_time)");
-    if (field == SPH_F_WARM_K && h->cfg.solver != SPH_SOLVER_DFSPH) return fail(h, SPH_E_STATE, "warm_start_k needs a dfsph handle");
+    if (!(row->upload & (1u << h->cfg.solver))) return fail(h, SPH_E_STATE, "%s", row->not_owner);
+    FieldLoc f;
+    if ((rc = locate_field(h, field, FV_API, &f))) return rc;
     hipStream_t s = h->stream;
     HIP_TRY(h, hipMemcpyAsync(h->staging, host, sizeof(float) * count, hipMemcpyHostToDevice, s));
     ProfScope ps(h, K_TRANSFER);
-    const dim3 g = grid_for(h->N), b(kBlock);
-    if (field == SPH_F_POS) hipLaunchKernelGGL(k_sort_in_vec, g, b, 0, s, h->N, h->staging, h->id[h->icur], h->P[h->pcur]);
-    else if (field == SPH_F_VEL) hipLaunchKernelGGL(k_sort_in_vec, g, b, 0, s, h->N, h->staging, h->id[h->icur], h->V[h->vcur]);
-    else hipLaunchKernelGGL(k_sort_in_scalar, g, b, 0, s, h->N, h->staging, h->id[h->icur], h->warm[h->wcur]);
+    launch_sort_in(h, h->staging, f);
     HIP_TRY(h, hipGetLastError());
     if (h->verlet) {              // new positions: the Verlet lists of the last build no longer apply
         h->ds_host->moved = 1;
@@ -730,8 +722,8 @@ int sph_download(SphHandle *h, int species, int field, float *host, size_t n_flo
 {
     if (!h || !host) return SPH_E_INVALID;
     HIP_TRY(h, hipSetDevice(h->device));
-    size_t count; bool vec;
-    int rc = field_floats(h, species, field, &count, &vec);
+    size_t count;
+    int rc = field_floats(h, species, field, &count);
     if (rc) return rc;
     if (count != n_floats) return fail(h, SPH_E_INVALID, "field %d holds %zu floats, got %zu", field, count, n_floats);
     if (species == SPH_SPECIES_WALL) {
@@ -758,64 +750,12 @@ int sph_download(SphHandle *h, int species, int field, float *host, size_t n_flo
     if (h->slab) return fail(h, SPH_E_STATE, "slab handle: use sph_download_local + sph_download_ids (device order, owned and ghost particles)");
     // get_neighbour_count after sph_rigid_set_active: the count of the flag as it stands, not of the lists built before it changed
     if (field == SPH_F_NBR_COUNT && h->lists_predate_flag && (rc = sph_build_neighbors(h))) return rc;
-    const bool dfsph = h->cfg.solver == SPH_SOLVER_DFSPH;
-    const bool pcisph = h->cfg.solver == SPH_SOLVER_PCISPH, iisph = h->cfg.solver == SPH_SOLVER_IISPH;
+    FieldLoc f;
+    if ((rc = locate_field(h, field, FV_API, &f))) return rc;
     hipStream_t s = h->stream;
-    const dim3 g = grid_for(h->N), b(kBlock);
-    const int *id = h->id[h->icur];
     {
         ProfScope ps(h, K_TRANSFER);
-        switch (field) {
-        case SPH_F_POS: hipLaunchKernelGGL(k_unsort_vec, g, b, 0, s, h->N, h->P[h->pcur], id, h->staging); break;
-        case SPH_F_VEL: hipLaunchKernelGGL(k_unsort_vec, g, b, 0, s, h->N, h->V[h->vcur], id, h->staging); break;
-        case SPH_F_ACC:
-            if (h->cfg.solver != SPH_SOLVER_WCSPH) return fail(h, SPH_E_STATE, "acc is a wcsph field (the other solvers never fill it, dfsph_solver.py:418-421)");
-            hipLaunchKernelGGL(k_unsort_vec, g, b, 0, s, h->N, h->VA[0], id, h->staging); break;
-        case SPH_F_PRESS_ITER:
-            if (!is_pressure_solver(h)) return fail(h, SPH_E_STATE, "press_iter / p_iter is a pcisph / iisph field");
-            hipLaunchKernelGGL(k_unsort_w, g, b, 0, s, h->N, h->X[3 + h->pb_final], id, h->staging); break;
-        case SPH_F_PRESS_FORCE:
-            if (!is_pressure_solver(h)) return fail(h, SPH_E_STATE, "press_force / f_press is a pcisph / iisph field");
-            hipLaunchKernelGGL(k_unsort_vec, g, b, 0, s, h->N, h->X[pcisph ? 1 : 2], id, h->staging); break;
-        case SPH_F_POS_PREDICT:
-            if (h->cfg.solver == SPH_SOLVER_PBF) { hipLaunchKernelGGL(k_unsort_vec, g, b, 0, s, h->N, h->P[h->pcur], id, h->staging); break; }   // pos = pos_predict after a step (:84)
-            if (!pcisph) return fail(h, SPH_E_STATE, "pos_predict is a pcisph / pbf field");
-            hipLaunchKernelGGL(k_unsort_vec, g, b, 0, s, h->N, h->X[2], id, h->staging); break;
-        case SPH_F_PBF_LAMBDA: case SPH_F_PBF_DELTA_POS:
-            if (h->cfg.solver != SPH_SOLVER_PBF) return fail(h, SPH_E_STATE, "pbf_lambda / delta_pos are pbf fields");
-            if (h->simulate_cnt == 0) return fail(h, SPH_E_STATE, "pbf_lambda / delta_pos exist after the first step");
-            // (the device order does not change inside a step: the ids of the current generation apply)
-            if (field == SPH_F_PBF_LAMBDA) hipLaunchKernelGGL(k_unsort_scalar, g, b, 0, s, h->N, h->aux, id, h->staging);
-            else hipLaunchKernelGGL(k_unsort_vec, g, b, 0, s, h->N, h->X[0], id, h->staging);
-            break;
-        case SPH_F_D_II: case SPH_F_D_IJ:
-            if (!iisph) return fail(h, SPH_E_STATE, "d_ii / d_ij are iisph fields");
-            hipLaunchKernelGGL(k_unsort_vec, g, b, 0, s, h->N, h->X[field == SPH_F_D_II ? 0 : 1], id, h->staging); break;
-        case SPH_F_A_II:
-            if (!iisph) return fail(h, SPH_E_STATE, "a_ii is an iisph field");
-            hipLaunchKernelGGL(k_unsort_scalar, g, b, 0, s, h->N, h->aux, id, h->staging); break;
-        case SPH_F_VEL_ADV:
-            if (iisph) { hipLaunchKernelGGL(k_unsort_vec, g, b, 0, s, h->N, h->VA[0], id, h->staging); break; }   // iisph v_adv
-            if (!dfsph) return fail(h, SPH_E_STATE, "vel_adv is a dfsph / iisph field");
-            hipLaunchKernelGGL(k_unsort_vec, g, b, 0, s, h->N, h->VA[0], id, h->staging); break;
-        case SPH_F_RHO: hipLaunchKernelGGL(k_unsort_scalar, g, b, 0, s, h->N, h->rho, id, h->staging); break;
-        case SPH_F_PRESSURE:
-            if (h->cfg.solver != SPH_SOLVER_WCSPH) return fail(h, SPH_E_STATE, "pressure is a wcsph field");
-            hipLaunchKernelGGL(k_unsort_scalar, g, b, 0, s, h->N, h->aux, id, h->staging); break;
-        case SPH_F_ALPHA:
-            if (!dfsph) return fail(h, SPH_E_STATE, "alpha is a dfsph field");
-            hipLaunchKernelGGL(k_unsort_scalar, g, b, 0, s, h->N, h->aux, id, h->staging); break;
-        case SPH_F_WARM_K:
-            if (!dfsph) return fail(h, SPH_E_STATE, "warm_start_k is a dfsph field");
-            hipLaunchKernelGGL(k_unsort_scalar, g, b, 0, s, h->N, h->warm[h->wcur], id, h->staging); break;
-        case SPH_F_RHO_ADV: hipLaunchKernelGGL(k_unsort_scalar, g, b, 0, s, h->N, h->rho_adv, id, h->staging); break;
-        case SPH_F_RHO_DER: hipLaunchKernelGGL(k_unsort_scalar, g, b, 0, s, h->N, h->drho, id, h->staging); break;
-        case SPH_F_NBR_COUNT:
-            if (rigid_binned(h)) hipLaunchKernelGGL(k_unsort_scalar_int, g, b, 0, s, h->N, h->ncount, id, h->staging);
-            else hipLaunchKernelGGL(k_unsort_count, g, b, 0, s, h->N, h->cnt, id, h->staging);
-            break;
-        default: return fail(h, SPH_E_INVALID, "field %d cannot be downloaded", field);
-        }
+        launch_unsort(h, f, h->staging);            // (the device order does not change inside a step: the ids of the current generation apply)
     }
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemcpyAsync(host, h->staging, sizeof(float) * count, hipMemcpyDeviceToHost, s));
@@ -1043,41 +983,19 @@ int sph_download_local(SphHandle *h, int field, float *host, size_t n_floats)
 {
     if (!h || !host) return SPH_E_INVALID;
     HIP_TRY(h, hipSetDevice(h->device));
-    const bool dfsph = h->cfg.solver == SPH_SOLVER_DFSPH;
     const size_t n = (size_t)h->c.n;
-    const float4 *vec = nullptr; const float *sca = nullptr;
-    switch (field) {
-    case SPH_F_POS: vec = h->P[h->pcur]; break;
-    case SPH_F_VEL: vec = h->V[h->vcur]; break;
-    case SPH_F_VEL_ADV: if (dfsph) vec = h->VA[0]; break;
-    case SPH_F_ACC: if (!dfsph) vec = h->VA[0]; break;
-    case SPH_F_RHO: sca = h->rho; break;
-    case SPH_F_PRESSURE: if (!dfsph) sca = h->aux; break;
-    case SPH_F_ALPHA: if (dfsph) sca = h->aux; break;
-    case SPH_F_WARM_K: if (dfsph) sca = h->warm[h->wcur]; break;
-    case SPH_F_RHO_ADV: sca = h->rho_adv; break;
-    case SPH_F_RHO_DER: sca = h->drho; break;
-    case SPH_F_PBF_LAMBDA: case SPH_F_PBF_DELTA_POS: case SPH_F_POS_PREDICT:
-        if (h->cfg.solver != SPH_SOLVER_PBF) break;
-        if (!h->pbf_fields)
-            return fail(h, SPH_E_STATE, h->simulate_cnt == 0 ? "pbf_lambda / delta_pos / pos_predict exist after the first step"
-                                                             : "pbf_lambda / delta_pos / pos_predict of a slab handle are valid from a step until the next sort "
-                                                               "(sph_build_neighbors, sph_compute_density, sph_slab_set_state): step first");
-        if (field == SPH_F_PBF_LAMBDA) sca = h->aux;
-        else vec = field == SPH_F_PBF_DELTA_POS ? h->X[0] : h->P[h->pcur];      // pos = pos_predict after a step (:84)
-        break;
-    default: break;
-    }
-    if (!vec && !sca) return fail(h, SPH_E_INVALID, "field %d cannot be downloaded from this handle", field);
+    FieldLoc f;
+    if (int rc = locate_field(h, field, FV_LOCAL, &f)) return rc;
+    const bool vec = f.kind == FK_XYZ;               // (the local view offers xyz and float arrays only)
     const size_t want = vec ? 3 * n : n;
     if (n_floats != want) return fail(h, SPH_E_INVALID, "field %d holds %zu floats locally, got %zu", field, want, n_floats);
     if (vec) {
         ProfScope ps(h, K_TRANSFER);
-        hipLaunchKernelGGL(k_copy_vec_local, grid_for((int)n), dim3(kBlock), 0, h->stream, (int)n, vec, h->staging);
+        hipLaunchKernelGGL(k_copy_vec_local, grid_for((int)n), dim3(kBlock), 0, h->stream, (int)n, (const float4 *)f.data, h->staging);
         HIP_TRY(h, hipGetLastError());
         HIP_TRY(h, hipMemcpyAsync(host, h->staging, sizeof(float) * want, hipMemcpyDeviceToHost, h->stream));
     } else {
-        HIP_TRY(h, hipMemcpyAsync(host, sca, sizeof(float) * want, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(host, f.data, sizeof(float) * want, hipMemcpyDeviceToHost, h->stream));
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SPH_OK;
@@ -1088,22 +1006,25 @@ int sph_build_neighbors(SphHandle *h)
     if (!h) return SPH_E_INVALID;
     HIP_TRY(h, hipSetDevice(h->device));
     // pbf_lambda and delta_pos are per-particle fields of the solver that neither update_grid nor compute_all_rho touches; they live in device order
-    // (aux, X[0]), which the re-sort changes: carry them through in API order -- lambda in the staging buffer, delta_pos as 3 N floats in X[1]
+    // (pbf_arrays), which the re-sort changes: carry them through in API order -- lambda in the staging buffer, delta_pos as 3 N floats in pos_new
     // (phase 1's new positions: scratch between steps, 4 N floats).  Here and not in sph_compute_density: a sph_build_neighbors of its own re-sorts too
     // Slab handles do NOT carry: there id[] holds global ids (~id for ghosts), fewer or more than N particles are resident, and the re-sort starts with
     // a particle exchange that changes who is -- k_unsort_* / k_sort_in_* over N elements would index outside the arrays.  pbf_lambda / delta_pos of a
     // slab handle are valid from a step until the next sort; sph_download_local answers SPH_E_STATE after it
     const bool keep = h->cfg.solver == SPH_SOLVER_PBF && h->simulate_cnt > 0 && !h->slab;
     if (h->slab) h->pbf_fields = false;
+    FieldLoc lambda = {}, delta_pos = {};
+    float *delta_pos_api = keep ? (float *)pbf_arrays(h).pos_new : nullptr;
+    int rc;
     if (keep) {
-        hipLaunchKernelGGL(k_unsort_scalar, grid_for(h->N), dim3(kBlock), 0, h->stream, h->N, h->aux, h->id[h->icur], h->staging);
-        hipLaunchKernelGGL(k_unsort_vec, grid_for(h->N), dim3(kBlock), 0, h->stream, h->N, h->X[0], h->id[h->icur], (float *)h->X[1]);
+        if ((rc = locate_field(h, SPH_F_PBF_LAMBDA, FV_API, &lambda)) || (rc = locate_field(h, SPH_F_PBF_DELTA_POS, FV_API, &delta_pos))) return rc;
+        launch_unsort(h, lambda, h->staging);
+        launch_unsort(h, delta_pos, delta_pos_api);
     }
-    int rc = stage_sort_and_lists(h);
-    if (rc) return rc;
+    if ((rc = stage_sort_and_lists(h))) return rc;
     if (keep) {
-        hipLaunchKernelGGL(k_sort_in_scalar, grid_for(h->N), dim3(kBlock), 0, h->stream, h->N, h->staging, h->id[h->icur], h->aux);
-        hipLaunchKernelGGL(k_sort_in_vec, grid_for(h->N), dim3(kBlock), 0, h->stream, h->N, (const float *)h->X[1], h->id[h->icur], h->X[0]);
+        launch_sort_in(h, h->staging, lambda);
+        launch_sort_in(h, delta_pos_api, delta_pos);
     }
     if ((rc = read_scalars(h))) return rc;
     return check_overflow_all(h);
@@ -1128,115 +1049,66 @@ int sph_compute_alpha(SphHandle *h)
     return sph_compute_density(h);   // the fused sweep produces rho and alpha together
 }
 
+// The WCSPH step is a fixed launch sequence with no host decision in it, so two steps (after which the ping-pong
+// buffers are back in the same roles) are captured once into a hipGraph and replayed: at 30k particles the step is
+// launch-bound and replay halves it.  Eager launches remain for odd remainders, profiling and slab handles.  *k: the steps taken
+static int wcsph_replay_pairs(SphHandle *h, int nsteps, int *k)
+{
+    if (!(h->graphs_enabled && !h->profiling && !h->slab && !h->rigid && nsteps >= 2)) return SPH_OK;
+    while (nsteps - *k >= 2) {
+        const int key = h->pcur | (h->vcur << 1) | (h->icur << 2);
+        if (!h->wcsph_graph[key]) {
+            hipGraph_t graph = nullptr;
+            const int sim_cnt = h->simulate_cnt;
+            if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { h->graphs_enabled = false; break; }
+            int rc = step_wcsph_once(h);
+            if (!rc) rc = step_wcsph_once(h);
+            hipError_t e = hipStreamEndCapture(h->stream, &graph);
+            h->simulate_cnt = sim_cnt;             // the capture launched nothing
+            if (rc || e != hipSuccess || !graph) { if (graph) (void)hipGraphDestroy(graph); h->graphs_enabled = false; (void)hipGetLastError(); break; }
+            e = hipGraphInstantiate(&h->wcsph_graph[key], graph, nullptr, nullptr, 0);
+            (void)hipGraphDestroy(graph);
+            if (e != hipSuccess) { h->wcsph_graph[key] = nullptr; h->graphs_enabled = false; (void)hipGetLastError(); break; }
+            if ((h->pcur | (h->vcur << 1) | (h->icur << 2)) != key) { h->graphs_enabled = false; break; }   // roles must return after 2 steps
+        }
+        HIP_TRY(h, hipGraphLaunch(h->wcsph_graph[key], h->stream));
+        h->graph_launches += 1;
+        h->simulate_cnt += 2;
+        h->nl_valid = false; h->density_valid = false;
+        *k += 2;
+    }
+    return SPH_OK;
+}
+
+// (the frame: run_steps in sph_host_dfsph.h.  wcsph and pbf steps read nothing back, so their calls end with the overflow read-back)
 int sph_step_wcsph(SphHandle *h, int nsteps)
 {
-    if (!h) return SPH_E_INVALID;
-    if (h->cfg.solver != SPH_SOLVER_WCSPH) return fail(h, SPH_E_STATE, "handle was not created for wcsph");
-    if (int rc = rigid_released_unprepared(h)) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    int k = 0;
-    // The WCSPH step is a fixed launch sequence with no host decision in it, so two steps (after which the ping-pong
-    // buffers are back in the same roles) are captured once into a hipGraph and replayed: at 30k particles the step is
-    // launch-bound and replay halves it.  Eager launches remain for odd remainders, profiling and slab handles.
-    if (h->graphs_enabled && !h->profiling && !h->slab && !h->rigid && nsteps >= 2) {
-        while (nsteps - k >= 2) {
-            const int key = h->pcur | (h->vcur << 1) | (h->icur << 2);
-            if (!h->wcsph_graph[key]) {
-                hipGraph_t graph = nullptr;
-                const int sim_cnt = h->simulate_cnt;
-                if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { h->graphs_enabled = false; break; }
-                int rc = step_wcsph_once(h);
-                if (!rc) rc = step_wcsph_once(h);
-                hipError_t e = hipStreamEndCapture(h->stream, &graph);
-                h->simulate_cnt = sim_cnt;             // the capture launched nothing
-                if (rc || e != hipSuccess || !graph) { if (graph) (void)hipGraphDestroy(graph); h->graphs_enabled = false; (void)hipGetLastError(); break; }
-                e = hipGraphInstantiate(&h->wcsph_graph[key], graph, nullptr, nullptr, 0);
-                (void)hipGraphDestroy(graph);
-                if (e != hipSuccess) { h->wcsph_graph[key] = nullptr; h->graphs_enabled = false; (void)hipGetLastError(); break; }
-                if ((h->pcur | (h->vcur << 1) | (h->icur << 2)) != key) { h->graphs_enabled = false; break; }   // roles must return after 2 steps
-            }
-            HIP_TRY(h, hipGraphLaunch(h->wcsph_graph[key], h->stream));
-            h->graph_launches += 1;
-            h->simulate_cnt += 2;
-            h->nl_valid = false; h->density_valid = false;
-            k += 2;
-        }
-    }
-    for (; k < nsteps; ++k) {
-        int rc = step_wcsph_once(h);
-        if (rc) return rc;
-    }
-    // overflow is sticky within a call: one read-back per call keeps the steps asynchronous
-    int rc = read_scalars(h);
-    if (rc) return rc;
-    return check_overflow_all(h);
+    const StepFrame f = {SPH_SOLVER_WCSPH, "handle was not created for wcsph", true, false, TAIL_ALWAYS};
+    return run_steps(h, f, nsteps, nullptr, [](SphHandle *hh, SphStepStats *) { return step_wcsph_once(hh); }, [&](int *k) { return wcsph_replay_pairs(h, nsteps, k); });
 }
 
 int sph_step_dfsph(SphHandle *h, int nsteps, SphStepStats *last)
 {
-    if (!h) return SPH_E_INVALID;
-    if (h->cfg.solver != SPH_SOLVER_DFSPH) return fail(h, SPH_E_STATE, "handle was not created for dfsph");
-    if (int rc = rigid_released_unprepared(h)) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    SphStepStats st;
-    memset(&st, 0, sizeof(st));
-    for (int k = 0; k < nsteps; ++k) {
-        int rc = step_dfsph_once(h, &st);
-        if (rc) return rc;
-    }
-    if (last) *last = st;
-    return SPH_OK;
+    const StepFrame f = {SPH_SOLVER_DFSPH, "handle was not created for dfsph", true, false, TAIL_NONE};
+    return run_steps(h, f, nsteps, last, step_dfsph_once);
 }
 
 int sph_step_pcisph(SphHandle *h, int nsteps, SphStepStats *last)
 {
-    if (!h) return SPH_E_INVALID;
-    if (h->cfg.solver != SPH_SOLVER_PCISPH) return fail(h, SPH_E_STATE, "handle was not created for pcisph");
-    if (int rc = rigid_released_unprepared(h)) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    SphStepStats st;
-    memset(&st, 0, sizeof(st));
-    for (int k = 0; k < nsteps; ++k) {
-        int rc = step_pcisph_once(h, &st);
-        if (rc) return rc;
-    }
-    if (last) *last = st;
-    return SPH_OK;
+    const StepFrame f = {SPH_SOLVER_PCISPH, "handle was not created for pcisph", true, false, TAIL_NONE};
+    return run_steps(h, f, nsteps, last, step_pcisph_once);
 }
 
 int sph_step_iisph(SphHandle *h, int nsteps, SphStepStats *last)
 {
-    if (!h) return SPH_E_INVALID;
-    if (h->cfg.solver != SPH_SOLVER_IISPH) return fail(h, SPH_E_STATE, "handle was not created for iisph");
-    if (int rc = rigid_released_unprepared(h)) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    SphStepStats st;
-    memset(&st, 0, sizeof(st));
-    for (int k = 0; k < nsteps; ++k) {
-        int rc = step_iisph_once(h, &st);
-        if (rc) return rc;
-    }
-    if (last) *last = st;
-    return SPH_OK;
+    const StepFrame f = {SPH_SOLVER_IISPH, "handle was not created for iisph", true, false, TAIL_NONE};
+    return run_steps(h, f, nsteps, last, step_iisph_once);
 }
 
-int sph_step_pbf(SphHandle *h, int nsteps)
+int sph_step_pbf(SphHandle *h, int nsteps)       // (pbf has no rigid coupling: nothing to have released)
 {
-    if (!h || nsteps < 0) return SPH_E_INVALID;
-    if (h->cfg.solver != SPH_SOLVER_PBF) return fail(h, SPH_E_STATE, "handle was not created with solver = SPH_SOLVER_PBF");
-    HIP_TRY(h, hipSetDevice(h->device));
-    for (int k = 0; k < nsteps; ++k) {
-        int rc = step_pbf_once(h);
-        if (rc) return rc;
-    }
-    if (nsteps > 0) {
-        // overflow is sticky within a call: one read-back per call, and on slab handles one verdict of all ranks (a rank that failed alone would leave
-        // its peers waiting in the next exchange)
-        int rc = read_scalars(h);
-        if (rc) return rc;
-        if ((rc = check_overflow_all(h))) return rc;
-    }
-    return SPH_OK;
+    const StepFrame f = {SPH_SOLVER_PBF, "handle was not created with solver = SPH_SOLVER_PBF", false, true, TAIL_IF_STEPPED};
+    return run_steps(h, f, nsteps, nullptr, [](SphHandle *hh, SphStepStats *) { return step_pbf_once(hh); });
 }
 
 int sph_get_scalar(SphHandle *h, int which, double *out)
@@ -1346,8 +1218,7 @@ static int set_param(SphHandle *h, int which, double value)
         HIP_TRY(h, hipMemcpyAsync(&h->ds->p_dens_thr, &h->ds_host->p_dens_thr, sizeof(DevScalars) - offsetof(DevScalars, p_dens_thr), hipMemcpyHostToDevice, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
     }
-    for (int k = 0; k < 8; ++k)                                      // captured wcsph step pairs carry the old constants as launch arguments
-        if (h->wcsph_graph[k]) { (void)hipGraphExecDestroy(h->wcsph_graph[k]); h->wcsph_graph[k] = nullptr; }
+    drop_wcsph_graphs(h);                                            // (they carry the old constants as launch arguments)
     return SPH_OK;
 }
 
