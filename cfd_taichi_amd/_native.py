@@ -37,7 +37,9 @@ RIGID_MODES = {"dynamic": RIGID_DYNAMIC, "scripted": RIGID_SCRIPTED, "fixed": RI
 # `solver.<attribute> = value` (include/sph_mi355x.h SPH_P_*): name of the reference's attribute -> id
 SOLVER_PARAMS = {"density_threshold": 64, "min_iteration_density": 65, "min_iteration_density_divergence": 66, "max_iteration_density_divergence": 67,
                  "density_divergence_threshold": 68, "warm_start": 69, "adaptive_dt": 70, "max_dt": 71, "min_dt": 72,
-                 "viscosity_c_s": 73, "viscosity_alpha": 74, "viscosity_epsilon": 75, "tension_k": 76}
+                 "viscosity_c_s": 73, "viscosity_alpha": 74, "viscosity_epsilon": 75, "tension_k": 76,
+                 # the adaptive time step of wcsph / pcisph / iisph / pbf handles (this library's own; dfsph has 70-72)
+                 "step_adaptive_dt": 77, "step_max_dt": 78, "step_min_dt": 79}
 VECTOR_FIELDS = {F_POS, F_VEL, F_ACC, F_VEL_ADV, F_WALL_POS, F_RIGID_POS, F_RIGID_FORCE, F_RIGID_VERT, F_PRESS_FORCE, F_POS_PREDICT, F_D_II, F_D_IJ,
                  F_PBF_DELTA_POS}
 
@@ -379,6 +381,31 @@ def gravity_calls(config):
     return calls
 
 
+def adaptive_dt_calls(config, solver_name=None):
+    """What `solver.adaptive_dt` / `solver.max_dt` / `solver.min_dt` of a config ask of a new wcsph, pcisph, iisph or pbf handle, as the
+    set_param calls that will be made, the bounds before the switch: [("step_max_dt", v), ("step_min_dt", v), ("step_adaptive_dt", 1.0)].
+    All three keys are optional; a bound that is absent keeps the library's default (max_dt: the configured delta_time, min_dt: 1e-5).
+    Under dfsph (solver_name, default `solver.name`) the keys are the reference's own attributes and nothing is asked here.  Pure Python; a bound that is not a finite number
+    > 0, or a flag that is not a truth value, raises ValueError."""
+    solver = config["solver"]
+    if (solver_name or solver.get("name")) == "dfsph":
+        return []
+    calls = []
+    for key in ("max_dt", "min_dt"):
+        v = solver.get(key)
+        if v is None:
+            continue
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not (v > 0 and v < float("inf")):
+            raise ValueError("solver.%s must be a finite number > 0, got %r" % (key, v))
+        calls.append(("step_" + key, float(v)))
+    flag = solver.get("adaptive_dt", False)
+    if flag not in (True, False, 0, 1):
+        raise ValueError("solver.adaptive_dt must be true or false, got %r" % (flag,))
+    if flag:
+        calls.append(("step_adaptive_dt", 1.0))
+    return calls
+
+
 def apply_gravity_calls(target, config):
     """make gravity_calls(config) on a Simulation, a SlabSimulation or a solver mirror, right after creation"""
     for name, *args in gravity_calls(config):
@@ -436,8 +463,8 @@ class Simulation:
     def __init__(self, cfg, rigid=None, lib=None, config=None):
         """rigid: dict(points, vertices, rho_0, pos_offset, attitude_offset (degrees), active) from mesh.rigid_from_config;
         lib: another implementation of the ABI's per-step path (bind_core), default libsph_mi355x.so;
-        config: the config dict cfg was flattened from: its `scene.gravity` list and `scene.forcing` block (gravity_calls) are applied right
-        after creation"""
+        config: the config dict cfg was flattened from: its `scene.gravity` list and `scene.forcing` block (gravity_calls) and its
+        `solver.adaptive_dt` / `max_dt` / `min_dt` (adaptive_dt_calls) are applied right after creation"""
         self._lib = lib or load()
         self.cfg = cfg
         handle = ctypes.c_void_p()
@@ -468,6 +495,8 @@ class Simulation:
         self.last_stats = SphStepStats()
         if config is not None:
             apply_gravity_calls(self, config)
+            for name, value in adaptive_dt_calls(config, "dfsph" if cfg.solver == SOLVER_DFSPH else "other"):
+                self.set_param(name, value)
 
     def _check(self, rc):
         if rc != SPH_OK:

@@ -129,8 +129,20 @@ struct DevScalars {
     double p_dens_thr;   // density_threshold * rho_0 * 0.01, folded in f64 like the Python expression                 :225
     double p_div_thr;    // density_divergence_threshold                                                            :400
     int p_min_dens, p_min_div, p_max_div, p_pad;       // min_iteration_density, min / max_iteration_density_divergence
+    // pcisph handles with the adaptive time step on: delta = 1 / (S * (float)beta(dt)) of the current step, re-formed by the
+    // thread that applies the rule (k_step_dt)                                                                  pcisph_solver.py:23, :47
+    float pci_delta, pci_pad;
 };
 constexpr int kNoteShards = 64;
+
+// The time step (k_pci_predict_rho: pcisph's delta) of a launch of the fixed-dt solvers: the host's value as a launch argument, or -- on a handle
+// whose adaptive time step is on (ds != null) -- what k_step_dt left in device memory at the head of the step.  Read once, at the kernel's head.
+struct StepDt {
+    float value;
+    const DevScalars *ds;
+};
+__device__ __forceinline__ float step_dt(const StepDt &s) { return s.ds ? s.ds->dt : s.value; }
+__device__ __forceinline__ float step_delta(const StepDt &s) { return s.ds ? s.ds->pci_delta : s.value; }
 
 // one thread per step: the step's dt joins the handle's clock (the same f64 additions in the same order as a host sum of the read-back dt's)
 __device__ __forceinline__ void clock_advance(double *clock, float dt) { *clock += (double)dt; }

@@ -264,6 +264,34 @@ int require_async_slab(SphHandle *h)
     return SPH_OK;
 }
 
+// max_rigid_vel of the CFL rule into ds->rigid_vmax, from the body's state as the host holds it now          dfsph_solver.py:104-110
+void launch_rigid_vmax(SphHandle *h)
+{
+    const bool moving = rigid_binned(h);
+    RigidBodyState st = rigid_state(h, nullptr, nullptr);
+    for (int a = 0; a < 3; ++a) st.omega[a] = moving ? h->r_omega[a] : 0.0f;
+    const float vn = moving ? sqrtf((h->r_vel[0] * h->r_vel[0] + h->r_vel[1] * h->r_vel[1]) + h->r_vel[2] * h->r_vel[2]) : 0.0f;
+    hipLaunchKernelGGL(k_rigid_vmax, rigid_parts_grid(h), dim3(kBlock), 0, h->stream, h->Nr, h->RPos, st, vn, h->ds, h->rvmax_part, 0);
+    hipLaunchKernelGGL(k_rigid_vmax, dim3(1), dim3(kBlock), 0, h->stream, h->Nr, h->RPos, st, vn, h->ds, h->rvmax_part, (int)rigid_parts_grid(h).x);
+}
+
+// The adaptive time step of wcsph / pcisph / iisph / pbf (SPH_P_STEP_ADAPTIVE_DT), at the head of the step: the maximum of
+// |v| over the velocities the step starts with (unsorted; one partial per workgroup in pmax), then one workgroup applies dfsph's rule and leaves
+// dt, dt^2, ps.delta_time and pcisph's delta in DevScalars, where every launch of the step reads them (StepDt).  Enqueued like any launch: no host
+// wait, and nodes of the captured wcsph step pair like the others
+void launch_step_dt(SphHandle *h)
+{
+    ProfScope ps(h, K_FINALIZE);
+    const bool body = h->rigid && rigid_binned(h);
+    if (body) launch_rigid_vmax(h);
+    const double r = h->cfg.particle_radius;
+    const StepRule rule{h->c.dt_cfl_num, (float)h->step_max_dt, (float)h->step_min_dt, body ? 1 : 0, h->cfg.solver == SPH_SOLVER_PCISPH ? 1 : 0, h->pci_s,
+                        1000 * (r * r * r) * 8};
+    const int parts = std::max(1, std::min(h->nblocks, kStepDtParts));
+    hipLaunchKernelGGL(k_step_vmax, dim3((unsigned)parts), dim3(kBlock), 0, h->stream, h->c.n, h->V[h->vcur], h->pmax);
+    hipLaunchKernelGGL(k_step_dt, dim3(1), dim3(kBlock), 0, h->stream, h->pmax, parts, rule, h->ds);
+}
+
 // What every solver's step does before its own sweeps: the count (solver_base.py:137), the step's acceleration vector if it is forced, reset_grid +
 // update_grid + the lists (:139-141), and compute_all_rho where the solver's step starts with it (all but pbf; after it P = (pos, rho))
 int step_begin(SphHandle *h)
@@ -272,6 +300,7 @@ int step_begin(SphHandle *h)
     h->simulate_cnt += 1;
     h->comm_stat[6] += 1;
     step_head(h);
+    if (h->step_adaptive) launch_step_dt(h);
     if (is_pressure_solver(h) && (rc = require_async_slab(h))) return rc;
     if ((rc = stage_sort_and_lists(h))) return rc;
     return h->cfg.solver == SPH_SOLVER_PBF ? SPH_OK : stage_density(h);
@@ -302,7 +331,7 @@ int step_wcsph_once(SphHandle *h)
         const Consts &cv = h->c;
         {
             ProfScope ps(h, K_W_FORCE);                     // + kinematic_phase :40-63
-            hipLaunchKernelGGL(k_wcsph_force_rx, grid_for(cv.n), dim3(kBlock), 0, h->stream, cv, h->dt_wcsph, h->P[h->pcur], h->V[h->vcur], h->nl, h->cnt,
+            hipLaunchKernelGGL(k_wcsph_force_rx, grid_for(cv.n), dim3(kBlock), 0, h->stream, cv, step_dt_arg(h), h->P[h->pcur], h->V[h->vcur], h->nl, h->cnt,
                                h->wall_grad, h->x0, h->P[1 - h->pcur], h->V[1 - h->vcur], h->VA[0], h->ds);
             h->pcur ^= 1; h->vcur ^= 1;
         }
@@ -314,7 +343,7 @@ int step_wcsph_once(SphHandle *h)
         ProfScope ps(h, K_W_FORCE);                          // wcsph_solver.py:36-38 + kinematic_phase :40-63
         const bool quad = sweep_mode(h) == SWEEP_QUAD;
         const dim3 gf = quad ? dim3((unsigned)std::max(1, (c.n + 63) / 64)) : grid_for(c.n);
-#define SPH_WFORCE(R, Q, RV) hipLaunchKernelGGL((k_wcsph_force<R, Q>), gf, dim3(kBlock), 0, h->stream, c, h->dt_wcsph, h->P[h->pcur], h->V[h->vcur], h->WP, \
+#define SPH_WFORCE(R, Q, RV) hipLaunchKernelGGL((k_wcsph_force<R, Q>), gf, dim3(kBlock), 0, h->stream, c, step_dt_arg(h), h->P[h->pcur], h->V[h->vcur], h->WP, \
                                                 h->nl, h->nlb, h->cnt, wcsph_pressure(h), h->P[1 - h->pcur], h->V[1 - h->vcur], h->VA[0], RV)
         if (rigid_coupled(h)) { if (quad) SPH_WFORCE(true, true, rigid_view(h)); else SPH_WFORCE(true, false, rigid_view(h)); }
         else { if (quad) SPH_WFORCE(false, true, RigidView()); else SPH_WFORCE(false, false, RigidView()); }
@@ -582,12 +611,7 @@ int dfsph_ext_and_dt(SphHandle *h)
             // A body that is not binned stands still: it enters the CFL rule with velocity and omega zero.  For a body that was never active that
             // is what it holds anyway; a FROZEN body keeps its velocity and omega for a later release (sph_rigid_set_active), and the reference would
             // go on adding that stored speed to max_vel -- here the fluid next to a frozen body steps as without a body
-            const bool moving = rigid_binned(h);
-            RigidBodyState st = rigid_state(h, nullptr, nullptr);
-            for (int a = 0; a < 3; ++a) st.omega[a] = moving ? h->r_omega[a] : 0.0f;
-            const float vn = moving ? sqrtf((h->r_vel[0] * h->r_vel[0] + h->r_vel[1] * h->r_vel[1]) + h->r_vel[2] * h->r_vel[2]) : 0.0f;
-            hipLaunchKernelGGL(k_rigid_vmax, rigid_parts_grid(h), b, 0, s, h->Nr, h->RPos, st, vn, h->ds, h->rvmax_part, 0);
-            hipLaunchKernelGGL(k_rigid_vmax, dim3(1), b, 0, s, h->Nr, h->RPos, st, vn, h->ds, h->rvmax_part, (int)rigid_parts_grid(h).x);
+            launch_rigid_vmax(h);
         }
     }
     const bool async = slab_async(h);

@@ -60,8 +60,8 @@ int step_pbf_once(SphHandle *h)
     if (h->slab && (rc = slab_exchange_field(h, 0, h->P[1 - h->pcur], nullptr, nullptr))) return rc;      // lambda of the ghosts
     {
         ProfScope ps(h, K_B_DELTA);                           // compute_all_delta_pos :55-64, the prediction :26-29, update_all_pos phase 1 :66-84
-        if (qsum) hipLaunchKernelGGL((k_pbf_delta<false, true, true>), g, dim3(kBlock), 0, s, c, k, h->dt_wcsph, h->P[1 - h->pcur], h->V[h->vcur], h->WP, h->nl, h->nlb, h->cnt, f.delta_pos, f.pos_new, f.vel_1);
-        else SPH_LAUNCH_PBF(k_pbf_delta, quad, rx, g, gq, s, c, k, h->dt_wcsph, h->P[1 - h->pcur], h->V[h->vcur], h->WP, h->nl, h->nlb, h->cnt, f.delta_pos, f.pos_new, f.vel_1);
+        if (qsum) hipLaunchKernelGGL((k_pbf_delta<false, true, true>), g, dim3(kBlock), 0, s, c, k, step_dt_arg(h), h->P[1 - h->pcur], h->V[h->vcur], h->WP, h->nl, h->nlb, h->cnt, f.delta_pos, f.pos_new, f.vel_1);
+        else SPH_LAUNCH_PBF(k_pbf_delta, quad, rx, g, gq, s, c, k, step_dt_arg(h), h->P[1 - h->pcur], h->V[h->vcur], h->WP, h->nl, h->nlb, h->cnt, f.delta_pos, f.pos_new, f.vel_1);
     }
     if (h->slab && (rc = slab_exchange_field(h, 4, f.pos_new, f.vel_1, nullptr))) return rc;               // their new position and phase-1 velocity
     {
@@ -124,7 +124,7 @@ int launch_pressure_finalize(SphHandle *h, int mode)
 // instruction (GATE_DENS) -- and the host looks at the control block once per chunk: first after as many iterations as the last step took (the count
 // changes slowly), then every two.  Fills the step's stats and notes which PB holds the final pressures
 template <class Iteration>
-int pressure_loop(SphHandle *h, int cap, float dt, SphStepStats *st, Iteration iteration)
+int pressure_loop(SphHandle *h, int cap, SphStepStats *st, Iteration iteration)
 {
     int rc;
     bool first = true;
@@ -144,7 +144,7 @@ int pressure_loop(SphHandle *h, int cap, float dt, SphStepStats *st, Iteration i
     st->n_dens = h->ds_host->dens_it;
     st->capped = h->ds_host->dens_capped;
     st->dens_err = h->ds_host->dens_avg;
-    st->dt = dt;
+    st->dt = h->step_adaptive ? h->ds_host->dt : h->dt_wcsph;      // (adaptive: k_step_dt's, in the block the loop just read back)
     h->pb_final = h->ds_host->dens_it & 1;
     h->last_iters = h->ds_host->dens_it;
     return SPH_OK;
@@ -159,7 +159,7 @@ int step_pcisph_once(SphHandle *h, SphStepStats *st)
     const Consts &c = h->c;
     hipStream_t s = h->stream;
     const dim3 g = grid_for(c.n), b(kBlock);
-    const float dt = h->dt_wcsph;                           // delta_time never changes in pcisph
+    const StepDt dt = step_dt_arg(h);                       // delta_time never changes inside a pcisph step
     const bool rg = rigid_coupled(h);
     const RigidView rv = rg ? rigid_view(h) : RigidView();
     const PciFields f = pci_fields(h);
@@ -182,12 +182,12 @@ int step_pcisph_once(SphHandle *h, SphStepStats *st)
         HIP_TRY(h, hipMemsetAsync(zero_press, c.boundary_handle ? 1 : 0, sizeof(int) * (size_t)h->nblocks, s));
     auto predict_rho = [&](int k, int gate) {               // the k-th predict_rho + residual: reads press from PB[k&1]
         ProfScope ps(h, K_P_PREDICT_RHO);
-        SPH_LAUNCH_RMX0(k_pci_predict_rho, rg, sweep_mode(h), relaxed_pressure(h), c.n, sweep_lds(h, StageF4<>::kBytes), s, c, h->pci_delta, PP, h->WP, h->nl, h->nlb, h->cnt, h->ds, PB[k & 1],
+        SPH_LAUNCH_RMX0(k_pci_predict_rho, rg, sweep_mode(h), relaxed_pressure(h), c.n, sweep_lds(h, StageF4<>::kBytes), s, c, step_delta_arg(h), PP, h->WP, h->nl, h->nlb, h->cnt, h->ds, PB[k & 1],
                        PB[(k + 1) & 1], h->rho_adv, h->psum, h->pcnt, gate, rv, h->stage_src, h->stage_cnt);
     };
     predict_rho(0, GATE_NONE);                              // :53-56
     if ((rc = slab_refresh_w_and_pressure_finalize(h, PB[1], PFIN_PCI_FIRST))) return rc;
-    rc = pressure_loop(h, cap, dt, st, [&](int k) -> int {
+    rc = pressure_loop(h, cap, st, [&](int k) -> int {
         int r;
         {
             ProfScope ps(h, K_P_PRESS);                     // iter_press (already in PB[k&1]), update_press_force, predict_vel_pos
@@ -217,7 +217,7 @@ int step_iisph_once(SphHandle *h, SphStepStats *st)
     const Consts &c = h->c;
     hipStream_t s = h->stream;
     const dim3 g = grid_for(c.n), b(kBlock);
-    const float dt = h->dt_wcsph;
+    const StepDt dt = step_dt_arg(h);
     const bool rg = rigid_coupled(h);
     const RigidView rv = rg ? rigid_view(h) : RigidView();
     const IiFields f = ii_fields(h);
@@ -239,7 +239,7 @@ int step_iisph_once(SphHandle *h, SphStepStats *st)
     }
     int *zero_dij = (h->pci_zero_press && h->staged && !h->slab) ? h->pci_zero_press : nullptr;      // tiles without pressure skip compute_all_d_ij (k_ii_dij)
     if (zero_dij) HIP_TRY(h, hipMemsetAsync(zero_dij, 0, sizeof(int) * (size_t)h->nblocks, s));      // DIJ still holds last step's sums
-    rc = pressure_loop(h, cap, dt, st, [&](int k) -> int {
+    rc = pressure_loop(h, cap, st, [&](int k) -> int {
         {
             ProfScope ps(h, K_I_DIJ);                       // compute_all_d_ij :91
             SPH_LAUNCH_RMX0(k_ii_dij, rg, sweep_mode(h), relaxed_pressure(h), c.n, sweep_lds(h, StageF4S::kBytes), s, c, dt, PB[(k - 1) & 1], h->rho, h->nl, h->cnt, h->ds,
@@ -422,6 +422,7 @@ int pcisph_precompute(SphHandle *h)
             for (int j : rbucket[bk]) add(h->rigid_pos_host.data() + 3 * (size_t)j);
         }
     }
-    h->pci_delta = 1.0f / ((((sx * sx + sy * sy) + sz * sz) + sq) * h->pci_beta);   // :47
+    h->pci_s = ((sx * sx + sy * sy) + sz * sz) + sq;
+    h->pci_delta = 1.0f / (h->pci_s * h->pci_beta);   // :47
     return SPH_OK;
 }

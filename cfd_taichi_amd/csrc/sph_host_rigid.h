@@ -292,11 +292,12 @@ int read_rigid_reduce(SphHandle *h)
     return SPH_OK;
 }
 
-// The dt of the coming body step: ps.delta_time if dfsph has set it, the value of the step before otherwise   rigid_solver.py:223-224
+// The dt of the coming body step: ps.delta_time if dfsph -- or the adaptive time step of another solver -- has set it, the value of the step
+// before otherwise                                                                                            rigid_solver.py:223-224
 int rigid_next_dt(SphHandle *h, float *dt)
 {
     *dt = h->rs_dt;
-    if (h->cfg.solver == SPH_SOLVER_DFSPH) {
+    if (h->cfg.solver == SPH_SOLVER_DFSPH || h->step_adaptive) {
         if (int rc = read_scalars(h)) return rc;
         if (h->ds_host->ps_dt > 0.0f) *dt = h->ds_host->ps_dt;
     }

@@ -834,6 +834,7 @@ int alloc_device(SphHandle *h, const HostScene &sc)
     HIP_TRY(h, hipMemcpyAsync(h->ds, h->ds_host, sizeof(DevScalars), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->dt_wcsph = (float)h->cfg.delta_time;
+    h->step_max_dt = h->cfg.delta_time;                              // SPH_P_STEP_MAX_DT's default: switching the rule on can only shorten steps
     return SPH_OK;
 }
 
@@ -890,7 +891,13 @@ inline void step_head(SphHandle *h)
     hipLaunchKernelGGL(k_accel_eval, dim3(1), dim3(1), 0, h->stream, h->ds);
 }
 
-// the captured wcsph step pairs hold the count, the grids, delta_time and the k_accel_eval node (or its absence) as they were at capture
+// The time step of a launch of wcsph / pcisph / iisph / pbf (StepDt, sph_device.h): the host's value, or the device's on a handle whose adaptive
+// time step is on; step_delta_arg: the same for pcisph's delta
+inline StepDt step_dt_arg(const SphHandle *h) { return StepDt{h->dt_wcsph, h->step_adaptive ? h->ds : nullptr}; }
+inline StepDt step_delta_arg(const SphHandle *h) { return StepDt{h->pci_delta, h->step_adaptive ? h->ds : nullptr}; }
+
+// the captured wcsph step pairs hold the count, the grids, delta_time, the k_accel_eval node and the two nodes of the adaptive time step (or their
+// absence) as they were at capture
 inline void drop_wcsph_graphs(SphHandle *h)
 {
     for (int k = 0; k < 8; ++k)
@@ -918,7 +925,9 @@ int write_delta_time(SphHandle *h, double value)
 {
     h->dt_wcsph = (float)value;                                      // the launch argument of the fixed-dt solvers
     h->cfg.delta_time = value;
-    if (h->cfg.solver == SPH_SOLVER_DFSPH) {                         // dfsph keeps delta_time, delta_time_2 on the device (dfsph_solver.py:20, :118)
+    // dfsph keeps delta_time, delta_time_2 on the device (dfsph_solver.py:20, :118); so does a handle of another solver while its adaptive time
+    // step is on (the next step's rule overwrites the value, as on dfsph)
+    if (h->cfg.solver == SPH_SOLVER_DFSPH || h->step_adaptive) {
         int rc = read_scalars(h);
         if (rc) return rc;
         h->ds_host->dt = (float)value;

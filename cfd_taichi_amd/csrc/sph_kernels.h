@@ -1806,6 +1806,54 @@ __global__ __launch_bounds__(kBlock) void k_finalize_max(const float *__restrict
     }
 }
 
+// ---- the adaptive time step of wcsph / pcisph / iisph / pbf -------------------------------------------------
+// Two launches at the head of a step while the handle's SPH_P_STEP_ADAPTIVE_DT is on, none otherwise.  The first streams the velocities the step
+// starts with -- unsorted: a maximum has no order -- into one f32 partial per workgroup (wave_max, then LDS; no float atomics); the second, one
+// workgroup, takes the maximum of the partials and applies dfsph's rule (dfsph_solver.py:104-119) with the handle's own bounds.
+constexpr int kStepDtParts = 1024;       // workgroups of the first launch at most (grid-stride above 256 k particles)
+struct StepRule {
+    float cfl_num, max_dt, min_dt;       // c.dt_cfl_num; SPH_P_STEP_MAX_DT / SPH_P_STEP_MIN_DT
+    int rigid;                           // a body is binned: ds->rigid_vmax (k_rigid_vmax, enqueued before) joins the maximum    :104-111
+    int pcisph;                          // the handle's solver is pcisph: delta follows dt
+    float pci_s;                         // pcisph_solver.py:47: the neighbourhood sums of construction, (sum grad W)^2 + sum |grad W|^2
+    double pci_m;                        // the particle mass as the Python expression of :23 has it (f64)
+};
+__global__ __launch_bounds__(kBlock) void k_step_vmax(int n, const float4 *__restrict__ V, float *__restrict__ part)
+{
+    float m = 0.0f;
+    for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+        const float4 v = V[i];
+        m = fmaxf(m, sqrtf((v.x * v.x + v.y * v.y) + v.z * v.z));
+    }
+    block_partial_max(blockIdx.x, m, part);
+}
+__global__ __launch_bounds__(kBlock) void k_step_dt(const float *__restrict__ part, int nparts, StepRule r, DevScalars *__restrict__ ds)
+{
+    __shared__ float s_part[kBlock / 64];
+    float m = 0.0f;
+    for (int k = threadIdx.x; k < nparts; k += kBlock) m = fmaxf(m, part[k]);
+    const float wm = wave_max(m);
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = wm;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    float max_vel = s_part[0];
+    for (int w = 1; w < kBlock / 64; ++w) max_vel = fmaxf(max_vel, s_part[w]);
+    ds->vmax = max_vel;
+    if (r.rigid) max_vel += ds->rigid_vmax;                       // :111
+    const float max_delta_time = r.cfl_num / max_vel * 0.2f;      // :112 (max_vel = 0: +inf, so max_dt)
+    float dt;
+    if (max_delta_time > r.max_dt) dt = r.max_dt;                 // :114-117
+    else dt = rmax(max_delta_time, r.min_dt);
+    ds->dt = dt;
+    ds->dt2 = dt * dt;                                            // :118
+    ds->ps_dt = dt;                                               // :119
+    if (r.pcisph) {
+        const double dtf = (double)dt;                            // pcisph_solver.py:23, as pcisph_precompute folds it for the configured step
+        const double beta = dtf * dtf * r.pci_m * r.pci_m * 2 / (double)(1000 * 1000);
+        ds->pci_delta = 1.0f / (r.pci_s * (float)beta);           // :47
+    }
+}
+
 // ======================================================================================
 // W1 / D1: density (+ alpha)          solver_base.py:41-72, dfsph_solver.py:32-89, wcsph_solver.py:66-68
 //   WCSPH: writes Pout = (pos, rho), Vout = (vel, p/rho^2), rho[], pressure[]
@@ -2155,12 +2203,13 @@ __device__ __forceinline__ void rigid_viscosity(const Consts &c, const RigidView
 //   reads P = (pos, rho), V = (vel, p/rho^2); writes the next state Pn = (pos', .), Vn = (vel', .), acc
 // ======================================================================================
 template <bool RIGID, bool QUAD>
-__global__ __launch_bounds__(kBlock) void k_wcsph_force(Consts c, float dt, const float4 *__restrict__ P, const float4 *__restrict__ V,
+__global__ __launch_bounds__(kBlock) void k_wcsph_force(Consts c, StepDt step, const float4 *__restrict__ P, const float4 *__restrict__ V,
                                                         const float4 *__restrict__ WP, const uint32_t *__restrict__ nl,
                                                         const uint32_t *__restrict__ nlb, const int *__restrict__ cnt,
                                                         const float *__restrict__ pressure, float4 *__restrict__ Pn,
                                                         float4 *__restrict__ Vn, float4 *__restrict__ acc_out, RigidView rv)
 {
+    const float dt = step_dt(step);
     if (blockIdx.x == 0 && threadIdx.x == 0) clock_advance(c.clock, dt);      // the step's last launch: its dt joins the handle's clock
     SPH_SWEEP_PROLOGUE_M(QUAD)
     const float4 vi = V[ii];

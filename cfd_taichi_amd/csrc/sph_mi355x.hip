@@ -92,6 +92,10 @@ struct SphHandle {
     int N = 0, Nb = 0, Nr = 0;
     int nblocks = 0;
     float dt_wcsph = 0.f;
+    // the adaptive time step of wcsph / pcisph / iisph / pbf (SPH_P_STEP_*).  While it is on the step's dt -- and pcisph's
+    // delta -- live in DevScalars (k_step_dt) and dt_wcsph / pci_delta are what they were when it was switched on; switching it off reads them back
+    bool step_adaptive = false;
+    double step_max_dt = 0.0, step_min_dt = 1e-5;          // max_dt: delta_time as configured (build_scene)
     int simulate_cnt = 0;
     // gravity as a vector, constant or harmonic (sph_set_gravity / sph_set_forcing): the host's copy of DevScalars.frc.  frc.accel is exact here
     // while frc.on == 0 (= frc.g); under forcing the device forms it (k_accel_eval) and a read-back refreshes this copy
@@ -114,6 +118,7 @@ struct SphHandle {
     unsigned sweep_lds = 0;      // sph_tune_time: dynamic LDS bytes per block on the unstaged DFSPH sweeps (caps the waves per CU)
     int last_iters = 2;          // iteration count of the last step's density / pressure loop: size of the next step's first chunk
     float pci_delta = 0.f, pci_beta = 0.f;   // pcisph_solver.py:23-24, :47
+    float pci_s = 0.f;                       // :47, the sums under delta: (sum grad W)^2 + sum |grad W|^2 of the fullest neighbourhood
     int pci_max_index = -1, pci_max_count = -1;
     std::vector<float> pci_fluid_pos, rigid_pos_host;   // initial lattice / placed rigid samples, for pre_compute's 27-cell walk on the host
     int *cnt = nullptr;
@@ -1116,13 +1121,15 @@ int sph_get_scalar(SphHandle *h, int which, double *out)
     if (!h || !out) return SPH_E_INVALID;
     switch (which) {
     case SPH_S_DELTA_TIME:
-        if (h->cfg.solver != SPH_SOLVER_DFSPH) { *out = (double)h->dt_wcsph; return SPH_OK; }   // only dfsph adapts delta_time
+        if (h->cfg.solver != SPH_SOLVER_DFSPH && !h->step_adaptive) { *out = (double)h->dt_wcsph; return SPH_OK; }   // a launch argument: the host's value
         else { int rc = read_scalars(h); if (rc) return rc; *out = (double)h->ds_host->dt; return SPH_OK; }
     case SPH_S_SIMULATE_CNT: *out = (double)h->simulate_cnt; return SPH_OK;
     case SPH_S_PARTICLE_M: *out = (double)h->c.m; return SPH_OK;
     case SPH_S_SUPPORT_RADIUS: *out = (double)h->c.h; return SPH_OK;
     case SPH_S_GRAPH_LAUNCHES: *out = (double)h->graph_launches; return SPH_OK;
-    case SPH_S_PCISPH_DELTA: *out = (double)h->pci_delta; return SPH_OK;
+    case SPH_S_PCISPH_DELTA:
+        if (h->step_adaptive) { int rc = read_scalars(h); if (rc) return rc; *out = (double)h->ds_host->pci_delta; return SPH_OK; }      // k_step_dt's
+        *out = (double)h->pci_delta; return SPH_OK;
     case SPH_S_PCISPH_BETA: *out = (double)h->pci_beta; return SPH_OK;
     case SPH_S_PCISPH_MAX_INDEX: *out = (double)h->pci_max_index; return SPH_OK;
     case SPH_S_PCISPH_MAX_COUNT: *out = (double)h->pci_max_count; return SPH_OK;
@@ -1153,6 +1160,9 @@ int sph_get_scalar(SphHandle *h, int which, double *out)
     case SPH_P_VISCOSITY_ALPHA: *out = h->p.viscosity_alpha; return SPH_OK;
     case SPH_P_VISCOSITY_EPSILON: *out = h->p.viscosity_epsilon; return SPH_OK;
     case SPH_P_TENSION_K: *out = h->p.tension_k; return SPH_OK;
+    case SPH_P_STEP_ADAPTIVE_DT: *out = h->step_adaptive ? 1.0 : 0.0; return SPH_OK;
+    case SPH_P_STEP_MAX_DT: *out = h->step_max_dt; return SPH_OK;
+    case SPH_P_STEP_MIN_DT: *out = h->step_min_dt; return SPH_OK;
     default:
         if (h->rigid && which >= SPH_S_RIGID_CENTROID && which < SPH_S_RIGID_INERTIA_INV + 9) {
             if (which < SPH_S_RIGID_OMEGA) *out = (double)h->centroid[which - SPH_S_RIGID_CENTROID];
@@ -1222,9 +1232,43 @@ static int set_param(SphHandle *h, int which, double value)
     return SPH_OK;
 }
 
+// SPH_P_STEP_*: the adaptive time step of wcsph / pcisph / iisph / pbf handles.  Validated before anything is touched.  Switching it on hands the
+// current delta_time (and pcisph's delta) to the device, where they live from then on; switching it off takes back what the last step left there.
+// Either way the captured wcsph step pairs hold or lack its two nodes and carry the bounds as launch arguments: they are dropped
+static int set_step_param(SphHandle *h, int which, double value)
+{
+    if (h->cfg.solver == SPH_SOLVER_DFSPH) return fail(h, SPH_E_STATE, "sph_set_scalar(%d): dfsph adapts delta_time through SPH_P_ADAPTIVE_DT / SPH_P_MAX_DT / SPH_P_MIN_DT", which);
+    if (h->slab) return fail(h, SPH_E_STATE, "sph_set_scalar(%d): the adaptive time step is not available on a slab handle", which);
+    if (which == SPH_P_STEP_ADAPTIVE_DT) {
+        if (value != 0.0 && value != 1.0) return fail(h, SPH_E_INVALID, "sph_set_scalar(%d): 0 or 1 expected, got %g", which, value);
+    } else if (!(value > 0.0) || !std::isfinite(value))
+        return fail(h, SPH_E_INVALID, "sph_set_scalar(%d): a finite value > 0 expected, got %g", which, value);
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (which == SPH_P_STEP_MAX_DT) h->step_max_dt = value;
+    else if (which == SPH_P_STEP_MIN_DT) h->step_min_dt = value;
+    else if ((value != 0.0) != h->step_adaptive) {
+        if (int rc = read_scalars(h)) return rc;
+        if (value != 0.0) {
+            h->ds_host->dt = h->dt_wcsph;
+            h->ds_host->dt2 = h->ds_host->dt * h->ds_host->dt;
+            h->ds_host->pci_delta = h->pci_delta;
+            HIP_TRY(h, hipMemcpyAsync(h->ds, h->ds_host, offsetof(DevScalars, ps_dt), hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(h, hipMemcpyAsync(&h->ds->pci_delta, &h->ds_host->pci_delta, sizeof(float), hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+        } else {
+            if (h->ds_host->dt != h->dt_wcsph) { h->dt_wcsph = h->ds_host->dt; h->cfg.delta_time = (double)h->ds_host->dt; }      // (as write_delta_time)
+            if (h->cfg.solver == SPH_SOLVER_PCISPH) h->pci_delta = h->ds_host->pci_delta;        // (SPH_S_PCISPH_BETA stays the attribute of construction, :23)
+        }
+        h->step_adaptive = value != 0.0;
+    }
+    drop_wcsph_graphs(h);
+    return SPH_OK;
+}
+
 int sph_set_scalar(SphHandle *h, int which, double value)
 {
     if (!h) return SPH_E_INVALID;
+    if (which >= SPH_P_STEP_ADAPTIVE_DT && which <= SPH_P_STEP_MIN_DT) return set_step_param(h, which, value);
     if (which >= SPH_P_DENSITY_THRESHOLD && which <= SPH_P_TENSION_K) return set_param(h, which, value);      // (on slab handles too: every rank sets the same)
     if (which == SPH_S_TIME) {                                        // the handle's clock; the acceleration vector follows at once
         if (!std::isfinite(value)) return fail(h, SPH_E_INVALID, "sph_set_scalar(SPH_S_TIME): a finite value expected, got %g", value);

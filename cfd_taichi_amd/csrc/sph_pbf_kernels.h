@@ -188,11 +188,12 @@ __global__ __launch_bounds__(kBlock) void k_pbf_lambda(Consts c, PbfConsts k, co
 
 // delta_pos, the prediction and phase 1 of update_all_pos.  PL = (pos, lambda); writes Pn = new position, Vn = phase-1 velocity.
 template <bool QUAD, bool RX = false, bool QSUM = false>
-__global__ __launch_bounds__(kBlock) void k_pbf_delta(Consts c, PbfConsts k, float dt, const float4 *__restrict__ PL, const float4 *__restrict__ V,
+__global__ __launch_bounds__(kBlock) void k_pbf_delta(Consts c, PbfConsts k, StepDt step, const float4 *__restrict__ PL, const float4 *__restrict__ V,
                                                       const float4 *__restrict__ WP, const uint32_t *__restrict__ nl,
                                                       const uint32_t *__restrict__ nlb, const int *__restrict__ cnt,
                                                       float4 *__restrict__ dpos_out, float4 *__restrict__ Pn, float4 *__restrict__ Vn)
 {
+    const float dt = step_dt(step);
     if (blockIdx.x == 0 && threadIdx.x == 0) clock_advance(c.clock, dt);      // once per step: its dt joins the handle's clock
     const float4 *P = PL;
     SPH_SWEEP_PROLOGUE_M(QUAD)

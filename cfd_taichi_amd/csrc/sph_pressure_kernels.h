@@ -92,9 +92,9 @@ __global__ __launch_bounds__(kFinBlock) void k_finalize_pressure(const double *_
     }
 }
 
-__global__ void k_pressure_ctrl_begin(DevScalars *__restrict__ ds, int cap, float dt)
+__global__ void k_pressure_ctrl_begin(DevScalars *ds, int cap, StepDt step)
 {
-    clock_advance(&ds->sim_time, dt);      // once per step, one thread: delta_time never changes inside a pcisph / iisph step
+    clock_advance(&ds->sim_time, step_dt(step));      // once per step, one thread: delta_time never changes inside a pcisph / iisph step
     ds->overflow_any = 0;
     ds->dens_active = 1; ds->dens_it = 0; ds->dens_cap = cap; ds->dens_capped = 0; ds->dens_avg = 0.f;
     ds->res_prev = 0.f; ds->res_have_prev = 0; ds->res_diverged = 0;
@@ -106,11 +106,12 @@ __global__ void k_pressure_ctrl_begin(DevScalars *__restrict__ ds, int cap, floa
 // compute_ext_force (:237-244: tension, viscosity, gravity) + reset() (:247-250) + the first predict_vel_pos (:73-89)
 //   reads P = (pos, rho), V = (vel, -)
 template <bool RIGID, int SWEEP, bool RX = false>
-__global__ __launch_bounds__(kBlock) void k_pci_ext(Consts c, float dt, const float4 *__restrict__ P, const float4 *__restrict__ V,
+__global__ __launch_bounds__(kBlock) void k_pci_ext(Consts c, StepDt step, const float4 *__restrict__ P, const float4 *__restrict__ V,
                                                     const uint32_t *__restrict__ nl, const int *__restrict__ cnt,
                                                     float4 *__restrict__ EF, float4 *__restrict__ PF, float4 *__restrict__ PB0,
                                                     float4 *__restrict__ PP, RigidView rv, const uint2 *__restrict__ stage_src, const int *__restrict__ stage_cnt)
 {
+    const float dt = step_dt(step);
     constexpr bool STAGED = SWEEP == SWEEP_STAGED, QUAD = SWEEP == SWEEP_QUAD;
     using K = KF<RX>;                                        // kernel functions of the handle's arithmetic (sph_device.h)
     extern __shared__ float4 s_operand[];
@@ -179,7 +180,7 @@ __global__ __launch_bounds__(kBlock) void k_pci_ext(Consts c, float dt, const fl
 // predict_rho (:91-103) + compute_residual partials (:126-138) + the iter_press this particle would see next (:105-109).
 //   P here is PP = predicted positions: the neighbour SET is the list (current positions), the kernel argument is not.
 template <bool RIGID, int SWEEP, bool RX = false>
-__global__ __launch_bounds__(kBlock) void k_pci_predict_rho(Consts c, float delta, const float4 *__restrict__ P,
+__global__ __launch_bounds__(kBlock) void k_pci_predict_rho(Consts c, StepDt step, const float4 *__restrict__ P,
                                                             const float4 *__restrict__ WP, const uint32_t *__restrict__ nl,
                                                             const uint32_t *__restrict__ nlb, const int *__restrict__ cnt,
                                                             const DevScalars *__restrict__ ds, const float4 *__restrict__ PBin,
@@ -187,6 +188,7 @@ __global__ __launch_bounds__(kBlock) void k_pci_predict_rho(Consts c, float delt
                                                             double *__restrict__ psum, int *__restrict__ pcnt, int gate, RigidView rv,
                                                             const uint2 *__restrict__ stage_src, const int *__restrict__ stage_cnt)
 {
+    const float delta = step_delta(step);
     constexpr bool STAGED = SWEEP == SWEEP_STAGED, QUAD = SWEEP == SWEEP_QUAD;
     using K = KF<RX>;                                        // kernel functions of the handle's arithmetic (sph_device.h)
     extern __shared__ float4 s_operand[];
@@ -232,7 +234,7 @@ __global__ __launch_bounds__(kBlock) void k_pci_predict_rho(Consts c, float delt
 
 // update_press_force (:111-124, :192-224) + predict_vel_pos (:73-89).   P here is PB = (pos, press_iter)
 template <bool RIGID, int SWEEP, bool RX = false>
-__global__ __launch_bounds__(kBlock) void k_pci_press(Consts c, float dt, const float4 *__restrict__ P, const float4 *__restrict__ WP,
+__global__ __launch_bounds__(kBlock) void k_pci_press(Consts c, StepDt step, const float4 *__restrict__ P, const float4 *__restrict__ WP,
                                                       const uint32_t *__restrict__ nl, const uint32_t *__restrict__ nlb,
                                                       const int *__restrict__ cnt, const float *__restrict__ rho,
                                                       const float4 *__restrict__ V, const float4 *__restrict__ EF,
@@ -240,6 +242,7 @@ __global__ __launch_bounds__(kBlock) void k_pci_press(Consts c, float dt, const 
                                                       float4 *__restrict__ PP, int gate, RigidView rv, const uint2 *__restrict__ stage_src, const int *__restrict__ stage_cnt,
                                                       int *__restrict__ zero_press)
 {
+    const float dt = step_dt(step);
     constexpr bool STAGED = SWEEP == SWEEP_STAGED, QUAD = SWEEP == SWEEP_QUAD;
     using K = KF<RX>;                                        // kernel functions of the handle's arithmetic (sph_device.h)
     extern __shared__ float4 s_operand[];
@@ -323,10 +326,11 @@ __global__ __launch_bounds__(kBlock) void k_pci_press(Consts c, float dt, const 
 }
 
 // integration :226-245
-__global__ __launch_bounds__(kBlock) void k_pci_integrate(Consts c, float dt, const float4 *__restrict__ P, const float4 *__restrict__ V,
+__global__ __launch_bounds__(kBlock) void k_pci_integrate(Consts c, StepDt step, const float4 *__restrict__ P, const float4 *__restrict__ V,
                                                           const float4 *__restrict__ EF, const float4 *__restrict__ PF,
                                                           float4 *__restrict__ Pn, float4 *__restrict__ Vn)
 {
+    const float dt = step_dt(step);
     int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= c.n) return;
     const float4 p = P[i], vi = V[i], e = EF[i], f = PF[i];
@@ -349,12 +353,13 @@ __global__ __launch_bounds__(kBlock) void k_pci_integrate(Consts c, float dt, co
 // ======================================================================================
 // predict_advection, first half (:43-56): tension, viscosity, f_adv, v_adv, d_ii.   P = (pos, rho), V = (vel, -)
 template <bool RIGID, int SWEEP, bool RX = false>
-__global__ __launch_bounds__(kBlock) void k_ii_advect(Consts c, float dt, const float4 *__restrict__ P, const float4 *__restrict__ V,
+__global__ __launch_bounds__(kBlock) void k_ii_advect(Consts c, StepDt step, const float4 *__restrict__ P, const float4 *__restrict__ V,
                                                       const float4 *__restrict__ WP, const uint32_t *__restrict__ nl,
                                                       const uint32_t *__restrict__ nlb, const int *__restrict__ cnt,
                                                       float4 *__restrict__ VA, float4 *__restrict__ DII, RigidView rv,
                                                       const uint2 *__restrict__ stage_src, const int *__restrict__ stage_cnt)
 {
+    const float dt = step_dt(step);
     constexpr bool STAGED = SWEEP == SWEEP_STAGED, QUAD = SWEEP == SWEEP_QUAD;
     using K = KF<RX>;                                        // kernel functions of the handle's arithmetic (sph_device.h)
     extern __shared__ float4 s_operand[];
@@ -434,13 +439,14 @@ __global__ __launch_bounds__(kBlock) void k_ii_advect(Consts c, float dt, const 
 
 // predict_advection, second half (:58-82): rho_adv, p_iter = 0.5 p_past, a_ii.   P = (pos, rho), V = VA = (v_adv, -)
 template <bool RIGID, int SWEEP, bool RX = false>
-__global__ __launch_bounds__(kBlock) void k_ii_rho_adv(Consts c, float dt, const float4 *__restrict__ P, const float4 *__restrict__ V,
+__global__ __launch_bounds__(kBlock) void k_ii_rho_adv(Consts c, StepDt step, const float4 *__restrict__ P, const float4 *__restrict__ V,
                                                        const float4 *__restrict__ WP, const uint32_t *__restrict__ nl,
                                                        const uint32_t *__restrict__ nlb, const int *__restrict__ cnt,
                                                        const float4 *__restrict__ DII, const float *__restrict__ p_past,
                                                        float *__restrict__ rho_adv, float *__restrict__ a_ii, float4 *__restrict__ PB0,
                                                        RigidView rv, const uint2 *__restrict__ stage_src, const int *__restrict__ stage_cnt)
 {
+    const float dt = step_dt(step);
     constexpr bool STAGED = SWEEP == SWEEP_STAGED, QUAD = SWEEP == SWEEP_QUAD;
     using K = KF<RX>;                                        // kernel functions of the handle's arithmetic (sph_device.h)
     extern __shared__ float4 s_operand[];
@@ -498,11 +504,12 @@ __global__ __launch_bounds__(kBlock) void k_ii_rho_adv(Consts c, float dt, const
 
 // compute_all_d_ij (:130-135, :324-327).   P here is PB = (pos, p_iter)
 template <bool RIGID, int SWEEP, bool RX = false>
-__global__ __launch_bounds__(kBlock) void k_ii_dij(Consts c, float dt, const float4 *__restrict__ P, const float *__restrict__ rho,
+__global__ __launch_bounds__(kBlock) void k_ii_dij(Consts c, StepDt step, const float4 *__restrict__ P, const float *__restrict__ rho,
                                                    const uint32_t *__restrict__ nl, const int *__restrict__ cnt,
                                                    const DevScalars *__restrict__ ds, float4 *__restrict__ DIJ, int gate, RigidView rv,
                                                    const uint2 *__restrict__ stage_src, const int *__restrict__ stage_cnt, int *__restrict__ zero_dij)
 {
+    const float dt = step_dt(step);
     constexpr bool STAGED = SWEEP == SWEEP_STAGED, QUAD = SWEEP == SWEEP_QUAD;
     using K = KF<RX>;                                        // kernel functions of the handle's arithmetic (sph_device.h)
     extern __shared__ float4 s_operand[];
@@ -558,7 +565,7 @@ struct StageUpdateP {
 };
 // update_p (:137-157) + compute_residual partials (:110-121).   P = PBin = (pos, p_iter); writes PBout = (pos, new p_iter)
 template <bool RIGID, int SWEEP, bool RX = false>
-__global__ __launch_bounds__(kBlock) void k_ii_update_p(Consts c, float dt, const float4 *__restrict__ P, const float4 *__restrict__ DII,
+__global__ __launch_bounds__(kBlock) void k_ii_update_p(Consts c, StepDt step, const float4 *__restrict__ P, const float4 *__restrict__ DII,
                                                         const float4 *__restrict__ DIJ, const float4 *__restrict__ WP,
                                                         const uint32_t *__restrict__ nl, const uint32_t *__restrict__ nlb,
                                                         const int *__restrict__ cnt, const float *__restrict__ rho,
@@ -567,6 +574,7 @@ __global__ __launch_bounds__(kBlock) void k_ii_update_p(Consts c, float dt, cons
                                                         double *__restrict__ psum, int *__restrict__ pcnt, int gate, RigidView rv,
                                                         const uint2 *__restrict__ stage_src, const int *__restrict__ stage_cnt)
 {
+    const float dt = step_dt(step);
     constexpr bool STAGED = SWEEP == SWEEP_STAGED, QUAD = SWEEP == SWEEP_QUAD;
     using K = KF<RX>;                                        // kernel functions of the handle's arithmetic (sph_device.h)
     extern __shared__ float4 s_operand[];
@@ -640,11 +648,12 @@ __global__ __launch_bounds__(kBlock) void k_ii_update_p(Consts c, float dt, cons
 }
 
 // intergation (:189-210) with compute_all_press_force (:172-176)
-__global__ __launch_bounds__(kBlock) void k_ii_integrate(Consts c, float dt, const float4 *__restrict__ P, const float4 *__restrict__ VA,
+__global__ __launch_bounds__(kBlock) void k_ii_integrate(Consts c, StepDt step, const float4 *__restrict__ P, const float4 *__restrict__ VA,
                                                          const float4 *__restrict__ DII, const float4 *__restrict__ DIJ,
                                                          const float4 *__restrict__ PB, float4 *__restrict__ Pn, float4 *__restrict__ Vn,
                                                          float4 *__restrict__ FP, float *__restrict__ p_past)
 {
+    const float dt = step_dt(step);
     int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= c.n) return;
     const float4 p = P[i], va = VA[i], di = DII[i], dj = DIJ[i];

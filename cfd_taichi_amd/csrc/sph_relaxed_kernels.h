@@ -435,12 +435,13 @@ __global__ __launch_bounds__(kBlock) void k_wcsph_density_rx(Consts c, const flo
 // W2: pressure gradient, wall pressure, viscosity, tension, symplectic Euler      wcsph_solver.py:40-129, solver_base.py:170-217
 //   reads P = (pos, rho), V = (vel, p / rho^2), G; writes the next state and raises DevScalars.moved when a particle is more than skin / 2
 //   away from X0, its position at the last list build
-__global__ __launch_bounds__(kBlock) void k_wcsph_force_rx(Consts c, float dt, const float4 *__restrict__ P, const float4 *__restrict__ V,
+__global__ __launch_bounds__(kBlock) void k_wcsph_force_rx(Consts c, StepDt step, const float4 *__restrict__ P, const float4 *__restrict__ V,
                                                            const uint32_t *__restrict__ nl, const int *__restrict__ cnt,
                                                            const float4 *__restrict__ G, const float4 *__restrict__ X0,
                                                            float4 *__restrict__ Pn, float4 *__restrict__ Vn, float4 *__restrict__ acc_out,
                                                            DevScalars *__restrict__ ds)
 {
+    const float dt = step_dt(step);
     if (blockIdx.x == 0 && threadIdx.x == 0) clock_advance(c.clock, dt);       // the step's last launch: its dt joins the handle's clock
     const uint32_t *nlb = nullptr;
     SPH_SWEEP_PROLOGUE_M(false)

@@ -8,6 +8,8 @@ from .solver_base import solver_base
 
 class iisph_solver(solver_base):
     _kind = "iisph"
+    _LIVE = solver_base._ADAPTIVE
+    _PARAM = solver_base._ADAPTIVE_PARAM
 
     def __init__(self, particle_system, config, verbose=True):
         super().__init__(particle_system, config)
@@ -24,6 +26,7 @@ class iisph_solver(solver_base):
         self.p_iter = DeviceField(self, nat.F_PRESS_ITER)
         self.f_press = DeviceField(self, nat.F_PRESS_FORCE)
         self.last_stats = None
+        self._adaptive_dt_attributes(config)
 
     def step(self, nsteps=1):
         self._forward_attributes()

@@ -8,6 +8,9 @@ from .solver_base import solver_base
 
 class pbf_solver(solver_base):
     _kind = "pbf"
+    _BAKED = ()                                         # (pbf_solver has none of solver_base's viscosity / tension attributes)
+    _LIVE = solver_base._ADAPTIVE
+    _PARAM = solver_base._ADAPTIVE_PARAM
 
     def __init__(self, particle_system, config, arith=None):
         super().__init__(particle_system, config, arith)
@@ -18,6 +21,8 @@ class pbf_solver(solver_base):
         self.pbf_lambda = DeviceField(self, nat.F_PBF_LAMBDA)
         self.delta_pos = DeviceField(self, nat.F_PBF_DELTA_POS)
         self.pos_predict = DeviceField(self, nat.F_POS_PREDICT)
+        self._adaptive_dt_attributes(config)
 
     def step(self, nsteps=1):
+        self._forward_attributes()
         self._sim.step_pbf(nsteps)

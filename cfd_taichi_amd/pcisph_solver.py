@@ -9,6 +9,8 @@ from .solver_base import solver_base
 
 class pcisph_solver(solver_base):
     _kind = "pcisph"
+    _LIVE = solver_base._ADAPTIVE
+    _PARAM = solver_base._ADAPTIVE_PARAM
 
     def __init__(self, particle_system, config, verbose=True):
         super().__init__(particle_system, config)
@@ -23,6 +25,7 @@ class pcisph_solver(solver_base):
         self.pos_predict = DeviceField(self, nat.F_POS_PREDICT)
         self.rho_predict = DeviceField(self, nat.F_RHO_ADV)
         self.last_stats = None
+        self._adaptive_dt_attributes(config)
         print("PCISPH parameter delta: {}, beta: {}".format(self.delta[None], self.beta))   # :38
 
     def step(self, nsteps=1):

@@ -123,6 +123,8 @@ def main(argv=None):
     np_rgba = ps.rgba.to_numpy()
     frame_time = 1.0 / scene_config.get("output_fps", 60)
     frame_cnt, ply_cnt, t = 0, 0, 0.0
+    adaptive = name != "dfsph" and solver.adaptive_dt       # this package's adaptive time step: the steps of a frame differ, t is the handle's clock
+    frame_dt = []
     while True:
         if frame_cnt > 100000:                                                   # :98
             break
@@ -139,7 +141,8 @@ def main(argv=None):
             if rs and ps.active_rigid[None] == 1:
                 rs.step()
         frame_cnt += 1
-        t += iter_cnt * solver.delta_time[None]
+        frame_dt.append(solver.delta_time[None])
+        t = solver.time[None] if adaptive else t + iter_cnt * frame_dt[-1]
         if ply_dir and (t / frame_time) > ply_cnt:                               # :189
             if len(np_rgba) != ps.particle_num:                                   # an emitter or a sink changed the count
                 np_rgba = ps.rgba.to_numpy()
@@ -153,7 +156,7 @@ def main(argv=None):
             break
     print("frames: %d, simulated time: %.6f s, PLY frames: %d" % (frame_cnt, t, ply_cnt))
     print("Simulation time: {}".format(time.time() - start_time))               # :211
-    LAST.update(ps=ps, solver=solver, rigid=rs, emitters=emitters, sinks=sinks)
+    LAST.update(ps=ps, solver=solver, rigid=rs, emitters=emitters, sinks=sinks, frame_dt=frame_dt)      # frame_dt: delta_time after every frame
     return frame_cnt, t, ply_cnt
 
 

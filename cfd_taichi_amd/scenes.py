@@ -177,6 +177,21 @@ SCENES.update({
 })
 
 
+def _with_adaptive_dt(cfg, max_dt, min_dt=None):
+    cfg["solver"]["adaptive_dt"] = True
+    cfg["solver"]["max_dt"] = max_dt
+    if min_dt is not None:
+        cfg["solver"]["min_dt"] = min_dt
+    return cfg
+
+
+SCENES.update({
+    # not the reference's: the 30 k dam under iisph with this package's adaptive time step (`solver.adaptive_dt`): the rule
+    # of dfsph_solver.py:104-119 picks every step between min_dt (1e-5) and 2e-3, eight times the fixed step of breaking_dam_30k_iisph
+    "dam_adaptive_iisph": lambda: _with_adaptive_dt(_scene("iisph", 2.5e-4, [5.0, 3.0, 1.5], [1.0, 2.8, 1.3]), 2e-3),
+})
+
+
 def get(name):
     return SCENES[name]()
 

@@ -12,6 +12,13 @@ class solver_base:
     # loops at every step (dfsph_solver.py:225, :396-404) and are forwarded whenever they changed.
     _BAKED = ("viscosity_c_s", "viscosity_alpha", "viscosity_epsilon", "tension_k")
     _LIVE = ()
+    # The adaptive time step of wcsph / pcisph / iisph / pbf (not the reference's, which adapts delta_time under dfsph only): `adaptive_dt`
+    # (default False), `max_dt` (default: the configured delta_time) and `min_dt` (1e-5) are this package's own attributes, read by the
+    # library at every step, so they are forwarded live: those four mirrors set _LIVE = _ADAPTIVE and _PARAM = _ADAPTIVE_PARAM, the library's
+    # names of the three (dfsph's attributes of the same names are the reference's own, ids 70-72, baked).
+    _ADAPTIVE = ("max_dt", "min_dt", "adaptive_dt")            # the bounds before the switch
+    _ADAPTIVE_PARAM = {"adaptive_dt": "step_adaptive_dt", "max_dt": "step_max_dt", "min_dt": "step_min_dt"}
+    _PARAM = {}                                                # attribute -> the library's name where the two differ
 
     def __init__(self, particle_system, config, arith=None):
         """arith: None keeps the ParticleSystem's arithmetic; "exact" / "relaxed" rebuilds its handle with that one (see ParticleSystem)."""
@@ -46,12 +53,20 @@ class solver_base:
         for name in (self._BAKED if first else ()) + self._LIVE:
             value = float(getattr(self, name))
             if sent.get(name) != value:
-                if first and value == self._sim.param(name):       # the library starts from the reference's values
+                param = self._PARAM.get(name, name)
+                if first and value == self._sim.param(param):      # the library starts from the reference's values (or the config's)
                     sent[name] = value
                     continue
-                self._sim.set_param(name, value)
+                self._sim.set_param(param, value)
                 sent[name] = value
         sent["_started"] = 1.0
+
+    def _adaptive_dt_attributes(self, config):
+        """`adaptive_dt`, `max_dt`, `min_dt` as the config's `solver` block says (all optional), else the library's defaults"""
+        solver_config = config.get("solver")
+        self.adaptive_dt = bool(solver_config.get("adaptive_dt", False))
+        self.max_dt = float(solver_config.get("max_dt", solver_config.get("delta_time")))
+        self.min_dt = float(solver_config.get("min_dt", 1e-5))
 
     def set_gravity(self, vec):
         """The acceleration vector's base g, wherever the reference writes `gravity * (0, -1, 0)` (between steps).  The scalar attribute

@@ -8,6 +8,8 @@ from .solver_base import solver_base
 
 class wcsph_solver(solver_base):
     _kind = "wcsph"
+    _LIVE = solver_base._ADAPTIVE
+    _PARAM = solver_base._ADAPTIVE_PARAM
 
     def __init__(self, particle_system, config, arith=None):
         super().__init__(particle_system, config, arith)
@@ -16,6 +18,7 @@ class wcsph_solver(solver_base):
         self.gamma = 7
         self.B = 70000
         self.pressure = DeviceField(self, nat.F_PRESSURE)
+        self._adaptive_dt_attributes(config)
 
     def step(self, nsteps=1):
         self._forward_attributes()

@@ -216,6 +216,16 @@ typedef struct SphRigid {
 #define SPH_P_VISCOSITY_ALPHA 74                   /* solver.viscosity_alpha    solver_base.py:25, :187 */
 #define SPH_P_VISCOSITY_EPSILON 75                 /* solver.viscosity_epsilon  solver_base.py:23, :188 */
 #define SPH_P_TENSION_K 76                         /* solver.tension_k          solver_base.py:26 (0.5), wcsph_solver.py:20 (0.2); :216 */
+/* The adaptive time step of wcsph, pcisph, iisph and pbf handles on one GPU -- this library's own: the reference adapts delta_time under dfsph only.
+ * Off by default.  While it is on, every solver step starts by applying dfsph's rule (dfsph_solver.py:104-119) on the device to the velocities the
+ * step starts with: dt = clamp(0.4 * particle_diameter / (max |v| + the body's term) * 0.2, min_dt, max_dt), written to delta_time, delta_time_2
+ * and ps.delta_time; every sweep of the step uses it, the clock advances by it, pcisph's delta follows it (SPH_S_PCISPH_DELTA), sph_rigid_step takes it
+ * like on a dfsph handle, SPH_S_DELTA_TIME / SPH_S_PS_DELTA_TIME / SphStepStats.dt report it, and a written SPH_S_DELTA_TIME lasts until the next
+ * step.  No host wait is added to a step.  Switching it off leaves delta_time (and pcisph's delta) where the last step left them.  May be written
+ * between steps.  SPH_E_STATE, handle unchanged: on a dfsph handle (which has 70-72) and on a slab handle. */
+#define SPH_P_STEP_ADAPTIVE_DT 77                  /* 0 / 1 */
+#define SPH_P_STEP_MAX_DT 78                       /* finite, > 0; default: the handle's delta_time as configured */
+#define SPH_P_STEP_MIN_DT 79                       /* finite, > 0; default: 1e-5 (dfsph's) */
 
 typedef struct SphHandle SphHandle;
 
@@ -343,7 +353,8 @@ int sph_compute_alpha(SphHandle *h);
 
 int sph_get_scalar(SphHandle *h, int which, double *out);
 /* `solver.delta_time[None] = value` (the reference's 0-d field is writable, main.py:111; dfsph re-derives it every step from the CFL
- * rule, dfsph_solver.py:112-119, so a written value lasts one step there): which = SPH_S_DELTA_TIME; with it a device state
+ * rule, dfsph_solver.py:112-119, so a written value lasts one step there, as on a handle of another solver while SPH_P_STEP_ADAPTIVE_DT is on):
+ * which = SPH_S_DELTA_TIME; with it a device state
  * (pos, vel, warm_start_k, delta_time) can be moved into another handle, or into the oracle, completely.
  * `solver.<attribute> = value`: which = SPH_P_* (above). */
 int sph_set_scalar(SphHandle *h, int which, double value);
