@@ -51,8 +51,14 @@ EXPORTS = [
     "sph_set_comm", "sph_rccl_unique_id", "sph_rccl_attach", "sph_rccl_selftest", "sph_get_stream", "sph_plan_slabs", "sph_replan_slabs", "sph_slab_set_overlap", "sph_slab_info", "sph_comm_stats", "sph_download_local", "sph_download_ids",
     "sph_create_rigid", "sph_rigid_step", "sph_rigid_set_active", "sph_rigid_init_data", "sph_slab_set_state",
     "sph_rigid_set_mode", "sph_rigid_set_motion", "sph_rigid_get_load", "sph_set_gravity", "sph_set_forcing",
-    "sph_add_particles", "sph_remove_in_box",
+    "sph_add_particles", "sph_remove_in_box", "sph_diagnostics", "sph_diag_record", "sph_diag_read",
 ]
+# the 32 slots of an SphDiagnostics row (include/sph_mi355x.h), in order: the members' names, _x / _y / _z for the vectors
+DIAG_SLOTS = ("time", "dt", "step", "n", "mass", "momentum_x", "momentum_y", "momentum_z",
+              "angular_momentum_x", "angular_momentum_y", "angular_momentum_z", "kinetic", "potential", "com_x", "com_y", "com_z",
+              "vmax", "vmax_id", "pos_min_x", "pos_min_y", "pos_min_z", "pos_max_x", "pos_max_y", "pos_max_z", "rho_min", "rho_max", "rho_mean",
+              "reserved_0", "reserved_1", "reserved_2", "reserved_3", "reserved_4")
+DIAG_DTYPE = np.dtype([(name, np.float64) for name in DIAG_SLOTS])
 
 
 class SphConfig(ctypes.Structure):
@@ -184,7 +190,7 @@ CORE_EXPORTS = [
 # library without them raises SphError(SPH_E_STATE)
 OPTIONAL_EXPORTS = ["sph_rigid_set_active", "sph_rigid_init_data", "sph_selftest_stage", "sph_selftest_walk", "sph_slab_set_state",
                     "sph_rigid_set_mode", "sph_rigid_set_motion", "sph_rigid_get_load", "sph_set_gravity", "sph_set_forcing",
-                    "sph_add_particles", "sph_remove_in_box"]
+                    "sph_add_particles", "sph_remove_in_box", "sph_diagnostics", "sph_diag_record", "sph_diag_read"]
 
 
 def _bind_core(lib):
@@ -236,6 +242,12 @@ def _bind_core(lib):
         lib.sph_add_particles.argtypes = [vp, vp, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int32)]
     if hasattr(lib, "sph_remove_in_box"):
         lib.sph_remove_in_box.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_int32)]
+    if hasattr(lib, "sph_diagnostics"):
+        lib.sph_diagnostics.argtypes = [vp, vp]
+    if hasattr(lib, "sph_diag_record"):
+        lib.sph_diag_record.argtypes = [vp, ci, ci]
+    if hasattr(lib, "sph_diag_read"):
+        lib.sph_diag_read.argtypes = [vp, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int64)]
     return lib
 
 
@@ -545,6 +557,30 @@ class Simulation:
         self._check(self._optional("sph_remove_in_box")(self._h, lo.ctypes.data, hi.ctypes.data, ctypes.byref(removed)))
         self._refresh_count()
         return int(removed.value)
+
+    def diagnostics(self):
+        """The run diagnostics of the fluid as it stands, between steps (sph_diagnostics): a dict keyed by the names of DIAG_SLOTS, f64.  The
+        rho_* entries are NaN unless compute_density ran since the positions last changed.  Changes nothing on the handle."""
+        row = np.zeros(1, dtype=DIAG_DTYPE)
+        self._check(self._optional("sph_diagnostics")(self._h, row.ctypes.data))
+        return {name: float(row[name][0]) for name in DIAG_SLOTS}
+
+    def record_diagnostics(self, every, rows=4096):
+        """Record one diagnostics row at the end of every `every`-th solver step into a ring of `rows` rows on the device (sph_diag_record);
+        every = 0 stops.  No host wait is added to a step; diagnostics_log() reads the rows when the caller likes."""
+        self._check(self._optional("sph_diag_record")(self._h, int(every), int(rows)))
+        if every:
+            self._diag_rows, self._diag_seen = int(rows), 0
+
+    def diagnostics_log(self):
+        """The recorded rows not read yet, oldest first, as a structured array of DIAG_DTYPE, and the number of rows that were overwritten in the
+        ring before any read could return them (since recording was switched on).  The read consumes the rows."""
+        cap = getattr(self, "_diag_rows", 0)
+        out = np.zeros(max(cap, 1), dtype=DIAG_DTYPE)
+        n, total = ctypes.c_size_t(0), ctypes.c_int64(0)
+        self._check(self._optional("sph_diag_read")(self._h, out.ctypes.data, cap, ctypes.byref(n), ctypes.byref(total)))
+        self._diag_seen = getattr(self, "_diag_seen", 0) + int(n.value)
+        return out[:int(n.value)].copy(), int(total.value) - self._diag_seen
 
     def close(self):
         if getattr(self, "_h", None):

@@ -306,8 +306,11 @@ int step_begin(SphHandle *h)
     return h->cfg.solver == SPH_SOLVER_PBF ? SPH_OK : stage_density(h);
 }
 // ... and behind its integrator: the positions moved, so neither the lists nor the densities describe them
+// While diagnostics are being recorded (sph_diag_record) the step's row follows here, for every solver and every step of a multi-step call
 int step_end(SphHandle *h)
 {
+    if (h->diag_every)
+        if (int rc = diag_step_end(h)) return rc;
     HIP_TRY(h, hipGetLastError());
     h->nl_valid = false;
     h->density_valid = false;

@@ -25,6 +25,7 @@
 #include "sph_rigid_kernels.h"
 #include "sph_pbf_kernels.h"
 #include "sph_relaxed_kernels.h"
+#include "sph_diag_kernels.h"
 #include "sph_selftest_walk.h"
 
 using namespace sph;
@@ -263,6 +264,13 @@ struct SphHandle {
     bool graphs_enabled = true;
     long long graph_launches = 0;
 
+    // run diagnostics: memory of its own, taken at the first use.  diag_part: the partial rows, diag_row: the on-demand row;
+    // recording (diag_every > 0): the ring, the device-resident counters, and how many recorded rows sph_diag_read has handed out or seen overwritten
+    double *diag_part = nullptr, *diag_row = nullptr, *diag_ring = nullptr;
+    DiagCtl *diag_ctl = nullptr;
+    int diag_every = 0, diag_rows = 0;
+    long long diag_consumed = 0;
+
     // profiling
     bool profiling = false;
     struct Ev { hipEvent_t a, b; int kid; };
@@ -327,6 +335,7 @@ inline dim3 grid_for(int n) { return dim3((unsigned)std::max(1, (n + kBlock - 1)
 
 #include "sph_host_scene.h"
 #include "sph_host_fields.h"
+#include "sph_host_diag.h"
 #include "sph_host_transport.h"
 #include "sph_host_rigid.h"
 #include "sph_host_dfsph.h"
@@ -559,6 +568,8 @@ static int fluid_count_changed(SphHandle *h, int n)
     }
     HIP_TRY(h, hipStreamSynchronize(s));
     drop_wcsph_graphs(h);                                            // (they carry the old count and grids as launch arguments)
+    // The run diagnostics (section 6i) need nothing here: their launches take the live count of the moment as an argument and keep no state about
+    // particles -- a recording goes on, its next row counts the new n
     return SPH_OK;
 }
 
@@ -662,6 +673,9 @@ void sph_destroy(SphHandle *h)
     for (auto &e : h->ev_pool) (void)hipEventDestroy(e);
     for (int k = 0; k < 8; ++k) if (h->wcsph_graph[k]) (void)hipGraphExecDestroy(h->wcsph_graph[k]);
     for (char *arena : h->arenas) (void)hipFree(arena);        // every dalloc'd array
+    if (h->diag_part) (void)hipFree(h->diag_part);
+    if (h->diag_ring) (void)hipFree(h->diag_ring);
+    if (h->diag_ctl) (void)hipFree(h->diag_ctl);
     if (h->rred_host) (void)hipHostFree(h->rred_host);
     if (h->own_dev_comm) { (void)hipFree(h->dsend[0]); (void)hipFree(h->dsend[1]); (void)hipFree(h->drecv[0]); (void)hipFree(h->drecv[1]); }
     if (h->own_red) (void)hipFree(h->red_dev);
@@ -1309,6 +1323,88 @@ int sph_set_forcing(SphHandle *h, const double amp[3], const double omega[3], co
         if (h->frc.amp[a] != 0.0) h->frc.on = 1;                      // all amplitudes zero: a = g, nothing is evaluated
     }
     return forcing_commit(h);
+}
+
+// ---- run diagnostics -----------------------------------------------------------------------------------------
+// On demand, between steps: the two launches into the scratch row and one blocking read.  Nothing on the handle changes -- no flag, no buffer
+// role, no array a step reads -- so the steps that follow are those of a handle that never called it
+int sph_diagnostics(SphHandle *h, SphDiagnostics *out)
+{
+    if (!h) return SPH_E_INVALID;
+    if (!out) return fail(h, SPH_E_INVALID, "sph_diagnostics: null argument");
+    if (int rc = diag_refused(h, "sph_diagnostics")) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (int rc = diag_scratch(h)) return rc;
+    const float *rho = nullptr;                       // the densities describe the current positions only after sph_compute_density
+    if (h->density_valid)
+        if (int rc = diag_rho(h, &rho)) return rc;
+    launch_diag(h, rho, nullptr, h->diag_row);
+    HIP_TRY(h, hipGetLastError());
+    static_assert(sizeof(SphDiagnostics) == sizeof(double) * kDiagSlots, "SphDiagnostics is 32 doubles");
+    HIP_TRY(h, hipMemcpyAsync(out, h->diag_row, sizeof(SphDiagnostics), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return SPH_OK;
+}
+
+// every >= 1: (re)start recording into a fresh ring of `rows` rows, the counters at zero; every == 0: stop (rows is ignored; what the ring holds
+// stays readable).  Validated and allocated before anything is touched.  The captured wcsph step pairs hold or lack the two nodes: dropped
+int sph_diag_record(SphHandle *h, int every, int rows)
+{
+    if (!h) return SPH_E_INVALID;
+    if (int rc = diag_refused(h, "sph_diag_record")) return rc;
+    if (every < 0) return fail(h, SPH_E_INVALID, "sph_diag_record: every >= 0 expected, got %d", every);
+    if (every > 0 && (rows < 1 || rows > kDiagMaxRows)) return fail(h, SPH_E_INVALID, "sph_diag_record: 1 <= rows <= %d expected, got %d", kDiagMaxRows, rows);
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (every > 0) {
+        if (int rc = diag_scratch(h)) return rc;
+        double *ring = nullptr;
+        HIP_TRY(h, hipMalloc((void **)&ring, sizeof(double) * kDiagSlots * (size_t)rows));
+        if (!h->diag_ctl && hipMalloc((void **)&h->diag_ctl, sizeof(DiagCtl)) != hipSuccess) {
+            (void)hipFree(ring); h->diag_ctl = nullptr;
+            return fail(h, SPH_E_HIP, "sph_diag_record: out of device memory");
+        }
+        const DiagCtl ctl{0, 0, h->simulate_cnt, every, rows, 0};
+        hipError_t e = hipMemcpyAsync(h->diag_ctl, &ctl, sizeof(ctl), hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) { (void)hipFree(ring); return fail(h, SPH_E_HIP, "sph_diag_record: %s", hipGetErrorString(e)); }
+        if (h->diag_ring) (void)hipFree(h->diag_ring);
+        h->diag_ring = ring;
+        h->diag_rows = rows;
+        h->diag_consumed = 0;
+    }
+    h->diag_every = every;
+    drop_wcsph_graphs(h);
+    return SPH_OK;
+}
+
+// the rows still in the ring, oldest first, at most max_rows of them; *total = rows recorded since recording was switched on.  What is handed out
+// (and what was overwritten before it could be) is consumed: a second read returns the rows recorded since
+int sph_diag_read(SphHandle *h, SphDiagnostics *out, size_t max_rows, size_t *n_rows, int64_t *total)
+{
+    if (!h) return SPH_E_INVALID;
+    if (!n_rows || (!out && max_rows > 0)) return fail(h, SPH_E_INVALID, "sph_diag_read: null argument");
+    if (int rc = diag_refused(h, "sph_diag_read")) return rc;
+    *n_rows = 0;
+    if (total) *total = 0;
+    if (!h->diag_ring) return SPH_OK;                  // never recorded
+    HIP_TRY(h, hipSetDevice(h->device));
+    DiagCtl ctl;
+    HIP_TRY(h, hipMemcpyAsync(&ctl, h->diag_ctl, sizeof(ctl), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    const long long rows = h->diag_rows, first = std::max(h->diag_consumed, ctl.count - rows);
+    const long long k = std::min<long long>(ctl.count - first, (long long)std::min<size_t>(max_rows, (size_t)rows));
+    for (long long done = 0; done < k;) {              // at most two runs of slots
+        const long long slot = (first + done) % rows, run = std::min(k - done, rows - slot);
+        HIP_TRY(h, hipMemcpyAsync(out + done, h->diag_ring + slot * kDiagSlots, sizeof(SphDiagnostics) * (size_t)run, hipMemcpyDeviceToHost, h->stream));
+        done += run;
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->diag_consumed = first + k;
+    *n_rows = (size_t)k;
+    if (total) *total = ctl.count;
+    return SPH_OK;
 }
 
 const char *sph_overrides(SphHandle *h) { return h ? h->overrides.c_str() : ""; }

@@ -10,7 +10,10 @@ xyz + the constant RGBA of ParticleSystem.py:152) and, when a rigid body exists,
 --release-rigid-at FRAME runs the release sequence the reference keeps commented out at main.py:100-106 when frame_cnt reaches FRAME: a body
 created with `solid.active: false` drops into the fluid as it is then.
 `scene.emitters` / `scene.sinks` (cfd_taichi_amd/emitter.py; the handle needs a `fluid.capacity`): after every solver step the sinks are applied,
-then the emitters; the PLY frames hold the particles of the moment.  Single GPU, no rigid body."""
+then the emitters; the PLY frames hold the particles of the moment.  Single GPU, no rigid body.
+--diag-csv PATH [--diag-every N]: the fluid's run diagnostics (energy, momentum, centre of mass, extent, ...; _native.DIAG_SLOTS), summed on the device at
+the end of every N-th solver step and drained once per frame; one CSV line per recorded step under a header of the slot names, written at the end of
+the run.  Single GPU."""
 import argparse
 import importlib
 import os
@@ -33,6 +36,25 @@ def write_ply_ascii(path, pos, rgba):
             f.write("property float %s\n" % name)
         f.write("end_header\n")
         np.savetxt(f, np.hstack([pos, rgba]), fmt="%.6f")
+
+
+def write_diag_csv(path, chunks):
+    """One line per recorded step under a header of the slot names; `chunks`: the structured arrays of Simulation.diagnostics_log(), in order.
+    %.17g: every f64 comes back bit for bit."""
+    from ._native import DIAG_SLOTS
+    with open(path, "w") as f:
+        f.write(",".join(DIAG_SLOTS) + "\n")
+        for rows in chunks:
+            for row in rows:
+                f.write(",".join("%.17g" % row[name] for name in DIAG_SLOTS) + "\n")
+
+
+def drain_diag(sim, chunks, dropped):
+    """the rows recorded since the last drain onto `chunks`; returns the running count of rows lost to the ring"""
+    rows, lost = sim.diagnostics_log()
+    if len(rows):
+        chunks.append(rows)
+    return max(dropped, lost)
 
 
 def main_sharded(args, config):
@@ -98,12 +120,18 @@ def main(argv=None):
                     help="exact (default): the reference's f32 operations in its order; relaxed: the tolerance-grade sweeps (SphConfig.arith)")
     ap.add_argument("--release-rigid-at", type=int, default=None, metavar="FRAME",
                     help="activate the rigid body when frame_cnt reaches FRAME (main.py:100-106: let the fluid settle first)")
+    ap.add_argument("--diag-csv", default=None, metavar="PATH", help="record the fluid's run diagnostics on the device and write them as CSV at the end of the run")
+    ap.add_argument("--diag-every", type=int, default=1, metavar="N", help="with --diag-csv: one row every N solver steps (default 1)")
     args = ap.parse_args(argv)
+    if args.diag_csv and args.diag_every < 1:
+        raise SystemExit("--diag-every must be >= 1")
 
     config = utils.read_config(args.config)
     if args.solver:
         config["solver"]["name"] = args.solver
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        if args.diag_csv:
+            raise SystemExit("--diag-csv is not sharded: run this config on one GPU")
         return main_sharded(args, config)
     scene_config, solver_config = config["scene"], config["solver"]
     print("Simulation Start!")
@@ -125,6 +153,9 @@ def main(argv=None):
     frame_cnt, ply_cnt, t = 0, 0, 0.0
     adaptive = name != "dfsph" and solver.adaptive_dt       # this package's adaptive time step: the steps of a frame differ, t is the handle's clock
     frame_dt = []
+    diag_chunks, diag_dropped = [], 0
+    if args.diag_csv:
+        ps._sim.record_diagnostics(args.diag_every)
     while True:
         if frame_cnt > 100000:                                                   # :98
             break
@@ -141,6 +172,8 @@ def main(argv=None):
             if rs and ps.active_rigid[None] == 1:
                 rs.step()
         frame_cnt += 1
+        if args.diag_csv:
+            diag_dropped = drain_diag(ps._sim, diag_chunks, diag_dropped)
         frame_dt.append(solver.delta_time[None])
         t = solver.time[None] if adaptive else t + iter_cnt * frame_dt[-1]
         if ply_dir and (t / frame_time) > ply_cnt:                               # :189
@@ -154,6 +187,10 @@ def main(argv=None):
             ply_cnt += 1
         if (args.steps and frame_cnt >= args.steps) or t > args.until:           # :205
             break
+    if args.diag_csv:
+        ps._sim.record_diagnostics(0)
+        write_diag_csv(args.diag_csv, diag_chunks)
+        print("diagnostics: %d rows in %s%s" % (sum(len(c) for c in diag_chunks), args.diag_csv, ", %d lost to the ring" % diag_dropped if diag_dropped else ""))
     print("frames: %d, simulated time: %.6f s, PLY frames: %d" % (frame_cnt, t, ply_cnt))
     print("Simulation time: {}".format(time.time() - start_time))               # :211
     LAST.update(ps=ps, solver=solver, rigid=rs, emitters=emitters, sinks=sinks, frame_dt=frame_dt)      # frame_dt: delta_time after every frame

@@ -308,6 +308,48 @@ int sph_set_forcing(SphHandle *h, const double amp[3], const double omega[3], co
  * removed: nothing changes, not even what is valid.  SPH_E_INVALID: a box that would remove every particle (an empty handle is not supported). */
 int sph_add_particles(SphHandle *h, const float *pos, const float *vel, size_t n, int32_t *first_id);
 int sph_remove_in_box(SphHandle *h, const float lo[3], const float hi[3], int32_t *removed);
+/* Run diagnostics of the FLUID of a single-GPU handle, summed on the device: every solver, exact or relaxed, with or without
+ * a body (the body's own momentum and energy are not in the row).  One row is 32 doubles.  m = SPH_S_PARTICLE_M, x / v = SPH_F_POS / SPH_F_VEL.
+ * Arithmetic: every f32 operand is widened to f64 first, products and the three-term sums inside a term are f64, the terms are summed in f64 in a
+ * fixed order (no atomics; the same state in the same device order gives the same bits, another order after a re-sort may differ in the last
+ * bits), and the scalings by m, 1/2, 1/n are applied once, at the end.  n, step, vmax, vmax_id, pos_min / pos_max, rho_min / rho_max are exact. */
+typedef struct SphDiagnostics {
+    double time;                  /* SPH_S_TIME */
+    double dt;                    /* the delta_time the last step used (SPH_S_DELTA_TIME) */
+    double step;                  /* SPH_S_SIMULATE_CNT */
+    double n;                     /* the live particle count */
+    double mass;                  /* n m */
+    double momentum[3];           /* m sum v */
+    double angular_momentum[3];   /* m sum x cross v, about the origin */
+    double kinetic;               /* 1/2 m sum |v|^2 */
+    double potential;             /* -m sum a . x, a = the handle's acceleration vector of the moment (SPH_S_ACCEL) */
+    double com[3];                /* sum x / n */
+    double vmax;                  /* the largest speed, the f32 value sqrtf((vx vx + vy vy) + vz vz) the adaptive time step forms */
+    double vmax_id;               /* original id of the particle that has it (the lowest id among ties) */
+    double pos_min[3];            /* the fluid's extent: per-axis minimum ... */
+    double pos_max[3];            /* ... and maximum position (f32 values) */
+    double rho_min;               /* f32 values ... */
+    double rho_max;
+    double rho_mean;              /* sum rho / n */
+    double reserved[5];           /* 0 */
+} SphDiagnostics;
+/* On demand, between steps: synchronises, two launches, one blocking read.  Changes nothing on the handle: the steps that follow are bit for bit
+ * those of a handle that never called it.  rho_min / rho_max / rho_mean are NaN unless the densities describe the current positions (after
+ * sph_compute_density).  SPH_E_INVALID: out == NULL; SPH_E_STATE: a slab handle (the sums would need an all-reduce). */
+int sph_diagnostics(SphHandle *h, SphDiagnostics *out);
+/* Recorded: every >= 1 (re)starts recording into a ring of `rows` rows in device memory, every == 0 stops it (rows is ignored; the ring stays
+ * readable).  While it is on, every solver step -- of all five sph_step_* calls, the steps inside a multi-step call and the replayed wcsph step
+ * pairs included -- ends with the two launches; step k since the call is recorded when k is a multiple of `every` (decided on the device: no host
+ * wait is added, a step that is not due costs two empty launches) into ring slot (rows recorded so far) % rows.  The row describes the state the
+ * step leaves: the new positions and velocities, the advanced clock, the dt it used, and the densities its density sweep computed (pbf: its
+ * lambda sweep).  Recording changes no trajectory.  sph_add_particles / sph_remove_in_box need nothing: the next row counts the new n.
+ * SPH_E_INVALID (handle unchanged): every < 0; every >= 1 with rows < 1 or rows > 2^20.  SPH_E_STATE: a slab handle. */
+int sph_diag_record(SphHandle *h, int every, int rows);
+/* Synchronises and copies out the rows still in the ring, oldest first, at most max_rows; *n_rows = their number, *total (may be NULL) = rows
+ * recorded since recording was switched on, so the caller sees how many were overwritten before they were read.  The read consumes the rows: the
+ * next one returns what was recorded since.  A handle that never recorded returns no rows.  SPH_E_INVALID: n_rows == NULL, out == NULL with
+ * max_rows > 0; SPH_E_STATE: a slab handle. */
+int sph_diag_read(SphHandle *h, SphDiagnostics *out, size_t max_rows, size_t *n_rows, int64_t *total);
 void sph_destroy(SphHandle *h);
 int sph_get_sizes(SphHandle *h, SphSizes *out);
 const char *sph_last_error(SphHandle *h);
