@@ -51,7 +51,7 @@ EXPORTS = [
     "sph_set_comm", "sph_rccl_unique_id", "sph_rccl_attach", "sph_rccl_selftest", "sph_get_stream", "sph_plan_slabs", "sph_replan_slabs", "sph_slab_set_overlap", "sph_slab_info", "sph_comm_stats", "sph_download_local", "sph_download_ids",
     "sph_create_rigid", "sph_rigid_step", "sph_rigid_set_active", "sph_rigid_init_data", "sph_slab_set_state",
     "sph_rigid_set_mode", "sph_rigid_set_motion", "sph_rigid_get_load", "sph_set_gravity", "sph_set_forcing",
-    "sph_add_particles", "sph_remove_in_box", "sph_diagnostics", "sph_diag_record", "sph_diag_read",
+    "sph_add_particles", "sph_remove_in_box", "sph_diagnostics", "sph_diag_record", "sph_diag_read", "sph_derived",
 ]
 # the 32 slots of an SphDiagnostics row (include/sph_mi355x.h), in order: the members' names, _x / _y / _z for the vectors
 DIAG_SLOTS = ("time", "dt", "step", "n", "mass", "momentum_x", "momentum_y", "momentum_z",
@@ -59,6 +59,10 @@ DIAG_SLOTS = ("time", "dt", "step", "n", "mass", "momentum_x", "momentum_y", "mo
               "vmax", "vmax_id", "pos_min_x", "pos_min_y", "pos_min_z", "pos_max_x", "pos_max_y", "pos_max_z", "rho_min", "rho_max", "rho_mean",
               "reserved_0", "reserved_1", "reserved_2", "reserved_3", "reserved_4")
 DIAG_DTYPE = np.dtype([(name, np.float64) for name in DIAG_SLOTS])
+# the derived per-particle fields (include/sph_mi355x.h SPH_D_*): name -> id, and id -> the shape of one particle's entry
+D_VELGRAD, D_VORTICITY, D_DIVERGENCE, D_NORMAL, D_COVER = 0, 1, 2, 3, 4
+DERIVED = {"velgrad": D_VELGRAD, "vorticity": D_VORTICITY, "divergence": D_DIVERGENCE, "normal": D_NORMAL, "cover": D_COVER}
+DERIVED_SHAPE = {D_VELGRAD: (3, 3), D_VORTICITY: (3,), D_DIVERGENCE: (), D_NORMAL: (3,), D_COVER: ()}
 
 
 class SphConfig(ctypes.Structure):
@@ -190,7 +194,7 @@ CORE_EXPORTS = [
 # library without them raises SphError(SPH_E_STATE)
 OPTIONAL_EXPORTS = ["sph_rigid_set_active", "sph_rigid_init_data", "sph_selftest_stage", "sph_selftest_walk", "sph_slab_set_state",
                     "sph_rigid_set_mode", "sph_rigid_set_motion", "sph_rigid_get_load", "sph_set_gravity", "sph_set_forcing",
-                    "sph_add_particles", "sph_remove_in_box", "sph_diagnostics", "sph_diag_record", "sph_diag_read"]
+                    "sph_add_particles", "sph_remove_in_box", "sph_diagnostics", "sph_diag_record", "sph_diag_read", "sph_derived"]
 
 
 def _bind_core(lib):
@@ -248,6 +252,8 @@ def _bind_core(lib):
         lib.sph_diag_record.argtypes = [vp, ci, ci]
     if hasattr(lib, "sph_diag_read"):
         lib.sph_diag_read.argtypes = [vp, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int64)]
+    if hasattr(lib, "sph_derived"):
+        lib.sph_derived.argtypes = [vp, ci, vp, ctypes.c_size_t]
     return lib
 
 
@@ -581,6 +587,16 @@ class Simulation:
         self._check(self._optional("sph_diag_read")(self._h, out.ctypes.data, cap, ctypes.byref(n), ctypes.byref(total)))
         self._diag_seen = getattr(self, "_diag_seen", 0) + int(n.value)
         return out[:int(n.value)].copy(), int(total.value) - self._diag_seen
+
+    def derived(self, which):
+        """A derived per-particle field of the fluid as it stands (sph_derived): `which` is a name of DERIVED or an SPH_D_* id.  Returns f32 in
+        original particle order: (n, 3, 3) velgrad (row a, column b: d v_a / d x_b), (n, 3) vorticity / normal, (n,) divergence / cover.  Runs
+        compute_density first (its caveat applies); changes no trajectory.  All five come from one sweep, kept until the state changes."""
+        wid = DERIVED[which] if isinstance(which, str) else int(which)
+        shape = DERIVED_SHAPE.get(wid, ())
+        out = np.empty((self._n_fluid,) + shape, dtype=np.float32)
+        self._check(self._optional("sph_derived")(self._h, wid, out.ctypes.data, out.size))
+        return out
 
     def close(self):
         if getattr(self, "_h", None):

@@ -149,6 +149,7 @@ int stage_sort_and_lists(SphHandle *h)
     HIP_TRY(h, hipGetLastError());
     h->nl_valid = true;
     h->density_valid = false;
+    h->derived_valid = false;
     h->lists_predate_flag = false;
     return SPH_OK;
 }
@@ -314,6 +315,7 @@ int step_end(SphHandle *h)
     HIP_TRY(h, hipGetLastError());
     h->nl_valid = false;
     h->density_valid = false;
+    h->derived_valid = false;
     return SPH_OK;
 }
 

@@ -946,7 +946,7 @@ int write_delta_time(SphHandle *h, double value)
 // or a new array that carries stamps or per-tile flags across steps, is added HERE and nowhere else.  Enqueues on the handle's stream; no wait
 int forget_step_history(SphHandle *h)
 {
-    h->nl_valid = false; h->density_valid = false; h->lists_predate_flag = false;
+    h->nl_valid = false; h->density_valid = false; h->derived_valid = false; h->lists_predate_flag = false;
     h->flow_stamp = h->flow_last = 0; h->flow_d6 = kNoFlow;
     h->dens_sparse = false; h->dens_first = true; h->pending_div = kNoRide;
     h->pbf_fields = false;                    // pbf_lambda / delta_pos: "before the first step" again

@@ -26,6 +26,7 @@
 #include "sph_pbf_kernels.h"
 #include "sph_relaxed_kernels.h"
 #include "sph_diag_kernels.h"
+#include "sph_derived_kernels.h"
 #include "sph_selftest_walk.h"
 
 using namespace sph;
@@ -36,14 +37,14 @@ enum KernelId {
     K_HASH = 0, K_SCAN, K_SCATTER, K_ORDER_GATHER, K_BUILD_NL, K_W_DENSITY, K_W_FORCE, K_D_DENSITY_ALPHA,
     K_D_WARM, K_D_DIV_RESIDUAL, K_D_DIV_CORRECT, K_D_EXT, K_D_DENS_RESIDUAL, K_D_DENS_CORRECT, K_D_INTEGRATE,
     K_FINALIZE, K_TRANSFER, K_SLAB, K_RIGID, K_P_EXT, K_P_PREDICT_RHO, K_P_PRESS, K_P_INTEGRATE, K_I_ADVECT, K_I_RHO_ADV, K_I_DIJ,
-    K_I_UPDATE_P, K_I_INTEGRATE, K_B_LAMBDA, K_B_DELTA, K_B_XSPH, K_ACCEL, K_COUNT
+    K_I_UPDATE_P, K_I_INTEGRATE, K_B_LAMBDA, K_B_DELTA, K_B_XSPH, K_ACCEL, K_DERIVED, K_COUNT
 };
 const char *kKernelNames[K_COUNT] = {
     "hash_count", "scan", "scatter", "order_gather", "build_nl", "wcsph_density", "wcsph_force", "dfsph_density_alpha",
     "dfsph_warm_start", "dfsph_div_residual", "dfsph_div_correct", "dfsph_ext_force", "dfsph_dens_residual",
     "dfsph_dens_correct", "dfsph_integrate", "finalize", "transfer", "slab_exchange", "rigid",
     "pcisph_ext_force", "pcisph_predict_rho", "pcisph_press_force", "pcisph_integrate", "iisph_advect", "iisph_rho_adv", "iisph_d_ij",
-    "iisph_update_p", "iisph_integrate", "pbf_lambda", "pbf_delta_pos", "pbf_xsph", "accel_eval"};
+    "iisph_update_p", "iisph_integrate", "pbf_lambda", "pbf_delta_pos", "pbf_xsph", "accel_eval", "derived"};
 
 thread_local std::string g_create_error;
 thread_local bool g_creating_with_rigid = false;     // sph_create_rigid builds the fluid handle first: no Verlet lists there (the body moves through the grid)
@@ -271,6 +272,13 @@ struct SphHandle {
     int diag_every = 0, diag_rows = 0;
     long long diag_consumed = 0;
 
+    // derived per-particle fields: memory of its own, taken at the first sph_derived.  drv_vr: (vel, rho) packed; drv_out: the
+    // 17 planes of the result in device order; drv_api: one quantity in API order.  derived_valid: drv_out describes the state the handle holds --
+    // taken down wherever density_valid is
+    float4 *drv_vr = nullptr;
+    float *drv_out = nullptr, *drv_api = nullptr;
+    bool derived_valid = false;
+
     // profiling
     bool profiling = false;
     struct Ev { hipEvent_t a, b; int kid; };
@@ -340,6 +348,7 @@ inline dim3 grid_for(int n) { return dim3((unsigned)std::max(1, (n + kBlock - 1)
 #include "sph_host_rigid.h"
 #include "sph_host_dfsph.h"
 #include "sph_host_pressure.h"
+#include "sph_host_derived.h"
 
 }  // namespace
 
@@ -454,6 +463,7 @@ int sph_rigid_set_active(SphHandle *h, int active)
     // density loop's working-tiles-first order (dens_order) is a launch order only; it starts afresh as on a new handle
     h->nl_valid = false;
     h->density_valid = false;
+    h->derived_valid = false;
     h->lists_predate_flag = true;
     h->dens_sparse = false;
     return SPH_OK;
@@ -479,6 +489,7 @@ int sph_rigid_init_data(SphHandle *h)
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->nl_valid = false;
     h->density_valid = false;
+    h->derived_valid = false;
     return SPH_OK;
 }
 
@@ -676,6 +687,7 @@ void sph_destroy(SphHandle *h)
     if (h->diag_part) (void)hipFree(h->diag_part);
     if (h->diag_ring) (void)hipFree(h->diag_ring);
     if (h->diag_ctl) (void)hipFree(h->diag_ctl);
+    if (h->drv_vr) (void)hipFree(h->drv_vr);
     if (h->rred_host) (void)hipHostFree(h->rred_host);
     if (h->own_dev_comm) { (void)hipFree(h->dsend[0]); (void)hipFree(h->dsend[1]); (void)hipFree(h->drecv[0]); (void)hipFree(h->drecv[1]); }
     if (h->own_red) (void)hipFree(h->red_dev);
@@ -734,6 +746,7 @@ int sph_upload(SphHandle *h, int species, int field, const float *host, size_t n
     HIP_TRY(h, hipStreamSynchronize(s));
     h->nl_valid = false;
     h->density_valid = false;
+    h->derived_valid = false;
     return SPH_OK;
 }
 
@@ -1093,7 +1106,7 @@ static int wcsph_replay_pairs(SphHandle *h, int nsteps, int *k)
         HIP_TRY(h, hipGraphLaunch(h->wcsph_graph[key], h->stream));
         h->graph_launches += 1;
         h->simulate_cnt += 2;
-        h->nl_valid = false; h->density_valid = false;
+        h->nl_valid = false; h->density_valid = false; h->derived_valid = false;
         *k += 2;
     }
     return SPH_OK;
@@ -1325,6 +1338,13 @@ int sph_set_forcing(SphHandle *h, const double amp[3], const double omega[3], co
     return forcing_commit(h);
 }
 
+// ---- derived per-particle fields ------------------------------------------------------------------------------
+int sph_derived(SphHandle *h, int which, float *host, size_t n_floats)
+{
+    if (!h) return SPH_E_INVALID;
+    return derived_fetch(h, which, host, n_floats);
+}
+
 // ---- run diagnostics -----------------------------------------------------------------------------------------
 // On demand, between steps: the two launches into the scratch row and one blocking read.  Nothing on the handle changes -- no flag, no buffer
 // role, no array a step reads -- so the steps that follow are those of a handle that never called it
@@ -1489,7 +1509,7 @@ int sph_tune_time(SphHandle *h, int which, unsigned lds_bytes, int reps, double 
     (void)hipEventDestroy(a); (void)hipEventDestroy(b);
     h->sweep_lds = saved;
     h->tune_all = false;
-    if (which == 3) h->density_valid = false;
+    if (which == 3) { h->density_valid = false; h->derived_valid = false; }
     *avg_us = (double)ms * 1000.0 / reps;
     return SPH_OK;
 }

@@ -13,7 +13,9 @@ created with `solid.active: false` drops into the fluid as it is then.
 then the emitters; the PLY frames hold the particles of the moment.  Single GPU, no rigid body.
 --diag-csv PATH [--diag-every N]: the fluid's run diagnostics (energy, momentum, centre of mass, extent, ...; _native.DIAG_SLOTS), summed on the device at
 the end of every N-th solver step and drained once per frame; one CSV line per recorded step under a header of the slot names, written at the end of
-the run.  Single GPU."""
+the run.  Single GPU.
+--ply-fields vorticity,divergence,normal,cover: derived per-particle fields (Simulation.derived) as further `property float` columns of every PLY
+frame, after alpha: vort_x vort_y vort_z div normal_x normal_y normal_z cover -- only the named ones, always in that order.  Single GPU."""
 import argparse
 import importlib
 import os
@@ -27,15 +29,37 @@ from . import ParticleSystem, emitter, rigid_solver, utils
 LAST = {}      # the objects of the last single-GPU main() call (ps, solver, rigid), for a caller that embeds the runner and reads the end state
 
 
-def write_ply_ascii(path, pos, rgba):
-    """ASCII PLY in the layout of ti.tools.PLYWriter.export_frame_ascii: float x y z red green blue alpha."""
+# --ply-fields: the derived fields a PLY frame can carry, in column order, with their column names
+PLY_FIELDS = (("vorticity", ("vort_x", "vort_y", "vort_z")), ("divergence", ("div",)), ("normal", ("normal_x", "normal_y", "normal_z")), ("cover", ("cover",)))
+
+
+def parse_ply_fields(text):
+    """the names of --ply-fields in column order (whatever order they were given in); an unknown name ends the run"""
+    asked = [w.strip() for w in (text or "").split(",") if w.strip()]
+    known = [name for name, _ in PLY_FIELDS]
+    for w in asked:
+        if w not in known:
+            raise SystemExit("--ply-fields: unknown field '%s' (choose from %s)" % (w, ", ".join(known)))
+    return [name for name in known if name in asked]
+
+
+def ply_extra(sim, fields):
+    """[(column names, (n, k) values)] of the named derived fields of the state `sim` holds"""
+    cols = dict(PLY_FIELDS)
+    return [(cols[name], sim.derived(name).reshape(sim.n_fluid, -1)) for name in fields]
+
+
+def write_ply_ascii(path, pos, rgba, extra=()):
+    """ASCII PLY in the layout of ti.tools.PLYWriter.export_frame_ascii: float x y z red green blue alpha; extra: [(column names, values)] appended
+    as further float properties."""
     n = len(pos)
+    names = ["x", "y", "z", "red", "green", "blue", "alpha"] + [c for cols, _ in extra for c in cols]
     with open(path, "w") as f:
         f.write("ply\nformat ascii 1.0\ncomment created by cfd_taichi_amd\nelement vertex %d\n" % n)
-        for name in ("x", "y", "z", "red", "green", "blue", "alpha"):
+        for name in names:
             f.write("property float %s\n" % name)
         f.write("end_header\n")
-        np.savetxt(f, np.hstack([pos, rgba]), fmt="%.6f")
+        np.savetxt(f, np.hstack([pos, rgba] + [np.asarray(v, dtype=np.float32).reshape(n, -1) for _, v in extra]), fmt="%.6f")
 
 
 def write_diag_csv(path, chunks):
@@ -78,6 +102,11 @@ def main_sharded(args, config):
         dist.init_process_group("gloo")
     transport = args.transport or ("native" if own_gpu else "torch")
     sim = SlabSimulation(config, rank, world, device=device, transport=transport, rebalance_every=50, arith=nat.arith_id(args.arith))
+    if args.ply_fields:              # derived fields are not sharded: the library says why
+        try:
+            sim.sim.derived(args.ply_fields[0])
+        except nat.SphError as e:
+            raise SystemExit(str(e))
     scene_config, solver_config = config["scene"], config["solver"]
     iter_cnt = solver_config.get("iter_cnt")
     ply_dir = args.ply_dir or ("./output" if scene_config.get("is_output_ply", False) else None)
@@ -122,7 +151,9 @@ def main(argv=None):
                     help="activate the rigid body when frame_cnt reaches FRAME (main.py:100-106: let the fluid settle first)")
     ap.add_argument("--diag-csv", default=None, metavar="PATH", help="record the fluid's run diagnostics on the device and write them as CSV at the end of the run")
     ap.add_argument("--diag-every", type=int, default=1, metavar="N", help="with --diag-csv: one row every N solver steps (default 1)")
+    ap.add_argument("--ply-fields", default=None, metavar="NAMES", help="derived fields as extra PLY columns: a comma-separated choice of vorticity, divergence, normal, cover")
     args = ap.parse_args(argv)
+    args.ply_fields = parse_ply_fields(args.ply_fields)
     if args.diag_csv and args.diag_every < 1:
         raise SystemExit("--diag-every must be >= 1")
 
@@ -179,7 +210,7 @@ def main(argv=None):
         if ply_dir and (t / frame_time) > ply_cnt:                               # :189
             if len(np_rgba) != ps.particle_num:                                   # an emitter or a sink changed the count
                 np_rgba = ps.rgba.to_numpy()
-            write_ply_ascii(os.path.join(ply_dir, "output_%06d.ply" % ply_cnt), ps.fluid_particles.pos.to_numpy(), np_rgba)
+            write_ply_ascii(os.path.join(ply_dir, "output_%06d.ply" % ply_cnt), ps.fluid_particles.pos.to_numpy(), np_rgba, ply_extra(ps._sim, args.ply_fields))
             if ps.exist_rigid[None] == 1:                                        # :196-200
                 ps.update_mesh_vextics()
                 with open(os.path.join(ply_dir, "obj_%06d.obj" % ply_cnt), "w") as f:

@@ -350,6 +350,34 @@ int sph_diag_record(SphHandle *h, int every, int rows);
  * next one returns what was recorded since.  A handle that never recorded returns no rows.  SPH_E_INVALID: n_rows == NULL, out == NULL with
  * max_rows > 0; SPH_E_STATE: a slab handle. */
 int sph_diag_read(SphHandle *h, SphDiagnostics *out, size_t max_rows, size_t *n_rows, int64_t *total);
+
+/* Derived per-particle fields of the fluid: the plain SPH estimates, without kernel-gradient correction, at the positions
+ * and velocities the handle holds now, any of the five solvers, summed in f32 in the order of each particle's neighbour list with the exact kernel
+ * functions (on relaxed handles too).  With vol_j = m / rho_j (rho: SPH_F_RHO as sph_compute_density leaves it), W and grad W over fluid
+ * neighbours j, the samples r of a COUPLED body and wall samples b, no self term:
+ *   velgrad[a][b] = sum_j vol_j (v_j,a - v_i,a) dW/dx_b        estimates d v_a / d x_b; 9 floats per particle, row a, column b
+ *   vorticity     = (G_zy - G_yz, G_xz - G_zx, G_yx - G_xy)     3
+ *   divergence    = (G_xx + G_yy) + G_zz                        1
+ *   normal        = -h (sum_j vol_j grad W + sum_r V_r grad W + sum_b V_b grad W)     3; dimensionless, points out of the fluid: about 0 inside,
+ *                                                               O(1) at a free surface
+ *   cover         = sum_j vol_j W + sum_r V_r W + sum_b V_b W   1; about 1 inside the fluid, falls towards a free surface
+ * A particle without neighbours gets zeros.  A free-surface flag is the caller's threshold on |normal| and cover.  A body's samples do not enter
+ * velgrad.  grad W is the solvers' own (solver_base.py:90-103, with the factor 6 the reference carries), so velgrad, vorticity, divergence and
+ * normal are six times the textbook estimates; cover is not affected. */
+#define SPH_D_VELGRAD 0
+#define SPH_D_VORTICITY 1
+#define SPH_D_DIVERGENCE 2
+#define SPH_D_NORMAL 3
+#define SPH_D_COVER 4
+/* `host` receives the quantity in API (original particle) order; n_floats must be its width times the live particle count.  The call runs
+ * sph_compute_density first (which builds the lists if positions changed), so sph_compute_density's caveat holds here too: the re-sort leaves the
+ * OTHER per-particle results of the last step (alpha, pressure, acc, press_iter, ...) not downloadable until they are computed again.  Like the
+ * stage calls it changes no trajectory: called between steps any number of times, the steps that follow are bit for bit those of a handle that
+ * never called it.  One sweep computes all five quantities; they are kept until a step, a sph_upload, sph_add_particles / sph_remove_in_box, a
+ * re-sort or a change of the body's state or activity, so a second call on an unchanged state only copies.  The feature's device memory (30 floats
+ * per particle of the capacity) is taken at the first call.  Refusals leave the handle unchanged -- SPH_E_STATE: a slab handle; SPH_E_INVALID:
+ * host == NULL, an unknown `which`, a wrong n_floats. */
+int sph_derived(SphHandle *h, int which, float *host, size_t n_floats);
 void sph_destroy(SphHandle *h);
 int sph_get_sizes(SphHandle *h, SphSizes *out);
 const char *sph_last_error(SphHandle *h);
