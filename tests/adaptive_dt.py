@@ -16,6 +16,7 @@ import copy
 
 import numpy as np
 
+import harness as h
 import particle_flow as pf
 from oracle import oracle as orc
 
@@ -80,28 +81,28 @@ def with_dt(cfg, dt):
     return c
 
 
-def oracle_step(o, cfg, solver, dt):
+def oracle_step_dt(o, cfg, solver, dt):
     """one oracle step under the time step dt.  Returns (the oracle to go on with, the step's statistics): pcisph moves to a fresh oracle
     constructed with delta_time = dt, every other solver keeps its oracle and gets set_dt(dt)"""
     if solver == "pcisph":
-        st = pf.fluid_state(o, solver)
+        st = h.fluid_state(o, solver)
         o.close()
-        o = pf.give(pf.make_oracle(with_dt(cfg, dt)), st, solver)
+        o = h.give(h.make_oracle(with_dt(cfg, dt)), st, solver)
         assert F(o.dt) == F(dt)
     else:
         o.set_dt(float(dt))
-    return o, pf.oracle_step(o, solver)
+    return o, h.oracle_step(o, solver)
 
 
 def oracle_run(solver, walls, steps=STEPS):
     """the lockstep case on the oracle alone.  Returns (dt_1 .. dt_steps, the final oracle)"""
     cfg = pf.config(solver, walls, 640)
-    o = pf.make_oracle(cfg)
+    o = h.make_oracle(cfg)
     o.set(orc.F_VEL, velocities(o.N, AMPLITUDE[solver]))
     max_dt, min_dt = bounds(solver)
     dts = []
     for _ in range(steps):
         dt = rule(o.get(orc.F_VEL), max_dt, min_dt)
-        o, _ = oracle_step(o, cfg, solver, dt)
+        o, _ = oracle_step_dt(o, cfg, solver, dt)
         dts.append(dt)
     return dts, o

@@ -10,6 +10,7 @@ step used (SPH_S_ACCEL), feeds it to the restatement and compares every field on
 import numpy as np
 
 import restatement_compare as rc
+from harness import same_bits
 from second_restatement import Solver
 from second_restatement_pbf import PbfSolver
 from second_restatement_rigid import Body
@@ -148,7 +149,7 @@ def lockstep(nat, cfg, sims, steps, rg=None, forcing=None, fields=("pos", "vel",
                 assert d <= 1, (when, a, want)
             if used is None:
                 used = a
-            rc.same(used, a, "%s: the step's vector" % when)
+            same_bits(used, a, "%s: the step's vector" % when)
             if st is not None:
                 ev["lost"] += int(st.lost)
                 ev["capped"] += int(st.capped)
@@ -165,10 +166,10 @@ def lockstep(nat, cfg, sims, steps, rg=None, forcing=None, fields=("pos", "vel",
                 assert stats_of(s) == stats_of_handle(solver, sim.last_stats), (when, stats_of(s))
             for name in fields:
                 attr = [a_ for a_, f_ in rc.FIELDS[solver].items() if f_ == name][0]
-                rc.same(getattr(s, attr), sim.download(rc.F_ID[name]), "%s: %s" % (when, name))
+                same_bits(getattr(s, attr), sim.download(rc.F_ID[name]), "%s: %s" % (when, name))
             if s.body is not None:
                 b, sc = s.body, sim.rigid_scalars()
-                rc.same(b.pos, sim.download(nat.F_RIGID_POS, nat.SPECIES_RIGID), "%s: body samples" % when)
+                same_bits(b.pos, sim.download(nat.F_RIGID_POS, nat.SPECIES_RIGID), "%s: body samples" % when)
                 for mine, key in ((b.centroid, "centroid"), (b.vel, "vel"), (b.omega, "omega")):
-                    rc.same(mine, sc[key], "%s: body %s" % (when, key))
+                    same_bits(mine, sc[key], "%s: body %s" % (when, key))
     return s, ev

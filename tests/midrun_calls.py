@@ -32,21 +32,20 @@ import functools
 
 import numpy as np
 
+import harness as h
 import pinned_loops as pl
 from cfd_taichi_amd import mesh, scenes
+from cfd_taichi_amd._native import S_DELTA_TIME, S_SIMULATE_CNT, SPECIES_FLUID as FLUID, SPECIES_RIGID as RIGID, SPECIES_WALL as WALL
+from harness import LINEAR, MORTON, ORACLE_STATS, same_values_nan_signed, squeezed
 from oracle import oracle as orc
+from oracle.oracle import (F_A_II, F_ACC, F_ALPHA, F_D_II, F_D_IJ, F_NBR_COUNT, F_PBF_DELTA_POS, F_PBF_LAMBDA, F_POS, F_POS_PREDICT, F_PRESS_FORCE, F_PRESS_ITER,
+                           F_PRESSURE, F_RHO, F_RHO_ADV, F_RHO_DER, F_RIGID_FORCE, F_RIGID_MASS, F_RIGID_POS, F_RIGID_VERT, F_RIGID_VOL, F_VEL, F_VEL_ADV,
+                           F_WALL_POS, F_WALL_VOL, F_WARM_K)
 
 K, M = 40, 20
 SEED = 20240807
 
-# field and scalar ids of include/sph_mi355x.h (the oracle shares the field ids)
-F_POS, F_VEL, F_ACC, F_RHO, F_PRESSURE, F_ALPHA, F_WARM_K, F_RHO_ADV, F_RHO_DER, F_VEL_ADV = range(10)
-F_NBR_COUNT = 14
-F_PRESS_ITER, F_PRESS_FORCE, F_POS_PREDICT, F_D_II, F_A_II, F_D_IJ, F_PBF_LAMBDA, F_PBF_DELTA_POS = range(16, 24)
-F_WALL_POS, F_WALL_VOL = 32, 33
-F_RIGID_POS, F_RIGID_VOL, F_RIGID_FORCE, F_RIGID_MASS, F_RIGID_VERT = 48, 49, 50, 51, 52
-FLUID, WALL, RIGID = 0, 1, 2
-S_DELTA_TIME, S_SIMULATE_CNT = 0, 1
+# (field ids: the oracle's, which the library shares; scalar and species ids: the library's)
 SCALARS = tuple(range(10)) + (30, 31, 32)
 RIGID_SCALARS = tuple(range(10, 29))
 PARAMS = {"density_threshold": 64, "min_iteration_density": 65, "min_iteration_density_divergence": 66, "max_iteration_density_divergence": 67,
@@ -73,11 +72,7 @@ LOCAL_OTHERS = (F_POS, F_VEL, F_RHO, F_RHO_ADV, F_RHO_DER, F_ACC, F_PRESSURE)
 PERSISTENT = {"wcsph": (F_POS, F_VEL), "dfsph": (F_POS, F_VEL, F_WARM_K), "pcisph": (F_POS, F_VEL), "iisph": (F_POS, F_VEL),
               "pbf": (F_POS, F_VEL, F_PBF_LAMBDA, F_PBF_DELTA_POS)}
 STATS = ("n_div", "n_dens", "n_div_evals", "div_first_err", "div_err", "dens_err", "dt", "lost", "max_nbrs")
-ORACLE_STATS = STATS[:7]         # OrcStepStats; `lost` is Oracle.lost, max_nbrs has no counterpart there (twin only)
-KNOBS = ("SPH_CELL_ORDER", "SPH_CELL_TILE", "SPH_STAGE", "SPH_STAGE_CAP", "SPH_QUAD", "SPH_NL16", "SPH_KR_SPLIT", "SPH_VERLET_SKIN", "SPH_ARITH",
-         "SPH_TILE_SKIP", "SPH_BNL_SPLIT")
-MORTON = {"SPH_CELL_ORDER": "morton", "SPH_CELL_TILE": "4"}
-LINEAR = {"SPH_CELL_ORDER": "linear"}
+# (harness.ORACLE_STATS is STATS[:7], OrcStepStats; `lost` is Oracle.lost, max_nbrs has no counterpart there: twin only)
 
 Case = collections.namedtuple("Case", "name scene solver arith env oracle rigid squeeze chunks k m start compression")
 
@@ -151,47 +146,12 @@ def rigid_of(case):
     return mesh.rigid_from_config(config(case)) if case.rigid else None
 
 
-def make_oracle(case, num_threads=8):
-    return orc.Oracle(config(case), solver=case.solver, num_threads=num_threads, rigid=rigid_of(case))
-
-
-def squeezed(pos, factor):
-    """test_pbf_gpu.squeeze: the rest lattice is under-dense, squeezing it makes lambda and delta_pos act from the first step"""
-    about = pos.min(0)
-    return (about + (pos - about) * np.float32(factor)).astype(np.float32)
-
-
-def oracle_step(o, solver):
-    """One step; returns the oracle's statistics as stats_bits gives them (None for wcsph / pbf)."""
-    if solver == "dfsph":
-        capped = o.step_dfsph(1, 100)
-    elif solver in ("wcsph", "pbf"):
-        getattr(o, "step_" + solver)(1)
-        return None
-    else:
-        capped = getattr(o, "step_" + solver)(1)
-    return stats_bits(o.last_stats, ORACLE_STATS) + (o.lost,), capped
-
-
-def u32(a):
-    """the bits: -0.0 != 0.0, a NaN equals only the same NaN"""
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+def oracle_of(case, num_threads=8):
+    return h.make_oracle(config(case), case.solver, rigid=rigid_of(case), num_threads=num_threads)
 
 
 def stats_bits(st, names=STATS):
-    return tuple(int(u32(np.float32(v)).reshape(-1)[0]) if isinstance(v, float) else int(v) for v in (getattr(st, n) for n in names))
-
-
-def same(a, b, what):
-    """np.array_equal(..., equal_nan=True) and the sign of zero"""
-    a, b = np.asarray(a, dtype=np.float32), np.asarray(b, dtype=np.float32)
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    if np.array_equal(a, b, equal_nan=True) and np.array_equal(u32(a) == 0x80000000, u32(b) == 0x80000000):
-        return
-    bad = np.argwhere(~((a == b) | (np.isnan(a) & np.isnan(b))) | ((u32(a) == 0x80000000) != (u32(b) == 0x80000000)))
-    scale = max(float(np.nanmax(np.abs(b))) if b.size else 0.0, 1e-30)
-    raise AssertionError("%s differs at %d of %d entries, rel err %.3e, first %s: %r vs %r" % (
-        what, len(bad), a.size, float(np.nanmax(np.abs(a.astype(np.float64) - b))) / scale, bad[0], a[tuple(bad[0])], b[tuple(bad[0])]))
+    return h.stats_bits(st, names)
 
 
 # ---- states S of a re-seat -----------------------------------------------------------------------------------------------------------------
@@ -317,7 +277,7 @@ class Disturber:
     def _upload(self, f):
         before = self.sim.download(f)
         self.sim.upload(f, before)
-        assert np.array_equal(u32(self.sim.download(f)), u32(before)), f
+        assert h.bits_equal(self.sim.download(f), before), f
 
     # -- refused calls
     def _refused(self, fn):
@@ -422,7 +382,7 @@ class Disturber:
             if f == "dt":
                 assert before[f] == after[f], (when, names, before[f], after[f])
             else:
-                same(after[f], before[f], "%s: field %s after %s" % (when, f, names))
+                same_values_nan_signed(after[f], before[f], "%s: field %s after %s" % (when, f, names))
 
     def finish(self):
         """every call was issued at least once"""
@@ -477,7 +437,7 @@ def begin(case, o=None, sims=()):
 
 def lockstep(case, o, sim, when, rec):
     """One step (and rigid_step) of the oracle and, if given, of the handle in lock step; rec collects what the CPU file's conditions are about."""
-    r = oracle_step(o, case.solver)
+    r = h.oracle_step(o, case.solver, bits_view=True)
     rec["lost"] = max(rec.get("lost", 0), o.lost)
     if r is not None:
         rec.setdefault("n_dens", []).append(o.last_stats.n_dens)
@@ -492,46 +452,46 @@ def lockstep(case, o, sim, when, rec):
             assert got == r[0], (when, dict(zip(ORACLE_STATS + ("lost",), zip(got, r[0]))))
             assert st.capped == int(r[1]), (when, st.capped, r[1])
         else:
-            same(sim.download(F_POS), o.get(orc.F_POS), "%s: pos" % when)
+            same_values_nan_signed(sim.download(F_POS), o.get(orc.F_POS), "%s: pos" % when)
             assert np.float32(sim.scalar(S_DELTA_TIME)) == np.float32(o.dt), when
     if case.rigid:
         force = o.get(orc.F_RIGID_FORCE)
         rec["force"] = max(rec.get("force", 0.0), float(np.abs(force).max()))
         if sim is not None:
-            same(sim.download(F_RIGID_FORCE, RIGID), force, "%s: force on the body" % when)
+            same_values_nan_signed(sim.download(F_RIGID_FORCE, RIGID), force, "%s: force on the body" % when)
             sim.rigid_step()
         o.rigid_step()
         if sim is not None:
             a, b = sim.rigid_scalars(), o.rigid_scalars()
             for k in ("centroid", "omega", "vel"):
-                same(np.float32(a[k]), np.float32(b[k]), "%s: body %s" % (when, k))
+                same_values_nan_signed(np.float32(a[k]), np.float32(b[k]), "%s: body %s" % (when, k))
 
 
 def same_as_oracle(case, sim, o, when):
     """every field a step leaves downloadable, and the body"""
     for f in SOLVER_FIELDS[case.solver]:
-        same(sim.download(f), o.get(f), "%s: field %d" % (when, f))
+        same_values_nan_signed(sim.download(f), o.get(f), "%s: field %d" % (when, f))
     assert np.float32(sim.scalar(S_DELTA_TIME)) == np.float32(o.dt), when
     if case.rigid:
         for f in (F_RIGID_POS, F_RIGID_FORCE, F_RIGID_VERT):
-            same(sim.download(f, RIGID), o.get(f), "%s: rigid field %d" % (when, f))
+            same_values_nan_signed(sim.download(f, RIGID), o.get(f), "%s: rigid field %d" % (when, f))
 
 
 def stage_fields_as_oracle(case, sim, o, when):
     """compute_density (dfsph: + alpha) and the neighbour count of the state both sides hold now, through the validity flags of the handle"""
     sim.compute_density()
     o.build_grid(); o.compute_rho(); o.compute_nbr_count()
-    same(sim.download(F_RHO), o.get(orc.F_RHO), "%s: rho of compute_density" % when)
-    same(sim.download(F_NBR_COUNT), o.get(orc.F_NBR_COUNT), "%s: neighbour count" % when)
+    same_values_nan_signed(sim.download(F_RHO), o.get(orc.F_RHO), "%s: rho of compute_density" % when)
+    same_values_nan_signed(sim.download(F_NBR_COUNT), o.get(orc.F_NBR_COUNT), "%s: neighbour count" % when)
     if case.solver == "dfsph":
         sim.compute_alpha(); o.compute_alpha()
-        same(sim.download(F_ALPHA), o.get(orc.F_ALPHA), "%s: alpha of compute_alpha" % when)
+        same_values_nan_signed(sim.download(F_ALPHA), o.get(orc.F_ALPHA), "%s: alpha of compute_alpha" % when)
 
 
 def reseat_run(case, order, sim=None, seed=1):
     """K steps, S, M steps, the second S, M steps.  Returns [history record, record of the M steps after each S]: what the CPU file's conditions are about."""
     k, m = reseat_steps(case)
-    o = make_oracle(case)
+    o = oracle_of(case)
     begin(case, o, [sim] if sim is not None else [])
     recs, half = [{"kind": "history"}], None
     for s in range(k):

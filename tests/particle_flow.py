@@ -1,5 +1,5 @@
 """Scenes and helpers of the inlet / sink suites (TEST INFRASTRUCTURE: test_particle_flow_cpu.py and test_particle_flow_gpu.py; nothing here
-imports the HIP library -- the GPU file hands in `nat`, cfd_taichi_amd._native).
+loads the HIP library; the generic helpers are tests/harness.py's).
 
 The yardstick is the equivalence that sph_add_particles / sph_remove_in_box promise: a handle whose particles arrived
 or left between steps computes, bit for bit, what a fresh oracle (or, under the relaxed arithmetic, a fresh handle) holding the same particles
@@ -15,20 +15,16 @@ import copy
 
 import numpy as np
 
+from cfd_taichi_amd import _native as nat
 from cfd_taichi_amd import scenes
+from harness import fluid_state, oracle_step, same_bits, same_stats
 from oracle import oracle as orc
-from rigid_release import fluid_state, give, give_sim  # noqa: F401  (re-exported for the two suites)
 
 SOLVERS = ("wcsph", "dfsph", "pcisph", "iisph", "pbf")
 DT = {"dfsph": 1e-3, "wcsph": 2.5e-4, "pcisph": 1e-3, "iisph": 1e-3, "pbf": 2.5e-4}       # as the tiny scenes of scenes.SCENES set it
 HEIGHTS = {640: 0.5, 704: 0.55, 832: 0.65}
 ADD_CALLS = (37, 27, 64, 64)                  # 640 -> 677 -> 704 -> 768 -> 832
 D = 0.05                                      # particle diameter of the tiny scenes
-MORTON = {"SPH_CELL_ORDER": "morton", "SPH_CELL_TILE": "4"}      # as tests/midrun_calls.py selects Morton cells (and with them the staged sweeps)
-KNOBS = ("SPH_CELL_ORDER", "SPH_CELL_TILE", "SPH_STAGE", "SPH_STAGE_CAP", "SPH_QUAD", "SPH_NL16", "SPH_KR_SPLIT", "SPH_VERLET_SKIN", "SPH_ARITH",
-         "SPH_TILE_SKIP", "SPH_BNL_SPLIT")
-F_POS, F_VEL, F_RHO, F_WARM_K, F_NBR_COUNT, F_PRESS_ITER = 0, 1, 3, 6, 14, 16
-S_DELTA_TIME, S_GRAPH_LAUNCHES, S_ARITH_RELAXED = 0, 5, 30
 
 
 def config(solver, walls, n, capacity=0):
@@ -60,53 +56,19 @@ def threshold_config(solver, n, capacity=0):
     return cfg
 
 
-def make_oracle(cfg, num_threads=8):
-    return orc.Oracle(cfg, solver=cfg["solver"]["name"], num_threads=num_threads)
-
-
-def oracle_step(o, solver):
-    if solver == "dfsph":
-        o.step_dfsph(1, 100)
-    else:
-        getattr(o, "step_" + solver)(1)
-    return o.last_stats
-
-
-def stats_tuple(st, solver):
-    """rigid_release.stats_tuple, with pbf (no statistics) beside wcsph"""
-    if solver == "dfsph":
-        return (st.n_div, st.n_dens, st.div_first_err, st.div_err, st.dens_err, st.dt)
-    if solver in ("wcsph", "pbf"):
-        return ()
-    return (st.n_dens, st.dens_err)
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def same(a, b, what):
-    """bit for bit, as tests/midrun_calls.py::same"""
-    a, b = np.asarray(a, dtype=np.float32), np.asarray(b, dtype=np.float32)
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    if not np.array_equal(u32(a), u32(b)):
-        bad = np.argwhere(u32(a) != u32(b))
-        raise AssertionError("%s differs at %d of %d entries, first %s: %r vs %r" % (what, len(bad), a.size, bad[0], a[tuple(bad[0])], b[tuple(bad[0])]))
-
-
 def same_state(sim, o, solver, when):
-    """every field fluid_state names, plus rho"""
+    """every field fluid_state names, plus rho (harness.same_bits)"""
     a, b = fluid_state(sim, solver), fluid_state(o, solver)
     for k in a:
-        same(np.float32(a[k]), np.float32(b[k]), "%s: %s" % (when, k))
-    same(sim.download(F_RHO), o.get(orc.F_RHO), "%s: rho" % when)
+        same_bits(np.float32(a[k]), np.float32(b[k]), "%s: %s" % (when, k))
+    same_bits(sim.download(nat.F_RHO), o.get(orc.F_RHO), "%s: rho" % when)
 
 
 def same_nbr_count(sim, o, when):
     """SPH_F_NBR_COUNT of the positions both sides hold now (re-sorts the handle: the last comparison of a run)"""
     sim.build_neighbors()
     o.build_grid(); o.compute_nbr_count()
-    same(sim.download(F_NBR_COUNT), o.get(orc.F_NBR_COUNT), "%s: neighbour count" % when)
+    same_bits(sim.download(nat.F_NBR_COUNT), o.get(orc.F_NBR_COUNT), "%s: neighbour count" % when)
 
 
 def lockstep(sim, o, solver, steps, when, every=5, count=True):
@@ -116,8 +78,7 @@ def lockstep(sim, o, solver, steps, when, every=5, count=True):
     for s in range(steps):
         st = sim.step(1)
         ot = oracle_step(o, solver)
-        if stats_tuple(ot, solver):
-            same(np.float32(stats_tuple(st, solver)), np.float32(stats_tuple(ot, solver)), "%s, step %d: statistics" % (when, s + 1))
+        same_stats(st, ot, solver, "%s, step %d: statistics" % (when, s + 1))
         if (s + 1) % every == 0 or s + 1 == steps:
             same_state(sim, o, solver, "%s, step %d" % (when, s + 1))
     if count:

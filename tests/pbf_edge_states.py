@@ -29,6 +29,7 @@ import numpy as np
 
 import pbf_states as pb
 from cfd_taichi_amd import scenes
+from harness import squeezed
 from oracle import oracle as orc
 
 SCENES = ("pbf_tiny_wall", "pbf_tiny_clamp")
@@ -63,8 +64,7 @@ def ragged(scene, water):
     cfg = scenes.get(scene)
     cfg["fluid"].update(start_pos=[0.05, 0.05, 0.05], water_size=list(water))
     pos = _lattice(cfg)
-    about = pos.min(0)
-    pos = (about + (pos - about) * np.float32(SQUEEZE)).astype(np.float32)
+    pos = squeezed(pos, SQUEEZE)
     return Input("ragged %s N=%d" % (scene, len(pos)), cfg, pos, np.zeros_like(pos))
 
 

@@ -20,7 +20,7 @@ from oracle import oracle as orc
 from pinned_loops import FLOOR, MARGIN, STATS, compare, errors, state, stats3, wall_mask  # noqa: F401  (re-exported)
 
 # field ids are those of include/sph_mi355x.h, which the oracle shares
-F_POS, F_VEL, F_RHO, F_PBF_LAMBDA, F_PBF_DELTA_POS = 0, 1, 3, 22, 23
+from oracle.oracle import F_PBF_DELTA_POS, F_PBF_LAMBDA, F_POS, F_RHO, F_VEL  # noqa: E402,F401
 FIELDS = (("rho", F_RHO), ("pbf_lambda", F_PBF_LAMBDA), ("delta_pos", F_PBF_DELTA_POS), ("pos", F_POS), ("vel", F_VEL))
 SEEDS = (1, 3)
 # (scene, state kind, steps): the cases of both test files

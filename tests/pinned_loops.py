@@ -19,7 +19,7 @@ from cfd_taichi_amd import scenes
 from oracle import oracle as orc
 
 # field ids are those of include/sph_mi355x.h, which the oracle shares
-F_POS, F_VEL, F_RHO, F_ALPHA, F_WARM_K, F_RHO_ADV, F_RHO_DER, F_VEL_ADV, F_NBR_COUNT, F_RIGID_FORCE = 0, 1, 3, 5, 6, 7, 8, 9, 14, 50
+from oracle.oracle import F_ALPHA, F_NBR_COUNT, F_POS, F_RHO, F_RHO_ADV, F_RHO_DER, F_RIGID_FORCE, F_VEL, F_VEL_ADV, F_WARM_K  # noqa: E402,F401
 FIELDS = (("rho", F_RHO), ("alpha", F_ALPHA), ("rho_der", F_RHO_DER), ("warm_k", F_WARM_K), ("rho_adv", F_RHO_ADV), ("vel_adv", F_VEL_ADV),
           ("pos", F_POS), ("vel", F_VEL))
 # `solver.<attribute>`: name -> SPH_P_* (include/sph_mi355x.h)

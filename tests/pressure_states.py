@@ -20,12 +20,12 @@ import functools
 import numpy as np
 
 from cfd_taichi_amd import scenes
+from harness import same_values
 from oracle import oracle as orc
 from pinned_loops import FLOOR, JITTER, MARGIN, STATS, VEL_AMP, Pool, compare, errors, stats3  # noqa: F401  (re-exported)
 
 # field ids are those of include/sph_mi355x.h, which the oracle shares
-F_POS, F_VEL, F_ACC, F_RHO, F_PRESSURE, F_NBR_COUNT = 0, 1, 2, 3, 4, 14
-F_PRESS_ITER, F_PRESS_FORCE, F_POS_PREDICT, F_D_II, F_A_II, F_D_IJ = 16, 17, 18, 19, 20, 21
+from oracle.oracle import F_A_II, F_ACC, F_D_II, F_D_IJ, F_NBR_COUNT, F_POS, F_POS_PREDICT, F_PRESS_FORCE, F_PRESS_ITER, F_PRESSURE, F_RHO, F_VEL  # noqa: E402,F401
 FIELDS = {
     "wcsph": (("rho", F_RHO), ("pressure", F_PRESSURE), ("acc", F_ACC), ("vel", F_VEL), ("pos", F_POS)),
     "pcisph": (("rho", F_RHO), ("press_iter", F_PRESS_ITER), ("press_force", F_PRESS_FORCE), ("pos_predict", F_POS_PREDICT), ("vel", F_VEL),
@@ -294,10 +294,6 @@ def handles(nat, cfg, knobs, monkeypatch, rigid=None, exact=True):
     return rx, ex
 
 
-def same(a, b, what):
-    assert a.shape == b.shape and np.array_equal(a, b), "%s: differ at %d of %d entries" % (what, int((a != b).sum()), a.size)
-
-
 def check_steps(label, scene, seed, compression, a, b, r32, r64, pool, vel_amp=VEL_AMP, nbr_of_relaxed=True):
     """items 2-6 of the docstring for the steps of one case: a = relaxed handle, b = exact handle (or None)"""
     cfg, solver = config(scene), solver_of(scene)
@@ -311,7 +307,7 @@ def check_steps(label, scene, seed, compression, a, b, r32, r64, pool, vel_amp=V
                 assert np.array_equal(r.nbr, r64[s].nbr), (tag, who, int((r.nbr != r64[s].nbr).sum()))
         if b is not None:          # the exact handle IS the f32 oracle
             for name, _ in FIELDS[solver]:
-                same(b[s][name], r32[s][name], "%s %s, exact handle and f32 oracle" % (tag, name))
+                same_values(b[s][name], r32[s][name], "%s %s, exact handle and f32 oracle" % (tag, name))
         if not cfg["solver"].get("boundary_handle", True):
             ca, c64 = clamped(cfg, a[s]["pos"]), clamped(cfg, r64[s]["pos"])
             assert np.array_equal(ca, c64), "%s: the clamped set of the relaxed handle is not the f64 oracle's (%d entries differ)" % (tag, int((ca != c64).sum()))

@@ -3,6 +3,7 @@ one run of the second restatement, any number of other sides in lockstep, every 
 of what the run exercised.  TEST INFRASTRUCTURE ONLY."""
 import numpy as np
 
+from harness import same_bits
 from second_restatement import Solver
 from second_restatement_pbf import PbfSolver
 
@@ -19,19 +20,6 @@ FIELDS = {
     "iisph": {"rho": "rho", "p_iter": "press_iter", "f_press": "press_force", "d_ii": "d_ii", "a_ii": "a_ii", "d_ij": "d_ij", "vel": "vel", "pos": "pos"},
     "pbf": {"rho": "rho", "pbf_lambda": "pbf_lambda", "delta_pos": "pbf_delta_pos", "vel": "vel", "pos": "pos"},
 }
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def same(a, b, what):
-    a, b = np.asarray(a, dtype=np.float32), np.asarray(b, dtype=np.float32)
-    assert a.shape == b.shape, what
-    if not np.array_equal(bits(a), bits(b)):
-        bad = np.argwhere(bits(a) != bits(b))
-        i = tuple(bad[0])
-        raise AssertionError("%s: %d of %d values differ, first at %s: %r (second restatement) vs %r" % (what, len(bad), a.size, i, a[i], b[i]))
 
 
 class OracleSide:
@@ -161,7 +149,7 @@ def compare_run(cfg, steps, sides, state=None, rg=None, density_after=False):
             if b is not None:
                 for side in sides:
                     _same_body(b, side, "at creation", b.active)
-                    same(b.vol, side.get("rigid_vol"), "%s: sample volumes" % side.label)
+                    same_bits(b.vol, side.get("rigid_vol"), "%s: sample volumes" % side.label)
             for k in range(1, steps + 1):
                 before = [side.ncount_before_step() if count_too else None for side in sides]
                 s.step()
@@ -169,16 +157,16 @@ def compare_run(cfg, steps, sides, state=None, rg=None, density_after=False):
                     st = side.step()
                     when = "%s, step %d" % (side.label, k)
                     if count_too:
-                        same(s.ncount, nc if nc is not None else side.ncount_after_step(), "%s: ncount" % when)
+                        same_bits(s.ncount, nc if nc is not None else side.ncount_after_step(), "%s: ncount" % when)
                     if solver == "dfsph":
                         mine = (s.n_div, s.n_dens, np.float32(s.div_first), np.float32(s.div_err), np.float32(s.dens_err), np.float32(s.dt))
                         assert mine == (st.n_div, st.n_dens, np.float32(st.div_first_err), np.float32(st.div_err), np.float32(st.dens_err), np.float32(st.dt)), (when, mine)
                     elif solver not in ("wcsph", "pbf"):
                         assert (s.n_dens, np.float32(s.dens_err)) == (st.n_dens, np.float32(st.dens_err)), (when, s.n_dens, st.n_dens, s.dens_err, st.dens_err)
                     for attr, name in FIELDS[solver].items():
-                        same(getattr(s, attr), side.get(name), "%s: %s" % (when, attr))
+                        same_bits(getattr(s, attr), side.get(name), "%s: %s" % (when, attr))
                     if b is not None:
-                        same(b.force, side.get("rigid_force"), "%s: per-sample force" % when)
+                        same_bits(b.force, side.get("rigid_force"), "%s: per-sample force" % when)
                 ev["iters"].append((s.n_div, s.n_dens) if solver == "dfsph" else s.n_dens)
                 if solver == "pbf":
                     ev["lambda_active"].append(int((s.pbf_lambda != 0).sum()))
@@ -204,11 +192,11 @@ def compare_run(cfg, steps, sides, state=None, rg=None, density_after=False):
                 for side in sides:
                     kept = {name: side.get(name).copy() for name in FIELDS[solver].values() if name != "rho"}
                     side.density_only()
-                    same(s.rho, side.get("rho"), "%s: rho of compute_all_rho alone" % side.label)
+                    same_bits(s.rho, side.get("rho"), "%s: rho of compute_all_rho alone" % side.label)
                     for name, was in kept.items():
-                        same(was, side.get(name), "%s: %s across compute_all_rho alone" % (side.label, name))
+                        same_bits(was, side.get(name), "%s: %s across compute_all_rho alone" % (side.label, name))
                 for attr, name in FIELDS[solver].items():       # ... and the restatement's own
-                    same(getattr(s, attr), sides[0].get(name), "%s after compute_all_rho alone" % attr)
+                    same_bits(getattr(s, attr), sides[0].get(name), "%s after compute_all_rho alone" % attr)
     finally:
         for side in sides:
             side.close()
@@ -219,8 +207,8 @@ def compare_run(cfg, steps, sides, state=None, rg=None, density_after=False):
 
 def _same_body(b, side, when, finite):
     sc = side.rigid_scalars()
-    same(b.pos, side.get("rigid_pos"), "%s: sample positions %s" % (side.label, when))
-    same(b.vert, side.get("rigid_vert"), "%s: vertices %s" % (side.label, when))
+    same_bits(b.pos, side.get("rigid_pos"), "%s: sample positions %s" % (side.label, when))
+    same_bits(b.vert, side.get("rigid_vert"), "%s: vertices %s" % (side.label, when))
     if finite:
         for mine, key in ((b.centroid, "centroid"), (b.vel, "vel"), (b.omega, "omega"), (b.inertia_inv.ravel(), "inertia_inv")):
-            same(mine, sc[key], "%s: %s %s" % (side.label, key, when))
+            same_bits(mine, sc[key], "%s: %s %s" % (side.label, key, when))

@@ -50,12 +50,3 @@ def scene(solver, mode):
 
 def rigid(cfg):
     return mesh.rigid_from_config(cfg) if "solid" in cfg else None
-
-
-def oracle_step(o, solver):
-    """One step of the oracle's restatement of `solver`; returns its stats (the dfsph density loop capped as test_rigid_gpu caps it)."""
-    if solver == "dfsph":
-        o.step_dfsph(1, 100)
-    else:
-        getattr(o, "step_" + solver)(1)
-    return o.last_stats

@@ -18,8 +18,8 @@ import numpy as np
 
 import rigid_modes
 from cfd_taichi_amd import scenes
-from oracle import oracle as orc
-from rigid_modes import DT, SOLVERS, oracle_step, rigid  # noqa: F401  (re-exported for the two suites)
+from harness import make_oracle
+from rigid_modes import DT, SOLVERS, rigid  # noqa: F401  (re-exported for the two suites)
 
 K, AFTER = 10, 30                       # steps with the body inactive, steps after the release
 TWO_WAY = [round(v - d, 3) for v, d in zip(scenes.get("dfsph_rigid_small")["solid"]["pos_offset"], (0.05, 0.0, 0.0))]      # [0.70, 0.1, 0.5]
@@ -38,57 +38,8 @@ def scene(solver, active, fs_couple=True, offset=None):
     return cfg
 
 
-def make_oracle(cfg, solver):
-    return orc.Oracle(cfg, solver=solver, num_threads=8, rigid=rigid(cfg))
-
-
-def fluid_state(x, solver):
-    """Everything a step of `solver` reads of the fluid, from an Oracle or a Simulation."""
-    if isinstance(x, orc.Oracle):
-        st = {"pos": x.get(orc.F_POS), "vel": x.get(orc.F_VEL), "dt": x.dt}
-        if solver == "dfsph":
-            st["warm_k"] = x.get(orc.F_WARM_K)
-        if solver == "iisph":
-            st["p_past"] = x.get(orc.F_P_PAST)
-        return st
-    from cfd_taichi_amd import _native as nat
-    st = {"pos": x.download(nat.F_POS), "vel": x.download(nat.F_VEL), "dt": x.scalar(nat.S_DELTA_TIME)}
-    if solver == "dfsph":
-        st["warm_k"] = x.download(nat.F_WARM_K)
-    if solver == "iisph":
-        st["p_past"] = x.download(nat.F_PRESS_ITER)         # last step's pressure (iisph_solver.py:68, :209-210)
-    return st
-
-
-def give(o, st, solver):
-    """Hand a fluid state to a fresh oracle."""
-    o.set(orc.F_POS, st["pos"]); o.set(orc.F_VEL, st["vel"])
-    if solver == "dfsph":
-        o.set(orc.F_WARM_K, st["warm_k"])
-        o.set_dt(st["dt"])
-    if solver == "iisph":
-        o.set(orc.F_P_PAST, st["p_past"])
-    return o
-
-
-def give_sim(sim, st, solver):
-    """The same into a Simulation (iisph's last pressure cannot be uploaded: dfsph, wcsph and pcisph only)."""
-    from cfd_taichi_amd import _native as nat
-    assert solver != "iisph"
-    sim.upload(nat.F_POS, st["pos"]); sim.upload(nat.F_VEL, st["vel"])
-    if solver == "dfsph":
-        sim.upload(nat.F_WARM_K, st["warm_k"])
-        sim.set_dt(st["dt"])
-    return sim
-
-
-def stats_tuple(st, solver):
-    """What the suites compare of a step's statistics."""
-    if solver == "dfsph":
-        return (st.n_div, st.n_dens, st.div_first_err, st.div_err, st.dens_err, st.dt)
-    if solver == "wcsph":
-        return ()
-    return (st.n_dens, st.dens_err)
+def body_oracle(cfg, solver):
+    return make_oracle(cfg, solver, rigid=rigid(cfg))
 
 
 def same_fields(a, b):

@@ -11,6 +11,7 @@ puts a ScriptedBody into restatement_compare.compare_run unchanged; the library 
 import numpy as np
 
 import restatement_compare as rc
+from harness import bits_equal, same_bits
 import second_restatement_rigid as srr
 from second_restatement import F, _cross
 
@@ -100,15 +101,15 @@ class PlannedSide(rc.NativeSide):
         self.sim.rigid_step()
         b = ScriptedBody.current
         force, torque = self.sim.rigid_load()
-        rc.same(b.load[0], force.astype(np.float32), "%s: load, force, body step %d" % (self.label, self.steps))
-        rc.same(b.load[1], torque.astype(np.float32), "%s: load, torque, body step %d" % (self.label, self.steps))
+        same_bits(b.load[0], force.astype(np.float32), "%s: load, force, body step %d" % (self.label, self.steps))
+        same_bits(b.load[1], torque.astype(np.float32), "%s: load, torque, body step %d" % (self.label, self.steps))
         sc = self.sim.rigid_scalars(motion=True)
-        rc.same(b.acc, sc["acc"], "%s: acc, body step %d" % (self.label, self.steps))
-        rc.same(b.s_alpha, sc["alpha"], "%s: alpha, body step %d" % (self.label, self.steps))
+        same_bits(b.acc, sc["acc"], "%s: acc, body step %d" % (self.label, self.steps))
+        same_bits(b.s_alpha, sc["alpha"], "%s: alpha, body step %d" % (self.label, self.steps))
         assert sc["mode"] == mode
         if all(self.plan(k)[0] == FIXED for k in range(1, self.steps + 1)):       # fixed so far: the bits of creation
-            assert np.array_equal(rc.bits(self.start[0]), rc.bits(self.get("rigid_pos"))), "%s: a fixed body's samples moved" % self.label
-            assert np.array_equal(rc.bits(self.start[1]), rc.bits(self.get("rigid_vert"))), "%s: a fixed body's vertices moved" % self.label
+            assert bits_equal(self.start[0], self.get("rigid_pos")), "%s: a fixed body's samples moved" % self.label
+            assert bits_equal(self.start[1], self.get("rigid_vert")), "%s: a fixed body's vertices moved" % self.label
 
 
 def sides(monkeypatch, plan):

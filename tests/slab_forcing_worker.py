@@ -16,7 +16,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import forcing as fo  # noqa: E402
-from slab_ranks import Ranks, loopback_env, same_bits  # noqa: E402
+from harness import bits_equal  # noqa: E402
+from slab_ranks import Ranks, loopback_env  # noqa: E402
 
 
 def clock_and_vector(sim):
@@ -69,7 +70,7 @@ def main():
         res["vectors"].append(ref.accel().tolist())
         if res["first_difference"] is None:
             for name, f in (("pos", nat.F_POS), ("vel", nat.F_VEL)):
-                if not same_bits(group.gather(f), ref.download(f)):
+                if not bits_equal(group.gather(f), ref.download(f)):
                     res["first_difference"] = {"step": k, "what": name}
                     break
         if res["first_difference"] is None:

@@ -22,7 +22,7 @@ import numpy as np
 
 from cfd_taichi_amd import scenes
 
-F_POS, F_VEL, F_RHO, F_PBF_LAMBDA, F_PBF_DELTA_POS = 0, 1, 3, 22, 23      # include/sph_mi355x.h, shared by the oracle
+from oracle.oracle import F_PBF_DELTA_POS, F_PBF_LAMBDA, F_POS, F_RHO, F_VEL  # noqa: E402,F401  (the library shares the ids)
 FIELDS = (("pos", F_POS), ("vel", F_VEL), ("rho", F_RHO), ("pbf_lambda", F_PBF_LAMBDA), ("delta_pos", F_PBF_DELTA_POS))
 SEEDS = (1, 3)
 STEPS = 60

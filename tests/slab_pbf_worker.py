@@ -25,13 +25,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import slab_pbf_states as sp  # noqa: E402
-from slab_ranks import Ranks, loopback_env, process_group, same_bits  # noqa: E402
+from harness import bits_equal  # noqa: E402
+from slab_ranks import Ranks, loopback_env, process_group  # noqa: E402
 
 
 def first_difference(step, got, ref):
     """None, or where the sharded fields leave the one-GPU handle's"""
     for name, _ in sp.FIELDS:
-        if not same_bits(got[name], ref[name]):
+        if not bits_equal(got[name], ref[name]):
             bad = np.flatnonzero((got[name].view(np.uint32) != ref[name].view(np.uint32)).reshape(len(ref[name]), -1).any(1))
             return {"step": step, "field": name, "particles": int(len(bad)), "first_ids": [int(i) for i in bad[:8]],
                     "max_abs": float(np.nanmax(np.abs(got[name].astype(np.float64) - ref[name])))}
@@ -116,7 +117,7 @@ def mode_roundtrip(nat, cfg, args):
         b.step()
     a.step_pbf(args.steps)
     pos, vel, dt = b.gather(nat.F_POS), b.gather(nat.F_VEL), b.sims[0].scalar(nat.S_DELTA_TIME)
-    res["state_equal_one_gpu"] = same_bits(pos, a.download(nat.F_POS)) and same_bits(vel, a.download(nat.F_VEL))
+    res["state_equal_one_gpu"] = bits_equal(pos, a.download(nat.F_POS)) and bits_equal(vel, a.download(nat.F_VEL))
     res["scalar_refused"] = b.codes(lambda r, s: s.slab_set_state(pos, vel, np.zeros(len(pos), dtype=np.float32), dt))
     c = Ranks(nat, cfg, 2)
     set_state(c, pos, vel, None, dt)
@@ -150,13 +151,13 @@ def mode_midrun(nat, cfg, args):
             b.each(lambda r, s: s.compute_density())
             a2 = one_gpu(nat, cfg, state)
             a2.step_pbf(args.at); a2.compute_density()
-            res["rho_after_compute_density"] = same_bits(b.gather(nat.F_RHO), a2.download(nat.F_RHO))
+            res["rho_after_compute_density"] = bits_equal(b.gather(nat.F_RHO), a2.download(nat.F_RHO))
             res["lambda_after_compute_density"] = b.codes(lambda r, s: s.download_local(nat.F_PBF_LAMBDA))
             a2.close()
             b.each(lambda r, s: (s.build_neighbors(), s.build_neighbors()))
             res["lambda_after_build"] = b.codes(lambda r, s: s.download_local(nat.F_PBF_LAMBDA))
             res["delta_pos_after_build"] = b.codes(lambda r, s: s.download_local(nat.F_PBF_DELTA_POS))
-            res["state_after_build"] = same_bits(b.gather(nat.F_POS), a.download(nat.F_POS)) and same_bits(b.gather(nat.F_VEL), a.download(nat.F_VEL))
+            res["state_after_build"] = bits_equal(b.gather(nat.F_POS), a.download(nat.F_POS)) and bits_equal(b.gather(nat.F_VEL), a.download(nat.F_VEL))
             res["owned_after_build"] = sum(i["owned"] for i in b.infos())
         if k == args.at + 1:
             res["lambda_after_next_step"] = b.codes(lambda r, s: s.download_local(nat.F_PBF_LAMBDA))
@@ -220,7 +221,7 @@ def mode_equal_gloo(args, rank, world, device):
     dist.gather_object((ghosts_max, sim.sim.slab_info(), sim.sim.comm_stats(), sim.comm.stats, sim.sim.scalar(nat.S_ARITH_RELAXED)), parts, dst=0)
     if rank == 0:
         res["step_returns_none"] = ret is None
-        res["state_round_trip"] = bool(same_bits(back[0], got["pos"]) and same_bits(back[1], got["vel"]) and back[2] is None and
+        res["state_round_trip"] = bool(bits_equal(back[0], got["pos"]) and bits_equal(back[1], got["vel"]) and back[2] is None and
                                        np.float32(back[3]) == np.float32(cfg["solver"]["delta_time"]))
         res["ghosts_max"] = [p[0] for p in parts]
         res["slabs"] = [p[1] for p in parts]

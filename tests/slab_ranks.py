@@ -39,11 +39,6 @@ def stat_row(st):
     return None if st is None else [st.n_div, st.n_dens, st.n_div_evals, float(st.div_first_err), float(st.div_err), float(st.dens_err), float(st.dt)]
 
 
-def same_bits(a, b):
-    """raw f32: -0.0 is not +0.0, a NaN equals the NaN of the same payload"""
-    return a.shape == b.shape and bool(np.array_equal(a.view(np.uint32), b.view(np.uint32)))
-
-
 def gather_by_id(sims, field):
     """(out, seen): the handles' owned particles in original order (NaN where nobody owns one), and how many handles own each id -- all 1 for a partition"""
     n = sims[0].n_fluid

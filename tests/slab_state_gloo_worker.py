@@ -21,7 +21,8 @@ def main():
     ap.add_argument("--out", required=True)
     args = ap.parse_args()
     import torch.distributed as dist
-    from slab_ranks import process_group, same_bits, stat_row
+    from harness import bits_equal
+    from slab_ranks import process_group, stat_row
     from slab_state_worker import one_gpu_state
     with process_group() as (rank, world, device):
         from cfd_taichi_amd import _native as nat
@@ -36,7 +37,7 @@ def main():
         res = {}
         if rank == 0:
             pos, vel, warm, dt = state
-            res["roundtrip"] = same_bits(back[0], pos) and same_bits(back[1], vel) and same_bits(back[2], warm)
+            res["roundtrip"] = bits_equal(back[0], pos) and bits_equal(back[1], vel) and bits_equal(back[2], warm)
             res["state_dt"] = np.float32(back[3]) == np.float32(dt)
             a = nat.Simulation(nat.config_from_dict(cfg, device=device))
             a.upload(nat.F_POS, pos); a.upload(nat.F_VEL, vel); a.upload(nat.F_WARM_K, warm)
@@ -52,7 +53,7 @@ def main():
                 if stats_bad is None and any(row != sa for row in rows):
                     stats_bad = {"step": k + 1, "one_gpu": sa, "ranks": rows}
                 for name, field, g in zip(("pos", "vel", "rho"), (nat.F_POS, nat.F_VEL, nat.F_RHO), got):
-                    if first_bad is None and not same_bits(g, a.download(field)):
+                    if first_bad is None and not bits_equal(g, a.download(field)):
                         first_bad = {"step": k + 1, "field": name}
         if rank == 0:
             res.update({"first_difference": first_bad, "stats_difference": stats_bad, "world": world, "n": int(sim.n_fluid)})

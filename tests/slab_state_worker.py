@@ -18,7 +18,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-from slab_ranks import Ranks, gather_by_id, loopback_env, same_bits, stat_row  # noqa: E402
+from harness import bits_equal  # noqa: E402
+from slab_ranks import Ranks, gather_by_id, loopback_env, stat_row  # noqa: E402
 
 
 def gather_ok(b, field):
@@ -59,7 +60,7 @@ def mode_equal(nat, cfg, args):
     res["n"] = int(a.n_fluid)
     back = [gather_ok(b, f) for f in (nat.F_POS, nat.F_VEL)] + ([gather_ok(b, nat.F_WARM_K)] if warm is not None else [])
     res["partition"] = all(ok for _, ok in back)
-    res["roundtrip"] = all(same_bits(got, want) for (got, _), want in zip(back, (pos, vel, warm)))
+    res["roundtrip"] = all(bits_equal(got, want) for (got, _), want in zip(back, (pos, vel, warm)))
     res["dt_set"] = [s.scalar(nat.S_DELTA_TIME) for s in b.sims] == [a.scalar(nat.S_DELTA_TIME)] * args.world
     first_bad, stats_bad = None, None
     for k in range(args.m):
@@ -69,7 +70,7 @@ def mode_equal(nat, cfg, args):
             stats_bad = {"step": k + 1, "one_gpu": sa, "ranks": sb}
         for name, field in (("pos", nat.F_POS), ("vel", nat.F_VEL), ("rho", nat.F_RHO)):
             got, ok = gather_ok(b, field)
-            if first_bad is None and not (ok and same_bits(got, a.download(field))):
+            if first_bad is None and not (ok and bits_equal(got, a.download(field))):
                 first_bad = {"step": k + 1, "field": name, "partition": ok}
     res.update({"steps_compared": args.m, "first_difference": first_bad, "stats_difference": stats_bad, "stats_last": sa,
                 "cuts_end": b.cuts(), "recuts": [s.slab_info()["recuts"] for s in b.sims], "overrides": b.sims[0].overrides()})
@@ -85,7 +86,7 @@ def mode_roundtrip(nat, cfg, args):
     b = Ranks(nat, cfg, args.world)
     b.each(lambda r, s: s.slab_set_state(pos, vel, warm, 0.0))
     back = [gather_ok(b, f) for f in (nat.F_POS, nat.F_VEL, nat.F_WARM_K)]
-    res = {"partition": all(ok for _, ok in back), "equal": [same_bits(got, want) for (got, _), want in zip(back, (pos, vel, warm))],
+    res = {"partition": all(ok for _, ok in back), "equal": [bits_equal(got, want) for (got, _), want in zip(back, (pos, vel, warm))],
            "owned": [s.slab_info()["owned"] for s in b.sims], "n": len(pos), "overrides": b.sims[0].overrides()}
     # vel / scalar NULL: zeros
     b.each(lambda r, s: s.slab_set_state(pos))

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import adaptive_dt as ad
+import harness as h
 import particle_flow as pf
 from cfd_taichi_amd import _native as nat
 from cfd_taichi_amd import scenes
@@ -58,12 +59,12 @@ def test_pcisph_delta_follows_the_oracle_of_that_step():
     roundings involved (2 per delta, each 2^-24 relative: bound 4 * 2^-23).  The GPU suite compares the handle's delta with such an oracle's,
     bit for bit."""
     cfg = pf.config("pcisph", "wall", 640)
-    o = pf.make_oracle(cfg)
+    o = h.make_oracle(cfg)
     d0 = F(o.pcisph_delta)
     o.close()
     m = 1000 * (0.025 ** 3) * 8
     for dt in (F(9.802e-4), F(5.1e-4), F(1.2345e-3)):
-        o = pf.make_oracle(ad.with_dt(cfg, dt))
+        o = h.make_oracle(ad.with_dt(cfg, dt))
         d = F(o.pcisph_delta)
         o.close()
         # delta scales with 1 / (float)beta: the ratio of the two deltas is the ratio of the betas to within three roundings
@@ -93,7 +94,7 @@ def test_lockstep_inputs_stay_strictly_inside_the_bounds(solver, walls):
 def test_set_dt_writes_all_three_for_every_solver():
     """Oracle.set_dt is what the GPU suite drives the oracle with: delta_time reads back, for every solver"""
     for solver in ad.SOLVERS:
-        o = pf.make_oracle(pf.config(solver, "wall", 640))
+        o = h.make_oracle(pf.config(solver, "wall", 640))
         o.set_dt(float(F(3.21e-4)))
         assert F(o.dt) == F(3.21e-4)
         o.close()

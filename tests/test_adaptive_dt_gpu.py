@@ -1,7 +1,7 @@
 """GPU suite of the adaptive time step of wcsph / pcisph / iisph / pbf handles (SPH_P_STEP_ADAPTIVE_DT / _MAX_DT / _MIN_DT; DESIGN.md section 6h;
 tests/adaptive_dt.py restates the rule, test_adaptive_dt_cpu.py shows the inputs fair on the oracle alone).
 
-Every comparison is bit for bit (particle_flow.same: np.array_equal on the u32 views; scalars through np.float32 views); no tolerance is
+Every comparison is bit for bit (harness.same_bits: np.array_equal on the u32 views; scalars through np.float32 views); no tolerance is
 involved.  Exact handles are held to the oracle driven with set_dt(dt_k) -- pcisph to a fresh oracle constructed with delta_time = dt_k --,
 relaxed and Morton handles to a fixed-step twin that gets set_dt(dt_k) between steps."""
 import os
@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import adaptive_dt as ad
+import harness as h
 import particle_flow as pf
 from cfd_taichi_amd import _native as nat
 from cfd_taichi_amd import run, scenes
@@ -18,15 +19,6 @@ from oracle import oracle as orc
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
-S_TIME, S_PS_DELTA_TIME, S_PCISPH_DELTA, S_VERLET_BUILDS = 40, 4, 6, 31
-
-
-def make(cfg, monkeypatch, env=None, arith="exact", **kw):
-    for k in pf.KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in (env or {}).items():
-        monkeypatch.setenv(k, v)
-    return nat.Simulation(nat.config_from_dict(cfg, arith=nat.arith_id(arith), **kw))
 
 
 def switch_on(sim, max_dt=None, min_dt=None):
@@ -40,20 +32,20 @@ def switch_on(sim, max_dt=None, min_dt=None):
 
 
 def same_scalar(a, b, what):
-    assert pf.u32(F(a)) == pf.u32(F(b)), "%s: %r vs %r" % (what, float(a), float(b))
+    assert h.bits(F(a)) == h.bits(F(b)), "%s: %r vs %r" % (what, float(a), float(b))
 
 
 def reported_dt(sim, dt, when):
     """the three places a handle reports the step's dt"""
     same_scalar(sim.scalar(nat.S_DELTA_TIME), dt, when + ": SPH_S_DELTA_TIME")
-    same_scalar(sim.scalar(S_PS_DELTA_TIME), dt, when + ": SPH_S_PS_DELTA_TIME")
+    same_scalar(sim.scalar(nat.S_PS_DELTA_TIME), dt, when + ": SPH_S_PS_DELTA_TIME")
     if sim.cfg.solver in (nat.SOLVER_PCISPH, nat.SOLVER_IISPH):
         same_scalar(sim.last_stats.dt, dt, when + ": SphStepStats.dt")
 
 
 def same_fields(a, b, when, fields=(nat.F_POS, nat.F_VEL, nat.F_RHO)):
     for f in fields:
-        pf.same(a.download(f), b.download(f), "%s: field %d" % (when, f))
+        h.same_bits(a.download(f), b.download(f), "%s: field %d" % (when, f))
 
 
 # ---- 1: lockstep against the oracle ----------------------------------------------------------------------------------------------------------
@@ -62,7 +54,7 @@ def same_fields(a, b, when, fields=(nat.F_POS, nat.F_VEL, nat.F_RHO)):
 def test_lockstep_against_the_oracle(solver, walls, monkeypatch):
     cfg = pf.config(solver, walls, 640)
     max_dt, min_dt = ad.bounds(solver)
-    sim, o = make(cfg, monkeypatch), pf.make_oracle(cfg)
+    sim, o = h.make_handle(cfg, monkeypatch), h.make_oracle(cfg)
     vel = ad.velocities(sim.n_fluid, ad.AMPLITUDE[solver])
     sim.upload(nat.F_VEL, vel); o.set(orc.F_VEL, vel)
     switch_on(sim, max_dt, min_dt)
@@ -72,12 +64,11 @@ def test_lockstep_against_the_oracle(solver, walls, monkeypatch):
         dt = ad.rule(sim.download(nat.F_VEL), max_dt, min_dt)
         assert F(min_dt) < dt < F(max_dt), (when, dt)                       # (test_adaptive_dt_cpu.py: never a clamped value)
         st = sim.step(1)
-        o, ot = ad.oracle_step(o, cfg, solver, dt)
+        o, ot = ad.oracle_step_dt(o, cfg, solver, dt)
         reported_dt(sim, dt, when)
         if solver == "pcisph":
-            same_scalar(sim.scalar(S_PCISPH_DELTA), o.pcisph_delta, when + ": SPH_S_PCISPH_DELTA")
-        if pf.stats_tuple(ot, solver):
-            pf.same(F(pf.stats_tuple(st, solver)), F(pf.stats_tuple(ot, solver)), when + ": statistics")
+            same_scalar(sim.scalar(nat.S_PCISPH_DELTA), o.pcisph_delta, when + ": SPH_S_PCISPH_DELTA")
+        h.same_stats(st, ot, solver, when + ": statistics")
         pf.same_state(sim, o, solver, when)
         clock += float(dt)
         assert sim.time() == clock, (when, sim.time(), clock)
@@ -89,7 +80,7 @@ def test_lockstep_against_the_oracle(solver, walls, monkeypatch):
 def test_clamps(solver, monkeypatch):
     cfg = pf.config(solver, "wall", 640)
     max_dt, min_dt = ad.bounds(solver)
-    sim = switch_on(make(cfg, monkeypatch), max_dt, min_dt)
+    sim = switch_on(h.make_handle(cfg, monkeypatch), max_dt, min_dt)
     sim.step(1)                                                             # from rest: vmax = 0, m = +inf
     reported_dt(sim, F(max_dt), solver + " from rest")
     vel = ad.velocities(sim.n_fluid, ad.AMPLITUDE[solver]) * F(8)           # dt_1 / 8 lies below min_dt = DT / 4 for every solver (dt_1 < DT)
@@ -99,7 +90,7 @@ def test_clamps(solver, monkeypatch):
     reported_dt(sim, F(min_dt), solver + " fast")
     sim.close()
     # max_dt left at its default: never above the configured step
-    sim = make(cfg, monkeypatch)
+    sim = h.make_handle(cfg, monkeypatch)
     sim.set_param("step_adaptive_dt", 1)
     assert sim.param("step_max_dt") == pf.DT[solver] and sim.param("step_min_dt") == 1e-5
     for k in range(3):                                                      # from rest: the configured step, until the rule asks for less
@@ -118,14 +109,14 @@ def test_clamps(solver, monkeypatch):
 
 # ---- 3: other sweep modes, against a host-driven twin -------------------------------------------------------------------------------------------
 # (iisph's relaxed sweeps are the staged ones: they exist on Morton cells only)
-TWINS = [("wcsph", pf.MORTON, "exact"), ("wcsph", None, "relaxed"), ("wcsph", pf.MORTON, "relaxed"), ("iisph", pf.MORTON, "exact"), ("iisph", pf.MORTON, "relaxed")]
+TWINS = [("wcsph", h.MORTON, "exact"), ("wcsph", None, "relaxed"), ("wcsph", h.MORTON, "relaxed"), ("iisph", h.MORTON, "exact"), ("iisph", h.MORTON, "relaxed")]
 
 
 @pytest.mark.parametrize("solver,env,arith", TWINS, ids=["%s-%s%s" % (s, "morton-" if e else "", a) for s, e, a in TWINS])
 def test_equals_a_host_driven_twin(solver, env, arith, monkeypatch):
     cfg = pf.config(solver, "wall", 640)
     max_dt, min_dt = ad.bounds(solver)
-    a, b = make(cfg, monkeypatch, env, arith), make(cfg, monkeypatch, env, arith)
+    a, b = h.make_handle(cfg, monkeypatch, env, arith), h.make_handle(cfg, monkeypatch, env, arith)
     if arith == "relaxed":
         assert a.scalar(nat.S_ARITH_RELAXED) == 1.0
     vel = ad.velocities(a.n_fluid, ad.AMPLITUDE[solver])
@@ -139,14 +130,13 @@ def test_equals_a_host_driven_twin(solver, env, arith, monkeypatch):
         reported_dt(a, dt, when)
         b.set_dt(float(dt))
         sb = b.step(1)
-        if pf.stats_tuple(sa, solver):
-            pf.same(F(pf.stats_tuple(sa, solver)), F(pf.stats_tuple(sb, solver)), when + ": statistics")
+        h.same_stats(sa, sb, solver, when + ": statistics")
         same_fields(a, b, when)
         dts.append(dt)
     assert len(set(float(d) for d in dts)) > 1
     assert a.time() == b.time()
     if solver == "wcsph" and arith == "relaxed":
-        assert a.scalar(S_VERLET_BUILDS) == b.scalar(S_VERLET_BUILDS) > 0
+        assert a.scalar(nat.S_VERLET_BUILDS) == b.scalar(nat.S_VERLET_BUILDS) > 0
     a.close(); b.close()
 
 
@@ -155,7 +145,7 @@ def test_equals_a_host_driven_twin(solver, env, arith, monkeypatch):
 def test_one_call_of_six_steps_equals_six_calls(solver, monkeypatch):
     cfg = pf.config(solver, "wall", 640)
     max_dt, min_dt = ad.bounds(solver)
-    a, b = make(cfg, monkeypatch), make(cfg, monkeypatch)
+    a, b = h.make_handle(cfg, monkeypatch), h.make_handle(cfg, monkeypatch)
     vel = ad.velocities(a.n_fluid, ad.AMPLITUDE[solver])
     for s in (a, b):
         s.upload(nat.F_VEL, vel)
@@ -164,7 +154,7 @@ def test_one_call_of_six_steps_equals_six_calls(solver, monkeypatch):
     for _ in range(6):
         b.step(1)
     same_fields(a, b, solver + " step(6) against 6 x step(1)")
-    for which in (nat.S_DELTA_TIME, S_PS_DELTA_TIME, S_PCISPH_DELTA):
+    for which in (nat.S_DELTA_TIME, nat.S_PS_DELTA_TIME, nat.S_PCISPH_DELTA):
         same_scalar(a.scalar(which), b.scalar(which), "scalar %d" % which)
     assert a.time() == b.time() and a.time() > 0
     if solver == "wcsph":
@@ -187,9 +177,9 @@ def test_added_particles_set_the_next_step(solver, monkeypatch):
     and recomputing the sums after the count changes is not this feature's)"""
     cfg = pf.config(solver, "wall", 640, capacity=704)
     max_dt = 2 * pf.DT[solver]
-    sim = switch_on(make(cfg, monkeypatch), max_dt)
+    sim = switch_on(h.make_handle(cfg, monkeypatch), max_dt)
     sim.step(3)
-    before = pf.fluid_state(sim, solver)
+    before = h.fluid_state(sim, solver)
     new = pf.layer_above(cfg, 640, 64)
     fast = np.tile(F([0, -20, 0]), (64, 1))
     assert sim.add_particles(new, fast) == 640 and sim.n_fluid == 704
@@ -200,12 +190,11 @@ def test_added_particles_set_the_next_step(solver, monkeypatch):
     same_scalar(dt, F(F(F(0.4 * 0.025 * 2) / F(20)) * F(0.2)), "the rule's value for 20 m/s")
     assert F(1e-5) < dt < F(max_dt) and dt != F(before["dt"])
     cfg704 = pf.config(solver, "wall", 704)
-    o = pf.give(pf.make_oracle(cfg704), st, solver)
+    o = h.give(h.make_oracle(cfg704), st, solver)
     stats = sim.step(1)
-    o, ot = ad.oracle_step(o, cfg704, solver, dt)
+    o, ot = ad.oracle_step_dt(o, cfg704, solver, dt)
     reported_dt(sim, dt, solver + " after add_particles")
-    if pf.stats_tuple(ot, solver):
-        pf.same(F(pf.stats_tuple(stats, solver)), F(pf.stats_tuple(ot, solver)), "statistics")
+    h.same_stats(stats, ot, solver, "statistics")
     pf.same_state(sim, o, solver, solver + " after add_particles")
     sim.close(); o.close()
 
@@ -219,7 +208,7 @@ def test_with_a_body(solver):
     radius = cfg["scene"]["particle_radius"]
     max_dt, min_dt = 2 * rr.DT[solver], rr.DT[solver] / 64                 # (the amplitudes of the lockstep cases: dt_1 just under DT)
     sim = nat.Simulation(nat.config_from_dict(cfg), rigid=rr.rigid(cfg))
-    o = rr.make_oracle(cfg, solver)
+    o = rr.body_oracle(cfg, solver)
     vel = ad.velocities(sim.n_fluid, ad.AMPLITUDE[solver])
     sim.upload(nat.F_VEL, vel); o.set(orc.F_VEL, vel)
     switch_on(sim, max_dt, min_dt)
@@ -233,11 +222,11 @@ def test_with_a_body(solver):
         terms.append(float(term))
         st = sim.step(1)
         o.set_dt(float(dt))
-        ot = rr.oracle_step(o, solver)
+        ot = h.oracle_step(o, solver)
         reported_dt(sim, dt, when)
-        if rr.stats_tuple(ot, solver):
-            assert rr.stats_tuple(st, solver) == rr.stats_tuple(ot, solver), when
-        pf.same(sim.download(nat.F_RIGID_FORCE, nat.SPECIES_RIGID), o.get(orc.F_RIGID_FORCE), when + ": force on the body")
+        if h.stats_tuple(ot, solver):
+            assert h.stats_tuple(st, solver) == h.stats_tuple(ot, solver), when
+        h.same_bits(sim.download(nat.F_RIGID_FORCE, nat.SPECIES_RIGID), o.get(orc.F_RIGID_FORCE), when + ": force on the body")
         sim.rigid_step(); o.rigid_step()                                   # both take ps.delta_time = dt_k
         check_rigid(sim, o, "after rigid " + when, nan_aware=False)
         pf.same_state(sim, o, solver, when)
@@ -246,36 +235,30 @@ def test_with_a_body(solver):
 
 
 # ---- 7: refusals leave the handle unchanged ----------------------------------------------------------------------------------------------------
-def refused(sim, name, value, code):
-    with pytest.raises(nat.SphError) as e:
-        sim.set_param(name, value)
-    assert e.value.code == code, (name, value, e.value.code)
-
-
 def test_refusals_leave_the_handle_unchanged(monkeypatch):
     # a dfsph handle has 70-72
     cfg = pf.config("dfsph", "wall", 640)
-    a, b = make(cfg, monkeypatch), make(cfg, monkeypatch)
+    a, b = h.make_handle(cfg, monkeypatch), h.make_handle(cfg, monkeypatch)
     for name, value in (("step_adaptive_dt", 1), ("step_max_dt", 5e-4), ("step_min_dt", 1e-4)):
-        refused(a, name, value, nat.SPH_E_STATE)
+        h.refused(nat.SPH_E_STATE, lambda: a.set_param(name, value))
     for s in range(3):
         sa, sb = a.step(1), b.step(1)
-        pf.same(F(pf.stats_tuple(sa, "dfsph")), F(pf.stats_tuple(sb, "dfsph")), "dfsph step %d: statistics" % (s + 1))
+        h.same_stats(sa, sb, "dfsph", "dfsph step %d: statistics" % (s + 1))
     same_fields(a, b, "dfsph after refused calls", (nat.F_POS, nat.F_VEL, nat.F_RHO, nat.F_WARM_K))
     a.close(); b.close()
     # a slab handle (its ranks would need a max all-reduce)
     cfg = pf.config("wcsph", "wall", 640)
-    for k in pf.KNOBS:
+    for k in h.KNOBS:
         monkeypatch.delenv(k, raising=False)
     slab = nat.Simulation(nat.config_from_dict(cfg, slab_rank=0, slab_count=2))
     for name, value in (("step_adaptive_dt", 1), ("step_max_dt", 5e-4), ("step_min_dt", 1e-4)):
-        refused(slab, name, value, nat.SPH_E_STATE)
+        h.refused(nat.SPH_E_STATE, lambda: slab.set_param(name, value))
     assert (slab.param("step_adaptive_dt"), slab.param("step_max_dt"), slab.param("step_min_dt")) == (0.0, pf.DT["wcsph"], 1e-5)
     slab.close()
     # bounds that are not finite or not positive, a flag that is neither 0 nor 1
     for solver in ("wcsph", "pcisph"):
         cfg = pf.config(solver, "wall", 640)
-        a, b = make(cfg, monkeypatch), make(cfg, monkeypatch)
+        a, b = h.make_handle(cfg, monkeypatch), h.make_handle(cfg, monkeypatch)
         vel = ad.velocities(a.n_fluid, ad.AMPLITUDE[solver])
         max_dt, min_dt = ad.bounds(solver)
         for s in (a, b):
@@ -283,9 +266,9 @@ def test_refusals_leave_the_handle_unchanged(monkeypatch):
             switch_on(s, max_dt, min_dt)
         for name in ("step_max_dt", "step_min_dt"):
             for value in (0.0, -1e-3, float("nan"), float("inf"), -float("inf")):
-                refused(a, name, value, nat.SPH_E_INVALID)
+                h.refused(nat.SPH_E_INVALID, lambda: a.set_param(name, value))
         for value in (2.0, -1.0, 0.5, float("nan")):
-            refused(a, "step_adaptive_dt", value, nat.SPH_E_INVALID)
+            h.refused(nat.SPH_E_INVALID, lambda: a.set_param("step_adaptive_dt", value))
         assert (a.param("step_adaptive_dt"), a.param("step_max_dt"), a.param("step_min_dt")) == (1.0, max_dt, min_dt)
         a.step(4); b.step(4)
         same_fields(a, b, solver + " after refused calls")
@@ -298,20 +281,19 @@ def test_refusals_leave_the_handle_unchanged(monkeypatch):
 @pytest.mark.parametrize("solver", ad.SOLVERS)
 def test_on_and_off_again_before_the_first_step_is_invisible(solver, monkeypatch):
     cfg = pf.config(solver, "wall", 640)
-    a, b = make(cfg, monkeypatch), make(cfg, monkeypatch)
+    a, b = h.make_handle(cfg, monkeypatch), h.make_handle(cfg, monkeypatch)
     vel = ad.velocities(a.n_fluid, ad.AMPLITUDE[solver])
     a.upload(nat.F_VEL, vel); b.upload(nat.F_VEL, vel)
-    delta = a.scalar(S_PCISPH_DELTA)
+    delta = a.scalar(nat.S_PCISPH_DELTA)
     switch_on(a, *ad.bounds(solver))
     a.set_param("step_adaptive_dt", 0)
-    assert a.param("step_adaptive_dt") == 0.0 and a.scalar(S_PCISPH_DELTA) == delta
+    assert a.param("step_adaptive_dt") == 0.0 and a.scalar(nat.S_PCISPH_DELTA) == delta
     for s in range(5):
         sa, sb = a.step(1), b.step(1)
-        if pf.stats_tuple(sa, solver):
-            pf.same(F(pf.stats_tuple(sa, solver)), F(pf.stats_tuple(sb, solver)), "step %d: statistics" % (s + 1))
+        h.same_stats(sa, sb, solver, "step %d: statistics" % (s + 1))
         same_fields(a, b, "%s step %d" % (solver, s + 1))
         assert a.scalar(nat.S_DELTA_TIME) == b.scalar(nat.S_DELTA_TIME) == float(F(pf.DT[solver]))
-    assert a.time() == b.time() and a.scalar(S_PS_DELTA_TIME) == b.scalar(S_PS_DELTA_TIME)
+    assert a.time() == b.time() and a.scalar(nat.S_PS_DELTA_TIME) == b.scalar(nat.S_PS_DELTA_TIME)
     a.close(); b.close()
 
 
@@ -321,7 +303,7 @@ def test_switching_off_keeps_the_last_step(solver, monkeypatch):
     oracle constructed with it)"""
     cfg = pf.config(solver, "wall", 640)
     max_dt, min_dt = ad.bounds(solver)
-    sim, o = make(cfg, monkeypatch), pf.make_oracle(cfg)
+    sim, o = h.make_handle(cfg, monkeypatch), h.make_oracle(cfg)
     vel = ad.velocities(sim.n_fluid, ad.AMPLITUDE[solver])
     sim.upload(nat.F_VEL, vel); o.set(orc.F_VEL, vel)
     switch_on(sim, max_dt, min_dt)
@@ -329,15 +311,15 @@ def test_switching_off_keeps_the_last_step(solver, monkeypatch):
     for k in range(3):
         dt = ad.rule(sim.download(nat.F_VEL), max_dt, min_dt)
         sim.step(1)
-        o, _ = ad.oracle_step(o, cfg, solver, dt)
-    delta = sim.scalar(S_PCISPH_DELTA)
+        o, _ = ad.oracle_step_dt(o, cfg, solver, dt)
+    delta = sim.scalar(nat.S_PCISPH_DELTA)
     sim.set_param("step_adaptive_dt", 0)
     same_scalar(sim.scalar(nat.S_DELTA_TIME), dt, "dt after the switch")
-    assert sim.scalar(S_PCISPH_DELTA) == delta
+    assert sim.scalar(nat.S_PCISPH_DELTA) == delta
     for k in range(3):
         st = sim.step(1)
-        ot = pf.oracle_step(o, solver)                                      # the oracle keeps dt (pcisph: and the delta of its construction with dt)
-        pf.same(F(pf.stats_tuple(st, solver)), F(pf.stats_tuple(ot, solver)), "fixed step %d: statistics" % (k + 1))
+        ot = h.oracle_step(o, solver)                                      # the oracle keeps dt (pcisph: and the delta of its construction with dt)
+        h.same_stats(st, ot, solver, "fixed step %d: statistics" % (k + 1))
         same_scalar(st.dt, dt, "SphStepStats.dt")
     pf.same_state(sim, o, solver, solver + " three fixed steps after the switch")
     sim.close(); o.close()
@@ -345,7 +327,7 @@ def test_switching_off_keeps_the_last_step(solver, monkeypatch):
 
 # ---- 9: the shipped scene ----------------------------------------------------------------------------------------------------------------------------
 def test_shipped_scene_through_the_runner(monkeypatch, capsys):
-    for k in pf.KNOBS:
+    for k in h.KNOBS:
         monkeypatch.delenv(k, raising=False)
     frames, t, _ = run.main(["--config", os.path.join(ROOT, "config", "dam_adaptive_iisph.json"), "--steps", "150"])
     capsys.readouterr()

@@ -6,6 +6,7 @@ import pytest
 
 from cfd_taichi_amd import _native as nat
 from cfd_taichi_amd import mesh, scenes
+from harness import same_values
 from oracle import oracle as orc
 
 
@@ -39,11 +40,11 @@ def scenario(lib, scene, steps):
     return seen
 
 
-def assert_same(a, b):
+def same_scenarios(a, b):
     assert a.keys() == b.keys()
     for k in a:
         if isinstance(a[k], np.ndarray):
-            assert np.array_equal(a[k], b[k]), k
+            same_values(a[k], b[k], k)
         elif isinstance(a[k], dict):
             assert {n: np.float32(v).tolist() for n, v in a[k].items()} == {n: np.float32(v).tolist() for n, v in b[k].items()}, k
         else:
@@ -82,4 +83,4 @@ def test_solver_attributes_through_the_abi_on_the_oracle_backend():
 @pytest.mark.parametrize("scene,steps", [("dfsph_small", 12), ("wcsph_tiny_wall", 40), ("dfsph_tiny_wall_pcisph", 15), ("dfsph_tiny_wall_iisph", 15),
                                          ("pbf_tiny_wall", 30), ("dfsph_rigid_small", 25)])
 def test_same_scenario_on_both_backends(scene, steps):
-    assert_same(scenario(None, scene, steps), scenario(nat.bind_core(orc.ABI_LIB), scene, steps))
+    same_scenarios(scenario(None, scene, steps), scenario(nat.bind_core(orc.ABI_LIB), scene, steps))

@@ -14,17 +14,14 @@ of the positive density errors (taken over exactly those particles, :139-149) un
 iteration cap (:225), would not return on this scene.  Library and oracle both stop at the reported cap (max_density_iters, 100) and
 agree on every step's iteration count; the test asserts that every particle that keeps rho* > rho_0 lies within two support radii of
 the body."""
-import json
 import os
-import socket
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from cfd_taichi_amd import _native as nat
 from cfd_taichi_amd import mesh, scenes
+from harness import run_ranks, same_values
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -40,13 +37,6 @@ def cores():
     except Exception:
         pass
     return n
-
-
-def same(a, b, what):
-    a, b = np.asarray(a), np.asarray(b)
-    if not np.array_equal(a, b):
-        bad = np.argwhere(a != b)
-        raise AssertionError("%s differs at %d of %d entries, first %s: %r vs %r" % (what, len(bad), a.size, bad[0], a[tuple(bad[0])], b[tuple(bad[0])]))
 
 
 def stuck_particles_near_body(sim, h):
@@ -88,16 +78,16 @@ def test_config5_coupling_demo_dfsph_against_oracle():
             n_stuck, far = stuck_particles_near_body(sim, 0.1)
             assert 0 < n_stuck < 0.02 * sim.n_fluid and far <= 2.0, (s, n_stuck, far)
         if s % 10 == 0:
-            same(sim.download(nat.F_RIGID_FORCE, nat.SPECIES_RIGID), o.get(orc.F_RIGID_FORCE), "force on the body, step %d" % s)
-            same(sim.download(nat.F_RHO_ADV), o.get(orc.F_RHO_ADV), "rho_adv, step %d" % s)
+            same_values(sim.download(nat.F_RIGID_FORCE, nat.SPECIES_RIGID), o.get(orc.F_RIGID_FORCE), "force on the body, step %d" % s)
+            same_values(sim.download(nat.F_RHO_ADV), o.get(orc.F_RHO_ADV), "rho_adv, step %d" % s)
         sim.rigid_step()
         o.rigid_step()
         a, b = sim.rigid_scalars(), o.rigid_scalars()
         for k in ("centroid", "omega", "vel", "inertia_inv"):
-            same(np.float32(a[k]), np.float32(b[k]), "%s after step %d" % (k, s))
-    same(sim.download(nat.F_POS), o.get(orc.F_POS), "fluid positions")
-    same(sim.download(nat.F_VEL), o.get(orc.F_VEL), "fluid velocities")
-    same(sim.download(nat.F_RIGID_POS, nat.SPECIES_RIGID), o.get(orc.F_RIGID_POS), "rigid positions")
+            same_values(np.float32(a[k]), np.float32(b[k]), "%s after step %d" % (k, s))
+    same_values(sim.download(nat.F_POS), o.get(orc.F_POS), "fluid positions")
+    same_values(sim.download(nat.F_VEL), o.get(orc.F_VEL), "fluid velocities")
+    same_values(sim.download(nat.F_RIGID_POS, nat.SPECIES_RIGID), o.get(orc.F_RIGID_POS), "rigid positions")
     # the oracle runs into the cap as well: the body is placed inside the water column's face (module docstring)
     assert capped_steps > 0 and max(n_dens) == 100, n_dens
     print("config 5 (coupling_demo_dfsph): n_dens per step %s, %d of 16 steps at the cap" % (n_dens, capped_steps))
@@ -194,24 +184,14 @@ def test_config4_dfsph_10m_single_gpu_properties():
     sim.close()
 
 
-def free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
 @pytest.mark.parametrize("world", [4])          # (2 slabs: tools/soak_slabs.sh; 8 slabs at 1 M: test_native_transport_on_the_loopback_stand_in)
 def test_config4_dfsph_10m_on_slabs(tmp_path, world):
     """Config 4 sharded into 2 and 4 x-slabs (ghost exchange, migration, all-reduced residuals; the ranks share this box's GPU and
     talk over gloo): 3 steps, every owned particle equal to the one-GPU run byte for byte, iteration counts and residuals included."""
     out = tmp_path / ("slab10m_%d.json" % world)
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
-           "--master-port", str(free_port()), os.path.join(ROOT, "tests", "slab_worker.py"), "--scene", "dfsph_10m", "--steps", "3",
-           "--backend", "gloo", "--rebalance", "0", "--out", str(out)]
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2")
-    p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
-    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
-    r = json.loads(out.read_text())
+    # (SPH_SLAB_CHECK=0, off as it always was here: its eight blocking read-backs per step are for the small scenes)
+    r = run_ranks(os.path.join(ROOT, "tests", "slab_worker.py"), ("--scene", "dfsph_10m", "--steps", 3, "--backend", "gloo", "--rebalance", 0, "--out", out),
+                  world, "gloo", out, {"SPH_SLAB_CHECK": "0"}, timeout=900)
     assert r["n"] == 10000000 and sum(s["owned"] for s in r["slabs"]) == r["n"]
     assert r["pos_equal"] and r["vel_equal"] and r["rho_equal"], {k: r[k] for k in ("pos_rel_err", "vel_rel_err", "slabs")}
     assert r["stats_equal"], (r["stats_last"], r["ref_stats_last"])

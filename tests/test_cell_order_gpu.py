@@ -15,8 +15,9 @@ import pytest
 
 from cfd_taichi_amd import _native as nat
 from cfd_taichi_amd import mesh, scenes
+from harness import make_handle, squeeze
 from oracle import oracle as orc
-from test_fuzz_gpu import PBF_FIELDS, random_scene, squeeze_both
+from test_fuzz_gpu import PBF_FIELDS, random_scene
 from test_slab_gpu import run_slabs
 
 pytestmark = pytest.mark.gpu
@@ -24,10 +25,9 @@ pytestmark = pytest.mark.gpu
 FIELDS = (nat.F_POS, nat.F_VEL, nat.F_RHO)
 
 
-def make(cfg, order, monkeypatch, tile="4", rigid=None):
-    monkeypatch.setenv("SPH_CELL_ORDER", order)
-    monkeypatch.setenv("SPH_CELL_TILE", tile)
-    return nat.Simulation(nat.config_from_dict(cfg), rigid=rigid)
+def make(cfg, order, monkeypatch, tile="4", rigid=None, env=None):
+    """a handle with its cells in `order` (tile: the Morton tile) and the further overrides `env`, every other one cleared"""
+    return make_handle(cfg, monkeypatch, dict(env or {}, SPH_CELL_ORDER=order, SPH_CELL_TILE=tile), rigid=rigid)
 
 
 @pytest.mark.parametrize("scene,steps,tile", [("wcsph_small", 80, "4"), ("dfsph_small", 40, "4"), ("dfsph_tiny_wall", 60, "16"), ("wcsph_tiny_wall", 120, "16"),
@@ -81,7 +81,7 @@ def test_random_scene_on_the_morton_curve_matches_oracle(solver, seed, monkeypat
     sim = make(cfg, "morton", monkeypatch)
     o = orc.Oracle(cfg, solver=solver, num_threads=4)
     if solver == "pbf":
-        squeeze_both(sim, o)
+        squeeze(sim, o)
     lambda_active = 0
     for s in range(25):
         sim.step(1)
@@ -131,11 +131,8 @@ def test_lds_staging_is_invisible(scene, steps, cap, monkeypatch):
     scenes stages more than 1792 particles in a workgroup, the second trip of the staging loops, is not established: that trip, the trip
     boundary and the clamp are covered by tests/test_stage_gpu.py, which runs the routine on plans of up to 2560 particles directly."""
     cfg = scenes.get(scene)
-    monkeypatch.setenv("SPH_STAGE", "1")
-    monkeypatch.setenv("SPH_STAGE_CAP", cap)
-    a = make(cfg, "morton", monkeypatch)
-    monkeypatch.setenv("SPH_STAGE", "0")
-    b = make(cfg, "morton", monkeypatch)
+    a = make(cfg, "morton", monkeypatch, env={"SPH_STAGE": "1", "SPH_STAGE_CAP": cap})
+    b = make(cfg, "morton", monkeypatch, env={"SPH_STAGE": "0", "SPH_STAGE_CAP": cap})
     for s_ in range(steps):
         sa, sb = a.step(1), b.step(1)
         assert (sa.n_div, sa.n_dens, sa.div_err, sa.dens_err, sa.dt, sa.max_nbrs) == (sb.n_div, sb.n_dens, sb.div_err, sb.dens_err, sb.dt, sb.max_nbrs), (scene, s_)
@@ -149,12 +146,9 @@ def test_list_and_scalar_formats_are_invisible(cap, monkeypatch):
     """The storage formats of the staged DFSPH sweeps -- 16-bit local list indices (SPH_NL16) and k / rho in its own 4-byte array
     (SPH_KR_SPLIT) -- change no bit: all on, the scalar array off, both off, at a capacity where staged and unstaged workgroups mix."""
     cfg = scenes.get("breaking_dam_30k_dfsph")
-    monkeypatch.setenv("SPH_STAGE_CAP", cap)
     sims = []
     for nl16, split in (("1", "1"), ("1", "0"), ("0", "0")):
-        monkeypatch.setenv("SPH_NL16", nl16)
-        monkeypatch.setenv("SPH_KR_SPLIT", split)
-        sims.append(make(cfg, "morton", monkeypatch))
+        sims.append(make(cfg, "morton", monkeypatch, env={"SPH_STAGE_CAP": cap, "SPH_NL16": nl16, "SPH_KR_SPLIT": split}))
     for s_ in range(15):
         st = [sim.step(1) for sim in sims]
         for other in st[1:]:
@@ -174,12 +168,9 @@ def test_list_and_scalar_formats_with_a_rigid_body(scene, steps, cap, monkeypatc
     array off, both off: coupled steps, force on the body and body state included."""
     cfg = scenes.get(scene)
     rg = mesh.rigid_from_config(cfg)
-    monkeypatch.setenv("SPH_STAGE_CAP", cap)
     sims = []
     for nl16, split in (("1", "1"), ("1", "0"), ("0", "0")):
-        monkeypatch.setenv("SPH_NL16", nl16)
-        monkeypatch.setenv("SPH_KR_SPLIT", split)
-        sims.append(make(cfg, "morton", monkeypatch, rigid=rg))
+        sims.append(make(cfg, "morton", monkeypatch, rigid=rg, env={"SPH_STAGE_CAP": cap, "SPH_NL16": nl16, "SPH_KR_SPLIT": split}))
     for s_ in range(steps):
         st = [sim.step_dfsph(1) for sim in sims]
         for other in st[1:]:
@@ -342,11 +333,8 @@ def test_lds_staging_with_a_rigid_body(cap, monkeypatch):
     """Tagged rigid entries stay global inside staged lists; the coupled run equals the unstaged one, body included."""
     cfg = scenes.get("dfsph_rigid_small")
     rg = mesh.rigid_from_config(cfg)
-    monkeypatch.setenv("SPH_STAGE", "1")
-    monkeypatch.setenv("SPH_STAGE_CAP", cap)
-    a = make(cfg, "morton", monkeypatch, rigid=rg)
-    monkeypatch.setenv("SPH_STAGE", "0")
-    b = make(cfg, "morton", monkeypatch, rigid=rg)
+    a = make(cfg, "morton", monkeypatch, rigid=rg, env={"SPH_STAGE": "1", "SPH_STAGE_CAP": cap})
+    b = make(cfg, "morton", monkeypatch, rigid=rg, env={"SPH_STAGE": "0", "SPH_STAGE_CAP": cap})
     for s_ in range(100):
         sa, sb = a.step_dfsph(1), b.step_dfsph(1)
         assert (sa.n_div, sa.n_dens, sa.div_err, sa.dens_err, sa.dt) == (sb.n_div, sb.n_dens, sb.div_err, sb.dens_err, sb.dt), s_
@@ -367,10 +355,8 @@ def test_lds_staging_with_particles_outside_the_box(solver, monkeypatch):
     hung the plan's look-up).  A few particles are put just outside each face of the box; staged and unstaged runs must agree."""
     cfg = scenes.get("dfsph_tiny_clamp")
     cfg["solver"]["name"] = solver
-    monkeypatch.setenv("SPH_STAGE", "1")
-    a = make(cfg, "morton", monkeypatch)
-    monkeypatch.setenv("SPH_STAGE", "0")
-    b = make(cfg, "morton", monkeypatch)
+    a = make(cfg, "morton", monkeypatch, env={"SPH_STAGE": "1"})
+    b = make(cfg, "morton", monkeypatch, env={"SPH_STAGE": "0"})
     pos = a.download(nat.F_POS)
     box = np.asarray(cfg["scene"]["box_max"], dtype=np.float32)
     h = np.float32(4 * cfg["scene"]["particle_radius"])

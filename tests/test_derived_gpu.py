@@ -12,6 +12,7 @@ import pytest
 
 import derived_ref as dr
 import midrun_calls as mc
+import harness as h
 import particle_flow as pf
 from cfd_taichi_amd import _native as nat
 from cfd_taichi_amd import mesh, run, scenes
@@ -20,19 +21,10 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 D = 0.05
-S_TIME = 40
 BIG = 1e6
 NAMES = tuple(name for name, _, _ in dr.QUANTITIES)
-PLAIN = dict(mc.LINEAR, SPH_QUAD="0")
-LAYOUTS = {"plain": PLAIN, "quad": None, "morton": pf.MORTON}
-
-
-def make(cfg, monkeypatch, env=None, arith="exact", **kw):
-    for k in pf.KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in (env or {}).items():
-        monkeypatch.setenv(k, v)
-    return nat.Simulation(nat.config_from_dict(cfg, arith=nat.arith_id(arith), **kw))
+PLAIN = dict(h.LINEAR, SPH_QUAD="0")
+LAYOUTS = {"plain": PLAIN, "quad": None, "morton": h.MORTON}
 
 
 def disturb(sim, seed):
@@ -60,7 +52,7 @@ def against_a(sim, cfg, when):
     st = state_of(sim, cfg)
     want = dr.yardstick_a(st, dr.canonical_lists(dr.Cells(cfg, st.h), st))
     for name, first, width in dr.QUANTITIES:
-        pf.same(got[:, first:first + width], want[:, first:first + width], "%s: %s against yardstick A" % (when, name))
+        h.same_bits(got[:, first:first + width], want[:, first:first + width], "%s: %s against yardstick A" % (when, name))
     return got
 
 
@@ -73,20 +65,20 @@ SEEN = {}            # (solver, walls) -> {layout: (n, 17)}: what the cases of (
 @pytest.mark.parametrize("solver", pf.SOLVERS)
 def test_bit_for_bit_against_yardstick_a(solver, walls, layout, monkeypatch):
     cfg = pf.config(solver, walls, 640)
-    sim = make(cfg, monkeypatch, LAYOUTS[layout])
+    sim = h.make_handle(cfg, monkeypatch, LAYOUTS[layout])
     disturb(sim, 21)
     got = against_a(sim, cfg, "%s %s %s" % (solver, walls, layout))
     assert np.abs(got[:, 0:9]).max() > 1.0 and np.abs(got[:, 13:16]).max() > 1.0 and got[:, 16].max() > 0.9        # (not a field of zeros)
     SEEN.setdefault((solver, walls), {})[layout] = got
     for other, earlier in SEEN[(solver, walls)].items():
-        pf.same(got, earlier, "%s %s: layout %s against layout %s" % (solver, walls, layout, other))
+        h.same_bits(got, earlier, "%s %s: layout %s against layout %s" % (solver, walls, layout, other))
     sim.close()
 
 
-@pytest.mark.parametrize("solver,env", [("dfsph", pf.MORTON), ("dfsph", mc.LINEAR), ("pbf", mc.LINEAR)], ids=["dfsph-morton", "dfsph-linear", "pbf-linear"])
+@pytest.mark.parametrize("solver,env", [("dfsph", h.MORTON), ("dfsph", h.LINEAR), ("pbf", h.LINEAR)], ids=["dfsph-morton", "dfsph-linear", "pbf-linear"])
 def test_relaxed_handles_use_the_exact_kernel_functions(solver, env, monkeypatch):
     cfg = pf.config(solver, "wall", 640)
-    sim = make(cfg, monkeypatch, env, arith="relaxed")
+    sim = h.make_handle(cfg, monkeypatch, env, arith="relaxed")
     disturb(sim, 22)
     against_a(sim, cfg, "relaxed %s" % solver)
     sim.step(3)
@@ -99,14 +91,14 @@ def test_layouts_agree_nl16_off_and_a_mixed_handle(monkeypatch):
     """640 particles, dfsph on Morton cells: 16-bit lists (the default), 32-bit lists (SPH_NL16=0), and a capacity at which no workgroup is staged"""
     cfg = pf.config("dfsph", "wall", 640)
     got = {}
-    for name, env in (("linear", mc.LINEAR), ("nl16", pf.MORTON), ("nl32", dict(pf.MORTON, SPH_NL16="0")), ("cap64", dict(pf.MORTON, SPH_STAGE_CAP="64"))):
-        sim = make(cfg, monkeypatch, env)
+    for name, env in (("linear", h.LINEAR), ("nl16", h.MORTON), ("nl32", dict(h.MORTON, SPH_NL16="0")), ("cap64", dict(h.MORTON, SPH_STAGE_CAP="64"))):
+        sim = h.make_handle(cfg, monkeypatch, env)
         disturb(sim, 23)
         sim.step(2)
         got[name] = derived17(sim)
         sim.close()
     for name in ("nl16", "nl32", "cap64"):
-        pf.same(got[name], got["linear"], "640 particles, %s against linear cells" % name)
+        h.same_bits(got[name], got["linear"], "640 particles, %s against linear cells" % name)
 
 
 def test_layouts_agree_on_many_workgroups(monkeypatch):
@@ -114,8 +106,8 @@ def test_layouts_agree_on_many_workgroups(monkeypatch):
     one handle, as tests/test_relaxed_sweeps_gpu.py selects them)"""
     cfg = scenes.get("dfsph_small")
     got = {}
-    for name, env in (("linear", mc.LINEAR), ("morton", pf.MORTON), ("nl32", dict(pf.MORTON, SPH_NL16="0")), ("mixed", dict(pf.MORTON, SPH_STAGE_CAP="300"))):
-        sim = make(cfg, monkeypatch, env)
+    for name, env in (("linear", h.LINEAR), ("morton", h.MORTON), ("nl32", dict(h.MORTON, SPH_NL16="0")), ("mixed", dict(h.MORTON, SPH_STAGE_CAP="300"))):
+        sim = h.make_handle(cfg, monkeypatch, env)
         assert sim.n_fluid == 5879
         disturb(sim, 24)
         sim.step(2)
@@ -123,14 +115,14 @@ def test_layouts_agree_on_many_workgroups(monkeypatch):
         sim.close()
     assert np.abs(got["linear"][:, 9:12]).max() > 1.0
     for name in ("morton", "nl32", "mixed"):
-        pf.same(got[name], got["linear"], "5.9 k particles, %s against linear cells" % name)
+        h.same_bits(got[name], got["linear"], "5.9 k particles, %s against linear cells" % name)
 
 
 # ---- 3: ragged counts ------------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("solver,env", [("wcsph", None), ("dfsph", pf.MORTON)], ids=["wcsph", "dfsph-morton"])
+@pytest.mark.parametrize("solver,env", [("wcsph", None), ("dfsph", h.MORTON)], ids=["wcsph", "dfsph-morton"])
 def test_677_particles_after_add_particles(solver, env, monkeypatch):
     cfg = pf.config(solver, "wall", 640, capacity=704)
-    sim = make(cfg, monkeypatch, env)
+    sim = h.make_handle(cfg, monkeypatch, env)
     sim.step(2)
     before = sim.derived("cover")
     assert sim.add_particles(pf.layer_above(cfg, 640, 37), np.tile(F([0.25, -1, 0.5]), (37, 1))) == 640 and sim.n_fluid == 677
@@ -173,7 +165,7 @@ def shrink_to(sim, survivors):
 @pytest.mark.parametrize("survivors", [1, 63, 64, 65])
 def test_small_counts_after_remove_in_box(survivors, monkeypatch):
     cfg = pf.config("wcsph", "clamp", 640)           # (no wall samples: a lone particle has no neighbour of any kind)
-    sim = make(cfg, monkeypatch)
+    sim = h.make_handle(cfg, monkeypatch)
     sim.derived("velgrad")                            # the feature's memory exists before the count shrinks
     shrink_to(sim, survivors)
     disturb(sim, 30 + survivors)
@@ -189,7 +181,7 @@ def test_small_counts_after_remove_in_box(survivors, monkeypatch):
 # ---- 4: a Verlet handle between two builds ----------------------------------------------------------------------------------------------------------
 def test_verlet_lists_with_pairs_beyond_h(monkeypatch):
     cfg = pf.config("wcsph", "wall", 640)
-    sim = make(cfg, monkeypatch, arith="relaxed")
+    sim = h.make_handle(cfg, monkeypatch, arith="relaxed")
     assert sim.scalar(nat.S_ARITH_RELAXED) == 1.0
     disturb(sim, 41)
     at_build = sim.download(nat.F_POS)               # the upload asks for a rebuild: the next step's lists are built from these positions
@@ -199,13 +191,13 @@ def test_verlet_lists_with_pairs_beyond_h(monkeypatch):
     got = derived17(sim)
     assert sim.scalar(nat.S_VERLET_BUILDS) == builds, "the lists were rebuilt: no stale list was walked"
     st = state_of(sim, cfg)
-    h = float(st.h)
+    sup = float(st.h)
     d0 = np.linalg.norm(at_build[:, None, :].astype(np.float64) - at_build[None, :, :], axis=2)
     d1 = np.linalg.norm(st.pos[:, None, :].astype(np.float64) - st.pos[None, :, :], axis=2)
-    beyond = int(((d0 <= 1.04 * h) & (d1 > h * (1 + 1e-6))).sum())          # listed (the skin is 0.05 h), and now outside the support
+    beyond = int(((d0 <= 1.04 * sup) & (d1 > sup * (1 + 1e-6))).sum())          # listed (the skin is 0.05 h), and now outside the support
     moved = float(np.abs(st.pos - at_build).max())
-    print("Verlet handle: %d listed pairs beyond h, largest move %.3e (skin / 2 = %.3e)" % (beyond, moved, 0.025 * h))
-    assert beyond > 0 and 0 < moved < 0.025 * h
+    print("Verlet handle: %d listed pairs beyond h, largest move %.3e (skin / 2 = %.3e)" % (beyond, moved, 0.025 * sup))
+    assert beyond > 0 and 0 < moved < 0.025 * sup
     val, bnd = dr.yardstick_b(st)
     ratio = dr.worst_ratio(got, val, bnd)
     print("Verlet handle: worst error / bound %.3f" % ratio)
@@ -216,7 +208,7 @@ def test_verlet_lists_with_pairs_beyond_h(monkeypatch):
 # ---- 5: a body -----------------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("mode", ["coupled", "one-way", "inactive"])
 def test_a_body_enters_normal_and_cover_only_when_coupled(mode, monkeypatch):
-    for k in pf.KNOBS:
+    for k in h.KNOBS:
         monkeypatch.delenv(k, raising=False)
     cfg = scenes.get("dfsph_rigid_small")
     if mode == "one-way":
@@ -259,17 +251,17 @@ def test_a_body_enters_normal_and_cover_only_when_coupled(mode, monkeypatch):
 def same_handles(a, b, solver, when):
     fields = (nat.F_POS, nat.F_VEL, nat.F_RHO) + ((nat.F_WARM_K,) if solver == "dfsph" else ()) + ((nat.F_PRESS_ITER,) if solver in ("pcisph", "iisph") else ())
     for f in fields:
-        pf.same(a.download(f), b.download(f), "%s: field %d" % (when, f))
-    for which in mc.SCALARS + (S_TIME,):
+        h.same_bits(a.download(f), b.download(f), "%s: field %d" % (when, f))
+    for which in mc.SCALARS + (nat.S_TIME,):
         sa, sb = np.float64(a.scalar(which)), np.float64(b.scalar(which))
         assert sa.view(np.uint64) == sb.view(np.uint64), "%s: scalar %d is %r, the twin's %r" % (when, which, float(sa), float(sb))
 
 
-@pytest.mark.parametrize("solver,env", [("wcsph", None), ("dfsph", pf.MORTON), ("pcisph", None), ("iisph", pf.MORTON), ("pbf", None)],
+@pytest.mark.parametrize("solver,env", [("wcsph", None), ("dfsph", h.MORTON), ("pcisph", None), ("iisph", h.MORTON), ("pbf", None)],
                          ids=["wcsph", "dfsph-morton", "pcisph", "iisph-morton", "pbf"])
 def test_calling_between_steps_is_invisible(solver, env, monkeypatch):
     cfg = pf.config(solver, "wall", 640)
-    a, b = make(cfg, monkeypatch, env), make(cfg, monkeypatch, env)
+    a, b = h.make_handle(cfg, monkeypatch, env), h.make_handle(cfg, monkeypatch, env)
     for k in range(10):
         if k % 3 != 2:
             a.derived(NAMES[k % 5])
@@ -284,7 +276,7 @@ def test_calling_between_steps_is_invisible(solver, env, monkeypatch):
 
 def test_calling_is_invisible_across_a_replayed_wcsph_call(monkeypatch):
     cfg = pf.config("wcsph", "wall", 640)
-    a, b = make(cfg, monkeypatch), make(cfg, monkeypatch)
+    a, b = h.make_handle(cfg, monkeypatch), h.make_handle(cfg, monkeypatch)
     a.step(4); b.step(4)
     a.derived("vorticity"); a.derived("cover")
     a.step(6); b.step(6)
@@ -294,7 +286,7 @@ def test_calling_is_invisible_across_a_replayed_wcsph_call(monkeypatch):
 
 
 def test_calling_is_invisible_to_a_coupled_body(monkeypatch):
-    for k in pf.KNOBS:
+    for k in h.KNOBS:
         monkeypatch.delenv(k, raising=False)
     cfg = scenes.get("dfsph_rigid_small")
     rg = mesh.rigid_from_config(cfg)
@@ -308,30 +300,30 @@ def test_calling_is_invisible_to_a_coupled_body(monkeypatch):
             a.derived("divergence")                  # between the fluid's step and the body's
         a.rigid_step(); b.rigid_step()
     for f in (nat.F_POS, nat.F_VEL, nat.F_RHO, nat.F_WARM_K):
-        pf.same(a.download(f), b.download(f), "coupled scene: field %d" % f)
-    pf.same(a.download(nat.F_RIGID_POS, nat.SPECIES_RIGID), b.download(nat.F_RIGID_POS, nat.SPECIES_RIGID), "coupled scene: the samples")
+        h.same_bits(a.download(f), b.download(f), "coupled scene: field %d" % f)
+    h.same_bits(a.download(nat.F_RIGID_POS, nat.SPECIES_RIGID), b.download(nat.F_RIGID_POS, nat.SPECIES_RIGID), "coupled scene: the samples")
     ra, rb = a.rigid_scalars(), b.rigid_scalars()
     assert ra == rb, (ra, rb)
     a.close(); b.close()
 
 
 # ---- 7: the cache --------------------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("solver,env", [("dfsph", pf.MORTON), ("wcsph", None)], ids=["dfsph-morton", "wcsph"])
+@pytest.mark.parametrize("solver,env", [("dfsph", h.MORTON), ("wcsph", None)], ids=["dfsph-morton", "wcsph"])
 def test_one_sweep_serves_all_quantities_until_the_state_changes(solver, env, monkeypatch):
     cfg = pf.config(solver, "wall", 640)
-    sim = make(cfg, monkeypatch, env)
+    sim = h.make_handle(cfg, monkeypatch, env)
     disturb(sim, 71)
     sim.step(2)
     sim.profile_enable(True)
     sim.profile_reset()
     first = sim.derived("velgrad")
-    pf.same(sim.derived("velgrad"), first, "two calls")
+    h.same_bits(sim.derived("velgrad"), first, "two calls")
     vort, div = sim.derived("vorticity"), sim.derived("divergence")
     sim.synchronize()
     assert sim.profile()["derived"][1] == 1, sim.profile()          # one sweep; the later calls launched only the un-sort
     G = first
-    pf.same(vort, np.stack([G[:, 2, 1] - G[:, 1, 2], G[:, 0, 2] - G[:, 2, 0], G[:, 1, 0] - G[:, 0, 1]], axis=1), "vorticity from the returned velgrad")
-    pf.same(div, (G[:, 0, 0] + G[:, 1, 1]) + G[:, 2, 2], "divergence from the returned velgrad")
+    h.same_bits(vort, np.stack([G[:, 2, 1] - G[:, 1, 2], G[:, 0, 2] - G[:, 2, 0], G[:, 1, 0] - G[:, 0, 1]], axis=1), "vorticity from the returned velgrad")
+    h.same_bits(div, (G[:, 0, 0] + G[:, 1, 1]) + G[:, 2, 2], "divergence from the returned velgrad")
     sim.step(1)
     stepped = sim.derived("velgrad")
     assert sim.profile()["derived"][1] == 2 and not np.array_equal(stepped, first)
@@ -341,35 +333,28 @@ def test_one_sweep_serves_all_quantities_until_the_state_changes(solver, env, mo
     assert sim.profile()["derived"][1] == 3 and not np.array_equal(faster, stepped)
     cover = sim.derived("cover")
     sim.compute_density(); sim.build_neighbors()                    # a re-sort: the device order changed under the kept result
-    pf.same(sim.derived("cover"), cover, "after a re-sort of the same state")
+    h.same_bits(sim.derived("cover"), cover, "after a re-sort of the same state")
     sim.close()
 
 
 # ---- 8: refusals against an undisturbed twin -----------------------------------------------------------------------------------------------------------
-def refused(code, call):
-    with pytest.raises(nat.SphError) as e:
-        call()
-    assert e.value.code == code, (e.value.code, code, str(e.value))
-    return str(e.value)
-
-
 def test_refusals_leave_the_handle_unchanged(monkeypatch):
-    slab = make(pf.config("wcsph", "wall", 640), monkeypatch, slab_count=2, slab_rank=0)
-    assert "slab" in refused(nat.SPH_E_STATE, lambda: slab.derived("cover"))
+    slab = h.make_handle(pf.config("wcsph", "wall", 640), monkeypatch, slab_count=2, slab_rank=0)
+    assert "slab" in h.refused(nat.SPH_E_STATE, lambda: slab.derived("cover"))
     slab.close()
     cfg = pf.config("dfsph", "wall", 640)
-    a, b = make(cfg, monkeypatch), make(cfg, monkeypatch)
+    a, b = h.make_handle(cfg, monkeypatch), h.make_handle(cfg, monkeypatch)
     a.step(3); b.step(3)
     lib, buf = a._lib, np.full(9 * 640 + 8, F(7.0), dtype=F)
-    refused(nat.SPH_E_INVALID, lambda: a.derived(5))
-    refused(nat.SPH_E_INVALID, lambda: a.derived(-1))
+    h.refused(nat.SPH_E_INVALID, lambda: a.derived(5))
+    h.refused(nat.SPH_E_INVALID, lambda: a.derived(-1))
     assert lib.sph_derived(a._h, nat.D_VORTICITY, buf.ctypes.data, 640) == nat.SPH_E_INVALID
     assert lib.sph_derived(a._h, nat.D_COVER, buf.ctypes.data, 641) == nat.SPH_E_INVALID
     assert lib.sph_derived(a._h, nat.D_VELGRAD, buf.ctypes.data, 3 * 640) == nat.SPH_E_INVALID
     assert lib.sph_derived(a._h, nat.D_COVER, None, 640) == nat.SPH_E_INVALID
     assert lib.sph_derived(None, nat.D_COVER, buf.ctypes.data, 640) == nat.SPH_E_INVALID
     assert (buf == F(7.0)).all()
-    pf.same(a.download(nat.F_ALPHA), b.download(nat.F_ALPHA), "alpha of the last step (a refused call re-sorts nothing)")
+    h.same_bits(a.download(nat.F_ALPHA), b.download(nat.F_ALPHA), "alpha of the last step (a refused call re-sorts nothing)")
     for _ in range(3):
         sa, sb = a.step(1), b.step(1)
         assert mc.stats_bits(sa) == mc.stats_bits(sb)
@@ -387,7 +372,7 @@ def read_ply(path):
 
 def test_the_runner_writes_the_extra_columns(tmp_path, monkeypatch):
     import json
-    for k in pf.KNOBS:
+    for k in h.KNOBS:
         monkeypatch.delenv(k, raising=False)
     cfg = pf.config("dfsph", "wall", 640)
     cfg["scene"]["output_fps"] = 2000                 # a frame per step of 1e-3 s

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import diagnostics_ref as dr
+import harness as h
 import particle_flow as pf
 from cfd_taichi_amd import _native as nat
 from cfd_taichi_amd import run
@@ -25,11 +26,11 @@ def states():
     out = {}
     for solver in ("dfsph", "wcsph"):
         cfg = pf.config(solver, "wall", 640)
-        o = pf.make_oracle(cfg)
+        o = h.make_oracle(cfg)
         m = float(F(1000.0 * (2 * cfg["scene"]["particle_radius"]) ** 3))
         for steps in (0, 10):
             for _ in range(10 if steps else 0):
-                pf.oracle_step(o, solver)
+                h.oracle_step(o, solver)
             out[solver, steps] = (o.get(orc.F_POS).copy(), o.get(orc.F_VEL).copy(), o.get(orc.F_RHO).copy(), m)
         o.close()
     return out

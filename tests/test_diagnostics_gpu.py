@@ -12,6 +12,7 @@ import pytest
 import adaptive_dt as ad
 import diagnostics_ref as dr
 import midrun_calls as mc
+import harness as h
 import particle_flow as pf
 from cfd_taichi_amd import _native as nat
 from cfd_taichi_amd import mesh, run, scenes
@@ -19,33 +20,24 @@ from cfd_taichi_amd import mesh, run, scenes
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
-S_TIME, S_ACCEL = 40, 41
 TILTED = [1.5, -9.0, 2.5]
 BIG = 1e6                                     # "everything on this side" in a removal box
 
 
-def make(cfg, monkeypatch, env=None, arith="exact", **kw):
-    for k in pf.KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in (env or {}).items():
-        monkeypatch.setenv(k, v)
-    return nat.Simulation(nat.config_from_dict(cfg, arith=nat.arith_id(arith), **kw))
-
-
-def bits(row):
+def row_bits(row):
     """the 32 slots of a row (a dict by name, or a record of DIAG_DTYPE) as u64: NaN compares like any other pattern"""
-    return np.array([float(row[k]) for k in dr.SLOTS], dtype=np.float64).view(np.uint64)
+    return h.bits(np.array([float(row[k]) for k in dr.SLOTS], dtype=np.float64))
 
 
 def same_rows(a, b, when, slots=32):
-    ba, bb = bits(a)[:slots], bits(b)[:slots]
+    ba, bb = row_bits(a)[:slots], row_bits(b)[:slots]
     assert np.array_equal(ba, bb), "%s: slots %s differ: %r vs %r" % (when, [dr.SLOTS[k] for k in np.flatnonzero(ba != bb)],
                                                                       [float(a[dr.SLOTS[k]]) for k in np.flatnonzero(ba != bb)],
                                                                       [float(b[dr.SLOTS[k]]) for k in np.flatnonzero(ba != bb)])
 
 
 def accel_of(sim):
-    return F([sim.scalar(S_ACCEL + k) for k in range(3)])
+    return F([sim.scalar(nat.S_ACCEL + k) for k in range(3)])
 
 
 def reference(sim, rho):
@@ -104,7 +96,7 @@ def shrink_to(sim, survivors):
 @pytest.mark.parametrize("walls", ["wall", "clamp"])
 @pytest.mark.parametrize("solver", pf.SOLVERS)
 def test_on_demand_against_the_reference(solver, walls, order, monkeypatch):
-    sim = make(pf.config(solver, walls, 640), monkeypatch, pf.MORTON if order == "morton" else mc.LINEAR)
+    sim = h.make_handle(pf.config(solver, walls, 640), monkeypatch, h.MORTON if order == "morton" else h.LINEAR)
     when = "%s %s %s" % (solver, walls, order)
     r0 = check(sim, when + ", step 0")
     assert r0["kinetic"] == 0.0 and r0["vmax"] == 0.0 and r0["vmax_id"] == 0.0 and r0["step"] == 0.0
@@ -121,7 +113,7 @@ def test_on_demand_against_the_reference(solver, walls, order, monkeypatch):
 @pytest.mark.parametrize("solver", ["wcsph", "dfsph"])
 def test_an_odd_count_after_add_particles(solver, monkeypatch):
     cfg = pf.config(solver, "wall", 640, capacity=704)
-    sim = make(cfg, monkeypatch)
+    sim = h.make_handle(cfg, monkeypatch)
     sim.step(2)
     assert sim.add_particles(pf.layer_above(cfg, 640, 37), np.tile(F([0.25, -1, 0.5]), (37, 1))) == 640 and sim.n_fluid == 677
     assert check(sim, solver + " 677, added")["n"] == 677.0
@@ -134,7 +126,7 @@ def test_an_odd_count_after_add_particles(solver, monkeypatch):
 
 @pytest.mark.parametrize("survivors", [1, 63, 64, 65])
 def test_small_counts_after_remove_in_box(survivors, monkeypatch):
-    sim = make(pf.config("wcsph", "wall", 640), monkeypatch)
+    sim = h.make_handle(pf.config("wcsph", "wall", 640), monkeypatch)
     shrink_to(sim, survivors)
     sim.upload(nat.F_VEL, ad.velocities(survivors, 2.0, seed=survivors))
     assert check(sim, "%d survivors, uploaded velocities" % survivors)["n"] == float(survivors)
@@ -144,7 +136,7 @@ def test_small_counts_after_remove_in_box(survivors, monkeypatch):
 
 
 def test_uploaded_velocities_uniform_unique_and_tied(monkeypatch):
-    sim = make(pf.config("dfsph", "wall", 640), monkeypatch, pf.MORTON)
+    sim = h.make_handle(pf.config("dfsph", "wall", 640), monkeypatch, h.MORTON)
     sim.step(2)                                            # the device order is the cell order now, not the order of the ids
     sim.upload(nat.F_VEL, np.zeros((640, 3), dtype=F))
     rest = check(sim, "at rest")
@@ -170,7 +162,7 @@ def test_uploaded_velocities_uniform_unique_and_tied(monkeypatch):
 
 
 def test_tilted_gravity_uses_all_three_components(monkeypatch):
-    sim = make(pf.config("dfsph", "wall", 640), monkeypatch)
+    sim = h.make_handle(pf.config("dfsph", "wall", 640), monkeypatch)
     flat = check(sim, "default gravity")
     sim.set_gravity(TILTED)
     assert list(accel_of(sim)) == list(F(TILTED))
@@ -185,7 +177,7 @@ def test_tilted_gravity_uses_all_three_components(monkeypatch):
 @pytest.mark.parametrize("n", [64512, 66560])
 def test_the_stride_loop_runs(n, monkeypatch):
     """k_diag_partials launches at most 256 workgroups of 256 threads: 64 512 particles are 252 workgroups, 66 560 need the stride loop"""
-    sim = make(pf.threshold_config("wcsph", n), monkeypatch)
+    sim = h.make_handle(pf.threshold_config("wcsph", n), monkeypatch)
     assert sim.n_fluid == n and (n > 256 * 256) == (n == 66560)
     vel = ad.velocities(n, 1.0)
     vel[n - 3] = [0, 6, 8]                                 # the fastest particle sits in the loop's second trip at 66 560
@@ -201,7 +193,7 @@ def test_the_stride_loop_runs(n, monkeypatch):
 @pytest.mark.parametrize("solver", ["dfsph", "pbf"])
 def test_same_state_same_bits(solver, monkeypatch):
     cfg = pf.config(solver, "wall", 640)
-    a, b = make(cfg, monkeypatch, pf.MORTON), make(cfg, monkeypatch, pf.MORTON)
+    a, b = h.make_handle(cfg, monkeypatch, h.MORTON), h.make_handle(cfg, monkeypatch, h.MORTON)
     for s in (a, b):
         s.step(7)
         s.compute_density()
@@ -234,14 +226,14 @@ def recorded_equal_on_demand(rec, rows, rho, when):
         assert all(got[n] == 0.0 for n in dr.SLOTS[27:])
 
 
-RECORDED = [("wcsph", None, "exact"), ("dfsph", pf.MORTON, "exact"), ("pcisph", None, "exact"), ("iisph", pf.MORTON, "exact"), ("pbf", None, "exact"),
-            ("wcsph", None, "relaxed"), ("pcisph", pf.MORTON, "relaxed"), ("pbf", None, "relaxed")]
+RECORDED = [("wcsph", None, "exact"), ("dfsph", h.MORTON, "exact"), ("pcisph", None, "exact"), ("iisph", h.MORTON, "exact"), ("pbf", None, "exact"),
+            ("wcsph", None, "relaxed"), ("pcisph", h.MORTON, "relaxed"), ("pbf", None, "relaxed")]
 
 
 @pytest.mark.parametrize("solver,env,arith", RECORDED, ids=["%s-%s%s" % (s, "morton-" if e else "", a) for s, e, a in RECORDED])
 def test_recorded_rows_are_the_on_demand_rows(solver, env, arith, monkeypatch):
     cfg = pf.config(solver, "wall", 640)
-    a, b = make(cfg, monkeypatch, env, arith), make(cfg, monkeypatch, env, arith)
+    a, b = h.make_handle(cfg, monkeypatch, env, arith), h.make_handle(cfg, monkeypatch, env, arith)
     if arith == "relaxed":
         assert a.scalar(nat.S_ARITH_RELAXED) == 1.0
     a.record_diagnostics(1)
@@ -255,14 +247,14 @@ def test_recorded_rows_are_the_on_demand_rows(solver, env, arith, monkeypatch):
     again, dropped = a.diagnostics_log()
     assert len(again) == 0 and dropped == 0
     for f in (nat.F_POS, nat.F_VEL, nat.F_RHO):
-        pf.same(a.download(f), b.download(f), "%s: field %d of the recording handle and its twin" % (solver, f))
+        h.same_bits(a.download(f), b.download(f), "%s: field %d of the recording handle and its twin" % (solver, f))
     a.close(); b.close()
 
 
 @pytest.mark.parametrize("solver", ["wcsph", "iisph"])
 def test_every_third_step_and_a_ring_of_five(solver, monkeypatch):
     cfg = pf.config(solver, "wall", 640)
-    a, b, c = (make(cfg, monkeypatch) for _ in range(3))
+    a, b, c = (h.make_handle(cfg, monkeypatch) for _ in range(3))
     rows, rho = twin_rows(b, 12)
     a.record_diagnostics(3, rows=8)
     a.step(12)
@@ -287,7 +279,7 @@ def test_every_third_step_and_a_ring_of_five(solver, monkeypatch):
 def test_recorded_dt_under_the_adaptive_time_step(solver, monkeypatch):
     cfg = pf.config(solver, "wall", 640)
     max_dt, min_dt = ad.bounds(solver)
-    a, b = make(cfg, monkeypatch), make(cfg, monkeypatch)
+    a, b = h.make_handle(cfg, monkeypatch), h.make_handle(cfg, monkeypatch)
     vel = ad.velocities(640, ad.AMPLITUDE[solver])
     for s in (a, b):
         s.upload(nat.F_VEL, vel)
@@ -308,7 +300,7 @@ def test_recorded_dt_under_the_adaptive_time_step(solver, monkeypatch):
 
 def test_recorded_count_follows_add_particles(monkeypatch):
     cfg = pf.config("wcsph", "wall", 640, capacity=704)
-    a, b = make(cfg, monkeypatch), make(cfg, monkeypatch)
+    a, b = h.make_handle(cfg, monkeypatch), h.make_handle(cfg, monkeypatch)
     new, vel = pf.layer_above(cfg, 640, 37), np.tile(F([0, -1, 0]), (37, 1))
     a.record_diagnostics(1)
     a.step(2); a.add_particles(new, vel); a.step(2)
@@ -330,8 +322,8 @@ def test_recorded_count_follows_add_particles(monkeypatch):
 # ---- 5: recording and calling are invisible --------------------------------------------------------------------------------------------------------
 def same_handles(a, b, solver, when):
     for f in (nat.F_POS, nat.F_VEL, nat.F_RHO) + ((nat.F_WARM_K,) if solver == "dfsph" else ()):
-        pf.same(a.download(f), b.download(f), "%s: field %d" % (when, f))
-    for which in mc.SCALARS + (S_TIME,):                   # the carried scalars, bit for bit
+        h.same_bits(a.download(f), b.download(f), "%s: field %d" % (when, f))
+    for which in mc.SCALARS + (nat.S_TIME,):                   # the carried scalars, bit for bit
         sa, sb = np.float64(a.scalar(which)), np.float64(b.scalar(which))
         assert sa.view(np.uint64) == sb.view(np.uint64), "%s: scalar %d is %r, the twin's %r" % (when, which, float(sa), float(sb))
 
@@ -339,7 +331,7 @@ def same_handles(a, b, solver, when):
 @pytest.mark.parametrize("solver", ["dfsph", "pbf"])
 def test_recording_and_calling_are_invisible(solver, monkeypatch):
     cfg = pf.config(solver, "wall", 640)
-    a, b = make(cfg, monkeypatch, pf.MORTON), make(cfg, monkeypatch, pf.MORTON)
+    a, b = h.make_handle(cfg, monkeypatch, h.MORTON), h.make_handle(cfg, monkeypatch, h.MORTON)
     rng = np.random.default_rng(11)
     a.record_diagnostics(2, rows=4)
     for k in range(20):
@@ -361,7 +353,7 @@ def test_recording_and_calling_are_invisible(solver, monkeypatch):
 
 def test_recording_is_invisible_in_one_wcsph_call(monkeypatch):
     cfg = pf.config("wcsph", "wall", 640)
-    a, b = make(cfg, monkeypatch), make(cfg, monkeypatch)
+    a, b = h.make_handle(cfg, monkeypatch), h.make_handle(cfg, monkeypatch)
     a.record_diagnostics(1, rows=32)
     a.step(20); b.step(20)
     assert a.scalar(nat.S_GRAPH_LAUNCHES) > 0 and a.scalar(nat.S_GRAPH_LAUNCHES) == b.scalar(nat.S_GRAPH_LAUNCHES)
@@ -375,7 +367,7 @@ def test_recording_is_invisible_in_one_wcsph_call(monkeypatch):
 
 
 def test_recording_is_invisible_to_a_coupled_body(monkeypatch):
-    for k in pf.KNOBS:
+    for k in h.KNOBS:
         monkeypatch.delenv(k, raising=False)
     cfg = scenes.get("dfsph_rigid_small")
     rg = mesh.rigid_from_config(cfg)
@@ -388,7 +380,7 @@ def test_recording_is_invisible_to_a_coupled_body(monkeypatch):
         assert mc.stats_bits(sa) == mc.stats_bits(sb), "step %d: statistics" % (k + 1)
         a.rigid_step(); b.rigid_step()
     for f in (nat.F_POS, nat.F_VEL, nat.F_RHO):
-        pf.same(a.download(f), b.download(f), "coupled scene: field %d" % f)
+        h.same_bits(a.download(f), b.download(f), "coupled scene: field %d" % f)
     ra, rb = a.rigid_scalars(), b.rigid_scalars()
     assert ra == rb, (ra, rb)
     rec, _ = a.diagnostics_log()
@@ -397,25 +389,19 @@ def test_recording_is_invisible_to_a_coupled_body(monkeypatch):
 
 
 # ---- 6: refusals against an undisturbed twin -------------------------------------------------------------------------------------------------------
-def refused(code, call):
-    with pytest.raises(nat.SphError) as e:
-        call()
-    assert e.value.code == code, (e.value.code, code, str(e.value))
-
-
 def test_refusals_leave_the_handle_unchanged(monkeypatch):
     cfg = pf.config("dfsph", "wall", 640)
-    slab = make(pf.config("wcsph", "wall", 640), monkeypatch, slab_count=2, slab_rank=0)
-    refused(nat.SPH_E_STATE, slab.diagnostics)
-    refused(nat.SPH_E_STATE, lambda: slab.record_diagnostics(1))
-    refused(nat.SPH_E_STATE, slab.diagnostics_log)
+    slab = h.make_handle(pf.config("wcsph", "wall", 640), monkeypatch, slab_count=2, slab_rank=0)
+    h.refused(nat.SPH_E_STATE, slab.diagnostics)
+    h.refused(nat.SPH_E_STATE, lambda: slab.record_diagnostics(1))
+    h.refused(nat.SPH_E_STATE, slab.diagnostics_log)
     slab.close()
-    a, b = make(cfg, monkeypatch), make(cfg, monkeypatch)
+    a, b = h.make_handle(cfg, monkeypatch), h.make_handle(cfg, monkeypatch)
     a.step(3); b.step(3)
     a.record_diagnostics(1, rows=6)
     a.step(2); b.step(2)
     for every, rows in ((-1, 16), (1, 0), (1, -4), (2, (1 << 20) + 1), (1, 2 ** 31 - 1)):
-        refused(nat.SPH_E_INVALID, lambda: a.record_diagnostics(every, rows))
+        h.refused(nat.SPH_E_INVALID, lambda: a.record_diagnostics(every, rows))
     lib, n, buf = a._lib, ctypes.c_size_t(99), np.zeros(4, dtype=nat.DIAG_DTYPE)
     assert lib.sph_diagnostics(a._h, None) == nat.SPH_E_INVALID
     assert lib.sph_diagnostics(None, buf.ctypes.data) == nat.SPH_E_INVALID
@@ -435,7 +421,7 @@ def test_refusals_leave_the_handle_unchanged(monkeypatch):
 
 # ---- 7: the runner -----------------------------------------------------------------------------------------------------------------------------------
 def test_the_runner_writes_the_csv(tmp_path, monkeypatch):
-    for k in pf.KNOBS:
+    for k in h.KNOBS:
         monkeypatch.delenv(k, raising=False)
     path = str(tmp_path / "slosh.csv")
     base = ["--config", os.path.join(ROOT, "config", "sloshing_dfsph.json"), "--steps", "20"]
@@ -449,4 +435,4 @@ def test_the_runner_writes_the_csv(tmp_path, monkeypatch):
     assert (np.diff(table[:, 0]) > 0).all() and list(table[:, 2]) == list(range(2, 21, 2))
     assert len(set(table[:, 13])) > 1                      # the shaken tank's centre of mass moves along x
     run.main(base)
-    pf.same(with_csv, run.LAST["ps"].fluid_particles.pos.to_numpy(), "final positions with and without --diag-csv")
+    h.same_bits(with_csv, run.LAST["ps"].fluid_particles.pos.to_numpy(), "final positions with and without --diag-csv")

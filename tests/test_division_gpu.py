@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 from cfd_taichi_amd import _native as nat
+from harness import bits
 
 pytestmark = pytest.mark.gpu
 
@@ -42,11 +43,7 @@ def binade(e, mant=None):
     return (np.uint32((e + 127) << 23) | mant).view(np.float32)
 
 
-def bits(x):
-    return np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
-
-
-def same_bits(got, ref, what, a, d):
+def same_quotients(got, ref, what, a, d):
     bad = np.flatnonzero(bits(got) != bits(ref))
     print("%s: %d of %d differ" % (what, len(bad), got.size))
     assert len(bad) == 0, "%s differs at %d of %d; first: a=%r (0x%08x) d=%r (0x%08x): %r vs %r" % (
@@ -84,8 +81,8 @@ def test_exceptional_denominators_all_numerators(exceptional):
             d = np.full_like(a, d1)
             one, two = nat.selftest_math(nat.MATH_DIV_SHARED, a, d), nat.selftest_math(nat.MATH_DIV_SHARED_TWO_STEP, a, d)
             what = "d = 2^%d * 1.[0x%06x]" % (e, mant)
-            same_bits(one, two, what + ": one correction vs two", a, d)
-            same_bits(one, a / d, what + ": one correction vs a/d", a, d)
+            same_quotients(one, two, what + ": one correction vs two", a, d)
+            same_quotients(one, a / d, what + ": one correction vs a/d", a, d)
 
 
 SLICES = 16
@@ -136,7 +133,7 @@ def test_ordinary_denominators(part, exceptional):
     assert len(cols) == 64 and np.all(np.isfinite(a)) and np.all(np.abs(a) >= 2.0 ** (e + NUM_SHIFT - 2))
     keep = np.tile(~np.isin(mant, exceptional[e]), len(cols))       # the exceptional d have all their numerators in (b); none are left out
     a, d = a[keep], d[keep]
-    same_bits(nat.selftest_math(nat.MATH_DIV_SHARED, a, d), a / d, "ordinary denominators %d/%d, %d quotients" % (part + 1, SLICES, a.size), a, d)
+    same_quotients(nat.selftest_math(nat.MATH_DIV_SHARED, a, d), a / d, "ordinary denominators %d/%d, %d quotients" % (part + 1, SLICES, a.size), a, d)
 
 
 def test_zero_numerators_over_a_floored_divisor():

@@ -10,6 +10,7 @@ from cfd_taichi_amd import scenes
 import coupled_scenes as cs
 import forcing as fo
 import restatement_compare as rc
+from harness import same_bits
 from second_restatement import Scene, Solver
 from second_restatement_pbf import PbfSolver
 
@@ -28,7 +29,7 @@ def test_helper_fed_the_default_vector_is_the_untouched_restatement(scene):
         for _ in range(5):
             ref.step()
     for attr in rc.FIELDS[solver]:
-        rc.same(getattr(ref, attr), getattr(mine, attr), "%s: %s" % (scene, attr))
+        same_bits(getattr(ref, attr), getattr(mine, attr), "%s: %s" % (scene, attr))
     assert fo.stats_of(ref) == fo.stats_of(mine)
 
 
@@ -44,9 +45,9 @@ def test_forced_body_fed_the_default_vector_is_the_untouched_body():
             ref.rigid_step()
     assert isinstance(mine.body, fo.ForcedBody) and not isinstance(ref.body, fo.ForcedBody)
     for what in ("pos", "vel"):
-        rc.same(getattr(ref, what), getattr(mine, what), "fluid " + what)
+        same_bits(getattr(ref, what), getattr(mine, what), "fluid " + what)
     for what in ("pos", "centroid", "vel", "omega", "acc"):
-        rc.same(getattr(ref.body, what), getattr(mine.body, what), "body " + what)
+        same_bits(getattr(ref.body, what), getattr(mine.body, what), "body " + what)
 
 
 def test_forced_body_reads_the_vector():

@@ -17,6 +17,7 @@ from cfd_taichi_amd import scenes
 import coupled_scenes as cs
 import forcing as fo
 import restatement_compare as rc
+from harness import MORTON, make_handle, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -34,12 +35,8 @@ def make(monkeypatch, cfg, rg=None, quad=True, arith=nat.ARITH_EXACT, staged=Fal
     if not quad:
         knobs["SPH_QUAD"] = "0"
     if staged:
-        knobs.update(SPH_CELL_ORDER="morton", SPH_CELL_TILE="4")
-    for name in ("SPH_QUAD", "SPH_CELL_ORDER", "SPH_CELL_TILE"):
-        monkeypatch.delenv(name, raising=False)
-    for name, value in knobs.items():
-        monkeypatch.setenv(name, value)
-    sim = nat.Simulation(nat.config_from_dict(cfg, max_density_iters=100 if cfg["solver"]["name"] == "dfsph" else 0, arith=arith), rigid=rg)
+        knobs.update(MORTON)
+    sim = make_handle(cfg, monkeypatch, knobs, arith, rigid=rg, max_density_iters=100 if cfg["solver"]["name"] == "dfsph" else 0)
     for name in knobs:
         monkeypatch.delenv(name, raising=False)
     named = [o for o in sim.overrides() if o.split("=")[0] in ("SPH_QUAD", "SPH_CELL_ORDER")]
@@ -72,7 +69,7 @@ def all_fields(sim, solver):
 def same_handles(a, b, solver, what, names=None):
     fa, fb = all_fields(a, solver), all_fields(b, solver)
     for name in names or fa:
-        rc.same(fa[name], fb[name], "%s: %s" % (what, name))
+        same_bits(fa[name], fb[name], "%s: %s" % (what, name))
 
 
 def close(*sims):
@@ -90,10 +87,10 @@ def test_explicit_default_equals_untouched(solver, arith, monkeypatch):
     kw = {} if arith == "exact" else dict(arith=nat.ARITH_RELAXED, quad=solver not in ("pcisph", "iisph"), staged=arith.endswith("staged"))
     a, b = make(monkeypatch, cfg, **kw), make(monkeypatch, cfg, **kw)
     try:
-        rc.same(a.accel(), [G * F(0.0), G * F(-1.0), G * F(0.0)], "the default vector")
-        rc.same(a.gravity_vec(), a.accel(), "g of an untouched handle")
+        same_bits(a.accel(), [G * F(0.0), G * F(-1.0), G * F(0.0)], "the default vector")
+        same_bits(a.gravity_vec(), a.accel(), "g of an untouched handle")
         b.set_gravity([G * F(0.0), G * F(-1.0), G * F(0.0)])
-        rc.same(b.accel(), a.accel(), "the vector after set_gravity(default)")
+        same_bits(b.accel(), a.accel(), "the vector after set_gravity(default)")
         a.step(10); b.step(10)
         same_handles(a, b, solver, "%s, 10 steps" % solver)
         assert a.time() == b.time() and a.time() > 0.0
@@ -109,7 +106,7 @@ def test_gravity_as_a_list_in_the_config_gives_the_same_bits():
     vec["scene"]["gravity"] = [0, -cfg["scene"]["gravity"], 0]
     a, b = nat.Simulation(nat.config_from_dict(cfg), config=cfg), nat.Simulation(nat.config_from_dict(vec), config=vec)
     try:
-        rc.same(a.accel(), b.accel(), "the vector")
+        same_bits(a.accel(), b.accel(), "the vector")
         a.step(10); b.step(10)
         same_handles(a, b, "dfsph", "number against list")
     finally:
@@ -125,13 +122,13 @@ def test_constant_tilt(scene, monkeypatch):
     try:
         for sim in sims:
             sim.set_gravity(fo.TILT)
-            rc.same(sim.accel(), F(fo.TILT), "the vector after set_gravity")
+            same_bits(sim.accel(), F(fo.TILT), "the vector after set_gravity")
         s, ev = fo.lockstep(nat, cfg, sims, 10, labels=labels)
         print("%s: iterations %s" % (scene, ev["iters"]))
         assert ev["lost"] == 0 and ev["capped"] == 0, ev
         assert fo.inside_box(cfg, s.pos), "a particle left the box: the comparison could hide behind lost particles"
         for v in ev["vectors"]:
-            rc.same(v, F(fo.TILT), "the vector of a step")
+            same_bits(v, F(fo.TILT), "the vector of a step")
     finally:
         close(*sims)
 
@@ -147,7 +144,7 @@ def test_harmonic_forcing(solver, monkeypatch):
             force(sim)
             assert sim.time() == 0.0
             assert fo.ulp_distance(sim.accel(), fo.accel_formula(*FORCING, 0.0)).max() <= 1      # read back before the first step
-            rc.same(sim.gravity_vec(), F(fo.TILT), "g")
+            same_bits(sim.gravity_vec(), F(fo.TILT), "g")
         s, ev = fo.lockstep(nat, cfg, sims, 10, forcing=FORCING, labels=labels)
         print("%s: largest distance to the f64 formula %d ulp; times %s" % (solver, ev["ulps"], ev["times"]))
         assert ev["lost"] == 0 and fo.inside_box(cfg, s.pos)
@@ -184,7 +181,7 @@ def _state(sim):
 
 def _same_state(a, b, what):
     sa, sb = _state(a), _state(b)
-    rc.same(sa[0], sb[0], what + ": pos"); rc.same(sa[1], sb[1], what + ": vel"); rc.same(sa[3], sb[3], what + ": accel")
+    same_bits(sa[0], sb[0], what + ": pos"); same_bits(sa[1], sb[1], what + ": vel"); same_bits(sa[3], sb[3], what + ": accel")
     assert sa[2] == sb[2] and sa[2] > 0, (what, sa[2], sb[2])
 
 
@@ -222,15 +219,15 @@ def test_set_gravity_between_two_replayed_calls(monkeypatch):
             b.step(1)
         assert launches > 0 and a.scalar(nat.S_GRAPH_LAUNCHES) > launches
         _same_state(a, b, "4 + set_gravity + 4 against single steps")
-        rc.same(a.gravity_vec(), F(other), "g")
+        same_bits(a.gravity_vec(), F(other), "g")
         # ... and forcing switched off between two calls: the vector is g again, with no arithmetic
         a.set_forcing(None); b.set_forcing(None)
-        rc.same(a.accel(), F(other), "the vector with forcing off")
+        same_bits(a.accel(), F(other), "the vector with forcing off")
         a.step(4)
         for _ in range(4):
             b.step(1)
         _same_state(a, b, "forcing off, 4 against single steps")
-        rc.same(a.accel(), F(other), "the vector with forcing off, after steps")
+        same_bits(a.accel(), F(other), "the vector with forcing off, after steps")
     finally:
         close(a, b)
 
@@ -275,7 +272,7 @@ def test_fixed_body_keeps_its_positions_under_tilt(monkeypatch):
         for _ in range(10):
             sim.step(1)
             sim.rigid_step()
-        rc.same(start, sim.download(nat.F_RIGID_POS, nat.SPECIES_RIGID), "the fixed body's samples")
+        same_bits(start, sim.download(nat.F_RIGID_POS, nat.SPECIES_RIGID), "the fixed body's samples")
         assert sim.rigid_scalars()["centroid"] == centroid
         assert float(np.abs(sim.rigid_load()[0]).max()) > 0, "the fluid never pushed the obstacle"
     finally:
@@ -334,7 +331,7 @@ def test_refusals_leave_the_handle_unchanged(monkeypatch):
             with pytest.raises(nat.SphError) as e:
                 call()
             assert e.value.code == nat.SPH_E_INVALID
-        rc.same(before[0], a.accel(), "the vector after the refusals"); rc.same(before[1], a.gravity_vec(), "g after the refusals")
+        same_bits(before[0], a.accel(), "the vector after the refusals"); same_bits(before[1], a.gravity_vec(), "g after the refusals")
         assert before[2] == a.time()
         a.step(3); b.step(3)
         same_handles(a, b, "dfsph", "3 steps after the refusals")

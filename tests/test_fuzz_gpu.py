@@ -8,6 +8,7 @@ import pytest
 
 from cfd_taichi_amd import _native as nat
 from cfd_taichi_amd import scenes
+from harness import squeeze
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -29,14 +30,6 @@ def random_scene(rng, solver):
     return cfg
 
 
-def squeeze_both(sim, o, factor=0.9):
-    """test_pbf_gpu.squeeze: the rest lattice scaled about its minimum corner on both sides, so that the PBF constraint acts from step 1"""
-    pos = o.get(orc.F_POS)
-    about = pos.min(0)
-    sq = (about + (pos - about) * np.float32(factor)).astype(np.float32)
-    o.set(orc.F_POS, sq); sim.upload(nat.F_POS, sq)
-
-
 PBF_FIELDS = ((nat.F_PBF_LAMBDA, orc.F_PBF_LAMBDA), (nat.F_PBF_DELTA_POS, orc.F_PBF_DELTA_POS))
 
 
@@ -54,7 +47,7 @@ def test_random_scene_matches_oracle(solver, seed):
         assert np.array_equal(sim.download(nat.F_WALL_VOL, nat.SPECIES_WALL), o.get(orc.F_WALL_VOL)), "wall volumes"
     steps = 30
     if solver == "pbf":
-        squeeze_both(sim, o)
+        squeeze(sim, o)
     lambda_active = 0
     for s in range(steps):
         if solver == "pbf":

@@ -21,6 +21,7 @@ import pytest
 
 from cfd_taichi_amd import _native as nat
 from cfd_taichi_amd import mesh, scenes
+from harness import same_values
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -35,15 +36,6 @@ def cores():
     except Exception:
         pass
     return n
-
-
-def same(a, b, what):
-    a, b = np.asarray(a), np.asarray(b)
-    if not np.array_equal(a, b):
-        bad = np.argwhere(a != b)
-        scale = max(float(np.abs(b).max()), 1e-30)
-        raise AssertionError("%s differs at %d of %d entries, rel err %.3e, first %s: %r vs %r" % (
-            what, len(bad), a.size, float(np.abs(a.astype(np.float64) - b).max()) / scale, bad[0], a[tuple(bad[0])], b[tuple(bad[0])]))
 
 
 def hand_over_dfsph(sim, cfg):
@@ -68,10 +60,10 @@ def dfsph_steps_equal(sim, o, nsteps, label):
         assert st.lost == 0 and st.capped == 0
         counts.append((st.n_div, st.n_dens))
         print("%s: step +%d (n_div, n_dens) = (%d, %d), %.1f s" % (label, s + 1, st.n_div, st.n_dens, time.time() - t0), flush=True)
-    same(sim.download(nat.F_RHO_ADV), o.get(orc.F_RHO_ADV), label + ": rho_adv")
-    same(sim.download(nat.F_WARM_K), o.get(orc.F_WARM_K), label + ": warm_start_k")
-    same(sim.download(nat.F_POS), o.get(orc.F_POS), label + ": pos")
-    same(sim.download(nat.F_VEL), o.get(orc.F_VEL), label + ": vel")
+    same_values(sim.download(nat.F_RHO_ADV), o.get(orc.F_RHO_ADV), label + ": rho_adv")
+    same_values(sim.download(nat.F_WARM_K), o.get(orc.F_WARM_K), label + ": warm_start_k")
+    same_values(sim.download(nat.F_POS), o.get(orc.F_POS), label + ": pos")
+    same_values(sim.download(nat.F_VEL), o.get(orc.F_VEL), label + ": vel")
     return counts
 
 
@@ -124,9 +116,9 @@ def test_pressure_solvers_1m_mid_run_bit_exact(scene, solver, pre_steps):
         assert (st.n_dens, st.dens_err) == (o.last_stats.n_dens, o.last_stats.dens_err), (scene, s)
         print("%s @%d: step +%d iterations %d, %.1f s" % (scene, pre_steps, s + 1, st.n_dens, time.time() - t0), flush=True)
     label = "%s @%d: " % (scene, pre_steps)
-    same(sim.download(nat.F_PRESS_ITER), o.get(orc.F_PRESS_ITER), label + "pressure")
-    same(sim.download(nat.F_POS), o.get(orc.F_POS), label + "pos")
-    same(sim.download(nat.F_VEL), o.get(orc.F_VEL), label + "vel")
+    same_values(sim.download(nat.F_PRESS_ITER), o.get(orc.F_PRESS_ITER), label + "pressure")
+    same_values(sim.download(nat.F_POS), o.get(orc.F_POS), label + "pos")
+    same_values(sim.download(nat.F_VEL), o.get(orc.F_VEL), label + "vel")
     sim.close(); o.close()
 
 
@@ -140,9 +132,9 @@ def test_wcsph_250k_steps_151_to_155_bit_exact():
     o.set(orc.F_POS, sim.download(nat.F_POS)); o.set(orc.F_VEL, sim.download(nat.F_VEL))
     sim.step_wcsph(5)
     o.step_wcsph(5)
-    same(sim.download(nat.F_RHO), o.get(orc.F_RHO), "wcsph_250k @150: rho")
-    same(sim.download(nat.F_POS), o.get(orc.F_POS), "wcsph_250k @150: pos")
-    same(sim.download(nat.F_VEL), o.get(orc.F_VEL), "wcsph_250k @150: vel")
+    same_values(sim.download(nat.F_RHO), o.get(orc.F_RHO), "wcsph_250k @150: rho")
+    same_values(sim.download(nat.F_POS), o.get(orc.F_POS), "wcsph_250k @150: pos")
+    same_values(sim.download(nat.F_VEL), o.get(orc.F_VEL), "wcsph_250k @150: vel")
     sim.close(); o.close()
 
 
@@ -164,17 +156,17 @@ def test_dfsph_rigid_2m_two_coupled_steps_bit_exact():
         assert (st.n_div, st.n_dens, st.n_div_evals, st.div_first_err, st.div_err, st.dens_err, st.dt) == (
             so.n_div, so.n_dens, so.n_div_evals, so.div_first_err, so.div_err, so.dens_err, so.dt), s
         assert st.n_dens <= 40 and st.capped == (1 if st.n_dens == 40 and so.dens_err > 1.0 else 0), (s, st.n_dens, st.capped)
-        same(sim.download(nat.F_RIGID_FORCE, nat.SPECIES_RIGID), o.get(orc.F_RIGID_FORCE), "force on the body, step %d" % s)
+        same_values(sim.download(nat.F_RIGID_FORCE, nat.SPECIES_RIGID), o.get(orc.F_RIGID_FORCE), "force on the body, step %d" % s)
         sim.rigid_step()
         o.rigid_step()
         a, b = sim.rigid_scalars(), o.rigid_scalars()
         for k in ("centroid", "omega", "vel", "inertia_inv"):
-            same(np.float32(a[k]), np.float32(b[k]), "%s after step %d" % (k, s))
+            same_values(np.float32(a[k]), np.float32(b[k]), "%s after step %d" % (k, s))
         print("dfsph_rigid_2m: step %d (n_div, n_dens) = (%d, %d), %.1f s" % (s + 1, st.n_div, st.n_dens, time.time() - t0), flush=True)
-    same(sim.download(nat.F_RHO_ADV), o.get(orc.F_RHO_ADV), "rho_adv")
-    same(sim.download(nat.F_POS), o.get(orc.F_POS), "fluid positions")
-    same(sim.download(nat.F_VEL), o.get(orc.F_VEL), "fluid velocities")
-    same(sim.download(nat.F_RIGID_POS, nat.SPECIES_RIGID), o.get(orc.F_RIGID_POS), "rigid positions")
+    same_values(sim.download(nat.F_RHO_ADV), o.get(orc.F_RHO_ADV), "rho_adv")
+    same_values(sim.download(nat.F_POS), o.get(orc.F_POS), "fluid positions")
+    same_values(sim.download(nat.F_VEL), o.get(orc.F_VEL), "fluid velocities")
+    same_values(sim.download(nat.F_RIGID_POS, nat.SPECIES_RIGID), o.get(orc.F_RIGID_POS), "rigid positions")
     sim.close(); o.close()
 
 

@@ -9,6 +9,7 @@
 import numpy as np
 import pytest
 
+import harness as h
 import midrun_calls as mc
 from oracle import oracle as orc
 
@@ -24,7 +25,7 @@ def test_the_oracle_has_the_property(scene, solver):
     disturbed steps (the carry of pbf_lambda / delta_pos through a re-sort is checked on what is non-zero then); the body feels the fluid."""
     case = first_case(scene, solver)
     assert all((c.k, c.m) == (case.k, case.m) for c in mc.CASES.values() if (c.scene, c.solver) == (scene, solver))
-    a, b = mc.make_oracle(case), mc.make_oracle(case)
+    a, b = mc.oracle_of(case), mc.oracle_of(case)
     mc.begin(case, a); mc.begin(case, b)
     rng = np.random.default_rng(mc.SEED)
     print("seed", mc.SEED)
@@ -32,7 +33,7 @@ def test_the_oracle_has_the_property(scene, solver):
     for s in range(case.k + case.m):
         if s >= case.k:
             mc.oracle_disturb(a, case, rng)
-        ra, rb = mc.oracle_step(a, solver), mc.oracle_step(b, solver)
+        ra, rb = h.oracle_step(a, solver, bits_view=True), h.oracle_step(b, solver, bits_view=True)
         assert ra == rb, (scene, s, ra, rb)
         if ra is not None:
             n_dens.append(b.last_stats.n_dens); n_div.append(b.last_stats.n_div)
@@ -41,13 +42,13 @@ def test_the_oracle_has_the_property(scene, solver):
         if case.rigid:
             if case.k <= s < case.k + case.m - 1:        # (not behind the last step: a compute_rho there is the rho the run ends with)
                 mc.oracle_disturb(a, case, rng)
-            mc.same(a.get(orc.F_RIGID_FORCE), b.get(orc.F_RIGID_FORCE), "step %d: force on the body" % (s + 1))
+            h.same_values_nan_signed(a.get(orc.F_RIGID_FORCE), b.get(orc.F_RIGID_FORCE), "step %d: force on the body" % (s + 1))
             force = max(force, float(np.abs(b.get(orc.F_RIGID_FORCE)).max()))
             a.rigid_step(); b.rigid_step()
             assert a.rigid_scalars() == b.rigid_scalars(), s
-        mc.same(a.get(orc.F_POS), b.get(orc.F_POS), "step %d: pos" % (s + 1))
+        h.same_values_nan_signed(a.get(orc.F_POS), b.get(orc.F_POS), "step %d: pos" % (s + 1))
     for f in mc.SOLVER_FIELDS[solver]:
-        mc.same(a.get(f), b.get(f), "field %d" % f)
+        h.same_values_nan_signed(a.get(f), b.get(f), "field %d" % f)
     assert a.dt == b.dt
     print(scene, solver, "n_dens", n_dens, "n_div", n_div, "lambda != 0", lam, "force", force)
     if solver in ("dfsph", "pcisph", "iisph"):

@@ -7,10 +7,11 @@ yardstick has the property and that the runs reach what they are meant to reach)
      handle given the same state and delta_time;
   3. a CHANGED solver attribute or delta_time reaches the captured wcsph step pairs (the same-value writes of 1. cannot tell).
 
-Bit equality throughout: np.array_equal(..., equal_nan=True), the sign of zero through the uint32 view (midrun_calls.same)."""
+Bit equality throughout: np.array_equal(..., equal_nan=True), the sign of zero through the uint32 view (harness.same_values_nan_signed)."""
 import numpy as np
 import pytest
 
+import harness as h
 import midrun_calls as mc
 from cfd_taichi_amd import _native as nat
 from oracle import oracle as orc
@@ -18,13 +19,8 @@ from oracle import oracle as orc
 pytestmark = pytest.mark.gpu
 
 
-def make(case, monkeypatch):
-    for k in mc.KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in case.env.items():
-        monkeypatch.setenv(k, v)
-    sim = nat.Simulation(nat.config_from_dict(mc.config(case), arith=nat.arith_id(case.arith)), rigid=mc.rigid_of(case))
-    return sim
+def handle(case, monkeypatch):
+    return h.make_handle(mc.config(case), monkeypatch, case.env, case.arith, rigid=mc.rigid_of(case))
 
 
 def is_relaxed(sim):
@@ -34,15 +30,15 @@ def is_relaxed(sim):
 def same_handles(case, a, b, when):
     """every downloadable field of every species, the scalars a step moves, the body"""
     for f in mc.DOWNLOADABLE[case.solver]:
-        mc.same(a.download(f), b.download(f), "%s: field %d" % (when, f))
+        h.same_values_nan_signed(a.download(f), b.download(f), "%s: field %d" % (when, f))
     for s in (nat.S_DELTA_TIME, nat.S_SIMULATE_CNT, nat.S_PS_DELTA_TIME):
         assert a.scalar(s) == b.scalar(s), (when, s)
     if case.rigid:
         for f in (nat.F_RIGID_POS, nat.F_RIGID_FORCE, nat.F_RIGID_VERT, nat.F_RIGID_VOL, nat.F_RIGID_MASS):
-            mc.same(a.download(f, nat.SPECIES_RIGID), b.download(f, nat.SPECIES_RIGID), "%s: rigid field %d" % (when, f))
+            h.same_values_nan_signed(a.download(f, nat.SPECIES_RIGID), b.download(f, nat.SPECIES_RIGID), "%s: rigid field %d" % (when, f))
         ra, rb = a.rigid_scalars(), b.rigid_scalars()
         for k in ra:
-            mc.same(np.float32(ra[k]), np.float32(rb[k]), "%s: body %s" % (when, k))
+            h.same_values_nan_signed(np.float32(ra[k]), np.float32(rb[k]), "%s: body %s" % (when, k))
 
 
 def history_is_real(case, n_dens, n_div):
@@ -61,9 +57,9 @@ def test_midrun_calls_are_invisible(name, monkeypatch):
     case = mc.CASES[name]
     seed = mc.SEED + list(mc.CASES).index(name)
     print("case %s, seed %d" % (name, seed))
-    a, b = make(case, monkeypatch), make(case, monkeypatch)                  # the disturbed handle and its twin
-    single = make(case, monkeypatch) if case.chunks and case.oracle else None  # wcsph: one step per call, never a graph replay
-    o = mc.make_oracle(case) if case.oracle else None
+    a, b = handle(case, monkeypatch), handle(case, monkeypatch)                  # the disturbed handle and its twin
+    single = handle(case, monkeypatch) if case.chunks and case.oracle else None  # wcsph: one step per call, never a graph replay
+    o = mc.oracle_of(case) if case.oracle else None
     mc.begin(case, o, [s for s in (a, b, single) if s is not None])
     d = mc.Disturber(a, case, nat, pytest.raises, seed)
     verlet = case.solver == "wcsph" and case.arith == "relaxed"
@@ -81,21 +77,21 @@ def test_midrun_calls_are_invisible(name, monkeypatch):
             single.step(1) if n == 1 else [single.step(1) for _ in range(n)]
         if o is not None:
             for _ in range(n):
-                r = mc.oracle_step(o, case.solver)
+                r = h.oracle_step(o, case.solver, bits_view=True)
             if r is not None:
-                got = mc.stats_bits(sa, mc.ORACLE_STATS) + (int(sa.lost),)
-                assert got == r[0] and sa.capped == int(r[1]), (when, d.log[-8:], dict(zip(mc.ORACLE_STATS + ("lost",), zip(got, r[0]))))
+                got = mc.stats_bits(sa, h.ORACLE_STATS) + (int(sa.lost),)
+                assert got == r[0] and sa.capped == int(r[1]), (when, d.log[-8:], dict(zip(h.ORACLE_STATS + ("lost",), zip(got, r[0]))))
             else:
-                mc.same(a.download(nat.F_POS), o.get(orc.F_POS), "%s: pos against the oracle after %s" % (when, d.log[-8:]))
+                h.same_values_nan_signed(a.download(nat.F_POS), o.get(orc.F_POS), "%s: pos against the oracle after %s" % (when, d.log[-8:]))
         if verlet:
             assert a.scalar(nat.S_VERLET_BUILDS) == b.scalar(nat.S_VERLET_BUILDS), (when, d.log[-8:])
         if case.rigid:
             if between:
                 d.draw("between %s and its rigid_step" % when)
             fa = a.download(nat.F_RIGID_FORCE, nat.SPECIES_RIGID)
-            mc.same(fa, b.download(nat.F_RIGID_FORCE, nat.SPECIES_RIGID), "%s: force on the body against the twin, after %s" % (when, d.log[-8:]))
+            h.same_values_nan_signed(fa, b.download(nat.F_RIGID_FORCE, nat.SPECIES_RIGID), "%s: force on the body against the twin, after %s" % (when, d.log[-8:]))
             if o is not None:
-                mc.same(fa, o.get(orc.F_RIGID_FORCE), "%s: force on the body against the oracle, after %s" % (when, d.log[-8:]))
+                h.same_values_nan_signed(fa, o.get(orc.F_RIGID_FORCE), "%s: force on the body against the oracle, after %s" % (when, d.log[-8:]))
                 o.rigid_step()
             a.rigid_step(); b.rigid_step()
         done[0] += n
@@ -131,7 +127,7 @@ RESEATS = [(n, order) for n in mc.ORACLE_CASES for order in mc.reseat_orders(mc.
 @pytest.mark.parametrize("name,order", RESEATS, ids=["%s-%s-%s" % ((n,) + o) for n, o in RESEATS])
 def test_reseat_follows_the_oracle(name, order, monkeypatch):
     case = mc.CASES[name]
-    sim = make(case, monkeypatch)
+    sim = handle(case, monkeypatch)
     recs = mc.reseat_run(case, order, sim)
     assert not is_relaxed(sim)
     print(name, order, [(r["kind"], r.get("n_dens"), r.get("lost")) for r in recs])
@@ -142,7 +138,7 @@ def handle_state(sim, case):
     return (sim.download(nat.F_POS), sim.download(nat.F_VEL), sim.download(nat.F_WARM_K) if case.solver == "dfsph" else None)
 
 
-def give(sim, state):
+def give_handle_state(sim, state):
     sim.upload(nat.F_POS, state[0]); sim.upload(nat.F_VEL, state[1])
     if state[2] is not None:
         sim.upload(nat.F_WARM_K, state[2])
@@ -157,7 +153,7 @@ def test_relaxed_reseat_equals_a_fresh_handle(name, order, monkeypatch):
     (midrun_calls' docstring) the re-seated handle equals a fresh relaxed handle given S and that delta_time -- Verlet handles included: both build
     their lists at S, and from then on rebuild at the same steps."""
     case = mc.CASES[name]
-    a = make(case, monkeypatch)
+    a = handle(case, monkeypatch)
     mc.begin(case, None, [a])
     verlet = case.solver == "wcsph"
     k, m = mc.reseat_steps(case)
@@ -176,9 +172,9 @@ def test_relaxed_reseat_equals_a_fresh_handle(name, order, monkeypatch):
         assert mc.inside_box(case, state[0]), when
         a.compute_density()                       # both validity flags say "valid" when the new state arrives
         builds = a.scalar(nat.S_VERLET_BUILDS)
-        give(a, state)
-        f = make(case, monkeypatch)
-        give(f, state)
+        give_handle_state(a, state)
+        f = handle(case, monkeypatch)
+        give_handle_state(f, state)
         f.set_dt(a.scalar(nat.S_DELTA_TIME))
         after = []
         for n_steps in mc.step_plan(case, m):
@@ -191,7 +187,7 @@ def test_relaxed_reseat_equals_a_fresh_handle(name, order, monkeypatch):
             if verlet:
                 assert a.scalar(nat.S_VERLET_BUILDS) - builds == f.scalar(nat.S_VERLET_BUILDS), when
         for fld in mc.DOWNLOADABLE[case.solver]:
-            mc.same(a.download(fld), f.download(fld), "%s: field %d against the fresh handle" % (when, fld))
+            h.same_values_nan_signed(a.download(fld), f.download(fld), "%s: field %d against the fresh handle" % (when, fld))
         assert a.scalar(nat.S_DELTA_TIME) == f.scalar(nat.S_DELTA_TIME)
         if case.solver == "dfsph":
             assert max(after) >= 3, (when, after)          # the density loop's tile order, taken from the state before S, was used and set again
@@ -206,7 +202,7 @@ def test_changed_attributes_reach_the_captured_wcsph_steps(monkeypatch):
     """wcsph step pairs are captured with the solver's constants and delta_time as launch arguments: writing another value between two calls must
     show in the very next replay, as it does on the oracle."""
     case = mc.CASES["wcsph_small"]
-    sim, o = make(case, monkeypatch), mc.make_oracle(case)
+    sim, o = handle(case, monkeypatch), mc.oracle_of(case)
     launches = 0
     for write in (None, lambda: (sim.set_param("viscosity_alpha", 0.03), o.set_param(mc.PARAMS["viscosity_alpha"], 0.03)),
                   lambda: (sim.set_param("tension_k", 0.35), o.set_param(mc.PARAMS["tension_k"], 0.35)),

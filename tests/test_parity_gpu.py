@@ -10,6 +10,7 @@ import pytest
 
 from cfd_taichi_amd import _native as nat
 from cfd_taichi_amd import scenes
+from harness import make_oracle, same_values
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -25,16 +26,7 @@ def rel_err(a, b):
 def make(scene, solver=None):
     cfg = scenes.get(scene)
     sim = nat.Simulation(nat.config_from_dict(cfg, solver_name=solver))
-    o = orc.Oracle(cfg, solver=solver, num_threads=8)
-    return sim, o
-
-
-def assert_same(a, b, what):
-    assert a.shape == b.shape, what
-    if not np.array_equal(a, b):
-        bad = np.argwhere(a != b)
-        raise AssertionError("%s differs at %d of %d entries; rel err %.3e; first %s: %r vs %r" % (
-            what, len(bad), a.size, rel_err(a, b), bad[0], a[tuple(bad[0])], b[tuple(bad[0])]))
+    return sim, make_oracle(cfg, solver)
 
 
 def test_device_divide_sqrt_are_ieee():
@@ -46,12 +38,12 @@ def test_device_divide_sqrt_are_ieee():
                         rng.uniform(1.0, 7.0, len(edge))]).astype(np.float32)
     with np.errstate(over="ignore", under="ignore"):
         quotient = (a / b).astype(np.float32)
-    assert_same(nat.selftest_math(0, a, b), quotient, "a/b")
-    assert_same(nat.selftest_math(1, a, b), np.sqrt(a).astype(np.float32), "sqrt(a)")
+    same_values(nat.selftest_math(0, a, b), quotient, "a/b")
+    same_values(nat.selftest_math(1, a, b), np.sqrt(a).astype(np.float32), "sqrt(a)")
     # the sweeps' 11-instruction root (sph_device.h sqrt_rn): correctly rounded on [0, 2^63), denormals and perfect squares included
     s = np.concatenate([a[a < 9e18], (rng.integers(1, 4000, 50000).astype(np.float32) ** 2) * np.float32(2.0) ** rng.integers(-60, 20, 50000).astype(np.float32),
                         np.float32([0.0, 1e-45, 1.1754944e-38, 1.1754942e-38, 0.01, 0.010000001, 9.2e18])]).astype(np.float32)
-    assert_same(nat.selftest_math(6, s, s), np.sqrt(s).astype(np.float32), "sqrt_rn(s)")
+    same_values(nat.selftest_math(6, s, s), np.sqrt(s).astype(np.float32), "sqrt_rn(s)")
 
 
 def test_wave_primitives():
@@ -80,22 +72,22 @@ def test_device_kernel_functions_match_oracle():
     h = np.full_like(r, 0.1)
     w = nat.selftest_math(2, r, h)
     w_ref = np.array([orc.cubic_kernel(float(x), 0.1) for x in r], dtype=np.float32)
-    assert_same(w, w_ref, "cubic_kernel")
+    same_values(w, w_ref, "cubic_kernel")
     x = np.concatenate([rng.uniform(-0.07, 0.07, 60000), 10.0 ** rng.uniform(-8, -2, 5000), [0.0, 0.05, 1e-7]]).astype(np.float32)
     y = np.concatenate([rng.uniform(-0.07, 0.07, 60000), -(10.0 ** rng.uniform(-8, -2, 5000)), [0.0, 0.0, 0.0]]).astype(np.float32)
     g = [nat.selftest_math(3 + k, x, y) for k in range(3)]
     ref = np.array([orc.cubic_kernel_derivative([a, b, np.float32(0.25) * a], 0.1) for a, b in zip(x, y)], dtype=np.float32)
     for k in range(3):
-        assert_same(g[k], ref[:, k], "cubic_kernel_derivative[%d]" % k)
+        same_values(g[k], ref[:, k], "cubic_kernel_derivative[%d]" % k)
 
 
 @pytest.mark.parametrize("scene", ["wcsph_tiny_wall", "dfsph_small", "breaking_dam_30k_wcsph"])
 def test_initial_conditions(scene):
     sim, o = make(scene)
     assert (sim.n_fluid, sim.n_wall, tuple(sim.grid), sim.n_cells) == (o.N, o.Nb, tuple(o.grid), o.C)
-    assert_same(sim.download(nat.F_POS), o.get(orc.F_POS), "fluid lattice")
-    assert_same(sim.download(nat.F_WALL_POS, nat.SPECIES_WALL), o.get(orc.F_WALL_POS), "wall positions")
-    assert_same(sim.download(nat.F_WALL_VOL, nat.SPECIES_WALL), o.get(orc.F_WALL_VOL), "wall volumes")
+    same_values(sim.download(nat.F_POS), o.get(orc.F_POS), "fluid lattice")
+    same_values(sim.download(nat.F_WALL_POS, nat.SPECIES_WALL), o.get(orc.F_WALL_POS), "wall positions")
+    same_values(sim.download(nat.F_WALL_VOL, nat.SPECIES_WALL), o.get(orc.F_WALL_VOL), "wall volumes")
     sim.close(); o.close()
 
 
@@ -104,9 +96,9 @@ def test_density_alpha_neighbour_count_at_rest(scene, kats):
     sim, o = make(scene)
     sim.compute_alpha()
     o.compute_rho(); o.compute_alpha(); o.compute_nbr_count()
-    assert_same(sim.download(nat.F_NBR_COUNT), o.get(orc.F_NBR_COUNT), "neighbour count")
-    assert_same(sim.download(nat.F_RHO), o.get(orc.F_RHO), "rho")
-    assert_same(sim.download(nat.F_ALPHA), o.get(orc.F_ALPHA), "alpha")
+    same_values(sim.download(nat.F_NBR_COUNT), o.get(orc.F_NBR_COUNT), "neighbour count")
+    same_values(sim.download(nat.F_RHO), o.get(orc.F_RHO), "rho")
+    same_values(sim.download(nat.F_ALPHA), o.get(orc.F_ALPHA), "alpha")
     sim.close(); o.close()
 
 
@@ -119,10 +111,10 @@ def test_density_on_perturbed_positions():
     sim.upload(nat.F_POS, pos); o.set(orc.F_POS, pos)
     sim.compute_alpha()
     o.build_grid(); o.compute_rho(); o.compute_alpha(); o.compute_nbr_count()
-    assert_same(sim.download(nat.F_POS), pos, "upload/download round trip")
-    assert_same(sim.download(nat.F_NBR_COUNT), o.get(orc.F_NBR_COUNT), "neighbour count")
-    assert_same(sim.download(nat.F_RHO), o.get(orc.F_RHO), "rho")
-    assert_same(sim.download(nat.F_ALPHA), o.get(orc.F_ALPHA), "alpha")
+    same_values(sim.download(nat.F_POS), pos, "upload/download round trip")
+    same_values(sim.download(nat.F_NBR_COUNT), o.get(orc.F_NBR_COUNT), "neighbour count")
+    same_values(sim.download(nat.F_RHO), o.get(orc.F_RHO), "rho")
+    same_values(sim.download(nat.F_ALPHA), o.get(orc.F_ALPHA), "alpha")
     sim.close(); o.close()
 
 
@@ -137,11 +129,11 @@ def test_wcsph_steps(scene, steps):
         v, vo = sim.download(nat.F_VEL), o.get(orc.F_VEL)
         assert np.isfinite(p).all()
         assert rel_err(p, po) <= REL_TOL and rel_err(v, vo) <= REL_TOL, (done, rel_err(p, po), rel_err(v, vo))
-        assert_same(p, po, "pos after %d steps" % done)
-        assert_same(v, vo, "vel after %d steps" % done)
-    assert_same(sim.download(nat.F_RHO), o.get(orc.F_RHO), "rho")
-    assert_same(sim.download(nat.F_PRESSURE), o.get(orc.F_PRESSURE), "pressure")
-    assert_same(sim.download(nat.F_ACC), o.get(orc.F_ACC), "acc")
+        same_values(p, po, "pos after %d steps" % done)
+        same_values(v, vo, "vel after %d steps" % done)
+    same_values(sim.download(nat.F_RHO), o.get(orc.F_RHO), "rho")
+    same_values(sim.download(nat.F_PRESSURE), o.get(orc.F_PRESSURE), "pressure")
+    same_values(sim.download(nat.F_ACC), o.get(orc.F_ACC), "acc")
     sim.close(); o.close()
 
 
@@ -159,11 +151,11 @@ def test_dfsph_steps(scene, steps):
     p, po = sim.download(nat.F_POS), o.get(orc.F_POS)
     v, vo = sim.download(nat.F_VEL), o.get(orc.F_VEL)
     assert rel_err(p, po) <= REL_TOL and rel_err(v, vo) <= REL_TOL
-    assert_same(p, po, "pos"); assert_same(v, vo, "vel")
+    same_values(p, po, "pos"); same_values(v, vo, "vel")
     for f_gpu, f_orc, name in ((nat.F_RHO, orc.F_RHO, "rho"), (nat.F_ALPHA, orc.F_ALPHA, "alpha"), (nat.F_WARM_K, orc.F_WARM_K, "warm_start_k"),
                                (nat.F_RHO_DER, orc.F_RHO_DER, "rho_derivative"), (nat.F_RHO_ADV, orc.F_RHO_ADV, "rho_adv"),
                                (nat.F_VEL_ADV, orc.F_VEL_ADV, "vel_adv")):
-        assert_same(sim.download(f_gpu), o.get(f_orc), name)
+        same_values(sim.download(f_gpu), o.get(f_orc), name)
     assert sim.scalar(nat.S_DELTA_TIME) == o.dt
     sim.close(); o.close()
 
@@ -182,7 +174,7 @@ def test_python_api_mirrors_reference_surface():
     assert abs(solver.delta_time[None] - 2.5e-4) < 1e-10 and solver.simulate_cnt[None] == 3
     o = orc.Oracle(cfg, solver="wcsph", num_threads=8)
     o.step_wcsph(3)
-    assert_same(pos, o.get(orc.F_POS), "pos via Python API")
+    same_values(pos, o.get(orc.F_POS), "pos via Python API")
     cfg2 = scenes.get("dfsph_small")
     ps2 = ParticleSystem(cfg2)
     s2 = dfsph_solver(ps2, cfg2)
@@ -294,14 +286,14 @@ def test_particles_outside_the_grid(solver):
         elif solver == "pbf":
             sim.step_pbf(1); o.step_pbf(1)
             assert o.lost >= 1
-            assert_same(sim.download(nat.F_PBF_LAMBDA), o.get(orc.F_PBF_LAMBDA), "pbf_lambda")
-            assert_same(sim.download(nat.F_PBF_DELTA_POS), o.get(orc.F_PBF_DELTA_POS), "delta_pos")
+            same_values(sim.download(nat.F_PBF_LAMBDA), o.get(orc.F_PBF_LAMBDA), "pbf_lambda")
+            same_values(sim.download(nat.F_PBF_DELTA_POS), o.get(orc.F_PBF_DELTA_POS), "delta_pos")
         else:
             st = sim.step_dfsph(1); o.step_dfsph(1, 100)
             assert st.lost == o.lost and st.lost >= 1
-        assert_same(sim.download(nat.F_POS), o.get(orc.F_POS), "pos")
-        assert_same(sim.download(nat.F_VEL), o.get(orc.F_VEL), "vel")
-    assert_same(sim.download(nat.F_RHO), o.get(orc.F_RHO), "rho")
+        same_values(sim.download(nat.F_POS), o.get(orc.F_POS), "pos")
+        same_values(sim.download(nat.F_VEL), o.get(orc.F_VEL), "vel")
+    same_values(sim.download(nat.F_RHO), o.get(orc.F_RHO), "rho")
     sim.close(); o.close()
 
 
@@ -329,6 +321,6 @@ def test_oracle_continues_from_device_state(scene, pre, post):
                                                                             o.last_stats.dens_err, o.last_stats.dt)
         else:
             sim.step_wcsph(1); o.step_wcsph(1)
-    assert_same(sim.download(nat.F_POS), o.get(orc.F_POS), "pos")
-    assert_same(sim.download(nat.F_VEL), o.get(orc.F_VEL), "vel")
+    same_values(sim.download(nat.F_POS), o.get(orc.F_POS), "pos")
+    same_values(sim.download(nat.F_VEL), o.get(orc.F_VEL), "vel")
     sim.close(); o.close()

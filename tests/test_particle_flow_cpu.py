@@ -5,6 +5,7 @@ import math
 import numpy as np
 import pytest
 
+import harness as h
 import particle_flow as pf
 from cfd_taichi_amd import _native as nat
 from cfd_taichi_amd import emitter, scenes
@@ -15,12 +16,12 @@ def test_lattice_counts_and_prefix(walls):
     """640, 704, 832 particles, and the tall lattices begin with the short one, id for id"""
     pos = {}
     for n in pf.HEIGHTS:
-        o = pf.make_oracle(pf.config("dfsph", walls, n), num_threads=1)
+        o = h.make_oracle(pf.config("dfsph", walls, n), num_threads=1)
         assert o.N == n
         pos[n] = o.get(pf.orc.F_POS)
         o.close()
     for n in (704, 832):
-        pf.same(pos[n][:640], pos[640], "the first 640 of %d" % n)
+        h.same_bits(pos[n][:640], pos[640], "the first 640 of %d" % n)
         assert (pos[n][640:, 1] > pos[640][:, 1].max()).all()        # whole layers above
     lo, hi = pf.inner_box(pf.config("dfsph", walls, 640))
     assert 0 < pf.in_box(pos[640], lo, hi).sum() <= 64
@@ -30,7 +31,7 @@ def test_lattice_counts_and_prefix(walls):
 
 def test_threshold_counts():
     for n in pf.THRESHOLD:
-        o = pf.make_oracle(pf.threshold_config("dfsph", n), num_threads=1)
+        o = h.make_oracle(pf.threshold_config("dfsph", n), num_threads=1)
         assert o.N == n
         o.close()
     assert 64512 < 65536 < 66560 <= 100000
@@ -45,7 +46,7 @@ def test_pcisph_delta_is_the_same_on_both_lattices(walls):
     704 -> 832, on which all three agree."""
     got = []
     for n in (640, 704, 832):
-        o = pf.make_oracle(pf.config("pcisph", walls, n), num_threads=1)
+        o = h.make_oracle(pf.config("pcisph", walls, n), num_threads=1)
         got.append((np.float32(o.pcisph_delta).tobytes(), o.pcisph_max_index))
         o.close()
     assert got[0][0] == got[1][0] == got[2][0] and got[0][1][1] == got[1][1][1] == got[2][1][1], got

@@ -2,7 +2,7 @@
 
 What tests/test_edge_cases_gpu.py and test_particles_outside_the_grid ask of the four older solvers, asked of the solver that walks its 27 cells
 itself (k_pbf_xsph: batches of four, its own Morton slot look-up) and has a second set of pair bodies (RX, csrc/sph_pbf_kernels.h).  One oracle run
-per input, compared with the four handles of tests/test_pbf_relaxed_gpu.py's KNOBS (quad or plain kernels, linear or Morton cells); every knob that
+per input, compared with the four handles of tests/test_pbf_relaxed_gpu.py's VARIANTS (quad or plain kernels, linear or Morton cells); every knob that
 was set is asserted to appear in sim.overrides().
 
   exact     rho, pbf_lambda, delta_pos, pos, vel bit for bit against the f32 oracle after EVERY step: ragged 25 steps, coincident 5, a fluid
@@ -29,7 +29,8 @@ import pytest
 import pbf_edge_states as pe
 import pbf_states as pb
 from cfd_taichi_amd import _native as nat
-from test_pbf_relaxed_gpu import KNOBS, handles, held, report, same
+from harness import same_values
+from test_pbf_relaxed_gpu import VARIANTS, handles, held, report
 
 pytestmark = pytest.mark.gpu
 
@@ -42,7 +43,7 @@ SEEDED_IDS = ["%s-seed%d" % c for c in SEEDED]
 def lockstep(inp, steps, knobs, monkeypatch, before=None):
     """the exact handle under `knobs` against the f32 oracle's run of the same input, every field after every step"""
     r32 = pe.references(inp, steps)[0]
-    rx, ex = handles(inp.cfg, KNOBS[knobs], monkeypatch)
+    rx, ex = handles(inp.cfg, VARIANTS[knobs], monkeypatch)
     rx.close()
     try:
         assert ex.n_fluid == len(inp.pos) and ex.scalar(nat.S_ARITH_RELAXED) == 0.0
@@ -53,13 +54,13 @@ def lockstep(inp, steps, knobs, monkeypatch, before=None):
             ex.step_pbf(1)
             got = pb.snapshot(ex.download)
             for name, _ in pb.FIELDS:
-                same(got[name], r32[s][name], "%s, %s: %s after step %d, exact handle and f32 oracle" % (inp.label, knobs, name, s + 1))
+                same_values(got[name], r32[s][name], "%s, %s: %s after step %d, exact handle and f32 oracle" % (inp.label, knobs, name, s + 1))
     finally:
         ex.close()
     return r32
 
 
-@pytest.mark.parametrize("knobs", KNOBS)
+@pytest.mark.parametrize("knobs", VARIANTS)
 @pytest.mark.parametrize("scene,water", RAGGED, ids=RAGGED_IDS)
 def test_ragged_particle_counts(scene, water, knobs, monkeypatch):
     """1, 6, 73 and 82 particles: below one quad workgroup's 64, just above it, far below a plain workgroup's 256"""
@@ -68,7 +69,7 @@ def test_ragged_particle_counts(scene, water, knobs, monkeypatch):
     lockstep(inp, 25, knobs, monkeypatch)
 
 
-@pytest.mark.parametrize("knobs", KNOBS)
+@pytest.mark.parametrize("knobs", VARIANTS)
 @pytest.mark.parametrize("scene,seed", SEEDED, ids=SEEDED_IDS)
 def test_coincident_particles_and_cell_faces(scene, seed, knobs, monkeypatch):
     inp = pe.coincident(scene, seed)
@@ -79,7 +80,7 @@ def test_coincident_particles_and_cell_faces(scene, seed, knobs, monkeypatch):
     assert not np.array_equal(r32[0]["pos"][b[0]], r32[0]["pos"][b[1]]), "pair (b) did not separate: its xsph term was not seen"
 
 
-@pytest.mark.parametrize("knobs", KNOBS)
+@pytest.mark.parametrize("knobs", VARIANTS)
 @pytest.mark.parametrize("seed", pe.SEEDS)
 def test_fluid_particle_on_a_wall_particle(seed, knobs, monkeypatch):
     inp = pe.on_a_wall_particle(seed)
@@ -87,13 +88,13 @@ def test_fluid_particle_on_a_wall_particle(seed, knobs, monkeypatch):
 
     def walls_agree(sim):
         wall = sim.download(nat.F_WALL_POS, nat.SPECIES_WALL)
-        same(wall, inp.wall, "wall positions, handle and f32 oracle")
+        same_values(wall, inp.wall, "wall positions, handle and f32 oracle")
         assert np.array_equal(wall[w], inp.pos[i])
     r32 = lockstep(inp, 5, knobs, monkeypatch, before=walls_agree)
     assert r32[0]["pbf_lambda"][i] != 0
 
 
-@pytest.mark.parametrize("knobs", KNOBS)
+@pytest.mark.parametrize("knobs", VARIANTS)
 @pytest.mark.parametrize("scene", pe.SCENES)
 def test_spray_and_clump(scene, knobs, monkeypatch):
     """k_pbf_xsph's batches of four over cells of 1 and of 40 or 41 particles (j == i in mid-batch), and lists of 39 and more"""
@@ -106,7 +107,7 @@ def test_spray_and_clump(scene, knobs, monkeypatch):
     assert (r32[0]["pbf_lambda"][inp.marks["clump"]] != 0).all()
 
 
-@pytest.mark.parametrize("knobs", KNOBS)
+@pytest.mark.parametrize("knobs", VARIANTS)
 @pytest.mark.parametrize("scene,seed", SEEDED, ids=SEEDED_IDS)
 def test_particles_outside_the_grid(scene, seed, knobs, monkeypatch):
     """48 particles beyond the six faces: some in the cell margin and in the lists, some in wrapped cells, some in no cell at all"""
@@ -120,7 +121,7 @@ def test_particles_outside_the_grid(scene, seed, knobs, monkeypatch):
 def relaxed(inp, steps, knobs, monkeypatch, ratios):
     """failures of the relaxed handle under `knobs` over `steps` steps of one input; the exact handle next to it must be the f32 oracle"""
     r32, r64 = pe.references(inp, steps)
-    rx, ex = handles(inp.cfg, KNOBS[knobs], monkeypatch)
+    rx, ex = handles(inp.cfg, VARIANTS[knobs], monkeypatch)
     try:
         pe.upload(rx, inp); pe.upload(ex, inp)
         got, twin = [], []
@@ -135,7 +136,7 @@ def relaxed(inp, steps, knobs, monkeypatch, ratios):
     for s in range(steps):
         label = "%s step %d:" % (inp.label, s + 1)
         for name, _ in pb.FIELDS:
-            same(twin[s][name], r32[s][name], "%s %s, exact handle and f32 oracle" % (label, name))
+            same_values(twin[s][name], r32[s][name], "%s %s, exact handle and f32 oracle" % (label, name))
         try:
             failures += held(label, inp.cfg, inp.pos, got[s], r32[s], r64[s], ratios)
         except AssertionError as e:        # a discrete set or a non-finite value: reported with the bounds of the other steps, not instead of them
@@ -143,7 +144,7 @@ def relaxed(inp, steps, knobs, monkeypatch, ratios):
     return failures, got
 
 
-@pytest.mark.parametrize("knobs", KNOBS)
+@pytest.mark.parametrize("knobs", VARIANTS)
 @pytest.mark.parametrize("scene", pe.SCENES)
 def test_relaxed_coincident_particles(scene, knobs, monkeypatch):
     failures, ratios = [], {}
@@ -166,7 +167,7 @@ def test_relaxed_coincident_particles(scene, knobs, monkeypatch):
     assert not failures, "\n".join(failures)
 
 
-@pytest.mark.parametrize("knobs", KNOBS)
+@pytest.mark.parametrize("knobs", VARIANTS)
 @pytest.mark.parametrize("scene", pe.SCENES)
 def test_relaxed_spray_and_clump(scene, knobs, monkeypatch):
     ratios = {}
@@ -175,7 +176,7 @@ def test_relaxed_spray_and_clump(scene, knobs, monkeypatch):
     assert not failures, "\n".join(failures)
 
 
-@pytest.mark.parametrize("knobs", KNOBS)
+@pytest.mark.parametrize("knobs", VARIANTS)
 @pytest.mark.parametrize("scene", pe.SCENES)
 def test_relaxed_ragged_73(scene, knobs, monkeypatch):
     inp = pe.ragged(scene, next(w for w, n in pe.RAGGED.items() if n == 73))

@@ -13,27 +13,10 @@ import pytest
 
 from cfd_taichi_amd import _native as nat
 from cfd_taichi_amd import scenes
+from harness import same_values, squeeze
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
-
-
-def same(a, b, what):
-    a, b = np.asarray(a), np.asarray(b)
-    if not np.array_equal(a, b):
-        bad = np.argwhere(a != b)
-        scale = max(float(np.abs(b).max()), 1e-30)
-        raise AssertionError("%s differs at %d of %d entries, rel err %.3e, first %s: %r vs %r" % (
-            what, len(bad), a.size, float(np.abs(a.astype(np.float64) - b).max()) / scale, bad[0], a[tuple(bad[0])], b[tuple(bad[0])]))
-
-
-def squeeze(sim, o, factor=0.9):
-    """The rest lattice is under-dense by the reference's density sum (no self term): the constraint max(rho / rho_0 - 1, 0) would stay
-    at zero until the column has collapsed.  Squeezing the lattice makes lambda and delta_pos act from the first step."""
-    pos = o.get(orc.F_POS)
-    about = pos.min(0)
-    sq = (about + (pos - about) * np.float32(factor)).astype(np.float32)
-    o.set(orc.F_POS, sq); sim.upload(nat.F_POS, sq)
 
 
 @pytest.mark.parametrize("scene,steps,squeezed", [("pbf_tiny_wall", 150, True), ("pbf_tiny_clamp", 150, True), ("pbf_small", 60, False),
@@ -51,11 +34,11 @@ def test_pbf_steps(scene, steps, squeezed):
         o.step_pbf(1)
         if s % 25 == 0 or s == steps - 1:
             lam = o.get(orc.F_PBF_LAMBDA)
-            same(sim.download(nat.F_RHO), o.get(orc.F_RHO), "rho, step %d" % s)
-            same(sim.download(nat.F_PBF_LAMBDA), lam, "pbf_lambda, step %d" % s)
-            same(sim.download(nat.F_PBF_DELTA_POS), o.get(orc.F_PBF_DELTA_POS), "delta_pos, step %d" % s)
-            same(sim.download(nat.F_POS), o.get(orc.F_POS), "pos, step %d" % s)
-            same(sim.download(nat.F_VEL), o.get(orc.F_VEL), "vel, step %d" % s)
+            same_values(sim.download(nat.F_RHO), o.get(orc.F_RHO), "rho, step %d" % s)
+            same_values(sim.download(nat.F_PBF_LAMBDA), lam, "pbf_lambda, step %d" % s)
+            same_values(sim.download(nat.F_PBF_DELTA_POS), o.get(orc.F_PBF_DELTA_POS), "delta_pos, step %d" % s)
+            same_values(sim.download(nat.F_POS), o.get(orc.F_POS), "pos, step %d" % s)
+            same_values(sim.download(nat.F_VEL), o.get(orc.F_VEL), "vel, step %d" % s)
             active = active or bool((lam != 0).any())
     pos = sim.download(nat.F_POS)
     assert np.isfinite(pos).all()
@@ -74,10 +57,10 @@ def test_pbf_mirror_api_and_30k():
     o = orc.Oracle(cfg, num_threads=8)
     for _ in range(5):
         solver.step(); o.step_pbf(1)
-    same(ps.fluid_particles.pos.to_numpy(), o.get(orc.F_POS), "pos")
-    same(ps.fluid_particles.vel.to_numpy(), o.get(orc.F_VEL), "vel")
-    same(solver.pbf_lambda.to_numpy(), o.get(orc.F_PBF_LAMBDA), "lambda")
-    same(solver.pos_predict.to_numpy(), o.get(orc.F_POS), "pos_predict == pos after a step (pbf_solver.py:84)")
+    same_values(ps.fluid_particles.pos.to_numpy(), o.get(orc.F_POS), "pos")
+    same_values(ps.fluid_particles.vel.to_numpy(), o.get(orc.F_VEL), "vel")
+    same_values(solver.pbf_lambda.to_numpy(), o.get(orc.F_PBF_LAMBDA), "lambda")
+    same_values(solver.pos_predict.to_numpy(), o.get(orc.F_POS), "pos_predict == pos after a step (pbf_solver.py:84)")
     solver.step(400)
     pos = ps.fluid_particles.pos.to_numpy()
     assert np.isfinite(pos).all() and solver.delta_time[None] == np.float32(2.5e-4) and solver.simulate_cnt[None] == 405
@@ -105,18 +88,18 @@ def test_pbf_compute_density_is_poly6_and_leaves_lambda_alone(scene):
     lam = o.get(orc.F_PBF_LAMBDA).copy()
     assert (lam != 0).any()
     pos, vel, dpos = sim.download(nat.F_POS), sim.download(nat.F_VEL), sim.download(nat.F_PBF_DELTA_POS)
-    same(dpos, o.get(orc.F_PBF_DELTA_POS), "delta_pos before compute_density")
+    same_values(dpos, o.get(orc.F_PBF_DELTA_POS), "delta_pos before compute_density")
     sim.compute_density()
     o.build_grid(); o.compute_rho()
-    same(sim.download(nat.F_RHO), o.get(orc.F_RHO), "rho after compute_density")
-    same(sim.download(nat.F_PBF_LAMBDA), lam, "pbf_lambda after compute_density")
-    same(sim.download(nat.F_PBF_DELTA_POS), dpos, "delta_pos after compute_density (carried through the re-sort like pbf_lambda)")
-    same(sim.download(nat.F_POS), pos, "pos after compute_density")
-    same(sim.download(nat.F_VEL), vel, "vel after compute_density")
+    same_values(sim.download(nat.F_RHO), o.get(orc.F_RHO), "rho after compute_density")
+    same_values(sim.download(nat.F_PBF_LAMBDA), lam, "pbf_lambda after compute_density")
+    same_values(sim.download(nat.F_PBF_DELTA_POS), dpos, "delta_pos after compute_density (carried through the re-sort like pbf_lambda)")
+    same_values(sim.download(nat.F_POS), pos, "pos after compute_density")
+    same_values(sim.download(nat.F_VEL), vel, "vel after compute_density")
     # rho is the poly6 sum, not the cubic spline one: the two differ on a squeezed lattice
     sim.step_pbf(1); o.step_pbf(1)
-    same(sim.download(nat.F_POS), o.get(orc.F_POS), "pos, the step after")
-    same(sim.download(nat.F_PBF_LAMBDA), o.get(orc.F_PBF_LAMBDA), "pbf_lambda, the step after")
+    same_values(sim.download(nat.F_POS), o.get(orc.F_POS), "pos, the step after")
+    same_values(sim.download(nat.F_PBF_LAMBDA), o.get(orc.F_PBF_LAMBDA), "pbf_lambda, the step after")
     sim.close(); o.close()
 
 
@@ -141,7 +124,7 @@ def lockstep(sim, o, steps):
     for s in range(steps):
         sim.step_pbf(1); o.step_pbf(1)
         for name, f, of in FIELDS:
-            same(sim.download(f), o.get(of), "%s, step %d" % (name, s + 1))
+            same_values(sim.download(f), o.get(of), "%s, step %d" % (name, s + 1))
         active = max(active, int((o.get(orc.F_PBF_LAMBDA) != 0).sum()))
     return active
 

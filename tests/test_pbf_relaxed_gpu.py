@@ -19,13 +19,14 @@ import pytest
 import pbf_states as pb
 from cfd_taichi_amd import _native as nat
 from cfd_taichi_amd import scenes
+from harness import same_values, squeezed
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
 
 KNOB_NAMES = ("SPH_QUAD", "SPH_CELL_ORDER", "SPH_CELL_TILE")
 # the four handles of tests/test_second_restatement_gpu.py's PBF cases: which kernels and which cell order
-KNOBS = {"quad-linear": {},
+VARIANTS = {"quad-linear": {},
          "plain-linear": {"SPH_QUAD": "0"},
          "quad-morton": {"SPH_CELL_ORDER": "morton", "SPH_CELL_TILE": "4"},
          "plain-morton": {"SPH_CELL_ORDER": "morton", "SPH_CELL_TILE": "4", "SPH_QUAD": "0"}}
@@ -48,10 +49,6 @@ def handles(cfg, knobs, monkeypatch):
     return rx, ex
 
 
-def same(a, b, what):
-    assert a.shape == b.shape and np.array_equal(a, b), "%s: differ at %d of %d entries" % (what, int((a != b).sum()), a.size)
-
-
 def held(label, cfg, pos0, cand, r32, r64, ratios, fields=None, sets=True):
     """items 3 and 4 of the docstring for one step of one participant; collects the worst ratio per field.  sets: on the states whose discrete sets
     tests/test_pbf_relaxed_cpu.py has shown to agree between the two oracles"""
@@ -70,7 +67,7 @@ def report(label, ratios):
     print("%s worst ratio (relaxed / (f32 oracle + floor)) per field: %s" % (label, "  ".join("%s %.2f" % kv for kv in ratios.items())))
 
 
-CHAIN = [(sc, kind, kn) for sc, kind, _ in pb.CASES for kn in KNOBS]
+CHAIN = [(sc, kind, kn) for sc, kind, _ in pb.CASES for kn in VARIANTS]
 
 
 @pytest.mark.parametrize("scene,kind,knobs", CHAIN, ids=["%s-%s-%s" % c for c in CHAIN])
@@ -80,7 +77,7 @@ def test_one_relaxed_step_against_the_f64_oracle(scene, kind, knobs, monkeypatch
     label = "%s %s %s:" % (scene, kind, knobs)
     failures, ratios = [], {}
     for seed in pb.SEEDS:
-        rx, ex = handles(cfg, KNOBS[knobs], monkeypatch)
+        rx, ex = handles(cfg, VARIANTS[knobs], monkeypatch)
         try:
             a, b = pb.run_handle(rx, scene, kind, seed, 1)[0], pb.run_handle(ex, scene, kind, seed, 1)[0]
             assert rx.scalar(nat.S_ARITH_RELAXED) == 1.0 and ex.scalar(nat.S_ARITH_RELAXED) == 0.0
@@ -88,7 +85,7 @@ def test_one_relaxed_step_against_the_f64_oracle(scene, kind, knobs, monkeypatch
             rx.close(); ex.close()
         r32, r64 = (r[0] for r in pb.references(scene, kind, seed, dict((c[:2], c[2]) for c in pb.CASES)[(scene, kind)]))
         for name, _ in pb.FIELDS:          # the exact handle IS the f32 oracle
-            same(b[name], r32[name], "%s seed %d %s, exact handle and f32 oracle" % (label, seed, name))
+            same_values(b[name], r32[name], "%s seed %d %s, exact handle and f32 oracle" % (label, seed, name))
         assert not np.array_equal(a["rho"], b["rho"]), "the relaxed handle gave the exact handle's rho: it ran the exact sweeps"
         if kind == "clamp":
             assert pb.clamped(cfg, a["pos"]).any(1).sum() >= 50
@@ -132,19 +129,13 @@ def water_block(nx, ny, nz, margin=0.5):
     return cfg
 
 
-def squeezed(pos, factor=0.9):
-    """the rest lattice drawn together about its lowest corner, so that lambda and delta_pos act from the first step"""
-    about = pos.min(0)
-    return (about + (pos - about) * np.float32(factor)).astype(np.float32)
-
-
 def squeezed_oracles(cfg, steps, num_threads, after=None):
     """(start positions, f32 fields, f64 fields) after `steps` squeezed steps (and `after(o)`) on both oracles"""
     out, pos0 = [], None
     for precision in ("f32", "f64"):
         o = orc.Oracle(cfg, num_threads=num_threads, precision=precision)
         if pos0 is None:
-            pos0 = squeezed(o.get(orc.F_POS))
+            pos0 = squeezed(o.get(orc.F_POS), 0.9)
         o.set(orc.F_POS, pos0)
         o.step_pbf(steps)
         if after:
@@ -217,7 +208,7 @@ def test_compute_density_on_a_relaxed_handle(monkeypatch):
         rx.close()
     assert (before["pbf_lambda"] != 0).any(), "pbf_lambda is all zero: 'untouched' would prove nothing"
     for name in ("pbf_lambda", "delta_pos", "pos", "vel"):
-        same(got[name], before[name], "%s before and after compute_density" % name)
+        same_values(got[name], before[name], "%s before and after compute_density" % name)
     ratios = {}
     failures = held("compute_density:", cfg, pos0, got, r32, r64, ratios, fields=("rho",), sets=False)
     report("compute_density:", ratios)
@@ -239,13 +230,13 @@ def test_mirror_api(monkeypatch):
     assert solver.arith == "exact" and solver._sim.scalar(nat.S_ARITH_RELAXED) == 0.0
     o = orc.Oracle(cfg, num_threads=8)
     try:
-        pos0 = squeezed(o.get(orc.F_POS))
+        pos0 = squeezed(o.get(orc.F_POS), 0.9)
         o.set(orc.F_POS, pos0)
         ps.fluid_particles.pos.from_numpy(pos0)
         solver.step(2); o.step_pbf(2)
-        same(ps.fluid_particles.pos.to_numpy(), o.get(orc.F_POS), "pos")
-        same(ps.fluid_particles.vel.to_numpy(), o.get(orc.F_VEL), "vel")
-        same(solver.pbf_lambda.to_numpy(), o.get(orc.F_PBF_LAMBDA), "pbf_lambda")
+        same_values(ps.fluid_particles.pos.to_numpy(), o.get(orc.F_POS), "pos")
+        same_values(ps.fluid_particles.vel.to_numpy(), o.get(orc.F_VEL), "vel")
+        same_values(solver.pbf_lambda.to_numpy(), o.get(orc.F_PBF_LAMBDA), "pbf_lambda")
         assert (solver.pbf_lambda.to_numpy() != 0).any()
     finally:
         o.close()

@@ -22,24 +22,17 @@ import pytest
 
 from cfd_taichi_amd import _native as nat
 from cfd_taichi_amd import scenes
+from harness import make_handle
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
 
 
-def make(scene, arith, morton=True):
+def make(scene, arith, monkeypatch, morton=True, env=None):
+    """(config, handle): on the Morton curve (the staged sweeps) unless morton is false; env: further overrides"""
     cfg = scenes.get(scene)
-    old = os.environ.get("SPH_CELL_ORDER")
-    if morton:
-        os.environ["SPH_CELL_ORDER"] = "morton"
-    try:
-        sim = nat.Simulation(nat.config_from_dict(cfg, arith=arith))
-    finally:
-        if morton:
-            if old is None:
-                os.environ.pop("SPH_CELL_ORDER", None)
-            else:
-                os.environ["SPH_CELL_ORDER"] = old
+    sim = make_handle(cfg, monkeypatch, dict(env or {}, **({"SPH_CELL_ORDER": "morton"} if morton else {})), arith)
+    monkeypatch.delenv("SPH_CELL_ORDER", raising=False)
     return cfg, sim
 
 
@@ -53,13 +46,13 @@ def quantiles(a, b, q=(0.5, 0.99)):
 
 
 @pytest.mark.parametrize("scene", ["dfsph_small", "dfsph_dam_x"])
-def test_relaxed_is_active_and_exact_is_not(scene):
-    _, rx = make(scene, nat.ARITH_RELAXED)
-    _, ex = make(scene, nat.ARITH_EXACT)
+def test_relaxed_is_active_and_exact_is_not(scene, monkeypatch):
+    _, rx = make(scene, nat.ARITH_RELAXED, monkeypatch)
+    _, ex = make(scene, nat.ARITH_EXACT, monkeypatch)
     rx.step_dfsph(1); ex.step_dfsph(1)
     assert rx.scalar(nat.S_ARITH_RELAXED) == 1.0 and ex.scalar(nat.S_ARITH_RELAXED) == 0.0
     # the same scene in the reference's cell order (quad sweeps, unstaged): since round 4 the exact sweeps with the relaxed kernel functions (KF<true>)
-    _, small = make(scene, nat.ARITH_RELAXED, morton=False)
+    _, small = make(scene, nat.ARITH_RELAXED, monkeypatch, morton=False)
     small.step_dfsph(1)
     assert small.scalar(nat.S_ARITH_RELAXED) == 1.0
     assert rel(small.download(nat.F_POS), ex.download(nat.F_POS)) <= 1e-5 and not np.array_equal(small.download(nat.F_VEL), ex.download(nat.F_VEL))
@@ -68,12 +61,12 @@ def test_relaxed_is_active_and_exact_is_not(scene):
 
 
 @pytest.mark.parametrize("scene,steps", [("dfsph_small", 40), ("dfsph_dam_x", 120), ("dfsph_tiny_clamp", 30), ("breaking_dam_30k_dfsph", 30)])
-def test_relaxed_density_and_alpha_per_particle(scene, steps):
+def test_relaxed_density_and_alpha_per_particle(scene, steps, monkeypatch):
     """D1 in the relaxed arithmetic (k_density_rx: W and grad W from one v_rsq_f32, the walls' share from the per-step wall sums, a tail mask
     for the particle's own padding entry) against the exact kernel on the SAME positions: rho and alpha of every particle within a few
     ulp -- walls, clamp walls, ragged cells after `steps` steps.  (The first-steps test below sees D1 only through what the solver makes of it.)"""
-    cfg, ex = make(scene, nat.ARITH_EXACT)
-    _, rx = make(scene, nat.ARITH_RELAXED)
+    cfg, ex = make(scene, nat.ARITH_EXACT, monkeypatch)
+    _, rx = make(scene, nat.ARITH_RELAXED, monkeypatch)
     ex.step_dfsph(steps)
     for f in (nat.F_POS, nat.F_VEL, nat.F_WARM_K):
         rx.upload(f, ex.download(f))
@@ -99,9 +92,7 @@ def test_relaxed_first_steps_within_1e5_of_the_oracle(scene, monkeypatch):
     `:quad` / `:plain`: the scene in the reference's cell order -- the unstaged sweeps (four lanes per particle / one) with the relaxed kernel
     functions KF<true> (round 4); the others on the Morton curve: the staged tolerance-grade kernels."""
     scene, _, mode = scene.partition(":")
-    if mode == "plain":
-        monkeypatch.setenv("SPH_QUAD", "0")
-    cfg, rx = make(scene, nat.ARITH_RELAXED, morton=not mode)
+    cfg, rx = make(scene, nat.ARITH_RELAXED, monkeypatch, morton=not mode, env={"SPH_QUAD": "0"} if mode == "plain" else None)
 
     canon = orc.Oracle(cfg, num_threads=8)
     legal = []
@@ -129,13 +120,13 @@ def test_relaxed_first_steps_within_1e5_of_the_oracle(scene, monkeypatch):
         o.close()
 
 
-def test_relaxed_stays_inside_the_reference_envelope_100_steps():
+def test_relaxed_stays_inside_the_reference_envelope_100_steps(monkeypatch):
     """dfsph_config_backup's geometry (SURVEY.md 8c iii), 100 steps: the relaxed kernels against the canonical oracle, next to two
     seeded LEGAL executions of the oracle (racy cell-list order, f32 atomic means) against the same canonical run.  Relaxed must not
     be further out than the reference is from itself: per-particle median and 99 % quantile of the position / velocity deviation
     within 2x the larger of the two legal runs' (they differ between seeds by about that)."""
     scene = "dfsph_small"
-    cfg, rx = make(scene, nat.ARITH_RELAXED)
+    cfg, rx = make(scene, nat.ARITH_RELAXED, monkeypatch)
     canon = orc.Oracle(cfg, num_threads=8)
     legal = []
     for seed in (11, 23):

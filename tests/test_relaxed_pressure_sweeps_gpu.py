@@ -28,6 +28,7 @@ import pytest
 import coupled_scenes
 import pressure_states as ps
 from cfd_taichi_amd import _native as nat
+from harness import same_values
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -75,7 +76,7 @@ def test_a_relaxed_request_the_quad_sweeps_do_not_cover_runs_exact(solver, monke
     for s in range(ps.STEPS):
         assert a[s].counts == r32[s].counts and np.array_equal(a[s].nbr, r32[s].nbr), (s, a[s].counts, r32[s].counts)
         for name, _ in ps.FIELDS[solver]:
-            ps.same(a[s][name], r32[s][name], "%s step %d %s, handle and f32 oracle" % (scene, s + 1, name))
+            same_values(a[s][name], r32[s][name], "%s step %d %s, handle and f32 oracle" % (scene, s + 1, name))
 
 
 def test_a_relaxed_request_next_to_a_coupled_body_runs_exact(monkeypatch):
@@ -96,9 +97,9 @@ def test_a_relaxed_request_next_to_a_coupled_body_runs_exact(monkeypatch):
             capped = o.step_pcisph(1)
             assert (st.n_dens, st.capped, st.lost) == (o.last_stats.n_dens, capped, 0), s
             for name, f in ps.FIELDS["pcisph"]:
-                ps.same(rx.download(f), o.get(f), "coupled pcisph step %d %s, handle and f32 oracle" % (s + 1, name))
+                same_values(rx.download(f), o.get(f), "coupled pcisph step %d %s, handle and f32 oracle" % (s + 1, name))
             force = o.get(orc.F_RIGID_FORCE)
-            ps.same(rx.download(nat.F_RIGID_FORCE, nat.SPECIES_RIGID), force, "coupled pcisph step %d, force on the samples" % (s + 1))
+            same_values(rx.download(nat.F_RIGID_FORCE, nat.SPECIES_RIGID), force, "coupled pcisph step %d, force on the samples" % (s + 1))
             felt += float(np.abs(force).sum())
             rx.rigid_step(); o.rigid_step()
         assert felt > 0, "the body never felt the fluid: the RIGID sweeps did not run"

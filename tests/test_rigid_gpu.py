@@ -6,39 +6,30 @@ import pytest
 
 from cfd_taichi_amd import _native as nat
 from cfd_taichi_amd import mesh, scenes
+from harness import make_oracle, same_values
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
-
-
-def same(a, b, what):
-    a, b = np.asarray(a), np.asarray(b)
-    if not np.array_equal(a, b):
-        bad = np.argwhere(a != b)
-        scale = max(float(np.abs(b).max()), 1e-30)
-        raise AssertionError("%s differs at %d of %d entries, rel err %.3e, first %s: %r vs %r" % (
-            what, len(bad), a.size, float(np.abs(a.astype(np.float64) - b).max()) / scale, bad[0], a[tuple(bad[0])], b[tuple(bad[0])]))
 
 
 def make(scene):
     cfg = scenes.get(scene)
     rg = mesh.rigid_from_config(cfg)
     sim = nat.Simulation(nat.config_from_dict(cfg), rigid=rg)
-    o = orc.Oracle(cfg, num_threads=8, rigid=rg)
-    return cfg, sim, o
+    return cfg, sim, make_oracle(cfg, rigid=rg)
 
 
 @pytest.mark.parametrize("scene", ["dfsph_rigid_small", "dfsph_rigid_tilted"])
 def test_rigid_initialisation(scene):
     cfg, sim, o = make(scene)
     assert (sim.n_fluid, sim.n_wall, sim.n_rigid) == (o.N, o.Nb, o.Nr) and sim.n_rigid > 0
-    same(sim.download(nat.F_RIGID_POS, nat.SPECIES_RIGID), o.get(orc.F_RIGID_POS), "rigid positions")
-    same(sim.download(nat.F_RIGID_VOL, nat.SPECIES_RIGID), o.get(orc.F_RIGID_VOL), "rigid volumes")
-    same(sim.download(nat.F_RIGID_MASS, nat.SPECIES_RIGID), o.get(orc.F_RIGID_MASS), "rigid masses")
-    same(sim.download(nat.F_RIGID_VERT, nat.SPECIES_RIGID), o.get(orc.F_RIGID_VERT), "mesh vertices")
+    same_values(sim.download(nat.F_RIGID_POS, nat.SPECIES_RIGID), o.get(orc.F_RIGID_POS), "rigid positions")
+    same_values(sim.download(nat.F_RIGID_VOL, nat.SPECIES_RIGID), o.get(orc.F_RIGID_VOL), "rigid volumes")
+    same_values(sim.download(nat.F_RIGID_MASS, nat.SPECIES_RIGID), o.get(orc.F_RIGID_MASS), "rigid masses")
+    same_values(sim.download(nat.F_RIGID_VERT, nat.SPECIES_RIGID), o.get(orc.F_RIGID_VERT), "mesh vertices")
     a, b = sim.rigid_scalars(), o.rigid_scalars()
-    same(np.float32(a["centroid"]), np.float32(b["centroid"]), "centroid")
-    same(np.float32(a["inertia_inv"]), np.float32(b["inertia_inv"]), "inverse inertia tensor")
+    same_values(np.float32(a["centroid"]), np.float32(b["centroid"]), "centroid")
+    same_values(np.float32(a["inertia_inv"]), np.float32(b["inertia_inv"]), "inverse inertia tensor")
     sim.close(); o.close()
 
 
@@ -46,9 +37,9 @@ def test_density_alpha_count_with_rigid_neighbours():
     cfg, sim, o = make("dfsph_rigid_small")
     sim.compute_alpha()
     o.compute_rho(); o.compute_alpha(); o.compute_nbr_count()
-    same(sim.download(nat.F_NBR_COUNT), o.get(orc.F_NBR_COUNT), "neighbour count (with the rigid-entry quirk)")
-    same(sim.download(nat.F_RHO), o.get(orc.F_RHO), "rho")
-    same(sim.download(nat.F_ALPHA), o.get(orc.F_ALPHA), "alpha")
+    same_values(sim.download(nat.F_NBR_COUNT), o.get(orc.F_NBR_COUNT), "neighbour count (with the rigid-entry quirk)")
+    same_values(sim.download(nat.F_RHO), o.get(orc.F_RHO), "rho")
+    same_values(sim.download(nat.F_ALPHA), o.get(orc.F_ALPHA), "alpha")
     sim.close(); o.close()
 
 
@@ -63,17 +54,17 @@ def test_coupled_steps(scene, steps):
         assert (st.n_div, st.n_dens, st.div_first_err, st.div_err, st.dens_err, st.dt) == (
             so.n_div, so.n_dens, so.div_first_err, so.div_err, so.dens_err, so.dt), s
         if s % 10 == 0:
-            same(sim.download(nat.F_RIGID_FORCE, nat.SPECIES_RIGID), o.get(orc.F_RIGID_FORCE), "force on the body before rigid step %d" % s)
+            same_values(sim.download(nat.F_RIGID_FORCE, nat.SPECIES_RIGID), o.get(orc.F_RIGID_FORCE), "force on the body before rigid step %d" % s)
         sim.rigid_step()
         o.rigid_step()
         a, b = sim.rigid_scalars(), o.rigid_scalars()
         for k in ("centroid", "omega", "vel", "inertia_inv"):
-            same(np.float32(a[k]), np.float32(b[k]), "%s after step %d" % (k, s))
+            same_values(np.float32(a[k]), np.float32(b[k]), "%s after step %d" % (k, s))
         moved = moved or any(abs(v) > 1e-3 for v in a["omega"])
-    same(sim.download(nat.F_POS), o.get(orc.F_POS), "fluid positions")
-    same(sim.download(nat.F_VEL), o.get(orc.F_VEL), "fluid velocities")
-    same(sim.download(nat.F_RIGID_POS, nat.SPECIES_RIGID), o.get(orc.F_RIGID_POS), "rigid positions")
-    same(sim.download(nat.F_RIGID_VERT, nat.SPECIES_RIGID), o.get(orc.F_RIGID_VERT), "mesh vertices")
+    same_values(sim.download(nat.F_POS), o.get(orc.F_POS), "fluid positions")
+    same_values(sim.download(nat.F_VEL), o.get(orc.F_VEL), "fluid velocities")
+    same_values(sim.download(nat.F_RIGID_POS, nat.SPECIES_RIGID), o.get(orc.F_RIGID_POS), "rigid positions")
+    same_values(sim.download(nat.F_RIGID_VERT, nat.SPECIES_RIGID), o.get(orc.F_RIGID_VERT), "mesh vertices")
     assert moved, "the body never picked up angular velocity: coupling not exercised"
     sim.close(); o.close()
 
@@ -130,17 +121,17 @@ def test_coupled_steps_other_solvers(solver, dt, steps):
             assert (st.n_dens, st.dens_err) == (so.n_dens, so.dens_err), (s, st.n_dens, so.n_dens, st.dens_err, so.dens_err)
         fg, fo = sim.download(nat.F_RIGID_FORCE, nat.SPECIES_RIGID), o.get(orc.F_RIGID_FORCE)
         if s % 10 == 0 or s < 3:
-            same(fg, fo, "force on the body before rigid step %d" % s)
+            same_values(fg, fo, "force on the body before rigid step %d" % s)
         pushed = pushed or float(np.abs(fo).max()) > 0
         sim.rigid_step()
         o.rigid_step()
         a, b = sim.rigid_scalars(), o.rigid_scalars()
         for k in ("centroid", "omega", "vel"):
-            same(np.float32(a[k]), np.float32(b[k]), "%s after step %d" % (k, s))
-    same(sim.download(nat.F_RHO), o.get(orc.F_RHO), "rho")
-    same(sim.download(nat.F_POS), o.get(orc.F_POS), "fluid positions")
-    same(sim.download(nat.F_VEL), o.get(orc.F_VEL), "fluid velocities")
-    same(sim.download(nat.F_RIGID_POS, nat.SPECIES_RIGID), o.get(orc.F_RIGID_POS), "rigid positions")
+            same_values(np.float32(a[k]), np.float32(b[k]), "%s after step %d" % (k, s))
+    same_values(sim.download(nat.F_RHO), o.get(orc.F_RHO), "rho")
+    same_values(sim.download(nat.F_POS), o.get(orc.F_POS), "fluid positions")
+    same_values(sim.download(nat.F_VEL), o.get(orc.F_VEL), "fluid velocities")
+    same_values(sim.download(nat.F_RIGID_POS, nat.SPECIES_RIGID), o.get(orc.F_RIGID_POS), "rigid positions")
     assert pushed, "the fluid never pushed the body: coupling not exercised"
     sim.close(); o.close()
 
@@ -164,9 +155,9 @@ def test_shipped_solid_configs_run(scene, solver):
         rs.step()
         o_step(1)
         o.rigid_step()
-    same(ps.fluid_particles.pos.to_numpy(), o.get(orc.F_POS), "fluid positions")
-    same(ps.fluid_particles.vel.to_numpy(), o.get(orc.F_VEL), "fluid velocities")
-    same(ps.rigid_particles.pos.to_numpy(), o.get(orc.F_RIGID_POS), "rigid positions")
+    same_values(ps.fluid_particles.pos.to_numpy(), o.get(orc.F_POS), "fluid positions")
+    same_values(ps.fluid_particles.vel.to_numpy(), o.get(orc.F_VEL), "fluid velocities")
+    same_values(ps.rigid_particles.pos.to_numpy(), o.get(orc.F_RIGID_POS), "rigid positions")
     o.close()
 
 
@@ -189,7 +180,7 @@ def test_coupled_steps_non_box_body(body, fill):
     sim = nat.Simulation(nat.config_from_dict(cfg), rigid=rg)
     o = orc.Oracle(cfg, num_threads=8, rigid=rg)
     assert sim.n_rigid == o.Nr == len(pts)
-    same(sim.download(nat.F_RIGID_VOL, nat.SPECIES_RIGID), o.get(orc.F_RIGID_VOL), "rigid volumes")
+    same_values(sim.download(nat.F_RIGID_VOL, nat.SPECIES_RIGID), o.get(orc.F_RIGID_VOL), "rigid volumes")
     pushed = False
     for s in range(100 if body == "sphere" else 50):
         st = sim.step_dfsph(1)
@@ -198,15 +189,15 @@ def test_coupled_steps_non_box_body(body, fill):
         assert (st.n_div, st.n_dens, st.div_err, st.dens_err, st.dt) == (so.n_div, so.n_dens, so.div_err, so.dens_err, so.dt), s
         fo = o.get(orc.F_RIGID_FORCE)
         if s % 20 == 0:
-            same(sim.download(nat.F_RIGID_FORCE, nat.SPECIES_RIGID), fo, "force on the body before rigid step %d" % s)
+            same_values(sim.download(nat.F_RIGID_FORCE, nat.SPECIES_RIGID), fo, "force on the body before rigid step %d" % s)
         pushed = pushed or float(np.abs(fo).max()) > 0
         sim.rigid_step()
         o.rigid_step()
         a, b = sim.rigid_scalars(), o.rigid_scalars()
         for k in ("centroid", "omega", "vel", "inertia_inv"):
-            same(np.float32(a[k]), np.float32(b[k]), "%s after step %d" % (k, s))
-    same(sim.download(nat.F_POS), o.get(orc.F_POS), "fluid positions")
-    same(sim.download(nat.F_VEL), o.get(orc.F_VEL), "fluid velocities")
-    same(sim.download(nat.F_RIGID_POS, nat.SPECIES_RIGID), o.get(orc.F_RIGID_POS), "rigid positions")
+            same_values(np.float32(a[k]), np.float32(b[k]), "%s after step %d" % (k, s))
+    same_values(sim.download(nat.F_POS), o.get(orc.F_POS), "fluid positions")
+    same_values(sim.download(nat.F_VEL), o.get(orc.F_VEL), "fluid velocities")
+    same_values(sim.download(nat.F_RIGID_POS, nat.SPECIES_RIGID), o.get(orc.F_RIGID_POS), "rigid positions")
     assert pushed, "the fluid never pushed the body: coupling not exercised"
     sim.close(); o.close()

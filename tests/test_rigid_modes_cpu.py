@@ -11,7 +11,8 @@ import numpy as np
 import pytest
 
 from oracle import oracle as orc
-from rigid_modes import STEPS, oracle_step, rigid, scene
+from harness import oracle_step
+from rigid_modes import STEPS, rigid, scene
 from second_restatement import Neighbours, Scene
 
 

@@ -11,28 +11,21 @@ import pytest
 
 from cfd_taichi_amd import _native as nat
 from oracle import oracle as orc
-from rigid_modes import MODES, SOLVERS, STEPS, oracle_step, rigid, scene
-from test_rigid_gpu import same
+from harness import make_oracle, oracle_step, same_nan_mask, same_values
+from rigid_modes import MODES, SOLVERS, STEPS, rigid, scene
 
 pytestmark = pytest.mark.gpu
-
-
-def same_nan(a, b, what):
-    """same() for values that may hold NaN: the NaN masks agree and everything else is equal bit for bit"""
-    a, b = np.asarray(a, dtype=np.float32), np.asarray(b, dtype=np.float32)
-    assert np.array_equal(np.isnan(a), np.isnan(b)), "%s: NaN at different places: %r vs %r" % (what, a, b)
-    assert np.array_equal(a, b, equal_nan=True), "%s differs: %r vs %r" % (what, a, b)
 
 
 def check_rigid(sim, o, when, nan_aware):
     a, b = sim.rigid_scalars(), o.rigid_scalars()
     for k in ("centroid", "omega", "vel", "inertia_inv", "mass"):
         if nan_aware:
-            same_nan(a[k], b[k], "%s %s" % (k, when))
+            same_nan_mask(a[k], b[k], "%s %s" % (k, when))
         else:
-            same(np.float32(a[k]), np.float32(b[k]), "%s %s" % (k, when))
-    same(sim.download(nat.F_RIGID_POS, nat.SPECIES_RIGID), o.get(orc.F_RIGID_POS), "rigid positions " + when)
-    same(sim.download(nat.F_RIGID_VERT, nat.SPECIES_RIGID), o.get(orc.F_RIGID_VERT), "mesh vertices " + when)
+            same_values(np.float32(a[k]), np.float32(b[k]), "%s %s" % (k, when))
+    same_values(sim.download(nat.F_RIGID_POS, nat.SPECIES_RIGID), o.get(orc.F_RIGID_POS), "rigid positions " + when)
+    same_values(sim.download(nat.F_RIGID_VERT, nat.SPECIES_RIGID), o.get(orc.F_RIGID_VERT), "mesh vertices " + when)
     return a
 
 
@@ -42,7 +35,7 @@ def test_rigid_mode_steps(solver, mode):
     cfg = scene(solver, mode)
     rg = rigid(cfg)
     sim = nat.Simulation(nat.config_from_dict(cfg), rigid=rg)
-    o = orc.Oracle(cfg, solver=solver, num_threads=8, rigid=rg)
+    o = make_oracle(cfg, solver, rigid=rg)
     active = mode == "oneway"                                   # ps.active_rigid[None] == 1 (ParticleSystem.py:63-64)
     assert (sim.n_fluid, sim.n_wall, sim.n_rigid) == (o.N, o.Nb, o.Nr) and sim.n_rigid > 0
     if solver == "pcisph":
@@ -58,7 +51,7 @@ def test_rigid_mode_steps(solver, mode):
         if solver == "dfsph":
             assert (st.n_div, st.n_dens, st.div_first_err, st.div_err, st.dens_err, st.dt) == (
                 so.n_div, so.n_dens, so.div_first_err, so.div_err, so.dens_err, so.dt), s
-            same(sim.download(nat.F_NBR_COUNT), o.get(orc.F_NBR_COUNT), "neighbour count (the rigid-entry quirk) of step %d" % s)
+            same_values(sim.download(nat.F_NBR_COUNT), o.get(orc.F_NBR_COUNT), "neighbour count (the rigid-entry quirk) of step %d" % s)
         elif solver != "wcsph":
             assert (st.n_dens, st.dens_err) == (so.n_dens, so.dens_err), (s, st.n_dens, so.n_dens, st.dens_err, so.dens_err)
         if active:
@@ -68,9 +61,9 @@ def test_rigid_mode_steps(solver, mode):
             sim.rigid_step()                                    # main.py:169-171: only an active body is stepped
             o.rigid_step()
             vy.append(check_rigid(sim, o, "after rigid step %d" % s, nan_aware=False)["vel"][1])
-    same(sim.download(nat.F_POS), o.get(orc.F_POS), "fluid positions")
-    same(sim.download(nat.F_VEL), o.get(orc.F_VEL), "fluid velocities")
-    same(sim.download(nat.F_RHO), o.get(orc.F_RHO), "rho")
+    same_values(sim.download(nat.F_POS), o.get(orc.F_POS), "fluid positions")
+    same_values(sim.download(nat.F_VEL), o.get(orc.F_VEL), "fluid velocities")
+    same_values(sim.download(nat.F_RHO), o.get(orc.F_RHO), "rho")
     if active:
         assert vy[0] < 0, "the body did not fall"
         if solver != "wcsph":       # (40 steps of 2.5e-4 end before the floor)

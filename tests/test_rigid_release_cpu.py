@@ -16,16 +16,17 @@ import pytest
 
 from cfd_taichi_amd import _native as nat
 from oracle import oracle as orc
-from rigid_release import AFTER, K, ONE_WAY, SOLVERS, TWO_WAY, fluid_state, give, make_oracle, oracle_step, scene
+from harness import fluid_state, give, oracle_step
+from rigid_release import AFTER, K, ONE_WAY, SOLVERS, TWO_WAY, body_oracle, scene
 
 
 def released_and_inactive(solver, fs_couple):
     """(the inactive oracle after K + AFTER steps, the fresh active oracle given its step-K fluid state after AFTER coupled steps, neighbour
     counts that differed on the way)"""
-    off = make_oracle(scene(solver, False, fs_couple), solver)
+    off = body_oracle(scene(solver, False, fs_couple), solver)
     for _ in range(K):
         oracle_step(off, solver)
-    on = give(make_oracle(scene(solver, True, fs_couple), solver), fluid_state(off, solver), solver)
+    on = give(body_oracle(scene(solver, True, fs_couple), solver), fluid_state(off, solver), solver)
     counts = 0
     for _ in range(AFTER):
         oracle_step(off, solver)
@@ -52,12 +53,12 @@ def test_one_way_release_changes_the_neighbour_count():
 
 
 def test_pcisph_delta_does_not_see_the_two_way_placement():
-    a, b = make_oracle(scene("pcisph", True), "pcisph"), make_oracle(scene("pcisph", False), "pcisph")
+    a, b = body_oracle(scene("pcisph", True), "pcisph"), body_oracle(scene("pcisph", False), "pcisph")
     assert np.float32(a.pcisph_delta) == np.float32(b.pcisph_delta) and a.pcisph_max_index == b.pcisph_max_index, (TWO_WAY, a.pcisph_delta, b.pcisph_delta)
     assert np.isfinite(a.pcisph_delta) and a.pcisph_max_index[0] >= 0
     a.close(); b.close()
     # ... and does see the corner placement of the one-way scenes: no pcisph case there
-    a, b = make_oracle(scene("pcisph", True, False), "pcisph"), make_oracle(scene("pcisph", False, False), "pcisph")
+    a, b = body_oracle(scene("pcisph", True, False), "pcisph"), body_oracle(scene("pcisph", False, False), "pcisph")
     assert np.float32(a.pcisph_delta) != np.float32(b.pcisph_delta), (ONE_WAY, a.pcisph_delta)
     a.close(); b.close()
 

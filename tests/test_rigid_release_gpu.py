@@ -27,9 +27,9 @@ import pytest
 
 from cfd_taichi_amd import _native as nat
 from oracle import oracle as orc
-from rigid_release import AFTER, K, SOLVERS, fluid_state, give, give_sim, make_oracle, oracle_step, rigid, scene, stats_tuple
-from test_rigid_gpu import same
-from test_rigid_modes_gpu import check_rigid, same_nan
+from harness import fluid_state, give, give_sim, oracle_step, same_nan_mask, same_values, stats_tuple
+from rigid_release import AFTER, K, SOLVERS, body_oracle, rigid, scene
+from test_rigid_modes_gpu import check_rigid
 
 pytestmark = pytest.mark.gpu
 
@@ -55,9 +55,9 @@ def body(sim):
 
 def same_body(a, b, what, nan_aware=False):
     for k in ("centroid", "omega", "vel", "inertia_inv", "mass"):
-        (same_nan if nan_aware else same)(np.float32(a[0][k]), np.float32(b[0][k]), "%s: %s" % (what, k))
-    same(a[1], b[1], what + ": sample positions")
-    same(a[2], b[2], what + ": mesh vertices")
+        (same_nan_mask if nan_aware else same_values)(np.float32(a[0][k]), np.float32(b[0][k]), "%s: %s" % (what, k))
+    same_values(a[1], b[1], what + ": sample positions")
+    same_values(a[2], b[2], what + ": mesh vertices")
 
 
 def count_before_step(sim, o, solver, when):
@@ -66,7 +66,7 @@ def count_before_step(sim, o, solver, when):
         return
     sim.build_neighbors()
     o.build_grid(); o.compute_nbr_count()
-    same(sim.download(nat.F_NBR_COUNT), o.get(orc.F_NBR_COUNT), "neighbour count before " + when)
+    same_values(sim.download(nat.F_NBR_COUNT), o.get(orc.F_NBR_COUNT), "neighbour count before " + when)
 
 
 def lockstep(sim, o, solver, nsteps, active, one_way=False):
@@ -81,19 +81,19 @@ def lockstep(sim, o, solver, nsteps, active, one_way=False):
         if solver != "wcsph":
             assert stats_tuple(st, solver) == stats_tuple(so, solver), (when, stats_tuple(st, solver), stats_tuple(so, solver))
         if solver == "dfsph":
-            same(sim.download(nat.F_NBR_COUNT), o.get(orc.F_NBR_COUNT), "neighbour count of " + when)
+            same_values(sim.download(nat.F_NBR_COUNT), o.get(orc.F_NBR_COUNT), "neighbour count of " + when)
         if active:
             if s % 10 == 0:
                 fg, fo = sim.download(nat.F_RIGID_FORCE, nat.SPECIES_RIGID), o.get(orc.F_RIGID_FORCE)
-                same(fg, fo, "force on the body, " + when)
+                same_values(fg, fo, "force on the body, " + when)
                 if one_way:
                     assert not fg.any(), "%s: a force on a body the fluid does not couple to" % when
             sim.rigid_step()
             o.rigid_step()
             vy.append(check_rigid(sim, o, "after rigid " + when, nan_aware=False)["vel"][1])
-    same(sim.download(nat.F_POS), o.get(orc.F_POS), "fluid positions")
-    same(sim.download(nat.F_VEL), o.get(orc.F_VEL), "fluid velocities")
-    same(sim.download(nat.F_RHO), o.get(orc.F_RHO), "rho")
+    same_values(sim.download(nat.F_POS), o.get(orc.F_POS), "fluid positions")
+    same_values(sim.download(nat.F_VEL), o.get(orc.F_VEL), "fluid velocities")
+    same_values(sim.download(nat.F_RHO), o.get(orc.F_RHO), "rho")
     return vy
 
 
@@ -101,15 +101,15 @@ def lockstep(sim, o, solver, nsteps, active, one_way=False):
 @pytest.mark.parametrize("solver", SOLVERS)
 def test_release_at_step_0_equals_created_active(solver):
     cfg_off, cfg_on = scene(solver, False), scene(solver, True)
-    a, b, o = make_sim(cfg_off), make_sim(cfg_on), make_oracle(cfg_on, solver)
+    a, b, o = make_sim(cfg_off), make_sim(cfg_on), body_oracle(cfg_on, solver)
     assert a.scalar(nat.S_RIGID_ACTIVE) == 0.0 and b.scalar(nat.S_RIGID_ACTIVE) == 1.0
     assert not a.download(nat.F_RIGID_VOL, nat.SPECIES_RIGID).any() and np.isnan(np.float32(a.rigid_scalars()["centroid"])).all()
     release(a)
     assert a.scalar(nat.S_RIGID_ACTIVE) == 1.0
     same_body(body(a), body(b), "released at step 0 vs created active")
     for f, name in ((nat.F_RIGID_VOL, "volumes"), (nat.F_RIGID_MASS, "masses")):
-        same(a.download(f, nat.SPECIES_RIGID), b.download(f, nat.SPECIES_RIGID), "sample " + name)
-        same(a.download(f, nat.SPECIES_RIGID), o.get({nat.F_RIGID_VOL: orc.F_RIGID_VOL, nat.F_RIGID_MASS: orc.F_RIGID_MASS}[f]), "sample %s vs the oracle" % name)
+        same_values(a.download(f, nat.SPECIES_RIGID), b.download(f, nat.SPECIES_RIGID), "sample " + name)
+        same_values(a.download(f, nat.SPECIES_RIGID), o.get({nat.F_RIGID_VOL: orc.F_RIGID_VOL, nat.F_RIGID_MASS: orc.F_RIGID_MASS}[f]), "sample %s vs the oracle" % name)
     assert a.download(nat.F_RIGID_VOL, nat.SPECIES_RIGID).all()
     check_rigid(a, o, "released at step 0 vs the oracle created active", nan_aware=False)
     if solver == "pcisph":      # the delta of construction stays (semantics 3); at this placement it is the active handle's and the oracle's too
@@ -122,7 +122,7 @@ def test_release_at_step_0_equals_created_active(solver):
         stepper(sim, solver)(1)
         sim.rigid_step()
     same_body(body(a), body(b), "one step after the release")
-    same(a.download(nat.F_POS), b.download(nat.F_POS), "fluid positions one step after the release")
+    same_values(a.download(nat.F_POS), b.download(nat.F_POS), "fluid positions one step after the release")
     a.close(); b.close(); o.close()
 
 
@@ -135,8 +135,8 @@ def release_at_step_k(solver, fs_couple):
     at_k = body(sim)
     state = fluid_state(sim, solver)
     release(sim)
-    o = give(make_oracle(scene(solver, True, fs_couple), solver), state, solver)
-    same(at_k[1], o.get(orc.F_RIGID_POS), "the inactive body did not move")
+    o = give(body_oracle(scene(solver, True, fs_couple), solver), state, solver)
+    same_values(at_k[1], o.get(orc.F_RIGID_POS), "the inactive body did not move")
     check_rigid(sim, o, "at the release", nan_aware=False)
     vy = lockstep(sim, o, solver, AFTER, active=True, one_way=not fs_couple)
     assert vy[0] < 0, "the released body did not fall"
@@ -165,9 +165,9 @@ def test_freeze_then_release_again(solver):
     state = fluid_state(sim, solver)
     sim.rigid_set_active(0)
     assert sim.scalar(nat.S_RIGID_ACTIVE) == 0.0
-    o = give(make_oracle(scene(solver, None), solver), state, solver)
+    o = give(body_oracle(scene(solver, None), solver), state, solver)
     o.build_grid(); o.compute_nbr_count()
-    same(sim.download(nat.F_NBR_COUNT), o.get(orc.F_NBR_COUNT), "neighbour count right after the freeze: the fluid-only count")
+    same_values(sim.download(nat.F_NBR_COUNT), o.get(orc.F_NBR_COUNT), "neighbour count right after the freeze: the fluid-only count")
     lockstep(sim, o, solver, 20, active=False)
     same_body(body(sim), at_10, "the frozen body after 20 fluid steps")
     if solver != "dfsph":
@@ -204,11 +204,11 @@ def test_release_under_the_relaxed_arithmetic(monkeypatch):
         sa, sb = a.step_dfsph(1), b.step_dfsph(1)
         assert a.scalar(nat.S_ARITH_RELAXED) == 1.0 and b.scalar(nat.S_ARITH_RELAXED) == 1.0
         assert stats_tuple(sa, "dfsph") == stats_tuple(sb, "dfsph"), (s, stats_tuple(sa, "dfsph"), stats_tuple(sb, "dfsph"))
-        same(a.download(nat.F_RIGID_FORCE, nat.SPECIES_RIGID), b.download(nat.F_RIGID_FORCE, nat.SPECIES_RIGID), "force on the body, step +%d" % (s + 1))
+        same_values(a.download(nat.F_RIGID_FORCE, nat.SPECIES_RIGID), b.download(nat.F_RIGID_FORCE, nat.SPECIES_RIGID), "force on the body, step +%d" % (s + 1))
         a.rigid_step(); b.rigid_step()
         same_body(body(a), body(b), "step +%d" % (s + 1))
     for f, name in ((nat.F_POS, "positions"), (nat.F_VEL, "velocities"), (nat.F_RHO, "rho"), (nat.F_WARM_K, "warm_start_k")):
-        same(a.download(f), b.download(f), "fluid " + name)
+        same_values(a.download(f), b.download(f), "fluid " + name)
     assert b.rigid_scalars()["vel"][1] < 0
     a.close(); b.close()
 
@@ -252,7 +252,7 @@ def test_stepping_a_released_body_needs_init_data(solver):
         with pytest.raises(nat.SphError, match="call sph_rigid_init_data after releasing the body") as e:
             call()
         assert e.value.code == nat.SPH_E_STATE
-    same(sim.download(nat.F_POS), before["pos"], "a refused step moved the fluid")
+    same_values(sim.download(nat.F_POS), before["pos"], "a refused step moved the fluid")
     sim.rigid_init_data()
     g_step(1)
     sim.rigid_step()

@@ -18,7 +18,7 @@ from cfd_taichi_amd import _native as nat
 import coupled_scenes as cs
 import scripted_body as sb
 import second_restatement_rigid as srr
-from restatement_compare import bits, same
+from harness import bits_equal, same_bits
 from second_restatement import F, Solver
 
 REPLAY_OFFSET = [0.47, 0.2, 0.12]
@@ -47,7 +47,7 @@ def run_dynamic(monkeypatch, solver, steps):
             s.rigid_step()
             b = s.body
             assert b.hit == 0, "the dynamic body met a wall at step %d: nothing a scripted body could replay" % k
-            same(b.centroid, before + b.vel * dt, "centroid step == vel dt at step %d (no wall clamp)" % k)
+            same_bits(b.centroid, before + b.vel * dt, "centroid step == vel dt at step %d (no wall clamp)" % k)
             snaps.append({name: getattr(s, name).copy() for name in ("pos", "vel", "rho")} |
                          {"rigid_pos": b.pos.copy(), "vert": b.vert.copy(), "centroid": b.centroid.copy(), "inertia_inv": b.inertia_inv.copy(),
                           "load": b.load})
@@ -67,10 +67,10 @@ def test_replay_premise(solver, monkeypatch):
             s.rigid_step()
             want, b = snaps[k - 1], s.body
             for name in ("pos", "vel", "rho"):
-                same(want[name], getattr(s, name), "replayed fluid %s, step %d" % (name, k))
+                same_bits(want[name], getattr(s, name), "replayed fluid %s, step %d" % (name, k))
             for name, mine in (("rigid_pos", b.pos), ("vert", b.vert), ("centroid", b.centroid), ("inertia_inv", b.inertia_inv),
                                ("load", np.array(b.load))):
-                same(np.array(want[name]), mine, "replayed body %s, step %d" % (name, k))
+                same_bits(np.array(want[name]), mine, "replayed body %s, step %d" % (name, k))
 
 
 def test_fixed_body_keeps_its_bits(monkeypatch):
@@ -85,7 +85,7 @@ def test_fixed_body_keeps_its_bits(monkeypatch):
             s.rigid_step()
             b = s.body
             for was, now in ((pos0, b.pos), (vert0, b.vert), (c0, b.centroid), (inv0, b.inertia_inv)):
-                assert np.array_equal(bits(was), bits(now))
+                assert bits_equal(was, now)
             assert not b.force.any() and not b.vel.any() and not b.s_omega.any() and not b.acc.any() and not b.s_alpha.any()
             assert np.abs(b.load[0]).max() > 0
     assert largest > 0, "the fluid never pushed the obstacle"

@@ -17,6 +17,7 @@ import pytest
 from cfd_taichi_amd import _native as nat
 import coupled_scenes as cs
 import restatement_compare as rc
+from harness import same_bits
 import scripted_body as sb
 import second_restatement_rigid as srr
 from test_scripted_body_cpu import REPLAY_OFFSET, REPLAY_STEPS
@@ -87,7 +88,7 @@ def test_replay_on_the_library(solver):
             if solver == "dfsph":
                 assert (st_d.n_div, np.float32(st_d.div_err), np.float32(st_d.div_first_err)) == (st_s.n_div, np.float32(st_s.div_err), np.float32(st_s.div_first_err)), k
             for name in ("pos", "vel", "rho", "rigid_force"):
-                rc.same(dyn.get(name), scr.get(name), "%s before body step %d" % (name, k))
+                same_bits(dyn.get(name), scr.get(name), "%s before body step %d" % (name, k))
             largest = max(largest, float(np.abs(dyn.get("rigid_force")).max()))
             dyn.rigid_step()
             sc = dyn.sim.rigid_scalars(motion=True)
@@ -95,13 +96,13 @@ def test_replay_on_the_library(solver):
             scr.rigid_step()
             a, b = _body_state(dyn), _body_state(scr)
             for name in a:
-                rc.same(a[name], b[name], "body %s after body step %d" % (name, k))
+                same_bits(a[name], b[name], "body %s after body step %d" % (name, k))
             (fd, td), (fs, ts) = dyn.sim.rigid_load(), scr.sim.rigid_load()
             assert fd.tobytes() == fs.tobytes() and td.tobytes() == ts.tobytes(), (k, fd, fs, td, ts)
             # the dynamic handle's acc is its own load over its mass, plus gravity (rigid_solver.py:40-41)
             mass = np.float32(sc["mass"])
             want = fd.astype(np.float32) / mass + np.array([g * np.float32(0.0), g * np.float32(-1.0), g * np.float32(0.0)], dtype=np.float32)
-            rc.same(want, sc["acc"], "acc == F32(force) / mass + g at step %d" % k)
+            same_bits(want, sc["acc"], "acc == F32(force) / mass + g at step %d" % k)
         assert largest > 0, "the fluid never pushed the body"
     finally:
         dyn.close()
@@ -199,9 +200,9 @@ def test_mirror_api(mode):
             direct.rigid_step()
             solver.step()
             rigid.step()
-            rc.same(direct.get("pos"), ps.fluid_particles.pos.to_numpy(), "fluid pos, step %d" % k)
-            rc.same(direct.get("rigid_pos"), ps.rigid_particles.pos.to_numpy(), "sample pos, step %d" % k)
-            rc.same(direct.rigid_scalars()["centroid"], ps.rigid_centriod[None], "centroid, step %d" % k)
+            same_bits(direct.get("pos"), ps.fluid_particles.pos.to_numpy(), "fluid pos, step %d" % k)
+            same_bits(direct.get("rigid_pos"), ps.rigid_particles.pos.to_numpy(), "sample pos, step %d" % k)
+            same_bits(direct.rigid_scalars()["centroid"], ps.rigid_centriod[None], "centroid, step %d" % k)
             assert direct.sim.rigid_load()[0].tobytes() == rigid.load()[0].tobytes()
         assert np.abs(rigid.load()[0]).max() > 0
     finally:

@@ -18,22 +18,10 @@ import pytest
 
 import coupled_scenes as cs
 import restatement_compare as rc
+from harness import same_bits, squeezed
 from cfd_taichi_amd import scenes
 from oracle import oracle as orc
 from second_restatement import Scene, Solver
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def same(a, b, what):
-    a, b = np.asarray(a, dtype=np.float32), np.asarray(b, dtype=np.float32)
-    assert a.shape == b.shape, what
-    if not np.array_equal(bits(a), bits(b)):
-        bad = np.argwhere(bits(a) != bits(b))
-        i = tuple(bad[0])
-        raise AssertionError("%s: %d of %d values differ, first at %s: %r (second restatement) vs %r (oracle)" % (what, len(bad), a.size, i, a[i], b[i]))
 
 
 @pytest.mark.parametrize("scene", ["wcsph_tiny_wall", "dfsph_tiny_wall", "wcsph_tiny_clamp", "dfsph_tiny_clamp"])
@@ -43,10 +31,10 @@ def test_scene_construction(scene):
     o = orc.Oracle(cfg)
     sc = Scene(cfg)
     assert (sc.N, sc.Nb, tuple(sc.grid), sc.C) == (o.N, o.Nb, tuple(o.grid), o.C)
-    same(sc.pos, o.get(orc.F_POS), "lattice")
-    same(sc.wall_pos, o.get(orc.F_WALL_POS), "wall positions")
+    same_bits(sc.pos, o.get(orc.F_POS), "lattice")
+    same_bits(sc.wall_pos, o.get(orc.F_WALL_POS), "wall positions")
     if cfg["solver"]["boundary_handle"]:
-        same(sc.wall_vol, o.get(orc.F_WALL_VOL), "wall volumes")
+        same_bits(sc.wall_vol, o.get(orc.F_WALL_VOL), "wall volumes")
     o.close()
 
 
@@ -61,13 +49,13 @@ def test_wcsph_ten_steps(scene, steps):
         for k in range(steps):
             s.step()
             o.step_wcsph(1)
-            same(s.rho, o.get(orc.F_RHO), "rho, step %d" % (k + 1))
-            same(s.pressure, o.get(orc.F_PRESSURE), "pressure, step %d" % (k + 1))
-            same(s.viscosity, o.get(orc.F_VISCOSITY), "viscosity, step %d" % (k + 1))
-            same(s.tension, o.get(orc.F_TENSION), "tension, step %d" % (k + 1))
-            same(s.acc, o.get(orc.F_ACC), "acc, step %d" % (k + 1))
-            same(s.vel, o.get(orc.F_VEL), "vel, step %d" % (k + 1))
-            same(s.pos, o.get(orc.F_POS), "pos, step %d" % (k + 1))
+            same_bits(s.rho, o.get(orc.F_RHO), "rho, step %d" % (k + 1))
+            same_bits(s.pressure, o.get(orc.F_PRESSURE), "pressure, step %d" % (k + 1))
+            same_bits(s.viscosity, o.get(orc.F_VISCOSITY), "viscosity, step %d" % (k + 1))
+            same_bits(s.tension, o.get(orc.F_TENSION), "tension, step %d" % (k + 1))
+            same_bits(s.acc, o.get(orc.F_ACC), "acc, step %d" % (k + 1))
+            same_bits(s.vel, o.get(orc.F_VEL), "vel, step %d" % (k + 1))
+            same_bits(s.pos, o.get(orc.F_POS), "pos, step %d" % (k + 1))
     o.close()
 
 
@@ -88,14 +76,14 @@ def test_dfsph_ten_steps(scene, steps):
             assert np.float32(s.div_first) == np.float32(st.div_first_err) and np.float32(s.div_err) == np.float32(st.div_err), "divergence residuals, step %d" % (k + 1)
             assert np.float32(s.dens_err) == np.float32(st.dens_err), "density residual, step %d" % (k + 1)
             assert np.float32(s.dt) == np.float32(st.dt), "dt, step %d" % (k + 1)
-            same(s.rho, o.get(orc.F_RHO), "rho, step %d" % (k + 1))
-            same(s.alpha, o.get(orc.F_ALPHA), "alpha, step %d" % (k + 1))
-            same(s.rho_derivative, o.get(orc.F_RHO_DER), "rho_derivative, step %d" % (k + 1))
-            same(s.warm, o.get(orc.F_WARM_K), "warm_start_k, step %d" % (k + 1))
-            same(s.rho_adv, o.get(orc.F_RHO_ADV), "rho_adv, step %d" % (k + 1))
-            same(s.vel_adv, o.get(orc.F_VEL_ADV), "vel_adv, step %d" % (k + 1))
-            same(s.vel, o.get(orc.F_VEL), "vel, step %d" % (k + 1))
-            same(s.pos, o.get(orc.F_POS), "pos, step %d" % (k + 1))
+            same_bits(s.rho, o.get(orc.F_RHO), "rho, step %d" % (k + 1))
+            same_bits(s.alpha, o.get(orc.F_ALPHA), "alpha, step %d" % (k + 1))
+            same_bits(s.rho_derivative, o.get(orc.F_RHO_DER), "rho_derivative, step %d" % (k + 1))
+            same_bits(s.warm, o.get(orc.F_WARM_K), "warm_start_k, step %d" % (k + 1))
+            same_bits(s.rho_adv, o.get(orc.F_RHO_ADV), "rho_adv, step %d" % (k + 1))
+            same_bits(s.vel_adv, o.get(orc.F_VEL_ADV), "vel_adv, step %d" % (k + 1))
+            same_bits(s.vel, o.get(orc.F_VEL), "vel, step %d" % (k + 1))
+            same_bits(s.pos, o.get(orc.F_POS), "pos, step %d" % (k + 1))
             iterated += (s.n_div > 1) + (s.n_dens > 2)
     assert iterated > 0, "neither solver loop ever ran past its minimum: the loops were not exercised"
     o.close()
@@ -123,10 +111,10 @@ def test_jittered_state_five_steps(scene, steps):
             else:
                 o.step_dfsph(1)
                 assert (s.n_div, s.n_dens) == (o.last_stats.n_div, o.last_stats.n_dens), "iteration counts, step %d" % (k + 1)
-                same(s.alpha, o.get(orc.F_ALPHA), "alpha, step %d" % (k + 1))
-            same(s.rho, o.get(orc.F_RHO), "rho, step %d" % (k + 1))
-            same(s.vel, o.get(orc.F_VEL), "vel, step %d" % (k + 1))
-            same(s.pos, o.get(orc.F_POS), "pos, step %d" % (k + 1))
+                same_bits(s.alpha, o.get(orc.F_ALPHA), "alpha, step %d" % (k + 1))
+            same_bits(s.rho, o.get(orc.F_RHO), "rho, step %d" % (k + 1))
+            same_bits(s.vel, o.get(orc.F_VEL), "vel, step %d" % (k + 1))
+            same_bits(s.pos, o.get(orc.F_POS), "pos, step %d" % (k + 1))
     o.close()
 
 
@@ -213,8 +201,8 @@ def test_inactive_body_equals_no_body():
     with_body, without = cs.coupled("pcisph", active=False), cs.coupled("pcisph", solid=False)
     a = rc.compare_run(with_body, 5, [rc.OracleSide], rg=cs.rigid(with_body))["solver"]
     b = rc.compare_run(without, 5, [rc.OracleSide])["solver"]
-    same(a.pos, b.pos, "positions with an inactive body and with none")
-    same(a.vel, b.vel, "velocities with an inactive body and with none")
+    same_bits(a.pos, b.pos, "positions with an inactive body and with none")
+    same_bits(a.vel, b.vel, "velocities with an inactive body and with none")
     assert (a.delta, a.max_index) == (b.delta, b.max_index)
     assert not a.body.vol.any() and not a.body.force.any()
 
@@ -228,8 +216,7 @@ PBF_THROWN_SHIFT = (-0.05, -0.05, 0.0)
 def pbf_squeezed(cfg, factor=0.9):
     """test_pbf_gpu.squeeze as a state: the rest lattice scaled about its minimum corner, at rest -- lambda and delta_pos act from step 1"""
     pos = Scene(cfg).pos
-    about = pos.min(0)
-    return (about + (pos - about) * np.float32(factor)).astype(np.float32), np.zeros_like(pos)
+    return squeezed(pos, factor), np.zeros_like(pos)
 
 
 def pbf_case(kind):

@@ -17,6 +17,7 @@ import pytest
 from cfd_taichi_amd import scenes
 import coupled_scenes as cs
 import restatement_compare as rc
+from harness import same_bits
 from test_second_restatement import KINDS, PBF_KINDS, _past_minimum, check_pbf, check_pbf_rho_bound, check_uncoupled, pbf_case, pbf_squeezed, uncoupled_case
 
 pytestmark = pytest.mark.gpu
@@ -90,8 +91,8 @@ def test_inactive_body_equals_no_body(monkeypatch):
     with_body, without = cs.coupled("pcisph", active=False), cs.coupled("pcisph", solid=False)
     a = rc.compare_run(with_body, 5, handles(monkeypatch), rg=cs.rigid(with_body))["solver"]
     b = rc.compare_run(without, 5, handles(monkeypatch))["solver"]
-    rc.same(a.pos, b.pos, "positions with an inactive body and with none")
-    rc.same(a.vel, b.vel, "velocities with an inactive body and with none")
+    same_bits(a.pos, b.pos, "positions with an inactive body and with none")
+    same_bits(a.vel, b.vel, "velocities with an inactive body and with none")
 
 
 # ---- PBF: quad and plain kernels, linear and Morton cells, against tests/second_restatement_pbf.py ------------------------------------------

@@ -1,7 +1,6 @@
 """CPU suite for the N>1 path: the torch.distributed transport behind the slab decomposition (world_size 2 and 3,
 gloo, CPU tensors) and the host-only slab planner.  The device side is covered by tests/test_slab_gpu.py."""
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -11,12 +10,7 @@ import torch.multiprocessing as mp
 
 from cfd_taichi_amd import _native as nat
 from cfd_taichi_amd import scenes
-
-
-def free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
+from harness import free_port
 
 
 def _worker(rank, world, port, results):

@@ -7,13 +7,12 @@ switched; the coupled case is the body over the water of tests/test_slab_scripte
 import copy
 import json
 import os
-import subprocess
-import sys
 
 import pytest
 
 from cfd_taichi_amd import scenes
 import slab_pbf_states as sp
+from harness import run_ranks
 
 pytestmark = pytest.mark.gpu
 
@@ -40,10 +39,8 @@ def run_worker(tmp_path, cfg, world, steps, body=False):
     scene = tmp_path / "scene.json"
     scene.write_text(json.dumps(cfg))
     out = tmp_path / "out.json"
-    cmd = [sys.executable, WORKER, "--scene", str(scene), "--world", str(world), "--steps", str(steps), "--out", str(out)] + (["--body"] if body else [])
-    p = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, OMP_NUM_THREADS="2"), capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
-    return json.loads(out.read_text())
+    args = ["--scene", scene, "--world", world, "--steps", steps, "--out", out] + (["--body"] if body else [])
+    return run_ranks(WORKER, args, world, "loopback", out)
 
 
 def check(r, world):

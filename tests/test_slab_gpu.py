@@ -3,35 +3,22 @@ reproduce the single-GPU result bit for bit -- every per-particle sum runs in th
 every decomposition.  Ranks share GPU 0 and talk over gloo here (one-GPU box); production uses nccl = RCCL."""
 import json
 import os
-import socket
 import subprocess
 import sys
 
 import pytest
 
+from harness import free_port, run_ranks
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
 def run_slabs(tmp_path, scene, world, steps, rebalance=0, legacy=False, env_extra=None, layers=0, overlap=0, arith=0):
     out = tmp_path / ("slab_%s_%d_%d_%d_%d%d%d.json" % (os.path.basename(scene), world, rebalance, legacy, layers, overlap, arith))
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
-           "--master-port", str(free_port()), os.path.join(ROOT, "tests", "slab_worker.py"), "--scene", scene, "--steps", str(steps),
-           "--backend", "gloo", "--rebalance", str(rebalance), "--layers", str(layers), "--overlap", str(overlap), "--arith", str(arith), "--out", str(out)]
-    if legacy:
-        cmd.append("--host-loops")
-    # SPH_SLAB_CHECK: every step, the host's bookkeeping of the edge-column populations is compared with the sorted arrays
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2", SPH_SLAB_CHECK="1")
-    env.update(env_extra or {})
-    p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
-    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
-    return json.loads(out.read_text())
+    args = ["--scene", scene, "--steps", steps, "--backend", "gloo", "--rebalance", rebalance, "--layers", layers, "--overlap", overlap, "--arith", arith,
+            "--out", out] + (["--host-loops"] if legacy else [])
+    return run_ranks(os.path.join(ROOT, "tests", "slab_worker.py"), args, world, "gloo", out, env_extra, timeout=900)
 
 
 @pytest.mark.parametrize("scene,world,steps,rebalance", [("dfsph_dam_x", 2, 120, 11)])

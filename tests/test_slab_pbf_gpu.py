@@ -11,16 +11,13 @@ On the comm identities of case 2 / 3: an ordinary step exchanges particles in on
 after sph_slab_set_state (include/sph_mi355x.h), which is how the state gets in and is no re-cut.  The identities the issue states per step
 (count_exchanges == steps + recuts, p2p_groups - recuts == 3 steps) are therefore asserted over steps 2 .. 60, and over the whole run with that
 one extra round named."""
-import json
 import os
-import socket
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import slab_pbf_states as sp
+from harness import run_ranks
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -37,25 +34,12 @@ def state_file(tmp_path, scene, seed):
 
 def run_loopback(tmp_path, *opts, env_extra=None, timeout=240):
     out = tmp_path / "pbf.json"
-    cmd = [sys.executable, WORKER, "--transport", "loopback", "--out", str(out)] + [str(o) for o in opts]
-    env = dict(os.environ, SPH_SLAB_CHECK="1")
-    env.update(env_extra or {})
-    p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
-    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
-    return json.loads(out.read_text())
+    return run_ranks(WORKER, ("--transport", "loopback", "--out", out) + opts, None, "loopback", out, env_extra, timeout)
 
 
 def run_gloo(tmp_path, world, *opts, timeout=300):
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
     out = tmp_path / "pbf_gloo.json"
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1", "--master-port", str(port),
-           WORKER, "--transport", "gloo", "--out", str(out)] + [str(o) for o in opts]
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2", SPH_SLAB_CHECK="1")
-    p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
-    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
-    return json.loads(out.read_text())
+    return run_ranks(WORKER, ("--transport", "gloo", "--out", out) + opts, world, "gloo", out, timeout=timeout)
 
 
 def assert_comm_identities(r, steps):

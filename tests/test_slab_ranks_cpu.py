@@ -11,6 +11,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import slab_ranks as sr  # noqa: E402
+from harness import bits_equal  # noqa: E402
 
 
 class FakeError(RuntimeError):
@@ -94,8 +95,8 @@ def test_gather_by_id_returns_a_partition_in_id_order_bit_for_bit():
     source[2, 1], source[4, 0] = np.nan, -0.0
     g = group_over(source, [[4, 0], [], [5, 3, 1, 2]])
     out, seen = sr.gather_by_id(g.sims, 0)
-    assert seen.tolist() == [1] * 6 and sr.same_bits(out, source)
-    assert sr.same_bits(g.gather(0), source)
+    assert seen.tolist() == [1] * 6 and bits_equal(out, source)
+    assert bits_equal(g.gather(0), source)
 
 
 def test_a_missing_and_a_duplicated_id_show_in_the_counts_and_fail_the_gather():
@@ -109,9 +110,9 @@ def test_a_missing_and_a_duplicated_id_show_in_the_counts_and_fail_the_gather():
 
 def test_same_bits_is_a_comparison_of_bits():
     a = np.array([0.0, np.nan], dtype=np.float32)
-    assert not sr.same_bits(a, np.array([-0.0, np.nan], dtype=np.float32))
-    assert sr.same_bits(a, a.copy()) and not np.array_equal(a, a.copy())
-    assert not sr.same_bits(a, a[:1])
+    assert not bits_equal(a, np.array([-0.0, np.nan], dtype=np.float32))
+    assert bits_equal(a, a.copy()) and not np.array_equal(a, a.copy())
+    assert not bits_equal(a, a[:1])
 
 
 def test_stat_row():

@@ -12,13 +12,12 @@ Every comparison is bit for bit against the one-GPU handle, which tests/test_rig
 import copy
 import json
 import os
-import subprocess
-import sys
 
 import pytest
 
 from cfd_taichi_amd import _native as nat
 from cfd_taichi_amd import scenes
+from harness import run_ranks
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WORKER = os.path.join(ROOT, "tests", "slab_rigid_worker.py")
@@ -43,28 +42,10 @@ def write_scene(tmp_path, solver, tilted):
     return str(path)
 
 
-def free_port():
-    import socket
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
 def run_worker(tmp_path, transport, solver, tilted, world, steps, rebalance, env_extra=None):
     out = tmp_path / ("rigid_%s_%s_%d_%d.json" % (transport, solver, world, rebalance))
-    tail = [WORKER, "--scene", write_scene(tmp_path, solver, tilted), "--transport", transport, "--world", str(world), "--steps", str(steps),
-            "--rebalance", str(rebalance), "--out", str(out)]
-    if transport == "gloo":
-        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
-               "--master-port", str(free_port())] + tail
-    else:
-        cmd = [sys.executable] + tail
-    # SPH_SLAB_CHECK: every step, the host's bookkeeping of the edge-column populations is compared with the sorted arrays
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2", SPH_SLAB_CHECK="1")
-    env.update(env_extra or {})
-    p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
-    return json.loads(out.read_text())
+    args = ["--scene", write_scene(tmp_path, solver, tilted), "--transport", transport, "--world", world, "--steps", steps, "--rebalance", rebalance, "--out", out]
+    return run_ranks(WORKER, args, world, transport, out, env_extra)
 
 
 def check(r, world, solver, rebalance, tilted=False):

@@ -9,12 +9,11 @@ starts at x = 0.245 -- its sample planes at 0.245, 0.295, ..., 0.645, the plane 
 import copy
 import json
 import os
-import subprocess
-import sys
 
 import pytest
 
-from test_slab_rigid_gpu import free_port, scene_config
+from harness import run_ranks
+from test_slab_rigid_gpu import scene_config
 
 pytestmark = pytest.mark.gpu
 
@@ -39,22 +38,8 @@ def run_worker(tmp_path, transport, solver, mode, world, steps, rebalance):
     scene = tmp_path / ("%s_%s_body.json" % (solver, mode))
     scene.write_text(json.dumps(scripted_scene(solver, mode)))
     out = tmp_path / ("scripted_%s_%s_%d.json" % (transport, solver, world))
-    tail = [WORKER, "--scene", str(scene), "--transport", transport, "--world", str(world), "--steps", str(steps), "--rebalance", str(rebalance),
-            "--mode", mode, "--vel"] + [str(v) for v in VEL] + ["--out", str(out)]
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2", SPH_SLAB_CHECK="1")
-    for attempt in range(2):
-        if transport == "gloo":
-            cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
-                   "--master-port", str(free_port())] + tail
-        else:
-            cmd = [sys.executable] + tail
-        p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
-        # free_port() names a port that was free a moment ago; if someone else on the machine took it before the launcher's store could listen,
-        # no worker was started: once more, with another port
-        if p.returncode == 0 or "EADDRINUSE" not in p.stderr:
-            break
-    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
-    return json.loads(out.read_text())
+    args = ["--scene", scene, "--transport", transport, "--world", world, "--steps", steps, "--rebalance", rebalance, "--mode", mode, "--vel"] + VEL + ["--out", out]
+    return run_ranks(WORKER, args, world, transport, out)
 
 
 def check(r, world, mode):

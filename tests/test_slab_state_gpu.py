@@ -5,12 +5,11 @@ The yardstick (tests/slab_state_worker.py): A = a fresh one-GPU handle given the
 B = fresh slab handles given the same state with sph_slab_set_state; positions, velocities, densities and the step statistics of B equal A's
 bit for bit after every following step.  No tolerance anywhere.  The ranks are handles of one process on the loopback stand-in for the native
 transport (one gloo case covers the callback transport), with SPH_SLAB_CHECK=1."""
-import json
 import os
-import subprocess
-import sys
 
 import pytest
+
+from harness import run_ranks
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,12 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def run_worker(tmp_path, *opts, env_extra=None, timeout=300):
     out = tmp_path / "state.json"
-    cmd = [sys.executable, os.path.join(ROOT, "tests", "slab_state_worker.py"), "--out", str(out)] + [str(o) for o in opts]
-    env = dict(os.environ, SPH_SLAB_CHECK="1")
-    env.update(env_extra or {})
-    p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
-    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
-    return json.loads(out.read_text())
+    return run_ranks(os.path.join(ROOT, "tests", "slab_state_worker.py"), ("--out", out) + opts, None, "loopback", out, env_extra, timeout)
 
 
 def assert_equal_to_one_gpu(r):
@@ -90,15 +84,6 @@ def test_refusals_leave_every_handle_untouched(tmp_path):
 
 def test_set_state_over_torch_distributed(tmp_path):
     """Case 10: SlabSimulation.set_state(..., src=0) -- rank 0's arrays broadcast through torch.distributed (gloo), the callback transport."""
-    import socket
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
     out = tmp_path / "gloo.json"
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "tests", "slab_state_gloo_worker.py"), "--scene", "dfsph_small", "--state-steps", "20", "--steps", "10", "--out", str(out)]
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2", SPH_SLAB_CHECK="1")
-    p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
-    r = json.loads(out.read_text())
+    r = run_ranks(os.path.join(ROOT, "tests", "slab_state_gloo_worker.py"), ("--scene", "dfsph_small", "--state-steps", 20, "--steps", 10, "--out", out), 2, "gloo", out)
     assert r["roundtrip"] and r["first_difference"] is None and r["stats_difference"] is None and r["state_dt"], r

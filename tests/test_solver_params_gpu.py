@@ -10,13 +10,10 @@ import pytest
 
 from cfd_taichi_amd import _native as nat
 from cfd_taichi_amd import scenes
+from harness import same_values
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
-
-
-def same(a, b, what):
-    assert a.shape == b.shape and np.array_equal(a, b), "%s differs at %d of %d entries" % (what, int((a != b).sum()), a.size)
 
 
 def lockstep_dfsph(sim, o, steps):
@@ -29,7 +26,7 @@ def lockstep_dfsph(sim, o, steps):
         assert st.div_first_err == so.div_first_err and st.div_err == so.div_err and st.dens_err == so.dens_err and st.dt == so.dt, s
         counts.append((st.n_div, st.n_dens, st.dt))
     for f, fo, what in ((nat.F_POS, orc.F_POS, "pos"), (nat.F_VEL, orc.F_VEL, "vel"), (nat.F_WARM_K, orc.F_WARM_K, "warm_start_k"), (nat.F_RHO_ADV, orc.F_RHO_ADV, "rho_adv")):
-        same(sim.download(f), o.get(fo), what)
+        same_values(sim.download(f), o.get(fo), what)
     return counts
 
 
@@ -108,8 +105,8 @@ def test_wcsph_viscosity_and_tension(scene, steps):
     for k, v in (("viscosity_c_s", 30.0), ("tension_k", 2.0), ("viscosity_alpha", 0.2)):
         sim.set_param(k, v); o.set_param(nat.SOLVER_PARAMS[k], v)
     sim.step_wcsph(steps); o.step_wcsph(steps)
-    same(sim.download(nat.F_POS), o.get(orc.F_POS), "pos")
-    same(sim.download(nat.F_VEL), o.get(orc.F_VEL), "vel")
+    same_values(sim.download(nat.F_POS), o.get(orc.F_POS), "pos")
+    same_values(sim.download(nat.F_VEL), o.get(orc.F_VEL), "vel")
     ref = nat.Simulation(nat.config_from_dict(cfg))
     ref.step_wcsph(4 + steps)
     assert not np.array_equal(ref.download(nat.F_VEL), sim.download(nat.F_VEL))
@@ -130,8 +127,8 @@ def test_pressure_solvers_viscosity_and_tension(scene, solver, steps):
         st = sim.step(1)
         (o.step_pcisph if solver == "pcisph" else o.step_iisph)(1)
         assert (st.n_dens, st.dens_err) == (o.last_stats.n_dens, o.last_stats.dens_err), s_
-    same(sim.download(nat.F_POS), o.get(orc.F_POS), "pos")
-    same(sim.download(nat.F_VEL), o.get(orc.F_VEL), "vel")
+    same_values(sim.download(nat.F_POS), o.get(orc.F_POS), "pos")
+    same_values(sim.download(nat.F_VEL), o.get(orc.F_VEL), "vel")
     ref = nat.Simulation(nat.config_from_dict(cfg))
     for _ in range(steps):
         ref.step(1)
@@ -181,8 +178,8 @@ def test_mirror_classes_forward_the_attributes():
             solver.max_iteration_density_divergence = 2 # read by a Python-scope loop: takes effect
             o.set_param(nat.SOLVER_PARAMS["max_iteration_density_divergence"], 2)
     assert st.n_div <= 2
-    same(ps.fluid_particles.pos.to_numpy(), o.get(orc.F_POS), "pos")
-    same(ps.fluid_particles.vel.to_numpy(), o.get(orc.F_VEL), "vel")
+    same_values(ps.fluid_particles.pos.to_numpy(), o.get(orc.F_POS), "pos")
+    same_values(ps.fluid_particles.vel.to_numpy(), o.get(orc.F_VEL), "vel")
     o.close()
 
 

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from cfd_taichi_amd import _native as nat
+from harness import bits_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -67,10 +68,6 @@ def image(layout, idx, A, B, S):
     return out
 
 
-def same_bits(got, want):
-    return np.array_equal(np.ascontiguousarray(got).view(np.uint32), np.ascontiguousarray(want).view(np.uint32))
-
-
 @pytest.mark.parametrize("nst", SIZES)
 @pytest.mark.parametrize("layout", LAYOUTS)
 def test_staged_image_is_the_expansion_of_the_runs(layout, nst):
@@ -84,7 +81,7 @@ def test_staged_image_is_the_expansion_of_the_runs(layout, nst):
         for pre in (False, True):                   # the plan's head fetched by the routine, or handed in by the caller: the same image
             got, verdict = nat.selftest_stage(layout, "none", runs, A, B, S, changed, use_pre=pre)
             assert verdict == STAGED, (kind, pre)
-            assert same_bits(got[:nst], want), (kind, pre)
+            assert bits_equal(got[:nst], want), (kind, pre)
             assert not got[nst:].any(), (kind, pre)                 # nothing past the staged set
 
 
@@ -113,7 +110,7 @@ def test_check_verdicts(layout, check):
                 got, verdict = nat.selftest_stage(layout, check, runs, A, B, S, changed, use_pre=pre)
                 assert verdict == expect, (nst, where, pre)
                 if check == "with" or verdict == STAGED:
-                    assert same_bits(got[:nst], image(layout, idx, A, B, S)), (nst, where, pre)
+                    assert bits_equal(got[:nst], image(layout, idx, A, B, S)), (nst, where, pre)
 
 
 @pytest.mark.parametrize("check", list(nat.STAGE_CHECKS))
@@ -131,4 +128,4 @@ def test_unstaged_and_empty_plans(check):
                 assert verdict == (IDLE if idle else STAGED) and not got.any()
                 # the named answer is for the empty set only: a set of one particle with its key set is "staged" (and copied) regardless
                 got, verdict = nat.selftest_stage(layout, check, runs[:1], A, B, S, changed, use_pre=pre, empty_idle=idle)
-                assert verdict == STAGED and same_bits(got[:runs[0, 1]], image(layout, expand(runs[:1]), A, B, S))
+                assert verdict == STAGED and bits_equal(got[:runs[0, 1]], image(layout, expand(runs[:1]), A, B, S))
