@@ -52,6 +52,7 @@ EXPORTS = [
     "sph_create_rigid", "sph_rigid_step", "sph_rigid_set_active", "sph_rigid_init_data", "sph_slab_set_state",
     "sph_rigid_set_mode", "sph_rigid_set_motion", "sph_rigid_get_load", "sph_set_gravity", "sph_set_forcing",
     "sph_add_particles", "sph_remove_in_box", "sph_diagnostics", "sph_diag_record", "sph_diag_read", "sph_derived",
+    "sph_scalar_enable", "sph_scalar_disable", "sph_scalar_upload", "sph_scalar_download", "sph_scalar_set_inflow", "sph_scalar_rate",
 ]
 # the 32 slots of an SphDiagnostics row (include/sph_mi355x.h), in order: the members' names, _x / _y / _z for the vectors
 DIAG_SLOTS = ("time", "dt", "step", "n", "mass", "momentum_x", "momentum_y", "momentum_z",
@@ -194,7 +195,8 @@ CORE_EXPORTS = [
 # library without them raises SphError(SPH_E_STATE)
 OPTIONAL_EXPORTS = ["sph_rigid_set_active", "sph_rigid_init_data", "sph_selftest_stage", "sph_selftest_walk", "sph_slab_set_state",
                     "sph_rigid_set_mode", "sph_rigid_set_motion", "sph_rigid_get_load", "sph_set_gravity", "sph_set_forcing",
-                    "sph_add_particles", "sph_remove_in_box", "sph_diagnostics", "sph_diag_record", "sph_diag_read", "sph_derived"]
+                    "sph_add_particles", "sph_remove_in_box", "sph_diagnostics", "sph_diag_record", "sph_diag_read", "sph_derived",
+                    "sph_scalar_enable", "sph_scalar_disable", "sph_scalar_upload", "sph_scalar_download", "sph_scalar_set_inflow", "sph_scalar_rate"]
 
 
 def _bind_core(lib):
@@ -254,6 +256,13 @@ def _bind_core(lib):
         lib.sph_diag_read.argtypes = [vp, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int64)]
     if hasattr(lib, "sph_derived"):
         lib.sph_derived.argtypes = [vp, ci, vp, ctypes.c_size_t]
+    if hasattr(lib, "sph_scalar_enable"):
+        lib.sph_scalar_enable.argtypes = [vp, ctypes.c_double, ctypes.c_double, ctypes.c_double]
+        lib.sph_scalar_disable.argtypes = [vp]
+        lib.sph_scalar_upload.argtypes = [vp, vp, ctypes.c_size_t]
+        lib.sph_scalar_download.argtypes = [vp, vp, ctypes.c_size_t]
+        lib.sph_scalar_set_inflow.argtypes = [vp, ctypes.c_double]
+        lib.sph_scalar_rate.argtypes = [vp, vp, ctypes.c_size_t]
     return lib
 
 
@@ -424,6 +433,43 @@ def adaptive_dt_calls(config, solver_name=None):
     return calls
 
 
+def scalar_init_values(pos, init, default=0.0):
+    """T of the initial lattice from `scene.scalar.init` = {"value": v, "boxes": [{"min": [...], "max": [...], "value": v}, ...]}: v (absent:
+    `default`, the reference value) everywhere, then every box in turn (later boxes win), a particle being inside when lo <= x < hi on all three
+    axes in f32.  Pure numpy; returns (n,) f32."""
+    pos = np.asarray(pos, dtype=np.float32)
+    init = init or {}
+    if not isinstance(init, dict) or set(init) - {"value", "boxes"}:
+        raise ValueError("scene.scalar.init must be {\"value\": v, \"boxes\": [...]}, got %r" % (init,))
+    out = np.full(len(pos), np.float32(init.get("value", default)), dtype=np.float32)
+    for box in init.get("boxes", []) or []:
+        if not isinstance(box, dict) or set(box) != {"min", "max", "value"}:
+            raise ValueError("scene.scalar.init.boxes: each entry needs min, max and value, got %r" % (box,))
+        lo = np.float32(_vec3(box["min"], "scene.scalar.init.boxes.min"))
+        hi = np.float32(_vec3(box["max"], "scene.scalar.init.boxes.max"))
+        inside = ((lo <= pos) & (pos < hi)).all(axis=1)
+        out[inside] = np.float32(box["value"])
+    return out
+
+
+def scalar_call(config):
+    """What `scene.scalar` = {"diffusivity", "beta", "ref", "init"} of a config asks of a new handle: None without the block, else the keyword
+    arguments of Simulation.enable_scalar but for `values` (diffusivity, beta, ref: 0 where absent) and the init block (or None).  Pure Python; an
+    unknown key or a value that is not a finite number raises ValueError."""
+    block = config["scene"].get("scalar")
+    if block is None:
+        return None
+    if not isinstance(block, dict) or set(block) - {"diffusivity", "beta", "ref", "init"}:
+        raise ValueError("scene.scalar must be {\"diffusivity\", \"beta\", \"ref\", \"init\"}, got %r" % (block,))
+    kw = {}
+    for key in ("diffusivity", "beta", "ref"):
+        v = block.get(key, 0.0)
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or v in (float("inf"), -float("inf")) or (key == "diffusivity" and v < 0):
+            raise ValueError("scene.scalar.%s must be a finite number%s, got %r" % (key, " >= 0" if key == "diffusivity" else "", v))
+        kw[key] = float(v)
+    return kw, block.get("init")
+
+
 def apply_gravity_calls(target, config):
     """make gravity_calls(config) on a Simulation, a SlabSimulation or a solver mirror, right after creation"""
     for name, *args in gravity_calls(config):
@@ -515,6 +561,11 @@ class Simulation:
             apply_gravity_calls(self, config)
             for name, value in adaptive_dt_calls(config, "dfsph" if cfg.solver == SOLVER_DFSPH else "other"):
                 self.set_param(name, value)
+            sc = scalar_call(config)
+            if sc is not None:
+                self.enable_scalar(**sc[0])                  # (a slab handle refuses here)
+                if sc[1] is not None:
+                    self.set_scalar(scalar_init_values(self.download(F_POS), sc[1], default=sc[0]["ref"]))
 
     def _check(self, rc):
         if rc != SPH_OK:
@@ -538,9 +589,17 @@ class Simulation:
         self._check(self._lib.sph_get_sizes(self._h, ctypes.byref(sizes)))
         self._n_fluid = sizes.n_fluid
 
-    def add_particles(self, pos, vel=None):
+    def add_particles(self, pos, vel=None, scalar=None):
         """Append len(pos) fluid particles between steps (sph_add_particles): pos (n, 3), vel (n, 3) or None (at rest).  Returns the original id
-        of the first one; the others follow it.  No overlap test is made against the fluid already there."""
+        of the first one; the others follow it.  No overlap test is made against the fluid already there.  scalar: the carried scalar of the new
+        particles (the handle's inflow value is set for this call and restored); None: the inflow value as it stands."""
+        if scalar is not None:
+            keep = getattr(self, "_scalar_inflow", 0.0)
+            self.set_scalar_inflow(scalar)
+            try:
+                return self.add_particles(pos, vel)
+            finally:
+                self.set_scalar_inflow(keep)
         pos = np.ascontiguousarray(pos, dtype=np.float32)
         if pos.ndim != 2 or pos.shape[1] != 3:
             raise ValueError("pos must be (n, 3), got %s" % (pos.shape,))
@@ -596,6 +655,42 @@ class Simulation:
         shape = DERIVED_SHAPE.get(wid, ())
         out = np.empty((self._n_fluid,) + shape, dtype=np.float32)
         self._check(self._optional("sph_derived")(self._h, wid, out.ctypes.data, out.size))
+        return out
+
+    def enable_scalar(self, diffusivity=0.0, beta=0.0, ref=0.0, values=None):
+        """Switch the carried scalar on (sph_scalar_enable), or change its parameters: diffusivity D in m^2/s, the buoyancy
+        coefficient beta (0: passive) and the reference value.  A first call sets T = ref everywhere and the inflow value to ref; values: (n,) to
+        upload behind it."""
+        fresh = not getattr(self, "_scalar_on", False)
+        self._check(self._optional("sph_scalar_enable")(self._h, float(diffusivity), float(beta), float(ref)))
+        self._scalar_on = True
+        if fresh:
+            self._scalar_inflow = float(ref)
+        if values is not None:
+            self.set_scalar(values)
+
+    def disable_scalar(self):
+        """sph_scalar_disable: the memory is freed, the handle steps as if the scalar had never been enabled"""
+        self._check(self._optional("sph_scalar_disable")(self._h))
+        self._scalar_on = False
+
+    def set_scalar(self, values):
+        """upload the carried scalar, (n,) in original particle order (sph_scalar_upload)"""
+        arr = np.ascontiguousarray(values, dtype=np.float32)
+        if arr.shape != (self._n_fluid,):
+            raise ValueError("expected shape %s, got %s" % ((self._n_fluid,), arr.shape))
+        self._check(self._optional("sph_scalar_upload")(self._h, arr.ctypes.data, arr.size))
+
+    def set_scalar_inflow(self, value):
+        """the carried scalar of the particles add_particles brings from now on (sph_scalar_set_inflow)"""
+        self._check(self._optional("sph_scalar_set_inflow")(self._h, float(value)))
+        self._scalar_inflow = float(value)
+
+    def scalar_rate(self):
+        """dT/dt of the state as it stands, (n,) f32 in original particle order (sph_scalar_rate): builds the lists first if positions changed
+        (build_neighbors' caveat applies); changes neither T nor any trajectory"""
+        out = np.empty(self._n_fluid, dtype=np.float32)
+        self._check(self._optional("sph_scalar_rate")(self._h, out.ctypes.data, out.size))
         return out
 
     def close(self):
@@ -707,7 +802,13 @@ class Simulation:
     def compute_alpha(self):
         self._check(self._lib.sph_compute_alpha(self._h))
 
-    def scalar(self, which):
+    def scalar(self, which=None):
+        """scalar(S_*): a scalar of the handle (sph_get_scalar).  scalar(): the carried scalar, (n,) f32 in original particle order
+        (sph_scalar_download)"""
+        if which is None:
+            out = np.empty(self._n_fluid, dtype=np.float32)
+            self._check(self._optional("sph_scalar_download")(self._h, out.ctypes.data, out.size))
+            return out
         out = ctypes.c_double()
         self._check(self._lib.sph_get_scalar(self._h, which, ctypes.byref(out)))
         return out.value

@@ -304,12 +304,15 @@ int step_begin(SphHandle *h)
     if (h->step_adaptive) launch_step_dt(h);
     if (is_pressure_solver(h) && (rc = require_async_slab(h))) return rc;
     if ((rc = stage_sort_and_lists(h))) return rc;
+    if (scalar_on(h)) launch_scalar_rate(h);                 // the carried scalar's rate at the positions the step starts from (section 6k)
     return h->cfg.solver == SPH_SOLVER_PBF ? SPH_OK : stage_density(h);
 }
 // ... and behind its integrator: the positions moved, so neither the lists nor the densities describe them
-// While diagnostics are being recorded (sph_diag_record) the step's row follows here, for every solver and every step of a multi-step call
+// While diagnostics are being recorded (sph_diag_record) the step's row follows here, for every solver and every step of a multi-step call; in front
+// of it, while the carried scalar is enabled, its kick and Euler step (the row sees the kicked velocities)
 int step_end(SphHandle *h)
 {
+    if (scalar_on(h)) scalar_step_end(h);                    // the carried scalar: the kick and T's Euler step (section 6k)
     if (h->diag_every)
         if (int rc = diag_step_end(h)) return rc;
     HIP_TRY(h, hipGetLastError());

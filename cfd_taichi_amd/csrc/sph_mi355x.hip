@@ -27,6 +27,7 @@
 #include "sph_relaxed_kernels.h"
 #include "sph_diag_kernels.h"
 #include "sph_derived_kernels.h"
+#include "sph_scalar_kernels.h"
 #include "sph_selftest_walk.h"
 
 using namespace sph;
@@ -37,14 +38,14 @@ enum KernelId {
     K_HASH = 0, K_SCAN, K_SCATTER, K_ORDER_GATHER, K_BUILD_NL, K_W_DENSITY, K_W_FORCE, K_D_DENSITY_ALPHA,
     K_D_WARM, K_D_DIV_RESIDUAL, K_D_DIV_CORRECT, K_D_EXT, K_D_DENS_RESIDUAL, K_D_DENS_CORRECT, K_D_INTEGRATE,
     K_FINALIZE, K_TRANSFER, K_SLAB, K_RIGID, K_P_EXT, K_P_PREDICT_RHO, K_P_PRESS, K_P_INTEGRATE, K_I_ADVECT, K_I_RHO_ADV, K_I_DIJ,
-    K_I_UPDATE_P, K_I_INTEGRATE, K_B_LAMBDA, K_B_DELTA, K_B_XSPH, K_ACCEL, K_DERIVED, K_COUNT
+    K_I_UPDATE_P, K_I_INTEGRATE, K_B_LAMBDA, K_B_DELTA, K_B_XSPH, K_ACCEL, K_DERIVED, K_SCALAR, K_COUNT
 };
 const char *kKernelNames[K_COUNT] = {
     "hash_count", "scan", "scatter", "order_gather", "build_nl", "wcsph_density", "wcsph_force", "dfsph_density_alpha",
     "dfsph_warm_start", "dfsph_div_residual", "dfsph_div_correct", "dfsph_ext_force", "dfsph_dens_residual",
     "dfsph_dens_correct", "dfsph_integrate", "finalize", "transfer", "slab_exchange", "rigid",
     "pcisph_ext_force", "pcisph_predict_rho", "pcisph_press_force", "pcisph_integrate", "iisph_advect", "iisph_rho_adv", "iisph_d_ij",
-    "iisph_update_p", "iisph_integrate", "pbf_lambda", "pbf_delta_pos", "pbf_xsph", "accel_eval", "derived"};
+    "iisph_update_p", "iisph_integrate", "pbf_lambda", "pbf_delta_pos", "pbf_xsph", "accel_eval", "derived", "scalar"};
 
 thread_local std::string g_create_error;
 thread_local bool g_creating_with_rigid = false;     // sph_create_rigid builds the fluid handle first: no Verlet lists there (the body moves through the grid)
@@ -279,6 +280,14 @@ struct SphHandle {
     float *drv_out = nullptr, *drv_api = nullptr;
     bool derived_valid = false;
 
+    // the carried scalar: memory of its own, taken by sph_scalar_enable and freed by sph_scalar_disable; sc_T != null is
+    // "enabled".  sc_T: the values by particle id (API order); sc_XT: (x, y, z, T) packed in device order; sc_rate: dT/dt in device order, scratch
+    // between steps
+    float4 *sc_XT = nullptr;
+    float *sc_rate = nullptr, *sc_T = nullptr;
+    double sc_D = 0.0;
+    float sc_beta = 0.f, sc_ref = 0.f, sc_inflow = 0.f;
+
     // profiling
     bool profiling = false;
     struct Ev { hipEvent_t a, b; int kid; };
@@ -346,6 +355,7 @@ inline dim3 grid_for(int n) { return dim3((unsigned)std::max(1, (n + kBlock - 1)
 #include "sph_host_diag.h"
 #include "sph_host_transport.h"
 #include "sph_host_rigid.h"
+#include "sph_host_scalar.h"
 #include "sph_host_dfsph.h"
 #include "sph_host_pressure.h"
 #include "sph_host_derived.h"
@@ -621,6 +631,8 @@ int sph_add_particles(SphHandle *h, const float *pos, const float *vel, size_t n
         HIP_TRY(h, hipStreamSynchronize(s));          // (rows is reused)
         at += (int)m;
     }
+    if (scalar_on(h))                                 // the new rows carry the handle's inflow value
+        if (int rc = scalar_fill(h, h->N, at - h->N, h->sc_inflow)) return rc;
     if (first_id) *first_id = h->N;
     return fluid_count_changed(h, at);
 }
@@ -670,6 +682,8 @@ int sph_remove_in_box(SphHandle *h, const float lo[3], const float hi[3], int32_
                            h->id[1 - h->icur]);
     }
     HIP_TRY(h, hipGetLastError());
+    if (scalar_on(h))
+        if (int rc = scalar_compact(h, n, n - r, box, P, id, scan_id)) return rc;
     h->pcur ^= 1; h->vcur ^= 1; h->icur ^= 1;
     if (carry) h->wcur ^= 1;
     return fluid_count_changed(h, n - r);
@@ -688,6 +702,7 @@ void sph_destroy(SphHandle *h)
     if (h->diag_ring) (void)hipFree(h->diag_ring);
     if (h->diag_ctl) (void)hipFree(h->diag_ctl);
     if (h->drv_vr) (void)hipFree(h->drv_vr);
+    if (h->sc_XT) (void)hipFree(h->sc_XT);
     if (h->rred_host) (void)hipHostFree(h->rred_host);
     if (h->own_dev_comm) { (void)hipFree(h->dsend[0]); (void)hipFree(h->dsend[1]); (void)hipFree(h->drecv[0]); (void)hipFree(h->drecv[1]); }
     if (h->own_red) (void)hipFree(h->red_dev);
@@ -1337,6 +1352,24 @@ int sph_set_forcing(SphHandle *h, const double amp[3], const double omega[3], co
     }
     return forcing_commit(h);
 }
+
+// ---- the carried scalar ----------------------------------------------------------------------------------------
+int sph_scalar_enable(SphHandle *h, double diffusivity, double beta, double t_ref) { return h ? scalar_enable(h, diffusivity, beta, t_ref) : SPH_E_INVALID; }
+int sph_scalar_disable(SphHandle *h) { return h ? scalar_disable(h) : SPH_E_INVALID; }
+int sph_scalar_upload(SphHandle *h, const float *values, size_t n)
+{
+    if (!h) return SPH_E_INVALID;
+    if (!values) { if (int rc = scalar_refused(h, "sph_scalar_upload", true)) return rc; return fail(h, SPH_E_INVALID, "sph_scalar_upload: null argument"); }
+    return scalar_copy(h, "sph_scalar_upload", nullptr, values, n);
+}
+int sph_scalar_download(SphHandle *h, float *values, size_t n)
+{
+    if (!h) return SPH_E_INVALID;
+    if (!values) { if (int rc = scalar_refused(h, "sph_scalar_download", true)) return rc; return fail(h, SPH_E_INVALID, "sph_scalar_download: null argument"); }
+    return scalar_copy(h, "sph_scalar_download", values, nullptr, n);
+}
+int sph_scalar_set_inflow(SphHandle *h, double value) { return h ? scalar_set_inflow(h, value) : SPH_E_INVALID; }
+int sph_scalar_rate(SphHandle *h, float *out, size_t n) { return h ? scalar_rate_fetch(h, out, n) : SPH_E_INVALID; }
 
 // ---- derived per-particle fields ------------------------------------------------------------------------------
 int sph_derived(SphHandle *h, int which, float *host, size_t n_floats)

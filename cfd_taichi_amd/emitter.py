@@ -48,9 +48,11 @@ class Emitter:
     add_particles call, every layer with t_k < min(t, stop) that has not been emitted yet, each advanced by speed (t - t_k) along the direction
     -- where it would be had it left the opening at t_k -- with the velocity speed * direction.  All of it in f64, rounded to f32 once.
     A layer that would exceed the simulation's capacity or `max_particles` ends the emitter (`exhausted`); partial layers are never emitted.
+    `scalar`: the carried scalar of what it pours in (add_particles(pos, vel, scalar=v); the simulation's scalar must be enabled); None: the
+    simulation's inflow value.
     """
 
-    def __init__(self, center, direction, size, speed, start=0.0, stop=math.inf, max_particles=None, radius=None):
+    def __init__(self, center, direction, size, speed, start=0.0, stop=math.inf, max_particles=None, radius=None, scalar=None):
         if radius is None or not (float(radius) > 0.0):
             raise ValueError("Emitter needs radius > 0 (from_config passes scene.particle_radius)")
         self.center = _vec3(center, "center")
@@ -67,6 +69,9 @@ class Emitter:
         if not (self.speed > 0.0) or not math.isfinite(self.speed) or not math.isfinite(self.start) or math.isnan(self.stop):
             raise ValueError("speed must be finite and > 0, start finite, stop a number or inf")
         self.max_particles = None if max_particles is None else int(max_particles)
+        self.scalar = None if scalar is None else float(scalar)
+        if self.scalar is not None and not math.isfinite(self.scalar):
+            raise ValueError("scalar must be a finite number, got %r" % (scalar,))
         self.radius = float(radius)
         self.d = 2.0 * self.radius
         y, x = np.array([0.0, 1.0, 0.0]), np.array([1.0, 0.0, 0.0])
@@ -122,13 +127,16 @@ class Emitter:
             return 0
         pos = np.concatenate(rows).astype(np.float32)
         vel = np.broadcast_to((self.speed * self.direction).astype(np.float32), pos.shape)
-        sim.add_particles(pos, np.ascontiguousarray(vel))
+        if self.scalar is None:
+            sim.add_particles(pos, np.ascontiguousarray(vel))
+        else:
+            sim.add_particles(pos, np.ascontiguousarray(vel), scalar=self.scalar)
         self.layers_emitted = k
         self.emitted += len(pos)
         return len(pos)
 
 
-_EMITTER_KEYS = {"center", "direction", "size", "speed", "start", "stop", "max_particles", "radius"}
+_EMITTER_KEYS = {"center", "direction", "size", "speed", "start", "stop", "max_particles", "radius", "scalar"}
 
 
 def from_config(config):
@@ -138,7 +146,7 @@ def from_config(config):
     emitters, sinks = [], []
     for e in scene.get("emitters", []) or []:
         if not isinstance(e, dict) or set(e) - _EMITTER_KEYS or not {"center", "direction", "size", "speed"} <= set(e):
-            raise ValueError("scene.emitters: each entry needs center, direction, size, speed (optional: start, stop, max_particles, radius), got %r" % (e,))
+            raise ValueError("scene.emitters: each entry needs center, direction, size, speed (optional: start, stop, max_particles, radius, scalar), got %r" % (e,))
         kw = dict(e)
         kw.setdefault("radius", scene["particle_radius"])
         emitters.append(Emitter(**kw))

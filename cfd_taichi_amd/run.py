@@ -15,7 +15,8 @@ then the emitters; the PLY frames hold the particles of the moment.  Single GPU,
 the end of every N-th solver step and drained once per frame; one CSV line per recorded step under a header of the slot names, written at the end of
 the run.  Single GPU.
 --ply-fields vorticity,divergence,normal,cover: derived per-particle fields (Simulation.derived) as further `property float` columns of every PLY
-frame, after alpha: vort_x vort_y vort_z div normal_x normal_y normal_z cover -- only the named ones, always in that order.  Single GPU."""
+frame, after alpha: vort_x vort_y vort_z div normal_x normal_y normal_z cover -- only the named ones, always in that order.  `scalar`: the carried
+scalar (scene.scalar; Simulation.scalar()) as one more column `scalar` behind them.  Single GPU."""
 import argparse
 import importlib
 import os
@@ -31,12 +32,13 @@ LAST = {}      # the objects of the last single-GPU main() call (ps, solver, rig
 
 # --ply-fields: the derived fields a PLY frame can carry, in column order, with their column names
 PLY_FIELDS = (("vorticity", ("vort_x", "vort_y", "vort_z")), ("divergence", ("div",)), ("normal", ("normal_x", "normal_y", "normal_z")), ("cover", ("cover",)))
+PLY_SCALAR = "scalar"          # ... and the carried scalar, which is no derived field: always the last column
 
 
 def parse_ply_fields(text):
     """the names of --ply-fields in column order (whatever order they were given in); an unknown name ends the run"""
     asked = [w.strip() for w in (text or "").split(",") if w.strip()]
-    known = [name for name, _ in PLY_FIELDS]
+    known = [name for name, _ in PLY_FIELDS] + [PLY_SCALAR]
     for w in asked:
         if w not in known:
             raise SystemExit("--ply-fields: unknown field '%s' (choose from %s)" % (w, ", ".join(known)))
@@ -44,9 +46,12 @@ def parse_ply_fields(text):
 
 
 def ply_extra(sim, fields):
-    """[(column names, (n, k) values)] of the named derived fields of the state `sim` holds"""
+    """[(column names, (n, k) values)] of the named derived fields of the state `sim` holds, the carried scalar behind them"""
     cols = dict(PLY_FIELDS)
-    return [(cols[name], sim.derived(name).reshape(sim.n_fluid, -1)) for name in fields]
+    out = [(cols[name], sim.derived(name).reshape(sim.n_fluid, -1)) for name in fields if name != PLY_SCALAR]
+    if PLY_SCALAR in fields:
+        out.append(((PLY_SCALAR,), sim.scalar().reshape(sim.n_fluid, 1)))
+    return out
 
 
 def write_ply_ascii(path, pos, rgba, extra=()):
@@ -93,6 +98,8 @@ def main_sharded(args, config):
         raise SystemExit("rigid bodies are not sharded: run this config on one GPU")
     if config["scene"].get("emitters") or config["scene"].get("sinks") or config["fluid"].get("capacity"):
         raise SystemExit("emitters, sinks and fluid.capacity are not sharded: run this config on one GPU")
+    if config["scene"].get("scalar") is not None or PLY_SCALAR in args.ply_fields:
+        raise SystemExit("the carried scalar (scene.scalar, --ply-fields scalar) is not sharded: run this config on one GPU")
     own_gpu = torch.cuda.device_count() >= int(os.environ.get("LOCAL_WORLD_SIZE", world))
     device = local if own_gpu else 0
     if own_gpu:
@@ -151,7 +158,7 @@ def main(argv=None):
                     help="activate the rigid body when frame_cnt reaches FRAME (main.py:100-106: let the fluid settle first)")
     ap.add_argument("--diag-csv", default=None, metavar="PATH", help="record the fluid's run diagnostics on the device and write them as CSV at the end of the run")
     ap.add_argument("--diag-every", type=int, default=1, metavar="N", help="with --diag-csv: one row every N solver steps (default 1)")
-    ap.add_argument("--ply-fields", default=None, metavar="NAMES", help="derived fields as extra PLY columns: a comma-separated choice of vorticity, divergence, normal, cover")
+    ap.add_argument("--ply-fields", default=None, metavar="NAMES", help="derived fields as extra PLY columns: a comma-separated choice of vorticity, divergence, normal, cover, scalar")
     args = ap.parse_args(argv)
     args.ply_fields = parse_ply_fields(args.ply_fields)
     if args.diag_csv and args.diag_every < 1:

@@ -192,6 +192,24 @@ SCENES.update({
 })
 
 
+def _with_scalar(cfg, diffusivity, beta, ref, value, boxes):
+    cfg["scene"]["scalar"] = {"diffusivity": diffusivity, "beta": beta, "ref": ref,
+                              "init": {"value": value, "boxes": [{"min": list(lo), "max": list(hi), "value": v} for lo, hi, v in boxes]}}
+    return cfg
+
+
+SCENES.update({
+    # not the reference's: the carried scalar (`scene.scalar`).
+    # A lock exchange: the closed tank of sloshing_dfsph at rest (2 288 particles), its left half warm (T = 1), its right half cold (T = 0); with
+    # beta > 0 the warm water is lifted and runs over the cold, which slides under it, while the two diffuse into each other
+    "lock_exchange_dfsph": lambda: _with_scalar(_with_radius(_scene("dfsph", 1e-3, [1.2, 0.8, 0.6], [1.04, 0.32, 0.44], start_pos=(0.08, 0.08, 0.08)), 0.02),
+                                                1e-4, 0.3, 0.5, 0.0, [([0.0, 0.0, 0.0], [0.6, 0.8, 0.6], 1.0)]),
+    # The 30 k dam break with the upper half of the column dyed (T = 1 above y = 1.5): a passive scalar (beta = 0) that shows how the column folds
+    "dye_dam_wcsph": lambda: _with_scalar(_scene("wcsph", 2.5e-4, [5.0, 3.0, 1.5], [1.0, 2.8, 1.3]),
+                                          1e-3, 0.0, 0.0, 0.0, [([0.0, 1.5, 0.0], [5.0, 3.0, 1.5], 1.0)]),
+})
+
+
 def get(name):
     return SCENES[name]()
 

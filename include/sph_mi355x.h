@@ -378,6 +378,40 @@ int sph_diag_read(SphHandle *h, SphDiagnostics *out, size_t max_rows, size_t *n_
  * per particle of the capacity) is taken at the first call.  Refusals leave the handle unchanged -- SPH_E_STATE: a slab handle; SPH_E_INVALID:
  * host == NULL, an unknown `which`, a wrong n_floats. */
 int sph_derived(SphHandle *h, int which, float *host, size_t n_floats);
+
+/* One carried scalar per single-GPU handle: a temperature or a dye concentration T that rides with the particles, diffuses
+ * between fluid neighbours and, with beta != 0, lifts the fluid.  Off by default; a handle that never enables it launches what it always launched.
+ * Any of the five solvers, exact or relaxed arithmetic, with or without a body, with or without fluid_capacity.  T is kept by particle id (API
+ * order) in memory of the feature's own, 24 B per particle of the capacity, taken at enable and freed at disable.
+ * Per solver step, while enabled:
+ *   behind the sort and the list build, at the positions x^n the step starts from:
+ *     rate_i = kq sum_j (T_i - T_j) f_ij,   f_ij = (g(q) r) / (r^2 + eta2),   q = r / h,   g = q <= 1/2 ? 3 q^2 - 2 q : -(1 - q)^2
+ *     over the FLUID entries j of i's list with r <= h, in list order, f32, unfused; eta2 = 0.01 h^2, kq = 12 D (m / rho0) kw / h, both formed in
+ *     f64 and rounded once.  This is Brookshaw's Laplacian 2 D sum V0 (T_i - T_j) W'(r) r / (r^2 + eta2) with the constant particle volume
+ *     V0 = m / rho0 and the TRUE W'(r) = 6 kw g / h (not the reference's gradient, which carries a further factor 6): D is a diffusivity in m^2/s.
+ *     Walls and a body's samples are insulated (they add nothing).  No density is read; the pair term is antisymmetric bit for bit.
+ *   behind the solver's integrator, with the dt the step used and a = the step's acceleration vector (SPH_S_ACCEL):
+ *     beta != 0:  vel_i += (dt s) a,  s = -(beta (T_i - t_ref))  from T^n (a Boussinesq kick, first-order splitting: the next step's CFL rule and
+ *     pressure solve see it); beta == 0: the velocities are not touched.  Then T_i += dt rate_i.
+ * The scheme is explicit: the caller keeps dt sum_j c_ij <= 1, c_ij = -kq f_ij >= 0 (undisturbed lattice of spacing 2 r, h = 4 r: dt <= 0.0585 h^2 / D
+ * -- DESIGN.md section 6k).  Nothing enforces it.
+ * Between steps: sph_add_particles gives every new particle the inflow value; sph_remove_in_box keeps the survivors' values under their new ids;
+ * sph_upload and sph_slab_set_state do not touch T; the stage calls, sph_derived and sph_diagnostics neither read nor advance it.
+ * Refusals come before any launch and leave the handle unchanged -- SPH_E_STATE: a slab handle; download / upload / rate / set_inflow before
+ * enable.  SPH_E_INVALID: a null pointer, n != the live particle count, a diffusivity that is negative or not finite, a beta, t_ref or value that
+ * is not finite (upload: any of the n values). */
+/* allocates, sets T = t_ref everywhere and the inflow value to t_ref.  On an enabled handle: changes the three parameters, keeps T and the inflow value */
+int sph_scalar_enable(SphHandle *h, double diffusivity, double beta, double t_ref);
+/* frees; the handle steps as if it had never been enabled.  Not enabled: nothing happens */
+int sph_scalar_disable(SphHandle *h);
+/* T in API (original particle) order; n must be the live particle count */
+int sph_scalar_upload(SphHandle *h, const float *values, size_t n);
+int sph_scalar_download(SphHandle *h, float *values, size_t n);
+/* the value sph_add_particles gives to new particles from now on */
+int sph_scalar_set_inflow(SphHandle *h, double value);
+/* rate_i of the CURRENT state in API order.  Builds the lists first if positions changed since the last build (what sph_build_neighbors does; its
+ * caveat applies); changes neither T nor any trajectory.  Profile id "scalar". */
+int sph_scalar_rate(SphHandle *h, float *out, size_t n);
 void sph_destroy(SphHandle *h);
 int sph_get_sizes(SphHandle *h, SphSizes *out);
 const char *sph_last_error(SphHandle *h);
