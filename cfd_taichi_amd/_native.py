@@ -53,6 +53,7 @@ EXPORTS = [
     "sph_rigid_set_mode", "sph_rigid_set_motion", "sph_rigid_get_load", "sph_set_gravity", "sph_set_forcing",
     "sph_add_particles", "sph_remove_in_box", "sph_diagnostics", "sph_diag_record", "sph_diag_read", "sph_derived",
     "sph_scalar_enable", "sph_scalar_disable", "sph_scalar_upload", "sph_scalar_download", "sph_scalar_set_inflow", "sph_scalar_rate",
+    "sph_geometry_add", "sph_geometry_remove", "sph_geometry_info", "sph_geometry_carve", "sph_geometry_wall_counts",
 ]
 # the 32 slots of an SphDiagnostics row (include/sph_mi355x.h), in order: the members' names, _x / _y / _z for the vectors
 DIAG_SLOTS = ("time", "dt", "step", "n", "mass", "momentum_x", "momentum_y", "momentum_z",
@@ -196,7 +197,8 @@ CORE_EXPORTS = [
 OPTIONAL_EXPORTS = ["sph_rigid_set_active", "sph_rigid_init_data", "sph_selftest_stage", "sph_selftest_walk", "sph_slab_set_state",
                     "sph_rigid_set_mode", "sph_rigid_set_motion", "sph_rigid_get_load", "sph_set_gravity", "sph_set_forcing",
                     "sph_add_particles", "sph_remove_in_box", "sph_diagnostics", "sph_diag_record", "sph_diag_read", "sph_derived",
-                    "sph_scalar_enable", "sph_scalar_disable", "sph_scalar_upload", "sph_scalar_download", "sph_scalar_set_inflow", "sph_scalar_rate"]
+                    "sph_scalar_enable", "sph_scalar_disable", "sph_scalar_upload", "sph_scalar_download", "sph_scalar_set_inflow", "sph_scalar_rate",
+                    "sph_geometry_add", "sph_geometry_remove", "sph_geometry_info", "sph_geometry_carve", "sph_geometry_wall_counts"]
 
 
 def _bind_core(lib):
@@ -263,6 +265,13 @@ def _bind_core(lib):
         lib.sph_scalar_download.argtypes = [vp, vp, ctypes.c_size_t]
         lib.sph_scalar_set_inflow.argtypes = [vp, ctypes.c_double]
         lib.sph_scalar_rate.argtypes = [vp, vp, ctypes.c_size_t]
+    if hasattr(lib, "sph_geometry_add"):
+        lib.sph_geometry_add.argtypes = [vp, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int32)]
+        lib.sph_geometry_remove.argtypes = [vp, ctypes.c_int32]
+        lib.sph_geometry_info.argtypes = [vp, vp, vp, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+        lib.sph_geometry_carve.argtypes = [vp, ctypes.c_int32, ctypes.c_float, ctypes.POINTER(ctypes.c_int32)]
+    if hasattr(lib, "sph_geometry_wall_counts"):
+        lib.sph_geometry_wall_counts.argtypes = [vp, vp, ctypes.c_size_t]
     return lib
 
 
@@ -557,6 +566,7 @@ class Simulation:
         self.n_cells = sizes.n_cells
         self.max_neighbors, self.max_wall_neighbors = sizes.max_neighbors, sizes.max_wall_neighbors
         self.last_stats = SphStepStats()
+        self.geometry_groups = {}
         if config is not None:
             apply_gravity_calls(self, config)
             for name, value in adaptive_dt_calls(config, "dfsph" if cfg.solver == SOLVER_DFSPH else "other"):
@@ -566,6 +576,8 @@ class Simulation:
                 self.enable_scalar(**sc[0])                  # (a slab handle refuses here)
                 if sc[1] is not None:
                     self.set_scalar(scalar_init_values(self.download(F_POS), sc[1], default=sc[0]["ref"]))
+            from . import geometry as _geometry
+            self.geometry_groups = _geometry.apply_config(self, config)      # `scene.geometry`: name -> group
 
     def _check(self, rc):
         if rc != SPH_OK:
@@ -622,6 +634,55 @@ class Simulation:
         self._check(self._optional("sph_remove_in_box")(self._h, lo.ctypes.data, hi.ctypes.data, ctypes.byref(removed)))
         self._refresh_count()
         return int(removed.value)
+
+    def _refresh_walls(self):
+        sizes = SphSizes()
+        self._check(self._lib.sph_get_sizes(self._h, ctypes.byref(sizes)))
+        self.n_wall = sizes.n_wall
+
+    def add_geometry(self, points):
+        """Append static geometry between steps (sph_geometry_add): points (n, 3) f32 in world coordinates become wall
+        samples of a new group, felt by every sweep as the box is.  Returns the group's id (1, 2, ...: never reused).  The volumes of all wall
+        samples are recomputed; n_wall and the wall downloads report the new set.  cfd_taichi_amd.geometry has samplers."""
+        pts = np.ascontiguousarray(points, dtype=np.float32)
+        if pts.ndim != 2 or pts.shape[1] != 3:
+            raise ValueError("points must be (n, 3), got %s" % (pts.shape,))
+        group = ctypes.c_int32(0)
+        self._check(self._optional("sph_geometry_add")(self._h, pts.ctypes.data if len(pts) else None, len(pts), ctypes.byref(group)))
+        self._refresh_walls()
+        return int(group.value)
+
+    def remove_geometry(self, group):
+        """Take a group out of the wall set between steps (sph_geometry_remove): later groups move down in the wall arrays and keep their ids"""
+        self._check(self._optional("sph_geometry_remove")(self._h, int(group)))
+        self._refresh_walls()
+
+    def geometry(self):
+        """the live groups in order of addition: a list of (group, first, count), [first, first + count) being the group's rows of the wall downloads"""
+        info = self._optional("sph_geometry_info")
+        n = ctypes.c_size_t(0)
+        self._check(info(self._h, None, None, None, 0, ctypes.byref(n)))
+        cap = max(int(n.value), 1)
+        g, f, c = (np.zeros(cap, dtype=np.int32) for _ in range(3))
+        self._check(info(self._h, g.ctypes.data, f.ctypes.data, c.ctypes.data, cap, ctypes.byref(n)))
+        return [(int(g[k]), int(f[k]), int(c[k])) for k in range(int(n.value))]
+
+    def carve(self, group=-1, clearance=None):
+        """Remove every fluid particle nearer than `clearance` (default: the particle diameter; at most h) to a sample of `group` (-1: of any added
+        group; the box never carves) -- sph_geometry_carve.  Survivors are renumbered as by remove_in_box.  Returns the number removed."""
+        if clearance is None:
+            clearance = np.float32(2.0 * self.cfg.particle_radius)
+        removed = ctypes.c_int32(0)
+        self._check(self._optional("sph_geometry_carve")(self._h, int(group), float(np.float32(clearance)), ctypes.byref(removed)))
+        self._refresh_count()
+        return int(removed.value)
+
+    def wall_neighbor_counts(self):
+        """(n,) int32 in original particle order: the wall samples, box and geometry, in each particle's list as the last list build left it
+        (sph_geometry_wall_counts)"""
+        out = np.zeros(self._n_fluid, dtype=np.int32)
+        self._check(self._optional("sph_geometry_wall_counts")(self._h, out.ctypes.data, out.size))
+        return out
 
     def diagnostics(self):
         """The run diagnostics of the fluid as it stands, between steps (sph_diagnostics): a dict keyed by the names of DIAG_SLOTS, f64.  The

@@ -139,11 +139,12 @@ int scalar_rate_fetch(SphHandle *h, float *out, size_t n)
     return SPH_OK;
 }
 
-// sph_remove_in_box, beside k_remove_compact and with its arguments (the roles of before the flip): the survivors' values under their new ids.
+// sph_remove_in_box / sph_geometry_carve, beside k_remove_compact and with its arguments (the roles of before the flip): the survivors' values under their new ids.
 // Through the rate array, which is scratch between steps
-int scalar_compact(SphHandle *h, int n, int survivors, const RemoveBox &box, const float4 *P, const int *id, const int *scan_id)
+template <class Pred>
+int scalar_compact(SphHandle *h, int n, int survivors, const Pred &gone, const float4 *P, const int *id, const int *scan_id)
 {
-    hipLaunchKernelGGL(k_scalar_compact, grid_for(n), dim3(kBlock), 0, h->stream, n, box, P, id, scan_id, (const float *)h->sc_T, h->sc_rate);
+    hipLaunchKernelGGL((k_scalar_compact<Pred>), grid_for(n), dim3(kBlock), 0, h->stream, n, gone, P, id, scan_id, (const float *)h->sc_T, h->sc_rate);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemcpyAsync(h->sc_T, h->sc_rate, sizeof(float) * (size_t)survivors, hipMemcpyDeviceToDevice, h->stream));
     return SPH_OK;

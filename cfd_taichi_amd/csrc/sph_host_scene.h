@@ -229,6 +229,60 @@ void loop_params(const SphHandle *h, DevScalars *ds)
     ds->p_max_div = h->p.max_iteration_density_divergence;
 }
 
+// The wall tables of a wall set: static cell list, volumes, cell-sorted copy.  `pos`: 3 * max(Nb, 1) floats in original order.  Used at creation
+// (build_scene) and by every edit of the wall set (sph_host_geometry.h): the one copy of this arithmetic.
+// order[e] = original index of the sample in sorted slot e
+int wall_tables(SphHandle *h, const std::vector<float> &pos, int Nb, std::vector<float> &vol, std::vector<float4> &sorted, std::vector<int> &wcell_start,
+                std::vector<int> &order)
+{
+    const Consts &c = h->c;
+    vol.assign((size_t)(Nb > 0 ? Nb : 1), 0.f);
+    // ---- static wall cell list (reset/update_boundary_grids :322-335), canonical order ----
+    std::vector<int> wcell(Nb > 0 ? Nb : 1), wc3(3 * (size_t)(Nb > 0 ? Nb : 1));
+    wcell_start.assign((size_t)c.C + 1, 0);
+    for (int i = 0; i < Nb; ++i) {
+        int cx = (int)floorf(pos[3 * (size_t)i] / c.hcell);
+        int cy = (int)floorf(pos[3 * (size_t)i + 1] / c.hcell);
+        int cz = (int)floorf(pos[3 * (size_t)i + 2] / c.hcell);
+        int id = cx + cy * c.sy + cz * c.sz;
+        if (id < 0 || id >= c.C) return fail(h, SPH_E_INVALID, "wall particle %d falls outside the grid", i);
+        wcell[i] = id; wc3[3 * (size_t)i] = cx; wc3[3 * (size_t)i + 1] = cy; wc3[3 * (size_t)i + 2] = cz;
+        wcell_start[(size_t)id + 1]++;
+    }
+    for (int k = 0; k < c.C; ++k) wcell_start[(size_t)k + 1] += wcell_start[k];
+    std::vector<int> fill(wcell_start.begin(), wcell_start.end() - 1);
+    order.assign(Nb > 0 ? Nb : 1, 0);
+    for (int i = 0; i < Nb; ++i) order[fill[wcell[i]]++] = i;
+    // ---- wall volumes, compute_all_boundary_volume :309-320 ----
+    for (int i = 0; i < Nb; ++i) {
+        float volume = 0.f;
+        const float pix = pos[3 * (size_t)i], piy = pos[3 * (size_t)i + 1], piz = pos[3 * (size_t)i + 2];
+        for (int dx = -1; dx <= 1; ++dx)
+            for (int dy = -1; dy <= 1; ++dy)
+                for (int dz = -1; dz <= 1; ++dz) {
+                    int x = wc3[3 * (size_t)i] + dx, y = wc3[3 * (size_t)i + 1] + dy, z = wc3[3 * (size_t)i + 2] + dz;
+                    if (x >= c.gx || y >= c.gy || z >= c.gz) continue;
+                    if (x < 0 || y < 0 || z < 0) continue;
+                    int cid = x + y * c.sy + z * c.sz;
+                    for (int e = wcell_start[cid]; e < wcell_start[(size_t)cid + 1]; ++e) {
+                        int j = order[e];
+                        if (j == i) continue;
+                        float ddx = pix - pos[3 * (size_t)j], ddy = piy - pos[3 * (size_t)j + 1], ddz = piz - pos[3 * (size_t)j + 2];
+                        float q = sqrtf((ddx * ddx + ddy * ddy) + ddz * ddz);
+                        if (q > c.h) continue;
+                        volume += host_cubic_w(q, c.h, c.kw);
+                    }
+                }
+        vol[i] = 1.0f / volume;                                 // :314
+    }
+    sorted.resize(Nb > 0 ? Nb : 1);
+    for (int e = 0; e < Nb; ++e) {
+        int j = order[e];
+        sorted[e] = make_float4(pos[3 * (size_t)j], pos[3 * (size_t)j + 1], pos[3 * (size_t)j + 2], vol[j]);
+    }
+    return SPH_OK;
+}
+
 int build_scene(SphHandle *h, HostScene &sc)
 {
     const SphConfig &cf = h->cfg;
@@ -468,48 +522,8 @@ int build_scene(SphHandle *h, HostScene &sc)
             sc.wall_pos[3 * (size_t)i] = x; sc.wall_pos[3 * (size_t)i + 1] = y; sc.wall_pos[3 * (size_t)i + 2] = z;
         }
     }
-    // ---- static wall cell list (reset/update_boundary_grids :322-335), canonical order ----
-    std::vector<int> wcell(Nb > 0 ? Nb : 1), wc3(3 * (size_t)(Nb > 0 ? Nb : 1));
-    sc.wcell_start.assign((size_t)c.C + 1, 0);
-    for (int i = 0; i < Nb; ++i) {
-        int cx = (int)floorf(sc.wall_pos[3 * (size_t)i] / c.hcell);
-        int cy = (int)floorf(sc.wall_pos[3 * (size_t)i + 1] / c.hcell);
-        int cz = (int)floorf(sc.wall_pos[3 * (size_t)i + 2] / c.hcell);
-        int id = cx + cy * c.sy + cz * c.sz;
-        if (id < 0 || id >= c.C) return fail(h, SPH_E_INVALID, "wall particle %d falls outside the grid", i);
-        wcell[i] = id; wc3[3 * (size_t)i] = cx; wc3[3 * (size_t)i + 1] = cy; wc3[3 * (size_t)i + 2] = cz;
-        sc.wcell_start[(size_t)id + 1]++;
-    }
-    for (int k = 0; k < c.C; ++k) sc.wcell_start[(size_t)k + 1] += sc.wcell_start[k];
-    std::vector<int> fill(sc.wcell_start.begin(), sc.wcell_start.end() - 1), order(Nb > 0 ? Nb : 1);
-    for (int i = 0; i < Nb; ++i) order[fill[wcell[i]]++] = i;
-    // ---- wall volumes, compute_all_boundary_volume :309-320 ----
-    for (int i = 0; i < Nb; ++i) {
-        float volume = 0.f;
-        const float pix = sc.wall_pos[3 * (size_t)i], piy = sc.wall_pos[3 * (size_t)i + 1], piz = sc.wall_pos[3 * (size_t)i + 2];
-        for (int dx = -1; dx <= 1; ++dx)
-            for (int dy = -1; dy <= 1; ++dy)
-                for (int dz = -1; dz <= 1; ++dz) {
-                    int x = wc3[3 * (size_t)i] + dx, y = wc3[3 * (size_t)i + 1] + dy, z = wc3[3 * (size_t)i + 2] + dz;
-                    if (x >= c.gx || y >= c.gy || z >= c.gz) continue;
-                    if (x < 0 || y < 0 || z < 0) continue;
-                    int cid = x + y * c.sy + z * c.sz;
-                    for (int e = sc.wcell_start[cid]; e < sc.wcell_start[(size_t)cid + 1]; ++e) {
-                        int j = order[e];
-                        if (j == i) continue;
-                        float ddx = pix - sc.wall_pos[3 * (size_t)j], ddy = piy - sc.wall_pos[3 * (size_t)j + 1], ddz = piz - sc.wall_pos[3 * (size_t)j + 2];
-                        float q = sqrtf((ddx * ddx + ddy * ddy) + ddz * ddz);
-                        if (q > c.h) continue;
-                        volume += host_cubic_w(q, c.h, c.kw);
-                    }
-                }
-        sc.wall_vol[i] = 1.0f / volume;                                 // :314
-    }
-    sc.wall_sorted.resize(Nb > 0 ? Nb : 1);
-    for (int e = 0; e < Nb; ++e) {
-        int j = order[e];
-        sc.wall_sorted[e] = make_float4(sc.wall_pos[3 * (size_t)j], sc.wall_pos[3 * (size_t)j + 1], sc.wall_pos[3 * (size_t)j + 2], sc.wall_vol[j]);
-    }
+    std::vector<int> order;
+    if (int rc = wall_tables(h, sc.wall_pos, Nb, sc.wall_vol, sc.wall_sorted, sc.wcell_start, order)) return rc;
     return SPH_OK;
 }
 

@@ -2705,6 +2705,14 @@ __global__ __launch_bounds__(kBlock) void k_unsort_count(int n, const int *__res
     if (s >= n) return;
     dst[id[s]] = (float)(cnt[s] & 0xffff);
 }
+// the wall half of the packed list counts (sph_geometry_wall_counts): kb as the sweeps decode it; a ghost that walks no list has none
+__global__ __launch_bounds__(kBlock) void k_unsort_wall_count(int n, const int *__restrict__ cnt, const int *__restrict__ id, int *__restrict__ dst)
+{
+    int s = blockIdx.x * kBlock + threadIdx.x;
+    if (s >= n) return;
+    const int cw = cnt[s];
+    dst[id[s]] = cw < 0 ? 0 : ((cw >> 16) & 0x7fff);
+}
 __global__ __launch_bounds__(kBlock) void k_unsort_scalar_int(int n, const int *__restrict__ src, const int *__restrict__ id, float *__restrict__ dst)
 {
     int s = blockIdx.x * kBlock + threadIdx.x;
@@ -2751,13 +2759,21 @@ __global__ __launch_bounds__(kBlock) void k_append(int n_old, int m, int first_i
     if (delta_pos) delta_pos[s] = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-// Remove: the sink's box test, lo[k] <= x[k] < hi[k] on all three axes in f32.  One function for the flags and the compaction, on the same
-// stored positions: both see the same verdict.
-struct RemoveBox { float lo[3], hi[3]; };
-__device__ __forceinline__ int in_remove_box(const RemoveBox &b, float4 p)
-{
-    return (b.lo[0] <= p.x && p.x < b.hi[0] && b.lo[1] <= p.y && p.y < b.hi[1] && b.lo[2] <= p.z && p.z < b.hi[2]) ? 1 : 0;
-}
+// Remove: the verdict on the particle in slot s at position p is a predicate struct's operator().  One function for the flags and the compaction,
+// on the same stored positions: both see the same verdict.
+// The sink's box test, lo[k] <= x[k] < hi[k] on all three axes in f32
+struct RemoveBox {
+    float lo[3], hi[3];
+    __device__ __forceinline__ int operator()(int, float4 p) const
+    {
+        return (lo[0] <= p.x && p.x < hi[0] && lo[1] <= p.y && p.y < hi[1] && lo[2] <= p.z && p.z < hi[2]) ? 1 : 0;
+    }
+};
+// A verdict reached once per slot and kept (k_carve_flag; the scans zero the flag arrays as they read them, this one stays)
+struct RemoveMarked {
+    const int *marked;
+    __device__ __forceinline__ int operator()(int s, float4) const { return marked[s]; }
+};
 // flag per slot, and the same flag scattered to the particle's id (every id below n is held by exactly one slot: all n entries are written).
 // The two exclusive scans over them (k_scan_tiles / k_scan_sums / k_scan_add, which zero the flags as they read them) give the removed
 // particles in front of a slot -- the compaction -- and the removed ids below an id -- the renumbering.
@@ -2766,16 +2782,49 @@ __global__ __launch_bounds__(kBlock) void k_remove_flag(int n, RemoveBox box, co
 {
     const int s = blockIdx.x * kBlock + threadIdx.x;
     if (s >= n) return;
-    const int f = in_remove_box(box, P[s]);
+    const int f = box(s, P[s]);
     flag_slot[s] = f;
     flag_id[id[s]] = f;
 }
-__global__ void k_remove_count(int n, RemoveBox box, const float4 *__restrict__ P, const int *__restrict__ scan_slot, int *__restrict__ total)
+// Carving (sph_geometry_carve): the flags of k_remove_flag for "nearer than `clearance` to a wall sample of group `group`
+// (< 0: of any added group; the box, group 0, never carves)", and the verdict kept in marked[].  One thread per particle walks the wall samples of
+// its 27 cells with the bounds tests of k_build_nl's cell_entry; clearance <= h <= the cell edge, so no sample further away can be near enough.
+// The test is f32: norm3 of the difference, (dx dx + dy dy) + dz dz under sqrt_rn.  A verdict depends on the particle's own position and the
+// static wall tables alone: nothing here is order-dependent.  wgroup[e]: the group of the sample in sorted slot e
+__global__ __launch_bounds__(kBlock) void k_carve_flag(Consts c, int group, float clearance, const float4 *__restrict__ P, const int *__restrict__ id,
+                                                       const float4 *__restrict__ WP, const int *__restrict__ wcell_start, const int *__restrict__ wgroup,
+                                                       int *__restrict__ flag_slot, int *__restrict__ flag_id, int *__restrict__ marked)
 {
-    *total = scan_slot[n - 1] + in_remove_box(box, P[n - 1]);
+    const int s = blockIdx.x * kBlock + threadIdx.x;
+    if (s >= c.n) return;
+    const float4 p = P[s];
+    const int cx = (int)floorf(p.x / c.hcell), cy = (int)floorf(p.y / c.hcell), cz = (int)floorf(p.z / c.hcell);
+    int f = 0;
+    for (int dx = -1; dx <= 1 && !f; ++dx)
+        for (int dy = -1; dy <= 1 && !f; ++dy)
+            for (int dz = -1; dz <= 1 && !f; ++dz) {
+                const int x = cx + dx, y = cy + dy, z = cz + dz;
+                if (x >= c.gx || y >= c.gy || z >= c.gz || x < 0 || y < 0 || z < 0) continue;
+                const int cid = x + y * c.sy + z * c.sz;
+                for (int e = wcell_start[cid]; e < wcell_start[cid + 1]; ++e) {
+                    const int g = wgroup[e];
+                    if (g == 0 || (group >= 0 && g != group)) continue;
+                    const float4 w = WP[e];
+                    if (norm3(p.x - w.x, p.y - w.y, p.z - w.z) < clearance) { f = 1; break; }
+                }
+            }
+    flag_slot[s] = f;
+    flag_id[id[s]] = f;
+    marked[s] = f;
+}
+template <class Pred>
+__global__ void k_remove_count(int n, Pred gone, const float4 *__restrict__ P, const int *__restrict__ scan_slot, int *__restrict__ total)
+{
+    *total = scan_slot[n - 1] + gone(n - 1, P[n - 1]);
 }
 // stable compaction into the other buffer of each pair: survivors keep the device order and the order of their ids
-__global__ __launch_bounds__(kBlock) void k_remove_compact(int n, RemoveBox box, const int *__restrict__ scan_slot, const int *__restrict__ scan_id,
+template <class Pred>
+__global__ __launch_bounds__(kBlock) void k_remove_compact(int n, Pred gone, const int *__restrict__ scan_slot, const int *__restrict__ scan_id,
                                                            const float4 *__restrict__ Pin, const float4 *__restrict__ Vin, const float *__restrict__ warm_in,
                                                            const int *__restrict__ id_in, float4 *__restrict__ Pout, float4 *__restrict__ Vout,
                                                            float *__restrict__ warm_out, int *__restrict__ id_out)
@@ -2783,7 +2832,7 @@ __global__ __launch_bounds__(kBlock) void k_remove_compact(int n, RemoveBox box,
     const int s = blockIdx.x * kBlock + threadIdx.x;
     if (s >= n) return;
     const float4 p = Pin[s];
-    if (in_remove_box(box, p)) return;
+    if (gone(s, p)) return;
     const int d = s - scan_slot[s], o = id_in[s];
     Pout[d] = p;
     Vout[d] = Vin[s];

@@ -288,6 +288,16 @@ struct SphHandle {
     double sc_D = 0.0;
     float sc_beta = 0.f, sc_ref = 0.f, sc_inflow = 0.f;
 
+    // static geometry: the wall set is the box samples (group 0, the first Nb0) and behind them every live group in order of
+    // addition.  geo_mem: memory of the feature's own, taken at the first sph_geometry_add and grown, never shrunk: WP of the edited set (h->WP
+    // points into it from then on), wgroup (the group of every sample in sorted order) and the carve verdicts
+    struct GeoGroup { int id, count; };
+    std::vector<GeoGroup> geo_groups;
+    int geo_next_id = 1;
+    char *geo_mem = nullptr;
+    size_t geo_cap = 0;                    // wall samples geo_mem has room for (+ 64 of padding, as the arena's WP)
+    int *geo_wgroup = nullptr, *geo_marked = nullptr;
+
     // profiling
     bool profiling = false;
     struct Ev { hipEvent_t a, b; int kid; };
@@ -359,6 +369,8 @@ inline dim3 grid_for(int n) { return dim3((unsigned)std::max(1, (n + kBlock - 1)
 #include "sph_host_dfsph.h"
 #include "sph_host_pressure.h"
 #include "sph_host_derived.h"
+#include "sph_host_flow.h"
+#include "sph_host_geometry.h"
 
 }  // namespace
 
@@ -563,37 +575,7 @@ int sph_rigid_get_load(SphHandle *h, double force[3], double torque[3])
     return SPH_OK;
 }
 
-// ---- inlets and sinks ---------------------------------------------------------------------------------------
-static int flow_refused(SphHandle *h, const char *call)
-{
-    if (h->slab) return fail(h, SPH_E_STATE, "%s is not available on a slab handle", call);
-    if (h->rigid) return fail(h, SPH_E_STATE, "%s is not available on a handle with a rigid body", call);
-    return SPH_OK;
-}
-
-// The live count is now `n`: what the host caches from it, and what the steps so far left behind that a fresh handle of these particles would
-// not have (forget_step_history, as sph_slab_set_state) -- but for what travels with the handle: delta_time, the clock, gravity and forcing, the
-// carried scalars of the particles that stay, pcisph's delta, last_iters and pb_final.
-static int fluid_count_changed(SphHandle *h, int n)
-{
-    hipStream_t s = h->stream;
-    h->N = n; h->n_owned = n;
-    h->c.n = n;
-    h->nblocks = (n + kBlock - 1) / kBlock;
-    if (int rc = forget_step_history(h)) return rc;
-    const void *tile_flags[] = {h->pci_zero_press};
-    if (int rc = dzero(h, tile_flags, 1)) return rc;
-    if (h->verlet) {              // the lists of the last build know neither the new particles nor the new slots: the next step builds them
-        h->ds_host->moved = 1;
-        HIP_TRY(h, hipMemcpyAsync(&h->ds->moved, &h->ds_host->moved, sizeof(int), hipMemcpyHostToDevice, s));
-    }
-    HIP_TRY(h, hipStreamSynchronize(s));
-    drop_wcsph_graphs(h);                                            // (they carry the old count and grids as launch arguments)
-    // The run diagnostics (section 6i) need nothing here: their launches take the live count of the moment as an argument and keep no state about
-    // particles -- a recording goes on, its next row counts the new n
-    return SPH_OK;
-}
-
+// ---- inlets and sinks (flow_refused, fluid_count_changed and remove_where: sph_host_flow.h) ----------------------
 int sph_add_particles(SphHandle *h, const float *pos, const float *vel, size_t n, int32_t *first_id)
 {
     if (!h) return SPH_E_INVALID;
@@ -642,52 +624,22 @@ int sph_remove_in_box(SphHandle *h, const float lo[3], const float hi[3], int32_
     if (!h) return SPH_E_INVALID;
     if (int rc = flow_refused(h, "sph_remove_in_box")) return rc;
     if (!lo || !hi) return fail(h, SPH_E_INVALID, "sph_remove_in_box: null argument");
-    HIP_TRY(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    HIP_TRY(h, hipStreamSynchronize(s));
-    const int n = h->c.n, stride = h->c.stride, nt = (n + kScanTile - 1) / kScanTile;
     RemoveBox box;
     for (int a = 0; a < 3; ++a) { box.lo[a] = lo[a]; box.hi[a] = hi[a]; }
-    // scratch between steps: the sort's three int arrays (rewritten by the next sort before anything reads them) and the staging buffer as
-    // three int arrays of `stride` entries -- the scan over ids, the two scans' tile sums, the count in the last word
-    int *flag_slot = h->cell_of, *flag_id = h->rank, *scan_slot = h->slot_src;
-    int *scan_id = (int *)h->staging, *sums_slot = scan_id + stride, *sums_id = scan_id + 2 * (size_t)stride, *total = scan_id + 3 * (size_t)stride - 1;
-    const dim3 g = grid_for(n), b(kBlock);
-    const float4 *P = h->P[h->pcur];
-    const int *id = h->id[h->icur];
-    {
-        ProfScope ps(h, K_TRANSFER);
-        hipLaunchKernelGGL(k_remove_flag, g, b, 0, s, n, box, P, id, flag_slot, flag_id);
-        hipLaunchKernelGGL(k_scan_tiles, dim3(nt), b, 0, s, flag_slot, scan_slot, sums_slot, n, (const int *)nullptr);
-        hipLaunchKernelGGL(k_scan_sums, dim3(1), b, 0, s, sums_slot, nt, (const int *)nullptr);
-        hipLaunchKernelGGL(k_scan_add, g, b, 0, s, scan_slot, (const int *)sums_slot, n, (const int *)nullptr, 0);
-        hipLaunchKernelGGL(k_scan_tiles, dim3(nt), b, 0, s, flag_id, scan_id, sums_id, n, (const int *)nullptr);
-        hipLaunchKernelGGL(k_scan_sums, dim3(1), b, 0, s, sums_id, nt, (const int *)nullptr);
-        hipLaunchKernelGGL(k_scan_add, g, b, 0, s, scan_id, (const int *)sums_id, n, (const int *)nullptr, 0);
-        hipLaunchKernelGGL(k_remove_count, dim3(1), dim3(1), 0, s, n, box, P, (const int *)scan_slot, total);
-    }
-    HIP_TRY(h, hipGetLastError());
-    int r = -1;
-    HIP_TRY(h, hipMemcpyAsync(&r, total, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    if (r < 0 || r > n) return fail(h, SPH_E_STATE, "internal: sph_remove_in_box counted %d of %d particles", r, n);
-    if (r == n) return fail(h, SPH_E_INVALID, "sph_remove_in_box: the box holds all %d particles (an empty handle is not supported)", n);
-    if (removed) *removed = r;
-    if (r == 0) return SPH_OK;
-    const bool carry = carries_scalar(h);
-    {
-        ProfScope ps(h, K_TRANSFER);
-        hipLaunchKernelGGL(k_remove_compact, g, b, 0, s, n, box, (const int *)scan_slot, (const int *)scan_id, P, (const float4 *)h->V[h->vcur],
-                           carry ? (const float *)h->warm[h->wcur] : (const float *)nullptr, id, h->P[1 - h->pcur], h->V[1 - h->vcur], h->warm[1 - h->wcur],
-                           h->id[1 - h->icur]);
-    }
-    HIP_TRY(h, hipGetLastError());
-    if (scalar_on(h))
-        if (int rc = scalar_compact(h, n, n - r, box, P, id, scan_id)) return rc;
-    h->pcur ^= 1; h->vcur ^= 1; h->icur ^= 1;
-    if (carry) h->wcur ^= 1;
-    return fluid_count_changed(h, n - r);
+    return remove_where(h, "sph_remove_in_box", "the box holds", box, [&](int n, const float4 *P, const int *id, int *flag_slot, int *flag_id) {
+        hipLaunchKernelGGL(k_remove_flag, grid_for(n), dim3(kBlock), 0, h->stream, n, box, P, id, flag_slot, flag_id);
+    }, removed);
 }
+
+// ---- static geometry -------------------------------------------------------------------------------------------
+int sph_geometry_add(SphHandle *h, const float *xyz, size_t n, int32_t *group) { return h ? geometry_add(h, xyz, n, group) : SPH_E_INVALID; }
+int sph_geometry_remove(SphHandle *h, int32_t group) { return h ? geometry_remove(h, group) : SPH_E_INVALID; }
+int sph_geometry_info(SphHandle *h, int32_t *groups, int32_t *first, int32_t *count, size_t cap, size_t *n_groups)
+{
+    return h ? geometry_info(h, groups, first, count, cap, n_groups) : SPH_E_INVALID;
+}
+int sph_geometry_carve(SphHandle *h, int32_t group, float clearance, int32_t *removed) { return h ? geometry_carve(h, group, clearance, removed) : SPH_E_INVALID; }
+int sph_geometry_wall_counts(SphHandle *h, int32_t *counts, size_t n) { return h ? geometry_wall_counts(h, counts, n) : SPH_E_INVALID; }
 
 void sph_destroy(SphHandle *h)
 {
@@ -703,6 +655,7 @@ void sph_destroy(SphHandle *h)
     if (h->diag_ctl) (void)hipFree(h->diag_ctl);
     if (h->drv_vr) (void)hipFree(h->drv_vr);
     if (h->sc_XT) (void)hipFree(h->sc_XT);
+    if (h->geo_mem) (void)hipFree(h->geo_mem);
     if (h->rred_host) (void)hipHostFree(h->rred_host);
     if (h->own_dev_comm) { (void)hipFree(h->dsend[0]); (void)hipFree(h->dsend[1]); (void)hipFree(h->drecv[0]); (void)hipFree(h->drecv[1]); }
     if (h->own_red) (void)hipFree(h->red_dev);

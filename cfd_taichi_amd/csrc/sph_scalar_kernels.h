@@ -95,12 +95,13 @@ __global__ __launch_bounds__(kBlock) void k_scalar_unsort(int n, const float *__
 
 // sph_remove_in_box: the survivors' values under their new ids, by the renumbering k_remove_compact applies (scan_id: removed ids below an id).
 // Into a second array: a survivor's new id is another particle's old one.
-__global__ __launch_bounds__(kBlock) void k_scalar_compact(int n, RemoveBox box, const float4 *__restrict__ P, const int *__restrict__ id,
+template <class Pred>
+__global__ __launch_bounds__(kBlock) void k_scalar_compact(int n, Pred gone, const float4 *__restrict__ P, const int *__restrict__ id,
                                                            const int *__restrict__ scan_id, const float *__restrict__ T, float *__restrict__ out)
 {
     const int s = blockIdx.x * kBlock + threadIdx.x;
     if (s >= n) return;
-    if (in_remove_box(box, P[s])) return;
+    if (gone(s, P[s])) return;
     const int o = id[s];
     out[o - scan_id[o]] = T[o];
 }

@@ -16,7 +16,11 @@ the end of every N-th solver step and drained once per frame; one CSV line per r
 the run.  Single GPU.
 --ply-fields vorticity,divergence,normal,cover: derived per-particle fields (Simulation.derived) as further `property float` columns of every PLY
 frame, after alpha: vort_x vort_y vort_z div normal_x normal_y normal_z cover -- only the named ones, always in that order.  `scalar`: the carried
-scalar (scene.scalar; Simulation.scalar()) as one more column `scalar` behind them.  Single GPU."""
+scalar (scene.scalar; Simulation.scalar()) as one more column `scalar` behind them.  Single GPU.
+`scene.geometry` (cfd_taichi_amd/geometry.py): static obstacles as wall samples, applied when the handle is made.
+--remove-geometry NAME@FRAME (repeatable) takes the entry NAME out of the wall set when frame_cnt reaches FRAME: pulls a gate; sharded runs too.
+--geometry-ply DIR writes the wall samples, box and geometry, with an int `group` column as `geometry_%06d.ply` at frame 0 and after every edit.
+Single GPU.  Without the flags a run does what it did."""
 import argparse
 import importlib
 import os
@@ -65,6 +69,48 @@ def write_ply_ascii(path, pos, rgba, extra=()):
             f.write("property float %s\n" % name)
         f.write("end_header\n")
         np.savetxt(f, np.hstack([pos, rgba] + [np.asarray(v, dtype=np.float32).reshape(n, -1) for _, v in extra]), fmt="%.6f")
+
+
+def parse_remove_geometry(items, known=None):
+    """--remove-geometry NAME@FRAME (repeatable) as {frame: [names]} in the order given; known: the names the config defines.  A malformed item,
+    a frame below 0, an unknown or repeated name ends the run"""
+    out, seen = {}, set()
+    for item in items or []:
+        name, sep, frame = item.rpartition("@")
+        if not sep or not name or not frame.isdigit():
+            raise SystemExit("--remove-geometry: expected NAME@FRAME with FRAME >= 0, got '%s'" % item)
+        if known is not None and name not in known:
+            raise SystemExit("--remove-geometry: the config defines no geometry '%s' (scene.geometry has %s)" % (name, ", ".join(sorted(known)) or "none"))
+        if name in seen:
+            raise SystemExit("--remove-geometry: '%s' is removed twice" % name)
+        seen.add(name)
+        out.setdefault(int(frame), []).append(name)
+    return out
+
+
+def geometry_names(config):
+    """the names of `scene.geometry` as the block gives them (nothing is sampled: the handle does that once, when it is made)"""
+    block = config["scene"].get("geometry")
+    return [e.get("name") for e in block if isinstance(e, dict)] if isinstance(block, list) else []
+
+
+def unreached_removals(removals, frames):
+    """the NAME@FRAME items whose frame the run never reached (`frames`: frames run; a removal at frame f happens before frame f + 1 starts)"""
+    return ["%s@%d" % (name, f) for f in sorted(removals) if f >= frames for name in removals[f]]
+
+
+def write_geometry_ply(path, sim, wall_species=1, f_wall_pos=32):
+    """The wall samples as they stand, box and geometry, as ASCII PLY: float x y z and an int `group` column (0: the box).  wall_species /
+    f_wall_pos: SPH_SPECIES_WALL / SPH_F_WALL_POS"""
+    pos = np.asarray(sim.download(f_wall_pos, wall_species), dtype=np.float32)
+    group = np.zeros(len(pos), dtype=np.int64)
+    for g, first, count in sim.geometry():
+        group[first:first + count] = g
+    with open(path, "w") as f:
+        f.write("ply\nformat ascii 1.0\ncomment created by cfd_taichi_amd\nelement vertex %d\n" % len(pos))
+        f.write("property float x\nproperty float y\nproperty float z\nproperty int group\nend_header\n")
+        for p, g in zip(pos, group):
+            f.write("%.6f %.6f %.6f %d\n" % (p[0], p[1], p[2], g))
 
 
 def write_diag_csv(path, chunks):
@@ -124,6 +170,8 @@ def main_sharded(args, config):
     frame_cnt, ply_cnt, t = 0, 0, 0.0
     start_time = time.time()
     while True:
+        for name in getattr(args, "removals", {}).get(frame_cnt, []):           # every rank alike, between the same steps
+            sim.remove_geometry(sim.geometry_groups[name])
         sim.step(iter_cnt)
         frame_cnt += 1
         t += iter_cnt * sim.sim.scalar(nat.S_DELTA_TIME)
@@ -135,6 +183,8 @@ def main_sharded(args, config):
         if (args.steps and frame_cnt >= args.steps) or t > args.until or frame_cnt > 100000:
             break
     if rank == 0:
+        for item in unreached_removals(getattr(args, "removals", {}), frame_cnt):
+            print("--remove-geometry %s: the run ended after %d frames, the geometry stayed" % (item, frame_cnt))
         print("slabs: %d, frames: %d, simulated time: %.6f s, PLY frames: %d" % (world, frame_cnt, t, ply_cnt))
         print("Simulation time: {}".format(time.time() - start_time))
     sim.close()
@@ -159,6 +209,9 @@ def main(argv=None):
     ap.add_argument("--diag-csv", default=None, metavar="PATH", help="record the fluid's run diagnostics on the device and write them as CSV at the end of the run")
     ap.add_argument("--diag-every", type=int, default=1, metavar="N", help="with --diag-csv: one row every N solver steps (default 1)")
     ap.add_argument("--ply-fields", default=None, metavar="NAMES", help="derived fields as extra PLY columns: a comma-separated choice of vorticity, divergence, normal, cover, scalar")
+    ap.add_argument("--remove-geometry", action="append", default=None, metavar="NAME@FRAME",
+                    help="take the scene.geometry entry NAME out of the wall set when frame_cnt reaches FRAME (repeatable): pulls a gate")
+    ap.add_argument("--geometry-ply", default=None, metavar="DIR", help="write the wall samples with a group column at frame 0 and after every edit")
     args = ap.parse_args(argv)
     args.ply_fields = parse_ply_fields(args.ply_fields)
     if args.diag_csv and args.diag_every < 1:
@@ -167,9 +220,13 @@ def main(argv=None):
     config = utils.read_config(args.config)
     if args.solver:
         config["solver"]["name"] = args.solver
+    removals = parse_remove_geometry(args.remove_geometry, known=geometry_names(config))
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         if args.diag_csv:
             raise SystemExit("--diag-csv is not sharded: run this config on one GPU")
+        if args.geometry_ply:
+            raise SystemExit("--geometry-ply is not sharded: run this config on one GPU")
+        args.removals = removals
         return main_sharded(args, config)
     scene_config, solver_config = config["scene"], config["solver"]
     print("Simulation Start!")
@@ -194,9 +251,20 @@ def main(argv=None):
     diag_chunks, diag_dropped = [], 0
     if args.diag_csv:
         ps._sim.record_diagnostics(args.diag_every)
+    geo_cnt = 0
+    if args.geometry_ply:
+        os.makedirs(args.geometry_ply, exist_ok=True)
+        write_geometry_ply(os.path.join(args.geometry_ply, "geometry_%06d.ply" % frame_cnt), ps._sim)
+        geo_cnt += 1
     while True:
         if frame_cnt > 100000:                                                   # :98
             break
+        for gname in removals.get(frame_cnt, []):
+            ps._sim.remove_geometry(ps._sim.geometry_groups[gname])
+            print("frame %d: geometry '%s' removed" % (frame_cnt, gname))
+            if args.geometry_ply:
+                write_geometry_ply(os.path.join(args.geometry_ply, "geometry_%06d.ply" % frame_cnt), ps._sim)
+                geo_cnt += 1
         if rs and args.release_rigid_at is not None and frame_cnt == args.release_rigid_at:   # :100-106
             ps.active_rigid[None] = 1
             ps.reset_grid()
@@ -229,9 +297,11 @@ def main(argv=None):
         ps._sim.record_diagnostics(0)
         write_diag_csv(args.diag_csv, diag_chunks)
         print("diagnostics: %d rows in %s%s" % (sum(len(c) for c in diag_chunks), args.diag_csv, ", %d lost to the ring" % diag_dropped if diag_dropped else ""))
+    for item in unreached_removals(removals, frame_cnt):
+        print("--remove-geometry %s: the run ended after %d frames, the geometry stayed" % (item, frame_cnt))
     print("frames: %d, simulated time: %.6f s, PLY frames: %d" % (frame_cnt, t, ply_cnt))
     print("Simulation time: {}".format(time.time() - start_time))               # :211
-    LAST.update(ps=ps, solver=solver, rigid=rs, emitters=emitters, sinks=sinks, frame_dt=frame_dt)      # frame_dt: delta_time after every frame
+    LAST.update(ps=ps, solver=solver, rigid=rs, emitters=emitters, sinks=sinks, frame_dt=frame_dt, geometry_frames=geo_cnt)      # frame_dt: delta_time after every frame
     return frame_cnt, t, ply_cnt
 
 

@@ -276,6 +276,18 @@ class SlabSimulation:
     def set_forcing(self, amp, omega=None, phase=None):
         self.sim.set_forcing(amp, omega, phase)
 
+    # static geometry: the walls are replicated, so these too are plain local calls that every rank makes alike between
+    # the same steps; the config's `scene.geometry` has been applied by the Simulation (geometry_groups: name -> group).  Carving is refused here
+    def add_geometry(self, points):
+        return self.sim.add_geometry(points)
+
+    def remove_geometry(self, group):
+        self.sim.remove_geometry(group)
+
+    @property
+    def geometry_groups(self):
+        return self.sim.geometry_groups
+
     def rigid_load(self):
         """(force, torque) over the WHOLE body as the last rigid_step summed them: the same bits on every rank"""
         return self.sim.rigid_load()

@@ -308,6 +308,35 @@ int sph_set_forcing(SphHandle *h, const double amp[3], const double omega[3], co
  * removed: nothing changes, not even what is valid.  SPH_E_INVALID: a box that would remove every particle (an empty handle is not supported). */
 int sph_add_particles(SphHandle *h, const float *pos, const float *vel, size_t n, int32_t *first_id);
 int sph_remove_in_box(SphHandle *h, const float lo[3], const float hi[3], int32_t *removed);
+
+/* Static geometry: obstacles, ramps, gates and meshes as wall samples, between steps, on a handle with Akinci walls
+ * (boundary_handle 1) of any solver, either arithmetic, one GPU or slabs.  The wall set of a handle is the box samples (group 0, indices
+ * 0 .. Nb0-1, as sph_create made them) and behind them every live group in order of addition; group ids are 1, 2, ... and never reused;
+ * removing a group closes the gap (later groups move down and keep their ids).  After every edit the volumes of ALL samples, the box's included,
+ * are recomputed by the rule of ParticleSystem.py:309-320 over the whole set, coincident samples each adding W(0); SPH_F_WALL_POS, SPH_F_WALL_VOL
+ * and SphSizes.n_wall report the current set.  The samples stay at rest; no sweep is added or changed: every solver walks them as it walks the box.
+ * An edit touches nothing else on the handle (fluid state, clock, delta_time, dfsph's warm start, pcisph's delta, gravity, the carried scalar, a
+ * recording, the body) and invalidates what the last list build derived from the old set: a handle edited at step k continues exactly as a handle
+ * that had that wall set all along and was given the same fluid state at step k.  On slab handles the walls are replicated: every rank makes the
+ * same calls between the same steps (plain local calls, as sph_rigid_set_mode).  The rigid body's own wall test (sph_rigid_step) sees the box only.
+ * Refusals come before any launch or upload and leave the handle unchanged.  SPH_E_INVALID: xyz == NULL, n == 0, a coordinate that is not finite, a
+ * sample whose cell lies outside the grid, an unknown group, a clearance outside (0, h], an edit after which some sample has no other sample within h
+ * (its volume would be infinite), a handle with clamp walls, 2^28 wall samples or more, a carve that would remove every particle.
+ * SPH_E_STATE: sph_geometry_carve on a slab handle or a handle with a body (as sph_remove_in_box).
+ * A step whose wall lists overflow returns SPH_E_OVERFLOW as ever (SphConfig.max_wall_neighbors). */
+/* appends n samples (x, y, z in world coordinates) as a new group; *group = its id (may be NULL) */
+int sph_geometry_add(SphHandle *h, const float *xyz, size_t n, int32_t *group);
+int sph_geometry_remove(SphHandle *h, int32_t group);
+/* the live groups in order with their ranges [first, first + count) in the wall arrays: up to cap entries are written, *n_groups = how many there are */
+int sph_geometry_info(SphHandle *h, int32_t *groups, int32_t *first, int32_t *count, size_t cap, size_t *n_groups);
+/* removes every fluid particle i with |x_i - x_b| < clearance for some sample b of `group` (-1: of any added group; the box never carves), f32,
+ * (dx dx + dy dy) + dz dz under a correctly rounded root; 0 < clearance <= h.  Survivors are compacted exactly as by sph_remove_in_box (id order
+ * kept, the carried scalar with them); *removed = how many went (may be NULL); nobody near: nothing changes, not even what is valid */
+int sph_geometry_carve(SphHandle *h, int32_t group, float clearance, int32_t *removed);
+/* how many wall samples, box and geometry, each particle's list holds as the last list build (a step, sph_build_neighbors) left it, in original
+ * particle order; n must be the live particle count.  Who touches a wall.  On a handle whose lists carry a skin (relaxed wcsph) the entries within
+ * h + skin.  SPH_E_INVALID: counts == NULL, n != n_fluid; SPH_E_STATE: a slab handle. */
+int sph_geometry_wall_counts(SphHandle *h, int32_t *counts, size_t n);
 /* Run diagnostics of the FLUID of a single-GPU handle, summed on the device: every solver, exact or relaxed, with or without
  * a body (the body's own momentum and energy are not in the row).  One row is 32 doubles.  m = SPH_S_PARTICLE_M, x / v = SPH_F_POS / SPH_F_VEL.
  * Arithmetic: every f32 operand is widened to f64 first, products and the three-term sums inside a term are f64, the terms are summed in f64 in a
