@@ -54,6 +54,7 @@ EXPORTS = [
     "sph_add_particles", "sph_remove_in_box", "sph_diagnostics", "sph_diag_record", "sph_diag_read", "sph_derived",
     "sph_scalar_enable", "sph_scalar_disable", "sph_scalar_upload", "sph_scalar_download", "sph_scalar_set_inflow", "sph_scalar_rate",
     "sph_geometry_add", "sph_geometry_remove", "sph_geometry_info", "sph_geometry_carve", "sph_geometry_wall_counts",
+    "sph_wall_load_select", "sph_wall_load_get", "sph_wall_load_impulse", "sph_wall_load_forces",
 ]
 # the 32 slots of an SphDiagnostics row (include/sph_mi355x.h), in order: the members' names, _x / _y / _z for the vectors
 DIAG_SLOTS = ("time", "dt", "step", "n", "mass", "momentum_x", "momentum_y", "momentum_z",
@@ -198,7 +199,8 @@ OPTIONAL_EXPORTS = ["sph_rigid_set_active", "sph_rigid_init_data", "sph_selftest
                     "sph_rigid_set_mode", "sph_rigid_set_motion", "sph_rigid_get_load", "sph_set_gravity", "sph_set_forcing",
                     "sph_add_particles", "sph_remove_in_box", "sph_diagnostics", "sph_diag_record", "sph_diag_read", "sph_derived",
                     "sph_scalar_enable", "sph_scalar_disable", "sph_scalar_upload", "sph_scalar_download", "sph_scalar_set_inflow", "sph_scalar_rate",
-                    "sph_geometry_add", "sph_geometry_remove", "sph_geometry_info", "sph_geometry_carve", "sph_geometry_wall_counts"]
+                    "sph_geometry_add", "sph_geometry_remove", "sph_geometry_info", "sph_geometry_carve", "sph_geometry_wall_counts",
+                    "sph_wall_load_select", "sph_wall_load_get", "sph_wall_load_impulse", "sph_wall_load_forces"]
 
 
 def _bind_core(lib):
@@ -272,6 +274,11 @@ def _bind_core(lib):
         lib.sph_geometry_carve.argtypes = [vp, ctypes.c_int32, ctypes.c_float, ctypes.POINTER(ctypes.c_int32)]
     if hasattr(lib, "sph_geometry_wall_counts"):
         lib.sph_geometry_wall_counts.argtypes = [vp, vp, ctypes.c_size_t]
+    if hasattr(lib, "sph_wall_load_select"):
+        lib.sph_wall_load_select.argtypes = [vp, vp, ctypes.c_size_t]
+        lib.sph_wall_load_get.argtypes = [vp, ctypes.c_int32, vp, vp, vp]
+        lib.sph_wall_load_impulse.argtypes = [vp, ctypes.c_int32, vp, vp, vp, ctypes.POINTER(ctypes.c_double), ci]
+        lib.sph_wall_load_forces.argtypes = [vp, ctypes.c_int32, vp, ctypes.c_size_t]
     return lib
 
 
@@ -567,6 +574,7 @@ class Simulation:
         self.max_neighbors, self.max_wall_neighbors = sizes.max_neighbors, sizes.max_wall_neighbors
         self.last_stats = SphStepStats()
         self.geometry_groups = {}
+        self.measured_groups = []            # the wall groups whose load is measured (measure_loads), by id
         if config is not None:
             apply_gravity_calls(self, config)
             for name, value in adaptive_dt_calls(config, "dfsph" if cfg.solver == SOLVER_DFSPH else "other"):
@@ -578,6 +586,11 @@ class Simulation:
                     self.set_scalar(scalar_init_values(self.download(F_POS), sc[1], default=sc[0]["ref"]))
             from . import geometry as _geometry
             self.geometry_groups = _geometry.apply_config(self, config)      # `scene.geometry`: name -> group
+            try:                              # `scene.loads`: the wall groups whose load is measured, on a handle that can measure (apply_loads)
+                _geometry.apply_loads(self, config)
+            except Exception:
+                self.close()                  # the handle exists by now: a config that names an unknown group must not leak it
+                raise
 
     def _check(self, rc):
         if rc != SPH_OK:
@@ -656,6 +669,7 @@ class Simulation:
         """Take a group out of the wall set between steps (sph_geometry_remove): later groups move down in the wall arrays and keep their ids"""
         self._check(self._optional("sph_geometry_remove")(self._h, int(group)))
         self._refresh_walls()
+        self.measured_groups = [g for g in self.measured_groups if g != int(group)]      # a removed group leaves the selection
 
     def geometry(self):
         """the live groups in order of addition: a list of (group, first, count), [first, first + count) being the group's rows of the wall downloads"""
@@ -682,6 +696,53 @@ class Simulation:
         (sph_geometry_wall_counts)"""
         out = np.zeros(self._n_fluid, dtype=np.int32)
         self._check(self._optional("sph_geometry_wall_counts")(self._h, out.ctypes.data, out.size))
+        return out
+
+    # ---- loads on walls and geometry (DESIGN.md section 6m) ----
+    def _load_group(self, group, all_allowed=False):
+        """a group as the load calls take it: "box" (0), a name of geometry_groups, or an id; None / "all": every measured group (-1)"""
+        if all_allowed and (group is None or group == "all"):
+            return -1
+        if group == "box":
+            return 0
+        if isinstance(group, str):
+            if group not in self.geometry_groups:
+                raise ValueError("no geometry named '%s' (the handle knows %s)" % (group, ", ".join(["box"] + sorted(self.geometry_groups))))
+            return int(self.geometry_groups[group])
+        return int(group)
+
+    def measure_loads(self, groups):
+        """Measure the load of the fluid on the wall groups named (sph_wall_load_select): "box", names of geometry_groups, or ids; an empty list
+        switches measuring off.  Impulses and seconds start at zero.  Invisible to the fluid; a step costs a few small launches more."""
+        ids = np.ascontiguousarray([self._load_group(g) for g in groups], dtype=np.int32)
+        self._check(self._optional("sph_wall_load_select")(self._h, ids.ctypes.data if len(ids) else None, len(ids)))
+        self.measured_groups = [int(g) for g in ids]
+
+    def wall_load(self, group=None, about=None):
+        """(force, torque) of the last step on a measured group (None: on all of them), f64 (3,) each; the torque about `about` (None: the origin)
+        -- sph_wall_load_get"""
+        c = None if about is None else np.ascontiguousarray(about, dtype=np.float64).reshape(3)
+        f, t = np.zeros(3), np.zeros(3)
+        self._check(self._optional("sph_wall_load_get")(self._h, self._load_group(group, True), None if c is None else c.ctypes.data, f.ctypes.data, t.ctypes.data))
+        return f, t
+
+    def wall_impulse(self, group=None, about=None, reset=True):
+        """(impulse, angular impulse, seconds) a measured group has collected since it was selected or last reset: the sums of dt F, dt torque and
+        dt over the steps; the mean force of the window is impulse / seconds (sph_wall_load_impulse).  reset: start the next window"""
+        c = None if about is None else np.ascontiguousarray(about, dtype=np.float64).reshape(3)
+        j, l, sec = np.zeros(3), np.zeros(3), ctypes.c_double(0.0)
+        self._check(self._optional("sph_wall_load_impulse")(self._h, self._load_group(group, True), None if c is None else c.ctypes.data, j.ctypes.data, l.ctypes.data,
+                                                            ctypes.byref(sec), 1 if reset else 0))
+        return j, l, float(sec.value)
+
+    def wall_forces(self, group):
+        """(count, 3) f32: the last step's force on every sample of a measured group, in the group's own sample order -- for "box" the first rows
+        of download(F_WALL_POS, SPECIES_WALL), for a geometry group the points it was added with (sph_wall_load_forces)"""
+        gid = self._load_group(group)
+        count = {g: c for g, _, c in self.geometry()}
+        n = self.n_wall - sum(count.values()) if gid == 0 else count.get(gid, 0)
+        out = np.zeros((n, 3), dtype=np.float32)
+        self._check(self._optional("sph_wall_load_forces")(self._h, gid, out.ctypes.data, out.size))
         return out
 
     def diagnostics(self):

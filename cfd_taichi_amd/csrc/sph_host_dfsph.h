@@ -142,6 +142,7 @@ int stage_sort_and_lists(SphHandle *h)
         ProfScope ps(h, K_RIGID);
         hipLaunchKernelGGL(k_build_rnl, grid_for(h->Nr), b, 0, s, c, h->Nr, h->RPs, h->P[h->pcur], h->cell_start, h->rnl, h->rcnt, h->ds);
     }
+    if (wl_on(h)) wl_build_lists(h);      // ... and the measured wall samples' (section 6m)
     if (h->wall_grad && h->c.kr_split && h->c.boundary_handle && use_relaxed(h)) {     // the wall sums of this step's positions
         ProfScope ps(h, K_BUILD_NL);
         hipLaunchKernelGGL(k_rx_wall_grad, g, b, 0, s, c, h->P[h->pcur], h->WP, h->nlb, h->cnt, h->wall_grad, h->wall_gsq);
@@ -301,6 +302,7 @@ int step_begin(SphHandle *h)
     h->simulate_cnt += 1;
     h->comm_stat[6] += 1;
     step_head(h);
+    if (wl_on(h)) wl_step_head(h);                           // measured wall samples: the step's totals start at zero (section 6m)
     if (h->step_adaptive) launch_step_dt(h);
     if (is_pressure_solver(h) && (rc = require_async_slab(h))) return rc;
     if ((rc = stage_sort_and_lists(h))) return rc;
@@ -313,6 +315,7 @@ int step_begin(SphHandle *h)
 int step_end(SphHandle *h)
 {
     if (scalar_on(h)) scalar_step_end(h);                    // the carried scalar: the kick and T's Euler step (section 6k)
+    if (wl_on(h)) wl_step_end(h);                            // loads on the measured wall groups: the per-group sums, impulses and seconds (section 6m)
     if (h->diag_every)
         if (int rc = diag_step_end(h)) return rc;
     HIP_TRY(h, hipGetLastError());
@@ -347,6 +350,7 @@ int step_wcsph_once(SphHandle *h)
     }
     const Consts &c = h->c;
     if (rigid_coupled(h)) launch_rigid_force_p<RF_WCSPH>(h, h->P[h->pcur], nullptr, GATE_NONE);   // wcsph_solver.py:127, positions of this step
+    if (wl_on(h)) wl_force_p<RF_WCSPH>(h, h->P[h->pcur], nullptr, GATE_NONE);                     // the same on the measured wall samples
     {
         ProfScope ps(h, K_W_FORCE);                          // wcsph_solver.py:36-38 + kinematic_phase :40-63
         const bool quad = sweep_mode(h) == SWEEP_QUAD;
@@ -808,6 +812,7 @@ int step_dfsph_device_loops(SphHandle *h, SphStepStats *st)
                 // D7 of iteration d runs iff iteration d runs (the decision of evaluation d - 1; gate_hist starts open) and carries decision d
                 launch_correct<CORR_DENS>(h, K_D_DENS_CORRECT, h->rho_adv, h->VA[0], GATE_HIST0 + ((d - 1) & 1), SpecSave{nullptr, nullptr}, FIN_DENS, d);   // :229
                 if (rigid_coupled(h)) launch_rigid_force(h, GATE_HIST0 + ((d - 1) & 1));
+                if (wl_on(h)) wl_force_dfsph(h, GATE_HIST0 + ((d - 1) & 1));
                 continue;
             }
             if (spec) {
@@ -816,6 +821,7 @@ int step_dfsph_device_loops(SphHandle *h, SphStepStats *st)
                 // D7 of iteration d runs iff iteration d runs: the decision of evaluation d - 1 (gate_hist starts open)
                 launch_correct<CORR_DENS>(h, K_D_DENS_CORRECT, h->rho_adv, h->VA[0], GATE_HIST0 + ((d - 1) & 1));   // :229
                 if (rigid_coupled(h)) launch_rigid_force(h, GATE_HIST0 + ((d - 1) & 1));
+                if (wl_on(h)) wl_force_dfsph(h, GATE_HIST0 + ((d - 1) & 1));
                 if ((rc = launch_finalize_decide(h, FIN_DENS, d))) return rc;
                 HIP_TRY(h, hipStreamWaitEvent(s, h->ev_dec, 0));
                 continue;
@@ -824,6 +830,7 @@ int step_dfsph_device_loops(SphHandle *h, SphStepStats *st)
             order_working_tiles_first();
             launch_correct<CORR_DENS>(h, K_D_DENS_CORRECT, h->rho_adv, h->VA[0], GATE_DENS_D7);   // :229
             if (rigid_coupled(h)) launch_rigid_force(h, GATE_DENS_D7);
+            if (wl_on(h)) wl_force_dfsph(h, GATE_DENS_D7);
             if ((rc = ghosts_v(h->VA[0]))) return rc;
         }
         if ((rc = read_scalars_fast(h))) return rc;
@@ -901,6 +908,7 @@ int step_dfsph_host_loops(SphHandle *h, SphStepStats *st)
         if ((rc = reduce_mean_host(h, 1000.0f, &avg))) return rc;
         launch_correct<CORR_DENS>(h, K_D_DENS_CORRECT, h->rho_adv, h->VA[0], GATE_NONE);
         if (rigid_coupled(h)) launch_rigid_force(h, GATE_NONE);
+        if (wl_on(h)) wl_force_dfsph(h, GATE_NONE);
         if ((rc = ghosts_v(h->VA[0]))) return rc;
         rho_avg = (double)avg;
         it += 1;

@@ -22,6 +22,7 @@ static int fluid_count_changed(SphHandle *h, int n)
     if (int rc = forget_step_history(h)) return rc;
     const void *tile_flags[] = {h->pci_zero_press};
     if (int rc = dzero(h, tile_flags, 1)) return rc;
+    if (int rc = wl_count_changed(h)) return rc;                      // the measured wall samples' lists (section 6m): stale entries must stay valid indices
     if (h->verlet) {              // the lists of the last build know neither the new particles nor the new slots: the next step builds them
         h->ds_host->moved = 1;
         HIP_TRY(h, hipMemcpyAsync(&h->ds->moved, &h->ds_host->moved, sizeof(int), hipMemcpyHostToDevice, s));

@@ -40,6 +40,15 @@ static int geometry_commit(SphHandle *h, const char *call, std::vector<float> &p
     HIP_TRY(h, hipStreamSynchronize(s));
     if (h->xstream) HIP_TRY(h, hipStreamSynchronize(h->xstream));
     if (h->rstream) HIP_TRY(h, hipStreamSynchronize(h->rstream));
+    // Loads on walls (section 6m): the selection is kept by id -- a removed group leaves it, the impulses of the others go on.  The measured set of
+    // the new wall set is built here, into memory of its own, before anything of the handle changes (a refusal leaves the selection as it was) ...
+    WlBuild wl_next;
+    std::vector<int> wl_ids;
+    for (const auto &sel : h->wl_groups)
+        for (size_t k = 0; k <= groups.size(); ++k)
+            if (k == groups.size() ? sel.id == 0 : groups[k].id == sel.id) { wl_ids.push_back(sel.id); break; }
+    if (!wl_ids.empty())
+        if (int rc = wl_prepare(h, call, wl_ids, sorted, order, Nb, groups, true, &wl_next)) return rc;
     // The device copy never shrinks: the sweeps fetch a group of list entries past a row's end and rely on stale entries being valid indices
     // (walk_list, sph_kernels.h).  Memory of the feature's own; the arena's WP is simply no longer pointed to
     // Every edit uploads into a fresh allocation through local pointers; the handle's fields change only behind the final wait, so a HIP error on
@@ -77,6 +86,10 @@ static int geometry_commit(SphHandle *h, const char *call, std::vector<float> &p
     pos.resize(3 * (size_t)Nb);
     h->wall_pos_host.swap(pos);
     h->wall_vol_host.swap(vol);
+    h->wall_order_host.swap(order);
+    // ... and becomes the handle's here; the last step's forces read zero until a step has run.  Nobody left of the selection: measuring is off
+    if (!wl_ids.empty()) wl_adopt(h, &wl_next);
+    else h->wl_groups.clear();
     // what the last list build derived from the old wall set: the lists and counts, the density, the derived fields; the captured wcsph step pairs
     // hold WP, wcell_start and the kernels' arguments of their capture.  The density loop's working-tiles-first order is a launch order only; it
     // starts afresh as on a new handle.  Fluid state, clock, dt, warm start, pcisph's delta, gravity, scalar, recording and the body are not touched

@@ -200,6 +200,9 @@ int step_pcisph_once(SphHandle *h, SphStepStats *st)
         return slab_refresh_w_and_pressure_finalize(h, PB[(k + 1) & 1], PFIN_PCI_LOOP);
     });
     if (rc) return rc;
+    // measured wall samples (section 6m): once, behind the loop -- press_iter as the last executed k_pci_press read it, PB[dens_it & 1].  (The body's
+    // rule above deposits in every iteration from a pressure that accumulates: several times the force the fluid receives)
+    if (wl_on(h)) wl_force_p<RF_PCISPH>(h, h->P[h->pcur], PB[h->pb_final], GATE_NONE);
     {
         ProfScope ps(h, K_P_INTEGRATE);
         hipLaunchKernelGGL(k_pci_integrate, g, b, 0, s, c, dt, h->P[h->pcur], h->V[h->vcur], EF, PF, h->P[1 - h->pcur], h->V[1 - h->vcur]);
@@ -256,6 +259,7 @@ int step_iisph_once(SphHandle *h, SphStepStats *st)
     if (rc) return rc;
     st->n_div = h->ds_host->res_diverged;                   // 1: the loop left on "Iteration trend to divergence" (:97-99)
     if (rg) launch_rigid_force_p<RF_IISPH>(h, h->P[h->pcur], PB[h->pb_final], GATE_NONE);   // compute_all_press_force :172-179
+    if (wl_on(h)) wl_force_p<RF_IISPH>(h, h->P[h->pcur], PB[h->pb_final], GATE_NONE);       // the same on the measured wall samples (section 6m)
     {
         ProfScope ps(h, K_I_INTEGRATE);
         hipLaunchKernelGGL(k_ii_integrate, g, b, 0, s, c, dt, h->P[h->pcur], VA, DII, DIJ, PB[h->pb_final], h->P[1 - h->pcur], h->V[1 - h->vcur],

@@ -522,8 +522,7 @@ int build_scene(SphHandle *h, HostScene &sc)
             sc.wall_pos[3 * (size_t)i] = x; sc.wall_pos[3 * (size_t)i + 1] = y; sc.wall_pos[3 * (size_t)i + 2] = z;
         }
     }
-    std::vector<int> order;
-    if (int rc = wall_tables(h, sc.wall_pos, Nb, sc.wall_vol, sc.wall_sorted, sc.wcell_start, order)) return rc;
+    if (int rc = wall_tables(h, sc.wall_pos, Nb, sc.wall_vol, sc.wall_sorted, sc.wcell_start, h->wall_order_host)) return rc;
     return SPH_OK;
 }
 

@@ -28,6 +28,7 @@
 #include "sph_diag_kernels.h"
 #include "sph_derived_kernels.h"
 #include "sph_scalar_kernels.h"
+#include "sph_wall_load_kernels.h"
 #include "sph_selftest_walk.h"
 
 using namespace sph;
@@ -38,14 +39,14 @@ enum KernelId {
     K_HASH = 0, K_SCAN, K_SCATTER, K_ORDER_GATHER, K_BUILD_NL, K_W_DENSITY, K_W_FORCE, K_D_DENSITY_ALPHA,
     K_D_WARM, K_D_DIV_RESIDUAL, K_D_DIV_CORRECT, K_D_EXT, K_D_DENS_RESIDUAL, K_D_DENS_CORRECT, K_D_INTEGRATE,
     K_FINALIZE, K_TRANSFER, K_SLAB, K_RIGID, K_P_EXT, K_P_PREDICT_RHO, K_P_PRESS, K_P_INTEGRATE, K_I_ADVECT, K_I_RHO_ADV, K_I_DIJ,
-    K_I_UPDATE_P, K_I_INTEGRATE, K_B_LAMBDA, K_B_DELTA, K_B_XSPH, K_ACCEL, K_DERIVED, K_SCALAR, K_COUNT
+    K_I_UPDATE_P, K_I_INTEGRATE, K_B_LAMBDA, K_B_DELTA, K_B_XSPH, K_ACCEL, K_DERIVED, K_SCALAR, K_WALL_LOAD, K_COUNT
 };
 const char *kKernelNames[K_COUNT] = {
     "hash_count", "scan", "scatter", "order_gather", "build_nl", "wcsph_density", "wcsph_force", "dfsph_density_alpha",
     "dfsph_warm_start", "dfsph_div_residual", "dfsph_div_correct", "dfsph_ext_force", "dfsph_dens_residual",
     "dfsph_dens_correct", "dfsph_integrate", "finalize", "transfer", "slab_exchange", "rigid",
     "pcisph_ext_force", "pcisph_predict_rho", "pcisph_press_force", "pcisph_integrate", "iisph_advect", "iisph_rho_adv", "iisph_d_ij",
-    "iisph_update_p", "iisph_integrate", "pbf_lambda", "pbf_delta_pos", "pbf_xsph", "accel_eval", "derived", "scalar"};
+    "iisph_update_p", "iisph_integrate", "pbf_lambda", "pbf_delta_pos", "pbf_xsph", "accel_eval", "derived", "scalar", "wall_load"};
 
 thread_local std::string g_create_error;
 thread_local bool g_creating_with_rigid = false;     // sph_create_rigid builds the fluid handle first: no Verlet lists there (the body moves through the grid)
@@ -171,6 +172,7 @@ struct SphHandle {
     float *staging = nullptr;    // 3*max(N,Nb) floats, device
     // host copies of the wall particles in original order (for download)
     std::vector<float> wall_pos_host, wall_vol_host;
+    std::vector<int> wall_order_host;      // ... and wall_tables' order: the row of the wall set in sorted slot e
 
     // multi-GPU x-slab state (slab_count > 1)
     bool slab = false;
@@ -298,6 +300,22 @@ struct SphHandle {
     size_t geo_cap = 0;                    // wall samples geo_mem has room for (+ 64 of padding, as the arena's WP)
     int *geo_wgroup = nullptr, *geo_marked = nullptr;
 
+    // loads on walls and geometry.  wl_groups: the selection in the caller's order (first: the group's first row of the
+    // wall set); empty: measuring is off and no step launches anything of the feature.  wl: the measured set, memory of the feature's own, taken
+    // by sph_wall_load_select and rebuilt by every edit of the wall set while a selection stands (sph_host_wall_load.h)
+    struct WlGroup { int id, first, count; };
+    std::vector<WlGroup> wl_groups;
+    struct WlMem {
+        char *mem = nullptr;
+        int nm = 0;                          // samples of the measured set
+        size_t nl_bytes = 0;
+        float4 *MP = nullptr;                // [nm + 64] (x, y, z, V_b) in the wall set's sorted order
+        uint32_t *nl = nullptr;              // [(nm + 64) kpitch] the samples' fluid neighbours (k_build_rnl), cnt their number
+        int *cnt = nullptr, *ident = nullptr /* 0 .. nm - 1: the forces stay in sorted order */, *slot = nullptr, *local = nullptr, *perm = nullptr, *seg = nullptr;
+        float *force = nullptr, *out = nullptr;      // [3 nm] the step's per-sample totals; one group's in its own order (sph_wall_load_forces)
+        double *part = nullptr, *load = nullptr, *acc = nullptr;      // the reduction's partial rows, its result per group, what a group accumulates
+    } wl;
+
     // profiling
     bool profiling = false;
     struct Ev { hipEvent_t a, b; int kid; };
@@ -365,6 +383,7 @@ inline dim3 grid_for(int n) { return dim3((unsigned)std::max(1, (n + kBlock - 1)
 #include "sph_host_diag.h"
 #include "sph_host_transport.h"
 #include "sph_host_rigid.h"
+#include "sph_host_wall_load.h"
 #include "sph_host_scalar.h"
 #include "sph_host_dfsph.h"
 #include "sph_host_pressure.h"
@@ -641,6 +660,18 @@ int sph_geometry_info(SphHandle *h, int32_t *groups, int32_t *first, int32_t *co
 int sph_geometry_carve(SphHandle *h, int32_t group, float clearance, int32_t *removed) { return h ? geometry_carve(h, group, clearance, removed) : SPH_E_INVALID; }
 int sph_geometry_wall_counts(SphHandle *h, int32_t *counts, size_t n) { return h ? geometry_wall_counts(h, counts, n) : SPH_E_INVALID; }
 
+// ---- loads on walls and geometry (sph_host_wall_load.h) ----------------------------------------------------------
+int sph_wall_load_select(SphHandle *h, const int32_t *groups, size_t n) { return h ? wall_load_select(h, groups, n) : SPH_E_INVALID; }
+int sph_wall_load_get(SphHandle *h, int32_t group, const double about[3], double force[3], double torque[3])
+{
+    return h ? wall_load_get(h, group, about, force, torque) : SPH_E_INVALID;
+}
+int sph_wall_load_impulse(SphHandle *h, int32_t group, const double about[3], double impulse[3], double angular[3], double *seconds, int reset)
+{
+    return h ? wall_load_impulse(h, group, about, impulse, angular, seconds, reset) : SPH_E_INVALID;
+}
+int sph_wall_load_forces(SphHandle *h, int32_t group, float *xyz, size_t n_floats) { return h ? wall_load_forces(h, group, xyz, n_floats) : SPH_E_INVALID; }
+
 void sph_destroy(SphHandle *h)
 {
     if (!h) return;
@@ -656,6 +687,7 @@ void sph_destroy(SphHandle *h)
     if (h->drv_vr) (void)hipFree(h->drv_vr);
     if (h->sc_XT) (void)hipFree(h->sc_XT);
     if (h->geo_mem) (void)hipFree(h->geo_mem);
+    if (h->wl.mem) (void)hipFree(h->wl.mem);
     if (h->rred_host) (void)hipHostFree(h->rred_host);
     if (h->own_dev_comm) { (void)hipFree(h->dsend[0]); (void)hipFree(h->dsend[1]); (void)hipFree(h->drecv[0]); (void)hipFree(h->drecv[1]); }
     if (h->own_red) (void)hipFree(h->red_dev);

@@ -129,6 +129,41 @@ def config_groups(config):
     return out
 
 
+def config_loads(config):
+    """`scene.loads` = ["box", "pillar_a", ...]: the wall groups whose load is measured, "box" or names of `scene.geometry`,
+    as a list in the order given.  Pure Python; anything but a list of such names, or a name twice, raises ValueError.  No key: an empty list."""
+    block = config["scene"].get("loads")
+    if block is None:
+        return []
+    if not isinstance(block, list) or not all(isinstance(n, str) for n in block):
+        raise ValueError("scene.loads must be a list of names, got %r" % (block,))
+    geo = config["scene"].get("geometry")
+    known = ["box"] + [e.get("name") for e in geo if isinstance(e, dict)] if isinstance(geo, list) else ["box"]
+    for n in block:
+        if n not in known:
+            raise ValueError("scene.loads: no wall group '%s' (scene.geometry has %s, and there is \"box\")" % (n, ", ".join(known[1:]) or "none"))
+        if block.count(n) > 1:
+            raise ValueError("scene.loads: '%s' is named twice" % n)
+    return list(block)
+
+
+def apply_loads(sim, config):
+    """The call `scene.loads` asks of a new handle (anything with measure_loads), after apply_config; no key or an empty list: no call.  A handle
+    that cannot measure -- the library answers SPH_E_STATE: a slab handle, a relaxed handle, pbf, a library without the entry points -- runs the
+    scene as it always did: the key is skipped with one printed line, and an explicit measure_loads is still refused.  Returns the names measured."""
+    names = config_loads(config)
+    if not names:
+        return []
+    try:
+        sim.measure_loads(names)
+    except RuntimeError as e:
+        if getattr(e, "code", None) != -5:              # SPH_E_STATE (include/sph_mi355x.h)
+            raise
+        print("scene.loads skipped, this handle measures no loads: %s" % e)
+        return []
+    return names
+
+
 def apply_config(sim, config):
     """Make the calls `scene.geometry` asks of a new handle (anything with add_geometry / carve): every group is added in order, then carved where
     its entry says so.  Returns {name: group}."""

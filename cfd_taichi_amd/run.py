@@ -20,7 +20,13 @@ scalar (scene.scalar; Simulation.scalar()) as one more column `scalar` behind th
 `scene.geometry` (cfd_taichi_amd/geometry.py): static obstacles as wall samples, applied when the handle is made.
 --remove-geometry NAME@FRAME (repeatable) takes the entry NAME out of the wall set when frame_cnt reaches FRAME: pulls a gate; sharded runs too.
 --geometry-ply DIR writes the wall samples, box and geometry, with an int `group` column as `geometry_%06d.ply` at frame 0 and after every edit.
-Single GPU.  Without the flags a run does what it did."""
+Single GPU.  While loads are measured the file carries three more float columns fx fy fz: the last step's force on every sample of a measured group,
+zero elsewhere.
+`scene.loads` (["box", "gate", ...]): the wall groups whose load is measured on the device while the steps run; skipped
+with one printed line where loads cannot be measured (sharded runs, --arith relaxed, pbf).
+--load-csv PATH: one line per frame and measured group -- frame, time, group, the seconds the frame covered, the mean force and the mean torque
+about the origin over the frame (impulse / seconds), and the last step's force -- written at the end of the run.  Single GPU.
+Without the flags a run does what it did."""
 import argparse
 import importlib
 import os
@@ -101,16 +107,55 @@ def unreached_removals(removals, frames):
 
 def write_geometry_ply(path, sim, wall_species=1, f_wall_pos=32):
     """The wall samples as they stand, box and geometry, as ASCII PLY: float x y z and an int `group` column (0: the box).  wall_species /
-    f_wall_pos: SPH_SPECIES_WALL / SPH_F_WALL_POS"""
+    f_wall_pos: SPH_SPECIES_WALL / SPH_F_WALL_POS.  While loads are measured (sim.measured_groups): float fx fy fz behind them, the last step's
+    force on every sample of a measured group, zero on the others"""
     pos = np.asarray(sim.download(f_wall_pos, wall_species), dtype=np.float32)
     group = np.zeros(len(pos), dtype=np.int64)
+    rows = {0: (0, len(pos))}
     for g, first, count in sim.geometry():
         group[first:first + count] = g
+        rows[g] = (first, count)
+        rows[0] = (0, rows[0][1] - count)
+    measured = list(getattr(sim, "measured_groups", []))
+    force = np.zeros((len(pos), 3), dtype=np.float32)
+    for g in measured:
+        force[rows[g][0]:rows[g][0] + rows[g][1]] = sim.wall_forces(g)
     with open(path, "w") as f:
         f.write("ply\nformat ascii 1.0\ncomment created by cfd_taichi_amd\nelement vertex %d\n" % len(pos))
-        f.write("property float x\nproperty float y\nproperty float z\nproperty int group\nend_header\n")
-        for p, g in zip(pos, group):
-            f.write("%.6f %.6f %.6f %d\n" % (p[0], p[1], p[2], g))
+        f.write("property float x\nproperty float y\nproperty float z\nproperty int group\n")
+        if measured:
+            f.write("property float fx\nproperty float fy\nproperty float fz\n")
+        f.write("end_header\n")
+        for k, (p, g) in enumerate(zip(pos, group)):
+            f.write("%.6f %.6f %.6f %d" % (p[0], p[1], p[2], g))
+            if measured:
+                f.write(" %.9g %.9g %.9g" % tuple(force[k]))
+            f.write("\n")
+
+
+LOAD_COLUMNS = ("frame", "time", "group", "seconds", "mean_fx", "mean_fy", "mean_fz", "mean_tx", "mean_ty", "mean_tz", "fx", "fy", "fz")
+
+
+def load_rows(sim, frame, t):
+    """One row of LOAD_COLUMNS per measured group of `sim` (anything with measured_groups, geometry_groups, wall_impulse, wall_load) for the frame
+    that just ended: the window since the last call is read and reset.  A window of no seconds gives NaN means."""
+    names = {0: "box"}
+    names.update({g: n for n, g in sim.geometry_groups.items()})
+    rows = []
+    for g in sim.measured_groups:
+        j, l, sec = sim.wall_impulse(g, reset=True)
+        f, _ = sim.wall_load(g)
+        mean = [float(v) / sec if sec > 0 else float("nan") for v in list(j) + list(l)]
+        rows.append((int(frame), float(t), names.get(g, str(g)), float(sec)) + tuple(mean) + tuple(float(v) for v in f))
+    return rows
+
+
+def write_load_csv(path, rows):
+    """the rows of load_rows under a header of LOAD_COLUMNS.  %.17g: every f64 comes back bit for bit"""
+    with open(path, "w") as f:
+        f.write(",".join(LOAD_COLUMNS) + "\n")
+        for r in rows:
+            f.write(",".join(v if isinstance(v, str) else ("%d" % v if isinstance(v, int) else "%.17g" % v) for v in r) + "\n")
 
 
 def write_diag_csv(path, chunks):
@@ -144,6 +189,7 @@ def main_sharded(args, config):
         raise SystemExit("rigid bodies are not sharded: run this config on one GPU")
     if config["scene"].get("emitters") or config["scene"].get("sinks") or config["fluid"].get("capacity"):
         raise SystemExit("emitters, sinks and fluid.capacity are not sharded: run this config on one GPU")
+    # (`scene.loads` is skipped on slab handles with a printed line -- geometry.apply_loads: loads are measured on one GPU)
     if config["scene"].get("scalar") is not None or PLY_SCALAR in args.ply_fields:
         raise SystemExit("the carried scalar (scene.scalar, --ply-fields scalar) is not sharded: run this config on one GPU")
     own_gpu = torch.cuda.device_count() >= int(os.environ.get("LOCAL_WORLD_SIZE", world))
@@ -212,6 +258,7 @@ def main(argv=None):
     ap.add_argument("--remove-geometry", action="append", default=None, metavar="NAME@FRAME",
                     help="take the scene.geometry entry NAME out of the wall set when frame_cnt reaches FRAME (repeatable): pulls a gate")
     ap.add_argument("--geometry-ply", default=None, metavar="DIR", help="write the wall samples with a group column at frame 0 and after every edit")
+    ap.add_argument("--load-csv", default=None, metavar="PATH", help="write the load on every measured wall group (scene.loads), frame by frame, as CSV at the end of the run")
     args = ap.parse_args(argv)
     args.ply_fields = parse_ply_fields(args.ply_fields)
     if args.diag_csv and args.diag_every < 1:
@@ -226,6 +273,8 @@ def main(argv=None):
             raise SystemExit("--diag-csv is not sharded: run this config on one GPU")
         if args.geometry_ply:
             raise SystemExit("--geometry-ply is not sharded: run this config on one GPU")
+        if args.load_csv:
+            raise SystemExit("--load-csv is not sharded: run this config on one GPU")
         args.removals = removals
         return main_sharded(args, config)
     scene_config, solver_config = config["scene"], config["solver"]
@@ -251,6 +300,9 @@ def main(argv=None):
     diag_chunks, diag_dropped = [], 0
     if args.diag_csv:
         ps._sim.record_diagnostics(args.diag_every)
+    load_table = []
+    if args.load_csv and not ps._sim.measured_groups:
+        raise SystemExit("--load-csv: the config measures no loads (scene.loads names the wall groups)")
     geo_cnt = 0
     if args.geometry_ply:
         os.makedirs(args.geometry_ply, exist_ok=True)
@@ -282,6 +334,8 @@ def main(argv=None):
             diag_dropped = drain_diag(ps._sim, diag_chunks, diag_dropped)
         frame_dt.append(solver.delta_time[None])
         t = solver.time[None] if adaptive else t + iter_cnt * frame_dt[-1]
+        if args.load_csv:
+            load_table += load_rows(ps._sim, frame_cnt, t)
         if ply_dir and (t / frame_time) > ply_cnt:                               # :189
             if len(np_rgba) != ps.particle_num:                                   # an emitter or a sink changed the count
                 np_rgba = ps.rgba.to_numpy()
@@ -297,6 +351,9 @@ def main(argv=None):
         ps._sim.record_diagnostics(0)
         write_diag_csv(args.diag_csv, diag_chunks)
         print("diagnostics: %d rows in %s%s" % (sum(len(c) for c in diag_chunks), args.diag_csv, ", %d lost to the ring" % diag_dropped if diag_dropped else ""))
+    if args.load_csv:
+        write_load_csv(args.load_csv, load_table)
+        print("loads: %d rows in %s" % (len(load_table), args.load_csv))
     for item in unreached_removals(removals, frame_cnt):
         print("--remove-geometry %s: the run ended after %d frames, the geometry stayed" % (item, frame_cnt))
     print("frames: %d, simulated time: %.6f s, PLY frames: %d" % (frame_cnt, t, ply_cnt))

@@ -210,8 +210,11 @@ SCENES.update({
 })
 
 
-def _with_geometry(cfg, entries):
+def _with_geometry(cfg, entries, loads=None):
+    """loads: `scene.loads`, the wall groups whose load is measured"""
     cfg["scene"]["geometry"] = [dict(e) for e in entries]
+    if loads is not None:
+        cfg["scene"]["loads"] = list(loads)
     return cfg
 
 
@@ -220,10 +223,10 @@ SCENES.update({
     # The 30 k dam break against three square pillars of 0.2 m standing across the tank 0.9 m from the column's face
     "dam_pillars_dfsph": lambda: _with_geometry(_scene("dfsph", 2.5e-4, [5.0, 3.0, 1.5], [1.0, 2.8, 1.3]),
                                                 [{"name": "pillar_%d" % k, "type": "box", "min": [2.0, 0.05, z], "max": [2.2, 1.5, z + 0.2]}
-                                                 for k, z in enumerate((0.2, 0.65, 1.1))]),
+                                                 for k, z in enumerate((0.2, 0.65, 1.1))], loads=["pillar_0", "pillar_1", "pillar_2"]),
     # The same column held behind a gate, a plate a spacing and a half from its face: `run.py --remove-geometry gate@FRAME` pulls it
     "dam_gate_wcsph": lambda: _with_geometry(_scene("wcsph", 2.5e-4, [5.0, 3.0, 1.5], [1.0, 2.8, 1.3]),
-                                             [{"name": "gate", "type": "plate", "origin": [1.125, 0.05, 0.05], "u": [0.0, 2.9, 0.0], "v": [0.0, 0.0, 1.4]}]),
+                                             [{"name": "gate", "type": "plate", "origin": [1.125, 0.05, 0.05], "u": [0.0, 2.9, 0.0], "v": [0.0, 0.0, 1.4]}], loads=["gate"]),
     # PBF's first obstacle: the column of pbf_small falls onto a box standing on the floor under it
     "pbf_step_pbf": lambda: _with_geometry(_scene("pbf", 2.5e-4, [1.5, 3.0, 1.5], [0.7, 1.5, 0.7], start_pos=(0.3, 0.5, 0.3)),
                                            [{"name": "step", "type": "box", "min": [0.5, 0.05, 0.5], "max": [0.9, 0.35, 0.9]}]),

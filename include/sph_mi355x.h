@@ -337,6 +337,33 @@ int sph_geometry_carve(SphHandle *h, int32_t group, float clearance, int32_t *re
  * particle order; n must be the live particle count.  Who touches a wall.  On a handle whose lists carry a skin (relaxed wcsph) the entries within
  * h + skin.  SPH_E_INVALID: counts == NULL, n != n_fluid; SPH_E_STATE: a slab handle. */
 int sph_geometry_wall_counts(SphHandle *h, int32_t *counts, size_t n);
+/* Loads on walls and geometry: how hard the fluid presses on selected wall groups, measured on the device while the steps
+ * run.  Group 0 is the box, ids >= 1 are the groups of sph_geometry_add.  During a step every sample b of a selected group collects f_b, the
+ * reaction to the pressure term the fluid feels from it, pair by pair the expression the reference deposits on a rigid body's samples with V_b in
+ * place of the sample's volume (no viscous term: the reference's walls exert none), summed in f32 over the fluid particles that list b, in the
+ * sample's own cell-walk order: wcsph once per step from the step's pressures; dfsph once per executed iteration of the density loop (the
+ * divergence loop's impulses are not counted, as the reference does not count them for a body); iisph and pcisph once, behind the pressure loop, from
+ * the final pressures -- the pressures behind the pressure force the integration applies, so that sum_b f_b = - m sum_i (the wall acceleration of
+ * particle i).  At the end of every step each selected group's force F = sum_b f_b and torque sum_b x_b x f_b are summed on the device in f64 in a
+ * fixed order (the arithmetic contract of SphDiagnostics: the same state gives the same bits) and added, times the dt the step used, to the group's
+ * impulse; no host wait is added to a step, a multi-step call or a replayed graph.  Selecting, reading and resetting are invisible to the fluid:
+ * the steps that follow are bit for bit those of a handle that never called them.
+ * An edit of the wall set keeps the selection by id: a removed group leaves it, the impulses of the others go on, and the last step's forces read
+ * zero until a step has run.  A sample with more than SphConfig.max_neighbors fluid neighbours makes the step return SPH_E_OVERFLOW.
+ * Refusals leave the handle unchanged.  SPH_E_STATE: a slab handle, a handle under the relaxed arithmetic, pbf, a read before any selection.
+ * SPH_E_INVALID: a handle with clamp walls, an unknown, unselected or twice-named group, more than 1024 groups, a null pointer, a wrong size. */
+/* measure the n groups named (any order; it is the order of "all selected" sums); n == 0 switches measuring off.  Impulses and seconds start at 0 */
+int sph_wall_load_select(SphHandle *h, const int32_t *groups, size_t n);
+/* the last step's force on `group` (-1: on all selected) and its torque sum_b (x_b - about) x f_b; about == NULL: the origin */
+int sph_wall_load_get(SphHandle *h, int32_t group, const double about[3], double force[3], double torque[3]);
+/* sum over the steps since the selection (or the last reset) of dt F and dt torque, and of dt: the mean force over the window is impulse / seconds.
+ * The samples do not move, so the angular impulse about `about` is taken from the one about the origin: L_0 - about x impulse.  reset != 0: the
+ * group's (-1: every selected group's) sums start at zero again behind this read.  group == -1 is one window of all selected groups: SPH_E_STATE
+ * if their seconds differ, as they do after a reset of a single group (read the groups one by one and reset each, or select again) */
+int sph_wall_load_impulse(SphHandle *h, int32_t group, const double about[3], double impulse[3], double angular[3], double *seconds, int reset);
+/* the last step's f_b of every sample of `group`, 3 floats each, in the group's own sample order (the box: the order of SPH_F_WALL_POS);
+ * n_floats must be 3 * the group's sample count */
+int sph_wall_load_forces(SphHandle *h, int32_t group, float *xyz, size_t n_floats);
 /* Run diagnostics of the FLUID of a single-GPU handle, summed on the device: every solver, exact or relaxed, with or without
  * a body (the body's own momentum and energy are not in the row).  One row is 32 doubles.  m = SPH_S_PARTICLE_M, x / v = SPH_F_POS / SPH_F_VEL.
  * Arithmetic: every f32 operand is widened to f64 first, products and the three-term sums inside a term are f64, the terms are summed in f64 in a

@@ -48,6 +48,7 @@ sim.close()
 sims = {}
 for name in ("dam_pillars_dfsph", "breaking_dam_30k_dfsph"):
     c = scenes.get(name)
+    c["scene"].pop("loads", None)             # the cost of the geometry alone (what measuring loads adds: tools/wall_load_cost.py)
     sims[name] = nat.Simulation(nat.config_from_dict(c), config=c)
     sims[name].step(warm)
     sims[name].synchronize()
