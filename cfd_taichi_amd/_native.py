@@ -31,6 +31,7 @@ S_VERLET_BUILDS = 31
 S_RIGID_ACTIVE = 32
 S_RIGID_ACC, S_RIGID_ALPHA, S_RIGID_MODE = 33, 36, 39
 S_TIME, S_ACCEL, S_GRAVITY_VEC = 40, 41, 44                  # the handle's clock (f64), its acceleration vector (+0, 1, 2) and the base vector g
+S_PAIR_BITS = 48                                              # diagnostics: 1 if the last dfsph step's solver-loop sweeps read the pair-bit cache
 S_FLUID_CAPACITY = 47                                         # fluid particles the handle can hold (SphConfig.fluid_capacity, or the lattice's count)
 RIGID_DYNAMIC, RIGID_SCRIPTED, RIGID_FIXED = 0, 1, 2          # sph_rigid_set_mode
 RIGID_MODES = {"dynamic": RIGID_DYNAMIC, "scripted": RIGID_SCRIPTED, "fixed": RIGID_FIXED}
@@ -47,7 +48,7 @@ EXPORTS = [
     "sph_abi_version", "sph_set_comm_sized", "sph_create", "sph_destroy", "sph_get_sizes", "sph_last_error", "sph_upload", "sph_download",
     "sph_step_wcsph", "sph_step_dfsph", "sph_step_pcisph", "sph_step_iisph", "sph_step_pbf", "sph_build_neighbors", "sph_compute_density", "sph_compute_alpha",
     "sph_get_scalar", "sph_set_scalar", "sph_synchronize", "sph_overrides", "sph_profile_enable", "sph_profile_reset", "sph_profile_kernel_count",
-    "sph_profile_kernel_name", "sph_profile_get", "sph_selftest_math", "sph_selftest_wave", "sph_selftest_stage", "sph_selftest_walk", "sph_tune_time",
+    "sph_profile_kernel_name", "sph_profile_get", "sph_selftest_math", "sph_selftest_wave", "sph_selftest_stage", "sph_selftest_walk", "sph_selftest_walk_bits", "sph_tune_time",
     "sph_set_comm", "sph_rccl_unique_id", "sph_rccl_attach", "sph_rccl_selftest", "sph_get_stream", "sph_plan_slabs", "sph_replan_slabs", "sph_slab_set_overlap", "sph_slab_info", "sph_comm_stats", "sph_download_local", "sph_download_ids",
     "sph_create_rigid", "sph_rigid_step", "sph_rigid_set_active", "sph_rigid_init_data", "sph_slab_set_state",
     "sph_rigid_set_mode", "sph_rigid_set_motion", "sph_rigid_get_load", "sph_set_gravity", "sph_set_forcing",
@@ -195,7 +196,7 @@ CORE_EXPORTS = [
 ]
 # entry points added without a change of SPH_ABI_VERSION (no struct grew, no signature changed): bound where the library has them, and a call on a
 # library without them raises SphError(SPH_E_STATE)
-OPTIONAL_EXPORTS = ["sph_rigid_set_active", "sph_rigid_init_data", "sph_selftest_stage", "sph_selftest_walk", "sph_slab_set_state",
+OPTIONAL_EXPORTS = ["sph_rigid_set_active", "sph_rigid_init_data", "sph_selftest_stage", "sph_selftest_walk", "sph_selftest_walk_bits", "sph_slab_set_state",
                     "sph_rigid_set_mode", "sph_rigid_set_motion", "sph_rigid_get_load", "sph_set_gravity", "sph_set_forcing",
                     "sph_add_particles", "sph_remove_in_box", "sph_diagnostics", "sph_diag_record", "sph_diag_read", "sph_derived",
                     "sph_scalar_enable", "sph_scalar_disable", "sph_scalar_upload", "sph_scalar_download", "sph_scalar_set_inflow", "sph_scalar_rate",
@@ -322,6 +323,8 @@ def load(build_if_missing=True):
     lib.sph_selftest_wave.argtypes = [ci, ci, vp, vp, ctypes.c_size_t]
     if hasattr(lib, "sph_selftest_walk"):
         lib.sph_selftest_walk.argtypes = [vp, ci, ci, ci, vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp]
+    if hasattr(lib, "sph_selftest_walk_bits"):
+        lib.sph_selftest_walk_bits.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp]
     if hasattr(lib, "sph_selftest_stage"):
         lib.sph_selftest_stage.argtypes = [vp, ci, ci, ci, ci, ci, vp, ci, vp, vp, vp, vp, ctypes.c_size_t, vp, ctypes.POINTER(ci)]
     lib.sph_tune_time.argtypes = [vp, ci, ctypes.c_uint, ci, ctypes.POINTER(ctypes.c_double)]
@@ -1084,12 +1087,14 @@ class Simulation:
 
 
 MATH_RECIP, MATH_DIV_SHARED, MATH_DIV_SHARED_TWO_STEP, MATH_DIV_SHARED_FLOORED = 7, 8, 9, 10    # sph_selftest_math ops (include/sph_mi355x.h)
+MATH_SQRT_BY_FIELD, MATH_SQRT_VERDICT = 11, 12
 
 
 def selftest_math(op, a, b, device=0):
     """out[i] = op(a[i], b[i]) in f32 on the device (see sph_selftest_math): 0 a/b, 1 sqrt(a), 2 W(a; h=b), 3-5 grad W, 6 sqrt_rn(a),
     MATH_RECIP recip_prepare(b).y, MATH_DIV_SHARED / MATH_DIV_SHARED_TWO_STEP the sweeps' quotient a/b with one / two residual corrections,
-    MATH_DIV_SHARED_FLOORED the first of them with the divisor raised to kDenFloor."""
+    MATH_DIV_SHARED_FLOORED the first of them with the divisor raised to kDenFloor, MATH_SQRT_BY_FIELD the root of a taken as the hardware root plus
+    the verdict of sqrt_rn's rounding step through a 2-bit field of the pair-bit cache, MATH_SQRT_VERDICT that verdict (-1, 0, +1)."""
     lib = load()
     a = np.ascontiguousarray(a, dtype=np.float32)
     b = np.ascontiguousarray(b, dtype=np.float32)
@@ -1142,6 +1147,26 @@ WALKS = {"list": 0, "quad": 1, "staged": 2, "list16": 3}
 WALK_SOURCES_MEM = {"p": 0, "a": 1, "ab": 2, "as": 3, "abc": 4}
 WALK_SOURCES_LDS = {"f4": 0, "f4_scaled": 1, "ps": 2, "ps_scaled": 3, "pv": 4, "pv_scaled": 5, "f4s": 6, "f4src_b": 7, "update_p": 8}
 WALK_ROWS, WALK_PITCH, WALK_PARTICLES = 24, 28, 256
+
+
+def selftest_walk_bits(lists, counts, words=None, verdicts=None, handle=None):
+    """walk_list16 with the pair-bit stream on one workgroup (see sph_selftest_walk_bits).  With `words` (256 x 3) the bodies read their fields from
+    them; with `verdicts` (256 x 24) body k records verdicts[i, k] and the words the walk stored are returned.  -> (seen 256 x 24, calls 256, words)"""
+    lib = load()
+    if not hasattr(lib, "sph_selftest_walk_bits"):
+        raise SphError(SPH_E_STATE, "this library has no sph_selftest_walk_bits")
+    write = verdicts is not None
+    lists = np.ascontiguousarray(lists, dtype=np.uint32).reshape(WALK_PARTICLES, WALK_ROWS)
+    counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(WALK_PARTICLES)
+    words = np.zeros((WALK_PARTICLES, WALK_ROWS // 8), dtype=np.uint32) if write else np.array(words, dtype=np.uint32).reshape(WALK_PARTICLES, WALK_ROWS // 8)
+    verdicts = np.ascontiguousarray(verdicts if write else np.zeros((WALK_PARTICLES, WALK_ROWS)), dtype=np.int32).reshape(WALK_PARTICLES, WALK_ROWS)
+    seen = np.zeros((WALK_PARTICLES, WALK_ROWS), dtype=np.uint32)
+    calls = np.zeros(WALK_PARTICLES, dtype=np.int32)
+    rc = lib.sph_selftest_walk_bits(handle, int(write), lists.ctypes.data, counts.ctypes.data, words.ctypes.data, verdicts.ctypes.data, seen.ctypes.data,
+                                    calls.ctypes.data)
+    if rc != SPH_OK:
+        raise SphError(rc, (lib.sph_last_error(None) or b"").decode())
+    return seen, calls, words
 
 
 def selftest_walk(walk, src, rigid, lists, counts, run, A, B, C, S, RP, handle=None):

@@ -342,6 +342,18 @@ __device__ __forceinline__ float norm3_scaled(float xs, float ys, float zs)
     r = 0.0f < rp ? yp : r;
     return r;
 }
+// The rounding step as a cached DECISION (the pair-bit cache of the staged DFSPH sweeps, sph_kernels.h).  Between a list build and the
+// integrator the positions are frozen, so for one list entry x is the same f32 in every sweep of the step, and so are the hardware root y
+// and the step's verdict r_bits - y_bits: -1, 0 or +1.  The first sweep behind a list build (D1) records the verdict; every later sweep takes
+// r = y_bits + verdict: two integer instructions in place of two integer adds, two FMAs and two compare-select pairs.  Same bits: the same
+// function of the same inputs, evaluated once.
+__device__ __forceinline__ float root_by_verdict(float xs, int verdict)                  // xs carries 2^64, the result 2^32
+{
+    return __int_as_float(__float_as_int(__builtin_amdgcn_sqrtf(xs)) + verdict);
+}
+__device__ __forceinline__ float norm3_scaled(float xs, float ys, float zs, int verdict) { return root_by_verdict((xs * xs + ys * ys) + zs * zs, verdict); }
+// ... and the unscaled twin (D5 stages plain positions): sqrt_rn's xs = x * 2^64 is the x of the scaled form (see above), hence its verdict
+__device__ __forceinline__ float norm3(float x, float y, float z, int verdict) { return root_by_verdict(((x * x + y * y) + z * z) * 0x1p64f, verdict) * 0x1p-32f; }
 __device__ __forceinline__ F3 grad_w_scaled(const Consts &c, float dxs, float dys, float dzs, float rs)
 {
     float q0 = rs * c.rh_s;                                        // div_by_h with both sides scaled

@@ -149,10 +149,24 @@ int stage_sort_and_lists(SphHandle *h)
     }
     HIP_TRY(h, hipGetLastError());
     h->nl_valid = true;
+    h->nl_gen += 1;                                          // (whatever D1 cached for the lists before is not about these: pair_bits_for)
     h->density_valid = false;
     h->derived_valid = false;
     h->lists_predate_flag = false;
     return SPH_OK;
+}
+
+// The pair-bit cache (walk_list16): where it applies -- the staged 16-bit walks of a one-GPU dfsph handle in the exact arithmetic without a binned
+// body (slab handles: D1's coverage of the ghost tiles' lists is not shown, they compute) -- and whether what it holds is about the lists a sweep is
+// about to walk: D1 stamps it with the list build it wrote it for, a sweep gets the pointer only while that is the current build.  Any caller that
+// runs a sweep without D1 behind the last build gets nullptr and the sweep computes the root's rounding step itself.
+inline bool pair_bits_scope(const SphHandle *h)
+{
+    return h->pair_bits && h->c.nl16 && sweep_mode(h) == SWEEP_STAGED && !h->slab && !rigid_binned(h) && !h->relaxed;
+}
+inline const uint32_t *pair_bits_for(const SphHandle *h)
+{
+    return (pair_bits_scope(h) && h->nl_valid && h->pair_bits_gen == h->nl_gen) ? h->pair_bits : nullptr;
 }
 
 int check_overflow(SphHandle *h)
@@ -227,12 +241,14 @@ int stage_density(SphHandle *h)
         if (!use_relaxed(h) || split)
         SPH_LAUNCH_RMX(k_density, true, rigid_coupled(h), sweep_mode(h), relaxed_unstaged(h), c.n, sweep_lds(h, StageF4<>::kBytes), s, c, h->P[h->pcur], h->V[h->vcur], h->WP, h->nl, h->nlb,
                       h->cnt, h->warm[h->wcur], h->ds, h->rho, dfsph_alpha(h), h->P[1 - h->pcur], h->V[h->vcur], rigid_view_or_none(h), h->id[h->icur],
-                      h->rho_orig, h->stage_src, h->stage_cnt, h->krho, wall_cache(h), split ? TilePhase{h->tile_order, h->nblocks, 1} : TilePhase{nullptr, 0, 0});
+                      h->rho_orig, h->stage_src, h->stage_cnt, h->krho, wall_cache(h), pair_bits_scope(h) ? h->pair_bits : (uint32_t *)nullptr,
+                      split ? TilePhase{h->tile_order, h->nblocks, 1} : TilePhase{nullptr, 0, 0});
+        if (pair_bits_scope(h)) h->pair_bits_gen = h->nl_gen;      // D1 walked every list of this build
     } else {
         ProfScope ps(h, K_W_DENSITY);
         SPH_LAUNCH_RM(k_density, false, rigid_coupled(h), sweep_mode(h), c.n, sweep_lds(h, StageF4<>::kBytes), s, c, h->P[h->pcur], h->V[h->vcur], h->WP, h->nl, h->nlb,
                       h->cnt, (const float *)nullptr, h->ds, h->rho, density_aux(h), h->P[1 - h->pcur], h->V[1 - h->vcur], rigid_view_or_none(h), h->id[h->icur],
-                      h->rho_orig, h->stage_src, h->stage_cnt, h->krho, (float4 *)nullptr);
+                      h->rho_orig, h->stage_src, h->stage_cnt, h->krho, (float4 *)nullptr, (uint32_t *)nullptr);
         h->pcur ^= 1; h->vcur ^= 1;   // P = (pos, rho), V = (vel, p/rho^2)
     }
     HIP_TRY(h, hipGetLastError());
@@ -474,7 +490,8 @@ void launch_residual(SphHandle *h, const ResidCtl &lc, const float4 *V, float *o
         if (!split) return;
     }
     SPH_LAUNCH_RMX(k_residual, DENS, rg, sweep_mode(h), relaxed_unstaged(h), c.n, sweep_lds(h, StagePV<>::kBytes), st, c, h->P[h->pcur], V, h->WP, h->nl, h->nlb, h->cnt,
-                  h->rho, dfsph_alpha(h), h->ds, out, h->krho, stage_args(h), lc, h->P[1 - h->pcur], rg ? rigid_view(h) : RigidView(), h->ncount, (const float4 *)wall_cache(h));
+                  h->rho, dfsph_alpha(h), h->ds, out, h->krho, stage_args(h), lc, h->P[1 - h->pcur], rg ? rigid_view(h) : RigidView(), h->ncount, (const float4 *)wall_cache(h), pair_bits_for(h));
+    h->pair_bits_read = pair_bits_for(h) != nullptr;
 }
 void launch_div_residual(SphHandle *h, int gate, int phase = 0, SpecUndo un = SpecUndo{nullptr, nullptr, nullptr, nullptr, 0}, hipStream_t st = nullptr)          // derivative_iter_all_rho sweep, dfsph_solver.py:252-277
 {
@@ -506,7 +523,7 @@ void launch_correct(SphHandle *h, int kid, const float *src, float4 *V, int gate
     }
     SPH_LAUNCH_RMX(k_correct, MODE, rigid_coupled(h), sweep_mode(h), relaxed_unstaged(h), n_grid, sweep_lds(h, StagePS<>::kBytes), h->stream, c,
                   c.kr_split ? h->P[h->pcur] : h->P[1 - h->pcur], h->WP, h->nl, h->nlb, h->cnt, h->rho, dfsph_alpha(h), src, h->warm[h->wcur], V, V, h->krho,
-                  stage_args(h), lc, rigid_view_or_none(h), (const float4 *)wall_cache(h));
+                  stage_args(h), lc, rigid_view_or_none(h), (const float4 *)wall_cache(h), pair_bits_for(h));
 }
 
 // The same in two halves, for the handles that hide the all-reduce (step_dfsph_device_loops): this slab's (sum, count) on the handle's stream ...
@@ -618,7 +635,8 @@ int dfsph_ext_and_dt(SphHandle *h)
                                h->VA[0], h->pmax, h->stage_src, h->stage_cnt, split ? TilePhase{h->tile_order, h->nblocks, 2} : TilePhase{nullptr, 0, 0});
         if (!use_relaxed(h) || split)
         SPH_LAUNCH_RMXQ0(k_dfsph_ext, rigid_coupled(h), sweep_mode(h), relaxed_unstaged(h), c.n, sweep_lds(h, StageF4Src::kBytes), s, c, h->P[h->pcur], h->V[h->vcur], h->nl,
-                       h->cnt, h->ds, h->VA[0], h->pmax, rigid_view_or_none(h), h->stage_src, h->stage_cnt, split ? TilePhase{h->tile_order, h->nblocks, 1} : TilePhase{nullptr, 0, 0});
+                       h->cnt, h->ds, h->VA[0], h->pmax, rigid_view_or_none(h), h->stage_src, h->stage_cnt, pair_bits_for(h),
+                       split ? TilePhase{h->tile_order, h->nblocks, 1} : TilePhase{nullptr, 0, 0});
         if (h->rigid) {   // max_rigid_vel, :104-110 (loops over the rigid particles whether or not the body is active)
             // A body that is not binned stands still: it enters the CFL rule with velocity and omega zero.  For a body that was never active that
             // is what it holds anyway; a FROZEN body keeps its velocity and omega for a later release (sph_rigid_set_active), and the reference would

@@ -731,6 +731,9 @@ int alloc_device(SphHandle *h, const HostScene &sc)
             }
             if ((h->cfg.solver == SPH_SOLVER_PCISPH || h->cfg.solver == SPH_SOLVER_IISPH) && !h->slab && h->opt_tile_skip)
                 if ((rc = dalloc(h, &h->pci_zero_press, (n + kBlock - 1) / kBlock + 64))) return rc;
+            // the pair-bit cache: a quarter of the fluid lists' words, where the 16-bit lists are (one GPU, exact arithmetic)
+            if (h->cfg.solver == SPH_SOLVER_DFSPH && h->opt_nl16 && !h->slab && !h->relaxed)
+                if ((rc = dalloc(h, &h->pair_bits, (n + 64) * (size_t)c.kpitch / 4))) return rc;
             if (h->relaxed && h->cfg.solver == SPH_SOLVER_DFSPH)      // the relaxed sweeps' per-step wall sums (use_relaxed)
                 if ((rc = dalloc(h, &h->wall_grad, n)) || (rc = dalloc(h, &h->wall_gsq, n))) return rc;
         }

@@ -633,11 +633,11 @@ struct OpA { float4 a; };
 struct OpAB { float4 a, b; };
 struct OpAS { float4 a; float s; };
 struct OpABC { float4 a, b, c; };
-template <class Body> __device__ __forceinline__ void nl_call(Body &body, const OpP &o, uint32_t) { body(o.a); }
-template <class Body> __device__ __forceinline__ void nl_call(Body &body, const OpA &o, uint32_t j) { body(o.a, make_float4(0.f, 0.f, 0.f, 0.f), j); }
-template <class Body> __device__ __forceinline__ void nl_call(Body &body, const OpAB &o, uint32_t j) { body(o.a, o.b, j); }
-template <class Body> __device__ __forceinline__ void nl_call(Body &body, const OpAS &o, uint32_t j) { body(o.a, o.s, j); }
-template <class Body> __device__ __forceinline__ void nl_call(Body &body, const OpABC &o, uint32_t j) { body(o.a, o.b, o.c, j); }
+template <class Body, class J> __device__ __forceinline__ void nl_call(Body &body, const OpP &o, J) { body(o.a); }
+template <class Body, class J> __device__ __forceinline__ void nl_call(Body &body, const OpA &o, J j) { body(o.a, make_float4(0.f, 0.f, 0.f, 0.f), j); }
+template <class Body, class J> __device__ __forceinline__ void nl_call(Body &body, const OpAB &o, J j) { body(o.a, o.b, j); }
+template <class Body, class J> __device__ __forceinline__ void nl_call(Body &body, const OpAS &o, J j) { body(o.a, o.s, j); }
+template <class Body, class J> __device__ __forceinline__ void nl_call(Body &body, const OpABC &o, J j) { body(o.a, o.b, o.c, j); }
 struct SrcP {
     const float4 *A;
     using Op = OpP; static constexpr bool kScaled = false;
@@ -752,32 +752,74 @@ struct Nl16Group {
     __device__ __forceinline__ uint32_t lo(int q) const { return w[q] & 0xffffu; }
     __device__ __forceinline__ uint32_t hi(int q) const { return w[q] >> 16; }
 };
-template <class Group>
-__device__ __forceinline__ void nl16_stream(const uint32_t *__restrict__ base, int cnt, Group group)
+// The PAIR-BIT CACHE of a staged nl16 handle rides on this stream: one word per lane per group of eight entries, laid out like the list rows
+// it belongs to -- group g of a lane at bits + g * 64, where bits = pair_bits + nl_index(i, 0, kpitch) / 4: a wave's group is 64 consecutive
+// words, a quarter of the list's stride.  Entry p (0..7) of the group owns bits [4p+3 : 4p]: 1:0 the verdict of the root's rounding step as a
+// signed field (root_by_verdict in sph_device.h), 3:2 reserved (written as 0).  D1 writes the words (kBitsWrite: the bodies fill a
+// PairFieldOut), the later sweeps of the step read them (kBitsRead: each body receives its PairField, the shift a compile-time constant); the
+// word is requested together with the group's uint4 -- same look-ahead, same "only lanes whose list goes on".  Fields past the count are 0.
+enum { kBitsNone = 0, kBitsRead = 1, kBitsWrite = 2 };
+template <int POS> struct PairField {
+    uint32_t word;
+    __device__ __forceinline__ int root() const { return __builtin_amdgcn_sbfe((int)word, 4 * POS, 2); }
+};
+template <int POS> struct PairFieldOut {
+    uint32_t *word;
+    __device__ __forceinline__ void root(int verdict) const { *word |= ((uint32_t)verdict & 3u) << (4 * POS); }
+};
+template <int BITS, int POS> struct PairArg { static __device__ __forceinline__ uint32_t make(uint32_t *) { return 0u; } };
+template <int POS> struct PairArg<kBitsRead, POS> { static __device__ __forceinline__ PairField<POS> make(uint32_t *w) { return PairField<POS>{*w}; } };
+template <int POS> struct PairArg<kBitsWrite, POS> { static __device__ __forceinline__ PairFieldOut<POS> make(uint32_t *w) { return PairFieldOut<POS>{w}; } };
+// what a pair body's third argument says about a rigid entry: the raw entry carries the tag, a field never belongs to one
+template <bool RIGID> __device__ __forceinline__ bool rigid_entry(uint32_t j) { return RIGID && (j & kRigidTag); }
+template <bool RIGID, int POS> __device__ __forceinline__ bool rigid_entry(PairField<POS>) { return false; }
+__device__ __forceinline__ uint32_t entry_index(uint32_t j) { return j & ~kRigidTag; }
+template <int POS> __device__ __forceinline__ uint32_t entry_index(PairField<POS>) { return 0u; }
+// the distance of a pair of a scaled sweep: from the cached verdict where the walk supplies one
+__device__ __forceinline__ float norm3_scaled_at(float xs, float ys, float zs, uint32_t) { return norm3_scaled(xs, ys, zs); }
+template <int POS> __device__ __forceinline__ float norm3_scaled_at(float xs, float ys, float zs, PairField<POS> f) { return norm3_scaled(xs, ys, zs, f.root()); }
+// ... and of a sweep over plain positions (D5), by the kernel functions K of its arithmetic
+template <class K> __device__ __forceinline__ float norm3_at(float x, float y, float z, uint32_t) { return K::norm3(x, y, z); }
+template <class K, int POS> __device__ __forceinline__ float norm3_at(float x, float y, float z, PairField<POS> f) { return norm3(x, y, z, f.root()); }
+
+__device__ __forceinline__ void store_word(uint32_t *p, size_t at, uint32_t v) { p[at] = v; }
+__device__ __forceinline__ void store_word(const uint32_t *, size_t, uint32_t) {}
+// (a group callback that does not ask for the word -- the relaxed sweeps -- is called without it)
+template <class Group> __device__ __forceinline__ auto nl16_group(Group &group, const Nl16Group &g, int kk, uint32_t w, int) -> decltype(group(g, kk, w)) { return group(g, kk, w); }
+template <class Group> __device__ __forceinline__ void nl16_group(Group &group, const Nl16Group &g, int kk, uint32_t, long) { group(g, kk); }
+template <int BITS = kBitsNone, class Word = const uint32_t, class Group>
+__device__ __forceinline__ void nl16_stream(const uint32_t *__restrict__ base, int cnt, Group group, Word *__restrict__ bits = nullptr)
 {
     if (cnt <= 0) return;
     uint4 jn = nl_load(base);
+    uint32_t wn = BITS == kBitsRead ? bits[0] : 0u;
     for (int kk = 0; kk < cnt; kk += 8) {
         const Nl16Group g = {{jn.x, jn.y, jn.z, jn.w}};
-        if (kk + 8 < cnt) jn = nl_load(base + (size_t)((kk >> 3) + 1) * 256);
-        group(g, kk);
+        const uint32_t w = wn;
+        if (kk + 8 < cnt) {
+            jn = nl_load(base + (size_t)((kk >> 3) + 1) * 256);
+            if (BITS == kBitsRead) wn = bits[(size_t)((kk >> 3) + 1) * 64];
+        }
+        nl16_group(group, g, kk, w, 0);
     }
 }
 // the exact sweeps take a group four entries at a time, tails masked, so that the registers in flight stay those of the 32-bit walk
-template <class Src, class Body>
-__device__ __forceinline__ void walk_list16(const Src &s, const uint32_t *__restrict__ base, int cnt, Body body)
+template <int BITS = kBitsNone, class Src, class Body, class Word = const uint32_t>
+__device__ __forceinline__ void walk_list16(const Src &s, const uint32_t *__restrict__ base, int cnt, Body body, Word *__restrict__ bits = nullptr)
 {
-    auto four = [&](uint32_t j0, uint32_t j1, uint32_t j2, uint32_t j3, int k0) {
+    auto four = [&](auto half, uint32_t j0, uint32_t j1, uint32_t j2, uint32_t j3, int k0, uint32_t *w) {
+        constexpr int H = decltype(half)::value * 4;
         const typename Src::Op o[4] = {nl_fluid(s, j0), nl_fluid(s, j1), nl_fluid(s, j2), nl_fluid(s, j3)};
-        nl_call(body, o[0], 0u);
-        if (k0 + 1 < cnt) nl_call(body, o[1], 0u);
-        if (k0 + 2 < cnt) nl_call(body, o[2], 0u);
-        if (k0 + 3 < cnt) nl_call(body, o[3], 0u);
+        nl_call(body, o[0], PairArg<BITS, H>::make(w));
+        if (k0 + 1 < cnt) nl_call(body, o[1], PairArg<BITS, H + 1>::make(w));
+        if (k0 + 2 < cnt) nl_call(body, o[2], PairArg<BITS, H + 2>::make(w));
+        if (k0 + 3 < cnt) nl_call(body, o[3], PairArg<BITS, H + 3>::make(w));
     };
-    nl16_stream(base, cnt, [&](const Nl16Group &g, int kk) {
-        four(g.lo(0), g.hi(0), g.lo(1), g.hi(1), kk);
-        if (kk + 4 < cnt) four(g.lo(2), g.hi(2), g.lo(3), g.hi(3), kk + 4);
-    });
+    nl16_stream<BITS>(base, cnt, [&](const Nl16Group &g, int kk, uint32_t word) {
+        four(std::integral_constant<int, 0>(), g.lo(0), g.hi(0), g.lo(1), g.hi(1), kk, &word);
+        if (kk + 4 < cnt) four(std::integral_constant<int, 1>(), g.lo(2), g.hi(2), g.lo(3), g.hi(3), kk + 4, &word);
+        if (BITS == kBitsWrite) store_word(bits, (size_t)(kk >> 3) * 64, word);
+    }, bits);
 }
 
 // ======================================================================================
@@ -2104,7 +2146,7 @@ __global__ __launch_bounds__(kBlock) void k_density(Consts c, const float4 *__re
                                                     float4 *__restrict__ Pout, float4 *Vout, RigidView rv,
                                                     const int *__restrict__ id, float *__restrict__ rho_orig,
                                                     const uint2 *__restrict__ stage_src, const int *__restrict__ stage_cnt, float *__restrict__ krho,
-                                                    float4 *__restrict__ wall_gc, TilePhase tp = TilePhase{nullptr, 0, 0})
+                                                    float4 *__restrict__ wall_gc, uint32_t *__restrict__ pair_bits, TilePhase tp = TilePhase{nullptr, 0, 0})
 {
     constexpr bool STAGED = MODE == SWEEP_STAGED, QUAD = MODE == SWEEP_QUAD;
     using K = KF<RX>;                                        // kernel functions of the sweep's arithmetic (sph_device.h); RX: unstaged handles under SPH_ARITH_RELAXED
@@ -2114,7 +2156,13 @@ __global__ __launch_bounds__(kBlock) void k_density(Consts c, const float4 *__re
     SPH_SWEEP_PROLOGUE_G(QUAD, tile, true)
     const SrcA mem{P};
     const StageF4<> lds{s_operand, P};
-    const bool staged = STAGED && stage_operands(lds, StagePlan{stage_src, stage_cnt, blk}) != kNotStaged;
+    // The first sweep behind a list build records the pair-bit cache of the step (walk_list16).  A workgroup that records stages its positions times
+    // 2^32 like the solver-loop sweeps and evaluates the scaled forms of the same functions (sph_device.h: norm3_scaled(d * 2^32) = norm3(d) * 2^32,
+    // grad_w_scaled = grad_w_in): the verdict it stores is then the one norm3_scaled reaches on the operands the consumers stage, at no cost of its own.
+    const bool record = DFSPH && STAGED && !RIGID && !RX && pair_bits != nullptr && c.nl16 != 0;      // uniform: the host's choice (pair_bits_scope)
+    const StageF4<true> lds_scaled{s_operand, P};
+    const StagePlan plan{stage_src, stage_cnt, blk};
+    const bool staged = STAGED && (record ? stage_operands(lds_scaled, plan) : stage_operands(lds, plan)) != kNotStaged;
     float fa[5] = {0.001f, 0.f, 0.f, 0.f, 0.f};              // rho starts at 0.001, solver_base.py:44
     float &rho = fa[0], &sx = fa[1], &sy = fa[2], &sz = fa[3], &sq = fa[4];
     auto pair = [&](const float4 pj, const float4, const uint32_t j) {
@@ -2131,7 +2179,19 @@ __global__ __launch_bounds__(kBlock) void k_density(Consts c, const float4 *__re
             sq += (rx * rx + ry * ry) + rz * rz;             // :71
         }
     };
+    const float sx_i = pi.x * 0x1p32f, sy_i = pi.y * 0x1p32f, sz_i = pi.z * 0x1p32f;
+    auto pair_record = [&](const float4 pj, const float4, const auto field) {            // pj carries 2^32; a fluid entry (16-bit lists hold no other)
+        float dx = sx_i - pj.x, dy = sy_i - pj.y, dz = sz_i - pj.z;
+        const float rs = norm3_scaled(dx, dy, dz);
+        field.root(__float_as_int(rs) - __float_as_int(__builtin_amdgcn_sqrtf((dx * dx + dy * dy) + dz * dz)));
+        rho += c.m * K::w_in(c, rs * 0x1p-32f);              // solver_base.py:62
+        F3 g = grad_w_scaled(c, dx, dy, dz, rs);
+        float rx = c.m * g.x, ry = c.m * g.y, rz = c.m * g.z;     // dfsph_solver.py:58,70
+        sx += rx; sy += ry; sz += rz;
+        sq += (rx * rx + ry * ry) + rz * rz;                 // :71
+    };
     if (QUAD) sweep_quad<RIGID>(mem, nlp, kf, q, fa, pair, rv);
+    else if (record && staged) walk_list16<kBitsWrite>(lds_scaled, nlp, kf, pair_record, pair_bits + (nl_index(ii, 0, c.kpitch) >> 2));
     else if (staged && (RIGID ? stage_lists16(stage_cnt, blk) : c.nl16 != 0)) walk_list16(lds, nlp, kf, pair);     // (a rigid build: no rigid cell near this tile)
     else if (staged) walk_staged<RIGID>(lds, nlp, kf, pair, rv);
     else sweep_list<RIGID>(mem, nlp, kf, pair, rv);
@@ -2325,7 +2385,8 @@ __global__ __launch_bounds__(kBlock) void k_correct(Consts c, const float4 *__re
                                                     const int *__restrict__ cnt, const float *__restrict__ rho,
                                                     const float *__restrict__ alpha, const float *__restrict__ src,   // drho (DIV) / rho_adv (DENS)
                                                     float *__restrict__ warm, const float4 *Vin, float4 *Vout, const float *__restrict__ krho,
-                                                    StageArgs st, CorrCtl lc, RigidView rv, const float4 *__restrict__ wall_gc)
+                                                    StageArgs st, CorrCtl lc, RigidView rv, const float4 *__restrict__ wall_gc,
+                                                    const uint32_t *__restrict__ pair_bits)
 {
     const DevScalars *const ds = lc.ds;
     const TilePhase &tp = lc.tp; const DensFlow &df = lc.df; int *const wave_dirty = lc.wave_dirty; unsigned char *const changed8 = lc.changed8;
@@ -2383,12 +2444,12 @@ __global__ __launch_bounds__(kBlock) void k_correct(Consts c, const float4 *__re
     float &ax = fa[0], &ay = fa[1], &az = fa[2];
     // one pair term; SCALED: every position carries 2^32 (staged operands) -- two multiplications less per pair, same bits
     const float sx_i = pi.x * 0x1p32f, sy_i = pi.y * 0x1p32f, sz_i = pi.z * 0x1p32f;
-    auto pair_term = [&](auto scaled, const float4 pj, const uint32_t j) {
+    auto pair_term = [&](auto scaled, const float4 pj, const auto j) {          // j: the raw entry, or the entry's field of the pair-bit cache
         constexpr bool SCALED = decltype(scaled)::value;
         float dx = (SCALED ? sx_i : pi.x) - pj.x, dy = (SCALED ? sy_i : pi.y) - pj.y, dz = (SCALED ? sz_i : pi.z) - pj.z;
-        float r = SCALED ? norm3_scaled(dx, dy, dz) : K::norm3(dx, dy, dz);
+        float r = SCALED ? norm3_scaled_at(dx, dy, dz, j) : K::norm3(dx, dy, dz);
         F3 g = SCALED ? grad_w_scaled(c, dx, dy, dz, r) : K::grad_in(c, dx, dy, dz, r);
-        if (RIGID && (j & kRigidTag)) {
+        if (rigid_entry<RIGID>(j)) {
             float s = pj.w * c.rho0 * k_i / rho_i;                                // :345 / :377 / :211  (no 1e-5 gate)
             ax += s * g.x; ay += s * g.y; az += s * g.z;
         } else {
@@ -2400,10 +2461,11 @@ __global__ __launch_bounds__(kBlock) void k_correct(Consts c, const float4 *__re
         }
     };
     auto pair = [&](const float4 pj, const float4, const uint32_t j) { pair_term(std::false_type{}, pj, j); };
-    auto pair_scaled = [&](const float4 pj, const float4, const uint32_t j) { pair_term(std::true_type{}, pj, j); };
+    auto pair_scaled = [&](const float4 pj, const float4, const auto j) { pair_term(std::true_type{}, pj, j); };
     const SrcA mem{P};
     const StageF4<true> lds{s_operand, P};                   // (either layout staged above leaves (pos * 2^32, k / rho): one reader)
     if (QUAD) sweep_quad<RIGID>(mem, nlp, kf, q, fa, pair, rv);
+    else if (!RIGID && !RX && pair_bits && staged && c.nl16 != 0) walk_list16<kBitsRead>(lds, nlp, kf, pair_scaled, pair_bits + (nl_index(ii, 0, c.kpitch) >> 2));   // (uniform: the host's choice, pair_bits_for)
     else if (staged && (RIGID ? stage_lists16(st.cnt, blk) : c.nl16 != 0)) walk_list16(lds, nlp, kf, pair_scaled);
     else if (staged) walk_staged<RIGID>(lds, nlp, kf, pair_scaled, rv);
     else if (split)          // a workgroup of a kr_split handle whose set did not fit: two global gathers per neighbour (a tagged entry: the rigid sample, V_r in .w)
@@ -2461,7 +2523,7 @@ __global__ __launch_bounds__(kBlock) void k_residual(Consts c, const float4 *__r
                                                      const float *__restrict__ rho, const float *__restrict__ alpha,
                                                      DevScalars *__restrict__ ds, float *__restrict__ out, float *__restrict__ krho, StageArgs st, ResidCtl lc,
                                                      float4 *__restrict__ Pout, RigidView rv, const int *__restrict__ ncount,
-                                                     const float4 *__restrict__ wall_gc)
+                                                     const float4 *__restrict__ wall_gc, const uint32_t *__restrict__ pair_bits)
 {
     const TilePhase &tp = lc.tp; const DensFlow &df = lc.df; const int *const wave_dirty = lc.wave_dirty; const unsigned char *const changed8 = lc.changed8;
     constexpr bool STAGED = SWEEP == SWEEP_STAGED, QUAD = SWEEP == SWEEP_QUAD;
@@ -2502,12 +2564,12 @@ __global__ __launch_bounds__(kBlock) void k_residual(Consts c, const float4 *__r
     const bool skip = !DENS && nq < 20;                                           // :258-261
     const float dt_r = RIGID ? ds->dt : 0.f;
     const float sx_i = pi.x * 0x1p32f, sy_i = pi.y * 0x1p32f, sz_i = pi.z * 0x1p32f;
-    auto pair_term = [&](auto scaled, const float4 pj, const float4 vj, const uint32_t j) {      // SCALED: positions carry 2^32 (see k_correct)
+    auto pair_term = [&](auto scaled, const float4 pj, const float4 vj, const auto j) {      // SCALED: positions carry 2^32; j: entry or field (see k_correct)
         constexpr bool SCALED = decltype(scaled)::value;
         float dx = (SCALED ? sx_i : pi.x) - pj.x, dy = (SCALED ? sy_i : pi.y) - pj.y, dz = (SCALED ? sz_i : pi.z) - pj.z;
-        float r = SCALED ? norm3_scaled(dx, dy, dz) : K::norm3(dx, dy, dz);
+        float r = SCALED ? norm3_scaled_at(dx, dy, dz, j) : K::norm3(dx, dy, dz);
         F3 g = SCALED ? grad_w_scaled(c, dx, dy, dz, r) : K::grad_in(c, dx, dy, dz, r);
-        if (RIGID && (j & kRigidTag)) {
+        if (rigid_entry<RIGID>(j)) {
             const float4 pu = SCALED ? make_float4(pj.x * 0x1p-32f, pj.y * 0x1p-32f, pj.z * 0x1p-32f, pj.w) : pj;     // the rigid sample, un-scaled
             const F3 w = rigid_velocity(rv, pu, dt_r, DENS);                      // :292-293 / :168-169
             acc += pj.w * c.rho0 * dot3(vi.x - w.x, vi.y - w.y, vi.z - w.z, g.x, g.y, g.z);   // :294 / :170
@@ -2516,8 +2578,9 @@ __global__ __launch_bounds__(kBlock) void k_residual(Consts c, const float4 *__r
         }
     };
     auto pair = [&](const float4 pj, const float4 vj, const uint32_t j) { pair_term(std::false_type{}, pj, vj, j); };
-    auto pair_scaled = [&](const float4 pj, const float4 vj, const uint32_t j) { pair_term(std::true_type{}, pj, vj, j); };
+    auto pair_scaled = [&](const float4 pj, const float4 vj, const auto j) { pair_term(std::true_type{}, pj, vj, j); };
     if (QUAD) sweep_quad<RIGID>(mem, nlp, skip ? 0 : kf, q, fa, pair, rv);
+    else if (!RIGID && !RX && pair_bits && staged && c.nl16 != 0) walk_list16<kBitsRead>(lds, nlp, skip ? 0 : kf, pair_scaled, pair_bits + (nl_index(ii, 0, c.kpitch) >> 2));
     else if (staged && (RIGID ? stage_lists16(st.cnt, blk) : c.nl16 != 0)) walk_list16(lds, nlp, skip ? 0 : kf, pair_scaled);
     else if (staged) walk_staged<RIGID>(lds, nlp, skip ? 0 : kf, pair_scaled, rv);
     else sweep_list<RIGID>(mem, nlp, skip ? 0 : kf, pair, rv);
@@ -2572,7 +2635,8 @@ __global__ __launch_bounds__(kBlock) void k_dfsph_ext(Consts c, const float4 *__
                                                       const uint32_t *__restrict__ nl, const int *__restrict__ cnt,
                                                       const DevScalars *__restrict__ ds, float4 *__restrict__ VAout,
                                                       float *__restrict__ pmax, RigidView rv,
-                                                      const uint2 *__restrict__ stage_src, const int *__restrict__ stage_cnt, TilePhase tp = TilePhase{nullptr, 0, 0})
+                                                      const uint2 *__restrict__ stage_src, const int *__restrict__ stage_cnt, const uint32_t *__restrict__ pair_bits,
+                                                      TilePhase tp = TilePhase{nullptr, 0, 0})
 {
     constexpr bool STAGED = SWEEP == SWEEP_STAGED, QUAD = SWEEP == SWEEP_QUAD;
     using K = KF<RX>;                                        // kernel functions of the sweep's arithmetic (sph_device.h); RX: unstaged handles under SPH_ARITH_RELAXED
@@ -2592,15 +2656,15 @@ __global__ __launch_bounds__(kBlock) void k_dfsph_ext(Consts c, const float4 *__
     float fa[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float &wx = fa[0], &wy = fa[1], &wz = fa[2];
     float &tx = fa[3], &ty = fa[4], &tz = fa[5];
-    auto pair = [&](const float4 pj, const float4 vj, const uint32_t j) {
+    auto pair = [&](const float4 pj, const float4 vj, const auto j) {            // j: the raw entry, or the entry's field of the pair-bit cache
         float dx = pi.x - pj.x, dy = pi.y - pj.y, dz = pi.z - pj.z;
-        float r = K::norm3(dx, dy, dz);
-        if (RIGID && (j & kRigidTag)) {
+        float r = norm3_at<K>(dx, dy, dz, j);
+        if (rigid_entry<RIGID>(j)) {
             // solver_base.py:190-201: no tension from rigid neighbours; viscosity against the body velocity, with
             // rho[particle_j.index] = the FLUID density at the rigid particle's local index (quirk, :198-199)
             float vx = vi.x - rv.vel[0], vy = vi.y - rv.vel[1], vz = vi.z - rv.vel[2];
             float shear = dot3(vx, vy, vz, dx, dy, dz);
-            const int jl = rv.rid[j & ~kRigidTag];
+            const int jl = rv.rid[entry_index(j)];
             if (shear < 0.f && jl < rv.n_fluid) {
                 F3 g = K::grad_in(c, dx, dy, dz, r);
                 float q2 = r * r;
@@ -2625,6 +2689,7 @@ __global__ __launch_bounds__(kBlock) void k_dfsph_ext(Consts c, const float4 *__
         }
     };
     if (QUAD) sweep_quad<RIGID>(mem, nlp, kf, q, fa, pair, rv);
+    else if (!RIGID && !RX && pair_bits && staged && c.nl16 != 0) walk_list16<kBitsRead>(lds, nlp, kf, pair, pair_bits + (nl_index(ii, 0, c.kpitch) >> 2));
     else if (staged && (RIGID ? stage_lists16(stage_cnt, blk) : c.nl16 != 0)) walk_list16(lds, nlp, kf, pair);
     else if (staged) walk_staged<RIGID>(lds, nlp, kf, pair, rv);
     else sweep_list<RIGID>(mem, nlp, kf, pair, rv);
@@ -2855,6 +2920,14 @@ __global__ void k_selftest(Consts c, int op, const float *__restrict__ a, const 
     else if (op == 8) r = div_shared(x, recip_prepare(y));
     else if (op == 9) r = div_shared_two_step(x, recip_prepare(y));
     else if (op == 10) r = div_shared(x, recip_prepare(__builtin_fmaxf(y, kDenFloor)));
+    else if (op == 11 || op == 12) {
+        // the root through the pair-bit cache: sqrt_rn's own verdict, packed into a 2-bit field and taken back out of it (11), and the verdict itself (12)
+        const float xs = x * 0x1p64f;
+        const int verdict = __float_as_int(sqrt_rn(x) * 0x1p32f) - __float_as_int(__builtin_amdgcn_sqrtf(xs));
+        uint32_t word = 0u;
+        PairFieldOut<5>{&word}.root(verdict);
+        r = op == 11 ? root_by_verdict(xs, PairField<5>{word}.root()) * 0x1p-32f : (float)verdict;
+    }
     else {
         float dz = 0.25f * x;
         float rn = norm3(x, y, dz);

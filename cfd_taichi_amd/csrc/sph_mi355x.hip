@@ -150,6 +150,11 @@ struct SphHandle {
     float *wall_gsq = nullptr;                   //   ... and the walls' share of alpha's denominator
     float4 *wall_gc = nullptr;                   // exact dfsph sweeps: (grad W_ib, V_b) per wall-list entry, written by D1 (for_wall_cache)
     bool opt_wall_cache = true;                  // SPH_WALL_CACHE=0 at sph_create: D2-D7 walk the wall lists themselves (A/B, tests)
+    // the pair-bit cache of the staged 16-bit walks (walk_list16 in sph_kernels.h): one word per lane per group of eight list entries, written by D1.
+    // It belongs to ONE list build: nl_gen counts the builds, pair_bits_gen is the build D1 last wrote the cache for (pair_bits_for)
+    uint32_t *pair_bits = nullptr;
+    uint64_t nl_gen = 0, pair_bits_gen = ~(uint64_t)0;
+    bool pair_bits_read = false;                 // SPH_S_PAIR_BITS: the last dfsph step's solver-loop sweeps read the cache
     // change propagation between the sweeps of the density loop (sph_kernels.h: stage_sources_flagged); SPH_TILE_SKIP=0 turns it off
     int *wave_dirty = nullptr;                   // per 64-particle wave: did the last density correction change a velocity there?
     unsigned char *changed8 = nullptr;           // ... and per particle (the second, exact level of the residual sweep's check)
@@ -1164,6 +1169,7 @@ int sph_get_scalar(SphHandle *h, int which, double *out)
     case SPH_S_ARITH_RELAXED: *out = (use_relaxed(h) || h->verlet || relaxed_pressure(h) || relaxed_unstaged(h) || relaxed_pbf(h)) ? 1.0 : 0.0; return SPH_OK;
     case SPH_S_RIGID_ACTIVE: *out = rigid_binned(h) ? 1.0 : 0.0; return SPH_OK;
     case SPH_S_RIGID_MODE: *out = h->rigid ? (double)h->rigid_mode : 0.0; return SPH_OK;
+    case SPH_S_PAIR_BITS: *out = h->pair_bits_read ? 1.0 : 0.0; return SPH_OK;
     case SPH_S_FLUID_CAPACITY: *out = (double)(h->slab ? h->N : h->ncap); return SPH_OK;      // (a slab handle's ncap is its slab's: sph_slab_info)
     case SPH_S_TIME: { int rc = read_scalars(h); if (rc) return rc; *out = h->ds_host->sim_time; return SPH_OK; }
     case SPH_S_ACCEL: case SPH_S_ACCEL + 1: case SPH_S_ACCEL + 2:
@@ -1702,6 +1708,56 @@ int sph_selftest_walk(SphHandle *h, int walk, int src, int rigid, const uint32_t
     }
     (void)hipFree(d_runs); (void)hipFree(d_head); (void)hipFree(d_cnt); (void)hipFree(d_A); (void)hipFree(d_B); (void)hipFree(d_C); (void)hipFree(d_S);
     (void)hipFree(d_RP); (void)hipFree(d_nl); (void)hipFree(d_out);
+    return rc;
+}
+
+// walk_list16 with the pair-bit stream, on one workgroup of kWalkTestParticles threads: lists (NP x 24 entries < NP), counts (0 .. 24), words (NP x 3: the
+// word of every group of eight, read when write == 0 and returned when write != 0), verdicts (NP x 24: what body k records when write != 0); seen
+// (NP x 24) and calls (NP) are what the bodies report (k_selftest_walk_bits)
+int sph_selftest_walk_bits(SphHandle *h, int write, const uint32_t *lists, const int *counts, uint32_t *words, const int *verdicts, uint32_t *seen, int *calls)
+{
+    int ndev = 0;
+    const int device = h ? h->device : 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, SPH_E_NO_DEVICE, "no HIP device available");
+    constexpr int NP = kWalkTestParticles, ROWS = kWalkTestRows, PITCH = kWalkTestPitch, GROUPS = ROWS / 8;
+    if (device < 0 || device >= ndev || !lists || !counts || !words || !verdicts || !seen || !calls) return fail(nullptr, SPH_E_INVALID, "bad argument");
+    std::vector<uint32_t> nl((size_t)(NP / 64 + 1) * PITCH * 64, 0u), bits(nl.size() / 4, 0u);
+    std::vector<float4> A(NP);
+    for (int i = 0; i < NP; ++i) {
+        A[i] = make_float4((float)i, 0.f, 0.f, 0.f);
+        if (counts[i] < 0 || counts[i] > ROWS) return fail(nullptr, SPH_E_INVALID, "a count leaves 0 .. 24");
+        for (int k = 0; k < ROWS; ++k) {
+            const uint32_t j = lists[(size_t)i * ROWS + k];
+            if (j >= (uint32_t)NP) return fail(nullptr, SPH_E_INVALID, "a list entry leaves its array");
+            nl[nl_index(i, 4 * (k >> 3) + ((k & 7) >> 1), PITCH)] |= j << (16 * (k & 1));
+        }
+        for (int g = 0; g < GROUPS; ++g) bits[(nl_index(i, 0, PITCH) >> 2) + (size_t)g * 64] = write ? 0xffffffffu : words[(size_t)i * GROUPS + g];
+    }
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, SPH_E_HIP, "hipSetDevice failed");
+    float4 *d_A = nullptr; uint32_t *d_nl = nullptr, *d_bits = nullptr, *d_seen = nullptr; int *d_cnt = nullptr, *d_verdict = nullptr, *d_calls = nullptr;
+    int rc = SPH_OK;
+    if (hipMalloc((void **)&d_A, NP * 16) != hipSuccess || hipMalloc((void **)&d_nl, nl.size() * 4) != hipSuccess || hipMalloc((void **)&d_bits, bits.size() * 4) != hipSuccess ||
+        hipMalloc((void **)&d_seen, (size_t)NP * ROWS * 4) != hipSuccess || hipMalloc((void **)&d_cnt, NP * 4) != hipSuccess ||
+        hipMalloc((void **)&d_verdict, (size_t)NP * ROWS * 4) != hipSuccess || hipMalloc((void **)&d_calls, NP * 4) != hipSuccess)
+        rc = fail(nullptr, SPH_E_HIP, "hipMalloc failed");
+    if (!rc) {
+        (void)hipMemcpy(d_A, A.data(), NP * 16, hipMemcpyHostToDevice);
+        (void)hipMemcpy(d_nl, nl.data(), nl.size() * 4, hipMemcpyHostToDevice);
+        (void)hipMemcpy(d_bits, bits.data(), bits.size() * 4, hipMemcpyHostToDevice);
+        (void)hipMemcpy(d_cnt, counts, NP * 4, hipMemcpyHostToDevice);
+        (void)hipMemcpy(d_verdict, verdicts, (size_t)NP * ROWS * 4, hipMemcpyHostToDevice);
+        (void)hipMemset(d_seen, 0xff, (size_t)NP * ROWS * 4);
+        hipLaunchKernelGGL(k_selftest_walk_bits, dim3(1), dim3(kBlock), 0, 0, write, d_A, d_nl, d_cnt, d_bits, d_verdict, d_seen, d_calls);
+        if (hipDeviceSynchronize() != hipSuccess) rc = fail(nullptr, SPH_E_HIP, "selftest kernel failed");
+        else {
+            (void)hipMemcpy(seen, d_seen, (size_t)NP * ROWS * 4, hipMemcpyDeviceToHost);
+            (void)hipMemcpy(calls, d_calls, NP * 4, hipMemcpyDeviceToHost);
+            (void)hipMemcpy(bits.data(), d_bits, bits.size() * 4, hipMemcpyDeviceToHost);
+            for (int i = 0; i < NP; ++i)
+                for (int g = 0; g < GROUPS; ++g) words[(size_t)i * GROUPS + g] = bits[(nl_index(i, 0, PITCH) >> 2) + (size_t)g * 64];
+        }
+    }
+    (void)hipFree(d_A); (void)hipFree(d_nl); (void)hipFree(d_bits); (void)hipFree(d_seen); (void)hipFree(d_cnt); (void)hipFree(d_verdict); (void)hipFree(d_calls);
     return rc;
 }
 

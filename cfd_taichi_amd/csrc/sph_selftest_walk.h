@@ -120,4 +120,24 @@ __global__ __launch_bounds__(kBlock) void k_selftest_walk(int src, const uint2 *
     out[4 * t + 2] = __float_as_uint(acc[0]); out[4 * t + 3] = __float_as_uint(acc[1]);
 }
 
+// sph_selftest_walk_bits: walk_list16 with a bits stream on one workgroup.  Every thread walks its 16-bit list (entries = indices into A, A[j].x = j)
+// and reports, per body call in order, seen[k] = entry | (field & 0xff) << 16 (the field sign-extended as the body received it), and its call count.
+//   write == 0 (kBitsRead): the fields come from the caller's words;  write == 1 (kBitsWrite): body k records verdict[k] and the words the walk stored come back
+__global__ __launch_bounds__(kBlock) void k_selftest_walk_bits(int write, const float4 *__restrict__ A, const uint32_t *__restrict__ nl, const int *__restrict__ cnt,
+                                                               uint32_t *__restrict__ bits, const int *__restrict__ verdict, uint32_t *__restrict__ seen,
+                                                               int *__restrict__ calls)
+{
+    const int i = (int)threadIdx.x;
+    const uint32_t *nlp = nl + nl_index(i, 0, kWalkTestPitch);
+    uint32_t *bp = bits + (nl_index(i, 0, kWalkTestPitch) >> 2);
+    const int kf = cnt[i];
+    int n = 0;
+    uint32_t *mine = seen + (size_t)i * kWalkTestRows;
+    const int *want = verdict + (size_t)i * kWalkTestRows;
+    const SrcA src{A};
+    if (write) walk_list16<kBitsWrite>(src, nlp, kf, [&](const float4 a, const float4, const auto f) { if (n < kWalkTestRows) { mine[n] = (uint32_t)a.x; f.root(want[n]); } ++n; }, bp);
+    else walk_list16<kBitsRead>(src, nlp, kf, [&](const float4 a, const float4, const auto f) { if (n < kWalkTestRows) mine[n] = (uint32_t)a.x | ((uint32_t)f.root() & 0xffu) << 16; ++n; }, (const uint32_t *)bp);
+    calls[i] = n;
+}
+
 }  // namespace sph

@@ -197,6 +197,8 @@ typedef struct SphRigid {
 #define SPH_S_FLUID_CAPACITY 47     /* read-only: fluid particles the handle can hold (SphConfig.fluid_capacity, or the lattice's count); SphSizes.n_fluid is
                                     * the live count */
 #define SPH_S_VERLET_BUILDS 31    /* diagnostics: list builds so far on a Verlet handle (wcsph under the relaxed arithmetic: the lists carry a skin and are rebuilt on demand) */
+#define SPH_S_PAIR_BITS 48          /* diagnostics, read-only: 1 if the solver-loop sweeps of the last dfsph step took the root's rounding step from the per-step
+                                      pair-bit cache (staged 16-bit lists of a one-GPU handle without a binned body, exact arithmetic), else 0 */
 #define SPH_S_ARITH_RELAXED 30    /* diagnostics: 1 if any pair sweep of this handle's solver runs the tolerance-grade kernels (SphConfig.arith asked AND the handle qualifies) */
 
 /* Solver attributes a caller of the reference edits on the solver object after constructing it -- sph_set_scalar / sph_get_scalar.
@@ -670,6 +672,10 @@ int sph_selftest_stage(SphHandle *h, int layout, int check, int empty_idle, int 
  * the memory walks.  A, B, C: n_src float4, S: n_src floats, RP: n_rig float4.  out: 4 words per thread (walk 1: 1024 threads, four per
  * particle; else 256): body calls, the hash h = h * 0x9E3779B1 + word over every call's operand bits and rigid flag, and (walk 1) the bits of two
  * sums that start at 0.001 and 0 and take a.x and a.y of every call in list order. */
+/* walk_list16 with the pair-bit stream on one workgroup of 256 threads (csrc/sph_selftest_walk.h): lists 256 x 24 entries < 256, counts 0 .. 24, words 256 x 3
+ * (read when write == 0, returned when write != 0: what the walk stored), verdicts 256 x 24 (recorded by body k when write != 0); seen 256 x 24: per body call
+ * in order entry | (field & 0xff) << 16, 0xffffffff where no call wrote; calls 256.  h may be NULL (device 0).  Fields: SPH_S_PAIR_BITS. */
+int sph_selftest_walk_bits(SphHandle *h, int write, const uint32_t *lists, const int32_t *counts, uint32_t *words, const int32_t *verdicts, uint32_t *seen, int32_t *calls);
 int sph_selftest_walk(SphHandle *h, int walk, int src, int rigid, const uint32_t *lists, const int *counts, uint32_t run_first, uint32_t run_n,
                       const float *A, const float *B, const float *C, const float *S, size_t n_src, const float *RP, size_t n_rig, uint32_t *out);
 

@@ -52,3 +52,10 @@ for _ in range(rounds):
 n_fluid = next(iter(sims.values())).n_fluid
 for n, t in res.items():
     print("%-10s ms/step min %.3f median %.3f  -> %.1f Mparticle-steps/s (median)" % (n, min(t), statistics.median(t), n_fluid / statistics.median(t) / 1e3))
+# the variants advanced in lock step: their states must be the same bytes (positions, velocities, warm-start k), and the spread between two
+# variants that are the same build (a byte copy) says what a difference between medians is worth
+first = next(iter(sims))
+ref = {f: sims[first].download(f) for f in (nat.F_POS, nat.F_VEL)}
+for n, sim in sims.items():
+    same = all(sim.download(f).tobytes() == a.tobytes() for f, a in ref.items())
+    print("%-10s state vs %s: %s" % (n, first, "byte-identical" if same else "DIFFERS"))

@@ -23,7 +23,10 @@ K, R = "sph_kernels.h", "sph_relaxed_kernels.h"
 PATCHES = {
     # exact k_residual (sph_kernels.h): the fluid pair loop / the wall loop removed
     "nofluid": [(K, "    else if (staged && (RIGID ? stage_lists16(st.cnt, blk) : c.nl16 != 0)) walk_list16(lds, nlp, skip ? 0 : kf, pair_scaled);",
-                 "    else if (staged && (RIGID ? stage_lists16(st.cnt, blk) : c.nl16 != 0)) walk_list16(lds, nlp, 0, pair_scaled);")],
+                 "    else if (staged && (RIGID ? stage_lists16(st.cnt, blk) : c.nl16 != 0)) walk_list16(lds, nlp, 0, pair_scaled);"),
+                (K, "walk_list16<kBitsRead>(lds, nlp, skip ? 0 : kf, pair_scaled,", "walk_list16<kBitsRead>(lds, nlp, 0, pair_scaled,")],
+    # a CORRECT variant: no sweep is handed the pair-bit cache, every pair computes the root's rounding step (the A of tools/ab_steps.py for the cache)
+    "nopairbits": [("sph_host_dfsph.h", "    return (pair_bits_scope(h) && h->nl_valid && h->pair_bits_gen == h->nl_gen) ? h->pair_bits : nullptr;", "    return nullptr;")],
     "nowall": [(K, "    else sweep_list<false>(SrcP{WP}, nlbp, skip ? 0 : kb, wall);\n    float val = 0.f, kr = 0.f;", "    else sweep_list<false>(SrcP{WP}, nlbp, 0, wall);\n    float val = 0.f, kr = 0.f;")],
     "nowall_correct": [(K, "    else sweep_list<false>(SrcP{WP}, nlbp, kb, wall);\n    if (track) {\n        const bool changed", "    else sweep_list<false>(SrcP{WP}, nlbp, 0, wall);\n    if (track) {\n        const bool changed")],
     # CORRECT variants (speed only): the solver-loop sweeps take their tiles in chunks of C consecutive tiles dealt round-robin over the XCDs
@@ -150,8 +153,8 @@ PATCHES = {
     # relaxed sweeps with HALF the index stream (every second 16-byte group of a list is not loaded, the walk reuses the group before it: same
     # LDS gathers, same arithmetic, half the list bytes from HBM): what a 2x more compact list encoding could buy at most.
     # The stream (nl16_stream) is shared with walk_list16: the exact sweeps of this build skip groups too -- time it under SPH_ARITH=relaxed only
-    "rx_halflist": [(K, "        if (kk + 8 < cnt) jn = nl_load(base + (size_t)((kk >> 3) + 1) * 256);\n        group(g, kk);",
-                     "        if (kk + 8 < cnt && ((kk >> 3) & 1)) jn = nl_load(base + (size_t)((kk >> 3) + 1) * 256);\n        group(g, kk);")],
+    "rx_halflist": [(K, "        if (kk + 8 < cnt) {\n            jn = nl_load(base + (size_t)((kk >> 3) + 1) * 256);",
+                     "        if (kk + 8 < cnt && ((kk >> 3) & 1)) {\n            jn = nl_load(base + (size_t)((kk >> 3) + 1) * 256);")],
     "rx_nostage": [(R, "    else verdict = stage_operands<kCheckWith, kStaged>(StagePV<>{s_operand, s_v2, P, V, (spread && hd.direct) ? lc.changed8 : nullptr}, plan);\n",
                     "    else verdict = kStaged;\n"),
                    (R, "        nl16_stream(nlp, kfx, [&](const Nl16Group &g, int) {\n            OpAB o[8];",
