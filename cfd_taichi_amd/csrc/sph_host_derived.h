@@ -20,14 +20,12 @@ inline bool derived_quantity(int which, int *width, int *first)
 // (the handle's staging buffer holds three)
 int derived_scratch(SphHandle *h)
 {
-    if (h->drv_vr) return SPH_OK;
+    if (h->own.derived) return SPH_OK;
     const size_t st = (size_t)h->c.stride;
-    float *base = nullptr;
-    HIP_TRY(h, hipMalloc((void **)&base, sizeof(float) * st * (4 + kDerivedPlanes + 9)));
-    HIP_TRY(h, hipMemsetAsync(base, 0, sizeof(float) * st * (4 + kDerivedPlanes + 9), h->stream));
-    h->drv_vr = (float4 *)base;
-    h->drv_out = base + 4 * st;
-    h->drv_api = h->drv_out + kDerivedPlanes * st;
+    h->own.derived.want(&h->drv_vr, st);
+    h->own.derived.want(&h->drv_out, kDerivedPlanes * st);
+    h->own.derived.want(&h->drv_api, 9 * st);
+    HIP_TRY(h, h->own.derived.commit(h->stream));
     return SPH_OK;
 }
 
@@ -56,20 +54,14 @@ int derived_fetch(SphHandle *h, int which, float *host, size_t n_floats)
     const size_t count = (size_t)width * (size_t)h->N;
     if (n_floats != count) return fail(h, SPH_E_INVALID, "sph_derived: quantity %d holds %zu floats, got %zu", which, count, n_floats);
     HIP_TRY(h, hipSetDevice(h->device));
-    if (!(h->derived_valid && h->nl_valid && h->density_valid)) {
+    if (!(h->derived_valid && h->nl_valid && h->density_valid)) {      // (all three: a body step takes the lists down alone, STALE_BODY_MOVED)
         if (int rc = sph_compute_density(h)) return rc;
         if (int rc = derived_scratch(h)) return rc;
         if (int rc = launch_derived(h)) return rc;
-        h->derived_valid = true;
+        mark_stale(h, STALE_DERIVED_COMPUTED);
     }
-    hipStream_t s = h->stream;
-    {
-        ProfScope ps(h, K_TRANSFER);
-        hipLaunchKernelGGL(k_unsort_planes, grid_for(h->N), dim3(kBlock), 0, s, h->N, (const float *)h->drv_out, (size_t)h->c.stride, first, width,
+    return fetch_api_order(h, [&] {
+        hipLaunchKernelGGL(k_unsort_planes, grid_for(h->N), dim3(kBlock), 0, h->stream, h->N, (const float *)h->drv_out, (size_t)h->c.stride, first, width,
                            (const int *)h->id[h->icur], h->drv_api);
-    }
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(host, h->drv_api, sizeof(float) * count, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return SPH_OK;
+    }, h->drv_api, host, sizeof(float) * count);
 }

@@ -148,11 +148,8 @@ int stage_sort_and_lists(SphHandle *h)
         hipLaunchKernelGGL(k_rx_wall_grad, g, b, 0, s, c, h->P[h->pcur], h->WP, h->nlb, h->cnt, h->wall_grad, h->wall_gsq);
     }
     HIP_TRY(h, hipGetLastError());
-    h->nl_valid = true;
+    mark_stale(h, STALE_LISTS_BUILT);
     h->nl_gen += 1;                                          // (whatever D1 cached for the lists before is not about these: pair_bits_for)
-    h->density_valid = false;
-    h->derived_valid = false;
-    h->lists_predate_flag = false;
     return SPH_OK;
 }
 
@@ -215,7 +212,7 @@ int stage_density(SphHandle *h)
         SPH_LAUNCH_PBF(k_pbf_lambda, sweep_mode(h) == SWEEP_QUAD, relaxed_pbf(h), grid_for(c.n), dim3((unsigned)std::max(1, (c.n + 63) / 64)), s, c, k,
                        h->P[h->pcur], h->WP, h->nl, h->nlb, h->cnt, h->rho, pbf_arrays(h).lambda, h->P[1 - h->pcur], 1);      // the step's own instantiation
         HIP_TRY(h, hipGetLastError());
-        h->density_valid = true;
+        mark_stale(h, STALE_DENSITY_COMPUTED);
         return SPH_OK;
     }
     const bool dfsph = h->cfg.solver == SPH_SOLVER_DFSPH;
@@ -225,7 +222,7 @@ int stage_density(SphHandle *h)
                            h->rho, wcsph_pressure(h), h->P[1 - h->pcur], h->V[1 - h->vcur], h->wall_grad, h->ds, 1);
         h->pcur ^= 1; h->vcur ^= 1;                         // P = (pos, rho), V = (vel, p / rho^2)
         HIP_TRY(h, hipGetLastError());
-        h->density_valid = true;
+        mark_stale(h, STALE_DENSITY_COMPUTED);
         return SPH_OK;
     }
     if (dfsph) {
@@ -270,7 +267,7 @@ int stage_density(SphHandle *h)
         int rc = slab_exchange_field(h, ps ? 3 : 2, dfsph ? h->P[1 - h->pcur] : h->P[h->pcur], h->V[h->vcur], (dfsph || ps) ? h->rho : nullptr);
         if (rc) return rc;
     }
-    h->density_valid = true;
+    mark_stale(h, STALE_DENSITY_COMPUTED);
     return SPH_OK;
 }
 
@@ -335,9 +332,7 @@ int step_end(SphHandle *h)
     if (h->diag_every)
         if (int rc = diag_step_end(h)) return rc;
     HIP_TRY(h, hipGetLastError());
-    h->nl_valid = false;
-    h->density_valid = false;
-    h->derived_valid = false;
+    mark_stale(h, STALE_STEP_RAN);
     return SPH_OK;
 }
 

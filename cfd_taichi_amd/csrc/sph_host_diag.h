@@ -8,10 +8,10 @@ constexpr int kDiagMaxRows = 1 << 20;        // 256 MiB of ring: anything larger
 // use: a handle that never asks for diagnostics is laid out as before
 int diag_scratch(SphHandle *h)
 {
-    if (h->diag_part) return SPH_OK;
-    HIP_TRY(h, hipMalloc((void **)&h->diag_part, sizeof(double) * ((size_t)kDiagParts * kDiagPartStride + kDiagSlots)));
-    HIP_TRY(h, hipMemsetAsync(h->diag_part, 0, sizeof(double) * ((size_t)kDiagParts * kDiagPartStride + kDiagSlots), h->stream));
-    h->diag_row = h->diag_part + (size_t)kDiagParts * kDiagPartStride;
+    if (h->own.diag) return SPH_OK;
+    h->own.diag.want(&h->diag_part, (size_t)kDiagParts * kDiagPartStride);
+    h->own.diag.want(&h->diag_row, kDiagSlots);
+    HIP_TRY(h, h->own.diag.commit(h->stream));
     return SPH_OK;
 }
 

@@ -117,6 +117,23 @@ void launch_unsort(SphHandle *h, const FieldLoc &f, float *dst)
     case FK_INT: hipLaunchKernelGGL(k_unsort_scalar_int, g, b, 0, s, h->N, (const int *)f.data, id, dst); break;
     }
 }
+// A per-particle array back in API order: `unsort` launches the caller's own kernel -- launch_unsort for an array of
+// FieldLoc's kinds, k_unsort_planes for planes with a stride, an int or a measured-set kernel -- from device order through id[icur] into the staging
+// area the caller names, under K_TRANSFER; then the check, `bytes` of it to the host, the wait.  The refusals (null pointer, element count) stay
+// with the callers, in their own words and order.  (The device order does not change inside a step: the ids of the current generation apply)
+template <class Unsort>
+int fetch_api_order(SphHandle *h, Unsort unsort, const void *staging, void *host, size_t bytes)
+{
+    hipStream_t s = h->stream;
+    {
+        ProfScope ps(h, K_TRANSFER);
+        unsort();
+    }
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(host, staging, bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return SPH_OK;
+}
 // ... and back: floats in API order at `src` (device) into a float4 array's xyz or a float array
 void launch_sort_in(SphHandle *h, const float *src, const FieldLoc &f)
 {

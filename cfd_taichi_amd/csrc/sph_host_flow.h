@@ -23,12 +23,9 @@ static int fluid_count_changed(SphHandle *h, int n)
     const void *tile_flags[] = {h->pci_zero_press};
     if (int rc = dzero(h, tile_flags, 1)) return rc;
     if (int rc = wl_count_changed(h)) return rc;                      // the measured wall samples' lists (section 6m): stale entries must stay valid indices
-    if (h->verlet) {              // the lists of the last build know neither the new particles nor the new slots: the next step builds them
-        h->ds_host->moved = 1;
-        HIP_TRY(h, hipMemcpyAsync(&h->ds->moved, &h->ds_host->moved, sizeof(int), hipMemcpyHostToDevice, s));
-    }
+    // the lists of the last build know neither the new particles nor the new slots; the captured step pairs carry the old count and grids
+    if (int rc = mark_stale(h, STALE_COUNT)) return rc;
     HIP_TRY(h, hipStreamSynchronize(s));
-    drop_wcsph_graphs(h);                                            // (they carry the old count and grids as launch arguments)
     // The run diagnostics (section 6i) need nothing here: their launches take the live count of the moment as an argument and keep no state about
     // particles -- a recording goes on, its next row counts the new n
     return SPH_OK;

@@ -42,44 +42,42 @@ static int geometry_commit(SphHandle *h, const char *call, std::vector<float> &p
     if (h->rstream) HIP_TRY(h, hipStreamSynchronize(h->rstream));
     // Loads on walls (section 6m): the selection is kept by id -- a removed group leaves it, the impulses of the others go on.  The measured set of
     // the new wall set is built here, into memory of its own, before anything of the handle changes (a refusal leaves the selection as it was) ...
-    WlBuild wl_next;
+    SphHandle::WlMem wl_next;
+    std::vector<SphHandle::WlGroup> wl_next_groups;
     std::vector<int> wl_ids;
     for (const auto &sel : h->wl_groups)
         for (size_t k = 0; k <= groups.size(); ++k)
             if (k == groups.size() ? sel.id == 0 : groups[k].id == sel.id) { wl_ids.push_back(sel.id); break; }
     if (!wl_ids.empty())
-        if (int rc = wl_prepare(h, call, wl_ids, sorted, order, Nb, groups, true, &wl_next)) return rc;
+        if (int rc = wl_prepare(h, call, wl_ids, sorted, order, Nb, groups, true, &wl_next, &wl_next_groups)) return rc;
     // The device copy never shrinks: the sweeps fetch a group of list entries past a row's end and rely on stale entries being valid indices
     // (walk_list, sph_kernels.h).  Memory of the feature's own; the arena's WP is simply no longer pointed to
     // Every edit uploads into a fresh allocation through local pointers; the handle's fields change only behind the final wait, so a HIP error on
     // the way leaves the handle as it was.  Edits are rare: an allocation per edit costs nothing that matters
-    char *mem = nullptr;
+    DevMem mem;
     const size_t cap = std::max(h->geo_cap, (size_t)Nb + (size_t)Nb / 2);
-    const size_t wp_bytes = (sizeof(float4) * (cap + 64) + 255) / 256 * 256, wg_bytes = (sizeof(int) * (cap + 64) + 255) / 256 * 256,
-                 bytes = wp_bytes + wg_bytes + sizeof(int) * (size_t)c.stride;
-    HIP_TRY(h, hipMalloc((void **)&mem, bytes));
-    if (hipMemsetAsync(mem, 0, bytes, s) != hipSuccess) { (void)hipFree(mem); return fail(h, SPH_E_HIP, "%s: hipMemsetAsync failed", call); }
-    float4 *wp_dev = (float4 *)mem;
-    int *wgroup_dev = (int *)(mem + wp_bytes), *marked_dev = (int *)(mem + wp_bytes + wg_bytes);
+    float4 *wp_dev = nullptr;
+    int *wgroup_dev = nullptr, *marked_dev = nullptr;
+    mem.want(&wp_dev, cap + 64);
+    mem.want(&wgroup_dev, cap + 64);
+    mem.want(&marked_dev, (size_t)c.stride);
+    HIP_TRY(h, mem.commit(s));
     hipError_t e = hipMemcpyAsync(wp_dev, sorted.data(), sizeof(float4) * (size_t)Nb, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(wgroup_dev, wgroup.data(), sizeof(int) * (size_t)Nb, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {
-        (void)hipFree(mem);
-        return fail(h, SPH_E_HIP, "%s: upload of the wall tables: %s", call, hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(h, SPH_E_HIP, "%s: upload of the wall tables: %s", call, hipGetErrorString(e));
     // from here on the handle changes: the cell starts (arena memory, read together with WP), the wall lists, the pointers
     HIP_TRY(h, hipMemcpyAsync(h->wcell_start, wcell_start.data(), sizeof(int) * ((size_t)c.C + 1), hipMemcpyHostToDevice, s));
     // ... and the wall lists are zeroed once, as the freeze zeroes the fluid lists (sph_rigid_set_active): index 0 is valid in every list format
     const void *lists[] = {h->nlb};
     if (int rc = dzero(h, lists, 1)) return rc;
-    if (h->verlet) {              // the Verlet lists of the last build hold the old wall entries: the next step builds them
-        h->ds_host->moved = 1;
-        HIP_TRY(h, hipMemcpyAsync(&h->ds->moved, &h->ds_host->moved, sizeof(int), hipMemcpyHostToDevice, s));
-    }
+    // what the last list build derived from the old wall set: the lists (Verlet ones included) and counts, the density, the derived fields; the
+    // captured wcsph step pairs hold WP, wcell_start and the kernels' arguments of their capture.  The density loop's working-tiles-first order is a
+    // launch order only; it starts afresh as on a new handle.  Fluid state, clock, dt, warm start, pcisph's delta, gravity, scalar, recording and
+    // the body are not touched
+    if (int rc = mark_stale(h, STALE_WALL_SET)) return rc;
     HIP_TRY(h, hipStreamSynchronize(s));
-    if (h->geo_mem) (void)hipFree(h->geo_mem);
-    h->geo_mem = mem; h->geo_cap = cap;
+    h->own.geometry = std::move(mem); h->geo_cap = cap;
     h->WP = wp_dev; h->geo_wgroup = wgroup_dev; h->geo_marked = marked_dev;
     h->Nb = Nb;
     h->geo_groups.swap(groups);
@@ -88,16 +86,8 @@ static int geometry_commit(SphHandle *h, const char *call, std::vector<float> &p
     h->wall_vol_host.swap(vol);
     h->wall_order_host.swap(order);
     // ... and becomes the handle's here; the last step's forces read zero until a step has run.  Nobody left of the selection: measuring is off
-    if (!wl_ids.empty()) wl_adopt(h, &wl_next);
+    if (!wl_ids.empty()) wl_adopt(h, &wl_next, &wl_next_groups);
     else h->wl_groups.clear();
-    // what the last list build derived from the old wall set: the lists and counts, the density, the derived fields; the captured wcsph step pairs
-    // hold WP, wcell_start and the kernels' arguments of their capture.  The density loop's working-tiles-first order is a launch order only; it
-    // starts afresh as on a new handle.  Fluid state, clock, dt, warm start, pcisph's delta, gravity, scalar, recording and the body are not touched
-    h->nl_valid = false;
-    h->density_valid = false;
-    h->derived_valid = false;
-    h->dens_sparse = false;
-    drop_wcsph_graphs(h);
     return SPH_OK;
 }
 
@@ -184,13 +174,7 @@ int geometry_wall_counts(SphHandle *h, int32_t *counts, size_t n)
     if (!counts) return fail(h, SPH_E_INVALID, "sph_geometry_wall_counts: null argument");
     if (n != (size_t)h->N) return fail(h, SPH_E_INVALID, "sph_geometry_wall_counts: the handle holds %d particles, got room for %zu", h->N, n);
     HIP_TRY(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    {
-        ProfScope ps(h, K_TRANSFER);
-        hipLaunchKernelGGL(k_unsort_wall_count, grid_for(h->N), dim3(kBlock), 0, s, h->N, (const int *)h->cnt, (const int *)h->id[h->icur], (int *)h->staging);
-    }
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(counts, h->staging, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return SPH_OK;
+    return fetch_api_order(h, [&] {
+        hipLaunchKernelGGL(k_unsort_wall_count, grid_for(h->N), dim3(kBlock), 0, h->stream, h->N, (const int *)h->cnt, (const int *)h->id[h->icur], (int *)h->staging);
+    }, h->staging, counts, sizeof(int32_t) * n);
 }

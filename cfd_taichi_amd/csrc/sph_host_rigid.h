@@ -217,7 +217,7 @@ int build_rigid(SphHandle *h, const SphRigid *rg)
     if (stg_need > 3 * std::max((size_t)h->c.stride, (size_t)h->Nb))
         if ((rc = dalloc(h, &h->staging, stg_need))) return rc;      // the fluid arena's staging buffer is too small for this body
     if ((rc = dcommit(h))) return rc;
-    HIP_TRY(h, hipHostMalloc((void **)&h->rred_host, sizeof(RigidReduce) * (kRigidParts + 1), hipHostMallocDefault));
+    HIP_TRY(h, h->own.rred.commit(&h->rred_host, kRigidParts + 1));
     std::vector<float4> rp4(nr);
     for (int i = 0; i < Nr; ++i) rp4[i] = make_float4(rpos[3 * (size_t)i], rpos[3 * (size_t)i + 1], rpos[3 * (size_t)i + 2], h->rvol_host[i]);
     HIP_TRY(h, hipMemcpyAsync(h->RPos, rp4.data(), sizeof(float4) * nr, hipMemcpyHostToDevice, h->stream));
@@ -355,7 +355,7 @@ int rigid_step_prescribed(SphHandle *h, float dt)
         for (int a = 0; a < 3; ++a) { h->centroid[a] += disp[a]; h->r_omega[a] = h->rs_omega[a]; }
     }
     HIP_TRY(h, hipGetLastError());
-    h->nl_valid = false;
+    mark_stale(h, STALE_BODY_MOVED);
     return SPH_OK;
 }
 
@@ -458,6 +458,6 @@ int rigid_step(SphHandle *h, float dt_next)
     if (h->Nv > 0) hipLaunchKernelGGL(k_rigid_translate, gv, b, 0, s, h->Nv, (float4 *)nullptr, h->rvert, disp[0], disp[1], disp[2], (float *)nullptr);
     for (int a = 0; a < 3; ++a) h->centroid[a] += disp[a];                                  // :104
     HIP_TRY(h, hipGetLastError());
-    h->nl_valid = false;
+    mark_stale(h, STALE_BODY_MOVED);
     return SPH_OK;
 }

@@ -65,12 +65,10 @@ int scalar_enable(SphHandle *h, double diffusivity, double beta, double t_ref)
     if (fresh) {
         // memory of its own (not the handle's arena), 24 B per particle of the capacity: XT[stride] float4, rate[stride], T[ncap]
         const size_t st = (size_t)h->c.stride;
-        float *base = nullptr;
-        HIP_TRY(h, hipMalloc((void **)&base, sizeof(float) * st * 6));
-        HIP_TRY(h, hipMemsetAsync(base, 0, sizeof(float) * st * 6, h->stream));
-        h->sc_XT = (float4 *)base;
-        h->sc_rate = base + 4 * st;
-        h->sc_T = base + 5 * st;
+        h->own.scalar.want(&h->sc_XT, st);
+        h->own.scalar.want(&h->sc_rate, st);
+        h->own.scalar.want(&h->sc_T, st);
+        HIP_TRY(h, h->own.scalar.commit(h->stream));
     }
     h->sc_D = diffusivity; h->sc_beta = (float)beta; h->sc_ref = (float)t_ref;
     if (fresh) {
@@ -78,7 +76,7 @@ int scalar_enable(SphHandle *h, double diffusivity, double beta, double t_ref)
         if (int rc = scalar_fill(h, 0, h->ncap, (float)t_ref)) return rc;
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    drop_wcsph_graphs(h);                                            // (they hold or lack the three launches and carry the parameters as arguments)
+    mark_stale(h, STALE_LAUNCH_ARGS);                                // (the captured step pairs hold or lack the three launches and carry the parameters as arguments)
     return SPH_OK;
 }
 
@@ -88,8 +86,8 @@ int scalar_disable(SphHandle *h)
     if (!scalar_on(h)) return SPH_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    drop_wcsph_graphs(h);
-    HIP_TRY(h, hipFree(h->sc_XT));
+    mark_stale(h, STALE_LAUNCH_ARGS);
+    h->own.scalar.release();
     h->sc_XT = nullptr; h->sc_rate = h->sc_T = nullptr;
     return SPH_OK;
 }
@@ -129,14 +127,9 @@ int scalar_rate_fetch(SphHandle *h, float *out, size_t n)
     if (!h->nl_valid)
         if (int rc = sph_build_neighbors(h)) return rc;
     launch_scalar_rate(h);
-    {
-        ProfScope ps(h, K_TRANSFER);
+    return fetch_api_order(h, [&] {
         hipLaunchKernelGGL(k_scalar_unsort, grid_for(h->c.n), dim3(kBlock), 0, h->stream, h->c.n, (const float *)h->sc_rate, (const int *)h->id[h->icur], h->staging);
-    }
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(out, h->staging, sizeof(float) * n, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return SPH_OK;
+    }, h->staging, out, sizeof(float) * n);
 }
 
 // sph_remove_in_box / sph_geometry_carve, beside k_remove_compact and with its arguments (the roles of before the flip): the survivors' values under their new ids.

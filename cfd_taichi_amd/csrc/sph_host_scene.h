@@ -594,41 +594,28 @@ inline bool is_pressure_solver(const SphHandle *h) { return h->cfg.solver == SPH
 // solvers with a per-particle scalar that must follow the particle through the sort: dfsph warm_start_k, iisph p_past
 inline bool carries_scalar(const SphHandle *h) { return h->cfg.solver == SPH_SOLVER_DFSPH || h->cfg.solver == SPH_SOLVER_IISPH; }
 
-// Device memory of a handle comes from ONE allocation per build phase (fluid state, rigid body): dalloc() records a request,
+// Device memory of a handle comes from ONE allocation per build phase (fluid state, rigid body), a DevMem each: dalloc() records a request,
 // dcommit() sizes the arena, allocates and zeroes it and hands out the pointers.  Identical handles have identical layouts,
-// arrays of 2 MiB and more start on a 2 MiB boundary, and closing a handle is one hipFree per phase.
+// arrays of 2 MiB and more start on a 2 MiB boundary, and closing a handle frees one allocation per phase.
 template <class T>
 int dalloc(SphHandle *h, T **p, size_t count)
 {
-    *p = nullptr;
-    h->plan.push_back({(void **)p, sizeof(T) * (count > 0 ? count : 1)});
+    h->own.arena_next.want(p, count);
     return SPH_OK;
 }
 
 int dcommit(SphHandle *h)
 {
-    const size_t big = (size_t)2 << 20;
-    std::vector<size_t> off(h->plan.size());
-    size_t cur = 0;
-    for (size_t k = 0; k < h->plan.size(); ++k) {
-        const size_t bytes = h->plan[k].second, align = bytes >= big ? big : 256;
-        cur = (cur + align - 1) / align * align;
-        off[k] = cur;
-        cur += bytes;
-    }
-    char *base = nullptr;
-    HIP_TRY(h, hipMalloc((void **)&base, cur > 0 ? cur : 1));
-    h->arenas.push_back(base);
-    for (size_t k = 0; k < h->plan.size(); ++k) { *h->plan[k].first = base + off[k]; h->blocks.push_back({base + off[k], h->plan[k].second}); }
-    HIP_TRY(h, hipMemsetAsync(base, 0, cur, h->stream));
-    h->plan.clear();
+    HIP_TRY(h, h->own.arena_next.commit(h->stream));
+    h->own.arenas.push_back(std::move(h->own.arena_next));
+    h->own.arena_next = DevMem();
     return SPH_OK;
 }
 
 // bytes of a dalloc'd array (0: not one)
 inline size_t dalloc_bytes(const SphHandle *h, const void *p)
 {
-    for (const auto &b : h->blocks) if (b.first == p) return b.second;
+    for (const auto &a : h->own.arenas) if (const size_t bytes = a.bytes_of(p)) return bytes;
     return 0;
 }
 // zero whole dalloc'd arrays on the handle's stream (a null or foreign pointer is skipped)
@@ -637,6 +624,89 @@ int dzero(SphHandle *h, const void *const *arrays, size_t count)
     for (size_t k = 0; k < count; ++k)
         if (const size_t bytes = arrays[k] ? dalloc_bytes(h, arrays[k]) : 0) HIP_TRY(h, hipMemsetAsync(const_cast<void *>(arrays[k]), 0, bytes, h->stream));
     return SPH_OK;
+}
+
+// ---- what an edit between steps makes stale ----------------------------------------------------------------------------
+// A call site names WHAT CHANGED; mark_stale says what that takes down.  It is the one writer of nl_valid / density_valid / derived_valid, of
+// lists_predate_flag and dens_sparse outside the solver loops, of the Verlet `moved` word outside the kernels, and the one caller of
+// drop_wcsph_graphs.  The rule: lists down => densities down => derived fields down (the one exception is STALE_BODY_MOVED, below).
+//
+//   kind                    lists  dens  derived  predate  dens_sparse  moved          graphs    who
+//   STALE_FIELD             down   down  down     -        -            upload(verlet) -         sph_upload
+//   STALE_WALL_SET          down   down  down     -        false        upload(verlet) dropped   geometry_commit
+//   STALE_BODY_FLAG         down   down  down     true     false        -              -         sph_rigid_set_active
+//   STALE_BODY_DATA         down   down  down     -        -            -              -         sph_rigid_init_data
+//   STALE_BODY_MOVED        down   -     -        -        -            -              -         the two body integrators (sph_host_rigid.h)
+//   STALE_COUNT             down   down  down     -        false        upload(verlet) dropped   fluid_count_changed, behind forget_step_history
+//   STALE_HISTORY           down   down  down     false    false        -              -         forget_step_history's share
+//   STALE_NEW_BLOCK         down   down  down     -        -            mirror only    -         alloc_device, slab_state_commit: the caller uploads the whole block
+//   STALE_LAUNCH_ARGS       -      -     -        -        -            -              dropped   delta_time, gravity / forcing, a solver attribute, the adaptive
+//                                                                                                step, recording, the scalar's and the measured set's nodes
+//   STALE_STEP_RAN          down   down  down     -        -            -              -         step_end, a replayed wcsph step pair
+//   STALE_LISTS_BUILT       UP     down  down     false    -            -              -         stage_sort_and_lists
+//   STALE_DENSITY           -      down  down     -        -            -              -         sph_tune_time(3): the sort ran under the densities
+//   STALE_DENSITY_COMPUTED  -      UP    -        -        -            -              -         stage_density
+//   STALE_DERIVED_COMPUTED  -      -     UP       -        -            -              -         derived_fetch
+//
+// The differences are kept as they were found, none is normalised: an upload or a new body datum leaves dens_sparse alone while a new wall set or
+// body flag resets it; only the flag edit raises lists_predate_flag, only a list build and the history reset lower it; a body step takes the lists
+// down ALONE (the densities of a coupled step were computed before it and stay readable: derived_fetch therefore re-tests all three flags); slab
+// handles and handles with a body never capture graphs, so their kinds drop none.  upload(verlet): on a Verlet handle the device's word follows on
+// the handle's stream, no wait -- the only part that can fail.
+enum StaleKind {
+    STALE_FIELD, STALE_WALL_SET, STALE_BODY_FLAG, STALE_BODY_DATA, STALE_BODY_MOVED, STALE_COUNT, STALE_HISTORY, STALE_NEW_BLOCK, STALE_LAUNCH_ARGS,
+    STALE_STEP_RAN, STALE_LISTS_BUILT, STALE_DENSITY, STALE_DENSITY_COMPUTED, STALE_DERIVED_COMPUTED
+};
+
+// the captured wcsph step pairs hold the count, the grids, delta_time, the k_accel_eval node and the two nodes of the adaptive time step (or their
+// absence) as they were at capture
+inline void drop_wcsph_graphs(SphHandle *h)
+{
+    for (int k = 0; k < 8; ++k)
+        if (h->wcsph_graph[k]) { (void)hipGraphExecDestroy(h->wcsph_graph[k]); h->wcsph_graph[k] = nullptr; }
+}
+
+int mark_stale(SphHandle *h, StaleKind what)
+{
+    // what the event is about: 0 the lists, 1 the densities, 2 the derived fields, 3 none of them
+    int from = 0;
+    switch (what) {
+    case STALE_LISTS_BUILT: h->nl_valid = true; from = 1; break;
+    case STALE_DENSITY: from = 1; break;
+    case STALE_DENSITY_COMPUTED: h->density_valid = true; from = 3; break;
+    case STALE_DERIVED_COMPUTED: h->derived_valid = true; from = 3; break;
+    case STALE_LAUNCH_ARGS: from = 3; break;
+    default: break;
+    }
+    // the cascade, once: what is down takes down what was computed from it (a body step: the lists alone)
+    const bool alone = what == STALE_BODY_MOVED;
+    if (from <= 0) h->nl_valid = false;
+    if (from <= 1 && !alone) h->density_valid = false;
+    if (from <= 2 && !alone) h->derived_valid = false;
+    if (what == STALE_BODY_FLAG) h->lists_predate_flag = true;
+    if (what == STALE_HISTORY || what == STALE_LISTS_BUILT) h->lists_predate_flag = false;
+    if (what == STALE_WALL_SET || what == STALE_BODY_FLAG || what == STALE_COUNT || what == STALE_HISTORY) h->dens_sparse = false;
+    if (what == STALE_WALL_SET || what == STALE_COUNT || what == STALE_LAUNCH_ARGS) drop_wcsph_graphs(h);
+    // Verlet lists: the device decides from DevScalars.moved whether the next step rebuilds them
+    const bool upload = h->verlet && (what == STALE_FIELD || what == STALE_WALL_SET || what == STALE_COUNT);
+    if (upload || what == STALE_NEW_BLOCK) h->ds_host->moved = 1;
+    if (upload) HIP_TRY(h, hipMemcpyAsync(&h->ds->moved, &h->ds_host->moved, sizeof(int), hipMemcpyHostToDevice, h->stream));
+    return SPH_OK;
+}
+
+// Forget what the steps so far left behind that a fresh handle of the same particles would not have: the host's flags about lists, density, the density
+// loop's launch order and stamps, pbf's fields, and the device arrays that hold stamps and per-tile flags of earlier sweeps (the stamps start at 0
+// again, so what was stamped must go with them; staged dfsph handles only, a few ints per tile).  "A handle's history must not show in its bits":
+// sph_slab_set_state (slab_state_commit) and the calls that change the particle count (fluid_count_changed) both end here -- a new flag of this kind,
+// or a new array that carries stamps or per-tile flags across steps, is added HERE and nowhere else.  Enqueues on the handle's stream; no wait
+int forget_step_history(SphHandle *h)
+{
+    mark_stale(h, STALE_HISTORY);
+    h->flow_stamp = h->flow_last = 0; h->flow_d6 = kNoFlow;
+    h->dens_first = true; h->pending_div = kNoRide;
+    h->pbf_fields = false;                    // pbf_lambda / delta_pos: "before the first step" again
+    const void *stamped[] = {h->wave_dirty, h->changed8, h->dens_hot, h->dens_order, h->tile_nbr, h->need6, h->need7, h->tile_nz, h->worked6, h->worked7, h->dens_bcast};
+    return dzero(h, stamped, sizeof(stamped) / sizeof(stamped[0]));
 }
 
 inline uint64_t morton_spread(uint64_t v)          // 21 bits -> every third bit
@@ -773,7 +843,7 @@ int alloc_device(SphHandle *h, const HostScene &sc)
             if ((rc = dalloc(h, &h->edge_list[k], n))) return rc;
         if ((rc = dalloc(h, &h->counters, kSlabCounters))) return rc;
         if ((rc = dalloc(h, &h->class_cnt, (size_t)kSlabCounted * (n / kBlock + 2)))) return rc;
-        HIP_TRY(h, hipHostMalloc((void **)&h->counters_host, sizeof(int) * kSlabCounters, hipHostMallocDefault));
+        HIP_TRY(h, h->own.counters.commit(&h->counters_host, kSlabCounters));
         // edge / interior split of the residual sweeps (dfsph, two ghost columns): tile flags and the edge-first tile order
         h->overlap = h->geom.layers == 2 && h->cfg.slab_overlap != 1;
         if (h->overlap) {
@@ -789,7 +859,7 @@ int alloc_device(SphHandle *h, const HostScene &sc)
             HIP_TRY(h, hipEventCreateWithFlags(&h->ev_dec, hipEventDisableTiming));
         }
         if ((rc = dalloc(h, &h->col_hist, (size_t)c.gx))) return rc;
-        HIP_TRY(h, hipHostMalloc((void **)&h->col_hist_host, sizeof(int) * (size_t)c.gx, hipHostMallocDefault));
+        HIP_TRY(h, h->own.col_hist.commit(&h->col_hist_host, (size_t)c.gx));
     }
     // one GPU, dfsph: the divergence correction runs ahead of its loop decision, which rides in the same launch (fin_ride_block): what it overwrites
     if (!h->slab && is_dfsph(h)) {
@@ -797,15 +867,14 @@ int alloc_device(SphHandle *h, const HostScene &sc)
         if ((rc = dalloc(h, &h->spec_w, n))) return rc;
     }
     if ((rc = dalloc(h, &h->ds, 1))) return rc;
-    HIP_TRY(h, hipHostMalloc((void **)&h->ds_host, sizeof(DevScalars), hipHostMallocDefault));
+    HIP_TRY(h, h->own.ds.commit(&h->ds_host, 1));
     // (coherent / fine-grained asked for by name: read_scalars_fast spins on a word the device writes while the stream is still busy, and
     // HIP_HOST_COHERENT=0 in the environment would otherwise make that word visible only after the stream has drained -- ADVICE r5)
-    if (hipHostMalloc((void **)&h->pub_host, sizeof(DevScalarsPub), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess) {
+    if (h->own.pub.commit(&h->pub_host, 1, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess) {
         memset(h->pub_host, 0, sizeof(DevScalarsPub));
-        if (hipHostGetDevicePointer((void **)&h->pub_dev, h->pub_host, 0) != hipSuccess) { (void)hipHostFree(h->pub_host); h->pub_host = nullptr; h->pub_dev = nullptr; }
+        if (hipHostGetDevicePointer((void **)&h->pub_dev, h->pub_host, 0) != hipSuccess) { h->own.pub.release(); h->pub_host = nullptr; h->pub_dev = nullptr; }
     } else {
         (void)hipGetLastError();
-        h->pub_host = nullptr;
     }
     size_t stg = 3 * std::max(n, (size_t)h->Nb);
     if ((rc = dalloc(h, &h->staging, stg))) return rc;
@@ -839,7 +908,7 @@ int alloc_device(SphHandle *h, const HostScene &sc)
     h->ds_host->dt = (float)h->cfg.delta_time;                       // solver_base.py:16
     h->ds_host->dt2 = h->ds_host->dt * h->ds_host->dt;               // dfsph_solver.py:20
     h->ds_host->ps_dt = 0.f;                                         // ParticleSystem.py:37
-    h->ds_host->moved = 1;                                           // Verlet handles: the first step builds the lists
+    mark_stale(h, STALE_NEW_BLOCK);                                  // Verlet handles: the first step builds the lists (moved = 1 in the block below)
     loop_params(h, h->ds_host);
     // the acceleration vector: the three floats the reference forms, gravity * (0, -1, 0), in f32 as its kernels do   solver_base.py:131-133
     h->frc = DevScalars::Forcing{};
@@ -912,14 +981,6 @@ inline void step_head(SphHandle *h)
 inline StepDt step_dt_arg(const SphHandle *h) { return StepDt{h->dt_wcsph, h->step_adaptive ? h->ds : nullptr}; }
 inline StepDt step_delta_arg(const SphHandle *h) { return StepDt{h->pci_delta, h->step_adaptive ? h->ds : nullptr}; }
 
-// the captured wcsph step pairs hold the count, the grids, delta_time, the k_accel_eval node and the two nodes of the adaptive time step (or their
-// absence) as they were at capture
-inline void drop_wcsph_graphs(SphHandle *h)
-{
-    for (int k = 0; k < 8; ++k)
-        if (h->wcsph_graph[k]) { (void)hipGraphExecDestroy(h->wcsph_graph[k]); h->wcsph_graph[k] = nullptr; }
-}
-
 // sph_set_gravity / sph_set_forcing / a written SPH_S_TIME, between steps: h->frc (validated by the caller) goes to the device, the vector is
 // formed at once for the current clock -- by the kernel the steps use, so the bits are the step's -- and read back.  The captured wcsph step pairs
 // hold or lack the k_accel_eval node: they are dropped (the vector itself is device memory and would reach a replay anyway).
@@ -932,7 +993,7 @@ int forcing_commit(SphHandle *h)
         HIP_TRY(h, hipMemcpyAsync(h->frc.accel, h->ds->frc.accel, sizeof(h->frc.accel), hipMemcpyDeviceToHost, h->stream));
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    drop_wcsph_graphs(h);
+    mark_stale(h, STALE_LAUNCH_ARGS);
     return SPH_OK;
 }
 
@@ -951,21 +1012,6 @@ int write_delta_time(SphHandle *h, double value)
         HIP_TRY(h, hipMemcpyAsync(h->ds, h->ds_host, offsetof(DevScalars, ps_dt), hipMemcpyHostToDevice, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
     }
-    drop_wcsph_graphs(h);                                            // (they carry the old delta_time as a launch argument)
+    mark_stale(h, STALE_LAUNCH_ARGS);                                // (the captured step pairs carry the old delta_time as a launch argument)
     return SPH_OK;
-}
-
-// Forget what the steps so far left behind that a fresh handle of the same particles would not have: the host's flags about lists, density, the density
-// loop's launch order and stamps, pbf's fields, and the device arrays that hold stamps and per-tile flags of earlier sweeps (the stamps start at 0
-// again, so what was stamped must go with them; staged dfsph handles only, a few ints per tile).  "A handle's history must not show in its bits":
-// sph_slab_set_state (slab_state_commit) and the calls that change the particle count (fluid_count_changed) both end here -- a new flag of this kind,
-// or a new array that carries stamps or per-tile flags across steps, is added HERE and nowhere else.  Enqueues on the handle's stream; no wait
-int forget_step_history(SphHandle *h)
-{
-    h->nl_valid = false; h->density_valid = false; h->derived_valid = false; h->lists_predate_flag = false;
-    h->flow_stamp = h->flow_last = 0; h->flow_d6 = kNoFlow;
-    h->dens_sparse = false; h->dens_first = true; h->pending_div = kNoRide;
-    h->pbf_fields = false;                    // pbf_lambda / delta_pos: "before the first step" again
-    const void *stamped[] = {h->wave_dirty, h->changed8, h->dens_hot, h->dens_order, h->tile_nbr, h->need6, h->need7, h->tile_nz, h->worked6, h->worked7, h->dens_bcast};
-    return dzero(h, stamped, sizeof(stamped) / sizeof(stamped[0]));
 }

@@ -439,11 +439,10 @@ int slab_exchange_resid(SphHandle *h, bool dens, float *val, bool overlap, bool 
 // The state streams through a buffer of its own, `chunk` particles at a time (28 bytes each): a slab's arena is sized for its share, not for the scene.
 // ---------------------------------------------------------------------------------------------
 struct StateBuf {
-    char *base = nullptr;
+    DevMem mem;                                  // the call's own, gone with it
     float *pos = nullptr, *vel = nullptr, *sca = nullptr;
     int *blk = nullptr, *words = nullptr;        // words[0]: particles pass B has placed, words[1]: pass A's refusal bits
     int chunk = 0;
-    ~StateBuf() { if (base) (void)hipFree(base); }
 };
 constexpr int kStateChunk = 1 << 20;
 
@@ -454,11 +453,8 @@ int state_buf_alloc(SphHandle *h, StateBuf &b)
     const long long want = e ? std::min<long long>(std::max(atoll(e), 1LL), kStateChunk) : kStateChunk;
     b.chunk = (int)((std::min<long long>(want, std::max(h->N, 1)) + kBlock - 1) / kBlock * kBlock);
     const size_t n = (size_t)b.chunk, nblk = n / kBlock + 1;
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-    const size_t o_vel = up(12 * n), o_sca = o_vel + up(12 * n), o_blk = o_sca + up(4 * n), o_words = o_blk + up(4 * nblk), total = o_words + 256;
-    HIP_TRY(h, hipMalloc((void **)&b.base, total));
-    b.pos = (float *)b.base; b.vel = (float *)(b.base + o_vel); b.sca = (float *)(b.base + o_sca);
-    b.blk = (int *)(b.base + o_blk); b.words = (int *)(b.base + o_words);
+    b.mem.want(&b.pos, 3 * n); b.mem.want(&b.vel, 3 * n); b.mem.want(&b.sca, n); b.mem.want(&b.blk, nblk); b.mem.want(&b.words, 64);
+    HIP_TRY(h, b.mem.commit(h->stream, false));      // (every chunk is written before it is read: only the two words start at zero)
     HIP_TRY(h, hipMemsetAsync(b.words, 0, 256, h->stream));
     return SPH_OK;
 }
@@ -539,7 +535,7 @@ int slab_state_commit(SphHandle *h, const float *pos, const float *vel, const fl
     memset(h->ds_host, 0, sizeof(DevScalars));
     h->ds_host->dt = dt; h->ds_host->dt2 = dt2; h->ds_host->ps_dt = ps_dt;
     h->ds_host->sim_time = sim_time; h->ds_host->frc = frc;
-    h->ds_host->moved = 1;
+    mark_stale(h, STALE_NEW_BLOCK);                           // (moved = 1 in the block uploaded below)
     loop_params(h, h->ds_host);
     HIP_TRY(h, hipMemcpyAsync(h->ds, h->ds_host, sizeof(DevScalars), hipMemcpyHostToDevice, s));
     HIP_TRY(h, hipStreamSynchronize(s));

@@ -15,24 +15,18 @@ inline WlView wl_view(const SphHandle *h)
     return WlView{m.nm, (int)h->wl_groups.size(), m.MP, m.force, m.perm, m.seg};
 }
 
-// a set that is built but not yet the handle's: freed unless adopted
-struct WlBuild {
-    SphHandle::WlMem m;
-    std::vector<SphHandle::WlGroup> groups;
-    ~WlBuild() { if (m.mem) (void)hipFree(m.mem); }
-};
-
 // The measured set of the groups `ids` (selection order; every id is 0 or a group of `geo`) over the wall set `sorted` / `order` of Nb samples, into
 // fresh memory: the lists zeroed (walk_list fetches past a row's end and relies on stale entries being valid indices), the totals zeroed, the
 // accumulators zero or -- carry -- those the handle's present selection holds for the same id.  Nothing of the handle changes.  The handle's stream
 // is idle (the callers have waited)
 int wl_prepare(SphHandle *h, const char *call, const std::vector<int> &ids, const std::vector<float4> &sorted, const std::vector<int> &order, int Nb,
-               const std::vector<SphHandle::GeoGroup> &geo, bool carry, WlBuild *out)
+               const std::vector<SphHandle::GeoGroup> &geo, bool carry, SphHandle::WlMem *out, std::vector<SphHandle::WlGroup> *out_groups)
 {
+    std::vector<SphHandle::WlGroup> &groups = *out_groups;
     const int ng = (int)ids.size();
     int box = Nb;
     for (const auto &g : geo) box -= g.count;
-    out->groups.clear();
+    groups.clear();
     for (int id : ids) {
         int first = id == 0 ? 0 : box, count = id == 0 ? box : 0;
         for (size_t k = 0; id != 0 && k < geo.size(); ++k) {
@@ -40,10 +34,10 @@ int wl_prepare(SphHandle *h, const char *call, const std::vector<int> &ids, cons
             first += geo[k].count;
         }
         if (count <= 0) return fail(h, SPH_E_INVALID, "%s: no live group %d", call, id);
-        out->groups.push_back({id, first, count});
+        groups.push_back({id, first, count});
     }
     std::vector<int> row_slot((size_t)Nb, -1);
-    for (int s = 0; s < ng; ++s) std::fill(row_slot.begin() + out->groups[(size_t)s].first, row_slot.begin() + out->groups[(size_t)s].first + out->groups[(size_t)s].count, s);
+    for (int s = 0; s < ng; ++s) std::fill(row_slot.begin() + groups[(size_t)s].first, row_slot.begin() + groups[(size_t)s].first + groups[(size_t)s].count, s);
     std::vector<float4> mp;
     std::vector<int> slot, local, seg((size_t)ng + 1, 0);
     for (int e = 0; e < Nb; ++e) {
@@ -51,7 +45,7 @@ int wl_prepare(SphHandle *h, const char *call, const std::vector<int> &ids, cons
         if (s < 0) continue;
         mp.push_back(sorted[(size_t)e]);
         slot.push_back(s);
-        local.push_back(row - out->groups[(size_t)s].first);
+        local.push_back(row - groups[(size_t)s].first);
         seg[(size_t)s + 1]++;
     }
     const int nm = (int)mp.size();
@@ -66,24 +60,17 @@ int wl_prepare(SphHandle *h, const char *call, const std::vector<int> &ids, cons
             for (size_t k = 0; k < h->wl_groups.size(); ++k)
                 if (h->wl_groups[k].id == ids[(size_t)s]) std::copy(old.begin() + (long)(k * kWlAcc), old.begin() + (long)((k + 1) * kWlAcc), acc.begin() + (long)((size_t)s * kWlAcc));
     }
-    // one allocation, every array on a 256-byte boundary
-    SphHandle::WlMem &m = out->m;
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 255) / 256 * 256; return o; };
+    // one allocation of the set's own, zeroed
+    SphHandle::WlMem &m = *out;
     const size_t n = (size_t)nm;
     m.nl_bytes = sizeof(uint32_t) * (n + 64) * (size_t)h->c.kpitch;
-    const size_t o_mp = take(sizeof(float4) * (n + 64)), o_nl = take(m.nl_bytes), o_cnt = take(sizeof(int) * n), o_ident = take(sizeof(int) * n),
-                 o_slot = take(sizeof(int) * n), o_local = take(sizeof(int) * n), o_perm = take(sizeof(int) * n), o_seg = take(sizeof(int) * ((size_t)ng + 1)),
-                 o_force = take(sizeof(float) * 3 * n), o_out = take(sizeof(float) * 3 * n), o_part = take(sizeof(double) * (size_t)ng * kWlParts * kWlRow),
-                 o_load = take(sizeof(double) * (size_t)ng * kWlRow), o_acc = take(sizeof(double) * (size_t)ng * kWlAcc);
-    HIP_TRY(h, hipMalloc((void **)&m.mem, at));
+    m.mem.want(&m.MP, n + 64); m.mem.want(&m.nl, (n + 64) * (size_t)h->c.kpitch);
+    m.mem.want(&m.cnt, n); m.mem.want(&m.ident, n); m.mem.want(&m.slot, n); m.mem.want(&m.local, n); m.mem.want(&m.perm, n); m.mem.want(&m.seg, (size_t)ng + 1);
+    m.mem.want(&m.force, 3 * n); m.mem.want(&m.out, 3 * n);
+    m.mem.want(&m.part, (size_t)ng * kWlParts * kWlRow); m.mem.want(&m.load, (size_t)ng * kWlRow); m.mem.want(&m.acc, (size_t)ng * kWlAcc);
     hipStream_t s = h->stream;
+    HIP_TRY(h, m.mem.commit(s));
     m.nm = nm;
-    m.MP = (float4 *)(m.mem + o_mp); m.nl = (uint32_t *)(m.mem + o_nl); m.cnt = (int *)(m.mem + o_cnt); m.ident = (int *)(m.mem + o_ident);
-    m.slot = (int *)(m.mem + o_slot); m.local = (int *)(m.mem + o_local); m.perm = (int *)(m.mem + o_perm); m.seg = (int *)(m.mem + o_seg);
-    m.force = (float *)(m.mem + o_force); m.out = (float *)(m.mem + o_out); m.part = (double *)(m.mem + o_part); m.load = (double *)(m.mem + o_load);
-    m.acc = (double *)(m.mem + o_acc);
-    HIP_TRY(h, hipMemsetAsync(m.mem, 0, at, s));
     HIP_TRY(h, hipMemcpyAsync(m.MP, mp.data(), sizeof(float4) * n, hipMemcpyHostToDevice, s));
     HIP_TRY(h, hipMemcpyAsync(m.ident, ident.data(), sizeof(int) * n, hipMemcpyHostToDevice, s));
     HIP_TRY(h, hipMemcpyAsync(m.slot, slot.data(), sizeof(int) * n, hipMemcpyHostToDevice, s));
@@ -97,13 +84,11 @@ int wl_prepare(SphHandle *h, const char *call, const std::vector<int> &ids, cons
 
 // the built set becomes the handle's (no HIP call that can fail).  The captured wcsph step pairs hold or lack the feature's nodes and the old
 // set's pointers: dropped, as sph_diag_record does
-void wl_adopt(SphHandle *h, WlBuild *b)
+void wl_adopt(SphHandle *h, SphHandle::WlMem *m, std::vector<SphHandle::WlGroup> *groups)
 {
-    if (h->wl.mem) (void)hipFree(h->wl.mem);
-    h->wl = b->m;
-    b->m.mem = nullptr;
-    h->wl_groups.swap(b->groups);
-    drop_wcsph_graphs(h);
+    h->wl = std::move(*m);
+    h->wl_groups.swap(*groups);
+    mark_stale(h, STALE_LAUNCH_ARGS);
 }
 
 // ---- the launches of a step (all enqueued like any launch: no host wait, nodes of a captured wcsph step pair) ---------------------------------
@@ -184,7 +169,7 @@ int wall_load_select(SphHandle *h, const int32_t *groups, size_t n)
     if (int rc = wl_refused(h, "sph_wall_load_select")) return rc;
     if (n == 0) {                        // off: the memory stays (nothing a step reads is freed), the steps launch what they launched without it
         h->wl_groups.clear();
-        drop_wcsph_graphs(h);
+        mark_stale(h, STALE_LAUNCH_ARGS);
         return SPH_OK;
     }
     if (!groups) return fail(h, SPH_E_INVALID, "sph_wall_load_select: null groups");
@@ -206,9 +191,10 @@ int wall_load_select(SphHandle *h, const int32_t *groups, size_t n)
         const size_t j = (size_t)order[(size_t)e];
         sorted[(size_t)e] = make_float4(h->wall_pos_host[3 * j], h->wall_pos_host[3 * j + 1], h->wall_pos_host[3 * j + 2], h->wall_vol_host[j]);
     }
-    WlBuild b;
-    if (int rc = wl_prepare(h, "sph_wall_load_select", ids, sorted, order, Nb, h->geo_groups, false, &b)) return rc;
-    wl_adopt(h, &b);
+    SphHandle::WlMem next;                  // (built but not yet the handle's: freed unless adopted)
+    std::vector<SphHandle::WlGroup> next_groups;
+    if (int rc = wl_prepare(h, "sph_wall_load_select", ids, sorted, order, Nb, h->geo_groups, false, &next, &next_groups)) return rc;
+    wl_adopt(h, &next, &next_groups);
     return SPH_OK;
 }
 
@@ -286,13 +272,8 @@ int wall_load_forces(SphHandle *h, int32_t group, float *xyz, size_t n_floats)
     const size_t want = 3 * (size_t)h->wl_groups[(size_t)slot].count;
     if (n_floats != want) return fail(h, SPH_E_INVALID, "sph_wall_load_forces: group %d has %d samples, got room for %zu floats", group, h->wl_groups[(size_t)slot].count, n_floats);
     HIP_TRY(h, hipSetDevice(h->device));
-    {
-        ProfScope ps(h, K_TRANSFER);
+    return fetch_api_order(h, [&] {
         hipLaunchKernelGGL(k_wl_unsort, grid_for(h->wl.nm), dim3(kBlock), 0, h->stream, h->wl.nm, slot, (const int *)h->wl.slot, (const int *)h->wl.local,
                            (const float *)h->wl.force, h->wl.out);
-    }
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(xyz, h->wl.out, sizeof(float) * want, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return SPH_OK;
+    }, h->wl.out, xyz, sizeof(float) * want);
 }

@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -74,6 +75,68 @@ const char *dev_env(std::string *record, const char *name)
     return e;
 }
 
+// Memory with an owner.  DevMem: a plan of (pointer, element count) requests, committed as ONE hipMalloc -- every array on a
+// 256-byte boundary, arrays of 2 MiB and more on a 2 MiB boundary, in the order of the requests -- zeroed on the caller's stream unless told not to,
+// freed with its owner, move-only.  A commit that fails sets no pointer and holds no memory.  The handle's arenas (one per build phase: dalloc /
+// dcommit, sph_host_scene.h), every feature's side memory and the self-tests' scratch are DevMems.  Releasing does not reach back into the pointers
+// it handed out: whoever releases a live feature's memory clears them (scalar_disable).
+struct DevFree { void operator()(void *p) const { (void)hipFree(p); } };
+struct PinnedFree { void operator()(void *p) const { (void)hipHostFree(p); } };
+struct DevMem {
+    std::unique_ptr<char, DevFree> base;                     // (move-only through it)
+    size_t bytes = 0;
+    std::vector<std::pair<void **, size_t>> plan;            // requests not yet committed
+    std::vector<std::pair<const void *, size_t>> blocks;     // every array of the allocation with its bytes
+    explicit operator bool() const { return (bool)base; }
+    void release() { base.reset(); bytes = 0; plan.clear(); blocks.clear(); }
+    template <class T>
+    void want(T **p, size_t count)
+    {
+        *p = nullptr;
+        plan.push_back({(void **)p, sizeof(T) * (count > 0 ? count : 1)});
+    }
+    hipError_t commit(hipStream_t stream, bool zero = true)
+    {
+        const size_t big = (size_t)2 << 20;
+        std::vector<size_t> off(plan.size());
+        size_t cur = 0;
+        for (size_t k = 0; k < plan.size(); ++k) {
+            const size_t align = plan[k].second >= big ? big : 256;
+            cur = (cur + align - 1) / align * align;
+            off[k] = cur;
+            cur += plan[k].second;
+        }
+        char *mem = nullptr;
+        hipError_t e = hipMalloc((void **)&mem, cur > 0 ? cur : 1);
+        if (e == hipSuccess && zero && (e = hipMemsetAsync(mem, 0, cur, stream)) != hipSuccess) (void)hipFree(mem);
+        if (e != hipSuccess) { plan.clear(); return e; }
+        base.reset(mem); bytes = cur; blocks.clear();
+        for (size_t k = 0; k < off.size(); ++k) { *plan[k].first = mem + off[k]; blocks.push_back({mem + off[k], plan[k].second}); }
+        plan.clear();
+        return hipSuccess;
+    }
+    size_t bytes_of(const void *p) const           // bytes of one of its arrays (0: not one)
+    {
+        for (const auto &b : blocks) if (b.first == p) return b.second;
+        return 0;
+    }
+};
+
+// ... and its pinned twin: one hipHostMalloc with the caller's flags, the pointer handed out as DevMem hands out its own (null after a failure)
+struct PinnedMem {
+    std::unique_ptr<void, PinnedFree> base;
+    void release() { base.reset(); }
+    template <class T>
+    hipError_t commit(T **p, size_t count, unsigned flags = hipHostMallocDefault)
+    {
+        void *mem = nullptr;
+        const hipError_t e = hipHostMalloc(&mem, sizeof(T) * (count > 0 ? count : 1), flags);
+        base.reset(e == hipSuccess ? mem : nullptr);
+        *p = (T *)base.get();
+        return e;
+    }
+};
+
 }  // namespace
 
 struct SphHandle {
@@ -132,9 +195,16 @@ struct SphHandle {
     int ntiles = 0;
     float4 *WP = nullptr;        // wall particles, cell-sorted: (x, y, z, V_b)
     int *wcell_start = nullptr;
-    std::vector<std::pair<void **, size_t>> plan;   // dalloc() requests not yet committed
-    std::vector<char *> arenas;                      // dcommit() allocations
-    std::vector<std::pair<const void *, size_t>> blocks;   // ... and every array in them with its bytes (dalloc_bytes)
+    // Everything the handle owns on the device or pinned on the host, but the measured wall set's memory, which travels with its view (wl.mem):
+    // sph_destroy lets go of it in one statement, a feature adds its owner HERE.  The pointers into these live beside what they serve, below
+    struct Owned {
+        DevMem arena_next;                           // dalloc() requests not yet committed
+        std::vector<DevMem> arenas;                  // dcommit() allocations, one per build phase: every dalloc'd array with its bytes (dalloc_bytes)
+        DevMem diag, diag_ring, diag_ctl;            // run diagnostics: the scratch of both uses, the ring, the device-resident counters
+        DevMem derived, scalar, geometry;            // sections 6j, 6k, 6l
+        DevMem comm, red, gath, cnt;                 // the transport's message buffers, reduction buffer, gathered triples and counts, where the library owns them
+        PinnedMem ds, pub, rred, cnt_host, red_host, counters, col_hist;
+    } own;
     int *tile_rank = nullptr;            // Consts.tile_rank
     // slab handles on the Morton curve keep the cell slots of THEIR columns only (slab_local_grid): the whole grid's tile ranks, and the slot count the
     // cell arrays were allocated for
@@ -187,8 +257,7 @@ struct SphHandle {
     int n_owned = 0, n_ghost = 0, n_dead = 0;
     bool comm_set = false;
     SphComm comm = {};
-    void *dsend[2] = {nullptr, nullptr}, *drecv[2] = {nullptr, nullptr};   // device-side message buffers
-    bool own_dev_comm = false;
+    void *dsend[2] = {nullptr, nullptr}, *drecv[2] = {nullptr, nullptr};   // device-side message buffers: the library's (own.comm) or the caller's (SphComm, on_host 0)
     int *dead = nullptr;
     // ordered edge lists, one per (side, direction): 0 ghost-left, 1 send-left, 2 send-right, 3 ghost-right.  With two ghost columns per side a
     // list holds the column next to the cut first (edge_n[k][0] entries), then the second one (edge_n[k][1]); edge_off[2 k + l] are the per-cell
@@ -228,7 +297,6 @@ struct SphHandle {
     bool opt_dens_push = true;
     bool opt_layer_generic = false;  // SPH_LAYER_GENERIC=1: k_layer_offsets in the form columns of more than 18 432 cells take (tests)
     bool opt_slab_check = false;     // SPH_SLAB_CHECK=1: the host's edge-column bookkeeping against the sorted arrays, every step (tests, soak runs)
-    bool own_red = false;
     int rebalance_every = 0, steps_since_rebalance = 0, n_recuts = 0;
     int *col_hist = nullptr, *col_hist_host = nullptr;
     int *counters = nullptr, *counters_host = nullptr;
@@ -296,13 +364,12 @@ struct SphHandle {
     float sc_beta = 0.f, sc_ref = 0.f, sc_inflow = 0.f;
 
     // static geometry: the wall set is the box samples (group 0, the first Nb0) and behind them every live group in order of
-    // addition.  geo_mem: memory of the feature's own, taken at the first sph_geometry_add and grown, never shrunk: WP of the edited set (h->WP
+    // addition.  own.geometry: memory of the feature's own, taken at the first sph_geometry_add and grown, never shrunk: WP of the edited set (h->WP
     // points into it from then on), wgroup (the group of every sample in sorted order) and the carve verdicts
     struct GeoGroup { int id, count; };
     std::vector<GeoGroup> geo_groups;
     int geo_next_id = 1;
-    char *geo_mem = nullptr;
-    size_t geo_cap = 0;                    // wall samples geo_mem has room for (+ 64 of padding, as the arena's WP)
+    size_t geo_cap = 0;                    // wall samples own.geometry has room for (+ 64 of padding, as the arena's WP)
     int *geo_wgroup = nullptr, *geo_marked = nullptr;
 
     // loads on walls and geometry.  wl_groups: the selection in the caller's order (first: the group's first row of the
@@ -311,7 +378,7 @@ struct SphHandle {
     struct WlGroup { int id, first, count; };
     std::vector<WlGroup> wl_groups;
     struct WlMem {
-        char *mem = nullptr;
+        DevMem mem;
         int nm = 0;                          // samples of the measured set
         size_t nl_bytes = 0;
         float4 *MP = nullptr;                // [nm + 64] (x, y, z, V_b) in the wall set's sorted order
@@ -507,11 +574,7 @@ int sph_rigid_set_active(SphHandle *h, int active)
     // what the last list build derived with the old flag: the fluid lists (tagged rigid entries or none), cnt / ncount, the rigid sort, the body's
     // lists (rnl / rcnt), the exact / relaxed tile split (tile_order) -- stage_sort_and_lists rebuilds all of it from the flag it finds.  The
     // density loop's working-tiles-first order (dens_order) is a launch order only; it starts afresh as on a new handle
-    h->nl_valid = false;
-    h->density_valid = false;
-    h->derived_valid = false;
-    h->lists_predate_flag = true;
-    h->dens_sparse = false;
+    mark_stale(h, STALE_BODY_FLAG);
     return SPH_OK;
 }
 
@@ -533,9 +596,7 @@ int sph_rigid_init_data(SphHandle *h)
     // the new volumes into RPos[i].w (a strided copy: the positions stay the device's); RPs takes them at the next sort of the samples
     HIP_TRY(h, hipMemcpy2DAsync(&h->RPos[0].w, sizeof(float4), h->rvol_host.data(), sizeof(float), sizeof(float), nr, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->nl_valid = false;
-    h->density_valid = false;
-    h->derived_valid = false;
+    mark_stale(h, STALE_BODY_DATA);
     return SPH_OK;
 }
 
@@ -685,26 +746,9 @@ void sph_destroy(SphHandle *h)
     for (auto &e : h->ev_pending) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     for (auto &e : h->ev_pool) (void)hipEventDestroy(e);
     for (int k = 0; k < 8; ++k) if (h->wcsph_graph[k]) (void)hipGraphExecDestroy(h->wcsph_graph[k]);
-    for (char *arena : h->arenas) (void)hipFree(arena);        // every dalloc'd array
-    if (h->diag_part) (void)hipFree(h->diag_part);
-    if (h->diag_ring) (void)hipFree(h->diag_ring);
-    if (h->diag_ctl) (void)hipFree(h->diag_ctl);
-    if (h->drv_vr) (void)hipFree(h->drv_vr);
-    if (h->sc_XT) (void)hipFree(h->sc_XT);
-    if (h->geo_mem) (void)hipFree(h->geo_mem);
-    if (h->wl.mem) (void)hipFree(h->wl.mem);
-    if (h->rred_host) (void)hipHostFree(h->rred_host);
-    if (h->own_dev_comm) { (void)hipFree(h->dsend[0]); (void)hipFree(h->dsend[1]); (void)hipFree(h->drecv[0]); (void)hipFree(h->drecv[1]); }
-    if (h->own_red) (void)hipFree(h->red_dev);
+    h->own = SphHandle::Owned();                               // every arena, side memory, message buffer and pinned buffer ...
+    h->wl.mem.release();                                       // ... and the measured wall set's, which travels with its view
     if (h->nccl && rccl().ok) (void)rccl().CommDestroy(h->nccl);
-    if (h->cnt_dev) (void)hipFree(h->cnt_dev);
-    if (h->cnt_host) (void)hipHostFree(h->cnt_host);
-    if (h->red_host) (void)hipHostFree(h->red_host);
-    if (h->gath_dev) (void)hipFree(h->gath_dev);
-    if (h->counters_host) (void)hipHostFree(h->counters_host);
-    if (h->col_hist_host) (void)hipHostFree(h->col_hist_host);
-    if (h->ds_host) (void)hipHostFree(h->ds_host);
-    if (h->pub_host) (void)hipHostFree(h->pub_host);
     if (h->ev_edge) (void)hipEventDestroy(h->ev_edge);
     if (h->ev_halo) (void)hipEventDestroy(h->ev_halo);
     if (h->xstream) { (void)hipStreamSynchronize(h->xstream); (void)hipStreamDestroy(h->xstream); }
@@ -744,14 +788,8 @@ int sph_upload(SphHandle *h, int species, int field, const float *host, size_t n
     ProfScope ps(h, K_TRANSFER);
     launch_sort_in(h, h->staging, f);
     HIP_TRY(h, hipGetLastError());
-    if (h->verlet) {              // new positions: the Verlet lists of the last build no longer apply
-        h->ds_host->moved = 1;
-        HIP_TRY(h, hipMemcpyAsync(&h->ds->moved, &h->ds_host->moved, sizeof(int), hipMemcpyHostToDevice, s));
-    }
+    if (int rc = mark_stale(h, STALE_FIELD)) return rc;      // new positions: neither the lists of the last build (Verlet ones included) nor what was computed over them apply
     HIP_TRY(h, hipStreamSynchronize(s));
-    h->nl_valid = false;
-    h->density_valid = false;
-    h->derived_valid = false;
     return SPH_OK;
 }
 
@@ -789,15 +827,7 @@ int sph_download(SphHandle *h, int species, int field, float *host, size_t n_flo
     if (field == SPH_F_NBR_COUNT && h->lists_predate_flag && (rc = sph_build_neighbors(h))) return rc;
     FieldLoc f;
     if ((rc = locate_field(h, field, FV_API, &f))) return rc;
-    hipStream_t s = h->stream;
-    {
-        ProfScope ps(h, K_TRANSFER);
-        launch_unsort(h, f, h->staging);            // (the device order does not change inside a step: the ids of the current generation apply)
-    }
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(host, h->staging, sizeof(float) * count, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return SPH_OK;
+    return fetch_api_order(h, [&] { launch_unsort(h, f, h->staging); }, h->staging, host, sizeof(float) * count);
 }
 
 int sph_plan_slabs(const SphConfig *cfg, int32_t *cuts, int32_t *counts)
@@ -837,6 +867,17 @@ int sph_replan_slabs(const int64_t *column_histogram, int32_t grid_x, int32_t sl
     return SPH_OK;
 }
 
+// the four device-side message buffers as the library's own (the native transport; a callback transport with host buffers): one allocation, not
+// zeroed -- a message is written before it is sent.  Whether the library owns them is whether own.comm holds memory
+static int own_message_buffers(SphHandle *h, size_t capacity_bytes)
+{
+    char *buf[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int k = 0; k < 4; ++k) h->own.comm.want(&buf[k], capacity_bytes);
+    HIP_TRY(h, h->own.comm.commit(h->stream, false));
+    for (int k = 0; k < 2; ++k) { h->dsend[k] = buf[2 * k]; h->drecv[k] = buf[2 * k + 1]; }
+    return SPH_OK;
+}
+
 int sph_rccl_unique_id(void *id128)
 {
     if (!id128) return SPH_E_INVALID;
@@ -863,22 +904,16 @@ int sph_rccl_attach(SphHandle *h, const void *id128, size_t capacity_bytes)
     ncclUniqueId id;
     memcpy(id.internal, id128, NCCL_UNIQUE_ID_BYTES);
     NCCL_TRY(h, n.CommInitRank(&h->nccl, world, id, rank));
-    if (h->own_dev_comm) { (void)hipFree(h->dsend[0]); (void)hipFree(h->dsend[1]); (void)hipFree(h->drecv[0]); (void)hipFree(h->drecv[1]); }
-    for (int k = 0; k < 2; ++k) {
-        HIP_TRY(h, hipMalloc(&h->dsend[k], capacity_bytes));
-        HIP_TRY(h, hipMalloc(&h->drecv[k], capacity_bytes));
-    }
-    h->own_dev_comm = true;
-    if (h->own_red) (void)hipFree(h->red_dev);
+    if (int rc = own_message_buffers(h, capacity_bytes)) return rc;
     h->red_cap = (int)std::max<size_t>(std::max(1024, h->c.gx + 8), slab_reduce_need(h));      // the re-balancing histogram (gx counts) and a rigid body's by-id sums go through it too
-    HIP_TRY(h, hipMalloc((void **)&h->red_dev, sizeof(double) * (size_t)h->red_cap));
-    h->own_red = true;
-    HIP_TRY(h, hipHostMalloc((void **)&h->red_host, sizeof(double) * (size_t)h->red_cap, hipHostMallocDefault));
-    if (h->gath_dev) (void)hipFree(h->gath_dev);
-    HIP_TRY(h, hipMalloc((void **)&h->gath_dev, sizeof(double) * 4 * (size_t)std::max(world, 1)));
-    HIP_TRY(h, hipMemsetAsync(h->gath_dev, 0, sizeof(double) * 4 * (size_t)std::max(world, 1), h->stream));
-    HIP_TRY(h, hipMalloc((void **)&h->cnt_dev, sizeof(int) * 4 * kCountInts));
-    HIP_TRY(h, hipHostMalloc((void **)&h->cnt_host, sizeof(int) * 4 * kCountInts, hipHostMallocDefault));
+    h->own.red.want(&h->red_dev, (size_t)h->red_cap);
+    HIP_TRY(h, h->own.red.commit(h->stream, false));
+    HIP_TRY(h, h->own.red_host.commit(&h->red_host, (size_t)h->red_cap));
+    h->own.gath.want(&h->gath_dev, 4 * (size_t)std::max(world, 1));
+    HIP_TRY(h, h->own.gath.commit(h->stream));                      // (zeroed)
+    h->own.cnt.want(&h->cnt_dev, 4 * kCountInts);
+    HIP_TRY(h, h->own.cnt.commit(h->stream, false));
+    HIP_TRY(h, h->own.cnt_host.commit(&h->cnt_host, 4 * kCountInts));
     memset(&h->comm, 0, sizeof(h->comm));
     h->comm.capacity = capacity_bytes;
     h->comm.stream_ordered = 1;
@@ -925,19 +960,15 @@ int sph_set_comm(SphHandle *h, const SphComm *comm)
     if (!comm->send_left || !comm->send_right || !comm->recv_left || !comm->recv_right || comm->capacity < 4096)
         return fail(h, SPH_E_INVALID, "SphComm buffers missing or smaller than 4 KiB");
     HIP_TRY(h, hipSetDevice(h->device));
-    if (h->own_dev_comm) { (void)hipFree(h->dsend[0]); (void)hipFree(h->dsend[1]); (void)hipFree(h->drecv[0]); (void)hipFree(h->drecv[1]); h->own_dev_comm = false; }
+    h->own.comm.release();
     h->comm = *comm;
     if (comm->on_host) {
-        for (int k = 0; k < 2; ++k) {
-            HIP_TRY(h, hipMalloc(&h->dsend[k], comm->capacity));
-            HIP_TRY(h, hipMalloc(&h->drecv[k], comm->capacity));
-        }
-        h->own_dev_comm = true;
+        if (int rc = own_message_buffers(h, comm->capacity)) return rc;
     } else {
         h->dsend[0] = comm->send_left; h->dsend[1] = comm->send_right;
         h->drecv[0] = comm->recv_left; h->drecv[1] = comm->recv_right;
     }
-    if (h->own_red) { (void)hipFree(h->red_dev); h->own_red = false; }
+    h->own.red.release();
     h->red_dev = nullptr;
     if (comm->allreduce_stream) {
         if (!comm->reduce_buf) return fail(h, SPH_E_INVALID, "SphComm.allreduce_stream needs reduce_buf");
@@ -945,7 +976,7 @@ int sph_set_comm(SphHandle *h, const SphComm *comm)
         if (have < slab_reduce_need(h))
             return fail(h, SPH_E_INVALID, "SphComm.reduce_buf holds %zu doubles, this handle (rigid body of %d samples) needs %zu: set reduce_capacity", have, h->Nr, slab_reduce_need(h));
         h->red_cap = (int)std::min<size_t>(have, 0x7fffffff);
-        if (comm->on_host) { HIP_TRY(h, hipMalloc((void **)&h->red_dev, sizeof(double) * have)); h->own_red = true; }
+        if (comm->on_host) { h->own.red.want(&h->red_dev, have); HIP_TRY(h, h->own.red.commit(h->stream, false)); }
         else h->red_dev = comm->reduce_buf;
     } else if (h->rigid) {
         return fail(h, SPH_E_INVALID, "a rigid body on a slab handle needs a transport with allreduce_stream");
@@ -1111,7 +1142,7 @@ static int wcsph_replay_pairs(SphHandle *h, int nsteps, int *k)
         HIP_TRY(h, hipGraphLaunch(h->wcsph_graph[key], h->stream));
         h->graph_launches += 1;
         h->simulate_cnt += 2;
-        h->nl_valid = false; h->density_valid = false; h->derived_valid = false;
+        mark_stale(h, STALE_STEP_RAN);
         *k += 2;
     }
     return SPH_OK;
@@ -1261,7 +1292,7 @@ static int set_param(SphHandle *h, int which, double value)
         HIP_TRY(h, hipMemcpyAsync(&h->ds->p_dens_thr, &h->ds_host->p_dens_thr, sizeof(DevScalars) - offsetof(DevScalars, p_dens_thr), hipMemcpyHostToDevice, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
     }
-    drop_wcsph_graphs(h);                                            // (they carry the old constants as launch arguments)
+    mark_stale(h, STALE_LAUNCH_ARGS);                                // (the captured step pairs carry the old constants as launch arguments)
     return SPH_OK;
 }
 
@@ -1294,7 +1325,7 @@ static int set_step_param(SphHandle *h, int which, double value)
         }
         h->step_adaptive = value != 0.0;
     }
-    drop_wcsph_graphs(h);
+    mark_stale(h, STALE_LAUNCH_ARGS);
     return SPH_OK;
 }
 
@@ -1403,23 +1434,25 @@ int sph_diag_record(SphHandle *h, int every, int rows)
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (every > 0) {
         if (int rc = diag_scratch(h)) return rc;
+        DevMem ring_mem;                   // (neither is zeroed: the counters are written whole, a row is written before it is read)
         double *ring = nullptr;
-        HIP_TRY(h, hipMalloc((void **)&ring, sizeof(double) * kDiagSlots * (size_t)rows));
-        if (!h->diag_ctl && hipMalloc((void **)&h->diag_ctl, sizeof(DiagCtl)) != hipSuccess) {
-            (void)hipFree(ring); h->diag_ctl = nullptr;
-            return fail(h, SPH_E_HIP, "sph_diag_record: out of device memory");
+        ring_mem.want(&ring, kDiagSlots * (size_t)rows);
+        HIP_TRY(h, ring_mem.commit(h->stream, false));
+        if (!h->own.diag_ctl) {
+            h->own.diag_ctl.want(&h->diag_ctl, 1);
+            if (h->own.diag_ctl.commit(h->stream, false) != hipSuccess) return fail(h, SPH_E_HIP, "sph_diag_record: out of device memory");
         }
         const DiagCtl ctl{0, 0, h->simulate_cnt, every, rows, 0};
         hipError_t e = hipMemcpyAsync(h->diag_ctl, &ctl, sizeof(ctl), hipMemcpyHostToDevice, h->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) { (void)hipFree(ring); return fail(h, SPH_E_HIP, "sph_diag_record: %s", hipGetErrorString(e)); }
-        if (h->diag_ring) (void)hipFree(h->diag_ring);
+        if (e != hipSuccess) return fail(h, SPH_E_HIP, "sph_diag_record: %s", hipGetErrorString(e));
+        h->own.diag_ring = std::move(ring_mem);
         h->diag_ring = ring;
         h->diag_rows = rows;
         h->diag_consumed = 0;
     }
     h->diag_every = every;
-    drop_wcsph_graphs(h);
+    mark_stale(h, STALE_LAUNCH_ARGS);
     return SPH_OK;
 }
 
@@ -1533,7 +1566,7 @@ int sph_tune_time(SphHandle *h, int which, unsigned lds_bytes, int reps, double 
     (void)hipEventDestroy(a); (void)hipEventDestroy(b);
     h->sweep_lds = saved;
     h->tune_all = false;
-    if (which == 3) { h->density_valid = false; h->derived_valid = false; }
+    if (which == 3) mark_stale(h, STALE_DENSITY);
     *avg_us = (double)ms * 1000.0 / reps;
     return SPH_OK;
 }
@@ -1545,9 +1578,10 @@ int sph_selftest_math(int device, int op, const float *a, const float *b, float 
     if (device < 0 || device >= ndev || !a || !b || !out) return fail(nullptr, SPH_E_INVALID, "bad argument");
     if (hipSetDevice(device) != hipSuccess) return fail(nullptr, SPH_E_HIP, "hipSetDevice failed");
     float *da = nullptr, *db = nullptr, *dout = nullptr;
+    DevMem mem;                            // (the self-tests' scratch: not zeroed, on the null stream, gone with the call)
+    mem.want(&da, n); mem.want(&db, n); mem.want(&dout, n);
     int rc = SPH_OK;
-    if (hipMalloc((void **)&da, n * 4) != hipSuccess || hipMalloc((void **)&db, n * 4) != hipSuccess || hipMalloc((void **)&dout, n * 4) != hipSuccess)
-        rc = fail(nullptr, SPH_E_HIP, "hipMalloc failed");
+    if (mem.commit(nullptr, false) != hipSuccess) rc = fail(nullptr, SPH_E_HIP, "hipMalloc failed");
     if (!rc) {
         (void)hipMemcpy(da, a, n * 4, hipMemcpyHostToDevice);
         (void)hipMemcpy(db, b, n * 4, hipMemcpyHostToDevice);
@@ -1564,7 +1598,6 @@ int sph_selftest_math(int device, int op, const float *a, const float *b, float 
         if (hipDeviceSynchronize() != hipSuccess) rc = fail(nullptr, SPH_E_HIP, "selftest kernel failed");
         else (void)hipMemcpy(out, dout, n * 4, hipMemcpyDeviceToHost);
     }
-    (void)hipFree(da); (void)hipFree(db); (void)hipFree(dout);
     return rc;
 }
 
@@ -1575,15 +1608,16 @@ int sph_selftest_wave(int device, int op, const double *in, double *out, size_t 
     if (device < 0 || device >= ndev || !in || !out || n == 0 || n % 256 != 0 || op < 0 || op > 4) return fail(nullptr, SPH_E_INVALID, "bad argument (n must be a multiple of 256)");
     if (hipSetDevice(device) != hipSuccess) return fail(nullptr, SPH_E_HIP, "hipSetDevice failed");
     double *din = nullptr, *dout = nullptr;
+    DevMem mem;
+    mem.want(&din, n); mem.want(&dout, n);
     int rc = SPH_OK;
-    if (hipMalloc((void **)&din, n * 8) != hipSuccess || hipMalloc((void **)&dout, n * 8) != hipSuccess) rc = fail(nullptr, SPH_E_HIP, "hipMalloc failed");
+    if (mem.commit(nullptr, false) != hipSuccess) rc = fail(nullptr, SPH_E_HIP, "hipMalloc failed");
     if (!rc) {
         (void)hipMemcpy(din, in, n * 8, hipMemcpyHostToDevice);
         hipLaunchKernelGGL(k_selftest_wave, dim3((unsigned)(n / 256)), dim3(256), 0, 0, op, din, dout);
         if (hipDeviceSynchronize() != hipSuccess) rc = fail(nullptr, SPH_E_HIP, "selftest kernel failed");
         else (void)hipMemcpy(out, dout, n * 8, hipMemcpyDeviceToHost);
     }
-    (void)hipFree(din); (void)hipFree(dout);
     return rc;
 }
 
@@ -1609,11 +1643,11 @@ int sph_selftest_stage(SphHandle *h, int layout, int check, int empty_idle, int 
     if (hipSetDevice(device) != hipSuccess) return fail(h, SPH_E_HIP, "hipSetDevice failed");
     const size_t out_bytes = (size_t)6 * kStageCapMax * sizeof(float);
     uint2 *d_runs = nullptr; int *d_cnt = nullptr; float4 *d_A = nullptr, *d_B = nullptr; float *d_S = nullptr, *d_out = nullptr; unsigned char *d_ch = nullptr;
+    DevMem mem;
+    mem.want(&d_runs, plan.size()); mem.want(&d_cnt, 2); mem.want(&d_A, n_src); mem.want(&d_B, n_src); mem.want(&d_S, n_src); mem.want(&d_ch, n_src);
+    mem.want(&d_out, out_bytes / sizeof(float));
     int rc = SPH_OK;
-    if (hipMalloc((void **)&d_runs, plan.size() * sizeof(uint2)) != hipSuccess || hipMalloc((void **)&d_cnt, 2 * sizeof(int)) != hipSuccess ||
-        hipMalloc((void **)&d_A, n_src * 16) != hipSuccess || hipMalloc((void **)&d_B, n_src * 16) != hipSuccess || hipMalloc((void **)&d_S, n_src * 4) != hipSuccess ||
-        hipMalloc((void **)&d_ch, n_src) != hipSuccess || hipMalloc((void **)&d_out, out_bytes) != hipSuccess)
-        rc = fail(h, SPH_E_HIP, "hipMalloc failed");
+    if (mem.commit(nullptr, false) != hipSuccess) rc = fail(h, SPH_E_HIP, "hipMalloc failed");
     if (!rc) {
         const int head[2] = {cnt, -1};                         // [1]: the verdict
         (void)hipMemcpy(d_runs, plan.data(), plan.size() * sizeof(uint2), hipMemcpyHostToDevice);
@@ -1638,7 +1672,6 @@ int sph_selftest_stage(SphHandle *h, int layout, int check, int empty_idle, int 
             (void)hipMemcpy(verdict, d_cnt + 1, sizeof(int), hipMemcpyDeviceToHost);
         }
     }
-    (void)hipFree(d_runs); (void)hipFree(d_cnt); (void)hipFree(d_A); (void)hipFree(d_B); (void)hipFree(d_S); (void)hipFree(d_ch); (void)hipFree(d_out);
     return rc;
 }
 
@@ -1673,12 +1706,11 @@ int sph_selftest_walk(SphHandle *h, int walk, int src, int rigid, const uint32_t
     if (hipSetDevice(device) != hipSuccess) return fail(h, SPH_E_HIP, "hipSetDevice failed");
     uint2 *d_runs = nullptr; int *d_head = nullptr, *d_cnt = nullptr; float4 *d_A = nullptr, *d_B = nullptr, *d_C = nullptr, *d_RP = nullptr; float *d_S = nullptr;
     uint32_t *d_nl = nullptr, *d_out = nullptr;
+    DevMem mem;
+    mem.want(&d_runs, plan.size()); mem.want(&d_head, 1); mem.want(&d_cnt, NP); mem.want(&d_A, n_src); mem.want(&d_B, n_src); mem.want(&d_C, n_src); mem.want(&d_S, n_src);
+    mem.want(&d_RP, n_rig); mem.want(&d_nl, nl.size()); mem.want(&d_out, (size_t)nthreads * 4);
     int rc = SPH_OK;
-    if (hipMalloc((void **)&d_runs, plan.size() * sizeof(uint2)) != hipSuccess || hipMalloc((void **)&d_head, sizeof(int)) != hipSuccess ||
-        hipMalloc((void **)&d_cnt, NP * sizeof(int)) != hipSuccess || hipMalloc((void **)&d_A, n_src * 16) != hipSuccess || hipMalloc((void **)&d_B, n_src * 16) != hipSuccess ||
-        hipMalloc((void **)&d_C, n_src * 16) != hipSuccess || hipMalloc((void **)&d_S, n_src * 4) != hipSuccess || hipMalloc((void **)&d_RP, n_rig * 16) != hipSuccess ||
-        hipMalloc((void **)&d_nl, nl.size() * 4) != hipSuccess || hipMalloc((void **)&d_out, (size_t)nthreads * 16) != hipSuccess)
-        rc = fail(h, SPH_E_HIP, "hipMalloc failed");
+    if (mem.commit(nullptr, false) != hipSuccess) rc = fail(h, SPH_E_HIP, "hipMalloc failed");
     if (!rc) {
         (void)hipMemcpy(d_runs, plan.data(), plan.size() * sizeof(uint2), hipMemcpyHostToDevice);
         (void)hipMemcpy(d_head, &head, sizeof(int), hipMemcpyHostToDevice);
@@ -1706,8 +1738,6 @@ int sph_selftest_walk(SphHandle *h, int walk, int src, int rigid, const uint32_t
         if (hipDeviceSynchronize() != hipSuccess) rc = fail(h, SPH_E_HIP, "selftest kernel failed");
         else (void)hipMemcpy(out, d_out, (size_t)nthreads * 16, hipMemcpyDeviceToHost);
     }
-    (void)hipFree(d_runs); (void)hipFree(d_head); (void)hipFree(d_cnt); (void)hipFree(d_A); (void)hipFree(d_B); (void)hipFree(d_C); (void)hipFree(d_S);
-    (void)hipFree(d_RP); (void)hipFree(d_nl); (void)hipFree(d_out);
     return rc;
 }
 
@@ -1735,11 +1765,11 @@ int sph_selftest_walk_bits(SphHandle *h, int write, const uint32_t *lists, const
     }
     if (hipSetDevice(device) != hipSuccess) return fail(nullptr, SPH_E_HIP, "hipSetDevice failed");
     float4 *d_A = nullptr; uint32_t *d_nl = nullptr, *d_bits = nullptr, *d_seen = nullptr; int *d_cnt = nullptr, *d_verdict = nullptr, *d_calls = nullptr;
+    DevMem mem;
+    mem.want(&d_A, NP); mem.want(&d_nl, nl.size()); mem.want(&d_bits, bits.size()); mem.want(&d_seen, (size_t)NP * ROWS); mem.want(&d_cnt, NP);
+    mem.want(&d_verdict, (size_t)NP * ROWS); mem.want(&d_calls, NP);
     int rc = SPH_OK;
-    if (hipMalloc((void **)&d_A, NP * 16) != hipSuccess || hipMalloc((void **)&d_nl, nl.size() * 4) != hipSuccess || hipMalloc((void **)&d_bits, bits.size() * 4) != hipSuccess ||
-        hipMalloc((void **)&d_seen, (size_t)NP * ROWS * 4) != hipSuccess || hipMalloc((void **)&d_cnt, NP * 4) != hipSuccess ||
-        hipMalloc((void **)&d_verdict, (size_t)NP * ROWS * 4) != hipSuccess || hipMalloc((void **)&d_calls, NP * 4) != hipSuccess)
-        rc = fail(nullptr, SPH_E_HIP, "hipMalloc failed");
+    if (mem.commit(nullptr, false) != hipSuccess) rc = fail(nullptr, SPH_E_HIP, "hipMalloc failed");
     if (!rc) {
         (void)hipMemcpy(d_A, A.data(), NP * 16, hipMemcpyHostToDevice);
         (void)hipMemcpy(d_nl, nl.data(), nl.size() * 4, hipMemcpyHostToDevice);
@@ -1757,7 +1787,6 @@ int sph_selftest_walk_bits(SphHandle *h, int write, const uint32_t *lists, const
                 for (int g = 0; g < GROUPS; ++g) words[(size_t)i * GROUPS + g] = bits[(nl_index(i, 0, PITCH) >> 2) + (size_t)g * 64];
         }
     }
-    (void)hipFree(d_A); (void)hipFree(d_nl); (void)hipFree(d_bits); (void)hipFree(d_seen); (void)hipFree(d_cnt); (void)hipFree(d_verdict); (void)hipFree(d_calls);
     return rc;
 }
 

@@ -325,6 +325,11 @@ class Disturber:
             "refused_wrong_length": lambda: self._refused(self._wrong_length),
             "refused_nan": self._nan_params, "refused_other_step": self._other_step,
             "refused_slab_overlap": lambda: self._refused(lambda: sim.set_slab_overlap(True)),
+            # the between-step features that read, or write what is there already: through the handle's validity flags (derived runs compute_density),
+            # its API-order read-back, and the drop of the captured wcsph step pairs (a gravity vector is a launch-time fact even when it is the same)
+            "diagnostics": sim.diagnostics, "derived": lambda: [sim.derived(q) for q in ("vorticity", "cover")],
+            "wall_neighbor_counts": sim.wall_neighbor_counts, "geometry": sim.geometry,
+            "set_gravity": lambda: sim.set_gravity(sim.gravity_vec()),
         }
         if c.solver != "pbf":
             calls["set_params"] = self._set_params
